@@ -9,6 +9,11 @@ adjoint -> P^T chain -> Adam update.  Metric = prod(cshape) * steps / wall
 reference solution, discrete rhs, zero initial state; poisson.py:21-24,71-86,264-266).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4a|5|1|2|3|3b|4b|5b] [--N 512] [--ndim 3]
+                  [--dump-outputs DIR]
+
+--dump-outputs DIR (config 4a on one GPU; bench_outputs/ is git-ignored): after the timed steps, what the timed
+optimize_grad call returned after its last step is written as DIR/<name>.npy (dump_outputs below), so that two builds
+can be compared output for output.
 
 N > 1: one rank per GPU over RCCL, weak scaling (every rank owns a 512^3 slab of the (N*512, 512, 512) grid;
 config 5: a (128, 32, 256, 256) slab of the tracer workload's (128, N*32, 256, 256) grid -- at N = 8 the
@@ -54,7 +59,14 @@ def parse_args():
     p.add_argument("--spinup_ms", type=float, default=80.0, help="untimed read-modify-write spin-up before the warm-up steps")
     p.add_argument("--no_other_configs", action="store_true",
                    help="skip the short runs of configs 3b, 5 (one rank) and 4b after the timed region")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed path returned after its last timed step as DIR/<name>.npy (config 4a, one GPU)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.config != "4a" or args.gpus != 1):
+        p.error("--dump-outputs needs --config 4a and --gpus 1")
+    return args
 
 
 def algorithmic_bytes_per_update(ndim, nlvl, wordsize):
@@ -329,6 +341,36 @@ class ApiPoissonRun:
         return float(np.array(self._loss))
 
 
+DUMP_SAMPLE = 1 << 18  # entries stored of a larger multigrid level (a seeded sample)
+DUMP_LIMIT = 64 << 20  # bytes of all dumped arrays together
+
+
+def dump_outputs(path, run):
+    """--dump-outputs: what the timed `optimize_grad` call returned after its last step -- the unknowns of every multigrid
+    level (`x_l<k>`) and Adam's two moments (`m_l<k>`, `v_l<k>`) in the run's dtype -- and the loss the driver's callback
+    received for that step (`loss`, float64), as `path`/<name>.npy.  A level of more than DUMP_SAMPLE entries is stored
+    as a fixed sample: sorted flat indices drawn with seed k (the same positions in every run of that shape), stored
+    beside it as `sample_index_l<k>` (float64, exact).  The inputs of the run are the same from run to run (zero start,
+    the example's deterministic reference solution), so two builds can be compared file by file.  -> {name: shape}."""
+    files = {"loss": np.array([run.last_loss()], dtype=np.float64)}
+    for lvl, (x, m, v) in enumerate(zip(run.w, run.mw, run.vw)):
+        take = lambda t: t.reshape(-1)
+        if x.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(lvl).choice(x.numel(), DUMP_SAMPLE, replace=False))
+            files["sample_index_l{}".format(lvl)] = idx.astype(np.float64)
+            ti = torch.as_tensor(idx, device=x.device)
+            take = lambda t, ti=ti: t.reshape(-1)[ti]
+        for name, t in (("x", x), ("m", m), ("v", v)):
+            files["{}_l{}".format(name, lvl)] = take(t.detach()).cpu().numpy()
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: {} bytes exceed the {} byte limit".format(total, DUMP_LIMIT)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
+
+
 def run_poisson(args, rank, world, dev, comm, barrier):
     from odil_amd.slab import SlabPoissonAdam
 
@@ -362,8 +404,11 @@ def run_poisson(args, rank, world, dev, comm, barrier):
         step()
         if world == 1:  # the run starts from the zero state: its first epochs ARE the epochs of the value-level fixture
             oracle = oracle_values_check(run, k + 1, oracle, (ndim, N, args.dtype))
+    dumped = None
     if world == 1:
         elapsed = run.timed(args.steps, timers, barrier)
+        if args.dump_outputs is not None:  # (after the timed region, before any further epoch)
+            dumped = dump_outputs(args.dump_outputs, run)
     else:
         barrier()
         t0 = time.perf_counter()
@@ -419,7 +464,7 @@ def run_poisson(args, rank, world, dev, comm, barrier):
             if (ndim, N) == (3, 512) else "{}D Poisson {}^{} multigrid Adam epoch".format(ndim, N, ndim)),
         config=dict(cells_per_gpu=run.local_cells, levels=run.nlvl, optimizer="adam lr=0.005"),
         roofline=roofline(kernel, model, moved, ms, traffic, source), abytes=abytes, dtype=args.dtype,
-        exchanges_per_epoch=2 if world > 1 else 0, oracle=oracle)
+        exchanges_per_epoch=2 if world > 1 else 0, oracle=oracle, dumped=dumped)
 
 
 def hat_reference_host(N):
@@ -937,6 +982,8 @@ def main():
         if others is not None:
             out["other_configs"] = others
         out["spinup_ms"] = args.spinup_ms
+        if res.get("dumped") is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": res["dumped"]}
         print(json.dumps(out))
         failed = (parity is not None and not parity["ok"]) or (oracle is not None and oracle.get("ok") is False)
     else:

@@ -62,3 +62,52 @@ def test_roofline_object_reports_physical_and_model_fractions():
     assert r["traffic"] is None and abs(r["achieved"] - 4000.0) < 1e-9 and "compulsory" in r["traffic_source"]
     per_update, S = bench.algorithmic_bytes_per_update(3, 9, 8)
     assert abs(per_update - 131.4285707) < 1e-4 and abs(S - 8 / 7) < 1e-7
+
+
+def test_dump_outputs_writes_every_level_and_samples_the_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: x, m, v of every multigrid level and the loss as float .npy files; a level larger than
+    DUMP_SAMPLE is a seeded sample (the same positions in every run), stored with its flat indices."""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    rng = np.random.default_rng(1)
+    shapes = [(8, 8, 8), (4, 4, 4), (2, 2, 2)]
+    lv = lambda: [torch.as_tensor(rng.standard_normal(s)) for s in shapes]
+
+    class Run:
+        w, mw, vw = lv(), lv(), lv()
+
+        def last_loss(self):
+            return 0.25
+
+    got = [bench.dump_outputs(str(tmp_path / d), Run()) for d in ("a", "b")]
+    assert got[0] == got[1]
+    names = {"loss", "sample_index_l0"} | {"{}_l{}".format(a, k) for a in "xmv" for k in range(3)}
+    assert set(got[0]) == names and sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    ld = lambda d, n: np.load(str(tmp_path / d / (n + ".npy")))
+    assert ld("a", "loss").dtype == np.float64 and float(ld("a", "loss")[0]) == 0.25
+    idx = ld("a", "sample_index_l0")
+    assert idx.dtype == np.float64 and idx.shape == (64,) and len(set(idx)) == 64 and np.array_equal(idx, np.sort(idx))
+    for a, arrays in (("x", Run.w), ("m", Run.mw), ("v", Run.vw)):
+        assert np.array_equal(ld("a", a + "_l0"), arrays[0].numpy().reshape(-1)[idx.astype(np.int64)])
+        for k in (1, 2):
+            assert ld("a", "{}_l{}".format(a, k)).dtype == np.float64
+            assert np.array_equal(ld("a", "{}_l{}".format(a, k)), arrays[k].numpy().reshape(-1))
+    for n in names:
+        assert np.array_equal(ld("a", n), ld("b", n))
+
+
+def test_dump_outputs_of_the_headline_size_fit_the_limit():
+    """512^3 f64 with 9 levels: x, m, v of every level, the sampled levels' indices and the loss stay under 64 MB."""
+    sizes = [(512 >> k) ** 3 for k in range(9)]
+    total = 8 + sum(3 * 8 * min(n, bench.DUMP_SAMPLE) + (8 * bench.DUMP_SAMPLE if n > bench.DUMP_SAMPLE else 0) for n in sizes)
+    assert total <= bench.DUMP_LIMIT == 64 << 20
+
+
+def test_steps_below_one_and_dumps_outside_the_headline_run_are_refused(monkeypatch):
+    for argv in (["--steps", "0"], ["--dump-outputs", "d", "--config", "5"], ["--dump-outputs", "d", "--gpus", "2"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.parse_args()
+        assert e.value.code == 2

@@ -1,7 +1,8 @@
 """On-disk artefacts either side of the hot path: `train.csv` through History
 and raw + XDMF2 field dumps, in the reference's formats (reference src/odil/history.py,
-src/odil/io.py, tests/test_io.py).  When the reference checkout is present (build container only)
-the files are also read back with the reference's own reader."""
+src/odil/io.py, tests/test_io.py).  The files the reference's own writers produce for the same inputs are stored in
+tests/golden/reference_io.npz (tests/golden/make_golden_reference_io.py): ours must be byte-identical to them, and ours
+must read theirs."""
 
 import os
 import sys
@@ -34,22 +35,40 @@ def test_raw_xmf_round_trip(tmp_path):
     assert os.path.exists(str(tmp_path / "sub" / "n.raw"))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/odil"), reason="reference checkout not present")
-def test_files_are_readable_by_the_reference_reader(tmp_path):
-    import importlib.util
+def io_field():
+    """The field of the reference-written files in tests/golden/reference_io.npz."""
+    return np.random.default_rng(0).standard_normal((5, 4, 3)).astype(np.float32)
 
-    spec = importlib.util.spec_from_file_location("ref_io", "/root/reference/src/odil/io.py")
-    ref_io = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref_io)
-    src = np.random.default_rng(0).standard_normal((5, 4, 3)).astype(np.float32)
+
+def history_rows(h):
+    """Appends and writes the rows of the reference-written train.csv in tests/golden/reference_io.npz through History `h`."""
+    for epoch in range(4):
+        h.append("epoch", epoch * 5)
+        h.append("frame", epoch // 2)
+        h.append("norm_fu", np.array(0.3 / (epoch + 1)))
+        h.append("loss", np.float64(0.09) / (epoch + 1) ** 2)
+        h.append("walltime", float(np.round(0.0123 * epoch, 3)))
+        if epoch:
+            h.append("error_u", np.float32(1.5) / epoch)
+        h.write()
+    h.close()
+
+
+def test_files_are_readable_by_the_reference_reader(tmp_path, golden):
+    """Ours writes the bytes the reference's writer does (what its reader reads), and reads the reference's files."""
+    fx = golden("reference_io")
+    src = io_field()
     xmf = str(tmp_path / "a.xmf")
     odil.write_raw_with_xmf(src, xmf, spacing=(0.1, 0.2, 0.3), name="vel", cell=False)
-    u, meta = ref_io.read_raw_with_xmf(xmf)
+    assert open(xmf, "rb").read() == fx["vel_xmf"].tobytes()
+    assert open(str(tmp_path / "a.raw"), "rb").read() == fx["vel_raw"].tobytes() == src.tobytes()
+    u, meta = odil.read_raw_with_xmf(xmf)
     assert np.array_equal(u, src) and meta["name"] == "vel" and not meta["cell"]
     np.testing.assert_allclose(meta["spacing"], (0.1, 0.2, 0.3))
     # and the other way round
     xmf2 = str(tmp_path / "b.xmf")
-    ref_io.write_raw_with_xmf(src.astype(np.float64), xmf2, spacing=(1, 2, 3), name="p")
+    open(xmf2, "wb").write(fx["p_xmf"].tobytes())
+    open(str(tmp_path / "b.raw"), "wb").write(fx["p_raw"].tobytes())
     u2, meta2 = odil.read_raw_with_xmf(xmf2)
     assert np.array_equal(u2, src.astype(np.float64)) and meta2["spacing"] == (1.0, 2.0, 3.0) and meta2["cell"]
 
@@ -84,27 +103,10 @@ def test_history_csv_format(tmp_path):
         h.write()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/odil"), reason="reference checkout not present")
-def test_history_matches_reference_bytes(tmp_path):
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("ref_history", "/root/reference/src/odil/history.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    paths = [str(tmp_path / "a.csv"), str(tmp_path / "b.csv")]
-    for cls, path in zip([ref.History, odil.History], paths):
-        h = cls(csvpath=path, warmup=1)
-        for epoch in range(4):
-            h.append("epoch", epoch * 5)
-            h.append("frame", epoch // 2)
-            h.append("norm_fu", np.array(0.3 / (epoch + 1)))
-            h.append("loss", np.float64(0.09) / (epoch + 1) ** 2)
-            h.append("walltime", float(np.round(0.0123 * epoch, 3)))
-            if epoch:
-                h.append("error_u", np.float32(1.5) / epoch)
-            h.write()
-        h.close()
-    assert open(paths[0], "rb").read() == open(paths[1], "rb").read()
+def test_history_matches_reference_bytes(tmp_path, golden):
+    path = str(tmp_path / "train.csv")
+    history_rows(odil.History(csvpath=path, warmup=1))
+    assert open(path, "rb").read() == golden("reference_io")["history_csv"].tobytes()
 
 
 @pytest.mark.parametrize("axis,world", [(0, 2), (1, 3), (2, 2)])

@@ -1,13 +1,15 @@
-"""north_star: "user residual callbacks drop in unchanged" -- SHOWN, in the build container (needs /root/reference; skipped
-on the GPU box, nothing of the reference is shipped): the reference's own example files are loaded by path with `import
-odil` resolved to THIS package, their operator functions (unchanged source) are handed to `odil_amd.Problem`, and
+"""north_star: "user residual callbacks drop in unchanged".  The reference's own example files, loaded by path with
+`import odil` resolved to THIS package, had their operator functions (unchanged source) handed to `odil_amd.Problem`
+and run ONCE on symbolic values through the tracer (`stencil_jit.trace_outputs`) -- the generated-kernel route, not the
+autograd fallback.  What they traced to is stored in tests/golden/reference_operators_traced.npz
+(tests/golden/make_golden_dropin.py, which needs a reference checkout and runs the reference's files through
+`odil_alias` and `traced_sources_and_values` below): per operator the output names, the traced outputs evaluated by
+the NumPy DAG interpreter (tests/dag_eval.py) on seeded random states, and the SHA-1 of every generated kernel source.
 
-  * run ONCE on symbolic values through the tracer (`stencil_jit.trace_outputs`) -- i.e. they take the generated-kernel
-    route, not the autograd fallback -- and the generated HIP source cross-compiles for gfx950;
-  * the traced outputs, evaluated by the NumPy DAG interpreter (tests/dag_eval.py) on random states, equal those of the
-    restated operator under `examples/` (the one the GPU parity tests hold to the reference-generated fixtures) to 1e-13;
-    where the two record their operations in the same order the generated source is identical, which is asserted too
-    for the operators where it holds today.
+The test traces the restated operator under `examples/` (the one the GPU parity tests hold to the reference-generated
+fixtures) on the same states: its outputs equal the reference operator's to 1e-13, and where the two record their
+operations in the same order the generated source is identical, which is asserted too for the operators where it
+holds today.
 
 Reference operators: examples/poisson/poisson.py:89-123, heat/heat.py:36-137, velocity_from_tracer/veltracer.py:34-130,
 wave/wave.py:29-75, heat_tmax/heat_tmax.py:29-75, infer_constant/infer_constant.py:44-74, basic/fields.py:16-40."""
@@ -27,10 +29,7 @@ from dag_eval import DagEval
 import odil_amd
 from odil_amd import runtime, stencil_jit
 
-REF = "/root/reference/examples"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists in the build container only")
-
-# (name, reference file, operator function in it, restated example module, its argv)
+# (name, reference file (under the reference's examples/), operator function in it, restated example module, its argv)
 CASES = [
     ("poisson", "poisson/poisson.py", "operator", "poisson", ["--ndim", "2", "--N", "16"]),
     ("heat", "heat/heat.py", "operator_odil", "heat", ["--Nt", "8", "--Nx", "16", "--infer_k", "1", "--imposed", "stripe",
@@ -44,11 +43,10 @@ CASES = [
 SAME_SOURCE = {"fields"}  # same recording order as the restated operator: byte-identical generated source
 
 
-@pytest.fixture()
-def as_odil(monkeypatch):
+def odil_alias(monkeypatch):
     """`import odil` (and `odil.runtime`, `odil.core`, ...) resolve to odil_amd on a CPU `mod`; the plotting modules
     (out of scope) are empty stand-ins, and `odil.runtime.tf` only knows the `@tf.function()`
-    decorator that reference files apply to plotting helpers at import time."""
+    decorator that reference files apply to plotting helpers at import time.  Returns the log file to restore."""
     import matplotlib
 
     matplotlib.use("Agg")
@@ -77,7 +75,13 @@ def as_odil(monkeypatch):
     for sub in ("poisson", "heat", "velocity_from_tracer", "wave", "heat_tmax", "infer_constant", "basic"):
         monkeypatch.syspath_prepend(os.path.join(ROOT, "examples", sub))
     monkeypatch.setenv("ODIL_FUSE", "0")
-    yield shim
+    return saved
+
+
+@pytest.fixture()
+def as_odil(monkeypatch):
+    saved = odil_alias(monkeypatch)
+    yield
     odil_amd.util.g_log_file = saved
 
 
@@ -106,17 +110,14 @@ def traced_sources_and_values(problem, state, arrays, nets):
     return sources, names, values
 
 
-@pytest.mark.parametrize("name,ref_file,opname,mine_name,argv", CASES, ids=[c[0] for c in CASES])
-def test_reference_operator_source_runs_on_this_api_and_traces_like_the_restated_one(as_odil, name, ref_file, opname, mine_name, argv):
+def restated_problem(argv_module, argv):
+    """The restated example's problem and a seeded random state: regular arrays of the grid fields (the DAG reads them),
+    parameter vectors, network weights -> (problem, state, arrays, nets)."""
     from odil_amd.core import Array, Field, MultigridField, NeuralNet
 
-    mine = importlib.import_module(mine_name)
+    mine = importlib.import_module(argv_module)
     problem, state = mine.make_problem(mine.parse_args(argv))
     domain = problem.domain
-    ref_operator = getattr(load_by_path(os.path.join(REF, ref_file), "reference_example_" + name), opname)
-    assert ref_operator.__code__.co_filename.startswith("/root/reference/")
-    ref_problem = odil_amd.Problem(ref_operator, domain, problem.extra, tracers=dict(problem.tracers or {}))
-    # a random state: regular arrays of the grid fields (the DAG reads them), parameter vectors, network weights
     rng = np.random.default_rng(5)
     arrays, nets = dict(), dict()
     for key, f in state.fields.items():
@@ -127,15 +128,30 @@ def test_reference_operator_source_runs_on_this_api_and_traces_like_the_restated
         elif isinstance(f, NeuralNet):
             nets[key] = ([rng.uniform(-1, 1, tuple(w.shape)) for w in f.weights], [rng.uniform(-0.5, 0.5, tuple(b.shape)) for b in f.biases])
     if problem.tracers is not None and "epoch" in (problem.tracers or {}):
-        problem.tracers["epoch"] = ref_problem.tracers["epoch"] = 7
+        problem.tracers["epoch"] = 7
+    return problem, state, arrays, nets
+
+
+def sha1(text):
+    return hashlib.sha1(text.encode()).hexdigest()
+
+
+@pytest.mark.parametrize("name,ref_file,opname,mine_name,argv", CASES, ids=[c[0] for c in CASES])
+def test_reference_operator_source_runs_on_this_api_and_traces_like_the_restated_one(as_odil, golden, name, ref_file, opname, mine_name, argv):
+    fx = golden("reference_operators_traced")
+    assert str(fx[name + "/ref_file"]) == ref_file and str(fx[name + "/opname"]) == opname
+    names_ref = [str(n) for n in fx[name + "/names"]]
+    val_ref = [fx["{}/value{}".format(name, k)] for k in range(len(names_ref))]
+    sha_ref = [str(h) for h in fx[name + "/source_sha1"]]
+    problem, state, arrays, nets = restated_problem(mine_name, argv)
     src_mine, names_mine, val_mine = traced_sources_and_values(problem, state, arrays, nets)
-    src_ref, names_ref, val_ref = traced_sources_and_values(ref_problem, state, arrays, nets)
     assert len(val_ref) == len(val_mine) and len(val_ref) >= 1
-    assert [n or "" for n in names_ref] == [n or "" for n in names_mine]
+    assert names_ref == [n or "" for n in names_mine]
     for k, (a, b) in enumerate(zip(val_ref, val_mine)):
         assert a.shape == b.shape, (name, k)
         scale = max(np.abs(b).max(), 1e-300)
         assert np.abs(a - b).max() <= 1e-13 * scale, (name, k, np.abs(a - b).max() / scale)
-    same = [hashlib.sha1(a.encode()).hexdigest() == hashlib.sha1(b.encode()).hexdigest() for a, b in zip(src_ref, src_mine)]
+    assert len(sha_ref) == len(src_mine)
+    same = [a == sha1(b) for a, b in zip(sha_ref, src_mine)]
     if name in SAME_SOURCE:
         assert all(same), name
