@@ -522,6 +522,41 @@ int odil_dense_block_gram_f64(const double* d, int64_t n, int p, int64_t ld, dou
 int odil_dense_block_gram_f32(const float* d, int64_t n, int p, int64_t ld, float* out, float* workspace,
                               void* stream);
 
+/* ---- Newton: multigrid for the normal equations of several grid fields (gmg.NormalGMG) ------------------------------
+ * The reference solves any Newton system with --linsolver multigrid by AMG on the normal equations (linsolver.py:61-72).
+ * A level: nf <= 8 fields concatenated in one vector; desc = {nf, off[0..nf], n[f][0..2] (canonical 3-D shape of every
+ * field, leading axes 1), ebeg[0..nf]}; table: DEVICE int64, 8 words per entry (a, b, o0, o1, o2, start, 0, 0), sorted by
+ * a, the entries of field a in [ebeg[a], ebeg[a+1]); coef: the coefficient arrays, entry e over a's grid at coef + start:
+ *     (A x)_a[q] = sum_e C_e[q] x_b[q + o]          (terms outside b's grid are zero).
+ * apply: mode 0 y = A x, 1 y = b - A x, 2 y = x + omega dinv (b - A x) (one weighted Jacobi sweep), 3 y = omega dinv b
+ * (the sweep from zero: x, coef, table not read).  y != x. */
+int odil_bmg_apply_f64(const double* coef, const int64_t* table, const int64_t* desc, const double* x, const double* b,
+                       const double* dinv, double* y, int mode, double omega, void* stream);
+int odil_bmg_apply_f32(const float* coef, const int64_t* table, const int64_t* desc, const float* x, const float* b,
+                       const float* dinv, float* y, int mode, float omega, void* stream);
+/* One term of A = M^T M: out[j] += c1[r(j)] c2[r(j)] over field a's grid (ashape, canonical 3-D), c1 / c2 the coefficient
+ * arrays of two stencil blocks of the same output (row grid rshape); rmap: DEVICE int64, per axis of a's grid
+ * (concatenated) the row reading a at j_d whose read of b is at j_d + o_d, or -1 (reference core.py:1144-1171). */
+int odil_bmg_assemble_f64(const double* c1, const double* c2, const int64_t* rmap, const int64_t* ashape,
+                          const int64_t* rshape, double* out, void* stream);
+int odil_bmg_assemble_f32(const float* c1, const float* c2, const int64_t* rmap, const int64_t* ashape,
+                          const int64_t* rshape, float* out, void* stream);
+/* Transfers between a level (fdesc) and the next coarser one (cdesc); code: HOST, 3 per field, per axis 0 = not coarsened,
+ * 1 = cells (3/4, 1/4 linear; all of the parent at a wall), 2 = nodes (coarse node I on fine node 2I, linear).
+ * mode 0: out_coarse = P^T in_fine; mode 1: out_fine = add_fine + P in_coarse (out may be add; in != out). */
+int odil_bmg_transfer_f64(const int64_t* fdesc, const int64_t* cdesc, const int* code, const double* in,
+                          const double* add, double* out, int mode, void* stream);
+int odil_bmg_transfer_f32(const int64_t* fdesc, const int64_t* cdesc, const int* code, const float* in,
+                          const float* add, float* out, int mode, void* stream);
+/* Galerkin coarsening C^c = P^T C P: every coefficient of the coarse table ctable (nce entries, `total` values) from the
+ * fine coefficients, one thread per coarse value, fixed summation order. */
+int odil_bmg_galerkin_f64(const int64_t* fdesc, const int64_t* cdesc, const int* code, const double* fcoef,
+                          const int64_t* ftable, const int64_t* ctable, int nce, int64_t total, double* ccoef,
+                          void* stream);
+int odil_bmg_galerkin_f32(const int64_t* fdesc, const int64_t* cdesc, const int* code, const float* fcoef,
+                          const int64_t* ftable, const int64_t* ctable, int nce, int64_t total, float* ccoef,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,10 @@ _SIGNATURES = {
     "csr_assemble": [_P, _I64P, c_int, _I64P, c_int, c_int64, _P, _P, _P, _P],
     "dense_block_xty": [_P, _P, c_int64, c_int, c_int, c_int64, c_int64, _P, _P, _P],
     "dense_block_gram": [_P, c_int64, c_int, c_int64, _P, _P, _P],
+    "bmg_apply": [_P, _P, _I64P, _P, _P, _P, _P, c_int, _R, _P],
+    "bmg_assemble": [_P, _P, _P, _I64P, _I64P, _P, _P],
+    "bmg_transfer": [_I64P, _I64P, _P, _P, _P, _P, c_int, _P],
+    "bmg_galerkin": [_I64P, _I64P, _P, _P, _P, _P, c_int, c_int64, _P, _P],
 }
 
 EXPORTED = [

@@ -18,10 +18,14 @@ Convergence is checked on the true residual with the deterministic dot products.
 
 import math
 
+import ctypes
+
 import numpy as np
 import torch
 
 from . import ops
+
+ctypes_int = ctypes.c_int
 
 
 def skewed(shape, dtype, device, k, zero=False):
@@ -748,3 +752,371 @@ def recognise_poisson(op):
     if not np.all(pairs[:, 0] <= rtol * pairs[:, 1]):  # (NaN compares false)
         return None
     return shape, h2
+
+
+# ======================================================================================================================
+# Multigrid for the damped normal equations of several grid fields (csrc/block_mg.hip)
+# ======================================================================================================================
+# Host planning (numpy, no device): the index maps of `Context.field`, the offset pattern of A = M^T M and of the
+# coarse operators.  Shapes are canonical 3-D (leading axes of extent 1).
+
+COARSEST_MAX_UNKNOWNS = 4096  # the coarsest level is solved exactly (a dense pseudo-inverse)
+
+
+def canon3(shape):
+    return (1,) * (3 - len(shape)) + tuple(int(s) for s in shape)
+
+
+def gather_map(sn, field_loc, loc, shift):
+    """Row r of the output grid reads field index g[r] along one axis, -1 where it reads the padded constant 0: the map
+    of odil_field_gather (pad 'c' -> 'n', periodic roll by -shift, trim 'n' -> 'c'; reference core.py:955-969)."""
+    pad = 1 if (field_loc == "c" and loc == "n") else 0
+    trim = 1 if (field_loc == "n" and loc == "c") else 0
+    nper = sn + pad
+    r = np.arange(nper - trim, dtype=np.int64)
+    return (r + int(shift) % nper) % nper - pad
+
+
+def pair_axis_tables(sa, g1, g2):
+    """One axis of the term c1 c2 of two blocks that read fields a (extent sa, map g1) and b (map g2) from the same rows:
+    {offset o: rmap} with rmap[j] the row that reads a at j and b at j + o, else -1."""
+    rows = np.full(sa, -1, dtype=np.int64)
+    ok = g1 >= 0
+    rows[g1[ok]] = np.nonzero(ok)[0]
+    k = np.where(rows >= 0, g2[np.maximum(rows, 0)], -1)
+    valid = (rows >= 0) & (k >= 0)
+    off = k - np.arange(sa)
+    return {int(o): np.where(valid & (off == o), rows, -1) for o in np.unique(off[valid])}
+
+
+def p1d(code, nf, nc):
+    """The 1-D prolongation (nf x nc) of transfer code 0 (identity), 1 (cells: 3/4, 1/4, all of the parent at a wall) or
+    2 (nodes: coarse node I on fine node 2 I, linear) -- the weights of pw1 in csrc/block_mg.hip."""
+    p = np.zeros((nf, nc))
+    for i in range(nf):
+        if code == 0:
+            p[i, i] = 1.0
+        elif code == 2:
+            if i % 2 == 0:
+                p[i, i // 2] = 1.0
+            else:
+                p[i, i // 2] = p[i, i // 2 + 1] = 0.5
+        else:
+            par = i // 2
+            nb = par + 1 if i % 2 else par - 1
+            if 0 <= nb < nc:
+                p[i, par], p[i, nb] = 0.75, 0.25
+            else:
+                p[i, par] = 1.0
+    return p
+
+
+_p1d_cache = dict()
+
+
+def _p1d(code, nf, nc):
+    key = (code, nf, nc)
+    if key not in _p1d_cache:
+        _p1d_cache[key] = p1d(code, nf, nc)
+    return _p1d_cache[key]
+
+
+def coarse_axis_offsets(code_a, nfa, nca, code_b, nfb, ncb, o):
+    """The offsets J - I at which the 1-D product P_a^T S_o P_b (S_o: k = i + o) is nonzero."""
+    pa, pb = _p1d(code_a, nfa, nca), _p1d(code_b, nfb, ncb)
+    i = np.arange(nfa)
+    ok = (i + o >= 0) & (i + o < nfb)
+    if not ok.any():
+        return []
+    prod = (pa[ok] != 0).astype(np.float64).T @ (pb[i[ok] + o] != 0).astype(np.float64)
+    ii, jj = np.nonzero(prod)
+    return sorted(set(int(v) for v in (jj - ii)))
+
+
+def coarse_shape3(shape, codes):
+    return tuple(n if c == 0 else n // 2 if c == 1 else (n - 1) // 2 + 1 for n, c in zip(shape, codes))
+
+
+def plan_levels(cshape, locs, max_coarsest=COARSEST_MAX_UNKNOWNS):
+    """Per level the canonical field shapes and, per transition, the transfer codes (3 per field).  An axis is halved
+    while its cell count is even; the hierarchy stops at the first level with at most `max_coarsest` unknowns.  None when
+    it cannot get there, or when there would be only one level."""
+    cells = list(canon3(cshape))
+    loc3 = ["." * (3 - len(l)) + l for l in locs]
+    shapes = [[tuple(1 if ch == "." else (cells[d] + (1 if ch == "n" else 0)) for d, ch in enumerate(l)) for l in loc3]]
+    codes = []
+    while sum(math.prod(s) for s in shapes[-1]) > max_coarsest or len(shapes) == 1:
+        halve = [d >= 3 - len(cshape) and cells[d] % 2 == 0 and cells[d] >= 2 for d in range(3)]
+        if not any(halve):
+            return None
+        cells = [c // 2 if h else c for c, h in zip(cells, halve)]
+        code = [[0 if (not halve[d] or l[d] == ".") else (1 if l[d] == "c" else 2) for d in range(3)] for l in loc3]
+        shapes.append([coarse_shape3(s, c) for s, c in zip(shapes[-1], code)])
+        codes.append(code)
+    return shapes, codes
+
+
+def level_desc(shapes, ebeg):
+    """The host descriptor of a level (include/odil_hip.h: odil_bmg_apply)."""
+    offs = [0]
+    for s in shapes:
+        offs.append(offs[-1] + math.prod(s))
+    vals = [len(shapes)] + offs + [v for s in shapes for v in s] + list(ebeg)
+    return ops.i64(vals), offs
+
+
+def normal_pattern(op):
+    """The terms of A = M^T M of a LinearizedOperator whose unknowns are all grid fields: a list of
+    (a, b, o, block 1, block 2, rmap) in the order of op.blocks (rmap: per axis, concatenated), and the field keys.
+    None when a block is dense or a field has a shape this form does not cover."""
+    from .core import Field
+
+    keys = list(op.key_to_field)
+    ndim = op.domain.ndim
+    if ndim > 3:
+        return None
+    fshape = dict()
+    for key, field in op.key_to_field.items():
+        if not isinstance(field, Field) or field.loc is None or len(field.loc) != ndim or any(ch not in "cn" for ch in field.loc):
+            return None
+        shape = tuple(field.array.shape)
+        want = tuple(c + (1 if ch == "n" else 0) for c, ch in zip(op.domain.cshape, field.loc))
+        if shape != want or op.key_to_size[key] != math.prod(shape):
+            return None
+        fshape[key] = canon3(shape)
+    groups = dict()
+    for blk in op.blocks:
+        row0, nrows, kind, key, payload = blk
+        if kind != "stencil" or key not in fshape:
+            return None
+        groups.setdefault(row0, []).append(blk)
+    terms = []
+    for row0, blks in groups.items():
+        maps = []
+        for _, _, _, key, (coeff, shift, loc, vshape) in blks:
+            field = op.key_to_field[key]
+            if len(vshape) != ndim:
+                return None
+            lead = [np.zeros(1, dtype=np.int64)] * (3 - ndim)
+            maps.append(lead + [gather_map(int(n), fl, l, s) for n, fl, l, s in zip(field.array.shape, field.loc, loc, shift)])
+        for i1, b1 in enumerate(blks):
+            a = keys.index(b1[3])
+            for i2, b2 in enumerate(blks):
+                b = keys.index(b2[3])
+                axes = [pair_axis_tables(fshape[b1[3]][d], maps[i1][d], maps[i2][d]) for d in range(3)]
+                for o0, r0 in axes[0].items():
+                    for o1, r1 in axes[1].items():
+                        for o2, r2 in axes[2].items():
+                            rmap = np.concatenate([r0, r1, r2])
+                            terms.append((a, b, (o0, o1, o2), b1, b2, rmap, canon3(b1[4][3])))
+    return terms, keys, [fshape[k] for k in keys]
+
+
+def coarse_pattern(entries, shapes_f, shapes_c, code):
+    """Offsets of the coarse entries P_a^T C_ab P_b from the fine entries [(a, b, o)], sorted (a, b, o)."""
+    out = set()
+    for a, b, o in entries:
+        per = [coarse_axis_offsets(code[a][d], shapes_f[a][d], shapes_c[a][d], code[b][d], shapes_f[b][d], shapes_c[b][d],
+                                   o[d]) for d in range(3)]
+        for d in range(3):
+            # linear P and 2x coarsening: |o| <= 2 gives |J - I| <= 2 (I - 2 <= (i + o - 1) / 2 with i >= 2 I - 1, ...)
+            if abs(o[d]) <= 2:
+                assert all(abs(v) <= 2 for v in per[d]), (a, b, o, d, per[d])
+        for v0 in per[0]:
+            for v1 in per[1]:
+                for v2 in per[2]:
+                    out.add((a, b, (v0, v1, v2)))
+    return sorted(out)
+
+
+def chebyshev_weights(n, lo, hi):
+    mid, half = 0.5 * (hi + lo), 0.5 * (hi - lo)
+    return [1.0 / (mid - half * math.cos(math.pi * (2 * k + 1) / (2 * n))) for k in range(n)]
+
+
+class NormalGMG:
+    """V-cycle preconditioner for the damped normal equations A = M^T M + damp^2 I + dampdiag^2 diag (reference order,
+    linsolver.py:19-23) of a Newton system whose unknowns are all grid `Field`s -- any number, any loc, 1-3 dimensions,
+    stencil blocks only.  The reference gives such systems to AMG on the normal equations + CG (linsolver.py:61-72).
+
+      fine level     A assembled from the stencil blocks, one gather launch per (block pair, offset) (odil_bmg_assemble)
+      coarse levels  Galerkin products P^T A P, one launch per level (odil_bmg_galerkin); P per field and axis by loc
+                     (cells: linear 3/4, 1/4; nodes: coarse node on every second fine node, linear)
+      sweeps         Chebyshev-weighted point Jacobi over all fields, one launch each (odil_bmg_apply mode 2 / 3)
+      transfers      all fields in one launch (odil_bmg_transfer)
+      coarsest       a dense pseudo-inverse applied by odil_lincomb
+
+    The cycle starts from zero and its post-sweeps repeat the pre-sweeps' weights in reverse order: the preconditioner
+    is symmetric (positive definite where A is), as the outer CG needs.  Build with `NormalGMG.create`, which returns
+    None (after a log line) when the hierarchy cannot reach a small enough coarsest level."""
+
+    # sweeps before and after the coarse correction, Chebyshev interval [hi / smooth_ratio, hi] (darcy with curl closure,
+    # CG iterations to 1e-8 at 512^2 / 64^3: nu = 2 on [hi / 4, hi] 50 / 51, nu = 3 on [hi / 10, hi] 32 / 36, nu = 4 on
+    # [hi / 16, hi] 25 / 28 and the shortest solve; kernel log)
+    nu = 4
+    smooth_ratio = 16.0
+
+    @classmethod
+    def create(cls, op, damp=0.0, dampdiag=0.0):
+        from .util import printlog
+
+        pat = normal_pattern(op)
+        if pat is None:
+            return None
+        plan = plan_levels(op.domain.cshape, [op.key_to_field[k].loc for k in pat[1]])
+        if plan is None:
+            printlog("odil_amd: multigrid on the normal equations: the extents {} do not coarsen to {} unknowns; "
+                     "using CG on the normal equations".format(tuple(op.domain.cshape), COARSEST_MAX_UNKNOWNS))
+            return None
+        return cls(op, pat, plan, damp, dampdiag)
+
+    def __init__(self, op, pattern, plan, damp=0.0, dampdiag=0.0):
+        terms, self.keys, shape0 = pattern
+        self.shapes, self.codes = plan
+        assert [tuple(s) for s in self.shapes[0]] == [tuple(s) for s in shape0]
+        self.dtype, self.device = op.dtype, op.device
+        self.nf = len(self.keys)
+        self.nlvl = len(self.shapes)
+        self.ndim = op.domain.ndim
+        dev, dt = self.device, self.dtype
+        # --- finest level: A = M^T M, terms summed in the order of op.blocks
+        fine = dict()
+        sizes = [math.prod(s) for s in self.shapes[0]]
+        for a, b, o, b1, b2, rmap, rshape in terms:
+            arr = fine.get((a, b, o))
+            if arr is None:
+                arr = fine[(a, b, o)] = torch.zeros(sizes[a], dtype=dt, device=dev)
+            rm = torch.as_tensor(rmap, device=dev)
+            ops.bmg_assemble(b1[4][0].reshape(-1).contiguous(), b2[4][0].reshape(-1).contiguous(), rm, self.shapes[0][a],
+                             rshape, arr)
+        for a in range(self.nf):
+            if (a, a, (0, 0, 0)) not in fine:
+                fine[(a, a, (0, 0, 0))] = torch.zeros(sizes[a], dtype=dt, device=dev)
+        if damp or dampdiag:
+            # reference linsolver.py:19-23 (as cg_normal): A_ii -> (A_ii + damp^2) (1 + dampdiag^2)
+            for a in range(self.nf):
+                d = fine[(a, a, (0, 0, 0))]
+                d.add_(float(damp) ** 2).mul_(1.0 + float(dampdiag) ** 2)
+        entries = sorted(fine)
+        self.entries, self.starts, self.coef, self.table, self.desc, self.offs = [], [], [], [], [], []
+        self._pack(0, entries, [fine[e] for e in entries])
+        del fine
+        # --- coarse levels
+        self.code_arrays = [(ctypes_int * (3 * self.nf))(*[c for cf in code for c in cf]) for code in self.codes]
+        for lvl in range(1, self.nlvl):
+            centries = coarse_pattern(self.entries[lvl - 1], self.shapes[lvl - 1], self.shapes[lvl], self.codes[lvl - 1])
+            self._pack(lvl, centries, None)
+            ops.bmg_galerkin(self.desc[lvl - 1], self.desc[lvl], self.code_arrays[lvl - 1], self.coef[lvl - 1],
+                             self.table[lvl - 1], self.table[lvl], len(centries), self.coef[lvl])
+        # --- smoothing: Jacobi on D^-1 A, Chebyshev weights on [hi / smooth_ratio, hi], hi a Gershgorin bound (one read-back
+        # per level at set-up; an upper bound keeps every sweep polynomial below 1 in modulus on the spectrum: B stays SPD)
+        self.dinv, self.weights = [], []
+        for lvl in range(self.nlvl):
+            diag = torch.empty(self.offs[lvl][-1], dtype=dt, device=dev)
+            rowabs = torch.zeros(self.offs[lvl][-1], dtype=dt, device=dev)
+            for (a, b, o), start in zip(self.entries[lvl], self.starts[lvl]):
+                n = self.offs[lvl][a + 1] - self.offs[lvl][a]
+                seg = self.coef[lvl][start:start + n]
+                rowabs[self.offs[lvl][a]:self.offs[lvl][a + 1]] += seg.abs()
+                if a == b and o == (0, 0, 0):
+                    diag[self.offs[lvl][a]:self.offs[lvl][a + 1]] = seg
+            dinv = torch.where(diag > 0, 1.0 / torch.where(diag > 0, diag, torch.ones_like(diag)), torch.zeros_like(diag))
+            hi = float((rowabs * dinv).max())
+            self.dinv.append(dinv)
+            self.weights.append(chebyshev_weights(self.nu, hi / self.smooth_ratio, hi))
+        # --- coarsest: dense pseudo-inverse (set-up on the host: at most COARSEST_MAX_UNKNOWNS unknowns)
+        self.coarse_inv = self._coarse_inverse()
+        n = [self.offs[l][-1] for l in range(self.nlvl)]
+        self.x = [torch.zeros(v, dtype=dt, device=dev) for v in n]
+        self.y = [torch.zeros(v, dtype=dt, device=dev) for v in n]
+        self.r = [torch.zeros(v, dtype=dt, device=dev) for v in n]
+        self.b = [None] + [torch.zeros(v, dtype=dt, device=dev) for v in n[1:]]
+        self.method = "gmg-normal ({} field{}, {} levels)".format(self.nf, "s" if self.nf > 1 else "", self.nlvl)
+
+    def _pack(self, lvl, entries, arrays):
+        sizes = [math.prod(s) for s in self.shapes[lvl]]
+        starts, ebeg, pos = [], [0] * (self.nf + 1), 0
+        rows = []
+        for e, (a, b, o) in enumerate(entries):
+            starts.append(pos)
+            rows.append([a, b, o[0], o[1], o[2], pos, 0, 0])
+            pos += sizes[a]
+            ebeg[a + 1] = e + 1
+        for a in range(self.nf):
+            ebeg[a + 1] = max(ebeg[a + 1], ebeg[a])
+        assert [r[0] for r in rows] == sorted(r[0] for r in rows)
+        coef = torch.empty(pos, dtype=self.dtype, device=self.device) if arrays is None else torch.cat(arrays)
+        desc, offs = level_desc(self.shapes[lvl], ebeg)
+        self.entries.append(list(entries))
+        self.starts.append(starts)
+        self.coef.append(coef)
+        self.table.append(torch.tensor(rows, dtype=torch.int64, device=self.device).reshape(-1))
+        self.desc.append(desc)
+        self.offs.append(offs)
+
+    def dense(self, lvl):
+        """The level's matrix, dense on the host (float64; tests and the coarsest level)."""
+        n = self.offs[lvl][-1]
+        amat = np.zeros((n, n))
+        coef = self.coef[lvl].double().cpu().numpy()
+        for (a, b, o), start in zip(self.entries[lvl], self.starts[lvl]):
+            sa, sb = self.shapes[lvl][a], self.shapes[lvl][b]
+            q = np.indices(sa).reshape(3, -1)
+            t = q + np.array(o)[:, None]
+            ok = np.all((t >= 0) & (t < np.array(sb)[:, None]), axis=0)
+            rows = self.offs[lvl][a] + np.ravel_multi_index(q[:, ok], sa)
+            cols = self.offs[lvl][b] + np.ravel_multi_index(t[:, ok], sb)
+            np.add.at(amat, (rows, cols), coef[start:start + math.prod(sa)][ok])
+        return amat
+
+    def _coarse_inverse(self):
+        amat = self.dense(self.nlvl - 1)
+        amat = 0.5 * (amat + amat.T)
+        w, v = np.linalg.eigh(amat)
+        keep = w > 1e-13 * max(float(np.abs(w).max()), 1e-300)
+        inv = (v[:, keep] / w[keep]) @ v[:, keep].T
+        return torch.as_tensor(inv, dtype=self.dtype).to(self.device).contiguous()
+
+    def apply(self, lvl, x, out=None):
+        """out = A_lvl x."""
+        out = torch.empty_like(x) if out is None else out
+        return ops.bmg_apply(self.coef[lvl], self.table[lvl], self.desc[lvl], x, out, mode=0)
+
+    def restrict(self, lvl, fine, out):
+        return ops.bmg_restrict(self.desc[lvl], self.desc[lvl + 1], self.code_arrays[lvl], fine, out)
+
+    def prolong_add(self, lvl, coarse, x):
+        return ops.bmg_prolong_add(self.desc[lvl], self.desc[lvl + 1], self.code_arrays[lvl], coarse, x, x)
+
+    def _sweeps(self, lvl, x, b, weights, zero):
+        """Jacobi sweeps x' = x + w D^-1 (b - A x); the iterate ping-pongs between x and the level's spare buffer.
+        zero: the iterate is the zero vector (x only a buffer).  Returns the tensor holding the result."""
+        cur, spare = x, self.y[lvl] if x is not self.y[lvl] else self.x[lvl]
+        for k, w in enumerate(weights):
+            if zero and k == 0:
+                ops.bmg_apply(None, None, self.desc[lvl], None, cur, b=b, dinv=self.dinv[lvl], mode=3, omega=w)
+                continue
+            ops.bmg_apply(self.coef[lvl], self.table[lvl], self.desc[lvl], cur, spare, b=b, dinv=self.dinv[lvl], mode=2,
+                          omega=w)
+            cur, spare = spare, cur
+        return cur
+
+    def _cycle(self, lvl, b):
+        if lvl == self.nlvl - 1:
+            x = self.x[lvl]
+            return ops.lincomb(x, 0.0, self.coarse_inv, b)
+        w = self.weights[lvl]
+        x = self._sweeps(lvl, self.x[lvl], b, w, zero=True)
+        r = ops.bmg_apply(self.coef[lvl], self.table[lvl], self.desc[lvl], x, self.r[lvl], b=b, mode=1)
+        bc = self.restrict(lvl, r, self.b[lvl + 1])
+        xc = self._cycle(lvl + 1, bc)
+        self.prolong_add(lvl, xc, x)
+        return self._sweeps(lvl, x, b, list(reversed(w)), zero=False)
+
+    def precondition(self, r, out=None):
+        """z = B r, B one V-cycle from zero (symmetric; no host synchronisation)."""
+        z = self._cycle(0, r.contiguous())
+        if out is None:
+            return z.clone()
+        out.copy_(z)
+        return out

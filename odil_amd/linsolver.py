@@ -11,7 +11,8 @@ Cholesky of A = M^T M up to 49152 unknowns, memory permitting (one f64 GEMM + ro
 multigrid for the recognised stencils beyond the dense factorisation's reach (gmg.py), and otherwise "CG to
 round-off" (tol 1e-14 relative, bounded by `--linsolver_maxiter` if given, else 20 n), which
 reproduces the reference's Newton iterate to solver tolerance; `cg` / `bicgstab` / `multigrid`
-use `--linsolver_tol`.
+use `--linsolver_tol`.  `multigrid` on systems of grid fields that no earlier route takes (several fields, mixed locations,
+non-square or damped M) is CG preconditioned by V-cycles on the normal equations (gmg.NormalGMG).
 cupy / sparseqr / pyamg variants of the reference are optional third-party paths and are
 not provided.
 """
@@ -26,9 +27,11 @@ def _dot(a, b):
     return ops.dots(a[None], b)[0]
 
 
-def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=None, x0=None, check_every=25, b=None):
+def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=None, x0=None, check_every=25, b=None,
+              precond=None):
     """Solves (M^T M + damp^2 I + dampdiag^2 diag(M^T M)) x = M^T rhs (or = b when `b` is given) by
-    Jacobi-preconditioned CG.
+    Jacobi-preconditioned CG.  precond: callable (r, out) writing z = B r into out instead of the Jacobi step (B symmetric
+    positive definite: gmg.NormalGMG.precondition).
 
     The iteration runs without host synchronisation: the scalars <r, z>, <p, A p>, alpha and beta
     stay 0-d device tensors (deterministic odil_dots; updates through odil_lincomb with device
@@ -62,7 +65,10 @@ def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=N
     # third, and the roles of rows 0 and 2 alternate (no aliasing inside odil_lincomb)
     buf = torch.empty((3, n), dtype=dtype, device=device)
     p, z, flip = buf[0], buf[1], False
-    ops.addcmul(z, minv, r, accumulate=False)
+    if precond is None:
+        ops.addcmul(z, minv, r, accumulate=False)
+    else:
+        precond(r, out=z)
     p.copy_(z)
     rz = _dot(r, z)
     bnorm = float(_dot(b, b)) ** 0.5
@@ -80,7 +86,10 @@ def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=N
             alpha = torch.where(pap > 0, rz / pap, torch.zeros_like(rz)).reshape(1)  # converged exactly: stay put
             ops.lincomb(x, 1.0, p[None], alpha)
             ops.lincomb(r, 1.0, ap[None], -alpha)
-            ops.addcmul(z, minv, r, accumulate=False)
+            if precond is None:
+                ops.addcmul(z, minv, r, accumulate=False)
+            else:
+                precond(r, out=z)
             rz_new = _dot(r, z)
             beta = torch.where(rz > 0, rz_new / rz, torch.zeros_like(rz))
             rz = rz_new
@@ -515,7 +524,40 @@ def solve(matr, rhs, args, status=None, linsolver="direct", consume=False):
             return x
     if linsolver in ("direct", "directsq"):
         return cg_normal(matr, rhs, damp, dampdiag, tol=1e-14, maxiter=maxiter, status=status)
+    if linsolver == "multigrid":
+        x = normal_multigrid(matr, rhs, damp, dampdiag, tol, maxiter, status)
+        if x is not None:
+            return x
     return cg_normal(matr, rhs, damp, dampdiag, tol=tol, maxiter=maxiter or 1000, status=status)
+
+
+def normal_multigrid(matr, rhs, damp=0.0, dampdiag=0.0, tol=1e-10, maxiter=None, status=None):
+    """`multigrid` for systems of grid fields that no earlier route takes (several fields, mixed locations, non-square or
+    damped M): CG on the damped normal equations preconditioned by V-cycles (gmg.NormalGMG), as the reference's AMG + CG
+    (linsolver.py:61-72).  Stops at a relative residual of the normal equations of `tol` or after `maxiter` iterations.
+    float32 problems are assembled and iterated in float64, the result rounded back.  None when the operator does not
+    qualify (an unknown that is not a `Field`, dense blocks, extents that do not coarsen)."""
+    from . import gmg
+
+    if status is None:
+        status = dict()
+    if any(kind == "dense" for _, _, kind, _, _ in matr.blocks) or not matr.blocks:
+        return None
+    wide = matr.promoted() if matr.dtype == torch.float32 else matr
+    solver = gmg.NormalGMG.create(wide, damp, dampdiag)
+    if solver is None:
+        return None
+    rhs = rhs.to(wide.dtype)
+    b = wide.rmatvec(rhs)
+    x = cg_normal(wide, rhs, damp, dampdiag, tol=tol, maxiter=maxiter or 1000, status=status, b=b,
+                  check_every=NORMAL_GMG_CHECK_EVERY, precond=solver.precondition)
+    bnorm = float(_dot(b, b)) ** 0.5
+    status["method"] = solver.method
+    status["converged"] = bool(status["residual"] <= tol * max(bnorm, 1e-300))
+    return x.to(matr.dtype)
+
+
+NORMAL_GMG_CHECK_EVERY = 2  # V-cycle-preconditioned CG: the residual norm is read back every second iteration
 
 
 def _exact_routes(matr, rhs, damp, dampdiag, maxiter, status, linsolver):

@@ -867,3 +867,38 @@ def csr_assemble(coeffs, shifts, shape, col_offset=0):
         c_int64(col_offset), ptr(indptr), ptr(indices), ptr(data), stream_ptr(),
     )
     return indptr, indices, data
+
+
+# ---- multigrid for the normal equations of several grid fields (csrc/block_mg.hip, gmg.NormalGMG) ------------------
+def bmg_apply(coef, table, desc, x, y, b=None, dinv=None, mode=0, omega=0.0):
+    """One launch over all fields of a level (include/odil_hip.h: odil_bmg_apply): mode 0 y = A x, 1 y = b - A x,
+    2 y = x + omega dinv (b - A x), 3 y = omega dinv b.  desc: the level's host descriptor (c_int64 array)."""
+    assert y.is_contiguous() and (x is None or x.data_ptr() != y.data_ptr())
+    call("bmg_apply", y.dtype, ptr(coef), ptr(table), desc, ptr(x), ptr(b), ptr(dinv), ptr(y), c_int(mode), float(omega),
+         stream_ptr())
+    return y
+
+
+def bmg_assemble(c1, c2, rmap, ashape, rshape, out):
+    """out += c1[r(j)] c2[r(j)] over field a's grid (one term of M^T M, odil_bmg_assemble)."""
+    call("bmg_assemble", out.dtype, ptr(c1), ptr(c2), ptr(rmap), i64(ashape), i64(rshape), ptr(out), stream_ptr())
+    return out
+
+
+def bmg_restrict(fdesc, cdesc, code, fine, out):
+    """out = P^T fine over all fields (odil_bmg_transfer, mode 0); code: host c_int array, 3 per field."""
+    call("bmg_transfer", out.dtype, fdesc, cdesc, code, ptr(fine), None, ptr(out), c_int(0), stream_ptr())
+    return out
+
+
+def bmg_prolong_add(fdesc, cdesc, code, coarse, add, out):
+    """out = add + P coarse over all fields (odil_bmg_transfer, mode 1; out may be add)."""
+    call("bmg_transfer", out.dtype, fdesc, cdesc, code, ptr(coarse), ptr(add), ptr(out), c_int(1), stream_ptr())
+    return out
+
+
+def bmg_galerkin(fdesc, cdesc, code, fcoef, ftable, ctable, nce, out):
+    """Coarse coefficients P^T C P of every entry of ctable (odil_bmg_galerkin)."""
+    call("bmg_galerkin", out.dtype, fdesc, cdesc, code, ptr(fcoef), ptr(ftable), ptr(ctable), c_int(nce),
+         c_int64(out.numel()), ptr(out), stream_ptr())
+    return out
