@@ -761,6 +761,7 @@ def recognise_poisson(op):
 # coarse operators.  Shapes are canonical 3-D (leading axes of extent 1).
 
 COARSEST_MAX_UNKNOWNS = 4096  # the coarsest level is solved exactly (a dense pseudo-inverse)
+MAX_FIELDS = 8  # fields per level descriptor: kBmgMaxFields in csrc/block_mg.hip
 
 
 def canon3(shape):
@@ -948,7 +949,8 @@ class NormalGMG:
 
     The cycle starts from zero and its post-sweeps repeat the pre-sweeps' weights in reverse order: the preconditioner
     is symmetric (positive definite where A is), as the outer CG needs.  Build with `NormalGMG.create`, which returns
-    None (after a log line) when the hierarchy cannot reach a small enough coarsest level."""
+    None (after a log line) when there are more than MAX_FIELDS fields or the hierarchy cannot reach a small enough
+    coarsest level."""
 
     # sweeps before and after the coarse correction, Chebyshev interval [hi / smooth_ratio, hi] (darcy with curl closure,
     # CG iterations to 1e-8 at 512^2 / 64^3: nu = 2 on [hi / 4, hi] 50 / 51, nu = 3 on [hi / 10, hi] 32 / 36, nu = 4 on
@@ -962,6 +964,10 @@ class NormalGMG:
 
         pat = normal_pattern(op)
         if pat is None:
+            return None
+        if len(pat[1]) > MAX_FIELDS:
+            printlog("odil_amd: multigrid on the normal equations: {} fields, the kernels take at most {}; "
+                     "using CG on the normal equations".format(len(pat[1]), MAX_FIELDS))
             return None
         plan = plan_levels(op.domain.cshape, [op.key_to_field[k].loc for k in pat[1]])
         if plan is None:

@@ -536,7 +536,8 @@ def normal_multigrid(matr, rhs, damp=0.0, dampdiag=0.0, tol=1e-10, maxiter=None,
     damped M): CG on the damped normal equations preconditioned by V-cycles (gmg.NormalGMG), as the reference's AMG + CG
     (linsolver.py:61-72).  Stops at a relative residual of the normal equations of `tol` or after `maxiter` iterations.
     float32 problems are assembled and iterated in float64, the result rounded back.  None when the operator does not
-    qualify (an unknown that is not a `Field`, dense blocks, extents that do not coarsen)."""
+    qualify (an unknown that is not a `Field`, dense blocks, more than gmg.MAX_FIELDS fields, extents that do not
+    coarsen)."""
     from . import gmg
 
     if status is None:

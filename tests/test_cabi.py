@@ -45,6 +45,68 @@ def test_host_side_validation_reports_errors():
     assert status == -1
 
 
+def test_bmg_host_side_validation():
+    """odil_bmg_apply / odil_bmg_transfer reject malformed level descriptors, transfer codes, modes and aliasing with
+    ODIL_E_INVAL before anything touches the device (the pointers are dummies)."""
+    from ctypes import c_int, c_void_p
+
+    from odil_amd import _lib
+
+    lib = _lib.load()
+    coef, table, x, b, dinv, y = (c_void_p(16 * k) for k in range(1, 7))
+
+    def desc(nf, off, n, ebeg):
+        return _lib.i64([nf] + off + [v for s in n for v in s] + ebeg)
+
+    def apply(d, mode=0, x=x, y=y):
+        return lib.odil_bmg_apply_f64(coef, table, d, x, b, dinv, y, c_int(mode), 0.5, None)
+
+    def transfer(fd, cd, code, mode=0, src=x, out=y):
+        codes = None if code is None else (c_int * len(code))(*code)
+        return lib.odil_bmg_transfer_f64(fd, cd, codes, src, b, out, c_int(mode), None)
+
+    good = ([0, 12, 15], [(1, 3, 4), (1, 1, 3)], [0, 2, 3])  # two fields, 12 + 3 unknowns, 3 table entries
+    bad_desc = {
+        "no fields": desc(0, [0], [], [0]),
+        "nine fields": desc(9, list(range(10)), [(1, 1, 1)] * 9, [0] * 10),
+        "empty extent": desc(2, [0, 0, 3], [(1, 0, 4), (1, 1, 3)], [0, 2, 3]),
+        "offsets off the shapes": desc(2, [0, 12, 16], *good[1:]),
+        "sizes off the shapes": desc(2, [0, 11, 14], *good[1:]),
+        "ebeg decreasing": desc(2, good[0], good[1], [0, 2, 1]),
+    }
+    for what, d in bad_desc.items():
+        for mode in range(4):
+            assert apply(d, mode) == -1, (what, mode)
+        assert b"bmg_apply" in lib.odil_last_error(), what
+    ok = desc(2, *good)
+    for mode in (-1, 4):
+        assert apply(ok, mode) == -1, mode
+    for mode in (0, 1, 2):
+        assert apply(ok, mode, x=y) == -1, mode  # x aliasing y
+    # transfers: fine (1, 3, 4) / (1, 1, 3) by codes (0, 0, 1) and (0, 0, 2) -> coarse (1, 3, 2) / (1, 1, 2)
+    fine, coarse = desc(2, *good), desc(2, [0, 6, 8], [(1, 3, 2), (1, 1, 2)], [0, 2, 3])
+    code = [0, 0, 1, 0, 0, 2]
+    for what, d in bad_desc.items():
+        assert transfer(d, coarse, code) == -1, what
+        assert transfer(fine, d, code, mode=1) == -1, what
+    for mode in (-1, 2):
+        assert transfer(fine, coarse, code, mode) == -1, mode
+    for mode in (0, 1):
+        assert transfer(fine, coarse, code, mode, src=y, out=y) == -1, mode  # in aliasing out
+    assert transfer(fine, coarse, None) == -1
+    assert transfer(fine, desc(1, [0, 12], [(1, 3, 4)], [0, 2]), code[:3]) == -1  # field counts differ
+    assert transfer(fine, coarse, [0, 0, 2, 0, 0, 2]) == -1  # code 2 on an even fine extent
+    # code 1 on an odd fine extent: (1, 3, 4) -> (1, 1, 4) along axis 1
+    odd = desc(2, [0, 4, 7], [(1, 1, 4), (1, 1, 3)], [0, 2, 3])
+    assert transfer(fine, odd, [0, 1, 0, 0, 0, 0]) == -1
+    # code 2 with coarse extent 1 (fine extent 1)
+    one = desc(2, [0, 12, 13], [(1, 3, 4), (1, 1, 1)], [0, 2, 3])
+    assert transfer(one, one, [0, 0, 0, 0, 0, 2]) == -1
+    assert b"transfer code" in lib.odil_last_error()
+    # code 0 on an axis whose extent changes
+    assert transfer(fine, coarse, [0, 0, 0, 0, 0, 2]) == -1
+
+
 def test_no_cpu_fallback():
     from odil_amd import _lib, ops
 

@@ -37,9 +37,9 @@ def field_shape(cshape, loc):
     return tuple(n + (1 if ch == "n" else 0) for n, ch in zip(cshape, loc))
 
 
-def synthetic(name, seed=0):
-    """(fake LinearizedOperator for the planner, restatement fields, restatement blocks)"""
-    cshape, locs, groups = CASES[name]
+def synthetic(name, seed=0, case=None):
+    """(fake LinearizedOperator for the planner, restatement fields, restatement blocks); case: a CASES value not listed"""
+    cshape, locs, groups = case or CASES[name]
     rng = np.random.default_rng(seed)
     fields = {k: (l, field_shape(cshape, l)) for k, l in locs.items()}
     blocks, opblocks, row0 = [], [], 0
@@ -166,3 +166,25 @@ def test_level_plan():
     assert gmg.plan_levels((3, 5), ["cc", "nc"]) is None            # nothing halves
     assert gmg.plan_levels((6, 250), ["cc"] * 20) is None            # stops short of the coarsest size
     assert len(gmg.plan_levels((4,), ["c"])[0]) == 2                 # at least two levels
+
+
+def many_fields(nf):
+    """A 3-D case of nf fields (locs cycling through ccc ... nnn): every field read by its own output group and by the next
+    field's group."""
+    locs = ["".join("cn"[(k >> (2 - d)) & 1] for d in range(3)) for k in range(8)]
+    keys = ["f{}".format(k) for k in range(nf)]
+    groups = [(locs[k % 8], [(keys[k], (0, 0, 0)), (keys[(k + 1) % nf], (0, 1, 0))]) for k in range(nf)]
+    return (4, 2, 6), {key: locs[k % 8] for k, key in enumerate(keys)}, groups
+
+
+def test_field_limit_of_the_kernels():
+    # 8 fields is the largest level descriptor of csrc/block_mg.hip (kBmgMaxFields); one more and the operator does not
+    # qualify: create returns None (the solve falls back to CG on the normal equations) before anything touches a device
+    assert gmg.MAX_FIELDS == 8
+    op8, _, _ = synthetic(None, case=many_fields(8))
+    terms, keys, shapes = gmg.normal_pattern(op8)
+    assert len(keys) == 8 and sorted({s for s in shapes}) == sorted({field_shape((4, 2, 6), l) for l in many_fields(8)[1].values()})
+    op9, _, _ = synthetic(None, case=many_fields(9))
+    assert len(gmg.normal_pattern(op9)[1]) == 9
+    assert gmg.NormalGMG.create(op9) is None
+    assert gmg.NormalGMG.create(op9, damp=0.5, dampdiag=0.1) is None
