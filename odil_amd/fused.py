@@ -186,7 +186,7 @@ class PoissonEvaluator:
         resident = bool(load().odil_poisson_small_epochs_resident(i64(flat), self.nlvl, self.ndim, 8 if self.dtype == torch.float64 else 4))
         if not resident and not self.small_force and not (self.ndim == 1 and self.sizes[0] <= self.small_max_cells):
             return None
-        if any(tuple(b) != tuple(n // 2 for n in a) for a, b in zip(self.shapes, self.shapes[1:])):
+        if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(self.shapes, self.shapes[1:])):  # (as the kernel requires)
             return None
 
         def packed(levels):
