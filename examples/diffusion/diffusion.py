@@ -7,6 +7,10 @@ against the reference's operator API exactly like examples/poisson/poisson.py (r
 same stencil access, same quadratic wall ghosts `extrap_quadh`), with the conductivity k given on the cell faces.
 
     python examples/diffusion/diffusion.py --ndim 3 --N 64 --optimizer newton --linsolver multigrid --kind jump
+    python -m torch.distributed.run --nproc-per-node 2 examples/diffusion/diffusion.py --ndim 3 --N 64 --slab 1
+
+With `--slab 1` every rank writes its planes of the final u into one raw + XDMF2 file, u_final.xmf; an undivided 3-D run
+writes the same file with `--write_u 1`.
 """
 
 import argparse
@@ -111,6 +115,8 @@ def parse_args(argv=None):
     parser.add_argument("--N", type=int, default=32, help="Grid size")
     parser.add_argument("--kind", type=str, default="smooth", choices=("one", "smooth", "jump"), help="Conductivity field")
     parser.add_argument("--sigma", type=float, default=0.0, help="Reaction coefficient: div(k grad u) - sigma u = f")
+    parser.add_argument("--slab", type=int, default=0, help="Slab decomposition along x over the ranks of torch.distributed")
+    parser.add_argument("--write_u", type=int, default=0, help="Write the final u to u_final.xmf (3-D; always with --slab 1)")
     odil.util.add_arguments(parser)
     odil.linsolver.add_arguments(parser)
     parser.set_defaults(frames=1, report_every=1, history_every=1, plot_every=1, history_full=50)
@@ -118,8 +124,37 @@ def parse_args(argv=None):
     return parser.parse_args(argv)
 
 
+def write_u(problem, u, outdir, rank=0, world=1, barrier=None):
+    """This rank's planes of u (x outermost) into the one raw + XDMF2 file u_final.xmf of all ranks."""
+    spacing = [float(h) for h in problem.domain.step()[1:]][::-1]
+    odil.write_raw_slab(u, os.path.join(outdir, "u_final.xmf"), rank, world, axis=0, spacing=spacing, name="u",
+                        barrier=barrier)
+
+
 def main():
     args = parse_args()
+    if args.slab:
+        # one process per GPU (python -m torch.distributed.run --nproc-per-node N diffusion.py --ndim 3 --slab 1 ...): every
+        # rank builds the global problem, owns a slab of x, logs through rank 0, and all ranks write their planes of the
+        # final u into one raw + XDMF2 file
+        from odil_amd.slab import init_distributed
+        from odil_amd.slab_traced import optimize_slab
+
+        import torch.distributed as dist
+
+        rank, world, _ = init_distributed()
+        outdir = os.path.abspath(args.outdir)
+        if rank == 0:
+            odil.setup_outdir(args)  # (may clear the directory: the other ranks touch it only after the barrier)
+        if world > 1:
+            dist.barrier()
+        if rank != 0:
+            os.makedirs(outdir, exist_ok=True)
+            odil.util.set_log_file(open(os.devnull, "w"))
+        problem, state = make_problem(args)
+        run = optimize_slab(args, problem, state)
+        write_u(problem, run.owned_arrays()[0], outdir, rank, world, barrier=dist.barrier if world > 1 else None)
+        return run
     odil.setup_outdir(args)
     problem, state = make_problem(args)
 
@@ -128,6 +163,8 @@ def main():
 
     callback = odil.make_callback(problem, args, report_func=report)
     odil.util.optimize(args, args.optimizer, problem, state, callback)
+    if args.write_u and args.ndim == 3:
+        write_u(problem, problem.domain.field(state, "u"), os.path.abspath(args.outdir))
 
 
 if __name__ == "__main__":

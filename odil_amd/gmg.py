@@ -661,10 +661,43 @@ class StencilGMG(PoissonGMG):
         return self.sweeps(lvl, out, b, self.weights(self.nu2) if post else [])
 
 
+def stencil_coefficients(items, shape, period=None, dtype=None, device=None):
+    """The coefficient tensor [(2 d + 1), *shape] (order 0, -e_0, +e_0, -e_1, ...) of a Jacobian given as `items` =
+    [(shift, coefficient array of `shape`)], or None when a shift is neither 0 nor a unit vector or the centre is missing.
+    Shifts are taken modulo `period` (the extents of the periodic roll; default `shape`: |shift| <= n / 2).  Shifts that do
+    not occur are zero arrays, duplicates are summed.  Arrays that already lie back to back in the wanted order (the
+    generated Jacobian kernel writes slices of one buffer in the order the operator reads them) give a view, no copies."""
+    ndim = len(shape)
+    period = tuple(period) if period is not None else tuple(shape)
+    want = [(0,) * ndim]
+    for i in range(ndim):
+        want += [tuple(-1 if j == i else 0 for j in range(ndim)), tuple(1 if j == i else 0 for j in range(ndim))]
+    norms = [tuple(((s + n // 2) % n) - n // 2 for s, n in zip(shift, period)) for shift, _ in items]
+    if any(norm not in want for norm in norms) or want[0] not in norms:
+        return None
+    if len(set(norms)) == len(norms) == len(want):
+        arrs = [items[norms.index(sft)][1] for sft in want]
+        first, size = arrs[0], arrs[0].numel()
+        if all(a.is_contiguous() and a.dtype == first.dtype and a.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
+               and a.storage_offset() == first.storage_offset() + j * size for j, a in enumerate(arrs)):
+            return torch.empty(0, dtype=first.dtype, device=first.device).set_(
+                first.untyped_storage(), first.storage_offset(), (len(want),) + tuple(shape))
+    coeffs = torch.zeros((len(want),) + tuple(shape), dtype=dtype or items[0][1].dtype, device=device or items[0][1].device)
+    seen = set()
+    for norm, (_, coeff) in zip(norms, items):
+        slot = want.index(norm)
+        if slot in seen:
+            ops.axpy(coeffs[slot].view(-1), coeff.reshape(-1).contiguous(), 1.0)
+        else:
+            coeffs[slot].view(-1).copy_(coeff.reshape(-1))
+            seen.add(slot)
+    return coeffs
+
+
 def recognise_stencil(op):
     """The coefficient tensor [(2 d + 1), *shape] (order 0, -e_0, +e_0, -e_1, ...) when the LinearizedOperator is square,
     acts on ONE cell-centred `Field` (d <= 3, extents >= 4) and every stencil block's shift is 0 or a unit vector --
-    the structure StencilGMG needs; None otherwise.  Shifts that do not occur are zero arrays, duplicates are summed."""
+    the structure StencilGMG needs; None otherwise (`stencil_coefficients`)."""
     from .core import Field
 
     if len(op.key_to_field) != 1 or op.nrows != op.ncols:
@@ -676,44 +709,17 @@ def recognise_stencil(op):
     ndim = len(shape)
     if ndim > 3 or field.loc != "c" * ndim or any(s < 4 for s in shape):
         return None
-    want = [(0,) * ndim]
-    for i in range(ndim):
-        want += [tuple(-1 if j == i else 0 for j in range(ndim)), tuple(1 if j == i else 0 for j in range(ndim))]
-    # the arrays already lie back to back in the wanted order (the generated Jacobian kernel writes slices of one buffer
-    # in the order the operator reads them): a view, no copies
-    by_shift = dict()
-    for row0, nrows, kind, k, payload in op.blocks:
-        if kind == "stencil" and row0 == 0 and nrows == op.ncols and payload[2] == field.loc and tuple(payload[3]) == shape:
-            norm = tuple(((s + n // 2) % n) - n // 2 for s, n in zip(payload[1], shape))
-            if norm in by_shift:
-                by_shift = None
-                break
-            by_shift[norm] = payload[0]
-    if by_shift is not None and len(by_shift) == len(op.blocks) and sorted(by_shift) == sorted(want):
-        arrs = [by_shift[sft] for sft in want]
-        first, size = arrs[0], arrs[0].numel()
-        if all(a.is_contiguous() and a.dtype == first.dtype and a.untyped_storage().data_ptr() == first.untyped_storage().data_ptr()
-               and a.storage_offset() == first.storage_offset() + j * size for j, a in enumerate(arrs)):
-            return torch.empty(0, dtype=first.dtype, device=first.device).set_(
-                first.untyped_storage(), first.storage_offset(), (len(want),) + shape)
-    coeffs = torch.zeros((len(want),) + shape, dtype=op.dtype, device=op.device)
-    seen = set()
+    items = []
     for row0, nrows, kind, k, payload in op.blocks:
         if kind != "stencil" or row0 != 0 or nrows != op.ncols:
             return None
         coeff, shift, loc, vshape = payload
-        norm = tuple(((s + n // 2) % n) - n // 2 for s, n in zip(shift, shape))  # periodic roll: |shift| <= n / 2
-        if loc != field.loc or tuple(vshape) != shape or norm not in want:
+        if loc != field.loc or tuple(vshape) != shape:
             return None
-        slot = want.index(norm)
-        if slot in seen:
-            ops.axpy(coeffs[slot].view(-1), coeff.reshape(-1).contiguous(), 1.0)
-        else:
-            coeffs[slot].view(-1).copy_(coeff.reshape(-1))
-            seen.add(slot)
-    if 0 not in seen:
+        items.append((shift, coeff))
+    if not items:
         return None
-    return coeffs
+    return stencil_coefficients(items, shape, dtype=op.dtype, device=op.device)
 
 
 def recognise_poisson(op):

@@ -755,8 +755,11 @@ class SlabStencilGMG:
             x = y
         return self._smooth(comm, l, x, b)
 
-    def solve(self, comm, b_owned, tol=1e-10, maxiter=40):
-        """x (owned planes) with A x = b to |b - A x| <= tol |b| over all ranks; self.status: niter, residual, converged."""
+    def solve(self, comm, b_owned, tol=1e-10, maxiter=40, stall=False):
+        """x (owned planes) with A x = b to |b - A x| <= tol |b| over all ranks; self.status: niter, residual, converged.
+        stall=True: also stop where the cycles stopped gaining -- from the fourth cycle on, a residual above 0.98 of the
+        previous cycle's (the rule of gmg.StencilGMG.solve, counted in cycles done) -- and say so in status["stagnated"]
+        (below 1: the rounding floor of the working precision, not divergence)."""
         if self.mc is None:
             self.setup(comm)
         lv = self.mlv[0]
@@ -765,14 +768,17 @@ class SlabStencilGMG:
         self._halo_planes(comm, b, lv, 1)
         bb = float(comm.exchange("gather", (b_owned.to(torch.float64) ** 2).sum().reshape(1), None).sum())
         x = torch.zeros_like(b)
-        it, rel = 0, 1.0
+        it, rel, stagnated = 0, 1.0, False
         while it < maxiter:
             x = self._vcycle(comm, 0, x, b)
             it += 1
-            rel = float(np.sqrt(self._last_res2 / bb)) if bb > 0 else 0.0  # (of the cycle's pre-smoothed iterate)
+            prev, rel = rel, float(np.sqrt(self._last_res2 / bb)) if bb > 0 else 0.0  # (of the cycle's pre-smoothed iterate)
             if rel <= tol:
                 break
-        self.status = dict(niter=it, residual=rel, converged=rel <= tol, method="slab variable-coefficient gmg ({} slab levels{})".format(
+            if stall and it > 3 and rel >= 0.98 * prev:
+                stagnated = rel == rel and rel < 1.0  # (not: diverging; the same numbers, so the same branch, on every rank)
+                break
+        self.status = dict(niter=it, residual=rel, converged=rel <= tol, stagnated=stagnated, method="slab variable-coefficient gmg ({} slab levels{})".format(
             len(self.mlv), " + agglomerated {}".format(tuple(self.agg[0].shape[1:])) if self.agg else ""))
         return lv.owned(x).clone()
 
@@ -887,3 +893,123 @@ class SlabTracedLbfgs:
         self.unpack(x, run.x)
         run._x_synced = False  # the ghost planes of the unknowns are refreshed by whoever evaluates next
         return res
+
+
+def check_slab_newton(args, problem, state, axis=None, world=1):
+    """Raises NotImplementedError, with the reason, unless Newton on the slab decomposition covers this run: a 3-D grid cut
+    along axis 0, ONE unknown that is a plain cell-centred `Field`, a square (2 d + 1)-point Jacobian (decided from the
+    `jac_items` of the generated Jacobian kernel, traced on the host: no GPU, no compiler), no damping, `--linsolver`
+    multigrid or direct.  (Walls across the cut axis are checked on the coefficients, by every step: SlabTracedNewton.)"""
+    from .core import Field
+    from .stencil_codegen import _Codegen
+    from .stencil_jit import trace_outputs
+    from .stencil_trace import TraceUnsupported
+
+    domain = problem.domain
+    if domain.ndim != 3:
+        raise NotImplementedError("Newton on the slab decomposition: {}-D grid (3-D only)".format(domain.ndim))
+    if axis not in (None, 0):
+        raise NotImplementedError("Newton on the slab decomposition: cut along axis {} (axis 0 only)".format(axis))
+    fields = list(state.fields.items())
+    if len(fields) != 1:
+        raise NotImplementedError("Newton on the slab decomposition: {} unknowns ({}; one Field only)".format(
+            len(fields), ", ".join(k for k, _ in fields)))
+    key, field = fields[0]
+    if type(field) is not Field:
+        raise NotImplementedError("Newton on the slab decomposition: unknown '{}' is a {} (a plain Field only)".format(
+            key, type(field).__name__))
+    if field.loc != "ccc":
+        raise NotImplementedError("Newton on the slab decomposition: field '{}' at loc '{}' (cell-centred only)".format(
+            key, field.loc))
+    damp, dampdiag = getattr(args, "linsolver_damp", 0) or 0, getattr(args, "linsolver_dampdiag", 0) or 0
+    if damp or dampdiag:
+        raise NotImplementedError("Newton on the slab decomposition: damping (linsolver_damp={}, linsolver_dampdiag={})".format(
+            damp, dampdiag))
+    linsolver = getattr(args, "linsolver", "direct")
+    if linsolver not in ("multigrid", "direct"):
+        raise NotImplementedError("Newton on the slab decomposition: linsolver '{}' (multigrid, direct)".format(linsolver))
+    N = domain.cshape[0]
+    if N % world:
+        raise NotImplementedError("Newton on the slab decomposition: {} cells on axis 0 over {} ranks".format(N, world))
+    try:
+        tr, outs, raw, _, G = trace_outputs(problem, state)
+        cg = _Codegen(tr, outs, raw, G, state, slab=(0, N // world))
+        cg.want_jac = True
+        cg.source()
+    except TraceUnsupported as e:
+        raise NotImplementedError("Newton on the slab decomposition: no generated Jacobian kernel ({})".format(e))
+    if len(outs) != 1:
+        raise NotImplementedError("Newton on the slab decomposition: {} outputs (a square Jacobian has one)".format(len(outs)))
+    want = [(0, 0, 0)] + [tuple(s if j == i else 0 for j in range(3)) for i in range(3) for s in (-1, 1)]
+    for _, attr in cg.jac_items:
+        if attr is None:
+            continue
+        rkey, shift, loc = attr[0], tuple(int(v) for v in attr[1]), attr[2]
+        norm = tuple(((s + n // 2) % n) - n // 2 for s, n in zip(shift, G))
+        if rkey != key or loc != field.loc or norm not in want:
+            raise NotImplementedError("Newton on the slab decomposition: the Jacobian reads '{}' at shift {} loc '{}' "
+                                      "(a (2 d + 1)-point stencil only)".format(rkey, shift, loc))
+    if not any(attr is not None and not any(((s + n // 2) % n) - n // 2 for s, n in zip(attr[1], G))
+               for _, attr in cg.jac_items):
+        raise NotImplementedError("Newton on the slab decomposition: the Jacobian has no diagonal")
+
+
+class SlabTracedNewton:
+    """Newton (`util.optimize_newton`) on the slab decomposition of `slab_traced.SlabTracedAdam` (whose layout, unknowns and
+    exchanges it borrows; its kernels must carry `k_jac`: HipSlabKernels(..., jac=True)), for what `check_slab_newton`
+    admits.  One step: the ghost and wrap planes of u, `k_jac` on the owned cells -> the value r and the 7 coefficient
+    arrays of M (a view of the kernel's buffer), the walls across the cut ends checked, M d = r solved by `SlabStencilGMG`,
+    x <- x - d on the owned planes, and one forward evaluation (the loss of the new state: `run.last_terms`)."""
+
+    def __init__(self, run, linsolver="multigrid", tol=1e-10, maxiter=None):
+        self.run = run
+        if len(run.entries) != 1 or run.entries[0]["kind"] != "field" or run.axis != 0:
+            raise NotImplementedError("Newton on the slab decomposition: one Field cut along axis 0")
+        if not getattr(run.kern, "jac_items", None):
+            raise RuntimeError("SlabTracedNewton needs slab kernels generated with their Jacobian kernel (jac=True)")
+        # the tolerance rule of linsolver.solve (`direct`: to 1e-12) and the floor of gmg.StencilGMG.solve
+        tol = 1e-12 if linsolver == "direct" else tol
+        self.tol = max(tol, 50 * float(torch.finfo(run.dtype).eps))
+        self.maxiter = maxiter or 60
+        self.status = dict()
+        self._evaluated = False
+
+    def step(self, comm):
+        run = self.run
+        e = run.entries[0]
+        lv = e["levels"][0]
+        if not self._evaluated:  # (else the evaluation that ended the last step left u and the wrap planes of this state)
+            drive(run.evaluate_gen(), comm)
+        buf = run.kern.jacobian(run.u, *run.wrap_planes())
+        from .gmg import stencil_coefficients
+
+        items = [(attr[1], buf[j]) for j, (_, attr) in enumerate(run.kern.jac_items) if attr is not None]
+        r = buf[next(j for j, (_, attr) in enumerate(run.kern.jac_items) if attr is None)]
+        coeffs = stencil_coefficients(items, tuple(buf.shape[1:]), period=run.domain.cshape)
+        if coeffs is None:
+            raise NotImplementedError("Newton on the slab decomposition: the Jacobian is not a (2 d + 1)-point stencil")
+        # walls across the cut ends: nothing below the first plane of rank 0 and nothing above the last plane of the last
+        # rank may couple (a periodic cut axis needs the ring closure SlabStencilGMG does not have)
+        bad = torch.zeros(1, dtype=torch.float64, device=run.device)
+        if run.rank == 0:
+            bad += (coeffs[1, 0] != 0).sum().to(torch.float64)
+        if run.rank == run.world - 1:
+            bad += (coeffs[2, -1] != 0).sum().to(torch.float64)
+        if float(comm.exchange("gather", bad, None).sum()) > 0:
+            raise NotImplementedError("Newton on the slab decomposition: the operator couples across the ends of the cut "
+                                      "axis (periodic); walls only")
+        solver = SlabStencilGMG(coeffs if coeffs.is_contiguous() else coeffs.contiguous(), run.rank, run.world)
+        solver.setup(comm)
+        d = solver.solve(comm, r, tol=self.tol, maxiter=self.maxiter, stall=True)
+        st = solver.status
+        self.status = dict(niter=st["niter"], residual=st["residual"], converged=st["converged"], stagnated=st["stagnated"],
+                           method=st["method"])
+        # the single-GPU rule (linsolver.solve): converged, or stopped at the rounding floor well below |r|
+        if not (st["converged"] or (st["stagnated"] and st["residual"] <= 1e-3)):
+            raise RuntimeError("Newton on the slab decomposition: multigrid stopped at relative residual {:.3e} after {} "
+                               "cycles (tolerance {:.1e}); the step is not applied".format(st["residual"], st["niter"], self.tol))
+        hip_ops.axpy(lv.owned(e["x"][0]), d, -1.0)
+        run._x_synced = False
+        drive(run.evaluate_gen(), comm)  # the loss of the new state, and the sources of the next step
+        self._evaluated = True
+        return self.status

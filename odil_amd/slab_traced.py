@@ -105,10 +105,13 @@ class _Level:
 class HipSlabKernels:
     """The generated kernels of one rank (stencil_codegen in slab mode) and their buffers."""
 
-    def __init__(self, problem, state, axis, n, device):
+    def __init__(self, problem, state, axis, n, device, jac=False):
+        """jac: also generate `k_jac` (`jacobian`), in a library of its own -- the library of the gradient optimizers keeps
+        its source and cache key."""
         tr, outs, raw, self.names, Gshape = trace_outputs(problem, state)
         self.problem, self.tr, self.raw = problem, tr, raw
         cg = _Codegen(tr, outs, raw, Gshape, state, slab=(axis, n))
+        cg.want_jac = bool(jac)
         # outputs in parameter space (a weight regulariser): every rank evaluates them, redundantly, with the generated
         # kernel of param_expr.py AFTER the parameter gradients were summed over the ranks
         self.par_outputs = None
@@ -187,6 +190,10 @@ class HipSlabKernels:
             self.lib.jit_gather_all.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [
                 ctypes.c_double] * 4 + [ctypes.c_void_p, ctypes.c_void_p]
         self.param_groups = {key: (cg.pg_offset[key], [len(g) for g in groups]) for key, groups in cg.pgrads.items()}
+        self.jac_items = list(getattr(cg, "jac_items", None) or [])
+        if self.jac_items:
+            self.lib.jit_jac.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+            self.jac_buf = torch.empty((len(self.jac_items),) + tuple(cg.GL), dtype=dt, device=device)
 
     _host_value = TracedOperator._host_value  # host scalars (functions of problem.tracers): the single-GPU evaluator
 
@@ -218,6 +225,29 @@ class HipSlabKernels:
         rc = self.lib.jit_fwd(ctypes.byref(self.args), hip_ops.stream_ptr())
         if rc != 0:
             raise RuntimeError("traced slab kernel launch failed: hip error {}".format(rc))
+
+    def jacobian(self, srcs, wlo, whi):
+        """`k_jac` on the owned cells (one launch): the value of every output and d output / d read for every distinct
+        read, in the order of `self.jac_items` ((output, None) for a value, (output, read attr) for a derivative), as the
+        leading slices of ONE buffer of shape [len(jac_items), *owned shape] -- reused by the next call.  srcs / wlo /
+        whi as in `forward`: u after the halo exchange, the wrap planes across the ends of the decomposition."""
+        from ._lib import ptr
+
+        if not self.jac_items:
+            raise RuntimeError("these slab kernels were generated without their Jacobian kernel (jac=False)")
+        ptr(self.out)  # fails loudly on a CPU tensor: there is no CPU path
+        memo = dict()
+        for i, node in enumerate(self.cg.hs):
+            self.args.hsv[i] = float(self._host_value(node, memo))
+        for i, key in enumerate(self.src_keys):
+            self.args.src[i] = srcs[key].data_ptr()
+            self.args.wlo[i], self.args.whi[i] = wlo[key].data_ptr(), whi[key].data_ptr()
+        n = len(self.jac_items)
+        ptrs = (ctypes.c_void_p * n)(*[self.jac_buf[j].data_ptr() for j in range(n)])
+        rc = self.lib.jit_jac(ctypes.byref(self.args), ptrs, hip_ops.stream_ptr())
+        if rc != 0:
+            raise RuntimeError("traced slab Jacobian launch failed: hip error {}".format(rc))
+        return self.jac_buf
 
     fused_adam = True  # gather() can apply the optimizer's update to the planes whose gradient it completes
 
@@ -633,28 +663,12 @@ class SlabTracedAdam:
             if fac:
                 torch.mul(dst, fac[l], out=view(e["g"][l]))
 
-    # ---- one epoch -------------------------------------------------------------------------------------
-    def epoch_gen(self, timers=None, update=True):
-        """One Adam epoch as a generator that yields at its exchanges.  update=False: loss and gradient only (the
-        quasi-Newton driver of slab_solvers.py) -- the ghost planes of the unknowns are refreshed first (somebody else
-        changed the unknowns), no launch applies an update, and self.g is left complete on the owned planes, on the
-        replicated levels and on the parameters."""
+    def _sources_gen(self, refresh, tic, toc):
+        """What the generated kernels read, as a generator that yields at its exchanges: the inner ghost planes of the
+        unknowns (refresh=True, or the first time), the synthesised arrays u and the wrap planes across the ends."""
         rank, world, h = self.rank, self.world, self.h
         first, last = rank == 0, rank == world - 1
-        fused = self._fused if update else dict()
-
-        def tic(name):
-            if timers is None:
-                return None
-            a, b = timers.section(name)
-            a.record()
-            return b
-
-        def toc(b):
-            if b is not None:
-                b.record()
-
-        if not (update and self.redundant and self._x_synced):
+        if refresh or not self._x_synced:
             # the neighbours' boundary planes of the unknowns -> inner ghost planes: every epoch, or once at the start
             # when the ghost planes are updated redundantly afterwards
             b = tic("halo")
@@ -689,8 +703,43 @@ class SlabTracedAdam:
             if recv_hi is not None:
                 self._wrapbuf["hi"].copy_(recv_hi.reshape(-1))
             toc(b)
+
+    def wrap_planes(self):
+        """(wlo, whi): src key -> the wrap planes of u across the low / high end (filled by the last exchange)."""
+        return {k: w["lo"] for k, w in self.wrap.items()}, {k: w["hi"] for k, w in self.wrap.items()}
+
+    def evaluate_gen(self):
+        """The loss terms of the current unknowns (forward kernel only, no gradient), as a generator that yields at its
+        exchanges; afterwards the ghost planes, u and the wrap planes hold this state (what `HipSlabKernels.jacobian`
+        reads)."""
+        nothing = lambda name: None
+        yield from self._sources_gen(True, nothing, nothing)
+        self.kern.forward(self.u, *self.wrap_planes())
+
+    # ---- one epoch -------------------------------------------------------------------------------------
+    def epoch_gen(self, timers=None, update=True):
+        """One Adam epoch as a generator that yields at its exchanges.  update=False: loss and gradient only (the
+        quasi-Newton driver of slab_solvers.py) -- the ghost planes of the unknowns are refreshed first (somebody else
+        changed the unknowns), no launch applies an update, and self.g is left complete on the owned planes, on the
+        replicated levels and on the parameters."""
+        rank, world, h = self.rank, self.world, self.h
+        first, last = rank == 0, rank == world - 1
+        fused = self._fused if update else dict()
+
+        def tic(name):
+            if timers is None:
+                return None
+            a, b = timers.section(name)
+            a.record()
+            return b
+
+        def toc(b):
+            if b is not None:
+                b.record()
+
+        yield from self._sources_gen(not (update and self.redundant and self._x_synced), tic, toc)
         b = tic("forward")
-        self.kern.forward(self.u, {k: w["lo"] for k, w in self.wrap.items()}, {k: w["hi"] for k, w in self.wrap.items()})
+        self.kern.forward(self.u, *self.wrap_planes())
         toc(b)
         t = self.npdt(self.t + 1)
         alpha = self.lr * np.sqrt(1 - self.b2**t) / (1 - self.b1**t)
@@ -830,7 +879,8 @@ def optimize_slab(args, problem, state, callback=None, axis=None):
     """`odil.util.optimize(args, "adam", ...)` for a run started with one process per GPU (e.g. `python -m
     torch.distributed.run --nproc-per-node 8 examples/velocity_from_tracer/veltracer3d.py --slab 1`): every rank
     builds the same GLOBAL problem, owns a slab of it (this module) and runs `args.epochs` Adam epochs (or, with
-    `--optimizer lbfgsb`, that many L-BFGS-B iterations: slab_solvers.SlabTracedLbfgs); the loss
+    `--optimizer lbfgsb`, that many L-BFGS-B iterations: slab_solvers.SlabTracedLbfgs; with `--optimizer newton`, that many
+    Newton steps of one cell-centred Field on a 3-D grid cut along axis 0: slab_solvers.SlabTracedNewton); the loss
     terms are all-reduced and logged by rank 0 every `args.report_every` epochs (the quantity the reference's
     callback reports, src/odil/util.py:337-467).  `callback(run, epoch, terms)` is called on every rank at those
     epochs.  Returns the rank's SlabTracedAdam (its `owned_arrays()` are the rank's part of the solution; dump
@@ -841,6 +891,13 @@ def optimize_slab(args, problem, state, callback=None, axis=None):
     rank, world, comm = init_distributed()
     kw = {name: getattr(args, "adam_" + name) for name in ("beta_1", "beta_2", "epsilon")
           if getattr(args, "adam_" + name, None) is not None}
+    optname = getattr(args, "optimizer", "adam") or "adam"
+    if optname == "newton":
+        # refused on every rank alike, before anything is built or changed (slab_solvers.check_slab_newton)
+        from .slab_solvers import check_slab_newton
+
+        check_slab_newton(args, problem, state, axis=axis, world=world)
+        kw["kernels"] = lambda *a: HipSlabKernels(*a, jac=True)
     run = SlabTracedAdam(problem, state, rank, world, axis=axis, lr=args.lr, **kw)
     every = getattr(args, "report_every", 0) or 0
     start = getattr(args, "epoch_start", 0)
@@ -853,7 +910,20 @@ def optimize_slab(args, problem, state, callback=None, axis=None):
         if callback is not None:
             callback(run, epoch, terms)
 
-    optname = getattr(args, "optimizer", "adam") or "adam"
+    if optname == "newton":
+        # Newton on the slabs (slab_solvers.SlabTracedNewton): an "epoch" is a step, its loss that of the state after it
+        # (util.optimize_newton)
+        from .slab_solvers import SlabTracedNewton
+
+        newton = SlabTracedNewton(run, linsolver=getattr(args, "linsolver", "direct"),
+                                  tol=getattr(args, "linsolver_tol", 1e-10), maxiter=getattr(args, "linsolver_maxiter", None))
+        for epoch in range(start + 1, args.epochs + 1):
+            status = newton.step(comm)
+            if getattr(args, "linsolver_verbose", 0) and rank == 0:
+                printlog(status)
+            if every and (epoch % every == 0 or epoch == args.epochs):
+                report(epoch)
+        return run
     if optname == "lbfgsb":
         # L-BFGS-B on the slabs (slab_solvers.SlabTracedLbfgs): an "epoch" is an iteration, as in the undivided driver
         from .slab_solvers import SlabTracedLbfgs

@@ -1655,7 +1655,9 @@ class _Codegen:
         read (key, shift, loc), i.e. the per-shift coefficient arrays of the Jacobian -- from the SYMBOLIC derivative of the
         traced DAG (stencil_grad.GradBuilder with the unit seed), instead of one autograd pass per output over a graph
         of torch elementwise kernels.  Operators whose outputs are windows of the grid, or that differentiate through
-        parameter arrays (dense Jacobian columns), keep the autograd route (TraceUnsupported)."""
+        parameter arrays (dense Jacobian columns), keep the autograd route (TraceUnsupported).  Slab mode: the rank's owned
+        cells only, u read from the ghost-extended array and the wrap planes, one owned-shape array per item
+        (slab_traced.HipSlabKernels.jacobian)."""
         tr = self.tr
         items, self.jac_items = [], []  # jac_items[j] = (output position, None for its value | the read's attr)
         for k, o in enumerate(self.outputs):
@@ -1679,7 +1681,7 @@ class _Codegen:
         saved = dict(self.gather_reads_sources)
         S.append("struct JacP {{ T* p[{}]; }};".format(len(items)))
         self.jac_blocks = self._gather_kernel(S, "k_jac", items, "const JacP jp, const AdamP ad", lambda k: "jp.p[{}]".format(k),
-                                              lambda k: "ad")
+                                              lambda k: "ad", owned=self.slab is not None)
         self.gather_reads_sources = saved  # (bookkeeping of the optimizer fusion: the Jacobian kernel is not a gather)
 
     def _standard_gathers(self, S):
@@ -2343,14 +2345,16 @@ class _Codegen:
         self.gather_blocks[gi] = self._gather_kernel(S, "k_gat_{}".format(gi), [(key, root)],
                                                      "T* __restrict__ g, const AdamP ad", lambda k: "g", lambda k: "ad")
 
-    def _gather_kernel(self, S, name, items, params, G_, AD_):
+    def _gather_kernel(self, S, name, items, params, G_, AD_, owned=False):
         """A pointwise kernel over the gradient expressions of `items` = [(field key, expression)] (one thread per
         point, or per four points of the last axis): common sub-expressions and loads of the fields' expressions are
         shared, every field's gradient is stored, and the optimizer's update applied, by the lane that holds it.
         Slab mode: threads cover planes -2 .. n + 2 of the sharded axis; planes that exist in the rank's ghost-extended
         gradient array are stored there (ghost planes: what this rank's cells contribute to the neighbour's), planes
         beyond an end of the decomposition that a periodic read reached go to the wrap buffers (as the legacy slab
-        gather).  Returns the number of workgroups to launch."""
+        gather).  owned=True (slab mode, `k_jac`): threads cover the OWNED planes 0 .. n only, reads go through the same
+        ghost / wrap addressing, and every item is stored into an array of the owned shape; no optimizer update.
+        Returns the number of workgroups to launch."""
         self.vw = self.vw_gat
         vw, last = self.vw, self.ndim - 1
         saved = (self.order, self.lines, self.pre, self.loads, self.groups)
@@ -2377,7 +2381,7 @@ class _Codegen:
         names = ["i{}".format(d) for d in range(self.ndim)]
         if self.slab is not None:
             ax, nloc = self.slab
-            shape[ax] = nloc + 4
+            shape[ax] = nloc if owned else nloc + 4
             names[ax] = "jx"
         threads = int(np.prod(shape)) // vw
         if threads >= 2**31 - 1024:
@@ -2392,7 +2396,10 @@ class _Codegen:
         self._chunk_remap(S, shape, vw, flat + "r", flat)
         self._index_prologue(S, shape, names, vw, flat)
         nblocks = (threads + 255) // 256
-        if self.slab is not None:
+        if self.slab is not None and owned:
+            S.append("  const int jo = jx;")
+            S.append("  const int i{}g = jo + a.off;".format(ax))
+        elif self.slab is not None:
             S.append("  const int jo = jx - 2;")  # owned-relative position on the sharded axis
             S.append("  const int i{}g = wrap(jo + a.off, {});".format(ax, self.G[ax]))
         S.extend(pre)
@@ -2434,6 +2441,12 @@ class _Codegen:
             ext = [extent if d == ax else self.G[d] for d in range(self.ndim)]
             return self._offset(full, ext)
 
+        if owned:
+            S.append("  const int o = {};".format(offset("jo", nloc)))
+            for k in range(len(items)):
+                S.append("  " + put.format(dst=G_(k), o="o", k=k))
+            S.append("}")
+            return nblocks
         S.append("  const int jl = jo + a.lo;")
         # owned planes a.alo <= jo < a.ahi have their whole gradient here (no neighbour's cell reads them): the optimizer's
         # update is applied on the spot; the planes next to an interface wait for the halo sum (slab_traced.py)
