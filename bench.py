@@ -9,7 +9,15 @@ adjoint -> P^T chain -> Adam update.  Metric = prod(cshape) * steps / wall
 reference solution, discrete rhs, zero initial state; poisson.py:21-24,71-86,264-266).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4a|5|1|2|3|3b|4b|5b] [--N 512] [--ndim 3]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does only what its headline figure needs: set-up, spin-up, the W warm-up steps, the K timed steps,
+--dump-outputs if asked, and the JSON line (roofline and kernel_ms from the HIP events of the timed steps themselves).
+--full adds everything else the benchmark measures or checks: the CPU baseline before the GPU is touched (unless
+--no_cpu_baseline), the per-kernel times of a few extra epochs after the timed ones, the value-level comparison of the
+first warm-up epochs with the C oracle's fixture and the multi-GPU loss against the emulated-rank table (`parity_ok`; a
+mismatch fails the run), and at the headline size on one GPU the short runs of the other configs (unless
+--no_other_configs).  The timed steps themselves are the same with and without it.
 
 --dump-outputs DIR (config 4a on one GPU; bench_outputs/ is git-ignored): after the timed steps, what the timed
 optimize_grad call returned after its last step is written as DIR/<name>.npy (dump_outputs below), so that two builds
@@ -50,7 +58,9 @@ def parse_args():
     p.add_argument("--N", type=int, default=512)
     p.add_argument("--ndim", type=int, default=3)
     p.add_argument("--dtype", type=str, default="f64", choices=["f64", "f32"])
-    p.add_argument("--no_cpu_baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also the CPU baseline, the per-kernel epochs, the checks against the references and the other configs")
+    p.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--cpu_N", type=int, default=512, help="grid size of the 1-core CPU-baseline sample (512 = the headline's own: ~5 s "
                    "per epoch of the C port after ~1 min of untimed first-touch page faults of its 8.6 GB)")
     p.add_argument("--cpu_N_all", type=int, default=128, help="grid size per core of the all-cores CPU-baseline leg")
@@ -58,7 +68,7 @@ def parse_args():
     p.add_argument("--scale", type=float, default=1.0, help="shrinks the grids of the non-default configs (smoke runs)")
     p.add_argument("--spinup_ms", type=float, default=80.0, help="untimed read-modify-write spin-up before the warm-up steps")
     p.add_argument("--no_other_configs", action="store_true",
-                   help="skip the short runs of configs 3b, 5 (one rank) and 4b after the timed region")
+                   help="with --full: skip the short runs of the other configs after the timed region")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="write what the timed path returned after its last timed step as DIR/<name>.npy (config 4a, one GPU)")
     args = p.parse_args()
@@ -185,8 +195,8 @@ class Timers:
     """HIP-event pairs per kernel family, recorded on the stream the kernels run on.  `only`: the sections that are
     really timed (the others get no events).  Every recorded event is a barrier packet between two launches: with all
     sections of the epoch bracketed, the 512^3 epoch measured 3.21 instead of 2.83 ms (tools/host_enqueue.py), so
-    the TIMED region brackets the dominant launch only and the other sections are measured in a few extra epochs
-    after it."""
+    the TIMED region brackets the dominant launch only and the other sections are measured (--full) in a few extra
+    epochs after it."""
 
     def __init__(self, only=None, prealloc=0):
         """prealloc: event pairs created AND recorded once before they are needed.  The runtime grows its pool of
@@ -402,7 +412,7 @@ def run_poisson(args, rank, world, dev, comm, barrier):
     oracle = None
     for k in range(args.warmup):
         step()
-        if world == 1:  # the run starts from the zero state: its first epochs ARE the epochs of the value-level fixture
+        if args.full and world == 1:  # the run starts from the zero state: its first epochs ARE the epochs of the value-level fixture
             oracle = oracle_values_check(run, k + 1, oracle, (ndim, N, args.dtype))
     dumped = None
     if world == 1:
@@ -418,15 +428,17 @@ def run_poisson(args, rank, world, dev, comm, barrier):
         elapsed = time.perf_counter() - t0
     gc.enable()
     loss = run.last_loss(comm) if world > 1 else run.last_loss()
-    every = Timers(prealloc=8 * 5)  # the other sections: a few epochs outside the timed region (events primed: see Timers)
-    if world == 1:
-        run.timed(5, every, barrier)
-    else:
-        for _ in range(5):
-            step(every)
-    barrier()
+    kt = dict()
+    if args.full:
+        every = Timers(prealloc=8 * 5)  # the other sections: a few epochs outside the timed region (events primed: see Timers)
+        if world == 1:
+            run.timed(5, every, barrier)
+        else:
+            for _ in range(5):
+                step(every)
+        barrier()
+        kt = every.summary()
     wordsize = 8 if dtype == torch.float64 else 4
-    kt = every.summary()
     kt.update(timers.summary())
     if os.environ.get("ODIL_BENCH_DEBUG") and rank == 0:  # the dominant launch epoch by epoch (clock ramp, outliers)
         for name, pairs in timers.pairs.items():
@@ -484,7 +496,7 @@ def hat_reference_host(N):
 
 
 def oracle_values_check(run, epoch, acc, key):
-    """VALUE-level parity inside the bench run (N = 1, headline size only): the losses of the first epochs (untimed warm-up;
+    """--full: VALUE-level parity inside the bench run (N = 1, headline size only): the losses of the first epochs (untimed warm-up;
     zero start) and 64 sampled unknowns per level after the last recorded epoch against tests/golden/fullsize_poisson_N512.npz
     -- three epochs of the plain-C oracle at 512^3 (tests/golden/make_golden_fullsize.py; the oracle itself is NOT run
     here).  Inputs are the fixture's bit for bit (checked on its sampled entries).  Tolerances: loss 1e-10; unknowns 1e-6
@@ -587,11 +599,13 @@ def run_tracer(args, rank, world, dev, comm, barrier):
     elapsed = time.perf_counter() - t0
     gc.enable()
     loss = run.last_loss(comm)
-    every = Timers(prealloc=8 * 2)
-    for _ in range(2):
-        run.epoch(comm, every)
-    barrier()
-    kt = every.summary()
+    kt = dict()
+    if args.full:  # the other sections: two epochs outside the timed region
+        every = Timers(prealloc=8 * 2)
+        for _ in range(2):
+            run.epoch(comm, every)
+        barrier()
+        kt = every.summary()
     kt.update(timers.summary())
     nsrc, ncot = len(run.kern.src_keys), len(run.kern.cot)
     moved = float(nsrc + ncot) * run.local_cells * 4  # reads each field once (neighbours are cache hits), writes the cotangents
@@ -630,7 +644,7 @@ def pmc_traffic(path):
 
 
 def other_configs(args, dev):
-    """After the timed region of the default run (N = 1 only, outside every timed window): a few epochs each of the
+    """--full, after the timed region of the default run (N = 1 only, outside every timed window): a few epochs each of the
     other single-GPU BASELINE workloads, so that the driver's record carries them -- 3b heat inverse 256 x 512^2
     (traced operator, Adam), 5 the tracer workload's per-rank slab (128, 32, 256, 256) as one rank, 4b one Newton step
     of Poisson 512^3 with the geometric-multigrid solve.  ms_per_step by HIP events around the steps after a warm-up
@@ -860,7 +874,7 @@ def run_api(args, dev):
 
 
 def check_parity(args, res, world):
-    """The run checks ITSELF: the (all-reduced) loss after warmup + steps epochs against profiles/expected_losses.json --
+    """--full: the run checks ITSELF: the (all-reduced) loss after warmup + steps epochs against profiles/expected_losses.json --
     the same deterministic workload with its ranks emulated on one GPU (tools/expected_losses.py: device copies instead
     of RCCL messages, the same kernels).  A wrong halo, a reused receive buffer or a missed wait on the first real
     multi-GPU run changes the trajectory and fails here instead of printing a plausible number.  None: no reference for
@@ -892,7 +906,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     cpu = None
-    if not args.no_cpu_baseline and world == 1:  # child processes: started before this process initialises the GPU
+    if args.full and not args.no_cpu_baseline and world == 1:  # child processes: started before this process initialises the GPU
         cpu = cpu_baseline(args.ndim if args.config == "4a" else 3, args.cpu_N, args.cpu_N_all, args.cpu_budget)
     from odil_amd.slab import LocalComm
 
@@ -929,7 +943,7 @@ def main():
     others = None
     if args.config == "4a":
         res = run_poisson(args, rank, world, dev, comm, barrier)
-        if world == 1 and not args.no_other_configs and (args.ndim, args.N) == (3, 512):
+        if args.full and world == 1 and not args.no_other_configs and (args.ndim, args.N) == (3, 512):
             res_run = res.pop("run", None)
             del res_run
             torch.cuda.empty_cache()
@@ -967,16 +981,18 @@ def main():
             }
         out["kernel_ms"] = res["kernel_ms"]
         out["loss_after"] = res["loss"]
-        parity = check_parity(args, res, world)
+        out["full"] = args.full
+        parity = check_parity(args, res, world) if args.full else None
         oracle = res.get("oracle")
         if oracle is not None:
             oracle.pop("_fx", None)
-        # N = 1 at the headline size: parity_ok is the VALUE-level comparison with the C oracle's epochs (the emulated-rank
-        # table, produced by these same kernels, stays as the trajectory check of N > 1 and is reported beside it)
-        ok = [p["ok"] for p in (parity, oracle) if p is not None and p.get("ok") is not None and (p is not oracle or "epochs" in p)]
-        out["parity_ok"] = all(ok) if ok else None
-        out["parity"] = parity
-        out["parity_oracle"] = oracle
+        if args.full:
+            # N = 1 at the headline size: parity_ok is the VALUE-level comparison with the C oracle's epochs (the emulated-rank
+            # table, produced by these same kernels, stays as the trajectory check of N > 1 and is reported beside it)
+            ok = [p["ok"] for p in (parity, oracle) if p is not None and p.get("ok") is not None and (p is not oracle or "epochs" in p)]
+            out["parity_ok"] = all(ok) if ok else None
+            out["parity"] = parity
+            out["parity_oracle"] = oracle
         if cpu is not None:
             out["cpu_baseline"] = cpu
         if others is not None:

@@ -111,3 +111,21 @@ def test_steps_below_one_and_dumps_outside_the_headline_run_are_refused(monkeypa
         with pytest.raises(SystemExit) as e:
             bench.parse_args()
         assert e.value.code == 2
+
+
+def test_plain_run_starts_no_cpu_baseline_and_full_does(monkeypatch):
+    """A plain run goes straight to the GPU part; --full times the CPU baseline first (unless --no_cpu_baseline).
+    The GPU part is cut short here: the device is reported absent."""
+    started = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a: started.append(a) or {})
+    monkeypatch.setattr(bench.torch.cuda, "is_available", lambda: False)
+    for key in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(key, raising=False)
+    for argv, want in (([], []), (["--full", "--no_cpu_baseline"], []), (["--full"], [(3, 512, 128, 10.0)])):
+        started.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"] + argv)
+        with pytest.raises(AssertionError, match="needs a GPU"):
+            bench.main()
+        assert started == want, argv
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse_args().full is False

@@ -91,7 +91,7 @@ def test_bench_two_ranks_over_torch_distributed_on_one_gpu(tmp_path, launcher):
 
 
 def test_bench_single_gpu_json_contract():
-    """`python bench.py` at N = 1 on a small grid: ONE JSON line with every key of the driver's
+    """`python bench.py --full` at N = 1 on a small grid: ONE JSON line with every key of the driver's
     contract, the roofline object of the dominant kernel and the CPU baseline."""
     import json
     import os
@@ -99,7 +99,7 @@ def test_bench_single_gpu_json_contract():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--N", "64",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--N", "64",
                           "--cpu_N", "16", "--cpu_N_all", "16", "--cpu_budget", "1"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -119,6 +119,33 @@ def test_bench_single_gpu_json_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["unit"] == d["unit"] and c["sample"]
     assert c["all_cores"]["cores"] >= 1 and c["all_cores"]["value"] > 0 and c["all_cores"]["sample"]
+    assert d["full"] is True and "parity_ok" in d
+    # the sections outside the timed launch come from the extra epochs after the timed ones
+    assert d["kernel_ms"]["residual"] > 0
+
+
+def test_bench_plain_run_prints_the_headline_only():
+    """`python bench.py` without --full: the headline figure and the roofline of its own timed steps, and nothing of
+    what --full adds (no CPU baseline, no reference checks, no other configs, no extra per-kernel epochs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--N", "64"],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2
+    assert d["unit"] == "grid-point-updates/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 64**3 * 4 / (d["ms_per_step"] * 4e-3)) <= 1e-6 * d["value"]
+    for key in ("cpu_baseline", "other_configs", "parity_ok", "parity", "parity_oracle"):
+        assert key not in d, key
+    assert set(d["kernel_ms"]) <= {"adjoint_transpose", "adjoint", "adam"} and d["kernel_ms"]
+    assert d["roofline"]["bound"] == "hbm" and d["roofline"]["avg_launch_ms"] > 0 and np.isfinite(d["loss_after"])
 
 
 # ---- traced operators (odil_amd/slab_traced.py): ranks emulated on one GPU == the undivided HIP path ------------

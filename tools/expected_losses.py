@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Loss after every epoch of the two bench.py workloads at N = 1, 2, 4, 8 ranks, produced with the ranks EMULATED on one
 GPU (odil_amd.slab.run_lockstep: device copies instead of RCCL messages; the inputs are deterministic and so are the
-kernels).  `bench.py --gpus N` compares the all-reduced loss of its real multi-process run with this table and reports
+kernels).  `bench.py --full --gpus N` compares the all-reduced loss of its real multi-process run with this table and reports
 `parity_ok`: a wrong halo on the first RCCL run cannot pass as a plausible number.
 
     python3 tools/expected_losses.py [epochs] > profiles/expected_losses.json       (on a GPU box)

@@ -10,7 +10,7 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 for cfg in $CFGS; do
   for val in ${VALS:-1 0 1 0}; do
-    env $VAR=$val timeout 400 python bench.py --config $cfg --no_cpu_baseline --steps 20 --warmup 3 2>/dev/null | python -c "
+    env $VAR=$val timeout 400 python bench.py --full --config $cfg --no_cpu_baseline --steps 20 --warmup 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('cfg $cfg $VAR=$val', round(d['ms_per_step'],3), d.get('kernel_ms'))"
   done
