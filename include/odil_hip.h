@@ -556,6 +556,17 @@ int odil_bmg_galerkin_f64(const int64_t* fdesc, const int64_t* cdesc, const int*
 int odil_bmg_galerkin_f32(const int64_t* fdesc, const int64_t* cdesc, const int* code, const float* fcoef,
                           const int64_t* ftable, const int64_t* ctable, int nce, int64_t total, float* ccoef,
                           void* stream);
+/* The coarsest level factorised on the device (gmg.NormalGMG(coarse="device"), float64 only, n <= 8192 unknowns; np: n
+ * rounded up to a multiple of 64).  coarse_dense: rows / columns [0, np) of out (row stride lda >= np) become the dense
+ * symmetric matrix 0.5 (A + A^T) of the level, zero beyond n.  coarse_chol: work is np x 2 np (row stride 2 np) with the
+ * matrix of coarse_dense (lda = 2 np) in its left half; blocked Cholesky on [A | I] (f64 MFMA trailing updates), then
+ * inv (n x n, row stride n) = the symmetric generalised inverse.  A Schur-complement pivot <= tol_rel * max_i A_ii is
+ * dropped (its row and column of inv are zero); drops: DEVICE int[np / 64], the dropped pivots of every panel; thr:
+ * DEVICE, one double (scratch).  work is overwritten.  No atomics: bit-reproducible. */
+int odil_bmg_coarse_dense_f64(const double* coef, const int64_t* table, const int64_t* desc, int64_t np, int64_t lda,
+                              double* out, void* stream);
+int odil_bmg_coarse_chol_f64(double* work, int64_t n, int64_t np, double tol_rel, double* thr, int* drops,
+                             double* inv, void* stream);
 
 #ifdef __cplusplus
 }

@@ -82,12 +82,18 @@ _SIGNATURES = {
     "bmg_galerkin": [_I64P, _I64P, _P, _P, _P, _P, c_int, c_int64, _P, _P],
 }
 
+# float64-only entry points (no _f32 twin): name -> argument types
+_SIGNATURES_F64 = {
+    "bmg_coarse_dense": [_P, _P, _I64P, c_int64, c_int64, _P, _P],
+    "bmg_coarse_chol": [_P, c_int64, c_int64, c_double, _P, _P, _P, _P],
+}
+
 EXPORTED = [
     "odil_last_error", "odil_version", "odil_device_count", "odil_reduce_workspace_bytes", "odil_dots_workspace_bytes",
     "odil_dense_block_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy", "odil_poisson_small_epochs_resident",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
-]
+] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
 
 _lib = None
 
@@ -126,6 +132,10 @@ def load():
             fn = getattr(lib, "odil_{}_{}".format(name, suffix))
             fn.restype = c_int
             fn.argtypes = [real if a is _R else a for a in sig]
+    for name, sig in _SIGNATURES_F64.items():
+        fn = getattr(lib, "odil_{}_f64".format(name))
+        fn.restype = c_int
+        fn.argtypes = sig
     _lib = lib
     return lib
 

@@ -951,7 +951,9 @@ class NormalGMG:
                      (cells: linear 3/4, 1/4; nodes: coarse node on every second fine node, linear)
       sweeps         Chebyshev-weighted point Jacobi over all fields, one launch each (odil_bmg_apply mode 2 / 3)
       transfers      all fields in one launch (odil_bmg_transfer)
-      coarsest       a dense pseudo-inverse applied by odil_lincomb
+      coarsest       a dense pseudo-inverse applied by odil_lincomb: from np.linalg.eigh on the host (coarse="host", the
+                     default) or from a blocked Cholesky on the device (coarse="device": odil_bmg_coarse_dense /
+                     odil_bmg_coarse_chol, nothing read back)
 
     The cycle starts from zero and its post-sweeps repeat the pre-sweeps' weights in reverse order: the preconditioner
     is symmetric (positive definite where A is), as the outer CG needs.  Build with `NormalGMG.create`, which returns
@@ -965,7 +967,7 @@ class NormalGMG:
     smooth_ratio = 16.0
 
     @classmethod
-    def create(cls, op, damp=0.0, dampdiag=0.0):
+    def create(cls, op, damp=0.0, dampdiag=0.0, coarse="host"):
         from .util import printlog
 
         pat = normal_pattern(op)
@@ -980,9 +982,12 @@ class NormalGMG:
             printlog("odil_amd: multigrid on the normal equations: the extents {} do not coarsen to {} unknowns; "
                      "using CG on the normal equations".format(tuple(op.domain.cshape), COARSEST_MAX_UNKNOWNS))
             return None
-        return cls(op, pat, plan, damp, dampdiag)
+        return cls(op, pat, plan, damp, dampdiag, coarse=coarse)
 
-    def __init__(self, op, pattern, plan, damp=0.0, dampdiag=0.0):
+    def __init__(self, op, pattern, plan, damp=0.0, dampdiag=0.0, coarse="host"):
+        if coarse not in ("host", "device"):
+            raise ValueError("NormalGMG: coarse must be 'host' or 'device', got {!r}".format(coarse))
+        self.coarse = coarse
         terms, self.keys, shape0 = pattern
         self.shapes, self.codes = plan
         assert [tuple(s) for s in self.shapes[0]] == [tuple(s) for s in shape0]
@@ -1036,8 +1041,9 @@ class NormalGMG:
             hi = float((rowabs * dinv).max())
             self.dinv.append(dinv)
             self.weights.append(chebyshev_weights(self.nu, hi / self.smooth_ratio, hi))
-        # --- coarsest: dense pseudo-inverse (set-up on the host: at most COARSEST_MAX_UNKNOWNS unknowns)
-        self.coarse_inv = self._coarse_inverse()
+        # --- coarsest: dense pseudo-inverse (at most COARSEST_MAX_UNKNOWNS unknowns)
+        self.coarse_drops = None
+        self.coarse_inv = self._coarse_inverse() if coarse == "host" else self._coarse_inverse_device()
         n = [self.offs[l][-1] for l in range(self.nlvl)]
         self.x = [torch.zeros(v, dtype=dt, device=dev) for v in n]
         self.y = [torch.zeros(v, dtype=dt, device=dev) for v in n]
@@ -1088,6 +1094,24 @@ class NormalGMG:
         keep = w > 1e-13 * max(float(np.abs(w).max()), 1e-300)
         inv = (v[:, keep] / w[keep]) @ v[:, keep].T
         return torch.as_tensor(inv, dtype=self.dtype).to(self.device).contiguous()
+
+    def _coarse_inverse_device(self):
+        """The coarsest level's generalised inverse from a blocked Cholesky on the device (csrc/coarse_chol.hip), float64
+        whatever the level's precision.  A pivot <= 1e-13 max_i A_ii (the host route's eigenvalue cut) drops its row and
+        column: B = E_S A_SS^-1 E_S^T over the kept pivots S.  B is symmetric positive semidefinite, so the cycle stays
+        symmetric and positive semidefinite.  The outer CG's right-hand side M^T r lies in the range of A, so do its
+        residuals, and so do their restrictions on a coarse null vector v_c that prolongs to a null vector of A (a
+        constant pressure prolongs to a constant: (P v_c)^T r = 0).  There A B b = b: for a one-dimensional nullspace
+        v with a dropped pivot d (v_d != 0, A_SS nonsingular), A_dS A_SS^-1 b_S = -v_S^T b_S / v_d = b_d as v^T b = 0.  self.coarse_drops: the dropped pivots per panel
+        (device; read back only by `dropped_pivots`)."""
+        lvl = self.nlvl - 1
+        coef = self.coef[lvl] if self.coef[lvl].dtype == torch.float64 else self.coef[lvl].double()
+        inv, self.coarse_drops = ops.bmg_coarse_inverse(coef, self.table[lvl], self.desc[lvl], self.offs[lvl][-1])
+        return inv if self.dtype == torch.float64 else inv.to(self.dtype)
+
+    def dropped_pivots(self):
+        """Pivots the device factorisation of the coarsest level dropped (one read-back); None for coarse="host"."""
+        return None if self.coarse_drops is None else int(self.coarse_drops.sum())
 
     def apply(self, lvl, x, out=None):
         """out = A_lvl x."""

@@ -28,14 +28,15 @@ def _dot(a, b):
 
 
 def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=None, x0=None, check_every=25, b=None,
-              precond=None):
+              precond=None, stall=0):
     """Solves (M^T M + damp^2 I + dampdiag^2 diag(M^T M)) x = M^T rhs (or = b when `b` is given) by
     Jacobi-preconditioned CG.  precond: callable (r, out) writing z = B r into out instead of the Jacobi step (B symmetric
     positive definite: gmg.NormalGMG.precondition).
 
     The iteration runs without host synchronisation: the scalars <r, z>, <p, A p>, alpha and beta
     stay 0-d device tensors (deterministic odil_dots; updates through odil_lincomb with device
-    coefficients) and the residual norm is read back only every `check_every` iterations."""
+    coefficients) and the residual norm is read back only every `check_every` iterations.  stall > 0: also stop when
+    that many read-backs in a row brought no new smallest residual (status["stagnated"] = True)."""
     n = op.shape[1]
     dtype, device = op.dtype, op.device
     b = op.rmatvec(rhs) if b is None else b
@@ -79,6 +80,7 @@ def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=N
     res = float(_dot(r, r)) ** 0.5
     coef = torch.ones(3, dtype=dtype, device=device)  # (beta, 1) on rows 0:2, or (1, beta) on rows 1:3
     ok = res > tol * max(bnorm, 1e-300)
+    best, since = res, 0
     while ok and niter < maxiter:
         for _ in range(min(check_every, maxiter - niter)):
             ap = apply_a(p)
@@ -105,6 +107,12 @@ def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=N
             niter += 1
         res = float(_dot(r, r)) ** 0.5
         ok = res > tol * max(bnorm, 1e-300) and float(pap) > 0 and res == res
+        if stall and ok:
+            best, since = (res, 0) if res < best else (best, since + 1)
+            if since >= stall:
+                ok = False
+                if status is not None:
+                    status["stagnated"] = True
     if status is not None:
         status["residual"] = res
         status["niter"] = niter
@@ -523,6 +531,10 @@ def solve(matr, rhs, args, status=None, linsolver="direct", consume=False):
         if x is not None:
             return x
     if linsolver in ("direct", "directsq"):
+        if matr.ncols > DENSE_MAX_UNKNOWNS:
+            x = direct_multigrid(matr, rhs, damp, dampdiag, maxiter, status)
+            if x is not None:
+                return x
         return cg_normal(matr, rhs, damp, dampdiag, tol=1e-14, maxiter=maxiter, status=status)
     if linsolver == "multigrid":
         x = normal_multigrid(matr, rhs, damp, dampdiag, tol, maxiter, status)
@@ -559,6 +571,64 @@ def normal_multigrid(matr, rhs, damp=0.0, dampdiag=0.0, tol=1e-10, maxiter=None,
 
 
 NORMAL_GMG_CHECK_EVERY = 2  # V-cycle-preconditioned CG: the residual norm is read back every second iteration
+DIRECT_GMG_TOL = 1e-12  # `direct` by multigrid: relative residual of the normal equations (as PoissonGMG / StencilGMG)
+DIRECT_GMG_FLOOR = 1e-3  # ... or stagnation at the rounding floor below this fraction of |M^T r|
+DIRECT_GMG_STALL = 10  # read-backs (NORMAL_GMG_CHECK_EVERY iterations each) without a new smallest residual: stagnation
+
+
+def direct_multigrid(matr, rhs, damp=0.0, dampdiag=0.0, maxiter=None, status=None):
+    """`direct` beyond the dense factorisation for the systems no exact route takes (several fields, mixed locations,
+    non-square or damped M): CG on the damped normal equations preconditioned by V-cycles whose coarsest level is
+    factorised on the device (gmg.NormalGMG, coarse="device"), to a relative residual of DIRECT_GMG_TOL, or stagnated
+    at the rounding floor below DIRECT_GMG_FLOOR |M^T r|.  status["residual"] is the TRUE residual |b - A x| of the
+    returned iterate.  None (after a log line saying why) when the operator does not qualify or the iteration does not
+    get there: the caller then runs the Jacobi CG."""
+    from . import gmg
+    from .util import printlog
+
+    if status is None:
+        status = dict()
+    why = None
+    if not matr.blocks or any(kind == "dense" for _, _, kind, _, _ in matr.blocks):
+        why = "the operator has dense (Array / NeuralNet) columns"
+    wide = matr.promoted() if matr.dtype == torch.float32 else matr
+    solver = None if why else gmg.NormalGMG.create(wide, damp, dampdiag, coarse="device")
+    if solver is None:
+        printlog("odil_amd: `direct` with {} unknowns: no multigrid on the normal equations for this operator ({}); "
+                 "using Jacobi CG on the normal equations".format(matr.ncols, why or "see above"))
+        return None
+    rhs = rhs.to(wide.dtype)
+    b = wide.rmatvec(rhs)
+    sub = dict()
+    x = cg_normal(wide, rhs, damp, dampdiag, tol=DIRECT_GMG_TOL, maxiter=maxiter or 1000, status=sub, b=b,
+                  check_every=NORMAL_GMG_CHECK_EVERY, precond=solver.precondition, stall=DIRECT_GMG_STALL)
+    # the true residual of the iterate (CG's own residual is a recurrence and runs on below the rounding floor)
+    ax = wide.rmatvec(wide.matvec(x))
+    if damp or dampdiag:
+        shift = torch.full_like(x, float(damp) ** 2 * (1.0 + float(dampdiag) ** 2))
+        if dampdiag:
+            ops.axpy(shift, wide.normal_diagonal(), float(dampdiag) ** 2)
+        ops.addcmul(ax, shift, x)
+    r = b.clone()
+    ops.axpy(r, ax, -1.0)
+    res = float(_dot(r, r)) ** 0.5
+    bnorm = float(_dot(b, b)) ** 0.5
+    converged = res <= DIRECT_GMG_TOL * max(bnorm, 1e-300)
+    # (the recurrence met the tolerance, or stopped improving, with the true residual above it: the rounding floor)
+    stagnated = not converged and (sub.get("stagnated", False) or sub["residual"] <= DIRECT_GMG_TOL * max(bnorm, 1e-300))
+    if not (converged or (stagnated and res <= DIRECT_GMG_FLOOR * bnorm)):
+        printlog("odil_amd: `direct` by multigrid on the normal equations stopped at relative residual {:.1e} after {} "
+                 "iterations; using Jacobi CG on the normal equations".format(res / max(bnorm, 1e-300), sub["niter"]))
+        return None
+    status.update(sub)
+    status["residual"] = res
+    status["bnorm"] = bnorm
+    status["converged"] = converged
+    status["stagnated"] = stagnated
+    status["coarse_dropped"] = solver.dropped_pivots()
+    status["method"] = solver.method[:-1] + "; direct, device coarse)"
+    return x.to(matr.dtype)
+
 
 
 def _exact_routes(matr, rhs, damp, dampdiag, maxiter, status, linsolver):

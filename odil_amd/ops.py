@@ -902,3 +902,32 @@ def bmg_galerkin(fdesc, cdesc, code, fcoef, ftable, ctable, nce, out):
     call("bmg_galerkin", out.dtype, fdesc, cdesc, code, ptr(fcoef), ptr(ftable), ptr(ctable), c_int(nce),
          c_int64(out.numel()), ptr(out), stream_ptr())
     return out
+
+
+def bmg_coarse_inverse(coef, table, desc, n, tol_rel=1e-13):
+    """The coarsest level's symmetric generalised inverse, factorised on the device (odil_bmg_coarse_dense +
+    odil_bmg_coarse_chol; float64).  Returns (inv: n x n, drops: device int32 per panel of 64 rows -- the dropped pivots).
+    Nothing is read back."""
+    assert coef.dtype == torch.float64, "the coarse factorisation is float64 only"
+    npad = -(-int(n) // 64) * 64
+    dev = coef.device
+    work = torch.empty((npad, 2 * npad), dtype=torch.float64, device=dev)
+    thr = torch.empty(1, dtype=torch.float64, device=dev)
+    drops = torch.empty(npad // 64, dtype=torch.int32, device=dev)
+    inv = torch.empty((int(n), int(n)), dtype=torch.float64, device=dev)
+    stream = stream_ptr()
+    call("bmg_coarse_dense", torch.float64, ptr(coef), ptr(table), desc, c_int64(npad), c_int64(2 * npad), ptr(work),
+         stream)
+    call("bmg_coarse_chol", torch.float64, ptr(work), c_int64(int(n)), c_int64(npad), float(tol_rel), ptr(thr),
+         ptr(drops), ptr(inv), stream)
+    return inv, drops
+
+
+def bmg_coarse_dense(coef, table, desc, n):
+    """The coarsest level's dense symmetric matrix 0.5 (A + A^T) on the device (odil_bmg_coarse_dense; float64, n x n)."""
+    assert coef.dtype == torch.float64, "the coarse factorisation is float64 only"
+    npad = -(-int(n) // 64) * 64
+    out = torch.empty((npad, npad), dtype=torch.float64, device=coef.device)
+    call("bmg_coarse_dense", torch.float64, ptr(coef), ptr(table), desc, c_int64(npad), c_int64(npad), ptr(out),
+         stream_ptr())
+    return out[:int(n), :int(n)]

@@ -1,0 +1,259 @@
+"""`--linsolver direct` beyond the dense factorisation (49152 unknowns) for the systems no exact route takes -- several
+grid fields, mixed locations, non-square or damped M: CG on the normal equations preconditioned by the multigrid of
+gmg.NormalGMG with its coarsest level factorised on the device (csrc/coarse_chol.hip), instead of Jacobi CG to its
+50000-iteration cap.
+
+  * darcy 2-D at 256^2, one Newton step with --linsolver_maxiter 200: the route, its residual, its iteration count
+    (before: Jacobi CG, relative residual ~1e-3 at the cap)
+  * the step equals the `multigrid` route's at tol 1e-12; darcy 3-D 64^3: the loss after one step is no worse
+  * a damped single-field operator (diffusion 2-D 256^2, damp 1e-3) that the exact routes decline: the iterate matches a
+    float64 SciPy solve of the damped normal equations to the system's conditioning
+  * the factorisation: the dense scatter equals NormalGMG.dense, B b equals the host pseudo-inverse's on the range of A
+    (random SPD levels, n = 1 .. 4096; darcy's coarsest levels), a pure-Neumann block (one-dimensional nullspace) gives
+    A B b = b, two factorisations are bit-identical
+  * small systems keep their route"""
+
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+from conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+
+def example(name):
+    p = os.path.join(ROOT, "examples", name)
+    if p not in sys.path:
+        sys.path.insert(0, p)
+    return importlib.import_module(name)
+
+
+def newton_step(name, argv):
+    """One Newton step through the public driver; returns (loss before, loss after, the solver's status)."""
+    import odil_amd as odil
+
+    ex = example(name)
+    args = ex.parse_args(list(argv) + ["--optimizer", "newton"])
+    odil.util.set_log_file(open(os.devnull, "w"))
+    problem, state = ex.make_problem(args)
+    loss0 = float(problem.eval_loss_grad(state)[0])
+    args.epoch_start, args.epochs = 0, 1
+    seen = []
+    odil.util.optimize(args, "newton", problem, state,
+                       lambda s, e, p: seen.append(p.get("linsolver") if hasattr(p, "get") else None))
+    st = [s for s in seen if s]
+    return loss0, float(problem.eval_loss_grad(state)[0]), (st[-1] if st else dict())
+
+
+def linearize(name, argv, seed=0):
+    import odil_amd as odil
+
+    ex = example(name)
+    odil.util.set_log_file(open(os.devnull, "w"))
+    problem, state = ex.make_problem(ex.parse_args(list(argv)))
+    rng = np.random.default_rng(seed)
+    arrays = [torch.as_tensor(rng.standard_normal(tuple(a.shape)) * 0.1, dtype=a.dtype).to(a.device)
+              for a in problem.domain.arrays_from_state(state)]
+    problem.domain.arrays_to_state(arrays, state)
+    return problem.linearize_device(state)
+
+
+def solve(op, vector, linsolver, tol=1e-10, maxiter=None, damp=0.0):
+    import odil_amd as odil
+
+    args = argparse.Namespace(linsolver_tol=tol, linsolver_maxiter=maxiter, linsolver_damp=damp, linsolver_dampdiag=0)
+    status = dict()
+    x = odil.linsolver.solve(op, -vector, args, status, linsolver)
+    return x, status
+
+
+def test_darcy_direct_newton_step_takes_multigrid():
+    """Fails without the feature: `direct` ran Jacobi CG on M^T M and stopped at the 200-iteration cap near 1e-3."""
+    from odil_amd.linsolver import DENSE_MAX_UNKNOWNS
+
+    loss0, loss1, st = newton_step("darcy", ["--ndim", "2", "--N", "256", "--linsolver", "direct",
+                                             "--linsolver_maxiter", "200"])
+    assert st.get("method", "").startswith("gmg-normal") and "direct, device coarse" in st["method"], st
+    rel = st["residual"] / st["bnorm"]
+    assert (st["converged"] and rel <= 1e-12) or (st["stagnated"] and not st["converged"] and rel <= 1e-3), st
+    assert st["niter"] <= 100, st
+    assert st["coarse_dropped"] is not None and st["coarse_dropped"] >= 0, st
+    assert loss1 <= 1e-14 * loss0, (loss0, loss1, st)
+    _, op = linearize("darcy", ("--ndim", "2", "--N", "256"))
+    assert op.ncols > DENSE_MAX_UNKNOWNS
+
+
+def test_direct_step_equals_the_multigrid_step():
+    vector, op = linearize("darcy", ("--ndim", "2", "--N", "256"))
+    xd, sd = solve(op, vector, "direct")
+    xm, sm = solve(op, vector, "multigrid", tol=1e-12)
+    assert sd["method"].startswith("gmg-normal") and "device coarse" in sd["method"], sd
+    assert sm["method"].startswith("gmg-normal") and "device" not in sm["method"], sm
+    err = float((xd - xm).norm()) / float(xm.norm())
+    assert err <= 1e-9, (err, sd, sm)
+
+
+def test_darcy_3d_direct_step_is_no_worse_than_multigrid():
+    _, loss_d, sd = newton_step("darcy", ["--ndim", "3", "--N", "64", "--linsolver", "direct"])
+    _, loss_m, sm = newton_step("darcy", ["--ndim", "3", "--N", "64", "--linsolver", "multigrid", "--linsolver_tol",
+                                          "1e-12"])
+    assert sd["method"].startswith("gmg-normal") and "device coarse" in sd["method"], sd
+    assert loss_d <= loss_m * (1 + 1e-6), (loss_d, loss_m, sd, sm)
+
+
+def test_damped_single_field_matches_a_sparse_solve():
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+
+    import odil_amd as odil
+
+    damp = 1e-3
+    vector, op = linearize("diffusion", ("--ndim", "2", "--N", "256"))
+    assert op.ncols > odil.linsolver.DENSE_MAX_UNKNOWNS and len(op.key_to_field) == 1
+    # the exact routes decline it (and the stencil cycles do not take damped operators): before this route, `direct`
+    # ended in Jacobi CG
+    assert odil.linsolver._exact_routes(op, -vector, damp, 0.0, None, dict(), "direct") is None
+    x, st = solve(op, vector, "direct", damp=damp)
+    assert st["method"].startswith("gmg-normal (1 field") and "direct, device coarse" in st["method"], st
+    m = op.to_scipy().tocsr().astype(np.float64)
+    a = (m.T @ m + damp**2 * sp.identity(m.shape[1])).tocsc()
+    ref = spla.spsolve(a, m.T @ (-vector.cpu().numpy()))
+    got = x.cpu().numpy()
+    err = np.linalg.norm(got - ref) / np.linalg.norm(ref)
+    # (A = M^T M + damp^2 I is ill-conditioned enough that float64 solves agree to ~1e-8 only: measured 1.2e-8 between
+    # the two, and 6.0e-9 (SuperLU) / 6.4e-9 (this route) from a solution refined with long-double residuals.  The
+    # iterate's own residual on the host-assembled equations -- measured 5.6e-13 -- is held to 1e-11.)
+    b = m.T @ (-vector.cpu().numpy())
+    res_got = np.linalg.norm(a @ got - b) / np.linalg.norm(b)
+    res_ref = np.linalg.norm(a @ ref - b) / np.linalg.norm(b)
+    assert err <= 1e-7, (err, res_got, res_ref, st)
+    assert res_got <= max(1e-11, 10 * res_ref), (err, res_got, res_ref, st)
+
+
+def test_small_systems_keep_their_route():
+    vector, op = linearize("darcy", ("--ndim", "2", "--N", "32"))
+    _, st = solve(op, vector, "direct")
+    assert st["method"].startswith("dense"), st
+
+
+# ---- the factorisation -----------------------------------------------------------------------------------------------
+def dense_level(amat):
+    """A one-field level (shape 1 x 1 x n) whose matrix is amat: one entry per offset along the last axis."""
+    from odil_amd import gmg
+
+    n = amat.shape[0]
+    rows, coefs = [], []
+    pos = 0
+    for o in range(-(n - 1), n):
+        q = np.arange(n)
+        c = np.where((q + o >= 0) & (q + o < n), amat[q, np.clip(q + o, 0, n - 1)], 0.0)
+        if not c.any():
+            continue
+        rows.append([0, 0, 0, 0, o, pos, 0, 0])
+        coefs.append(c)
+        pos += n
+    dev = torch.device("cuda:0")
+    coef = torch.as_tensor(np.concatenate(coefs), device=dev)
+    table = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
+    desc, _ = gmg.level_desc([(1, 1, n)], [0, len(rows)])
+    return coef, table, desc
+
+
+def random_spd(n, seed):
+    rng = np.random.default_rng(seed)
+    g = rng.standard_normal((n, n))
+    return g @ g.T / n + 0.5 * np.eye(n)
+
+
+def host_inverse(amat):
+    amat = 0.5 * (amat + amat.T)
+    w, v = np.linalg.eigh(amat)
+    keep = w > 1e-13 * max(float(np.abs(w).max()), 1e-300)
+    return (v[:, keep] / w[keep]) @ v[:, keep].T, v[:, keep]
+
+
+@pytest.mark.parametrize("n", [1, 15, 16, 17, 63, 64, 65, 200, 4096])
+def test_random_spd_levels(n):
+    from odil_amd import ops
+
+    amat = random_spd(n, n)
+    coef, table, desc = dense_level(amat)
+    dense = ops.bmg_coarse_dense(coef, table, desc, n).cpu().numpy()
+    assert np.array_equal(dense, 0.5 * (amat + amat.T))
+    inv, drops = ops.bmg_coarse_inverse(coef, table, desc, n)
+    assert int(drops.sum()) == 0
+    b = np.random.default_rng(1).standard_normal(n)
+    z = inv.cpu().numpy() @ b
+    ref = host_inverse(amat)[0] @ b
+    assert np.linalg.norm(z - ref) <= 1e-12 * np.linalg.norm(ref)
+    assert torch.equal(inv, inv.t())
+
+
+def neumann_level(nx, ny):
+    """The 5-point Laplacian with zero-flux walls on nx x ny cells: singular, nullspace = the constants."""
+    idx = np.arange(nx * ny).reshape(nx, ny)
+    amat = np.zeros((nx * ny, nx * ny))
+    for i in range(nx):
+        for j in range(ny):
+            for di, dj in ((1, 0), (-1, 0), (0, 1), (0, -1)):
+                if 0 <= i + di < nx and 0 <= j + dj < ny:
+                    amat[idx[i, j], idx[i, j]] += 1.0
+                    amat[idx[i, j], idx[i + di, j + dj]] -= 1.0
+    return amat
+
+
+def test_pure_neumann_block_is_inverted_on_its_range():
+    from odil_amd import ops
+
+    amat = neumann_level(24, 20)
+    n = amat.shape[0]
+    coef, table, desc = dense_level(amat)
+    inv, drops = ops.bmg_coarse_inverse(coef, table, desc, n)
+    assert int(drops.sum()) == 1
+    b = np.random.default_rng(3).standard_normal(n)
+    b -= b.mean()  # in the range: orthogonal to the constants
+    z = inv.cpu().numpy() @ b
+    assert np.isfinite(z).all()
+    assert np.abs(amat @ z - b).max() <= 1e-10 * np.abs(b).max()
+    # equal to the pseudo-inverse's answer up to a constant
+    ref = host_inverse(amat)[0] @ b
+    d = (z - ref) - (z - ref).mean()
+    assert np.abs(d).max() <= 1e-10 * np.abs(ref).max()
+
+
+def test_two_factorisations_are_bit_identical():
+    from odil_amd import ops
+
+    amat = random_spd(300, 7)
+    coef, table, desc = dense_level(amat)
+    a, da = ops.bmg_coarse_inverse(coef, table, desc, 300)
+    b, db = ops.bmg_coarse_inverse(coef, table, desc, 300)
+    assert torch.equal(a, b) and torch.equal(da, db)
+
+
+@pytest.mark.parametrize("argv", [("--ndim", "2", "--N", "256"), ("--ndim", "3", "--N", "32")], ids=["darcy2", "darcy3"])
+def test_darcy_coarsest_level_matches_the_host_inverse(argv):
+    from odil_amd import gmg, ops
+
+    _, op = linearize("darcy", argv)
+    host = gmg.NormalGMG.create(op, coarse="host")
+    dev = gmg.NormalGMG.create(op, coarse="device")
+    lvl = dev.nlvl - 1
+    n = dev.offs[lvl][-1]
+    amat = host.dense(lvl)
+    assert np.array_equal(ops.bmg_coarse_dense(dev.coef[lvl], dev.table[lvl], dev.desc[lvl], n).cpu().numpy(),
+                          0.5 * (amat + amat.T))
+    _, vrange = host_inverse(amat)
+    b = amat @ np.random.default_rng(4).standard_normal(n)  # in the range of A
+    zd = dev.coarse_inv.cpu().numpy() @ b
+    zh = host.coarse_inv.cpu().numpy() @ b
+    d = vrange @ (vrange.T @ (zd - zh))
+    err = np.linalg.norm(d) / np.linalg.norm(zh)
+    assert err <= 1e-12, (n, err, np.abs(d).max(), np.abs(zh).max(), dev.dropped_pivots())
+    # the default stays the host factorisation
+    assert gmg.NormalGMG.create(op).coarse == "host"
