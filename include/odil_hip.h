@@ -357,8 +357,8 @@ int odil_dots3_f64(const double* a, int64_t lda, int nvec, const double* b0, con
                    int64_t n, double* partials, double* out, void* stream);
 int odil_dots3_f32(const float* a, int64_t lda, int nvec, const float* b0, const float* b1, const float* b2, int64_t n,
                    double* partials, float* out, void* stream);
-/* out[0] = <g, d>, out[1] = <g, g>, out[2] = max_i |g[i]| in one pass: what the L-BFGS-B line search and
- * stopping test read after an evaluation (reference optimizer.py:95-105 -> SciPy lnsrlb / projgr).
+/* out[0] = <g, d>, out[1] = <g, g>, out[2] = max_i |g[i]| (NaN if any g[i] is NaN) in one pass: what the L-BFGS-B
+ * line search and stopping test read after an evaluation (reference optimizer.py:95-105 -> SciPy lnsrlb / projgr).
  * `partials`: odil_dots_workspace_bytes(3) scratch. */
 int odil_lbfgs_probe_f64(const double* g, const double* d, int64_t n, double* partials, double* out, void* stream);
 int odil_lbfgs_probe_f32(const float* g, const float* d, int64_t n, double* partials, float* out, void* stream);
@@ -379,9 +379,10 @@ int odil_stencil_apply_f32(const float* coeffs, const int64_t* shifts, int nshif
                            const int64_t* shape, int ndim, int transpose, void* stream);
 /* x = M^-1 b for such a matrix when it is triangular along `axis` with the coefficient array `diag` (zero shift)
  * alone on the diagonal block -- the Jacobian of an operator that is explicit in time (wave): every other shift has
- * a negative (direction > 0, forward substitution) or positive (direction < 0) component along `axis` and no
- * coefficient that wraps around the ends.  M d = -r then has the solution of the normal equations
- * M^T M d = -M^T r the reference hands to SuperLU (linsolver.py:17-26).  One launch per level of `axis`. */
+ * a negative (direction > 0, forward substitution) or positive (direction < 0) component along `axis`, of size below
+ * the extent (other shifts, and direction 0, are refused), and no coefficient that wraps around the ends.  M d = -r
+ * then has the solution of the normal equations M^T M d = -M^T r the reference hands to SuperLU (linsolver.py:17-26).
+ * One launch per level of `axis`. */
 int odil_stencil_march_f64(const double* coeffs, const int64_t* shifts, int nshift, int diag, const double* b, double* x,
                            const int64_t* shape, int ndim, int axis, int direction, void* stream);
 int odil_stencil_march_f32(const float* coeffs, const int64_t* shifts, int nshift, int diag, const float* b, float* x,

@@ -135,6 +135,11 @@ static int fill_shifts(ShiftArgs& a, const int64_t* shifts, int nshift, const in
     return ODIL_E_INVAL;
   }
   canon_shape(shape, ndim, a.n);
+  for (int d = 0; d < 4; ++d)
+    if (a.n[d] < 1) {  // (the reduction below divides by every extent)
+      set_error("stencil: extent %lld < 1", (long long)a.n[d]);
+      return ODIL_E_INVAL;
+    }
   a.nshift = nshift;
   for (int s = 0; s < nshift; ++s)
     for (int d = 0; d < 4; ++d) {
@@ -181,8 +186,9 @@ static int stencil_march(const T* coeffs, const int64_t* shifts, int nshift, int
                          const int64_t* shape, int ndim, int axis, int direction, void* stream) {
   ShiftArgs a;
   if (int e = fill_shifts(a, shifts, nshift, shape, ndim)) return e;
-  if (!coeffs || !b || !x || diag < 0 || diag >= nshift || axis < 0 || axis >= ndim) {
-    set_error("stencil_march: null pointer, diagonal slot %d or axis %d out of range", diag, axis);
+  if (!coeffs || !b || !x || diag < 0 || diag >= nshift || axis < 0 || axis >= ndim || direction == 0) {
+    set_error("stencil_march: null pointer, diagonal slot %d, axis %d or direction %d out of range", diag, axis,
+              direction);
     return ODIL_E_INVAL;
   }
   const int ax = axis + (4 - ndim);
@@ -191,6 +197,15 @@ static int stencil_march(const T* coeffs, const int64_t* shifts, int nshift, int
       set_error("stencil_march: slot %d is not the diagonal", diag);
       return ODIL_E_INVAL;
     }
+  // every other neighbour must lie in a level solved before (a neighbour in the same level would be read while
+  // another thread writes it): 0 < -direction * shift < n along `axis`
+  for (int s = 0; s < nshift; ++s) {
+    const int64_t back = direction > 0 ? -shifts[s * ndim + axis] : shifts[s * ndim + axis];
+    if (s != diag && (back < 1 || back >= a.n[ax])) {
+      set_error("stencil_march: shift %d does not point to an earlier level along axis %d", s, axis);
+      return ODIL_E_INVAL;
+    }
+  }
   const int64_t levels = a.n[ax], plane = prod4(a.n) / levels;
   for (int64_t k = 0; k < levels; ++k) {
     const int64_t level = direction > 0 ? k : levels - 1 - k;

@@ -451,15 +451,19 @@ __global__ __launch_bounds__(kBlock) void k_lbfgs_probe(const T* __restrict__ g,
     const double gi = (double)g[i];
     gd += gi * (double)d[i];
     gg += gi * gi;
-    gm = fmax(gm, fabs(gi));
+    const double ai = fabs(gi);
+    gm = ai > gm || ai != ai ? ai : gm;  // (a NaN stays visible: fmax would drop it and pass the stopping test)
   }
   const double t0 = block_sum(gd), t1 = block_sum(gg);
   __shared__ double wave_max[kBlock / 64];
-  for (int off = 32; off > 0; off >>= 1) gm = fmax(gm, __shfl_down(gm, off, 64));
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_down(gm, off, 64);
+    gm = o > gm || o != o ? o : gm;
+  }
   if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = gm;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) gm = fmax(gm, wave_max[w]);
+    for (int w = 1; w < kBlock / 64; ++w) gm = wave_max[w] > gm || wave_max[w] != wave_max[w] ? wave_max[w] : gm;
     partials[blockIdx.x] = t0;
     partials[kDotPartials + blockIdx.x] = t1;
     partials[2 * kDotPartials + blockIdx.x] = gm;
@@ -473,15 +477,19 @@ __global__ __launch_bounds__(kBlock) void k_lbfgs_probe_final(const double* __re
   for (int i = threadIdx.x; i < count; i += kBlock) {
     gd += partials[i];
     gg += partials[kDotPartials + i];
-    gm = fmax(gm, partials[2 * kDotPartials + i]);
+    const double pm = partials[2 * kDotPartials + i];
+    gm = pm > gm || pm != pm ? pm : gm;
   }
   const double t0 = block_sum(gd), t1 = block_sum(gg);
   __shared__ double wave_max[kBlock / 64];
-  for (int off = 32; off > 0; off >>= 1) gm = fmax(gm, __shfl_down(gm, off, 64));
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_down(gm, off, 64);
+    gm = o > gm || o != o ? o : gm;
+  }
   if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = gm;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) gm = fmax(gm, wave_max[w]);
+    for (int w = 1; w < kBlock / 64; ++w) gm = wave_max[w] > gm || wave_max[w] != wave_max[w] ? wave_max[w] : gm;
     out[0] = (T)t0;
     out[1] = (T)t1;
     out[2] = (T)gm;

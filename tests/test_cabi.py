@@ -107,6 +107,89 @@ def test_bmg_host_side_validation():
     assert transfer(fine, coarse, [0, 0, 0, 0, 0, 2]) == -1
 
 
+def test_stencil_host_side_validation():
+    """odil_stencil_apply / _csr_assemble / _stencil_march and the solver reductions refuse malformed shift lists,
+    extents, diagonal slots, axes, directions, sizes and null pointers with ODIL_E_INVAL before anything touches the
+    device (the pointers are dummies)."""
+    from ctypes import c_double, c_int, c_int64, c_void_p
+
+    from odil_amd import _lib
+
+    lib = _lib.load()
+    coeffs, x, y, w = (c_void_p(16 * k) for k in range(1, 5))
+    shape = [4, 5]
+    good = [(0, 0), (-1, 0), (-2, 1)]  # diagonal, then two shifts pointing back along axis 0
+
+    def flat(shifts):
+        return _lib.i64([v for s in shifts for v in s] or [0])
+
+    for fn in (lib.odil_stencil_apply_f64, lib.odil_stencil_apply_f32):
+        def apply(shifts=good, nshift=None, shp=shape, ndim=None, c=coeffs, xx=x, yy=y, shifts_ptr=True):
+            nshift = len(shifts) if nshift is None else nshift
+            ndim = len(shp) if ndim is None else ndim
+            return fn(c, flat(shifts) if shifts_ptr else None, c_int(nshift), xx, yy, _lib.i64(shp or [1]),
+                      c_int(ndim), c_int(0), None)
+
+        assert apply(nshift=0) == -1
+        assert apply([(0, 0)] * 33) == -1
+        assert apply(shifts_ptr=False) == -1
+        assert apply(shp=[4, 0]) == -1 and b"extent" in lib.odil_last_error()
+        assert apply([(0,)], shp=[], ndim=0) == -1
+        assert apply([(0,) * 5], shp=[2] * 5) == -1
+        for c, xx, yy in ((None, x, y), (coeffs, None, y), (coeffs, x, None)):
+            assert apply(c=c, xx=xx, yy=yy) == -1
+            assert b"null pointer" in lib.odil_last_error()
+
+    for fn in (lib.odil_csr_assemble_f64, lib.odil_csr_assemble_f32):
+        def assemble(shifts=good, nshift=None, shp=shape, ptrs=(coeffs, x, y, w)):
+            nshift = len(shifts) if nshift is None else nshift
+            c, indptr, indices, data = ptrs
+            return fn(c, flat(shifts), c_int(nshift), _lib.i64(shp), c_int(len(shp)), c_int64(3 << 31), indptr,
+                      indices, data, None)
+
+        assert assemble(nshift=0) == -1
+        assert assemble([(0, 0)] * 33) == -1
+        assert assemble(shp=[0, 5]) == -1
+        for k in range(4):
+            ptrs = [coeffs, x, y, w]
+            ptrs[k] = None
+            assert assemble(ptrs=ptrs) == -1, k
+
+    for fn in (lib.odil_stencil_march_f64, lib.odil_stencil_march_f32):
+        def march(shifts=good, diag=0, axis=0, direction=1, nshift=None, shp=shape, c=coeffs, b=x, out=y):
+            nshift = len(shifts) if nshift is None else nshift
+            return fn(c, flat(shifts), c_int(nshift), c_int(diag), b, out, _lib.i64(shp), c_int(len(shp)),
+                      c_int(axis), c_int(direction), None)
+
+        assert march(nshift=0) == -1
+        assert march([(0, 0)] + [(-1, 0)] * 32) == -1
+        for diag in (-1, 3):
+            assert march(diag=diag) == -1, diag
+        assert march(diag=1) == -1 and b"not the diagonal" in lib.odil_last_error()
+        for axis in (-1, 2):
+            assert march(axis=axis) == -1, axis
+        assert march(direction=0) == -1
+        for c, b, out in ((None, x, y), (coeffs, None, y), (coeffs, x, None)):
+            assert march(c=c, b=b, out=out) == -1
+        # neighbours that are not in an earlier level: same level, the wrong direction, a whole period back
+        for bad in ((0, 1), (1, 0), (-4, 0)):
+            assert march([(0, 0), (-1, 0), bad]) == -1, bad
+            assert b"earlier level" in lib.odil_last_error()
+        assert march(direction=-1) == -1  # the good shifts point forward
+        assert march([(0, 0), (-1, 0)], axis=1) == -1  # no component along axis 1
+
+    part, out = c_void_p(64), c_void_p(128)
+    for n in (0, -1):
+        assert lib.odil_lbfgs_probe_f64(x, y, c_int64(n), part, out, None) == -1
+        assert lib.odil_lbfgs_probe_f32(x, y, c_int64(n), part, out, None) == -1
+        assert lib.odil_max_abs_diff_f64(x, y, c_int64(n), part, out, None) == -1
+        assert lib.odil_max_abs_diff_f32(x, y, c_int64(n), part, out, None) == -1
+    assert lib.odil_lbfgs_probe_f64(None, y, c_int64(8), part, out, None) == -1
+    assert lib.odil_max_abs_diff_f64(x, None, c_int64(8), part, out, None) == -1
+    assert lib.odil_narrow_scale(x, None, c_int64(8), c_double(1.0), None, None) == -1
+    assert lib.odil_widen_axpy(x, y, c_int64(-1), c_double(1.0), None, None) == -1
+
+
 def test_no_cpu_fallback():
     from odil_amd import _lib, ops
 
