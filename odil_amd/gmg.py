@@ -39,6 +39,12 @@ def skewed(shape, dtype, device, k, zero=False):
     return flat[pad:pad + n].view(shape)
 
 
+def jacobi_weights(ndim, n):
+    """The weights of n Jacobi sweeps that form the degree-n Chebyshev polynomial on [1 / ndim, 2], the part of the
+    spectrum of D^-1 A that the coarse grid cannot see (`PoissonGMG.smooth`)."""
+    return chebyshev_weights(n, 1.0 / ndim, 2.0)
+
+
 class PoissonGMG:
     nu_default = (2, 2)  # pre- / post-smoothing sweeps of a cycle
 
@@ -49,9 +55,6 @@ class PoissonGMG:
         self.loc = "c" * self.ndim
         self.dtype, self.device = dtype, device
         npdt = np.float64 if dtype == torch.float64 else np.float32
-        self.omega = omega if omega is not None else {1: 2.0 / 3.0, 2: 4.0 / 5.0, 3: 6.0 / 7.0}[self.ndim]
-        self.nu1 = self.nu_default[0] if nu1 is None else nu1
-        self.nu2 = self.nu_default[1] if nu2 is None else nu2
         self.shapes, self.h2s = [tuple(shape)], [[npdt(v) for v in h2]]
         # SEMI-coarsening while the cells are far from cubes: point smoothing only damps what oscillates along the strongly
         # coupled axes (the small spacings), so only those are halved -- the axes whose h^2 is within a factor 2 of the
@@ -68,9 +71,16 @@ class PoissonGMG:
             self.shapes.append(tuple(n // 2 if on else n for n, on in zip(cur, halve)))
             self.h2s.append([v * npdt(4) if on else v for v, on in zip(h, halve)])
             self.locs.append("".join("c" if on else "." for on in halve))
+        self.finish_init(omega, nu1, nu2, lite)
+
+    def finish_init(self, omega, nu1, nu2, lite):
+        """What a hierarchy of either operator needs once `shapes` stands: the cycle's parameters, caches, work arrays."""
+        dtype, device = self.dtype, self.device
+        self.omega = omega if omega is not None else {1: 2.0 / 3.0, 2: 4.0 / 5.0, 3: 6.0 / 7.0}[self.ndim]
+        self.nu1 = self.nu_default[0] if nu1 is None else nu1
+        self.nu2 = self.nu_default[1] if nu2 is None else nu2
         self.nlvl = len(self.shapes)
-        mk = lambda s: torch.zeros(s, dtype=dtype, device=device)
-        self.loss = mk(())
+        self.loss = torch.zeros((), dtype=dtype, device=device)
         self._coarse_inv = None
         self._continuation = None
         self._r = [None] * self.nlvl                         # residuals (only where the fused restriction cannot be used)
@@ -91,11 +101,16 @@ class PoissonGMG:
             n = math.prod(shape)
             eye = torch.eye(n, dtype=self.dtype, device=self.device)
             zero = torch.zeros(shape, dtype=self.dtype, device=self.device)
-            cols = [ops.poisson_residual(eye[j].view(shape), zero, self.h2s[-1])[0].reshape(-1) for j in range(n)]
+            cols = [self.coarse_column(eye[j].view(shape), zero).reshape(-1) for j in range(n)]
             amat = torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)  # column j = A e_j
-            inv = np.linalg.inv(amat)
-            self._coarse_inv = torch.as_tensor(inv, dtype=self.dtype).to(self.device).contiguous()
+            self._coarse_inv = torch.as_tensor(self.invert(amat), dtype=self.dtype).to(self.device).contiguous()
         return self._coarse_inv
+
+    def coarse_column(self, e, zero):
+        """A e on the coarsest level."""
+        return ops.poisson_residual(e, zero, self.h2s[-1])[0]
+
+    invert = staticmethod(np.linalg.inv)
 
     def r(self, lvl):
         if self._r[lvl] is None:
@@ -117,37 +132,43 @@ class PoissonGMG:
         return self.sweeps(lvl, x, b, self.weights(n, chebyshev), zero=zero)
 
     def weights(self, n, chebyshev=True):
-        if not chebyshev:
-            return [self.omega] * n
-        lo, hi = 1.0 / self.ndim, 2.0
-        mid, half = 0.5 * (hi + lo), 0.5 * (hi - lo)
-        return [1.0 / (mid - half * math.cos(math.pi * (2 * k + 1) / (2 * n))) for k in range(n)]
+        return jacobi_weights(self.ndim, n) if chebyshev else [self.omega] * n
 
     def sweeps(self, lvl, x, b, weights, zero=False):
-        """Sweeps with the given weights, in PAIRS through the one-pass kernel (odil_poisson_jacobi2: the intermediate
-        iterate stays on the CU, 3 words per cell and pair instead of 6; bit-identical to two single sweeps) on levels
-        large enough to be bandwidth-bound.  zero: the iterate is the zero vector (every coarse level of a cycle starts
-        there): the first launch does not read `x` -- the same bits as from an array of zeros, which nobody has to write."""
+        """Sweeps with the given weights, in PAIRS through the one-pass kernel (`sweep_pair`; bit-identical to two single
+        sweeps) on levels large enough to be bandwidth-bound.  zero: the iterate is the zero vector (every coarse level of
+        a cycle starts there) and `x` only a buffer: the first launch does not read it (x = NULL) -- the same bits as from
+        an array of zeros, which nobody has to write."""
         weights = list(weights)
         if zero and (not weights or not self.zero_start):
             x.zero_()
             zero = False
-        # (float64 only: with four floats per lane the pair is bound by the vector ALU, 0.85 against 0.70 ms at 512^3)
-        pair = (self.dtype == torch.float64 and ops.jacobi2_supported(self.shapes[lvl], self.dtype)
-                and math.prod(self.shapes[lvl]) >= self.pair_min_cells)
+        pair = self.pair_eligible(lvl)
         while weights:
             y = self.spare[lvl]
             src = None if zero else x
             zero = False
             if pair and len(weights) >= 2:
-                ops.poisson_jacobi2(src, b, self.h2s[lvl], weights[0], weights[1], out=y)
+                self.sweep_pair(lvl, src, b, weights[0], weights[1], y)
                 weights = weights[2:]
             else:
-                ops.poisson_jacobi(src, b, self.h2s[lvl], weights[0], out=y)
+                self.sweep(lvl, src, b, weights[0], y)
                 weights = weights[1:]
             self.spare[lvl] = x
             x = y
         return x
+
+    def sweep(self, lvl, src, b, w, out):
+        ops.poisson_jacobi(src, b, self.h2s[lvl], w, out=out)
+
+    def sweep_pair(self, lvl, src, b, w1, w2, out):
+        """(odil_poisson_jacobi2: the intermediate iterate stays on the CU, 3 words per cell and pair instead of 6)"""
+        ops.poisson_jacobi2(src, b, self.h2s[lvl], w1, w2, out=out)
+
+    def pair_eligible(self, lvl):
+        # (float64 only: with four floats per lane the pair is bound by the vector ALU, 0.85 against 0.70 ms at 512^3)
+        return (self.dtype == torch.float64 and ops.jacobi2_supported(self.shapes[lvl], self.dtype)
+                and math.prod(self.shapes[lvl]) >= self.pair_min_cells)
 
     post_pair = True
     zero_start = True  # (False: the zero iterate of a coarse level is written and read back -- the tests compare both, bit for bit)
@@ -228,8 +249,7 @@ class PoissonGMG:
         xc_new = self.coarse_correction(lvl)
         out = self.spare[lvl]
         weights = self.weights(self.nu2) if post else []
-        pair = (self.post_pair and len(weights) >= 2 and self.dtype == torch.float64
-                and ops.jacobi2_supported(self.shapes[lvl], self.dtype) and math.prod(self.shapes[lvl]) >= self.pair_min_cells)
+        pair = self.post_pair and len(weights) >= 2 and self.pair_eligible(lvl)
         if pair:
             # x + P x_c as a pass of its own (2 1/8 words), then the post-smoothing PAIR in one pass (3 words): 5 1/8
             # against 3 1/8 + 3 for the prolongation fused into the first of two single sweeps
@@ -525,9 +545,6 @@ class StencilGMG(PoissonGMG):
         assert coeffs.shape[0] == 2 * self.ndim + 1 and self.ndim <= 3 and coeffs.is_contiguous()
         self.loc = "c" * self.ndim
         self.dtype, self.device = store or coeffs.dtype, coeffs.device
-        self.omega = {1: 2.0 / 3.0, 2: 4.0 / 5.0, 3: 6.0 / 7.0}[self.ndim]
-        self.nu1 = self.nu_default[0] if nu1 is None else nu1
-        self.nu2 = self.nu_default[1] if nu2 is None else nu2
         self.coeffs, self.shapes = [coeffs], [shape]
         self.locs = []  # per transition: 'c' on the merged axes, '.' on the others
         cur = coeffs
@@ -553,32 +570,16 @@ class StencilGMG(PoissonGMG):
             assert coeffs.dtype == torch.float64 and store == torch.float32
             self.coeffs = [ops.narrow_scale(c.reshape(-1), torch.empty(c.numel(), dtype=store, device=c.device)).view(c.shape)
                            for c in self.coeffs]
-        self.nlvl = len(self.shapes)
-        mk = lambda s: torch.zeros(s, dtype=self.dtype, device=self.device)
-        self.loss = mk(())
-        self._coarse_inv = None
-        self._continuation = None
-        self._r = [None] * self.nlvl
-        if lite:
-            return
-        self.x = [None] + [skewed(s, self.dtype, self.device, 2, zero=True) for s in self.shapes[1:]]
-        self.b = [None] + [skewed(s, self.dtype, self.device, 3, zero=True) for s in self.shapes[1:]]
-        self.spare = [skewed(s, self.dtype, self.device, 1) for s in self.shapes]
+        self.finish_init(None, nu1, nu2, lite)
 
-    def coarse_inverse(self):
-        """(Pseudo-)inverse of the coarsest operator, from the residual kernel applied to unit vectors; a singular
-        coarsest operator (all-periodic or all-Neumann problems: constants in the null space) gets the minimum-norm
-        solution."""
-        if self._coarse_inv is None:
-            shape = self.shapes[-1]
-            n = math.prod(shape)
-            eye = torch.eye(n, dtype=self.dtype, device=self.device)
-            zero = torch.zeros(shape, dtype=self.dtype, device=self.device)
-            cols = [-ops.stencil_var_residual(self.coeffs[-1], eye[j].view(shape).contiguous(), zero).reshape(-1) for j in range(n)]
-            amat = torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)  # column j = A e_j
-            inv = np.linalg.pinv(amat, rcond=1e-12)
-            self._coarse_inv = torch.as_tensor(inv, dtype=self.dtype).to(self.device).contiguous()
-        return self._coarse_inv
+    def coarse_column(self, e, zero):
+        return -ops.stencil_var_residual(self.coeffs[-1], e, zero)
+
+    @staticmethod
+    def invert(amat):
+        """The PSEUDO-inverse: a singular coarsest operator (all-periodic or all-Neumann problems: constants in the null
+        space) gets the minimum-norm solution."""
+        return np.linalg.pinv(amat, rcond=1e-12)
 
     residual_sign = -1.0  # `residual` returns b - A x (PoissonGMG: A x - b)
 
@@ -597,28 +598,15 @@ class StencilGMG(PoissonGMG):
         ops.mean_reduce(out.reshape(-1), square=True, out=self.loss)
         return out
 
-    def sweeps(self, lvl, x, b, weights, zero=False):
-        """Sweeps in PAIRS through the one-pass kernel (odil_stencil_var_smooth2: the coefficient arrays -- 7 of a sweep's
-        10 words in 3-D -- read once for both sweeps; bit-identical to two single sweeps) on the bandwidth-bound levels.
-        zero: the iterate is the zero vector and `x` only a buffer: the first launch does not read it (x = NULL)."""
-        weights = list(weights)
-        if zero and (not weights or not self.zero_start):
-            x.zero_()
-            zero = False
-        pair = ops.smooth2_supported(self.shapes[lvl]) and math.prod(self.shapes[lvl]) >= self.pair_min_cells
-        while weights:
-            y = self.spare[lvl]
-            src = None if zero else x
-            zero = False
-            if pair and len(weights) >= 2:
-                ops.stencil_var_smooth2(self.coeffs[lvl], src, b, weights[0], weights[1], out=y)
-                weights = weights[2:]
-            else:
-                ops.stencil_var_smooth(self.coeffs[lvl], src, b, weights[0], out=y)
-                weights = weights[1:]
-            self.spare[lvl] = x
-            x = y
-        return x
+    def sweep(self, lvl, src, b, w, out):
+        ops.stencil_var_smooth(self.coeffs[lvl], src, b, w, out=out)
+
+    def sweep_pair(self, lvl, src, b, w1, w2, out):
+        """(odil_stencil_var_smooth2: the coefficient arrays -- 7 of a sweep's 10 words in 3-D -- read once for both sweeps)"""
+        ops.stencil_var_smooth2(self.coeffs[lvl], src, b, w1, w2, out=out)
+
+    def pair_eligible(self, lvl):
+        return ops.smooth2_supported(self.shapes[lvl]) and math.prod(self.shapes[lvl]) >= self.pair_min_cells
 
     def coarse_rhs(self, lvl, x, b):
         bc = self.b[lvl + 1]

@@ -21,6 +21,7 @@ import threading
 import numpy as np
 import torch
 
+from . import gmg
 from . import ops as hip_ops
 from . import slab
 from .optimizer import LbfgsVectors, lbfgsb_minimize
@@ -163,6 +164,24 @@ class SlabPoissonLbfgs(slab.SlabPoissonAdam):
         return res
 
 
+def _rank_sum(comm, part):
+    """The sum over the ranks of one number per rank: ONE all-gather, added up in rank order on every rank (the same bits
+    everywhere, so the ranks take the same branches without further agreement)."""
+    return float(comm.exchange("gather", part.to(torch.float64).reshape(1), None).sum())
+
+
+def _halo_planes(comm, a, lv, planes):
+    """`planes` boundary planes of `a` ([..., z, y, x]: one array or a stack of arrays) into the neighbours' ghost planes
+    nearest the interface."""
+    lo = a[..., lv.g_lo: lv.g_lo + planes, :, :].contiguous() if lv.g_lo else None
+    hi = a[..., lv.g_lo + lv.nz - planes: lv.g_lo + lv.nz, :, :].contiguous() if lv.g_hi else None
+    recv_lo, recv_hi = comm.exchange("halo", lo, hi)
+    if recv_lo is not None:
+        a[..., lv.g_lo - planes: lv.g_lo, :, :].copy_(recv_lo.view(lo.shape))
+    if recv_hi is not None:
+        a[..., lv.g_lo + lv.nz: lv.g_lo + lv.nz + planes, :, :].copy_(recv_hi.view(hi.shape))
+
+
 class SlabPoissonNewtonCG:
     """One rank of a matrix-free Newton step of the slab-decomposed Poisson problem WITHOUT the multigrid decomposition
     (the reference's `linearize` refuses multigrid unknowns, reference core.py:1208-1209): the step solves the normal
@@ -197,34 +216,22 @@ class SlabPoissonNewtonCG:
     def owned(self, a):
         return self.lv.owned(a)
 
-    def _halo(self, comm, a):
-        """One boundary plane of `a` to each neighbour's inner ghost plane."""
-        lv = self.lv
-        lo = a[lv.g_lo] if self.rank > 0 else None
-        hi = a[lv.g_lo + lv.nz - 1] if self.rank < self.world - 1 else None
-        recv_lo, recv_hi = comm.exchange("halo", lo, hi)
-        if recv_lo is not None:
-            a[lv.g_lo - 1].copy_(recv_lo.view(lv.ny, lv.nx))
-        if recv_hi is not None:
-            a[lv.g_lo + lv.nz].copy_(recv_hi.view(lv.ny, lv.nx))
-
     def _dot(self, comm, a, b):
-        part = (self.owned(a).to(torch.float64) * self.owned(b).to(torch.float64)).sum().reshape(1)
-        return float(comm.exchange("gather", part, None).sum())
+        return _rank_sum(comm, (self.owned(a).to(torch.float64) * self.owned(b).to(torch.float64)).sum())
 
     def residual(self, comm, u, out):
         """out = f(u) = Lap(u) - rhs on the owned planes; -> global mean of its squares."""
-        self._halo(comm, u)
+        _halo_planes(comm, u, self.lv, 1)
         lv = self.lv
         self.ops.poisson_residual(u, self.rhs, self.h2, fu=out, loss=self.part, zrange=(lv.g_lo, lv.g_lo + lv.nz),
                                   denom=self.global_cells)
-        return float(comm.exchange("gather", self.part.to(torch.float64).reshape(1), None).sum())
+        return _rank_sum(comm, self.part)
 
     def normal_apply(self, comm, p, out, damp2=0.0):
         """out = M^T M p + damp2 p on the owned planes (ghost planes of p and of M p refreshed on the way)."""
-        self._halo(comm, p)
+        _halo_planes(comm, p, self.lv, 1)
         self.ops.poisson_residual(p, self.zero, self.h2, fu=self.q, loss=self.part)
-        self._halo(comm, self.q)
+        _halo_planes(comm, self.q, self.lv, 1)
         self.ops.poisson_adjoint(self.q, self.h2, 1.0, out=out)
         if damp2:
             out.add_(p, alpha=damp2)
@@ -233,7 +240,7 @@ class SlabPoissonNewtonCG:
         """One Newton step u <- u + dx; -> (loss before, loss after).  self.status: CG iterations and relative residual."""
         loss0 = self.residual(comm, self.u, self.f)
         # b = -M^T f
-        self._halo(comm, self.f)
+        _halo_planes(comm, self.f, self.lv, 1)
         b = self.z
         self.ops.poisson_adjoint(self.f, self.h2, -1.0, out=b)
         dx = torch.zeros_like(self.u)
@@ -258,20 +265,17 @@ class SlabPoissonNewtonCG:
         return loss0, loss1
 
 
-class SlabPoissonNewtonGMG(SlabPoissonNewtonCG):
-    """The Newton step of the slab-decomposed Poisson problem solved by GEOMETRIC MULTIGRID -- the slab form of
-    `gmg.PoissonGMG` ("Newton: matrix-free M / M^T apply = same halo pattern"; the reference's Newton driver,
-    src/odil/util.py:152-187, solves M^T M delta = -M^T f with SuperLU, linsolver.py:17-26; for the square nonsingular
-    Laplacian M delta = -f has the same solution).  `SlabPoissonNewtonCG` above is unpreconditioned CG on the normal
-    equations: O(N) iterations; this one needs ~12 cycles at any size.
+class SlabVCycle:
+    """GEOMETRIC MULTIGRID on a slab-decomposed 3-D grid: the cycle that `SlabPoissonNewtonGMG` and `SlabStencilGMG` below
+    share.  The global grid (world nz, ny, nx) is cut along axis 0, whose two ENDS are walls.
 
-    Levels: the box (world nz, N, N) is coarsened by 2 along every axis while every rank keeps >= 2 planes and the
-    cross-section extents stay even; level arrays are ghost-extended like the epochs' (`slab.SlabLevel`, G = 2 planes per
-    interior interface).  One V(2, 2) cycle per level, everything with the unmodified single-GPU kernels on the extended
-    arrays (an array end that is a ghost plane is treated as a wall by the kernel: only the ghost planes themselves see that):
+    Levels: the box is coarsened by 2 along every axis while every rank keeps >= 2 planes and the cross-section >= 4
+    cells; level arrays are ghost-extended like the epochs' (`slab.SlabLevel`, G = 2 planes per interior interface).  One
+    V(nu, nu) cycle per level, everything with the unmodified single-GPU kernels on the extended arrays (an array end that
+    is a ghost plane is treated as a wall or wrapped around by the kernel: only the outer ghost planes see that):
       * two planes of x to each neighbour, then TWO Chebyshev-weighted Jacobi sweeps (the first leaves owned + inner ghost
-        planes valid, the second the owned planes);
-      * one plane of x, the residual A x - b on the owned planes (its squared norm summed over the ranks by one all-gather),
+        planes valid, the second the owned planes; as ONE pass on large levels);
+      * one plane of x, the residual on the owned planes (its squared norm summed over the ranks by one all-gather),
         full-weighting restriction of the owned planes (pairs of owned planes: no exchange), one plane of the coarse
         right-hand side to each neighbour;
       * the coarse correction; one plane of it to each neighbour, then x += P x_c by the multigrid decomposition's
@@ -280,507 +284,386 @@ class SlabPoissonNewtonGMG(SlabPoissonNewtonCG):
     Five exchanges per level and cycle, 1 - 2 planes each (512^2 f64 planes: 2 - 4 MB at the finest level, halved twice per
     level).  Below the last slab level the problem is AGGLOMERATED: the coarse right-hand side is all-gathered
     (a few thousand numbers), every rank runs the remaining cycle on the whole coarse box and keeps its planes -- the same
-    bits on every rank, no further exchange."""
+    bits on every rank, no further exchange.
 
-    def __init__(self, N, rank, world, dtype=torch.float64, device=None, rhs_global=None, nz=None, nu=2, agg_cells=32**3,
-                 pair_min_cells=128**3):
-        """agg_cells: a level is a SLAB level only while a rank holds more cells of it than this -- an exchange costs ~65 us of
-        host time whatever its size (`profiles/r06_rccl_selfloop_sweep.txt`), four of them per level and cycle, and a level of
-        32^3 cells per rank is sooner solved redundantly on the whole agglomerated box (0: down to two planes per rank)."""
-        super().__init__(N, rank, world, dtype=dtype, device=device, rhs_global=rhs_global, nz=nz)
-        self.nu = nu
-        npdt = np.float64 if dtype == torch.float64 else np.float32
-        nz = self.lv.nz
-        self.mlv, self.mh2 = [self.lv], [list(self.h2)]
-        shape = (nz, N, N)
+    THE OPERATOR of a level is the subclass's.  `self.mc[l]` (slab levels) and `self.agg[k]` (levels of the agglomerated box)
+    hold whatever its kernels take as level data `c`; the cycle never looks inside.  A subclass provides
+      sweep(c, src, b, w, out), sweep_pair(c, src, b, w1, w2, out), pair_supported(x)
+      level_residual(c, x, b, out=None, lv=None)   the residual; lv: a slab level (only its owned planes matter)
+      rank_norm(r, lv)                             this rank's share of |r|^2 after level_residual(..., r, lv)
+      residual_restrict(c, x, b, out, lv), fused_supported(x)    residual + restriction in one pass, the share in self.part
+      rhs_sign              the coarse right-hand side is rhs_sign R (what `level_residual` returns)
+      coarsen(c)            level data of the next level of a WHOLE box
+      box_solver(c)         the single-GPU solver that cycles the agglomerated box
+      invert(amat)          the dense solve at the bottom of a stand-in's recursion
+      top2(l)               whether level l's coarse correction takes a second cycle
+      method                the name `status` reports
+    and self.ops, rank, world, dtype, device, nu, pair_min_cells."""
+
+    def _plan(self, first, agg_cells):
+        """The slab levels below `first` and the shape of the agglomerated box.  agg_cells: a level is a SLAB level only
+        while a rank holds more cells of it than this -- an exchange costs ~65 us of host time whatever its size
+        (`profiles/r06_rccl_selfloop_sweep.txt`), four of them per level and cycle, and a level of 32^3 cells per rank is
+        sooner solved redundantly on the whole agglomerated box (0: down to two planes per rank)."""
+        # The library's own kernels, or a stand-in `ops` (the host tests)?  With its own the cycle is the single-GPU one's:
+        # sweeps in pairs, the residual restricted in the pass that forms it, a zero iterate that is never read, the
+        # agglomerated box cycled by `gmg`; a stand-in keeps the plain launches and the plain recursion of `_box_cycle`.
+        self.native = getattr(self.ops, "__name__", "") == "odil_amd.ops"
+        self.mlv = [first]
+        shape = (first.nz, first.ny, first.nx)
         # (cross-sections of >= 4 cells on every slab level, so that the agglomerated box below the last one still has two)
         while (all(s % 2 == 0 for s in shape) and shape[0] // 2 >= 2 and min(shape[1], shape[2]) // 2 >= 4
                and int(np.prod(shape)) // 8 > agg_cells):
             shape = tuple(s // 2 for s in shape)
-            self.mlv.append(slab.SlabLevel(shape[0], shape[1], shape[2], rank, world))
-            self.mh2.append([v * npdt(4) for v in self.mh2[-1]])
+            self.mlv.append(slab.SlabLevel(shape[0], shape[1], shape[2], self.rank, self.world))
         # the agglomerated box below the last slab level (None when that level cannot be coarsened at all)
         last = self.mlv[-1]
         self.agg_shape = None
         if last.nz % 2 == 0 and last.ny % 2 == 0 and last.nx % 2 == 0 and min(last.ny, last.nx) >= 4:
-            self.agg_shape = (world * last.nz // 2, last.ny // 2, last.nx // 2)
-            self.agg_h2 = [v * npdt(4) for v in self.mh2[-1]]
-        mk = lambda lv: torch.zeros(lv.shape, dtype=dtype, device=device)
+            self.agg_shape = (self.world * last.nz // 2, last.ny // 2, last.nx // 2)
+
+    def _finish_setup(self, box):
+        """The work arrays of the slab levels, and the levels of the agglomerated box from its level data `box` (None: no
+        box)."""
+        mk = lambda lv: torch.zeros(lv.shape, dtype=self.dtype, device=self.device)
         self.mx = [None] + [mk(lv) for lv in self.mlv[1:]]
         self.mb = [None] + [mk(lv) for lv in self.mlv[1:]]
         self.spare = [mk(lv) for lv in self.mlv]
         self.res = [mk(lv) for lv in self.mlv]
-        self._dense = dict()
-        self.pair_min_cells = pair_min_cells
-        # with the library's own kernels underneath the cycle is the single-GPU one's: sweeps in pairs
-        # (`odil_poisson_jacobi2`), the residual restricted in the pass that forms it (`odil_poisson_residual_restrict`),
-        # the agglomerated box cycled by `gmg.PoissonGMG`; a stand-in `ops` (the host tests) keeps the plain launches
-        self.native = getattr(self.ops, "__name__", "") == "odil_amd.ops"
-        self.agg_gmg = None
-        if self.native and self.agg_shape is not None and min(self.agg_shape) >= 4:
-            from . import gmg
+        self.part = torch.zeros((), dtype=self.dtype, device=self.device)
+        self.agg = self.agg_gmg = self._agg_part = self._box_inv = None
+        if box is not None:
+            self.agg, shape = [box], self.agg_shape
+            while all(v % 2 == 0 and v // 2 >= 2 for v in shape) and int(np.prod(shape)) > 512:
+                self.agg.append(self.coarsen(self.agg[-1]))
+                shape = tuple(v // 2 for v in shape)
+            if self.native and min(self.agg_shape) >= 4:
+                self.agg_gmg = self.box_solver(box)  # (its paired sweeps and one-launch coarse tail)
 
-            self.agg_gmg = gmg.PoissonGMG(self.agg_shape, self.agg_h2, dtype, device)
-
-    # ---- pieces -------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def weights(n):
-        lo, hi = 1.0 / 3.0, 2.0  # the part of the spectrum of D^-1 A the coarse grid cannot see (gmg.PoissonGMG.weights)
-        mid, half = 0.5 * (hi + lo), 0.5 * (hi - lo)
-        return [1.0 / (mid - half * np.cos(np.pi * (2 * k + 1) / (2 * n))) for k in range(n)]
-
-    def _halo_planes(self, comm, a, lv, planes):
-        """`planes` (1 or 2) boundary planes of `a` into the neighbours' ghost planes nearest the interface."""
-        lo = a[lv.g_lo: lv.g_lo + planes] if self.rank > 0 else None
-        hi = a[lv.g_lo + lv.nz - planes: lv.g_lo + lv.nz] if self.rank < self.world - 1 else None
-        recv_lo, recv_hi = comm.exchange("halo", lo, hi)
-        if recv_lo is not None:
-            a[lv.g_lo - planes: lv.g_lo].copy_(recv_lo.view(planes, lv.ny, lv.nx))
-        if recv_hi is not None:
-            a[lv.g_lo + lv.nz: lv.g_lo + lv.nz + planes].copy_(recv_hi.view(planes, lv.ny, lv.nx))
-
+    # ---- the cycle on the slab levels -----------------------------------------------------------------------------------
     def _smooth(self, comm, l, x, b, zero=False):
         """`nu` sweeps, two per exchange of two planes; returns the tensor holding the iterate (owned planes valid).
         zero: x is zero on every rank -- its ghost planes are right as they are, the first exchange is skipped."""
-        lv, w = self.mlv[l], self.weights(self.nu)
-        k = 0
-        while k < len(w):
+        lv, c, w = self.mlv[l], self.mc[l], gmg.jacobi_weights(3, self.nu)
+        for k in range(0, len(w), 2):
             pair = w[k: k + 2]
-            if not (zero and k == 0):
-                self._halo_planes(comm, x, lv, min(2, lv.nz) if len(pair) == 2 else 1)
-            # (native kernels do not read a zero iterate: u = None -- the bits of the same launch on an array of zeros)
-            src = None if (zero and k == 0 and self.native) else x
-            if (self.native and len(pair) == 2 and self.dtype == torch.float64 and lv.size >= self.pair_min_cells
-                    and self.ops.jacobi2_supported(tuple(x.shape), self.dtype)):
+            first = zero and k == 0
+            if not first:
+                _halo_planes(comm, x, lv, min(2, lv.nz) if len(pair) == 2 else 1)
+            # (native kernels do not read a zero iterate: src = None -- the bits of the same launch on an array of zeros)
+            src = None if (first and self.native) else x
+            if self.native and len(pair) == 2 and lv.size >= self.pair_min_cells and self.pair_supported(x):
                 y = self.spare[l]
-                self.ops.poisson_jacobi2(src, b, self.mh2[l], pair[0], pair[1], out=y)  # (== the two sweeps below, bit for bit)
-                self.spare[l] = x
-                x = y
-                pair = []
+                self.sweep_pair(c, src, b, pair[0], pair[1], y)  # (== the two sweeps below, bit for bit)
+                self.spare[l], x = x, y
+                continue
             for wk in pair:
                 y = self.spare[l]
-                self.ops.poisson_jacobi(src, b, self.mh2[l], wk, out=y)
-                self.spare[l] = x
-                x, src = y, y
-            k += 2
+                self.sweep(c, src, b, wk, y)
+                self.spare[l], x, src = x, y, y
         return x
 
-    def _residual(self, comm, l, x, b, out):
-        """out = A x - b on the owned planes; -> its squared norm over all ranks (finest level only)."""
-        lv = self.mlv[l]
-        self._halo_planes(comm, x, lv, 1)
-        self.ops.poisson_residual(x, b, self.mh2[l], fu=out, loss=self.part, zrange=(lv.g_lo, lv.g_lo + lv.nz), denom=1.0)
-        if l:  # (a coarser level's norm is nobody's measure: no collective, no read-back)
-            return None
-        return float(comm.exchange("gather", self.part.to(torch.float64).reshape(1), None).sum())
+    def _vcycle(self, comm, l, x, b, zero=False):
+        """One V(nu, nu) cycle on level l of the slab hierarchy: returns the tensor holding the iterate (owned planes)."""
+        lv, c = self.mlv[l], self.mc[l]
+        x = self._smooth(comm, l, x, b, zero=zero)
+        r = self.res[l]
+        below = l + 1 < len(self.mlv)
+        coarser = below or self.agg_shape is not None
+        _halo_planes(comm, x, lv, 1)
+        if coarser and self.native and x.shape[0] % 2 == 0 and lv.g_lo % 2 == 0 and self.fused_supported(x):
+            # residual and restriction in ONE pass over the ghost-extended arrays (the fine residual is never stored),
+            # straight into the coarse right-hand side: its owned planes + one plane per interface, formed from the fine
+            # ghost planes, that nobody reads
+            if below:
+                lc = self.mlv[l + 1]
+                target = self.mb[l + 1][lc.g_lo - lv.g_lo // 2: lc.g_lo + lc.nz + lv.g_hi // 2]
+            else:
+                if self._agg_part is None:
+                    self._agg_part = torch.empty(tuple(n // 2 for n in x.shape), dtype=self.dtype, device=self.device)
+                target = self._agg_part
+            self.residual_restrict(c, x, b, target, lv)
+            r = None
+        else:
+            self.level_residual(c, x, b, r, lv)
+        if l == 0:
+            # (the coarser levels' residuals belong to THEIR systems, only the finest one is the solve's measure: no
+            # collective, no read-back below it)
+            self._last_res2 = _rank_sum(comm, self.part if r is None else self.rank_norm(r, lv))
+        if coarser:
+            xc = self._coarse_correction(comm, l, r)
+            y = self.spare[l]
+            self.ops.interp_add(xc.contiguous(), "ccc", add=x, out=y)
+            self.spare[l] = x
+            x = y
+        return self._smooth(comm, l, x, b)
 
-    def _restricted_residual(self, comm, l, x, b, out):
-        """out = -R (A x - b) of level l's owned planes in ONE pass over the ghost-extended arrays (the fine residual is never
-        stored): `out` has half the extended planes -- the owned coarse planes and one plane per interface formed from the
-        fine ghost planes, which nobody reads.  -> the squared norm of A x - b over all ranks' owned planes (finest level
-        only; `odil_poisson_residual_restrict_slab` counts the rank's own planes)."""
-        lv = self.mlv[l]
-        self._halo_planes(comm, x, lv, 1)
-        self.ops.poisson_residual_restrict(x, b, self.mh2[l], -0.125, out, self.part, zrange=(lv.g_lo, lv.g_lo + lv.nz),
-                                           denom=1.0)
-        if l:
-            return None
-        return float(comm.exchange("gather", self.part.to(torch.float64).reshape(1), None).sum())
-
-    def _fused_restriction(self, l, x):
-        lv = self.mlv[l]
-        shape = tuple(x.shape)
-        return (self.native and shape[0] % 2 == 0 and lv.g_lo % 2 == 0
-                and self.ops.residual_restrict_supported(shape, self.dtype))
-
-    def _dense_solve(self, b, h2):
-        """A^-1 b on a box of at most 512 cells (the residual kernel applied to unit vectors, factorised once)."""
-        shape = tuple(b.shape)
-        inv = self._dense.get(shape)
-        if inv is None:
-            n = int(np.prod(shape))
-            eye = torch.eye(n, dtype=self.dtype, device=self.device)
-            zero = torch.zeros(shape, dtype=self.dtype, device=self.device)
-            cols = [self.ops.poisson_residual(eye[j].view(shape).contiguous(), zero, h2)[0].reshape(-1) for j in range(n)]
-            amat = torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)
-            inv = self._dense[shape] = torch.as_tensor(np.linalg.inv(amat), dtype=self.dtype).to(self.device)
-        return (inv @ b.reshape(-1)).view(shape)
-
-    def _local_cycle(self, x, b, h2):
-        """One V(nu, nu) cycle on a WHOLE box held by this rank (the agglomerated coarse problem): returns the iterate."""
-        shape = tuple(b.shape)
-        if int(np.prod(shape)) <= 512 or any(s % 2 or s // 2 < 2 for s in shape):
-            if int(np.prod(shape)) <= 512:
-                return self._dense_solve(b, h2)
-            for _ in range(20):  # (cannot coarsen further: by iteration)
-                for wk in self.weights(2):
-                    x = self.ops.poisson_jacobi(x, b, h2, wk, out=torch.empty_like(x))
-            return x
-        for wk in self.weights(self.nu):
-            x = self.ops.poisson_jacobi(x, b, h2, wk, out=torch.empty_like(x))
-        r, _ = self.ops.poisson_residual(x, b, h2)
-        bc = self.ops.restrict_to_coarser(r, "ccc").mul_(-1.0)
-        xc = self._local_cycle(torch.zeros_like(bc), bc, [v * 4 for v in h2])
-        x = self.ops.interp_add(xc.contiguous(), "ccc", add=x)
-        for wk in self.weights(self.nu):
-            x = self.ops.poisson_jacobi(x, b, h2, wk, out=torch.empty_like(x))
-        return x
+    def _restricted(self, r):
+        """The coarse right-hand side from a stored residual (the mean of the children, with the operator's sign)."""
+        rc = self.ops.restrict_to_coarser(r, "ccc")
+        return rc if self.rhs_sign == 1.0 else rc.mul_(self.rhs_sign)
 
     def _coarse_correction(self, comm, l, r):
-        """x_c with A_c x_c ~= -R r for the residual r = A x - b of level l (owned planes valid); returned on level l + 1's
-        ghost-extended array with owned + inner ghost planes valid."""
-        lv = self.mlv[l]
+        """x_c with A_c x_c ~= the restricted residual of level l (r: the stored residual, owned planes valid; None: the
+        fused pass has written the coarse right-hand side); returned on level l + 1's ghost-extended array with owned +
+        inner ghost planes valid."""
+        lv, twice = self.mlv[l], self.top2(l)
         if l + 1 < len(self.mlv):
             lc = self.mlv[l + 1]
             bc, xc = self.mb[l + 1], self.mx[l + 1]
-            if r is not None:  # (else: `_restricted_residual` has written the owned planes of bc)
-                lc.owned(bc).copy_(self.ops.restrict_to_coarser(lv.owned(r).contiguous(), "ccc")).mul_(-1.0)
-            self._halo_planes(comm, bc, lc, 1)
+            if r is not None:
+                lc.owned(bc).copy_(self._restricted(lv.owned(r).contiguous()))
+            _halo_planes(comm, bc, lc, 1)
             if not self.native:
                 xc.zero_()
             xc = self._vcycle(comm, l + 1, xc, bc, zero=True)
+            if twice:
+                xc = self._vcycle(comm, l + 1, xc, bc)
             self.mx[l + 1] = xc
-            self._halo_planes(comm, xc, lc, 1)
+            _halo_planes(comm, xc, lc, 1)
             return lc.inner(xc)
         # agglomerated: every rank gets the whole coarse right-hand side and solves the whole coarse problem alike
         if r is not None:
-            part = self.ops.restrict_to_coarser(lv.owned(r).contiguous(), "ccc").mul_(-1.0)
+            part = self._restricted(lv.owned(r).contiguous())
         else:
             part = self._agg_part[lv.g_lo // 2: lv.g_lo // 2 + lv.nz // 2]
         bc = comm.exchange("gather", part.contiguous(), None).reshape(self.agg_shape).contiguous()
         if self.agg_gmg is not None:
             xc = self.agg_gmg.vcycle(0, torch.zeros_like(bc), bc, zero=True)
-        else:
-            xc = self._local_cycle(torch.zeros_like(bc), bc, self.agg_h2)
-        nzc = lv.nz // 2
-        lo = self.rank * nzc - (1 if self.rank > 0 else 0)
-        hi = (self.rank + 1) * nzc + (1 if self.rank < self.world - 1 else 0)
-        return xc[lo:hi]
-
-    def _vcycle(self, comm, l, x, b, pre=True, zero=False):
-        """One V(nu, nu) cycle on level l of the slab hierarchy: returns the tensor holding the iterate (owned planes)."""
-        lv = self.mlv[l]
-        if pre:
-            x = self._smooth(comm, l, x, b, zero=zero)
-        r = self.res[l]
-        coarser = l + 1 < len(self.mlv) or self.agg_shape is not None
-        if coarser and self._fused_restriction(l, x):
-            if l + 1 < len(self.mlv):  # straight into the coarse right-hand side: its owned planes + one per interface
-                lc = self.mlv[l + 1]
-                target = self.mb[l + 1][lc.g_lo - lv.g_lo // 2: lc.g_lo + lc.nz + lv.g_hi // 2]
-            else:
-                if getattr(self, "_agg_part", None) is None:
-                    self._agg_part = torch.empty(tuple(n // 2 for n in x.shape), dtype=self.dtype, device=self.device)
-                target = self._agg_part
-            res2 = self._restricted_residual(comm, l, x, b, target)
-            r = None
-        else:
-            res2 = self._residual(comm, l, x, b, r)
-        if l == 0:  # (the coarser levels' residuals belong to THEIR systems: only the finest one is the solve's measure)
-            self._last_res2 = res2
-        if coarser:
-            xc = self._coarse_correction(comm, l, r)
-            y = self.spare[l]
-            self.ops.interp_add(xc.contiguous(), "ccc", add=x, out=y)
-            self.spare[l] = x
-            x = y
-        return self._smooth(comm, l, x, b)
-
-    # ---- the Newton step ----------------------------------------------------------------------------------------------
-    def step(self, comm, maxiter=40, tol=1e-10, damp=0.0):
-        """One Newton step u <- u + delta with A delta = -f(u) by V-cycles; -> (loss before, loss after).
-        self.status: cycles, relative residual of the linear system, converged."""
-        assert not damp, "the multigrid step solves the undamped system"
-        loss0 = self.residual(comm, self.u, self.f)
-        lv = self.lv
-        b = self.z
-        b.copy_(self.f).mul_(-1.0)  # owned planes valid; the neighbours' planes of b follow
-        self._halo_planes(comm, b, lv, 1)
-        bb = float(comm.exchange("gather", (lv.owned(b).to(torch.float64) ** 2).sum().reshape(1), None).sum())
-        x = torch.zeros_like(self.u)
-        it, rel = 0, 1.0
-        while it < maxiter:
-            x = self._vcycle(comm, 0, x, b)
-            it += 1
-            # (the residual a cycle forms on its way down belongs to its pre-smoothed iterate: a cheap, slightly
-            # pessimistic convergence test that costs no pass of its own)
-            rel = float(np.sqrt(self._last_res2 / bb)) if bb > 0 else 0.0
-            if rel <= tol:
-                break
-        self.owned(self.u).add_(self.owned(x))
-        loss1 = self.residual(comm, self.u, self.f)
-        self.status = dict(niter=it, residual=rel, converged=rel <= tol, method="slab gmg-vcycle ({} slab levels{})".format(
-            len(self.mlv), " + agglomerated {}".format(self.agg_shape) if self.agg_shape else ""))
-        return loss0, loss1
-
-
-class SlabStencilGMG:
-    """Geometric multigrid for ANY (2 d + 1)-point operator with variable coefficients on a slab-decomposed 3-D grid -- the
-    slab form of `gmg.StencilGMG` (the Newton system M delta = -r of a single-field operator from its Jacobian's coefficient
-    arrays, reference src/odil/core.py:1113-1217, linsolver.py:17-26; SURVEY 8 E: "Newton: matrix-free M / M^T apply = same
-    halo pattern").  The global grid (world nz, ny, nx) is cut along axis 0, whose two ENDS are walls (zero coefficients
-    towards them; a periodic cut axis would need the ring closure).
-
-    Every rank holds its planes of the 7 coefficient arrays.  Levels are coarsened by 2 along every axis while a rank keeps
-    >= 2 planes and the cross-section >= 4 cells; level arrays and coefficient arrays are ghost-extended (`slab.SlabLevel`,
-    G = 2 planes per interior interface).  Set-up, once per solve (the coefficients change with the state): two boundary
-    planes of the seven arrays to each neighbour (ONE packed message per level); the coarse operators by
-    `odil_stencil_var_coarsen` on the extended arrays -- aggregates of 2^3 cells never straddle an interface, the
-    matrix-symmetric split reads the neighbour's coefficient one plane into the valid ghosts.  Below the last slab level the
-    problem is AGGLOMERATED: coefficient arrays and right-hand side are all-gathered and every rank runs the rest of the
-    cycle on the whole coarse box (the same bits on every rank).  One V(nu, nu) cycle per level, with the unmodified
-    single-GPU kernels on the extended arrays (their periodic wrap at an array end only reaches the outer ghost plane):
-    two planes of x, two sweeps (as ONE pass, `odil_stencil_var_smooth2`, on large levels); one plane of x, the residual on
-    the owned planes (its norm by one all-gather), the mean of the children as the coarse right-hand side, one plane of
-    it; the coarse correction, one plane of it, x += P x_c; two planes, two sweeps."""
-
-    def __init__(self, coeffs, rank, world, ops=None, nu=2, pair_min_cells=128**3, agg_cells=32**3):
-        """agg_cells: as SlabPoissonNewtonGMG -- levels of at most this many cells per rank are not slab levels but part of
-        the agglomerated box (0: slab levels down to two planes per rank)."""
-        assert coeffs.dim() == 4 and coeffs.shape[0] == 7 and coeffs.is_contiguous()
-        self.ops = ops or hip_ops
-        self._native = getattr(self.ops, "__name__", "") == "odil_amd.ops"  # (the library's kernels, not a stand-in)
-        self.rank, self.world, self.nu, self.pair_min_cells = rank, world, nu, pair_min_cells
-        self.dtype, self.device = coeffs.dtype, coeffs.device
-        nz, ny, nx = (int(v) for v in coeffs.shape[1:])
-        shape = (nz, ny, nx)
-        self.mlv = [slab.SlabLevel(nz, ny, nx, rank, world)]
-        while (all(v % 2 == 0 for v in shape) and shape[0] // 2 >= 2 and min(shape[1], shape[2]) // 2 >= 4
-               and int(np.prod(shape)) // 8 > agg_cells):
-            shape = tuple(v // 2 for v in shape)
-            self.mlv.append(slab.SlabLevel(shape[0], shape[1], shape[2], rank, world))
-        self.c_owned = coeffs
-        self.mc = None  # ghost-extended coefficient arrays per slab level, built by setup(comm)
-        self.status = dict()
-
-    @staticmethod
-    def weights(n):
-        lo, hi = 1.0 / 3.0, 2.0  # (gmg.PoissonGMG.weights, d = 3)
-        mid, half = 0.5 * (hi + lo), 0.5 * (hi - lo)
-        return [1.0 / (mid - half * np.cos(np.pi * (2 * k + 1) / (2 * n))) for k in range(n)]
-
-    # ---- exchanges ----------------------------------------------------------------------------------------------------
-    def _halo_planes(self, comm, a, lv, planes):
-        """`planes` boundary planes of `a` ([..., z, y, x]: one array or a stack of arrays) into the neighbours' ghosts."""
-        lo = a[..., lv.g_lo: lv.g_lo + planes, :, :].contiguous() if self.rank > 0 else None
-        hi = a[..., lv.g_lo + lv.nz - planes: lv.g_lo + lv.nz, :, :].contiguous() if self.rank < self.world - 1 else None
-        recv_lo, recv_hi = comm.exchange("halo", lo, hi)
-        if recv_lo is not None:
-            a[..., lv.g_lo - planes: lv.g_lo, :, :].copy_(recv_lo.view(lo.shape))
-        if recv_hi is not None:
-            a[..., lv.g_lo + lv.nz: lv.g_lo + lv.nz + planes, :, :].copy_(recv_hi.view(hi.shape))
-
-    def setup(self, comm):
-        """The operators of every level (see the class text); the agglomerated hierarchy below the last slab level."""
-        mk = lambda lv, lead=(): torch.zeros(tuple(lead) + lv.shape, dtype=self.dtype, device=self.device)
-        self.mc = []
-        c = mk(self.mlv[0], (7,))
-        c[:, self.mlv[0].g_lo: self.mlv[0].g_lo + self.mlv[0].nz].copy_(self.c_owned)
-        self._unit_ghost_diagonal(c, self.mlv[0])
-        self._halo_planes(comm, c, self.mlv[0], min(slab.G, self.mlv[0].nz))
-        self.mc.append(c)
-        for l in range(1, len(self.mlv)):
-            fine, lf, lc = self.mc[-1], self.mlv[l - 1], self.mlv[l]
-            cc_all = self.ops.stencil_var_coarsen(fine.contiguous())
-            c = mk(lc, (7,))
-            c[:, lc.g_lo: lc.g_lo + lc.nz].copy_(cc_all[:, lf.g_lo // 2: lf.g_lo // 2 + lc.nz])
-            self._unit_ghost_diagonal(c, lc)
-            self._halo_planes(comm, c, lc, min(slab.G, lc.nz))
-            self.mc.append(c)
-        self.mx = [None] + [mk(lv) for lv in self.mlv[1:]]
-        self.mb = [None] + [mk(lv) for lv in self.mlv[1:]]
-        self.spare = [mk(lv) for lv in self.mlv]
-        self.res = [mk(lv) for lv in self.mlv]
-        # the agglomerated box: every rank gets the whole coarse operator of the level below the last slab level
-        last, ll = self.mc[-1], self.mlv[-1]
-        self.agg = None
-        if ll.nz % 2 == 0 and ll.ny % 2 == 0 and ll.nx % 2 == 0 and min(ll.ny, ll.nx) >= 4:
-            cc_all = self.ops.stencil_var_coarsen(last.contiguous())
-            part = cc_all[:, ll.g_lo // 2: ll.g_lo // 2 + ll.nz // 2].contiguous()
-            rows = comm.exchange("gather", part, None)  # (world, 7, nz / 2, ny / 2, nx / 2)
-            whole = torch.cat([rows[r] for r in range(self.world)], dim=1).contiguous()
-            self.agg = [whole]
-            while all(v % 2 == 0 and v // 2 >= 2 for v in self.agg[-1].shape[1:]) and self.agg[-1][0].numel() > 512:
-                self.agg.append(self.ops.stencil_var_coarsen(self.agg[-1]))
-            self._agg_inv = None
-            # with the library's own kernels underneath, the box is cycled by the single-GPU solver (its paired sweeps and
-            # one-launch coarse tail); a stand-in `ops` (the host tests) keeps the plain recursion of `_agg_cycle`
-            self.agg_gmg = None
-            if getattr(self.ops, "__name__", "") == "odil_amd.ops" and min(whole.shape[1:]) >= 4:
-                from . import gmg
-
-                self.agg_gmg = gmg.StencilGMG(whole)
-        self.part = torch.zeros((), dtype=self.dtype, device=self.device)
-
-    @staticmethod
-    def _unit_ghost_diagonal(c, lv):
-        """Ghost rows that no neighbour fills (the outer planes of a thin level) keep a unit diagonal: the sweeps divide by it."""
-        if lv.g_lo:
-            c[0, : lv.g_lo].fill_(1.0)
-        if lv.g_hi:
-            c[0, lv.g_lo + lv.nz:].fill_(1.0)
-
-    # ---- pieces -------------------------------------------------------------------------------------------------------
-    def _sweeps(self, l, x, b, weights, zero=False):
-        """zero (the library's own kernels only): the iterate is the zero vector -- the first launch does not read x."""
-        c, size = self.mc[l], self.mlv[l].size
-        weights = list(weights)
-        pair = hasattr(self.ops, "stencil_var_smooth2") and size >= self.pair_min_cells and x.shape[-1] % 2 == 0
-        while weights:
-            y = self.spare[l]
-            src = None if zero else x
-            zero = False
-            if pair and len(weights) >= 2:
-                self.ops.stencil_var_smooth2(c, src, b, weights[0], weights[1], out=y)
-                weights = weights[2:]
-            else:
-                self.ops.stencil_var_smooth(c, src, b, weights[0], out=y)
-                weights = weights[1:]
-            self.spare[l] = x
-            x = y
-        return x
-
-    def _smooth(self, comm, l, x, b, zero=False):
-        lv, w = self.mlv[l], self.weights(self.nu)
-        k = 0
-        while k < len(w):
-            pair = w[k: k + 2]
-            if not (zero and k == 0):  # (a zero iterate has the right ghost planes on every rank)
-                self._halo_planes(comm, x, lv, min(2, lv.nz) if len(pair) == 2 else 1)
-            x = self._sweeps(l, x, b, pair, zero=zero and k == 0 and self._native)
-            k += 2
-        return x
-
-    def _residual(self, comm, l, x, b, out):
-        """out = b - A x on the owned planes; -> its squared norm over all ranks (finest level only)."""
-        lv = self.mlv[l]
-        self._halo_planes(comm, x, lv, 1)
-        self.ops.stencil_var_residual(self.mc[l], x, b, out=out)
-        if l:  # (a coarser level's norm is nobody's measure: no collective, no read-back)
-            return None
-        mine = (lv.owned(out).to(torch.float64) ** 2).sum().reshape(1)
-        return float(comm.exchange("gather", mine, None).sum())
-
-    def _agg_cycle(self, k, x, b):
-        """One V(nu, nu) cycle on level k of the agglomerated hierarchy (the whole coarse box on this rank)."""
-        c = self.agg[k]
-        if k == len(self.agg) - 1:
-            if self._agg_inv is None:
-                shape = tuple(c.shape[1:])
-                n = int(np.prod(shape))
-                eye = torch.eye(n, dtype=self.dtype, device=self.device)
-                zero = torch.zeros(shape, dtype=self.dtype, device=self.device)
-                cols = [-self.ops.stencil_var_residual(c, eye[j].view(shape).contiguous(), zero).reshape(-1) for j in range(n)]
-                amat = torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)
-                self._agg_inv = torch.as_tensor(np.linalg.pinv(amat, rcond=1e-12), dtype=self.dtype).to(self.device)
-            return (self._agg_inv @ b.reshape(-1)).view(b.shape)
-        for wk in self.weights(self.nu):
-            x = self.ops.stencil_var_smooth(c, x, b, wk, out=torch.empty_like(x))
-        r = self.ops.stencil_var_residual(c, x, b)
-        bc = self.ops.restrict_to_coarser(r, "ccc")
-        xc = self._agg_cycle(k + 1, torch.zeros_like(bc), bc.contiguous())
-        x = self.ops.interp_add(xc.contiguous(), "ccc", add=x)
-        for wk in self.weights(self.nu):
-            x = self.ops.stencil_var_smooth(c, x, b, wk, out=torch.empty_like(x))
-        return x
-
-    def _coarse_correction(self, comm, l, r):
-        lv = self.mlv[l]
-        if l + 1 < len(self.mlv):
-            lc = self.mlv[l + 1]
-            bc, xc = self.mb[l + 1], self.mx[l + 1]
-            if r is not None:  # (else: the fused pass has written the owned planes of bc)
-                lc.owned(bc).copy_(self.ops.restrict_to_coarser(lv.owned(r).contiguous(), "ccc"))
-            self._halo_planes(comm, bc, lc, 1)
-            if not self._native:
-                xc.zero_()
-            xc = self._vcycle(comm, l + 1, xc, bc, zero=True)
-            if l == 0 and len(self.mlv) + (len(self.agg) if self.agg else 0) > 2:
-                # TWO cycles on the first coarse level, as gmg.StencilGMG.finish_cycle: the aggregation-built coarse
-                # operators are less accurate at the walls than a rediscretisation (0.24 -> 0.14 per cycle there)
-                xc = self._vcycle(comm, l + 1, xc, bc)
-            self.mx[l + 1] = xc
-            self._halo_planes(comm, xc, lc, 1)
-            return lc.inner(xc)
-        if r is not None:
-            part = self.ops.restrict_to_coarser(lv.owned(r).contiguous(), "ccc")
-        else:
-            part = self._agg_part[lv.g_lo // 2: lv.g_lo // 2 + lv.nz // 2]
-        bc = comm.exchange("gather", part.contiguous(), None).reshape(tuple(self.agg[0].shape[1:]))
-        bc = bc.contiguous()
-        # (the box is the FIRST coarse level when there is one slab level: two cycles there, as above)
-        twice = l == 0 and len(self.agg) > 1
-        if self.agg_gmg is not None:
-            xc = self.agg_gmg.vcycle(0, torch.zeros_like(bc), bc, zero=True)
             if twice:
                 xc = self.agg_gmg.vcycle(0, xc, bc)
         else:
-            xc = self._agg_cycle(0, torch.zeros_like(bc), bc)
+            xc = self._box_cycle(0, torch.zeros_like(bc), bc)
             if twice:
-                xc = self._agg_cycle(0, xc, bc)
+                xc = self._box_cycle(0, xc, bc)
         nzc = lv.nz // 2
         lo = self.rank * nzc - (1 if self.rank > 0 else 0)
         hi = (self.rank + 1) * nzc + (1 if self.rank < self.world - 1 else 0)
         return xc[lo:hi]
 
-    def _vcycle(self, comm, l, x, b, zero=False):
-        x = self._smooth(comm, l, x, b, zero=zero)
-        r, lv = self.res[l], self.mlv[l]
-        coarser = l + 1 < len(self.mlv) or self.agg is not None
-        if (coarser and getattr(self.ops, "__name__", "") == "odil_amd.ops" and x.shape[0] % 2 == 0 and lv.g_lo % 2 == 0
-                and x.shape[2] % 2 == 0):
-            # residual and restriction in ONE pass over the ghost-extended arrays (the fine residual is never stored),
-            # straight into the coarse right-hand side: its owned planes + one plane per interface that nobody reads
-            if l + 1 < len(self.mlv):
-                lc = self.mlv[l + 1]
-                target = self.mb[l + 1][lc.g_lo - lv.g_lo // 2: lc.g_lo + lc.nz + lv.g_hi // 2]
-            else:
-                if getattr(self, "_agg_part", None) is None:
-                    self._agg_part = torch.empty(tuple(n // 2 for n in x.shape), dtype=self.dtype, device=self.device)
-                target = self._agg_part
-            self._halo_planes(comm, x, lv, 1)
-            self.ops.stencil_var_residual_restrict(self.mc[l], x, b, 0.125, target, self.part,
-                                                   zrange=(lv.g_lo, lv.g_lo + lv.nz), denom=1.0)
-            res2 = None if l else float(comm.exchange("gather", self.part.to(torch.float64).reshape(1), None).sum())
-            r = None
-        else:
-            res2 = self._residual(comm, l, x, b, r)
-        if l == 0:
-            self._last_res2 = res2
-        if coarser:
-            xc = self._coarse_correction(comm, l, r)
-            y = self.spare[l]
-            self.ops.interp_add(xc.contiguous(), "ccc", add=x, out=y)
-            self.spare[l] = x
-            x = y
-        return self._smooth(comm, l, x, b)
+    def _box_cycle(self, k, x, b):
+        """One V(nu, nu) cycle on level k of the agglomerated box, held whole by this rank, by plain launches (a stand-in
+        `ops`; the library's own kernels go through `box_solver`): returns the iterate."""
+        c = self.agg[k]
+        if k == len(self.agg) - 1:
+            if b.numel() > 512:  # (cannot coarsen further: by iteration)
+                for _ in range(20):
+                    for wk in gmg.jacobi_weights(3, 2):
+                        x = self.sweep(c, x, b, wk, torch.empty_like(x))
+                return x
+            if self._box_inv is None:  # (the residual kernel applied to unit vectors, factorised once)
+                n = b.numel()
+                eye = torch.eye(n, dtype=self.dtype, device=self.device)
+                zero = torch.zeros_like(b)
+                cols = [self.level_residual(c, eye[j].view(b.shape).contiguous(), zero).reshape(-1) for j in range(n)]
+                amat = -self.rhs_sign * torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)  # column j = A e_j
+                self._box_inv = torch.as_tensor(self.invert(amat), dtype=self.dtype).to(self.device)
+            return (self._box_inv @ b.reshape(-1)).view(b.shape)
+        for wk in gmg.jacobi_weights(3, self.nu):
+            x = self.sweep(c, x, b, wk, torch.empty_like(x))
+        bc = self._restricted(self.level_residual(c, x, b))
+        xc = self._box_cycle(k + 1, torch.zeros_like(bc), bc)
+        x = self.ops.interp_add(xc.contiguous(), "ccc", add=x)
+        for wk in gmg.jacobi_weights(3, self.nu):
+            x = self.sweep(c, x, b, wk, torch.empty_like(x))
+        return x
 
-    def solve(self, comm, b_owned, tol=1e-10, maxiter=40, stall=False):
-        """x (owned planes) with A x = b to |b - A x| <= tol |b| over all ranks; self.status: niter, residual, converged.
-        stall=True: also stop where the cycles stopped gaining -- from the fourth cycle on, a residual above 0.98 of the
-        previous cycle's (the rule of gmg.StencilGMG.solve, counted in cycles done) -- and say so in status["stagnated"]
-        (below 1: the rounding floor of the working precision, not divergence)."""
-        if self.mc is None:
-            self.setup(comm)
+    def _cycles(self, comm, b, tol, maxiter, stall):
+        """V-cycles from the zero iterate on A x = b (b: level 0's ghost-extended array, owned planes valid) until
+        |residual| <= tol |b| over all ranks; returns the tensor holding x and leaves self.status: niter, residual,
+        converged, stagnated, method.  stall=True: also stop where the cycles stopped gaining -- from the fourth cycle on, a
+        residual above 0.98 of the previous cycle's (the rule of gmg.StencilGMG.solve, counted in cycles done) -- and say
+        so in status["stagnated"] (below 1: the rounding floor of the working precision, not divergence)."""
         lv = self.mlv[0]
-        b = torch.zeros(lv.shape, dtype=self.dtype, device=self.device)
-        lv.owned(b).copy_(b_owned)
-        self._halo_planes(comm, b, lv, 1)
-        bb = float(comm.exchange("gather", (b_owned.to(torch.float64) ** 2).sum().reshape(1), None).sum())
+        _halo_planes(comm, b, lv, 1)
+        bb = _rank_sum(comm, (lv.owned(b).to(torch.float64) ** 2).sum())
         x = torch.zeros_like(b)
         it, rel, stagnated = 0, 1.0, False
         while it < maxiter:
             x = self._vcycle(comm, 0, x, b)
             it += 1
-            prev, rel = rel, float(np.sqrt(self._last_res2 / bb)) if bb > 0 else 0.0  # (of the cycle's pre-smoothed iterate)
+            # (the residual a cycle forms on its way down belongs to its pre-smoothed iterate: a cheap, slightly
+            # pessimistic convergence test that costs no pass of its own)
+            prev, rel = rel, float(np.sqrt(self._last_res2 / bb)) if bb > 0 else 0.0
             if rel <= tol:
                 break
             if stall and it > 3 and rel >= 0.98 * prev:
                 stagnated = rel == rel and rel < 1.0  # (not: diverging; the same numbers, so the same branch, on every rank)
                 break
-        self.status = dict(niter=it, residual=rel, converged=rel <= tol, stagnated=stagnated, method="slab variable-coefficient gmg ({} slab levels{})".format(
-            len(self.mlv), " + agglomerated {}".format(tuple(self.agg[0].shape[1:])) if self.agg else ""))
-        return lv.owned(x).clone()
+        self.status = dict(niter=it, residual=rel, converged=rel <= tol, stagnated=stagnated, method="{} ({} slab levels{})".format(
+            self.method, len(self.mlv), " + agglomerated {}".format(self.agg_shape) if self.agg_shape else ""))
+        return x
+
+
+class SlabPoissonNewtonGMG(SlabVCycle, SlabPoissonNewtonCG):
+    """The Newton step of the slab-decomposed Poisson problem solved by `SlabVCycle` -- the slab form of `gmg.PoissonGMG`
+    ("Newton: matrix-free M / M^T apply = same halo pattern"; the reference's Newton driver,
+    src/odil/util.py:152-187, solves M^T M delta = -M^T f with SuperLU, linsolver.py:17-26; for the square nonsingular
+    Laplacian M delta = -f has the same solution).  `SlabPoissonNewtonCG` above is unpreconditioned CG on the normal
+    equations: O(N) iterations; this one needs ~12 cycles at any size.  Level data: the squared spacings (the same stencil
+    rediscretised); the residual is A x - b, its norm over the rank's own planes formed by the kernels."""
+
+    rhs_sign = -1.0
+    method = "slab gmg-vcycle"
+
+    def __init__(self, N, rank, world, dtype=torch.float64, device=None, rhs_global=None, nz=None, nu=2, agg_cells=32**3,
+                 pair_min_cells=128**3):
+        """agg_cells: see `SlabVCycle._plan`."""
+        super().__init__(N, rank, world, dtype=dtype, device=device, rhs_global=rhs_global, nz=nz)
+        self.nu, self.pair_min_cells = nu, pair_min_cells
+        self._plan(self.lv, agg_cells)
+        self.mc = [list(self.h2)]
+        for _ in self.mlv[1:]:
+            self.mc.append(self.coarsen(self.mc[-1]))
+        self._finish_setup(self.coarsen(self.mc[-1]) if self.agg_shape else None)
+
+    def sweep(self, h2, src, b, w, out):
+        return self.ops.poisson_jacobi(src, b, h2, w, out=out)
+
+    def sweep_pair(self, h2, src, b, w1, w2, out):
+        self.ops.poisson_jacobi2(src, b, h2, w1, w2, out=out)  # (`odil_poisson_jacobi2`)
+
+    def pair_supported(self, x):
+        return self.dtype == torch.float64 and self.ops.jacobi2_supported(tuple(x.shape), self.dtype)
+
+    def level_residual(self, h2, x, b, out=None, lv=None):
+        """A x - b."""
+        return self.ops.poisson_residual(x, b, h2, fu=out, loss=self.part, denom=1.0,
+                                         zrange=None if lv is None else (lv.g_lo, lv.g_lo + lv.nz))[0]
+
+    def rank_norm(self, r, lv):
+        return self.part
+
+    def residual_restrict(self, h2, x, b, out, lv):
+        """(`odil_poisson_residual_restrict_slab` counts the rank's own planes)"""
+        self.ops.poisson_residual_restrict(x, b, h2, 0.125 * self.rhs_sign, out, self.part,
+                                           zrange=(lv.g_lo, lv.g_lo + lv.nz), denom=1.0)
+
+    def fused_supported(self, x):
+        return self.ops.residual_restrict_supported(tuple(x.shape), self.dtype)
+
+    def coarsen(self, h2):
+        return [v * 4 for v in h2]
+
+    def box_solver(self, h2):
+        return gmg.PoissonGMG(self.agg_shape, h2, self.dtype, self.device)
+
+    invert = staticmethod(gmg.PoissonGMG.invert)
+
+    def top2(self, l):
+        return False
+
+    def step(self, comm, maxiter=40, tol=1e-10, damp=0.0):
+        """One Newton step u <- u + delta with A delta = -f(u) by V-cycles; -> (loss before, loss after).
+        self.status: cycles, relative residual of the linear system, converged."""
+        assert not damp, "the multigrid step solves the undamped system"
+        loss0 = self.residual(comm, self.u, self.f)
+        b = self.z
+        b.copy_(self.f).mul_(-1.0)  # owned planes valid; the neighbours' planes of b follow
+        x = self._cycles(comm, b, tol, maxiter, stall=False)  # (to tol or maxiter: no stall rule for this step)
+        self.owned(self.u).add_(self.owned(x))
+        loss1 = self.residual(comm, self.u, self.f)
+        return loss0, loss1
+
+
+class SlabStencilGMG(SlabVCycle):
+    """`SlabVCycle` for ANY (2 d + 1)-point operator with variable coefficients -- the slab form of `gmg.StencilGMG` (the
+    Newton system M delta = -r of a single-field operator from its Jacobian's coefficient arrays, reference
+    src/odil/core.py:1113-1217, linsolver.py:17-26; SURVEY 8 E: "Newton: matrix-free M / M^T apply = same halo pattern").
+    The operator has zero coefficients towards the two ends of the cut axis (a periodic cut axis would need the ring
+    closure).
+
+    Every rank holds its planes of the 7 coefficient arrays; level data are the ghost-extended coefficient arrays.  Set-up,
+    once per solve (the coefficients change with the state): two boundary planes of the seven arrays to each neighbour
+    (ONE packed message per level); the coarse operators by `odil_stencil_var_coarsen` on the extended arrays --
+    aggregates of 2^3 cells never straddle an interface, the matrix-symmetric split reads the neighbour's coefficient one
+    plane into the valid ghosts; for the agglomerated box the coefficient arrays are all-gathered.  The residual is
+    b - A x, the coarse right-hand side the mean of its children."""
+
+    rhs_sign = 1.0
+    method = "slab variable-coefficient gmg"
+
+    def __init__(self, coeffs, rank, world, ops=None, nu=2, pair_min_cells=128**3, agg_cells=32**3):
+        """agg_cells: see `SlabVCycle._plan`."""
+        assert coeffs.dim() == 4 and coeffs.shape[0] == 7 and coeffs.is_contiguous()
+        self.ops = ops or hip_ops
+        self.rank, self.world, self.nu, self.pair_min_cells = rank, world, nu, pair_min_cells
+        self.dtype, self.device = coeffs.dtype, coeffs.device
+        nz, ny, nx = (int(v) for v in coeffs.shape[1:])
+        self._plan(slab.SlabLevel(nz, ny, nx, rank, world), agg_cells)
+        self.c_owned = coeffs
+        self.mc = None  # ghost-extended coefficient arrays per slab level, built by setup(comm)
+        self.status = dict()
+
+    def setup(self, comm):
+        """The operators of every level (see the class text); the agglomerated hierarchy below the last slab level."""
+        self.mc = []
+        for l, lc in enumerate(self.mlv):
+            # (level 0: the caller's arrays; below: the coarsened extended arrays of the level above, its owned planes' part)
+            cc_all, first = (self.coarsen(self.mc[-1]), self.mlv[l - 1].g_lo // 2) if l else (self.c_owned, 0)
+            c = torch.zeros((7,) + lc.shape, dtype=self.dtype, device=self.device)
+            c[:, lc.g_lo: lc.g_lo + lc.nz].copy_(cc_all[:, first: first + lc.nz])
+            # ghost rows that no neighbour fills (the outer planes of a thin level) keep a unit diagonal: the sweeps divide by it
+            if lc.g_lo:
+                c[0, : lc.g_lo].fill_(1.0)
+            if lc.g_hi:
+                c[0, lc.g_lo + lc.nz:].fill_(1.0)
+            _halo_planes(comm, c, lc, min(slab.G, lc.nz))
+            self.mc.append(c)
+        # the agglomerated box: every rank gets the whole coarse operator of the level below the last slab level
+        whole = None
+        if self.agg_shape is not None:
+            last = self.mlv[-1]
+            part = self.coarsen(self.mc[-1])[:, last.g_lo // 2: last.g_lo // 2 + last.nz // 2].contiguous()
+            rows = comm.exchange("gather", part, None)  # (world, 7, nz / 2, ny / 2, nx / 2)
+            whole = torch.cat([rows[r] for r in range(self.world)], dim=1).contiguous()
+        self._finish_setup(whole)
+
+    def sweep(self, c, src, b, w, out):
+        return self.ops.stencil_var_smooth(c, src, b, w, out=out)
+
+    def sweep_pair(self, c, src, b, w1, w2, out):
+        self.ops.stencil_var_smooth2(c, src, b, w1, w2, out=out)  # (`odil_stencil_var_smooth2`)
+
+    def pair_supported(self, x):
+        return x.shape[-1] % 2 == 0
+
+    def level_residual(self, c, x, b, out=None, lv=None):
+        """b - A x."""
+        return self.ops.stencil_var_residual(c, x, b, out=out)
+
+    def rank_norm(self, r, lv):
+        return (lv.owned(r).to(torch.float64) ** 2).sum()
+
+    def residual_restrict(self, c, x, b, out, lv):
+        self.ops.stencil_var_residual_restrict(c, x, b, 0.125 * self.rhs_sign, out, self.part,
+                                               zrange=(lv.g_lo, lv.g_lo + lv.nz), denom=1.0)
+
+    def fused_supported(self, x):
+        return x.shape[2] % 2 == 0
+
+    def coarsen(self, c):
+        return self.ops.stencil_var_coarsen(c.contiguous())
+
+    def box_solver(self, c):
+        return gmg.StencilGMG(c)
+
+    invert = staticmethod(gmg.StencilGMG.invert)
+
+    def top2(self, l):
+        """TWO cycles on the first coarse level (a slab level or the agglomerated box) when there is a level below it, as
+        gmg.StencilGMG.finish_cycle: the aggregation-built coarse operators are less accurate at the walls than a
+        rediscretisation (0.24 -> 0.14 per cycle there)."""
+        return l == 0 and len(self.mlv) + len(self.agg or ()) > 2
+
+    def solve(self, comm, b_owned, tol=1e-10, maxiter=40, stall=False):
+        """x (owned planes) with A x = b to |b - A x| <= tol |b| over all ranks; self.status and `stall`: `_cycles`."""
+        if self.mc is None:
+            self.setup(comm)
+        lv = self.mlv[0]
+        b = torch.zeros(lv.shape, dtype=self.dtype, device=self.device)
+        lv.owned(b).copy_(b_owned)
+        return lv.owned(self._cycles(comm, b, tol, maxiter, stall)).clone()
 
 
 class ReplicatedTailVectors(SlabLbfgsVectors):
