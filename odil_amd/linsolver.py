@@ -4,23 +4,24 @@ the device and matrix-free.
 The reference forms A = M^T M (+ damp^2 I + dampdiag^2 diag(A)) and b = M^T rhs with
 scipy.sparse and factorises A with SuperLU (`direct`, linsolver.py:17-26) or hands it to an
 iterative routine.  Here M stays a `core.LinearizedOperator` (per-shift coefficient
-arrays + dense blocks), A is applied as M^T (M x) with the HIP stencil kernels and the
-system is solved by Jacobi-preconditioned conjugate gradients with deterministic dot
-products (odil_dots) and no host synchronisation inside the iteration.  `direct` is a dense
-Cholesky of A = M^T M up to 49152 unknowns, memory permitting (one f64 GEMM + rocSOLVER, `dense_normal`), geometric
-multigrid for the recognised stencils beyond the dense factorisation's reach (gmg.py), and otherwise "CG to
-round-off" (tol 1e-14 relative, bounded by `--linsolver_maxiter` if given, else 20 n), which
-reproduces the reference's Newton iterate to solver tolerance; `cg` / `bicgstab` / `multigrid`
-use `--linsolver_tol`.  `multigrid` on systems of grid fields that no earlier route takes (several fields, mixed locations,
-non-square or damped M) is CG preconditioned by V-cycles on the normal equations (gmg.NormalGMG).
-cupy / sparseqr / pyamg variants of the reference are optional third-party paths and are
-not provided.
+arrays + dense blocks), A is applied as M^T (M x) with the HIP stencil kernels, and `solve` tries the solvers of
+this module in the order of the table ROUTES: geometric multigrid on M itself (gmg.py), the exact solvers of
+`direct` (substitution, block cyclic reduction, Schur complement, dense Cholesky), CG preconditioned by V-cycles on the
+normal equations (gmg.NormalGMG), and last Jacobi-preconditioned conjugate gradients with deterministic dot products
+(odil_dots) and no host synchronisation inside the iteration.  cupy / sparseqr / pyamg variants of the reference are
+optional third-party paths and are not provided.
 """
+
+import copy
+import os
+import types
 
 import numpy as np
 import torch
 
-from . import ops
+from . import blocktri, gmg, ops
+from .core import Field, LinearizedOperator
+from .util import printlog
 
 
 def _dot(a, b):
@@ -223,8 +224,6 @@ def schur_normal(op, rhs, damp=0.0, dampdiag=0.0, maxiter=None, status=None, inn
             return None
         niter = 0
     else:
-        import copy
-
         op_s = copy.copy(op)
         op_s.blocks = stencil_blocks
         dt = daug.t().contiguous()  # (p + 1) x rows: the columns of [D | r] as contiguous vectors
@@ -270,9 +269,6 @@ def blocktri_normal(op, rhs, damp=0.0, dampdiag=0.0, status=None):
     (implicit time stepping: reference examples/heat/heat.py:36-137): the normal equations (reference
     linsolver.py:17-26) by block cyclic reduction (blocktri.py), dense `NeuralNet` / `Array` columns through the
     Schur complement.  None when the structure is not there (the caller goes on to the general routes)."""
-    from . import blocktri
-    from .core import Field
-
     keys = {key for _, _, kind, key, _ in op.blocks if kind == "stencil"}
     if len(keys) != 1:
         return None
@@ -293,8 +289,6 @@ def blocktri_normal(op, rhs, damp=0.0, dampdiag=0.0, status=None):
         # error, a shape bug or an assertion is a defect and must not hide behind a slower solver
         if not (isinstance(e, (MemoryError, torch.cuda.OutOfMemoryError)) or "out of memory" in str(e).lower()):
             raise
-        from .util import printlog
-
         printlog("odil_amd: block cyclic reduction ran out of memory ({}); using the matrix-free routes".format(str(e).splitlines()[0]))
         return None
     if not inner.ok:
@@ -324,8 +318,6 @@ def recognise_marching(op):
     field and is triangular along one axis with only the unknown itself on the diagonal block -- the Jacobian of
     an operator that is explicit in time (examples/wave: shifts (0, 0), (-1, 0), (-2, 0), (-1, +-1)) -- and no
     coefficient wraps around the ends of that axis; None otherwise."""
-    from .core import Field
-
     if len(op.key_to_field) != 1 or op.nrows != op.ncols:
         return None
     (key, field), = op.key_to_field.items()
@@ -377,21 +369,6 @@ def march_solve(rec, rhs, status=None):
     return x.reshape(-1)
 
 
-SCHUR_MIN_UNKNOWNS = 16384  # systems with dense columns: Schur complement above this size, dense Cholesky below
-DENSE_MAX_UNKNOWNS = 49152  # `direct` factorises the dense normal matrix up to here, memory permitting
-
-
-def _dense_fits(op):
-    """M (rows x unknowns), A = M^T M and the Cholesky factor as dense matrices must fit comfortably:
-    16384 unknowns take 6 GB in f64, 49152 take 58 GB of the 288 GB of an MI355X."""
-    if op.ncols > DENSE_MAX_UNKNOWNS:
-        return False
-    esize = 8 if op.dtype == torch.float64 else 4
-    need = (op.nrows * op.ncols + 2 * op.ncols * op.ncols) * esize
-    free = torch.cuda.mem_get_info(op.device)[0] if op.device.type == "cuda" else 0
-    return need <= 0.5 * free
-
-
 def dense_normal(op, rhs, damp=0.0, dampdiag=0.0, status=None):
     """`direct` for small systems, as the reference's SuperLU solve of A = M^T M (linsolver.py:17-26):
     M is scattered into a dense device matrix, A = M^T M is one f64 GEMM (rocBLAS, the only
@@ -421,258 +398,306 @@ def dense_normal(op, rhs, damp=0.0, dampdiag=0.0, status=None):
     return x
 
 
-def solve(matr, rhs, args, status=None, linsolver="direct", consume=False):
-    """Reference signature (linsolver.py:4).  `matr` is a `core.LinearizedOperator`; returns the
-    solution as a device vector.  consume=True (the Newton driver): the result may be a work buffer of the solver, valid
-    until the next solve -- no copy of it is made."""
-    from .core import LinearizedOperator
-
-    if status is None:
-        status = dict()
-    if not isinstance(matr, LinearizedOperator):
-        raise TypeError(
-            "odil_amd.linsolver.solve expects the device operator returned by Problem.linearize_device(); "
-            "got {} (host sparse matrices are not solved here: there is no CPU path)".format(type(matr).__name__)
-        )
-    maxiter = getattr(args, "linsolver_maxiter", None)
-    damp = getattr(args, "linsolver_damp", 0) or 0
-    dampdiag = getattr(args, "linsolver_dampdiag", 0) or 0
-    tol = getattr(args, "linsolver_tol", 1e-10)
-    if not torch.is_tensor(rhs):
-        rhs = torch.as_tensor(np.asarray(rhs), dtype=matr.dtype, device=matr.device)
-    if linsolver not in ("direct", "directsq", "cg", "bicgstab", "multigrid", "lsqr"):
-        raise ValueError("Unknown linsolver=" + linsolver)
-    # Square Poisson stencil without damping: M d = rhs has the solution of the normal equations
-    # and is solved by geometric multigrid V-cycles (gmg.py) -- the only option that scales to
-    # 512^3.  `multigrid` always takes it when it applies, `direct` beyond the reach of the dense factorisation (49152
-    # unknowns; up to round 5 only above 2e5, and 256^2 or N = 100000 in 1-D went to 45000 - 50000 CG iterations).
-    if not damp and not dampdiag and (linsolver == "multigrid" or (linsolver == "direct" and matr.ncols > DENSE_MAX_UNKNOWNS)):
-        import os
-
-        from . import gmg
-
-        # ODIL_GMG = auto (default) | poisson | stencil: `stencil` sends even the constant-coefficient Laplacian through
-        # the variable-coefficient cycle (measurement, tests), `poisson` switches that cycle off
-        mode = os.environ.get("ODIL_GMG", "auto")
-        gtol = 1e-12 if linsolver == "direct" else tol
-        # ODIL_GMG_MIXED=1: float32 V-cycles inside a float64 residual loop (gmg.solve_mixed; float64 problems only)
-        mixed = matr.dtype == torch.float64 and bool(int(os.environ.get("ODIL_GMG_MIXED", 0)))
-        rec = gmg.recognise_poisson(matr) if mode != "stencil" else None
-        if rec is not None:
-            shape, h2 = rec
-            sub = dict()
-            if mixed and all(n % 2 == 0 for n in shape):  # (an odd finest level is solved by GCR in one precision)
-                x = gmg.solve_mixed(gmg.PoissonGMG(shape, h2, matr.dtype, matr.device, lite=True),
-                                    gmg.PoissonGMG(shape, h2, torch.float32, matr.device),
-                                    rhs.reshape(shape).contiguous(), tol=gtol, maxiter=maxiter or 60, status=sub)
-            else:
-                # (the constant-coefficient solver depends on shape, spacing and dtype only: kept with the domain, so that the
-                # next Newton step finds its level buffers and coarsest-grid inverse)
-                cache = matr.domain.__dict__.setdefault("_poisson_gmg", dict())
-                key = (tuple(shape), tuple(float(v) for v in h2), matr.dtype, str(matr.device))
-                solver = cache.get(key)
-                if solver is None:
-                    cache.clear()
-                    solver = cache[key] = gmg.PoissonGMG(shape, h2, matr.dtype, matr.device)
-                x = solver.solve(rhs.reshape(shape).contiguous(), tol=gtol, maxiter=maxiter or 60, status=sub, copy=not consume)
-            # cells far from cubes (point smoothing with full coarsening loses its rate) can leave the cycles short of the
-            # tolerance: the iterate is then handed to the normal-equation CG below as its starting point, not returned
-            bnorm = sub["bnorm"] if "bnorm" in sub else float(_dot(rhs, rhs)) ** 0.5
-            if sub.get("converged", True) or sub.get("residual", 0.0) <= 1e-6 * bnorm or (
-                    sub.get("stagnated") and sub.get("residual", 0.0) <= 1e-3 * bnorm):
-                status.update(sub)
-                return x.reshape(-1)
-            from .util import printlog
-
-            printlog("odil_amd: Poisson multigrid stopped at relative residual {:.1e}; finishing with CG on the normal equations".format(
-                sub.get("residual", float("nan")) / max(float(_dot(rhs, rhs)) ** 0.5, 1e-300)))
-            return cg_normal(matr, rhs, tol=min(gtol, 1e-10), maxiter=maxiter, status=status, x0=x.reshape(-1))
-        # Any other square (2 d + 1)-point operator on one cell-centred field (variable-coefficient diffusion, reaction,
-        # convection, other wall closures): V-cycles on its own coefficient arrays.  M d = rhs is solved, which for a
-        # nonsingular square M is the solution of the normal equations; cycles that do not contract hand over to the
-        # normal-equation routes below.
-        coeffs = gmg.recognise_stencil(matr) if mode != "poisson" else None
-        if coeffs is not None:
-            sub = dict()
-            mixed = mixed and all(n % 2 == 0 for n in coeffs.shape[1:])
-            if mixed:
-                solver = gmg.StencilGMG(coeffs, store=torch.float32)
-                x = gmg.solve_mixed(gmg.StencilGMG(coeffs, lite=True), solver, rhs.reshape(tuple(coeffs.shape[1:])).contiguous(),
-                                    tol=gtol, maxiter=maxiter or 60, status=sub)
-            else:
-                solver = gmg.StencilGMG(coeffs)
-                x = solver.solve(rhs.reshape(tuple(coeffs.shape[1:])).contiguous(), tol=gtol, maxiter=maxiter or 60, status=sub,
-                                 copy=not consume)
-            # (a residual below the tolerance, or cycles that stopped at the rounding floor of the working precision
-            # well below the right-hand side: the iterate is finite)
-            if sub.get("converged") or (sub.get("stagnated") and sub.get("residual", 0.0) <= 1e-3 * (
-                    sub["bnorm"] if "bnorm" in sub else float(_dot(rhs, rhs)) ** 0.5)):
-                sub["method"] = "gmg-vcycle (variable coefficients, {} levels{})".format(
-                    solver.nlvl, "; float32 cycles, float64 residual" if mixed else "")
-                status.update(sub)
-                return x.reshape(-1)
-            from .util import printlog
-
-            printlog("odil_amd: variable-coefficient multigrid did not converge (relative residual {:.1e} after {} cycles); "
-                     "using the normal-equation routes".format(sub.get("residual", float("nan")), sub.get("niter", 0)))
-            del solver, coeffs, x
-    # float32 problems: the EXACT routes below work on a float64 copy of the operator -- the normal matrix squares the
-    # condition number, which at 1e3 - 1e4 for M already exceeds what float32 resolves (heat with the network, 64 x 64:
-    # loss 45 -> 8e3 in one float32 step, 45 -> 0.5 with the copy; the reference's float32 SuperLU solve sits in between).
-    # The iterate is rounded back to the problem's precision; the matrix-free routes (multigrid above, CG below) stay
-    # in float32.
-    if matr.dtype == torch.float32 and linsolver in ("direct", "directsq", "multigrid"):
-        wide = matr.promoted()
-        x = _exact_routes(wide, rhs.double(), damp, dampdiag, maxiter, status, linsolver)
-        if x is not None:
-            return x.to(torch.float32)
-    else:
-        x = _exact_routes(matr, rhs, damp, dampdiag, maxiter, status, linsolver)
-        if x is not None:
-            return x
-    if linsolver in ("direct", "directsq"):
-        if matr.ncols > DENSE_MAX_UNKNOWNS:
-            x = direct_multigrid(matr, rhs, damp, dampdiag, maxiter, status)
-            if x is not None:
-                return x
-        return cg_normal(matr, rhs, damp, dampdiag, tol=1e-14, maxiter=maxiter, status=status)
-    if linsolver == "multigrid":
-        x = normal_multigrid(matr, rhs, damp, dampdiag, tol, maxiter, status)
-        if x is not None:
-            return x
-    return cg_normal(matr, rhs, damp, dampdiag, tol=tol, maxiter=maxiter or 1000, status=status)
-
-
-def normal_multigrid(matr, rhs, damp=0.0, dampdiag=0.0, tol=1e-10, maxiter=None, status=None):
-    """`multigrid` for systems of grid fields that no earlier route takes (several fields, mixed locations, non-square or
-    damped M): CG on the damped normal equations preconditioned by V-cycles (gmg.NormalGMG), as the reference's AMG + CG
-    (linsolver.py:61-72).  Stops at a relative residual of the normal equations of `tol` or after `maxiter` iterations.
-    float32 problems are assembled and iterated in float64, the result rounded back.  None when the operator does not
-    qualify (an unknown that is not a `Field`, dense blocks, more than gmg.MAX_FIELDS fields, extents that do not
-    coarsen)."""
-    from . import gmg
-
-    if status is None:
-        status = dict()
-    if any(kind == "dense" for _, _, kind, _, _ in matr.blocks) or not matr.blocks:
-        return None
-    wide = matr.promoted() if matr.dtype == torch.float32 else matr
-    solver = gmg.NormalGMG.create(wide, damp, dampdiag)
-    if solver is None:
-        return None
-    rhs = rhs.to(wide.dtype)
-    b = wide.rmatvec(rhs)
-    x = cg_normal(wide, rhs, damp, dampdiag, tol=tol, maxiter=maxiter or 1000, status=status, b=b,
-                  check_every=NORMAL_GMG_CHECK_EVERY, precond=solver.precondition)
-    bnorm = float(_dot(b, b)) ** 0.5
-    status["method"] = solver.method
-    status["converged"] = bool(status["residual"] <= tol * max(bnorm, 1e-300))
-    return x.to(matr.dtype)
-
-
+# ======================================================================================================================
+# Routing: which solver takes the Newton system.  `solve` builds ONE request `req` (types.SimpleNamespace: op, rhs,
+# linsolver, damp, dampdiag, tol, maxiter, consume, status) and walks ROUTES (below the route functions; that table IS the
+# order).  A route is a function route(req) -> x or None.  None: it does not apply, or it tried and refused its own
+# result -- nothing was written to req.status and the next route is tried.  Otherwise req.status describes the solve.
+# ======================================================================================================================
+LINSOLVERS = ("direct", "directsq", "cg", "bicgstab", "multigrid", "lsqr")
+_EXACT = ("direct", "directsq")  # the solver choices that ask for the solution of the normal equations to round-off
+SCHUR_MIN_UNKNOWNS = 16384  # systems with dense columns: Schur complement above this size, dense Cholesky below
+DENSE_MAX_UNKNOWNS = 49152  # `direct` factorises the dense normal matrix up to here, memory permitting
 NORMAL_GMG_CHECK_EVERY = 2  # V-cycle-preconditioned CG: the residual norm is read back every second iteration
-DIRECT_GMG_TOL = 1e-12  # `direct` by multigrid: relative residual of the normal equations (as PoissonGMG / StencilGMG)
-DIRECT_GMG_FLOOR = 1e-3  # ... or stagnation at the rounding floor below this fraction of |M^T r|
+DIRECT_GMG_TOL = 1e-12  # `direct` by multigrid (cycles on M, or CG on the normal equations): relative residual
+DIRECT_GMG_FLOOR = 1e-3  # ... or stagnation at the rounding floor below this fraction of the right-hand side
 DIRECT_GMG_STALL = 10  # read-backs (NORMAL_GMG_CHECK_EVERY iterations each) without a new smallest residual: stagnation
 
 
-def direct_multigrid(matr, rhs, damp=0.0, dampdiag=0.0, maxiter=None, status=None):
-    """`direct` beyond the dense factorisation for the systems no exact route takes (several fields, mixed locations,
-    non-square or damped M): CG on the damped normal equations preconditioned by V-cycles whose coarsest level is
-    factorised on the device (gmg.NormalGMG, coarse="device"), to a relative residual of DIRECT_GMG_TOL, or stagnated
-    at the rounding floor below DIRECT_GMG_FLOOR |M^T r|.  status["residual"] is the TRUE residual |b - A x| of the
-    returned iterate.  None (after a log line saying why) when the operator does not qualify or the iteration does not
-    get there: the caller then runs the Jacobi CG."""
-    from . import gmg
-    from .util import printlog
+def cycles_apply(linsolver, n, damped):
+    """Whether V-cycles on M itself may take a system of n unknowns: M d = rhs has the solution of the normal equations
+    only without damping.  `multigrid` always, `direct` beyond the reach of the dense factorisation (below it 256^2 or
+    N = 100000 in 1-D would go to 45000 - 50000 CG iterations; the cycles are the only option that scales to 512^3)."""
+    return not damped and (linsolver == "multigrid" or (linsolver == "direct" and n > DENSE_MAX_UNKNOWNS))
 
-    if status is None:
-        status = dict()
-    why = None
-    if not matr.blocks or any(kind == "dense" for _, _, kind, _, _ in matr.blocks):
-        why = "the operator has dense (Array / NeuralNet) columns"
-    wide = matr.promoted() if matr.dtype == torch.float32 else matr
-    solver = None if why else gmg.NormalGMG.create(wide, damp, dampdiag, coarse="device")
-    if solver is None:
-        printlog("odil_amd: `direct` with {} unknowns: no multigrid on the normal equations for this operator ({}); "
-                 "using Jacobi CG on the normal equations".format(matr.ncols, why or "see above"))
+
+def cycle_budget(linsolver, tol, maxiter):
+    """(relative tolerance, most cycles) of the V-cycle solves: `direct` means to round-off, whatever --linsolver_tol."""
+    return DIRECT_GMG_TOL if linsolver == "direct" else tol, maxiter or 60
+
+
+def cycles_accepted(st, rhs=None, bnorm=None, near=0.0):
+    """Whether a multigrid solve that left the status `st` is taken as the Newton step: converged, or within `near` |b|, or
+    stopped at the rounding floor well below |b| (nothing that works in this precision gets further; the iterate is
+    finite).  |b|: `bnorm`, else st["bnorm"] where the solver left it, else the norm of `rhs`, reduced only if needed.
+    (st holds `converged` and `residual`: gmg's solve / solve_mixed and the slab cycle always write both.)"""
+    if st.get("converged"):
+        return True
+    if bnorm is None:
+        bnorm = st["bnorm"] if "bnorm" in st else float(_dot(rhs, rhs)) ** 0.5
+    return st["residual"] <= near * bnorm or bool(st.get("stagnated") and st["residual"] <= DIRECT_GMG_FLOOR * bnorm)
+
+
+def gmg_mode():
+    # auto (default) | poisson | stencil: `stencil` sends even the constant-coefficient Laplacian through the
+    # variable-coefficient cycle (measurement, tests), `poisson` switches that cycle off
+    return os.environ.get("ODIL_GMG", "auto")
+
+
+def gmg_mixed(dtype, shape):
+    """Whether float32 V-cycles run inside a float64 residual loop (gmg.solve_mixed): opt-in, float64 problems only, and
+    every extent even (an odd finest level is solved by GCR in one precision)."""
+    return dtype == torch.float64 and bool(int(os.environ.get("ODIL_GMG_MIXED", 0))) and all(n % 2 == 0 for n in shape)
+
+
+def poisson_gmg(domain, shape, h2, dtype, device, mixed=False):
+    """The constant-coefficient solver (mixed: the pair (float64 residual operator, float32 cycles) of gmg.solve_mixed).
+    It depends on shape, spacing and dtype only: kept with the domain, so that the next Newton step -- through `solve` or
+    through the recognised-Poisson shortcut of util -- finds its level buffers and coarsest-grid inverse."""
+    cache = domain.__dict__.setdefault("_poisson_gmg", dict())
+    key = (tuple(shape), tuple(float(v) for v in h2), dtype, str(device), mixed)
+    if key not in cache:
+        cache.clear()
+        cache[key] = gmg.PoissonGMG(shape, h2, dtype, device) if not mixed else (
+            gmg.PoissonGMG(shape, h2, dtype, device, lite=True), gmg.PoissonGMG(shape, h2, torch.float32, device))
+    return cache[key]
+
+
+def _has_dense(op):
+    return any(kind == "dense" for _, _, kind, _, _ in op.blocks)
+
+
+def _dense_fits(op):
+    """M (rows x unknowns), A = M^T M and the Cholesky factor as dense float64 matrices (what the exact routes work on)
+    must fit comfortably: 16384 unknowns take 6 GB, 49152 take 58 GB of the 288 GB of an MI355X."""
+    if op.ncols > DENSE_MAX_UNKNOWNS:
+        return False
+    need = (op.nrows * op.ncols + 2 * op.ncols * op.ncols) * 8
+    free = torch.cuda.mem_get_info(op.device)[0] if op.device.type == "cuda" else 0
+    return need <= 0.5 * free
+
+
+def _widened(req):
+    """The request on a float64 copy of a float32 operator, made once: the normal matrix squares the condition number,
+    which at 1e3 - 1e4 for M already exceeds what float32 resolves (heat with the network, 64 x 64: loss 45 -> 8e3 in one
+    float32 step, 45 -> 0.5 with the copy; the reference's float32 SuperLU solve sits in between)."""
+    if req.op.dtype != torch.float32:
+        return req
+    if not hasattr(req, "wide"):
+        req.wide = types.SimpleNamespace(**dict(vars(req), op=req.op.promoted(), rhs=req.rhs.double()))
+    return req.wide
+
+
+def _finite(req, x, sub):  # a direct solver's result is accepted when it is finite
+    if x is None or not bool(torch.isfinite(x).all()):
         return None
-    rhs = rhs.to(wide.dtype)
-    b = wide.rmatvec(rhs)
+    req.status.update(sub)
+    return x
+
+
+def poisson_cycles(req):
+    """The zero-Dirichlet Laplacian of one cell-centred field: constant-coefficient V-cycles on M d = rhs.  Cells far from
+    cubes (point smoothing with full coarsening loses its rate) can leave the cycles short of the tolerance: this route
+    then ENDS the walk itself -- the iterate is the starting point of CG on the normal equations, whose result it returns."""
+    op, rhs = req.op, req.rhs
+    rec = gmg.recognise_poisson(op) if gmg_mode() != "stencil" else None
+    if rec is None:
+        return None
+    shape, h2 = rec
+    tol, maxiter = cycle_budget(req.linsolver, req.tol, req.maxiter)
+    b, sub = rhs.reshape(shape).contiguous(), dict()
+    if gmg_mixed(op.dtype, shape):
+        high, low = poisson_gmg(op.domain, shape, h2, op.dtype, op.device, mixed=True)
+        x = gmg.solve_mixed(high, low, b, tol=tol, maxiter=maxiter, status=sub)
+    else:
+        solver = poisson_gmg(op.domain, shape, h2, op.dtype, op.device)
+        x = solver.solve(b, tol=tol, maxiter=maxiter, status=sub, copy=not req.consume)
+    if cycles_accepted(sub, rhs, near=1e-6):
+        req.status.update(sub)
+        return x.reshape(-1)
+    printlog("odil_amd: Poisson multigrid stopped at relative residual {:.1e}; finishing with CG on the normal equations".format(
+        sub.get("residual", float("nan")) / max(float(_dot(rhs, rhs)) ** 0.5, 1e-300)))
+    return cg_normal(op, rhs, tol=min(tol, 1e-10), maxiter=req.maxiter, status=req.status, x0=x.reshape(-1))
+
+
+def stencil_cycles(req):
+    """Any other square (2 d + 1)-point operator on one cell-centred field (variable-coefficient diffusion, reaction,
+    convection, other wall closures): V-cycles on its own coefficient arrays.  M d = rhs is solved, which for a
+    nonsingular square M is the solution of the normal equations; cycles that do not contract are refused."""
+    op, rhs = req.op, req.rhs
+    coeffs = gmg.recognise_stencil(op) if gmg_mode() != "poisson" else None
+    if coeffs is None:
+        return None
+    shape = tuple(coeffs.shape[1:])
+    tol, maxiter = cycle_budget(req.linsolver, req.tol, req.maxiter)
+    b, sub = rhs.reshape(shape).contiguous(), dict()
+    mixed = gmg_mixed(op.dtype, shape)
+    if mixed:
+        solver = gmg.StencilGMG(coeffs, store=torch.float32)
+        x = gmg.solve_mixed(gmg.StencilGMG(coeffs, lite=True), solver, b, tol=tol, maxiter=maxiter, status=sub)
+    else:
+        solver = gmg.StencilGMG(coeffs)
+        x = solver.solve(b, tol=tol, maxiter=maxiter, status=sub, copy=not req.consume)
+    if cycles_accepted(sub, rhs):
+        sub["method"] = "gmg-vcycle (variable coefficients, {} levels{})".format(
+            solver.nlvl, "; float32 cycles, float64 residual" if mixed else "")
+        req.status.update(sub)
+        return x.reshape(-1)
+    bnorm = sub["bnorm"] if "bnorm" in sub else float(_dot(rhs, rhs)) ** 0.5
+    printlog("odil_amd: variable-coefficient multigrid did not converge (relative residual {:.1e} after {} cycles); "
+             "using the normal-equation routes".format(sub.get("residual", float("nan")) / max(bnorm, 1e-300), sub.get("niter", 0)))
+    return None
+
+
+def substitution(req):
+    """Square and triangular along one axis (time-explicit operators): M d = rhs by substitution is exact and has the
+    solution of the normal equations.  Run beyond its stability limit (wave with dt > dx) such a scheme amplifies rounding
+    by the growth factor of every level into finite garbage, and a diagonal block may be singular: what meets the
+    equations is accepted, the rest left to the normal-equation routes (which the reference takes for everything)."""
+    rec = recognise_marching(req.op)
+    if rec is None:
+        return None
     sub = dict()
-    x = cg_normal(wide, rhs, damp, dampdiag, tol=DIRECT_GMG_TOL, maxiter=maxiter or 1000, status=sub, b=b,
-                  check_every=NORMAL_GMG_CHECK_EVERY, precond=solver.precondition, stall=DIRECT_GMG_STALL)
+    x = march_solve(rec, req.rhs, sub)
+    if sub["residual"] <= 1e-6 * max(float(_dot(req.rhs, req.rhs)) ** 0.5, 1e-300):
+        return _finite(req, x, sub)
+    return None
+
+
+def block_cyclic_reduction(req):
+    sub = dict()
+    return _finite(req, blocktri_normal(req.op, req.rhs, req.damp, req.dampdiag, sub), sub)
+
+
+def schur_complement(req):
+    sub = dict()
+    try:
+        x = schur_normal(req.op, req.rhs, req.damp, req.dampdiag, maxiter=req.maxiter, status=sub)
+    except FloatingPointError:  # an inner CG solve broke down: the dense / CG routes still apply
+        return None
+    return _finite(req, x, sub)
+
+
+def dense_factorisation(req):
+    sub = dict()
+    return _finite(req, dense_normal(req.op, req.rhs, req.damp, req.dampdiag, status=sub), sub)
+
+
+def _gmg_cg(req, tol, coarse="host", stall=0, direct=False):
+    """Systems of grid fields that no earlier route takes (several fields, mixed locations, non-square or damped M): CG on
+    the damped normal equations preconditioned by V-cycles (gmg.NormalGMG), as the reference's AMG + CG
+    (linsolver.py:61-72), to a relative residual of `tol` or req.maxiter (1000) iterations.  None when the operator does
+    not qualify (an unknown that is not a `Field`, dense blocks, over gmg.MAX_FIELDS fields, extents that do not coarsen).
+    direct: the TRUE residual |b - A x| of the iterate is status["residual"] and decides (`cycles_accepted`: met `tol`, or
+    stagnated -- `stall` read-backs without progress -- at the rounding floor); a refusal leaves a log line saying why."""
+    op = req.op
+    why = "the operator has dense (Array / NeuralNet) columns" if not op.blocks or _has_dense(op) else None
+    solver = None if why else gmg.NormalGMG.create(op, req.damp, req.dampdiag, coarse=coarse)
+    if solver is None:
+        if direct:
+            printlog("odil_amd: `direct` with {} unknowns: no multigrid on the normal equations for this operator ({}); "
+                     "using Jacobi CG on the normal equations".format(op.ncols, why or "see above"))
+        return None
+    b = op.rmatvec(req.rhs)
+    sub = dict()
+    x = cg_normal(op, req.rhs, req.damp, req.dampdiag, tol=tol, maxiter=req.maxiter or 1000, status=sub, b=b,
+                  check_every=NORMAL_GMG_CHECK_EVERY, precond=solver.precondition, stall=stall)
+    bnorm = float(_dot(b, b)) ** 0.5
+    if not direct:
+        sub.update(method=solver.method, converged=bool(sub["residual"] <= tol * max(bnorm, 1e-300)))
+        req.status.update(sub)
+        return x
     # the true residual of the iterate (CG's own residual is a recurrence and runs on below the rounding floor)
-    ax = wide.rmatvec(wide.matvec(x))
-    if damp or dampdiag:
-        shift = torch.full_like(x, float(damp) ** 2 * (1.0 + float(dampdiag) ** 2))
-        if dampdiag:
-            ops.axpy(shift, wide.normal_diagonal(), float(dampdiag) ** 2)
+    ax = op.rmatvec(op.matvec(x))
+    if req.damp or req.dampdiag:
+        shift = torch.full_like(x, float(req.damp) ** 2 * (1.0 + float(req.dampdiag) ** 2))
+        if req.dampdiag:
+            ops.axpy(shift, op.normal_diagonal(), float(req.dampdiag) ** 2)
         ops.addcmul(ax, shift, x)
     r = b.clone()
     ops.axpy(r, ax, -1.0)
     res = float(_dot(r, r)) ** 0.5
-    bnorm = float(_dot(b, b)) ** 0.5
-    converged = res <= DIRECT_GMG_TOL * max(bnorm, 1e-300)
+    converged = res <= tol * max(bnorm, 1e-300)
     # (the recurrence met the tolerance, or stopped improving, with the true residual above it: the rounding floor)
-    stagnated = not converged and (sub.get("stagnated", False) or sub["residual"] <= DIRECT_GMG_TOL * max(bnorm, 1e-300))
-    if not (converged or (stagnated and res <= DIRECT_GMG_FLOOR * bnorm)):
+    stagnated = not converged and (sub.get("stagnated", False) or sub["residual"] <= tol * max(bnorm, 1e-300))
+    sub.update(residual=res, bnorm=bnorm, converged=converged, stagnated=stagnated)
+    if not cycles_accepted(sub):
         printlog("odil_amd: `direct` by multigrid on the normal equations stopped at relative residual {:.1e} after {} "
                  "iterations; using Jacobi CG on the normal equations".format(res / max(bnorm, 1e-300), sub["niter"]))
         return None
-    status.update(sub)
-    status["residual"] = res
-    status["bnorm"] = bnorm
-    status["converged"] = converged
-    status["stagnated"] = stagnated
-    status["coarse_dropped"] = solver.dropped_pivots()
-    status["method"] = solver.method[:-1] + "; direct, device coarse)"
-    return x.to(matr.dtype)
+    sub.update(coarse_dropped=solver.dropped_pivots(), method=solver.method[:-1] + "; direct, device coarse)")
+    req.status.update(sub)
+    return x
 
 
+def direct_multigrid(req):
+    """`direct` beyond the dense factorisation: the coarsest level factorised on the device, to round-off."""
+    return _gmg_cg(req, DIRECT_GMG_TOL, coarse="device", stall=DIRECT_GMG_STALL, direct=True)
 
-def _exact_routes(matr, rhs, damp, dampdiag, maxiter, status, linsolver):
-    """Substitution, block cyclic reduction, Schur complement, dense factorisation -- in this order, whichever applies;
-    None when none does (the caller iterates on the normal equations)."""
-    # Square and triangular along one axis (time-explicit operators): M d = rhs by substitution is exact and has the
-    # solution of the normal equations
-    if not damp and not dampdiag and linsolver in ("direct", "directsq", "multigrid"):
-        rec = recognise_marching(matr)
-        if rec is not None:
-            sub = dict()
-            x = march_solve(rec, rhs, sub)
-            # exact in exact arithmetic; a time-explicit scheme run beyond its stability limit (wave with dt > dx) amplifies
-            # rounding by the growth factor of every level: the iterate is then finite garbage.  Accept what meets the
-            # equations, leave the rest to the normal-equation routes (which the reference takes for everything)
-            if bool(torch.isfinite(x).all()) and sub["residual"] <= 1e-6 * max(float(_dot(rhs, rhs)) ** 0.5, 1e-300):
-                status.update(sub)
-                return x
-            # (or a singular diagonal block met on the way: the general solvers below regularise or report it)
-    if linsolver in ("direct", "directsq"):
-        x = blocktri_normal(matr, rhs, damp, dampdiag, status)
-        if x is not None and bool(torch.isfinite(x).all()):
-            return x
-        has_dense = any(kind == "dense" for _, _, kind, _, _ in matr.blocks)
-        # small systems: ONE dense Cholesky of the normal matrix beats the p + 1 inner CG solves of the Schur route
-        small = _dense_fits(matr) and matr.ncols <= SCHUR_MIN_UNKNOWNS
-        if has_dense and not small:
-            try:
-                x = schur_normal(matr, rhs, damp, dampdiag, maxiter=maxiter, status=status)
-            except FloatingPointError:  # an inner CG solve broke down: the dense / CG routes below still apply
-                x = None
-            if x is not None and bool(torch.isfinite(x).all()):
-                return x
-        if _dense_fits(matr):
-            x = dense_normal(matr, rhs, damp, dampdiag, status=status)
-            if x is not None and bool(torch.isfinite(x).all()):
-                return x
+
+def normal_multigrid(req):
+    """`multigrid`: the coarsest level inverted on the host, to --linsolver_tol; accepted whenever the operator qualifies."""
+    return _gmg_cg(req, req.tol)
+
+
+def jacobi_cg(req):
+    # `direct`: "CG to round-off" (1e-14 relative, bounded by --linsolver_maxiter if given, else by cg_normal's own cap),
+    # which reproduces the reference's Newton iterate to solver tolerance
+    exact = req.linsolver in _EXACT
+    return cg_normal(req.op, req.rhs, req.damp, req.dampdiag, tol=1e-14 if exact else req.tol,
+                     maxiter=req.maxiter if exact else req.maxiter or 1000, status=req.status)
+
+
+def _cycles(q):
+    return cycles_apply(q.linsolver, q.op.ncols, q.damp or q.dampdiag)
+
+
+# The order in which `solve` tries the routes; the first that returns a solution ends the walk.  "tried when": a cheap
+# test on the request -- the route may still find that the operator has not the structure it needs.  "float64": the route
+# sees a float64 copy of a float32 problem (`_widened`), its result is rounded back; the others work in the problem's precision.
+ROUTES = (
+    # route                   tried when                                                                       float64
+    (poisson_cycles,          _cycles,                                                                         False),
+    (stencil_cycles,          _cycles,                                                                         False),
+    (substitution,            lambda q: not (q.damp or q.dampdiag) and q.linsolver in _EXACT + ("multigrid",), True),
+    (block_cyclic_reduction,  lambda q: q.linsolver in _EXACT,                                                 True),
+    # (small systems: ONE dense Cholesky of the normal matrix beats the p + 1 inner CG solves of the Schur route)
+    (schur_complement,        lambda q: q.linsolver in _EXACT and _has_dense(q.op)
+                                        and not (_dense_fits(q.op) and q.op.ncols <= SCHUR_MIN_UNKNOWNS),      True),
+    (dense_factorisation,     lambda q: q.linsolver in _EXACT and _dense_fits(q.op),                           True),
+    (direct_multigrid,        lambda q: q.linsolver in _EXACT and q.op.ncols > DENSE_MAX_UNKNOWNS,             True),
+    (normal_multigrid,        lambda q: q.linsolver == "multigrid",                                            True),
+    (jacobi_cg,               lambda q: True,                                                                  False),
+)
+
+
+def solve(matr, rhs, args, status=None, linsolver="direct", consume=False):
+    """Reference signature (linsolver.py:4).  `matr` is a `core.LinearizedOperator`; returns the
+    solution as a device vector.  consume=True (the Newton driver): the result may be a work buffer of the solver, valid
+    until the next solve -- no copy of it is made."""
+    if not isinstance(matr, LinearizedOperator):
+        raise TypeError(
+            "odil_amd.linsolver.solve expects the device operator returned by Problem.linearize_device(); "
+            "got {} (host sparse matrices are not solved here: there is no CPU path)".format(type(matr).__name__))
+    if not torch.is_tensor(rhs):
+        rhs = torch.as_tensor(np.asarray(rhs), dtype=matr.dtype, device=matr.device)
+    if linsolver not in LINSOLVERS:
+        raise ValueError("Unknown linsolver=" + linsolver)
+    req = types.SimpleNamespace(
+        op=matr, rhs=rhs, linsolver=linsolver, consume=consume, status=dict() if status is None else status,
+        damp=getattr(args, "linsolver_damp", 0) or 0, dampdiag=getattr(args, "linsolver_dampdiag", 0) or 0,
+        tol=getattr(args, "linsolver_tol", 1e-10), maxiter=getattr(args, "linsolver_maxiter", None))
+    for route, applies, wide in ROUTES:
+        if applies(req):
+            x = route(_widened(req) if wide else req)
+            if x is not None:
+                return x.to(matr.dtype)  # (a float64 copy's iterate: rounded back to the problem's precision)
     return None
 
 
 def add_arguments(parser):
     """Same flag names as the reference (linsolver.py:90-131)."""
-    parser.add_argument("--linsolver", type=str, default="direct",
-                        choices=("direct", "directsq", "cg", "bicgstab", "multigrid", "lsqr"), help="Linear solver")
+    parser.add_argument("--linsolver", type=str, default="direct", choices=LINSOLVERS, help="Linear solver")
     parser.add_argument("--linsolver_tol", type=float, default=1e-10, help="Convergence tolerance of iterative solvers")
     parser.add_argument("--linsolver_maxiter", type=int, default=None, help="Maximum number of iterations")
     parser.add_argument("--linsolver_damp", type=float, default=0, help="Damping: adds damp^2 * I to the normal matrix")

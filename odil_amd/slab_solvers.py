@@ -24,6 +24,7 @@ import torch
 from . import gmg
 from . import ops as hip_ops
 from . import slab
+from .linsolver import cycle_budget, cycles_accepted
 from .optimizer import LbfgsVectors, lbfgsb_minimize
 
 
@@ -850,10 +851,8 @@ class SlabTracedNewton:
             raise NotImplementedError("Newton on the slab decomposition: one Field cut along axis 0")
         if not getattr(run.kern, "jac_items", None):
             raise RuntimeError("SlabTracedNewton needs slab kernels generated with their Jacobian kernel (jac=True)")
-        # the tolerance rule of linsolver.solve (`direct`: to 1e-12) and the floor of gmg.StencilGMG.solve
-        tol = 1e-12 if linsolver == "direct" else tol
-        self.tol = max(tol, 50 * float(torch.finfo(run.dtype).eps))
-        self.maxiter = maxiter or 60
+        tol, self.maxiter = cycle_budget(linsolver, tol, maxiter)
+        self.tol = max(tol, 50 * float(torch.finfo(run.dtype).eps))  # (the floor of gmg.StencilGMG.solve)
         self.status = dict()
         self._evaluated = False
 
@@ -864,11 +863,9 @@ class SlabTracedNewton:
         if not self._evaluated:  # (else the evaluation that ended the last step left u and the wrap planes of this state)
             drive(run.evaluate_gen(), comm)
         buf = run.kern.jacobian(run.u, *run.wrap_planes())
-        from .gmg import stencil_coefficients
-
         items = [(attr[1], buf[j]) for j, (_, attr) in enumerate(run.kern.jac_items) if attr is not None]
         r = buf[next(j for j, (_, attr) in enumerate(run.kern.jac_items) if attr is None)]
-        coeffs = stencil_coefficients(items, tuple(buf.shape[1:]), period=run.domain.cshape)
+        coeffs = gmg.stencil_coefficients(items, tuple(buf.shape[1:]), period=run.domain.cshape)
         if coeffs is None:
             raise NotImplementedError("Newton on the slab decomposition: the Jacobian is not a (2 d + 1)-point stencil")
         # walls across the cut ends: nothing below the first plane of rank 0 and nothing above the last plane of the last
@@ -887,8 +884,7 @@ class SlabTracedNewton:
         st = solver.status
         self.status = dict(niter=st["niter"], residual=st["residual"], converged=st["converged"], stagnated=st["stagnated"],
                            method=st["method"])
-        # the single-GPU rule (linsolver.solve): converged, or stopped at the rounding floor well below |r|
-        if not (st["converged"] or (st["stagnated"] and st["residual"] <= 1e-3)):
+        if not cycles_accepted(st, bnorm=1.0):  # (the single-GPU rule; this status carries the RELATIVE residual)
             raise RuntimeError("Newton on the slab decomposition: multigrid stopped at relative residual {:.3e} after {} "
                                "cycles (tolerance {:.1e}); the step is not applied".format(st["residual"], st["niter"], self.tol))
         hip_ops.axpy(lv.owned(e["x"][0]), d, -1.0)

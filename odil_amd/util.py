@@ -19,6 +19,8 @@ import time
 import numpy as np
 import torch
 
+from . import gmg, ops
+from .core import Field
 from .history import History
 from .optimizer import EarlyStopError, Optimizer, make_optimizer  # noqa: F401
 
@@ -289,49 +291,31 @@ def _pinfo(loss, terms, names, norms):
 
 def _poisson_newton_step(problem, state, args, status):
     """Newton step of a problem already recognised as the Poisson stencil (fused.detect: f(u) = A u -
-    rhs with the zero-Dirichlet Laplacian A): A delta = -f(u) straight from the fused residual and the
+    rhs with the zero-Dirichlet Laplacian A): d with A d = f(u) straight from the fused residual and the
     geometric multigrid, without forming the seven coefficient arrays of the Jacobian and without
     re-recognising them (512^3: 75 ms of a 215 ms step).  None when the general route must be taken:
-    other operators, multigrid-decomposed unknowns, damping, or a solver choice that is not multigrid
-    (`direct` switches to multigrid beyond the dense factorisation's reach exactly as linsolver.solve does)."""
-    from . import gmg, ops
-    from .core import Field
-    from .linsolver import DENSE_MAX_UNKNOWNS
+    other operators, multigrid-decomposed unknowns, or a request the constant-coefficient cycles of linsolver.ROUTES
+    do not take (the same helpers decide here and there).  d may be a work buffer of the solver."""
+    from . import linsolver as ls
 
     if state.initialized:
         problem.recognise(state)  # (without a callback no evaluation precedes the first step)
     ev = getattr(problem, "_fused", None)
-    linsolver = getattr(args, "linsolver", "direct")
     if ev is None or ev.nlvl != 1 or len(state.fields) != 1 or not int(os.environ.get("ODIL_NEWTON_SHORTCUT", 1)):
         return None  # (ODIL_NEWTON_SHORTCUT=0: the general route eval_operator_grad -> linearize -> linsolver.solve)
     (field,) = state.fields.values()
-    if not isinstance(field, Field) or getattr(args, "linsolver_damp", 0) or getattr(args, "linsolver_dampdiag", 0):
+    damped = getattr(args, "linsolver_damp", 0) or getattr(args, "linsolver_dampdiag", 0)
+    linsolver = getattr(args, "linsolver", "direct")
+    if not isinstance(field, Field) or not ls.cycles_apply(linsolver, field.array.numel(), damped):
         return None
-    n = field.array.numel()
-    if not (linsolver == "multigrid" or (linsolver == "direct" and n > DENSE_MAX_UNKNOWNS)):
-        return None
-    u = field.array.contiguous()
-    r, _ = ops.poisson_residual(u, ev.rhs, ev.h2, fu=ev.fu, loss=ev.loss)
-    mixed = ev.dtype == torch.float64 and bool(int(os.environ.get("ODIL_GMG_MIXED", 0))) and all(n % 2 == 0 for n in ev.cshape)
-    solver = ev.__dict__.get("_gmg_mixed" if mixed else "_gmg")
-    if solver is None and mixed:  # (float64 residual operator, float32 cycles: gmg.solve_mixed)
-        solver = ev.__dict__["_gmg_mixed"] = (gmg.PoissonGMG(ev.cshape, ev.h2, ev.dtype, ev.device, lite=True),
-                                              gmg.PoissonGMG(ev.cshape, ev.h2, torch.float32, ev.device))
-    elif solver is None:
-        solver = ev.__dict__["_gmg"] = gmg.PoissonGMG(ev.cshape, ev.h2, ev.dtype, ev.device)
-    tol = 1e-12 if linsolver == "direct" else getattr(args, "linsolver_tol", 1e-10)
+    r, _ = ops.poisson_residual(field.array.contiguous(), ev.rhs, ev.h2, fu=ev.fu, loss=ev.loss)
+    tol, maxiter = ls.cycle_budget(linsolver, getattr(args, "linsolver_tol", 1e-10), getattr(args, "linsolver_maxiter", None))
+    mixed = ls.gmg_mixed(ev.dtype, ev.cshape)
+    solver = ls.poisson_gmg(problem.domain, ev.cshape, ev.h2, ev.dtype, ev.device, mixed=mixed)
     if mixed:
-        b = ops.scale(r, -1.0, out=r)  # the evaluator's residual buffer is scratch: negate it in place
-        delta = gmg.solve_mixed(solver[0], solver[1], b, tol=tol, maxiter=getattr(args, "linsolver_maxiter", None) or 60, status=status)
-        return delta.reshape(-1)
-    # A d = r is solved and u - d formed (the solver is linear: d = -delta) -- the residual need not be negated first
+        return gmg.solve_mixed(solver[0], solver[1], r, tol=tol, maxiter=maxiter, status=status).reshape(-1)
     # (||r||: the evaluation above reduced mean(r^2) into ev.loss already)
-    d = solver.solve(r, tol=tol, maxiter=getattr(args, "linsolver_maxiter", None) or 60, status=status, copy=False,
-                     b_meansq=ev.loss)
-    ops.axpy(u, d, -1.0)  # (d: a work buffer of the solver, consumed here)
-    if u.data_ptr() != field.array.data_ptr():
-        field.array.copy_(u)
-    return True
+    return solver.solve(r, tol=tol, maxiter=maxiter, status=status, copy=False, b_meansq=ev.loss).reshape(-1)
 
 
 def optimize_newton(args, problem, state, callback=None, **kwargs):
@@ -351,31 +335,21 @@ def optimize_newton(args, problem, state, callback=None, **kwargs):
     for epoch in range(args.epoch_start, args.epochs):
         opt.evals += 1
         linstatus = dict()
-        delta = _poisson_newton_step(problem, state, args, linstatus)
-        applied = delta is True  # (the recognised-Poisson step updates the state itself)
-        negative = False  # (True: `delta` is d of M d = r and the update is x - d)
-        if delta is None:
+        # Every route returns d with M d = r, and x - d is formed here: each is a linear solve, whose result for -r is
+        # exactly -d (IEEE arithmetic is symmetric in sign) -- no pass that negates r first; d is consumed before the next
+        # solve (no copy out of the solver's work buffers)
+        d = _poisson_newton_step(problem, state, args, linstatus)
+        if d is None:
             vector, matrix = problem.linearize_device(state)
-            # M d = r is solved and x - d formed: every route is a linear solve, whose result for -r is exactly -d (IEEE
-            # arithmetic is symmetric in sign) -- the pass that negated r first is not needed; the result is consumed
-            # before the next solve (no copy out of the solver's work buffers)
-            delta = solve(matrix, vector.contiguous(), args, linstatus, getattr(args, "linsolver", "direct"), consume=True)
-            negative = True
+            d = solve(matrix, vector.contiguous(), args, linstatus, getattr(args, "linsolver", "direct"), consume=True)
         if getattr(args, "linsolver_verbose", 0):
             printlog(linstatus)
-        from . import ops
-        from .core import Field
-
         fields = list(state.fields.values())
-        if applied:
-            pass
-        elif len(fields) == 1 and type(fields[0]) is Field and torch.is_tensor(fields[0].array) \
-                and fields[0].array.is_contiguous() and fields[0].array.numel() == delta.numel():
-
-            ops.axpy(fields[0].array, delta.to(fields[0].array.dtype), -1.0 if negative else 1.0)  # x += delta in place (util.py:176-178)
+        if len(fields) == 1 and type(fields[0]) is Field and torch.is_tensor(fields[0].array) \
+                and fields[0].array.is_contiguous() and fields[0].array.numel() == d.numel():
+            ops.axpy(fields[0].array, d.to(fields[0].array.dtype), -1.0)  # x -= d in place (util.py:176-178)
         else:
-            packed = domain.pack_state(state)
-            domain.unpack_state(packed - delta if negative else packed + delta, state)
+            domain.unpack_state(domain.pack_state(state) - d, state)
         if callback:  # one extra evaluation per step, for the report only (reference util.py:180)
             report = eval_pinfo(state)
             report["linsolver"] = linstatus

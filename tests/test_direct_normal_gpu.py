@@ -106,7 +106,7 @@ def test_darcy_3d_direct_step_is_no_worse_than_multigrid():
     assert loss_d <= loss_m * (1 + 1e-6), (loss_d, loss_m, sd, sm)
 
 
-def test_damped_single_field_matches_a_sparse_solve():
+def test_damped_single_field_matches_a_sparse_solve(monkeypatch):
     import scipy.sparse as sp
     import scipy.sparse.linalg as spla
 
@@ -117,7 +117,11 @@ def test_damped_single_field_matches_a_sparse_solve():
     assert op.ncols > odil.linsolver.DENSE_MAX_UNKNOWNS and len(op.key_to_field) == 1
     # the exact routes decline it (and the stencil cycles do not take damped operators): before this route, `direct`
     # ended in Jacobi CG
-    assert odil.linsolver._exact_routes(op, -vector, damp, 0.0, None, dict(), "direct") is None
+    ls = odil.linsolver
+    exact = (ls.substitution, ls.block_cyclic_reduction, ls.schur_complement, ls.dense_factorisation)
+    with monkeypatch.context() as only_exact:
+        only_exact.setattr(ls, "ROUTES", tuple(entry for entry in ls.ROUTES if entry[0] in exact))
+        assert solve(op, vector, "direct", damp=damp)[0] is None
     x, st = solve(op, vector, "direct", damp=damp)
     assert st["method"].startswith("gmg-normal (1 field") and "direct, device coarse" in st["method"], st
     m = op.to_scipy().tocsr().astype(np.float64)

@@ -61,7 +61,6 @@ for rnd in range(4):
         for k, v in attrs.items():
             setattr(gmg.PoissonGMG, k, v)
         problem.domain.__dict__.pop("_poisson_gmg", None)  # (solvers are kept with the domain: rebuild under the new switches)
-        getattr(problem, "_fused", None) is not None and problem._fused.__dict__.pop("_gmg", None)
         step()
         dt, it = min(step() for _ in range(2))
         if dt < best[name][0]:
