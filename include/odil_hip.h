@@ -517,6 +517,16 @@ int odil_dense_block_xty_f64(const double* x, const double* y, int64_t n, int px
                              double* out, double* workspace, void* stream);
 int odil_dense_block_xty_f32(const float* x, const float* y, int64_t n, int px, int py, int64_t ldx, int64_t ldy,
                              float* out, float* workspace, void* stream);
+/* The same product for 1 <= px, py <= 1024 columns: 64-column panels of X and Y, one pair of panels and one row range
+ * per workgroup, row ranges summed in index order in double (bit-reproducible).  X == Y with the same row stride and
+ * px <= py (D^T D, D^T [D | r]): only pairs on or above the diagonal are computed and the rest mirrored, so that the
+ * p x p block is exactly symmetric.  `workspace`: `workspace_bytes` >= odil_dense_block_wide_workspace_bytes(px, py),
+ * which never exceeds 64 MiB (0 for column counts outside the range). */
+size_t odil_dense_block_wide_workspace_bytes(int px, int py);
+int odil_dense_block_xty_wide_f64(const double* x, const double* y, int64_t n, int px, int py, int64_t ldx,
+                                  int64_t ldy, double* out, double* workspace, size_t workspace_bytes, void* stream);
+int odil_dense_block_xty_wide_f32(const float* x, const float* y, int64_t n, int px, int py, int64_t ldx, int64_t ldy,
+                                  float* out, float* workspace, size_t workspace_bytes, void* stream);
 /* The Gram matrix D^T D (p x p) of one block: odil_dense_block_xty with X = Y = D. */
 int odil_dense_block_gram_f64(const double* d, int64_t n, int p, int64_t ld, double* out, double* workspace,
                               void* stream);

@@ -75,6 +75,7 @@ _SIGNATURES = {
     "max_abs_rows": [_P, c_int, c_int64, _P, _P, _P],
     "csr_assemble": [_P, _I64P, c_int, _I64P, c_int, c_int64, _P, _P, _P, _P],
     "dense_block_xty": [_P, _P, c_int64, c_int, c_int, c_int64, c_int64, _P, _P, _P],
+    "dense_block_xty_wide": [_P, _P, c_int64, c_int, c_int, c_int64, c_int64, _P, _P, c_size_t, _P],
     "dense_block_gram": [_P, c_int64, c_int, c_int64, _P, _P, _P],
     "bmg_apply": [_P, _P, _I64P, _P, _P, _P, _P, c_int, _R, _P],
     "bmg_assemble": [_P, _P, _P, _I64P, _I64P, _P, _P],
@@ -90,7 +91,8 @@ _SIGNATURES_F64 = {
 
 EXPORTED = [
     "odil_last_error", "odil_version", "odil_device_count", "odil_reduce_workspace_bytes", "odil_dots_workspace_bytes",
-    "odil_dense_block_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy", "odil_poisson_small_epochs_resident",
+    "odil_dense_block_workspace_bytes", "odil_dense_block_wide_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy",
+    "odil_poisson_small_epochs_resident",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
 ] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
@@ -121,6 +123,8 @@ def load():
     lib.odil_dots_workspace_bytes.restype = c_size_t
     lib.odil_dots_workspace_bytes.argtypes = [c_int]
     lib.odil_dense_block_workspace_bytes.restype = c_size_t
+    lib.odil_dense_block_wide_workspace_bytes.restype = c_size_t
+    lib.odil_dense_block_wide_workspace_bytes.argtypes = [c_int, c_int]
     lib.odil_poisson_small_epochs_resident.restype = c_int
     lib.odil_poisson_small_epochs_resident.argtypes = [_I64P, c_int, c_int, c_int]
     for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)

@@ -8,8 +8,9 @@ arrays + dense blocks), A is applied as M^T (M x) with the HIP stencil kernels, 
 this module in the order of the table ROUTES: geometric multigrid on M itself (gmg.py), the exact solvers of
 `direct` (substitution, block cyclic reduction, Schur complement, dense Cholesky), CG preconditioned by V-cycles on the
 normal equations (gmg.NormalGMG), and last Jacobi-preconditioned conjugate gradients with deterministic dot products
-(odil_dots) and no host synchronisation inside the iteration.  cupy / sparseqr / pyamg variants of the reference are
-optional third-party paths and are not provided.
+(odil_dots) and no host synchronisation inside the iteration.  The Schur route carries up to DENSE_COLUMNS_MAX = 1023
+`Array` / `NeuralNet` parameters (the MFMA kernel of ops.dense_xty takes [D | r] with at most 1024 columns), memory
+permitting.  cupy / sparseqr / pyamg variants of the reference are optional third-party paths and are not provided.
 """
 
 import copy
@@ -123,9 +124,10 @@ def cg_normal(op, rhs, damp=0.0, dampdiag=0.0, tol=1e-14, maxiter=None, status=N
 
 
 def _solve_small_spd(a, b, info=None, rcond=None, floor=0.0):
-    """x with a x = b for the p x p (p <= 63) Schur complement of the dense columns.  Network weights often leave it
-    SINGULAR (redundant directions: the reference's SuperLU then returns some member of the solution set): when the
-    plain solve is not finite or misses the equations, the minimum-norm solution through the eigen-decomposition."""
+    """x with a x = b for the p x p (p <= DENSE_COLUMNS_MAX) Schur complement of the dense columns.  Network weights
+    often leave it SINGULAR (redundant directions: the reference's SuperLU then returns some member of the solution
+    set): when the plain solve is not finite or misses the equations, the minimum-norm solution through the
+    eigen-decomposition."""
     if not (bool(torch.isfinite(a).all()) and bool(torch.isfinite(b).all())):
         return None  # (an inner solve broke down: the caller takes another route)
     if rcond is not None:
@@ -173,28 +175,46 @@ def _solve_small_spd(a, b, info=None, rcond=None, floor=0.0):
     return x
 
 
+def _schur_fits(op, p):
+    """The Schur route holds about six arrays of rows x (p + 1) at once ([D | r] and its transpose, C, Z and their
+    transposes): they must fit in half of the free device memory (as `_dense_fits`).  Says so in one line when they do
+    not.  (Off the device there is nothing to ask: the kernels of the route refuse such tensors themselves.)"""
+    if op.device.type != "cuda":
+        return True
+    need = 6 * op.nrows * (p + 1) * torch.empty((), dtype=op.dtype).element_size()
+    free = torch.cuda.mem_get_info(op.device)[0]
+    if need <= 0.5 * free:
+        return True
+    printlog("odil_amd: Schur complement of {} dense columns wants {} bytes of device memory, {} are free; "
+             "using the other routes".format(p, need, free))
+    return False
+
+
 def schur_normal(op, rhs, damp=0.0, dampdiag=0.0, maxiter=None, status=None, inner=None):
     """`direct` for systems with DENSE columns (`Array` / `NeuralNet` unknowns, reference core.py:1189-1203).
 
-    With M = [S | D] (S: the stencil blocks, matrix-free; D: rows x p dense, p <= 63) the normal equations
-    (reference linsolver.py:17-23) are solved through the Schur complement of the stencil part:
+    With M = [S | D] (S: the stencil blocks, matrix-free; D: rows x p dense, p <= DENSE_COLUMNS_MAX) the normal
+    equations (reference linsolver.py:17-23) are solved through the Schur complement of the stencil part:
         G = D^T D,  g = D^T r                      one pass of the MFMA kernel over [D | r]  (ops.dense_xty)
         C = S^T D,  c = S^T r                      p + 1 transposed stencil applications
         (S^T S) [Z | z] = [C | c]                  p + 1 matrix-free CG solves (cg_normal on the stencil part)
         (G - C^T Z) y = g - C^T z                  C^T [Z | z] again on the matrix cores; a p x p solve
         x = z - Z y
     Neither M nor S is ever densified.  Returns the full solution vector, or None when the system has no dense
-    columns / too many of them.  inner: callable [k, n_s] -> [k, n_s] that applies (S^T S + damping)^{-1} to all
-    right-hand sides at once (the block-tridiagonal direct solver, blocktri.py) instead of the CG solves."""
+    columns / too many of them (or not the memory for them: one log line).  inner: callable [k, n_s] -> [k, n_s] that
+    applies (S^T S + damping)^{-1} to all right-hand sides at once (the block-tridiagonal direct solver, blocktri.py)
+    instead of the CG solves."""
     dense_keys = []
     for row0, nrows, kind, key, payload in op.blocks:
         if kind == "dense" and key not in dense_keys:
             dense_keys.append(key)
     dense_keys.sort(key=lambda k: op.key_to_offset[k])
     p = sum(op.key_to_size[k] for k in dense_keys)
-    if not dense_keys or p > 63:
+    if not dense_keys or p > DENSE_COLUMNS_MAX:
         return None
     dtype, device = op.dtype, op.device
+    if not _schur_fits(op, p):
+        return None
     col0, pos = dict(), 0
     for k in dense_keys:
         col0[k] = pos
@@ -296,7 +316,7 @@ def blocktri_normal(op, rhs, damp=0.0, dampdiag=0.0, status=None):
     inner.offset, inner.size = op.key_to_offset[key], op.key_to_size[key]
     try:
         if dense_keys:
-            if sum(op.key_to_size[k] for k in dense_keys) > 63:
+            if sum(op.key_to_size[k] for k in dense_keys) > DENSE_COLUMNS_MAX:
                 return None
             return schur_normal(op, rhs, damp, dampdiag, status=status, inner=inner)
         b = op.rmatvec(rhs)
@@ -407,6 +427,7 @@ def dense_normal(op, rhs, damp=0.0, dampdiag=0.0, status=None):
 LINSOLVERS = ("direct", "directsq", "cg", "bicgstab", "multigrid", "lsqr")
 _EXACT = ("direct", "directsq")  # the solver choices that ask for the solution of the normal equations to round-off
 SCHUR_MIN_UNKNOWNS = 16384  # systems with dense columns: Schur complement above this size, dense Cholesky below
+DENSE_COLUMNS_MAX = 1023  # dense columns p of the Schur route: [D | r] has p + 1 <= 1024 columns (ops.dense_xty)
 DENSE_MAX_UNKNOWNS = 49152  # `direct` factorises the dense normal matrix up to here, memory permitting
 NORMAL_GMG_CHECK_EVERY = 2  # V-cycle-preconditioned CG: the residual norm is read back every second iteration
 DIRECT_GMG_TOL = 1e-12  # `direct` by multigrid (cycles on M, or CG on the normal equations): relative residual

@@ -6,7 +6,7 @@ semantics follow the reference functions cited in include/odil_hip.h.
 """
 
 import math
-from ctypes import c_double, c_int, c_int64, c_void_p
+from ctypes import c_double, c_int, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -650,22 +650,41 @@ def poisson_jac_coeffs(shape, h2, dtype, device):
 
 
 _dense_ws = {}
+_dense_wide_ws = {}
+DENSE_NARROW_COLUMNS = 64  # per operand: odil_dense_block_xty
+DENSE_WIDE_COLUMNS = 1024  # per operand: odil_dense_block_xty_wide
 
 
 def dense_xty(x, y):
-    """X^T Y of two tall, skinny matrices (rows x <= 64 columns each, row-major, any row stride) on the matrix
+    """X^T Y of two tall, skinny matrices (rows x <= 1024 columns each, row-major, any row stride) on the matrix
     cores: v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32, deterministic two-stage reduction.  The dense block of
-    the Newton normal equations (reference core.py:1189-1203, linsolver.py:17-23)."""
+    the Newton normal equations (reference core.py:1189-1203, linsolver.py:17-23).  Up to 64 columns per operand: one
+    workgroup per row range; beyond: 64-column panels (odil_dense_block_xty_wide).  There, when x and y are views of
+    the SAME memory with the same row stride and x has no more columns than y (D^T D, D^T [D | r]), the panel pairs
+    below the diagonal are mirrored from those above it: out[:, :px] is symmetric to the bit, and differs in the last
+    bits from what a contiguous copy of x against y gives (that call computes every pair)."""
     assert x.dim() == 2 and y.dim() == 2 and x.shape[0] == y.shape[0] and x.dtype == y.dtype
     assert x.stride(1) == 1 and y.stride(1) == 1
+    px, py = x.shape[1], y.shape[1]
+    if max(px, py) > DENSE_WIDE_COLUMNS:
+        raise ValueError("dense_xty: {} x {} columns; at most {} per operand".format(px, py, DENSE_WIDE_COLUMNS))
     key = (str(x.device), x.dtype)
-    ws = _dense_ws.get(key)
-    if ws is None:
-        ws = _dense_ws[key] = torch.empty(_lib.load().odil_dense_block_workspace_bytes() // 8, dtype=torch.float64,
-                                          device=x.device).view(x.dtype)
-    out = torch.empty((x.shape[1], y.shape[1]), dtype=x.dtype, device=x.device)
-    call("dense_block_xty", x.dtype, c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_int64(x.shape[0]),
-         c_int(x.shape[1]), c_int(y.shape[1]), c_int64(x.stride(0)), c_int64(y.stride(0)), ptr(out), ptr(ws), stream_ptr())
+    out = torch.empty((px, py), dtype=x.dtype, device=x.device)
+    if max(px, py) <= DENSE_NARROW_COLUMNS:
+        ws = _dense_ws.get(key)
+        if ws is None:
+            ws = _dense_ws[key] = torch.empty(_lib.load().odil_dense_block_workspace_bytes() // 8, dtype=torch.float64,
+                                              device=x.device).view(x.dtype)
+        call("dense_block_xty", x.dtype, c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_int64(x.shape[0]),
+             c_int(px), c_int(py), c_int64(x.stride(0)), c_int64(y.stride(0)), ptr(out), ptr(ws), stream_ptr())
+        return out
+    need = _lib.load().odil_dense_block_wide_workspace_bytes(px, py)
+    ws = _dense_wide_ws.get(key)
+    if ws is None or ws.numel() * ws.element_size() < need:  # grown on demand, never beyond the kernel's 64 MiB
+        ws = _dense_wide_ws[key] = torch.empty(need // 8, dtype=torch.float64, device=x.device).view(x.dtype)
+    call("dense_block_xty_wide", x.dtype, c_void_p(x.data_ptr()), c_void_p(y.data_ptr()), c_int64(x.shape[0]),
+         c_int(px), c_int(py), c_int64(x.stride(0)), c_int64(y.stride(0)), ptr(out), ptr(ws),
+         c_size_t(ws.numel() * ws.element_size()), stream_ptr())
     return out
 
 
