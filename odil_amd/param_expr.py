@@ -269,8 +269,10 @@ def _d(expr, target, j, slot_of, cg, path=()):
 
 def emit(cg, S, outputs, fresh):
     """Appends `k_par` and its launcher to the source lines S.  outputs: [(k, segments)] of convert(); fresh: array
-    indices whose gradient slot no grid kernel writes (set instead of added to).  Returns the array indices in the order
-    of ParArgs.val / .grad."""
+    indices whose gradient slot no grid kernel writes (set instead of added to).  Leaves the array indices in the order
+    of ParArgs.val / .grad in `cg.par_index`."""
+    from .stencil_codegen import struct_text
+
     arrays = []
     for _, segs in outputs:
         for _, e in segs:
@@ -283,8 +285,8 @@ def emit(cg, S, outputs, fresh):
                 elif x[0] not in ("const", "hs"):
                     stack.extend(x[1:])
     slot_of = {index: s for s, index in enumerate(arrays)}
-    K, nq = max(1, len(arrays)), len(outputs)
-    S.append("struct ParArgs {{ const T* val[{0}]; T* grad[{0}]; T* pout; }};".format(K))
+    cg.par_index = arrays
+    S.append(struct_text("ParArgs", cg.par_args_layout()))
     S.append('extern "C" __global__ __launch_bounds__(NB) void k_par(const Args a, const ParArgs pa) {')
     S.append("  __shared__ T sm[NB / 64];")
     # ---- terms ------------------------------------------------------------------------------------------------------
@@ -324,4 +326,3 @@ def emit(cg, S, outputs, fresh):
     S.append("  hipLaunchKernelGGL(k_par, dim3(1), dim3(NB), 0, (hipStream_t)stream, *a, *pa);")
     S.append("  return (int)hipGetLastError();")
     S.append("}")
-    return arrays

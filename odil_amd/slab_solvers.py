@@ -817,8 +817,7 @@ def check_slab_newton(args, problem, state, axis=None, world=1):
         raise NotImplementedError("Newton on the slab decomposition: {} cells on axis 0 over {} ranks".format(N, world))
     try:
         tr, outs, raw, _, G = trace_outputs(problem, state)
-        cg = _Codegen(tr, outs, raw, G, state, slab=(0, N // world))
-        cg.want_jac = True
+        cg = _Codegen(tr, outs, raw, G, state, slab=(0, N // world), jac=True)
         cg.source()
     except TraceUnsupported as e:
         raise NotImplementedError("Newton on the slab decomposition: no generated Jacobian kernel ({})".format(e))

@@ -40,7 +40,6 @@ per GPU over RCCL (slab.TorchDistComm), over gloo with CPU doubles of the kernel
 and with all ranks emulated in one process on one GPU (slab.run_lockstep, tests/test_slab_gpu.py).
 """
 
-import ctypes
 import contextlib
 import math
 
@@ -48,8 +47,8 @@ import numpy as np
 import torch
 
 from . import ops as hip_ops
-from .stencil_codegen import _Codegen, _compile
-from .stencil_jit import TracedOperator, trace_outputs
+from .stencil_bind import StencilBinding, field_ranges
+from .stencil_jit import trace_outputs
 from .stencil_trace import TraceUnsupported
 
 G = 2  # ghost planes per interior interface (the generated gathers assume 2)
@@ -102,100 +101,35 @@ class _Level:
         return (start + (self.g_lo + pos) * inner, outer, self.shape[self.axis] * inner, inner)
 
 
-class HipSlabKernels:
-    """The generated kernels of one rank (stencil_codegen in slab mode) and their buffers."""
+class HipSlabKernels(StencilBinding):
+    """The generated kernels of one rank (stencil_codegen in slab mode) and their buffers: the binding of stencil_bind.py,
+    plus the geometry of the rank's slab and the wrap planes across the ends of the decomposition."""
 
     def __init__(self, problem, state, axis, n, device, jac=False):
         """jac: also generate `k_jac` (`jacobian`), in a library of its own -- the library of the gradient optimizers keeps
         its source and cache key."""
         tr, outs, raw, self.names, Gshape = trace_outputs(problem, state)
-        self.problem, self.tr, self.raw = problem, tr, raw
-        cg = _Codegen(tr, outs, raw, Gshape, state, slab=(axis, n))
-        cg.want_jac = bool(jac)
+
         # outputs in parameter space (a weight regulariser): every rank evaluates them, redundantly, with the generated
         # kernel of param_expr.py AFTER the parameter gradients were summed over the ranks
-        self.par_outputs = None
-        if tr.offgrid:
-            from . import param_expr
-            from .core import Array, NeuralNet
+        def refuse(e):
+            raise TraceUnsupported("outputs in parameter space under the slab decomposition ({})".format(e))
 
-            domain = problem.domain
-            arrays0 = domain.arrays_from_state(state)
-            offgrid = [(k, e, tr.param_tape.slice_for(e.param_ids())) for k, e in tr.offgrid]
-            try:
-                self.par_outputs = param_expr.convert(tr.param_tape, offgrid, {i: int(a.numel()) for i, a in enumerate(arrays0)})
-            except param_expr.Unsupported as e:
-                raise TraceUnsupported("outputs in parameter space under the slab decomposition ({})".format(e))
-            cg.par_outputs, cg.par_numel, cg.par_keys, pos = self.par_outputs, dict(), dict(), 0
-            self.par_where = dict()  # global array index -> (field key, position among the field's arrays)
-            for key, field in state.fields.items():
-                cnt = len(domain.arrays_from_field(field))
-                for i in range(pos, pos + cnt):
-                    cg.par_numel[i] = int(arrays0[i].numel())
-                    if isinstance(field, (NeuralNet, Array)):
-                        cg.par_keys[i] = key
-                        self.par_where[i] = (key, i - pos)
-                pos += cnt
-        self.source = cg.source()
-        self.lib, self.lib_path = _compile(self.source, cg.flags)
-        self.cg = cg
+        super().__init__(problem, state, tr, outs, raw, Gshape, (axis, n), jac, device, refuse)
+        cg = self.cg
         self.halo = cg.halo
-        dt = tr.torch_dtype
-        self.dtype = dt
-        self.total = cg.total
-        cap = cg.max_blocks or (4096 if len(cg.pg_decl) > 8 else 65536)
-        self.nblocks = min((self.total // cg.vw_fwd + 255) // 256, cap)
-        nout = len(outs)
-        self.nout = nout
-        self.cot = [torch.empty(cg.GL, dtype=dt, device=device) for _ in range(cg.ncot)]
-        self.part = torch.empty(max(1, nout * self.nblocks), dtype=dt, device=device)
-        self.ppart = torch.empty(max(1, len(cg.pg_decl) * self.nblocks), dtype=dt, device=device)
-        self.part2 = torch.zeros(16 * (nout + len(cg.pg_decl)), dtype=dt, device=device)
-        self.out = torch.zeros(1 + 2 * nout, dtype=dt, device=device)
-        self.pgrad = torch.zeros(max(1, len(cg.pg_decl)), dtype=dt, device=device)
-        nsrc = max(1, len(cg.src_keys))
-
-        class Args(ctypes.Structure):
-            _fields_ = [
-                ("src", ctypes.c_void_p * nsrc),
-                ("ten", ctypes.c_void_p * max(1, len(tr.tensors))),
-                ("cot", ctypes.c_void_p * max(1, cg.ncot)),
-                ("par", ctypes.c_void_p * max(1, cg.par_arrays)),
-                ("hs", ctypes.c_void_p), ("hsv", ctypes.c_double * max(1, len(cg.hs))),
-                ("part", ctypes.c_void_p), ("ppart", ctypes.c_void_p), ("part2", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("pgrad", ctypes.c_void_p), ("edge", ctypes.c_void_p), ("nblocks", ctypes.c_int),
-                ("off", ctypes.c_int), ("lo", ctypes.c_int), ("ea", ctypes.c_int), ("hw", ctypes.c_int),
-                ("wlo", ctypes.c_void_p * nsrc), ("whi", ctypes.c_void_p * nsrc),
-                ("gwlo", ctypes.c_void_p * nsrc), ("gwhi", ctypes.c_void_p * nsrc),
-                ("alo", ctypes.c_int), ("ahi", ctypes.c_int),
-            ]
-
-        a = self.args = Args()
-        for i, t in enumerate(tr.tensors):
-            a.ten[i] = t.data_ptr()
-        for i, t in enumerate(self.cot):
-            a.cot[i] = t.data_ptr()
-        a.part, a.ppart, a.part2 = self.part.data_ptr(), self.ppart.data_ptr(), self.part2.data_ptr()
-        a.out, a.pgrad, a.nblocks, a.hs = self.out.data_ptr(), self.pgrad.data_ptr(), self.nblocks, None
-        self.lib.jit_fwd.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        self.lib.jit_gather.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        self.lib.jit_gather_adam.argtypes = [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_double] * 4 + [
-            ctypes.c_void_p, ctypes.c_void_p]
-        a.alo = a.ahi = 0
+        # global array index -> (field key, position among the field's arrays)
+        self.par_where = {i: (key, i - pos) for key, _, pos, cnt in field_ranges(problem.domain, state)
+                          for i in range(pos, pos + cnt)}
+        self.args.alo = self.args.ahi = 0
         self.src_keys, self.gather_keys = list(cg.src_keys), list(cg.gathers)
         # fields whose own arrays the gathers read again (local derivatives re-evaluated there, stencil_grad.py)
         self.reread = {k for keys in cg.gather_reads_sources.values() for k in keys}
         self.merged = list(cg.merged)
-        if self.merged:
-            self.lib.jit_gather_all.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [
-                ctypes.c_double] * 4 + [ctypes.c_void_p, ctypes.c_void_p]
         self.param_groups = {key: (cg.pg_offset[key], [len(g) for g in groups]) for key, groups in cg.pgrads.items()}
-        self.jac_items = list(getattr(cg, "jac_items", None) or [])
+        self.jac_items = list(cg.jac_items)
         if self.jac_items:
-            self.lib.jit_jac.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
-            self.jac_buf = torch.empty((len(self.jac_items),) + tuple(cg.GL), dtype=dt, device=device)
-
-    _host_value = TracedOperator._host_value  # host scalars (functions of problem.tracers): the single-GPU evaluator
+            self.jac_buf = torch.empty((len(self.jac_items),) + tuple(cg.GL), dtype=self.dtype, device=device)
 
     def set_geometry(self, off, lo, ea):
         self.args.off, self.args.lo, self.args.ea, self.args.hw = off, lo, ea, self.halo
@@ -211,42 +145,28 @@ class HipSlabKernels:
             self.args.par[i] = state_arrays_of(key)[0].data_ptr()
             i += 1
 
-    def forward(self, srcs, wlo, whi):
-        """Forward + cotangents on the owned cells.  srcs / wlo / whi: src key -> array."""
+    def _bind(self, srcs, wlo, whi):
+        """The argument block filled for one evaluation: host scalars, sources and their wrap planes (src key -> array)."""
         from ._lib import ptr
 
         ptr(self.out)  # fails loudly on a CPU tensor: there is no CPU path
-        memo = dict()
-        for i, node in enumerate(self.cg.hs):
-            self.args.hsv[i] = float(self._host_value(node, memo))
+        self.refresh_host_scalars()
         for i, key in enumerate(self.src_keys):
             self.args.src[i] = srcs[key].data_ptr()
             self.args.wlo[i], self.args.whi[i] = wlo[key].data_ptr(), whi[key].data_ptr()
-        rc = self.lib.jit_fwd(ctypes.byref(self.args), hip_ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("traced slab kernel launch failed: hip error {}".format(rc))
+
+    def forward(self, srcs, wlo, whi):
+        """Forward + cotangents on the owned cells.  srcs / wlo / whi: src key -> array."""
+        self._bind(srcs, wlo, whi)
+        self.fwd()
 
     def jacobian(self, srcs, wlo, whi):
         """`k_jac` on the owned cells (one launch): the value of every output and d output / d read for every distinct
         read, in the order of `self.jac_items` ((output, None) for a value, (output, read attr) for a derivative), as the
         leading slices of ONE buffer of shape [len(jac_items), *owned shape] -- reused by the next call.  srcs / wlo /
         whi as in `forward`: u after the halo exchange, the wrap planes across the ends of the decomposition."""
-        from ._lib import ptr
-
-        if not self.jac_items:
-            raise RuntimeError("these slab kernels were generated without their Jacobian kernel (jac=False)")
-        ptr(self.out)  # fails loudly on a CPU tensor: there is no CPU path
-        memo = dict()
-        for i, node in enumerate(self.cg.hs):
-            self.args.hsv[i] = float(self._host_value(node, memo))
-        for i, key in enumerate(self.src_keys):
-            self.args.src[i] = srcs[key].data_ptr()
-            self.args.wlo[i], self.args.whi[i] = wlo[key].data_ptr(), whi[key].data_ptr()
-        n = len(self.jac_items)
-        ptrs = (ctypes.c_void_p * n)(*[self.jac_buf[j].data_ptr() for j in range(n)])
-        rc = self.lib.jit_jac(ctypes.byref(self.args), ptrs, hip_ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("traced slab Jacobian launch failed: hip error {}".format(rc))
+        self._bind(srcs, wlo, whi)
+        self.jac(self.jac_buf)
         return self.jac_buf
 
     fused_adam = True  # gather() can apply the optimizer's update to the planes whose gradient it completes
@@ -258,42 +178,30 @@ class HipSlabKernels:
         (x, m, v laid out as g)."""
         i = self.src_keys.index(key)
         self.args.gwlo[i], self.args.gwhi[i] = gwlo.data_ptr(), gwhi.data_ptr()
-        which = self.gather_keys.index(key)
-        if adam is None:
-            self.args.alo = self.args.ahi = 0
-            rc = self.lib.jit_gather(which, ctypes.byref(self.args), g.data_ptr(), hip_ops.stream_ptr())
-        else:
-            x, m, v, alpha, omb1, omb2, eps, lo, hi = adam
+        self.args.alo = self.args.ahi = 0
+        if adam is not None:
+            x, m, v = adam[:3]
             assert x.shape == g.shape and x.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-            self.args.alo, self.args.ahi = int(lo), int(hi)
-            rc = self.lib.jit_gather_adam(which, ctypes.byref(self.args), g.data_ptr(), x.data_ptr(), m.data_ptr(),
-                                          v.data_ptr(), float(alpha), float(omb1), float(omb2), float(eps), None,
-                                          hip_ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("traced slab gather launch failed: hip error {}".format(rc))
+            self.args.alo, self.args.ahi = int(adam[7]), int(adam[8])
+            adam = adam[:7]
+        super().gather(self.gather_keys.index(key), g, adam)
 
     def gather_all(self, items, hyper=None, planes=(0, 0)):
         """Every merged field's ghost-extended gradient in ONE launch (see `gather`): items = [(key, g, gwlo, gwhi,
         (x, m, v) or None)] for exactly the keys of `self.merged`; hyper = (alpha, one_minus_b1, one_minus_b2, eps)."""
-        nk = len(self.merged)
-        arr = lambda: (ctypes.c_void_p * nk)()
-        gp, xp, mp, vp = arr(), arr(), arr(), arr()
         by_key = {it[0]: it for it in items}
-        for k, key in enumerate(self.merged):
+        lists = [], [], [], []  # g, x, m, v in the order of self.merged
+        for key in self.merged:
             _, g, gwlo, gwhi, xmv = by_key[key]
             i = self.src_keys.index(key)
             self.args.gwlo[i], self.args.gwhi[i] = gwlo.data_ptr(), gwhi.data_ptr()
-            gp[k] = g.data_ptr()
             if xmv is not None:
                 x, m, v = xmv
                 assert x.shape == g.shape and x.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-                xp[k], mp[k], vp[k] = x.data_ptr(), m.data_ptr(), v.data_ptr()
+            for lst, t in zip(lists, (g,) + tuple(xmv or (None, None, None))):
+                lst.append(t)
         self.args.alo, self.args.ahi = int(planes[0]), int(planes[1])
-        alpha, omb1, omb2, eps = hyper if hyper is not None else (0.0, 0.0, 0.0, 0.0)
-        rc = self.lib.jit_gather_all(ctypes.byref(self.args), gp, xp, mp, vp, float(alpha), float(omb1), float(omb2),
-                                     float(eps), None, hip_ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("traced slab gather launch failed: hip error {}".format(rc))
+        super().gather_all(*lists, hyper=hyper)
 
     def partial_terms(self):
         """This rank's share of every loss term (sum over owned cells / GLOBAL count)."""
@@ -304,23 +212,8 @@ class HipSlabKernels:
         values_of / grads_of: field key -> list of this rank's (replicated) arrays."""
         if self.par_outputs is None:
             return
-        if not hasattr(self, "par_args"):
-            npar = max(1, len(self.cg.par_index))
-
-            class ParArgs(ctypes.Structure):
-                _fields_ = [("val", ctypes.c_void_p * npar), ("grad", ctypes.c_void_p * npar), ("pout", ctypes.c_void_p)]
-
-            self.par_args = ParArgs()
-            self.pout = torch.zeros(2 * len(self.par_outputs), dtype=self.dtype, device=self.out.device)
-            self.par_args.pout = self.pout.data_ptr()
-            self.lib.jit_par.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        for s_, index in enumerate(self.cg.par_index):
-            key, j = self.par_where[index]
-            self.par_args.val[s_] = values_of(key)[j].data_ptr()
-            self.par_args.grad[s_] = grads_of(key)[j].data_ptr()
-        rc = self.lib.jit_par(ctypes.byref(self.args), ctypes.byref(self.par_args), hip_ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("parameter-space kernel launch failed: hip error {}".format(rc))
+        where = [self.par_where[index] for index in self.cg.par_index]
+        self.par([values_of(key)[j] for key, j in where], [grads_of(key)[j] for key, j in where])
 
 
 class SlabTracedAdam:

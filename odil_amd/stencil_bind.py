@@ -1,0 +1,180 @@
+"""Host side of ONE generated stencil library: from a traced operator to a loaded library with its buffers, its argument
+block and its launches.  The single-GPU evaluator (stencil_jit.TracedOperator) and the kernels of one slab rank
+(slab_traced.HipSlabKernels) are this binding plus what is their own: where the sources and gradients live.
+
+The argument blocks (`struct Args`, `struct ParArgs`) are described once, by the generator (`_Codegen.args_layout`,
+`par_args_layout`): the C text of the source and the ctypes structures here are both made from those lists.
+"""
+
+import ctypes
+
+import torch
+
+from . import ops, param_expr
+from .stencil_codegen import _Codegen, _compile
+from .stencil_trace import _HOST_BINARY, _HOST_UNARY
+
+_P = ctypes.c_void_p
+_PP = ctypes.POINTER(ctypes.c_void_p)
+_ADAM = [_P] * 3 + [ctypes.c_double] * 4 + [_P]  # x, m, v, alpha, 1 - beta_1, 1 - beta_2, eps, alpha on the device
+_ARGTYPES = dict(  # (launchers of stencil_codegen._launchers; all end with the stream)
+    jit_fwd=[_P, _P], jit_gather=[ctypes.c_int, _P, _P, _P], jit_gather_adam=[ctypes.c_int, _P, _P] + _ADAM + [_P],
+    jit_gather_all=[_P] + [_PP] * 4 + _ADAM[3:] + [_P], jit_jac=[_P, _PP, _P], jit_par=[_P, _P, _P])
+
+
+def field_ranges(domain, state):
+    """(key, field, first array, number of arrays) of every field, positions in `arrays_from_state` order."""
+    pos = 0
+    for key, field in state.fields.items():
+        n = len(domain.arrays_from_field(field))
+        yield key, field, pos, n
+        pos += n
+
+
+def ctypes_struct(name, members):
+    """The ctypes mirror of the C struct that `stencil_codegen.struct_text(name, members)` defines."""
+    return type(name, (ctypes.Structure,), dict(
+        _fields_=[(m.name, m.ctype if m.length is None else m.ctype * m.length) for m in members]))
+
+
+def _hyper(hyper):
+    """(alpha, 1 - beta_1, 1 - beta_2, eps, alpha_dev) as the launchers take them: alpha a host number, or a device tensor
+    (the step size of a replayed graph) passed by pointer."""
+    alpha, omb1, omb2, eps = hyper
+    adev = alpha.data_ptr() if isinstance(alpha, torch.Tensor) else None
+    return (0.0 if adev else float(alpha), float(omb1), float(omb2), float(eps), adev)
+
+
+class StencilBinding:
+    """The generated kernels of one traced operator: source, library, buffers, argument block, launches."""
+
+    def __init__(self, problem, state, tr, outs, raw, G, slab, jac, device, par_refused):
+        """tr, outs, raw, G: of `stencil_jit.trace_outputs`; slab, jac: of `_Codegen`.  par_refused(e): called when the
+        outputs in parameter space have no elementwise form (param_expr.Unsupported) -- it raises, or returns and leaves
+        them to the caller (`par_outputs` stays None)."""
+        from .core import Array, NeuralNet
+
+        domain = problem.domain
+        self.problem, self.domain, self.tr, self.raw, self.G = problem, domain, tr, raw, G
+        # outputs in parameter space (param_tape.py): [(position, expression, slice of the tape it needs)]
+        self.offgrid = [(k, e, tr.param_tape.slice_for(e.param_ids())) for k, e in tr.offgrid]
+        self.param_tape = tr.param_tape
+        cg = self.cg = _Codegen(tr, outs, raw, G, state, slab=slab, jac=jac)
+        # ... as ONE generated kernel when the taped operations have an elementwise form (param_expr.py)
+        self.par_outputs = None
+        if self.offgrid:
+            numel = {i: int(a.numel()) for i, a in enumerate(domain.arrays_from_state(state))}
+            try:
+                self.par_outputs = param_expr.convert(tr.param_tape, self.offgrid, numel)
+            except param_expr.Unsupported as e:
+                par_refused(e)
+        if self.par_outputs is not None:
+            cg.parameter_outputs(self.par_outputs, numel, {
+                i: key for key, field, pos, n in field_ranges(domain, state) if isinstance(field, (NeuralNet, Array))
+                for i in range(pos, pos + n)})
+        self.source = cg.source()
+        self.lib, self.lib_path = _compile(self.source, cg.flags)
+        for name, argtypes in _ARGTYPES.items():
+            if hasattr(self.lib, name):
+                getattr(self.lib, name).argtypes = argtypes
+        dt = self.dtype = tr.torch_dtype
+        self.total, self.nout = cg.total, len(outs)
+        # Every block ends with one block reduction per output and per network / array parameter: operators
+        # that differentiate through parameters (dozens of reductions) want few, long blocks -- heat with two
+        # space dimensions (46 parameters, 67 M points): 6.6 ms / epoch at 65536 blocks, 5.2 at 4096; plain
+        # stencils prefer many (tracer 4-D: 62.0 ms at 65536, 64.5 at 4096).
+        cap = cg.max_blocks or (4096 if len(cg.pg_decl) > 8 else 65536)
+        self.nblocks = min((self.total // cg.vw_fwd + 255) // 256, cap)
+        nout, npg = self.nout, len(cg.pg_decl)
+        self.cot = [torch.empty(cg.GL, dtype=dt, device=device) for _ in range(cg.ncot)]
+        self.part = torch.empty(max(1, nout * self.nblocks), dtype=dt, device=device)
+        self.ppart = torch.empty(max(1, npg * self.nblocks), dtype=dt, device=device)
+        self.part2 = torch.zeros(16 * (nout + npg), dtype=dt, device=device)
+        self.out = torch.zeros(1 + 2 * nout, dtype=dt, device=device)
+        self.pgrad = torch.zeros(max(1, npg), dtype=dt, device=device)
+        # marching kernels: what their in-kernel sums of read cotangents hand across segments of rows / strips of columns
+        self.edge = torch.zeros(max(1, cg.edge_numel), dtype=dt, device=device)
+        a = self.args = ctypes_struct("Args", cg.args_layout())()
+        for i, t in enumerate(tr.tensors):
+            a.ten[i] = t.data_ptr()
+        for i, t in enumerate(self.cot):
+            a.cot[i] = t.data_ptr()
+        for name in ("part", "ppart", "part2", "out", "pgrad", "edge"):
+            setattr(a, name, getattr(self, name).data_ptr())
+        a.nblocks, a.hs = self.nblocks, None
+        if self.par_outputs is not None:
+            self.par_args = ctypes_struct("ParArgs", cg.par_args_layout())()
+            self.pout = torch.zeros(2 * len(self.par_outputs), dtype=dt, device=device)
+            self.par_args.pout = self.pout.data_ptr()
+
+    # ---- host scalars -----------------------------------------------------------------------
+    def _host_value(self, n, memo):
+        if n.idx in memo:
+            return memo[n.idx]
+        if n.op == "const":
+            v = n.attr
+        elif n.op == "tracer":
+            v = self.problem.tracers[n.attr]
+        elif n.op == "where":
+            c, a, b = (self._host_value(x, memo) for x in n.args)
+            v = a if c else b
+        elif len(n.args) == 1:
+            v = _HOST_UNARY[n.op](self._host_value(n.args[0], memo))
+        else:
+            v = _HOST_BINARY[n.op](self._host_value(n.args[0], memo), self._host_value(n.args[1], memo))
+        memo[n.idx] = v
+        return v
+
+    def host_scalars(self):
+        """Host scalars of the trace: functions of `problem.tracers`, evaluated in Python double as the
+        operator itself would."""
+        memo = dict()
+        return [float(self._host_value(n, memo)) for n in self.cg.hs]
+
+    def refresh_host_scalars(self):
+        """Current host scalars -> the argument struct.  Every eager launch copies the struct, so epochs
+        queued behind each other keep their own values however far the host runs ahead."""
+        for i, v in enumerate(self.host_scalars()):
+            self.args.hsv[i] = v
+
+    # ---- launches (on the current stream; the argument block is copied by the launch) --------------------------------
+    def _launch(self, name, *args):
+        rc = getattr(self.lib, name)(*args, ops.stream_ptr())
+        if rc != 0:
+            raise RuntimeError("generated kernel launch failed ({}): hip error {}".format(name, rc))
+
+    def fwd(self):
+        """k_fwd, k_final, k_loss: cotangents, loss terms and norms, parameter gradients of the bound sources."""
+        self._launch("jit_fwd", ctypes.byref(self.args))
+
+    def gather(self, which, g, adam=None):
+        """Gather number `which` (position in `cg.gathers`) into g.  adam = (x, m, v, alpha, one_minus_b1, one_minus_b2,
+        eps): the Adam update (reference optimizer.py:316-318) by the lane that forms the gradient; alpha as in `_hyper`."""
+        if adam is None:
+            self._launch("jit_gather", which, ctypes.byref(self.args), g.data_ptr())
+        else:
+            self._launch("jit_gather_adam", which, ctypes.byref(self.args), g.data_ptr(), *(t.data_ptr() for t in adam[:3]),
+                         *_hyper(adam[3:]))
+
+    def gather_all(self, g, x=None, m=None, v=None, hyper=None):
+        """Every field of `cg.merged` in one launch.  g: their gradient arrays in that order; x, m, v: the arrays the
+        fused Adam update works on, None where a field gets none; hyper = (alpha, one_minus_b1, one_minus_b2, eps)."""
+        nk = len(self.cg.merged)
+        ptrs = [(_P * nk)(*[None if t is None else t.data_ptr() for t in (lst or [None] * nk)]) for lst in (g, x, m, v)]
+        self._launch("jit_gather_all", ctypes.byref(self.args), *ptrs, *_hyper(hyper or (0.0, 0.0, 0.0, 0.0)))
+
+    def jac(self, buf):
+        """k_jac: the arrays of `cg.jac_items` into the leading slices of `buf` [len(jac_items), *cg.GL]."""
+        n = len(self.cg.jac_items)
+        if not n:
+            raise RuntimeError("these kernels were generated without their Jacobian kernel (jac=False)")
+        self._launch("jit_jac", ctypes.byref(self.args), (_P * n)(*[buf[j].data_ptr() for j in range(n)]))
+
+    def par(self, vals, grads):
+        """k_par behind k_loss: the parameter-space outputs -- terms and norms into `pout`, the loss, gradients added to
+        (set in) `grads`.  vals, grads: the parameter arrays `cg.par_index` and their gradients."""
+        for s_, (val, grad) in enumerate(zip(vals, grads)):
+            if not val.is_contiguous() or val.dtype != self.dtype:
+                raise RuntimeError("parameter arrays must be contiguous {} tensors".format(self.dtype))
+            self.par_args.val[s_], self.par_args.grad[s_] = val.data_ptr(), grad.data_ptr()
+        self._launch("jit_par", ctypes.byref(self.args), ctypes.byref(self.par_args))

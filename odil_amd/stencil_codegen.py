@@ -4,6 +4,7 @@ deterministic final reductions, and the hipcc / cache plumbing that turns the so
 shared object.
 """
 
+import collections
 import ctypes
 import hashlib
 import math
@@ -169,9 +170,30 @@ def _lit(value, kind):
     return "((T){!r})".format(v)
 
 
+# One member of an argument block shared by the generated source and the host (`_Codegen.args_layout`): C declaration
+# type, name, array length (None: a scalar), ctypes type of one element; joined: declared in the previous member's statement
+# (`int off, lo`).  The C struct is rendered from the list by `struct_text`, the host's ctypes.Structure is built from it
+# (stencil_bind.ctypes_struct): there is no second description of the layout.
+Member = collections.namedtuple("Member", "decl name length ctype joined", defaults=(False,))
+_PTR, _INT = ctypes.c_void_p, ctypes.c_int
+
+
+def struct_text(name, members):
+    """The one-line C definition of `struct name` with `members` in order."""
+    decls = []
+    for m in members:
+        item = m.name if m.length is None else "{}[{}]".format(m.name, m.length)
+        if m.joined:
+            decls[-1] += ", " + item
+        else:
+            decls.append("{} {}".format(m.decl, item))
+    return "struct {} {{ {}; }};".format(name, "; ".join(decls))
+
+
 class _Codegen:
-    def __init__(self, tr, outputs, raw, shape, state, slab=None):
-        """slab = (axis, n): the kernels of ONE RANK of a slab decomposition along grid axis `axis` (n owned
+    def __init__(self, tr, outputs, raw, shape, state, slab=None, jac=False):
+        """jac: also emit `k_jac`, the Jacobian coefficient arrays (`_jacobian_kernel`).
+        slab = (axis, n): the kernels of ONE RANK of a slab decomposition along grid axis `axis` (n owned
         cells of it per rank; odil_amd/slab_traced.py).  Threads then cover the owned cells only; the index of
         that axis seen by index leaves, constant arrays and windows is the GLOBAL one (i + a.off); sources are
         the rank's ghost-extended arrays (a.lo ghost cells below the owned ones, a.ea cells in all along the
@@ -204,7 +226,12 @@ class _Codegen:
         if largest >= 2**31 - 1024:
             raise TraceUnsupported("grid too large for 32-bit indexing")
         self.lines = []
-        self.max_blocks = 0  # 0: chosen by the operator (stencil_jit)
+        self.max_blocks = 0  # 0: chosen by the host (stencil_bind)
+        self.want_jac = bool(jac)
+        self.par_outputs, self.par_numel, self.par_keys = None, dict(), dict()  # (parameter_outputs)
+        # what source() leaves for the host: defined from the start, empty until then
+        self.ncot, self.par_arrays, self.edge_numel, self.gathers_done = 0, 0, 0, False
+        self.jac_items, self.merged, self.par_index = [], [], []
         # reachable nodes
         live = set()
         stack = list(outputs)
@@ -271,6 +298,12 @@ class _Codegen:
         self.pseudo_slot = dict()  # "@..." pseudo-field of a stored adjoint array -> its slot in a.cot
         self.out_mode = self._choose_output_cuts()
         self.cut_set = self._choose_cuts()
+
+    def parameter_outputs(self, outputs, numel, keys):
+        """Before source(): the outputs in parameter space that `k_par` evaluates (param_expr.py).  outputs: what
+        param_expr.convert returns; numel: array index (`arrays_from_state` order) -> elements; keys: array index -> field
+        key, for the arrays of networks / `Array`s."""
+        self.par_outputs, self.par_numel, self.par_keys = outputs, numel, keys
 
     def _needs_grad(self):
         need = dict()
@@ -1469,8 +1502,7 @@ class _Codegen:
         fwd_pre = self.pre + self._group_arrays()
         nout = len(self.outputs)
         self.npar = sum(len(g) for names in self.pgrads.values() for g in names)
-        par_arrays = sum(2 * (len(layers) - 1) for _, layers in self.nets) + len(self.arrays)
-        self.par_arrays = par_arrays
+        self.par_arrays = sum(2 * (len(layers) - 1) for _, layers in self.nets) + len(self.arrays)
         T = "double" if tdt == torch.float64 else "float"
         fn = "name" if T == "double" else "name##f"
         # the optimizer state and the gradient stream through a gather once per epoch: non-temporal accesses keep them
@@ -1644,9 +1676,9 @@ class _Codegen:
             self._march_gather_kernels(S, mgather)
         self.gathers_done = mgather is not None
         self._standard_gathers(S)
-        if getattr(self, "want_jac", False):
+        if self.want_jac:
             self._jacobian_kernel(S)
-        self._launchers(S, nout, par_arrays, HEAD)
+        self._launchers(S, nout, HEAD)
         return "\n".join(HEAD + S) + "\n"
 
     def _jacobian_kernel(self, S):
@@ -1783,14 +1815,13 @@ class _Codegen:
             S.append("  return (int)hipGetLastError();")
             S.append("}")
 
-    def _launchers(self, S, nout, par_arrays, HEAD):
+    def _launchers(self, S, nout, HEAD):
         # outputs in parameter space as one generated kernel (param_expr.py), when their tape has an elementwise form
-        self.par_index = []
-        if getattr(self, "par_outputs", None):
+        if self.par_outputs:
             from . import param_expr
 
             fresh = {i for i, key in self.par_keys.items() if key not in self.pgrads}
-            self.par_index = param_expr.emit(self, S, self.par_outputs, fresh)
+            param_expr.emit(self, S, self.par_outputs, fresh)
         # launchers
         S.append('extern "C" int jit_fwd(const Args* a, void* stream) {')
         S.append("  hipLaunchKernelGGL(k_fwd, dim3(a->nblocks), dim3({}), 0, (hipStream_t)stream, *a);".format(self.fwd_threads))
@@ -1819,7 +1850,7 @@ class _Codegen:
         S.append("  }")
         S.append("  return (int)hipGetLastError();")
         S.append("}")
-        if getattr(self, "jac_items", None):
+        if self.jac_items:
             S.append('extern "C" int jit_jac(const Args* a, void* const* ptrs, void* stream) {')
             S.append("  JacP jp;")
             S.append("  for (int k = 0; k < {}; ++k) jp.p[k] = (T*)ptrs[k];".format(len(self.jac_items)))
@@ -1828,21 +1859,38 @@ class _Codegen:
             S.append("  return (int)hipGetLastError();")
             S.append("}")
         # the argument block: sized last (the gradient expressions add host scalars of their own)
+        HEAD.append(struct_text("Args", self.args_layout()))
+        HEAD.append("#define HS(i) (a.hs ? a.hs[i] : a.hsv[i])")
+
+    def args_layout(self):
+        """After source(): the members of `struct Args`, in order -- what `_launchers` writes into the source and what the
+        host builds its ctypes structure from."""
         nsrc = max(1, len(self.src_keys))
-        slab_members = ""
+        # host scalars (functions of `tracers`): BY VALUE in the argument struct (hsv) -- an eager launch owns its
+        # copy, nothing the host rewrites later is read by a queued kernel; a launch captured into a hipGraph
+        # reads them from device memory instead (hs != NULL: the row of the epoch being replayed)
+        members = [
+            Member("const T*", "src", nsrc, _PTR), Member("const void*", "ten", max(1, len(self.tr.tensors)), _PTR),
+            Member("T*", "cot", max(1, self.ncot), _PTR), Member("const T*", "par", max(1, self.par_arrays), _PTR),
+            Member("const double*", "hs", None, _PTR), Member("double", "hsv", max(1, len(self.hs)), ctypes.c_double),
+            Member("T*", "part", None, _PTR), Member("T*", "ppart", None, _PTR), Member("T*", "part2", None, _PTR),
+            Member("T*", "out", None, _PTR), Member("T*", "pgrad", None, _PTR), Member("T*", "edge", None, _PTR),
+            Member("int", "nblocks", None, _INT)]
         if self.slab is not None:
             # off: global index of the first owned cell; lo / ea: ghost cells below the owned ones / extent of the
             # local arrays along the sharded axis; hw: cells in a wrap plane buffer; wlo / whi: wrap planes of the
             # sources (read), gwlo / gwhi: of the gradients (written by the gathers where the array has no ghosts)
-            slab_members = " int off, lo, ea, hw; const T* wlo[{0}]; const T* whi[{0}]; T* gwlo[{0}]; T* gwhi[{0}]; int alo, ahi;".format(nsrc)
-        # host scalars (functions of `tracers`): BY VALUE in the argument struct (hsv) -- an eager launch owns its
-        # copy, nothing the host rewrites later is read by a queued kernel; a launch captured into a hipGraph
-        # reads them from device memory instead (hs != NULL: the row of the epoch being replayed)
-        HEAD.append("struct Args {{ const T* src[{}]; const void* ten[{}]; T* cot[{}]; const T* par[{}]; const double* hs; "
-                    "double hsv[{}]; T* part; T* ppart; T* part2; T* out; T* pgrad; T* edge; int nblocks;{} }};".format(
-                        nsrc, max(1, len(self.tr.tensors)), max(1, self.ncot),
-                        max(1, par_arrays), max(1, len(self.hs)), slab_members))
-        HEAD.append("#define HS(i) (a.hs ? a.hs[i] : a.hsv[i])")
+            members += [
+                Member("int", "off", None, _INT), Member("int", "lo", None, _INT, True), Member("int", "ea", None, _INT, True),
+                Member("int", "hw", None, _INT, True), Member("const T*", "wlo", nsrc, _PTR), Member("const T*", "whi", nsrc, _PTR),
+                Member("T*", "gwlo", nsrc, _PTR), Member("T*", "gwhi", nsrc, _PTR),
+                Member("int", "alo", None, _INT), Member("int", "ahi", None, _INT, True)]
+        return members
+
+    def par_args_layout(self):
+        """The members of `struct ParArgs` (param_expr.emit): values and gradients of the arrays `par_index`, the terms."""
+        K = max(1, len(self.par_index))
+        return [Member("const T*", "val", K, _PTR), Member("T*", "grad", K, _PTR), Member("T*", "pout", None, _PTR)]
 
     # ---- network evaluations shared by MARCHING (float kernels with a pointwise network at the faces) ---------------------
     def _march_parts(self):

@@ -20,19 +20,17 @@ The multigrid synthesis before and P^T (+ Adam) after are the hand-written kerne
 libodil_hip.so.  Everything the tracer cannot express (reductions, slicing of symbolic values,
 host control flow on device data, `Array` unknowns) raises TraceUnsupported and the problem keeps
 using the generic autograd path.  The source is compiled with hipcc into an in-tree cache
-(odil_amd/_jit_cache, keyed by the source hash) and loaded with ctypes.
+(odil_amd/_jit_cache, keyed by the source hash) and loaded with ctypes; library, buffers, argument block and launches
+are bound to the host in stencil_bind.py.
 """
 
-import ctypes
 import os
 
 import torch
 
 from . import ops
-from .stencil_codegen import _Codegen, _compile
+from .stencil_bind import StencilBinding, field_ranges
 from .stencil_trace import (  # noqa: F401  (re-exported: the public names of the tracer)
-    _HOST_BINARY,
-    _HOST_UNARY,
     _R,
     ModTrace,
     ParamArray,
@@ -119,120 +117,28 @@ def trace_outputs(problem, state, only=None):
     return tr, outs, raw, names, G
 
 
-class TracedOperator:
-    """loss / gradient of one user operator through its generated kernels."""
+class TracedOperator(StencilBinding):
+    """loss / gradient of one user operator through its generated kernels: the binding of stencil_bind.py, plus where the
+    sources come from and where the gradients go on a single GPU."""
 
     def __init__(self, problem, state, only=None, jac=False):
         """jac: also generate `k_jac`, the Jacobian coefficient arrays of `Problem.eval_operator_grad` (a library of its own:
         the Newton driver asks for it, the gradient optimizers never pay for it)."""
         from .core import Field, MultigridField
+        from .util import printlog
 
         domain = problem.domain
-        self.problem, self.domain = problem, domain
         tr, outs, raw, self.names, G = trace_outputs(problem, state, only)
-        self.G, self.raw = G, raw
-        # outputs in parameter space (param_tape.py): [(position, expression, slice of the tape it needs)]
-        self.offgrid = [(k, e, tr.param_tape.slice_for(e.param_ids())) for k, e in tr.offgrid]
-        self.param_tape = tr.param_tape
-        cg = _Codegen(tr, outs, raw, G, state)
-        cg.want_jac = bool(jac)
-        # ... as ONE generated kernel when the taped operations have an elementwise form (param_expr.py); else the torch
-        # replay of _eval_offgrid
-        self.par_outputs = None
-        if self.offgrid:
-            from . import param_expr
-            from .core import Array, NeuralNet
-
-            arrays0 = domain.arrays_from_state(state)
-            try:
-                self.par_outputs = param_expr.convert(tr.param_tape, self.offgrid, {i: int(a.numel()) for i, a in enumerate(arrays0)})
-            except param_expr.Unsupported as e:
-                from .util import printlog
-
-                printlog("odil_amd: parameter-space output evaluated by torch ({})".format(e))
-            if self.par_outputs is not None:
-                cg.par_outputs, cg.par_numel, cg.par_keys, pos = self.par_outputs, dict(), dict(), 0
-                for key, field in state.fields.items():
-                    n = len(domain.arrays_from_field(field))
-                    for i in range(pos, pos + n):
-                        cg.par_numel[i] = int(arrays0[i].numel())
-                        if isinstance(field, (NeuralNet, Array)):
-                            cg.par_keys[i] = key
-                    pos += n
-        self.source = cg.source()
-        self.lib, self.lib_path = _compile(self.source, cg.flags)
-        self.cg, self.tr = cg, tr
+        # (parameter-space outputs without an elementwise form: the torch replay of _eval_offgrid)
+        super().__init__(problem, state, tr, outs, raw, G, None, jac, domain.mod.device, lambda e: printlog(
+            "odil_amd: parameter-space output evaluated by torch ({})".format(e)))
+        cg, dev, dt = self.cg, domain.mod.device, self.dtype
         self.tracer_keys = [n.attr for n in tr.nodes if n.op == "tracer"]
-        dev, dt = domain.mod.device, tr.torch_dtype
-        self.total = cg.total
-        # Every block ends with one block reduction per output and per network / array parameter: operators
-        # that differentiate through parameters (dozens of reductions) want few, long blocks -- heat with two
-        # space dimensions (46 parameters, 67 M points): 6.6 ms / epoch at 65536 blocks, 5.2 at 4096; plain
-        # stencils prefer many (tracer 4-D: 62.0 ms at 65536, 64.5 at 4096).
-        cap = cg.max_blocks or (4096 if len(cg.pg_decl) > 8 else 65536)
-        self.nblocks = min((self.total // cg.vw_fwd + 255) // 256, cap)
-        nout = len(outs)
-        self.cot = [torch.empty(G, dtype=dt, device=dev) for _ in range(cg.ncot)]
-        self.part = torch.empty(max(1, nout * self.nblocks), dtype=dt, device=dev)
-        self.ppart = torch.empty(max(1, len(cg.pg_decl) * self.nblocks), dtype=dt, device=dev)
-        self.out = torch.zeros(1 + 2 * nout, dtype=dt, device=dev)
-        self.pgrad = torch.zeros(max(1, len(cg.pg_decl)), dtype=dt, device=dev)
-        par_arrays = cg.par_arrays
-
-        class Args(ctypes.Structure):
-            _fields_ = [
-                ("src", ctypes.c_void_p * max(1, len(cg.src_keys))),
-                ("ten", ctypes.c_void_p * max(1, len(tr.tensors))),
-                ("cot", ctypes.c_void_p * max(1, cg.ncot)),
-                ("par", ctypes.c_void_p * max(1, par_arrays)),
-                ("hs", ctypes.c_void_p), ("hsv", ctypes.c_double * max(1, len(cg.hs))),
-                ("part", ctypes.c_void_p), ("ppart", ctypes.c_void_p), ("part2", ctypes.c_void_p), ("out", ctypes.c_void_p),
-                ("pgrad", ctypes.c_void_p), ("edge", ctypes.c_void_p), ("nblocks", ctypes.c_int),
-            ]
-
-        self.args = Args()
-        for i, t in enumerate(tr.tensors):
-            self.args.ten[i] = t.data_ptr()
-        for i, t in enumerate(self.cot):
-            self.args.cot[i] = t.data_ptr()
-        self.part2 = torch.zeros(16 * (nout + len(cg.pg_decl)), dtype=dt, device=dev)
-        self.args.part, self.args.ppart = self.part.data_ptr(), self.ppart.data_ptr()
-        self.args.part2 = self.part2.data_ptr()
-        self.args.out, self.args.pgrad = self.out.data_ptr(), self.pgrad.data_ptr()
-        # marching kernels: what their in-kernel sums of read cotangents hand across segments of rows / strips of columns
-        self.edge = torch.zeros(max(1, getattr(cg, "edge_numel", 0)), dtype=dt, device=dev)
-        self.args.edge = self.edge.data_ptr()
-        self.args.nblocks = self.nblocks
-        self.args.hs = None
         self._hs_rows = None  # graph replay: (pinned table, device table, device row, device row index)
-        self.lib.jit_fwd.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        if self.par_outputs is not None:
-            npar = max(1, len(cg.par_index))
-
-            class ParArgs(ctypes.Structure):
-                _fields_ = [("val", ctypes.c_void_p * npar), ("grad", ctypes.c_void_p * npar), ("pout", ctypes.c_void_p)]
-
-            self.par_args = ParArgs()
-            self.pout = torch.zeros(2 * len(self.par_outputs), dtype=dt, device=dev)
-            self.par_args.pout = self.pout.data_ptr()
-            self.lib.jit_par.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        self.lib.jit_gather.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        self.lib.jit_gather_adam.argtypes = [ctypes.c_int, ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_double] * 4 + [
-            ctypes.c_void_p, ctypes.c_void_p]
-        if getattr(cg, "jac_items", None):
-            self.lib.jit_jac.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
-        if cg.merged:
-            self.lib.jit_gather_all.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_void_p)] * 4 + [
-                ctypes.c_double] * 4 + [ctypes.c_void_p, ctypes.c_void_p]
         # structure of the state: which arrays belong to which field
-        self.layout = []
-        pos = 0
-        for key, field in state.fields.items():
-            n = len(domain.arrays_from_field(field))
-            kind = ("field" if isinstance(field, Field) else "mg" if isinstance(field, MultigridField)
-                    else "net")  # NeuralNet or Array: a few parameters, gradients reduced over the grid
-            self.layout.append((key, kind, pos, n))
-            pos += n
+        # ("net": NeuralNet or Array -- a few parameters, gradients reduced over the grid)
+        self.layout = [(key, "field" if isinstance(f, Field) else "mg" if isinstance(f, MultigridField) else "net", pos, n)
+                       for key, f, pos, n in field_ranges(domain, state)]
         self.signature = self._signature(state)
         # gradients live in ONE packed buffer in `arrays_from_state` order (what the optimizers
         # want: no per-array copies); kernels write straight into its views
@@ -271,36 +177,6 @@ class TracedOperator:
 
     def matches(self, state):
         return self._signature(state) == self.signature
-
-    # ---- host scalars -----------------------------------------------------------------------
-    def _host_value(self, n, memo):
-        if n.idx in memo:
-            return memo[n.idx]
-        if n.op == "const":
-            v = n.attr
-        elif n.op == "tracer":
-            v = self.problem.tracers[n.attr]
-        elif n.op == "where":
-            c, a, b = (self._host_value(x, memo) for x in n.args)
-            v = a if c else b
-        elif len(n.args) == 1:
-            v = _HOST_UNARY[n.op](self._host_value(n.args[0], memo))
-        else:
-            v = _HOST_BINARY[n.op](self._host_value(n.args[0], memo), self._host_value(n.args[1], memo))
-        memo[n.idx] = v
-        return v
-
-    def host_scalars(self):
-        """Host scalars of the trace: functions of `problem.tracers`, evaluated in Python double as the
-        operator itself would."""
-        memo = dict()
-        return [float(self._host_value(n, memo)) for n in self.cg.hs]
-
-    def refresh_host_scalars(self):
-        """Current host scalars -> the argument struct.  Every eager launch copies the struct, so epochs
-        queued behind each other keep their own values however far the host runs ahead."""
-        for i, v in enumerate(self.host_scalars()):
-            self.args.hsv[i] = v
 
     # Epochs replayed as a hipGraph (optimizer._EpochGraph) cannot take new kernel arguments: the captured
     # launch reads row k of a device table, k a device counter advanced by the graph itself.  The host fills
@@ -347,19 +223,10 @@ class TracedOperator:
         return pool[: min(nfields, 4)]
 
     # ---- evaluation ---------------------------------------------------------------------------
-    def _launch(self, state):
-        keep = self._bind(state)
-        rc = self.lib.jit_fwd(ctypes.byref(self.args), ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("traced operator launch failed: hip error {}".format(rc))
-        return keep
-
     def eval_operator_grad(self, state):
         """values, grads, names of `Problem.eval_operator_grad` (reference core.py:1313-1361) from the generated `k_jac`:
         per output its value array and {(key, shift, loc): d output / d read}, one launch, no autograd graph."""
         cg = self.cg
-        if not getattr(cg, "jac_items", None):
-            raise RuntimeError("this operator was traced without its Jacobian kernel")
         keep = self._bind(state)
         dev, dt = self.out.device, self.tr.torch_dtype
         n = len(cg.jac_items)
@@ -367,10 +234,7 @@ class TracedOperator:
         # arrays back to back -- gmg.recognise_stencil -- takes a view instead of seven copies)
         buf = torch.empty((n,) + tuple(self.G), dtype=dt, device=dev)
         arrays = [buf[j] for j in range(n)]
-        ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in arrays])
-        rc = self.lib.jit_jac(ctypes.byref(self.args), ptrs, ops.stream_ptr())
-        if rc != 0:
-            raise RuntimeError("traced Jacobian launch failed: hip error {}".format(rc))
+        self.jac(buf)
         del keep
         nout = len(self.raw)
         values, grads = [None] * nout, [dict() for _ in range(nout)]
@@ -477,29 +341,20 @@ class TracedOperator:
     def eval_loss_grad(self, state, adam=None):
         """loss, grads (views of one packed buffer, overwritten by the next call), terms, names, norms."""
         cg = self.cg
-        keep = self._launch(state)
+        keep = self._bind(state)
+        self.fwd()
         cur = torch.cuda.current_stream()
         chains = [item for item in self.layout if item[1] in ("field", "mg") and (item[0] in cg.gathers or item[0] in cg.direct)]
         merged = set()
         if cg.merged:
             # the gradients of all these fields in ONE launch (what their expressions read is read once)
-            by_key = {key: (pos, n) for key, kind, pos, n in self.layout}
-            nk = len(cg.merged)
-            arr = lambda: (ctypes.c_void_p * nk)()
-            gp, xp, mp, vp = arr(), arr(), arr(), arr()
-            alpha, omb1, omb2, eps, adev = 0.0, 0.0, 0.0, 0.0, None
-            for k, key in enumerate(cg.merged):
-                pos = by_key[key][0]
-                gp[k] = self.gtmp.get(key, self.gviews[pos]).data_ptr()
-                if adam is not None and key in adam[0]:
-                    _, arrays, mm, vv, alpha, omb1, omb2, eps = adam
-                    xp[k], mp[k], vp[k] = arrays[pos].data_ptr(), mm[pos].data_ptr(), vv[pos].data_ptr()
-            if isinstance(alpha, torch.Tensor):
-                adev, alpha = alpha.data_ptr(), 0.0
-            rc = self.lib.jit_gather_all(ctypes.byref(self.args), gp, xp, mp, vp, float(alpha), float(omb1), float(omb2),
-                                         float(eps), adev, ops.stream_ptr())
-            if rc != 0:
-                raise RuntimeError("traced gather launch failed: hip error {}".format(rc))
+            first = {key: pos for key, kind, pos, n in self.layout}
+            g = [self.gtmp.get(key, self.gviews[first[key]]) for key in cg.merged]
+            if adam is not None:  # (x, m, v of the fields whose update the launch applies)
+                xmv = [[lst[first[key]] if key in adam[0] else None for key in cg.merged] for lst in adam[1:4]]
+                self.gather_all(g, *xmv, hyper=adam[4:])
+            else:
+                self.gather_all(g)
             merged = set(cg.merged)
         side = self._side_streams(len(chains))
         for i, (key, kind, pos, n) in enumerate(chains):
@@ -513,16 +368,10 @@ class TracedOperator:
                 elif key in cg.gathers:
                     g = self.gtmp.get(key, self.gviews[pos])
                     if fuse:
-                        _, arrays, mm, vv, alpha, omb1, omb2, eps = adam
-                        adev = alpha.data_ptr() if isinstance(alpha, torch.Tensor) else None
-                        rc = self.lib.jit_gather_adam(
-                            cg.gathers.index(key), ctypes.byref(self.args), g.data_ptr(), arrays[pos].data_ptr(),
-                            mm[pos].data_ptr(), vv[pos].data_ptr(), 0.0 if adev else float(alpha), float(omb1), float(omb2),
-                            float(eps), adev, ops.stream_ptr())
+                        _, arrays, mm, vv = adam[:4]
+                        self.gather(cg.gathers.index(key), g, (arrays[pos], mm[pos], vv[pos]) + tuple(adam[4:]))
                     else:
-                        rc = self.lib.jit_gather(cg.gathers.index(key), ctypes.byref(self.args), g.data_ptr(), ops.stream_ptr())
-                    if rc != 0:
-                        raise RuntimeError("traced gather launch failed: hip error {}".format(rc))
+                        self.gather(cg.gathers.index(key), g)
                 else:
                     g = self.cot[cg.direct[key]]
                 if kind == "mg":
@@ -551,14 +400,7 @@ class TracedOperator:
         if self.par_outputs is not None:
             # the parameter-space outputs: one launch behind k_loss -- terms, norms, the loss and the parameters' gradients
             arrays = self.domain.arrays_from_state(state)
-            for s_, index in enumerate(cg.par_index):
-                if not arrays[index].is_contiguous() or arrays[index].dtype != self.tr.torch_dtype:
-                    raise RuntimeError("parameter arrays must be contiguous {} tensors".format(self.tr.torch_dtype))
-                self.par_args.val[s_] = arrays[index].data_ptr()
-                self.par_args.grad[s_] = self.gviews[index].data_ptr()
-            rc = self.lib.jit_par(ctypes.byref(self.args), ctypes.byref(self.par_args), ops.stream_ptr())
-            if rc != 0:
-                raise RuntimeError("parameter-space kernel launch failed: hip error {}".format(rc))
+            self.par([arrays[i] for i in cg.par_index], [self.gviews[i] for i in cg.par_index])
         out = self.out.clone()
         nout = len(self.raw)
         loss = out[0]

@@ -385,3 +385,59 @@ def test_outputs_on_grids_of_different_shapes_become_one_kernel_set_per_shape(cp
     # an output that mixes two grids stays untraceable
     bad = lambda ctx: [ctx.field("a"), ctx.field("b")[1:, 1:] + ctx.field("a")]
     assert stencil_jit.trace(odil.Problem(bad, domain), state) is None
+
+
+def _natural_size(members):
+    """sizeof of a C struct with these members under natural alignment (every member at a multiple of its element's
+    size, the struct padded to a multiple of the largest)."""
+    import ctypes
+
+    size = widest = 0
+    for m in members:
+        elem = ctypes.sizeof(m.ctype)
+        size = -(-size // elem) * elem + elem * (1 if m.length is None else m.length)
+        widest = max(widest, elem)
+    return -(-size // widest) * widest
+
+
+def _check_shared_layout(source, name, members, struct):
+    import ctypes
+
+    from odil_amd.stencil_codegen import struct_text
+
+    lines = [line for line in source.splitlines() if line.startswith("struct {} {{".format(name))]
+    assert lines == [struct_text(name, members)]
+    assert [f[0] for f in struct._fields_] == [m.name for m in members]
+    for (_, ctype), m in zip(struct._fields_, members):
+        assert ctype is (m.ctype if m.length is None else m.ctype * m.length)
+    assert ctypes.sizeof(struct) == _natural_size(members)
+
+
+@pytest.mark.parametrize("mode", ["single", "slab"])
+@pytest.mark.parametrize("case", ["veltracer", "heat_wreg"])
+def test_args_layout_is_shared(cpu_mod, mode, case):
+    """The argument blocks have ONE description, `_Codegen.args_layout()` / `par_args_layout()`: the `struct Args` /
+    `struct ParArgs` lines of the generated source are its rendering, the ctypes structures of the host carry its
+    members in its order, and their size is the one a C compiler gives the struct (natural alignment).  veltracer: no
+    parameters; heat --kwreg: a network and an output in parameter space (`k_par`, ParArgs)."""
+    import heat
+    import veltracer
+
+    from odil_amd.slab_traced import HipSlabKernels
+
+    if case == "veltracer":
+        problem, state = veltracer.make_problem(veltracer.parse_args(["--Nx", "16", "--Nt", "8"]))
+    else:
+        problem, state = heat.make_problem(heat.parse_args(["--Nx", "16", "--Nt", "8", "--infer_k", "1", "--kwreg", "1"]))
+    bound = stencil_jit.TracedOperator(problem, state) if mode == "single" else HipSlabKernels(problem, state, 1, 8, "cpu")
+    members = bound.cg.args_layout()
+    names = [m.name for m in members]
+    assert names[:13] == ["src", "ten", "cot", "par", "hs", "hsv", "part", "ppart", "part2", "out", "pgrad", "edge", "nblocks"]
+    assert names[13:] == ([] if mode == "single" else ["off", "lo", "ea", "hw", "wlo", "whi", "gwlo", "gwhi", "alo", "ahi"])
+    _check_shared_layout(bound.source, "Args", members, type(bound.args))
+    assert (bound.par_outputs is not None) == (case == "heat_wreg")
+    if case == "heat_wreg":
+        assert len(bound.cg.par_index) >= 1
+        _check_shared_layout(bound.source, "ParArgs", bound.cg.par_args_layout(), type(bound.par_args))
+    else:
+        assert "struct ParArgs" not in bound.source and not hasattr(bound, "par_args")
