@@ -1074,7 +1074,7 @@ class Problem:
         if not state.initialized:
             raise RuntimeError("Uninitialized state, use `state = domain.init_state(state)`")
         domain = self.domain
-        # the generated Jacobian kernel (stencil_codegen._jacobian_kernel): values and every per-shift coefficient array in
+        # the generated Jacobian kernel (stencil_gather._jacobian_kernel): values and every per-shift coefficient array in
         # ONE pointwise launch from the symbolic derivative of the traced operator; operators it cannot express (dense
         # columns of parameter arrays, windows, untraceable code) take the autograd evaluation below
         from . import runtime

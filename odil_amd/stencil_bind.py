@@ -83,7 +83,7 @@ class StencilBinding:
         # that differentiate through parameters (dozens of reductions) want few, long blocks -- heat with two
         # space dimensions (46 parameters, 67 M points): 6.6 ms / epoch at 65536 blocks, 5.2 at 4096; plain
         # stencils prefer many (tracer 4-D: 62.0 ms at 65536, 64.5 at 4096).
-        cap = cg.max_blocks or (4096 if len(cg.pg_decl) > 8 else 65536)
+        cap = 4096 if len(cg.pg_decl) > 8 else 65536
         self.nblocks = min((self.total // cg.vw_fwd + 255) // 256, cap)
         nout, npg = self.nout, len(cg.pg_decl)
         self.cot = [torch.empty(cg.GL, dtype=dt, device=device) for _ in range(cg.ncot)]

@@ -1,25 +1,25 @@
-"""HIP source generation for traced operators (see odil_amd/stencil_jit.py for the overview): the
-forward + register-level reverse-mode kernel `k_fwd`, the per-field cotangent gathers `k_gat_*`, the
-deterministic final reductions, and the hipcc / cache plumbing that turns the source into a loadable
-shared object.
+"""HIP source generation for traced operators (see odil_amd/stencil_jit.py for the overview): the analysis of the traced
+DAG, expressions, the forward + register-level reverse-mode kernel `k_fwd`, the deterministic final reductions, the
+launchers and the argument block.  The marching form of `k_fwd` is emitted by stencil_march.py, the gathers `k_gat_*` and
+`k_jac` by stencil_gather.py; jit_cache.py turns the source into a loadable shared object.
 """
 
 import collections
+import contextlib
 import ctypes
-import hashlib
 import math
+import operator
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import torch
 
 from . import stencil_grad
+from .jit_cache import _HIPCC_FLAGS, _compile  # noqa: F401  (_compile: imported from here by the host side and the tools)
+from .stencil_gather import _GatherKernels
+from .stencil_march import _MarchKernels
 from .stencil_trace import _B, _CMP, _I, _R, TraceUnsupported, _promote
 
-_CACHE_DIR = os.environ.get("ODIL_JIT_CACHE", os.path.join(os.path.dirname(os.path.abspath(__file__)), "_jit_cache"))
-_HIPCC_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "--offload-arch=gfx950"]
 # float kernels (tolerance 2e-5, stated in the tests): contraction to FMA allowed -- the 5 x 5 layers of a pointwise
 # network and their parameter-gradient accumulations become (packed) FMAs instead of multiply + add pairs
 _HIPCC_FLAGS_F32 = [f if f != "-ffp-contract=off" else "-ffp-contract=fast" for f in _HIPCC_FLAGS]
@@ -190,7 +190,53 @@ def struct_text(name, members):
     return "struct {} {{ {}; }};".format(name, "; ".join(decls))
 
 
-class _Codegen:
+class _Adjoints:
+    """What the reverse pass of a body leaves for the kernels around it: the nodes whose adjoint it stores (live reads,
+    cut nodes, outputs cut for the gathers) and the accumulators of the parameter gradients."""
+
+    def __init__(self):
+        self.cots = []  # live read nodes that receive a cotangent
+        self.cut_nodes = []  # affine sub-expressions whose adjoint is stored instead of their reads' cotangents
+        self.jac_store = []  # (output, name of its seed): adjoints of the outputs the gathers differentiate
+        self.pg_decl, self.pg_offset = [], dict()  # accumulator names in the order of a.ppart; net / array key -> first one
+        self.pgrads = dict()  # net / array key -> list of per-array lists of accumulator names
+        self.pg2_used = set()  # keys of the networks whose packed evaluations have accumulators of their own
+
+    def stored(self):
+        return [n.idx for n in self.cots], self.pg_decl, [n.idx for n in self.cut_nodes], self.jac_store
+
+
+class _Body:
+    """The emission state of ONE kernel body: the nodes it evaluates and how, and what has been emitted so far.  The
+    generator has one current body (`_Codegen.body`, replaced by `_Codegen._body` only) and reads it as its own attributes."""
+
+    def __init__(self, order, vw, in_gather=False, fold=None, march_pref=None, march_live=None, adj=None):
+        self.order, self.vw = order, vw  # nodes in evaluation order; points of the last axis per thread (4 or 1)
+        self.in_gather = in_gather  # emitting a gather (slab mode: threads cover the ghost planes too)
+        self.fold = fold  # the interior copy of a body: {predicate node idx: constant value} (_fold_plan)
+        # marching kernel: {read descriptor: (slot, load expression)} of the reads requested a step ahead, the nodes the
+        # variant being emitted really evaluates (None: all), the slots it reads
+        self.march_pref, self.march_live, self.march_used = march_pref, march_live, set()
+        self.lines, self.pre = [], []  # statements per point; per thread, ahead of the points (row loads)
+        self.loads = dict()  # (key, shift, loc) -> variable
+        self.groups = dict()  # (key, shift on the leading axes, loc) -> the row loaded once for four points
+        self.adj = _Adjoints() if adj is None else adj
+
+    def take(self):
+        """The lines emitted since the last call."""
+        lines, self.lines = self.lines, []
+        return lines
+
+
+class _Codegen(_MarchKernels, _GatherKernels):
+    # the current body's state, read-only: another body is installed by `_body`, for the time of its emission
+    order, vw, in_gather, fold, march_pref, march_live, march_used, lines, pre, loads, groups = (
+        property(operator.attrgetter("body." + k)) for k in (
+            "order", "vw", "in_gather", "fold", "march_pref", "march_live", "march_used", "lines", "pre", "loads", "groups"))
+    cots, cut_nodes, jac_store, pg_decl, pg_offset, pgrads, pg2_used = (
+        property(operator.attrgetter("body.adj." + k)) for k in (
+            "cots", "cut_nodes", "jac_store", "pg_decl", "pg_offset", "pgrads", "pg2_used"))
+
     def __init__(self, tr, outputs, raw, shape, state, slab=None, jac=False):
         """jac: also emit `k_jac`, the Jacobian coefficient arrays (`_jacobian_kernel`).
         slab = (axis, n): the kernels of ONE RANK of a slab decomposition along grid axis `axis` (n owned
@@ -225,8 +271,6 @@ class _Codegen:
                         largest = max(largest, int(t.numel()))
         if largest >= 2**31 - 1024:
             raise TraceUnsupported("grid too large for 32-bit indexing")
-        self.lines = []
-        self.max_blocks = 0  # 0: chosen by the host (stencil_bind)
         self.want_jac = bool(jac)
         self.par_outputs, self.par_numel, self.par_keys = None, dict(), dict()  # (parameter_outputs)
         # what source() leaves for the host: defined from the start, empty until then
@@ -241,7 +285,16 @@ class _Codegen:
                 continue
             live.add(n.idx)
             stack.extend(n.args)
-        self.order = [n for n in tr.nodes if n.idx in live]
+        order = [n for n in tr.nodes if n.idx in live]
+        # four points of the last axis per thread, 16-byte accesses
+        last = self.ndim - 1
+        can_vec = self.GL[last] % 4 == 0 and self.GL[last] >= 8 and (slab is None or slab[0] != last)
+        # a forward kernel with a pointwise network is bound by its arithmetic, not by its loads: four points per thread
+        # only cost it registers (heat with two space dimensions: 2.0 -> 2.5 ms)
+        has_net = any(n.op == "mlp" for n in order)
+        self.vw_gat = 4 if can_vec else 1
+        self.vw_fwd = 4 if can_vec and not has_net else 1
+        self.body = _Body(order, self.vw_fwd)  # (of k_fwd)
         for n in self.order:
             if n.op in ("read", "index") and tuple(n.shape) != self.G:
                 raise TraceUnsupported("{} of shape {} on grid {}".format(n.op, n.shape, self.G))
@@ -261,9 +314,6 @@ class _Codegen:
         self.hs_slot = hs_slot
         # sources (regular arrays of fields) and load slots
         self.src_keys = []
-        self.loads = dict()  # (key, shift, loc) -> variable
-        self.cots = []  # live read nodes that receive a cotangent
-        self.cut_nodes = []  # affine sub-expressions whose adjoint is stored instead of their reads' cotangents
         self.nets = []  # (key, layers) with parameter pointers
         self.net_slot = dict()
         self.arrays = []  # (key, numel) of `Array` unknowns read through a[k]
@@ -272,30 +322,20 @@ class _Codegen:
         self.partner, self.pair_first = dict(), set()
         self.share, self.shared_A, self.shared_B = [], set(), set()
         self._choose_shared_calls()
+        # the marching kernel keeps the network's parameters in registers for the whole launch (source())
+        self.wregs = "const" if self.share else "mem"
         if self.fast:
             self._pair_mlps()
         # per output: None (the whole grid) or the lens of its window; the mean runs over that many points
         self.out_lens = [None if o.win is None else tuple(o.win[0]) for o in outputs]
         self.out_count = [int(np.prod(l)) if l is not None else int(np.prod(self.G)) for l in self.out_lens]  # GLOBAL counts
-        # four points of the last axis per thread, 16-byte accesses
-        last = self.ndim - 1
-        can_vec = self.GL[last] % 4 == 0 and self.GL[last] >= 8 and (slab is None or slab[0] != last)
-        vec = "auto"  # (frozen: "0" / "1" force one / four points per thread in tests of the generator)
-        # a forward kernel with a pointwise network is bound by its arithmetic, not by its loads: four points per thread
-        # only cost it registers (heat with two space dimensions: 2.0 -> 2.5 ms)
-        has_net = any(n.op == "mlp" for n in self.order)
-        vec_fwd = vec
-        self.vw_gat = 4 if can_vec and vec != "0" else 1
-        self.vw_fwd = 4 if can_vec and (vec_fwd == "1" or (vec_fwd == "auto" and not has_net)) else 1
-        self.vw = self.vw_fwd
         self.gloc = next(n.attr[2] for n in self.order if n.op == "read")
-        self.in_gather = False  # emitting a gather (slab mode: threads cover the ghost planes too)
-        self.fold = None  # emitting the interior copy of a body: {predicate node idx: constant value} (_fold_plan)
-        self.wregs = "mem"  # where the marching kernel keeps network parameters (source())
-        self.march_pref = None  # marching kernel: {read descriptor: (slot, load expression)} of the reads requested a step ahead
-        self.march_live, self.march_used = None, set()  # ... nodes the variant being emitted really evaluates; slots it reads
         self.mlp_out_seen = dict()  # network call idx -> {output index: mlp_out node}
         self.pseudo_slot = dict()  # "@..." pseudo-field of a stored adjoint array -> its slot in a.cot
+        self._affine_memo, self._consumers = dict(), dict()  # (_choose_cuts) node idx -> _affine of it; -> the nodes that take it
+        for n in self.order:
+            for a in n.args:
+                self._consumers.setdefault(a.idx, []).append(n)
         self.out_mode = self._choose_output_cuts()
         self.cut_set = self._choose_cuts()
 
@@ -304,6 +344,22 @@ class _Codegen:
         param_expr.convert returns; numel: array index (`arrays_from_state` order) -> elements; keys: array index -> field
         key, for the arrays of networks / `Array`s."""
         self.par_outputs, self.par_numel, self.par_keys = outputs, numel, keys
+
+    @contextlib.contextmanager
+    def _body(self, order=None, vw=None, in_gather=None, fold=None, march_pref=None, march_live=None, fresh_adjoints=False):
+        """Installs the state of another body for the time of its emission and yields it; order, vw, in_gather: as in the
+        enclosing body unless given.  fresh_adjoints: a further copy of the enclosing body with a reverse pass of its own,
+        which must store what the enclosing one stores."""
+        prev = self.body
+        self.body = body = _Body(
+            prev.order if order is None else order, prev.vw if vw is None else vw,
+            prev.in_gather if in_gather is None else in_gather, fold, march_pref, march_live, None if fresh_adjoints else prev.adj)
+        try:
+            yield body
+        finally:
+            self.body = prev
+        if fresh_adjoints and body.adj.stored() != prev.adj.stored():
+            raise RuntimeError("interior copy of the traced kernel stores other adjoints than the general one")
 
     def _needs_grad(self):
         need = dict()
@@ -362,13 +418,7 @@ class _Codegen:
         `lap = (q+ - 2 q + q-) / h^2 + ...` needs one array, not one per stencil point.  A node is cut when
         it is linear in at least two live reads and somebody non-linear (or the loss) consumes it."""
         modes = self.out_mode if modes is None else modes
-        memo = self.__dict__.setdefault("_affine_memo", dict())
-        consumers = self.__dict__.get("_consumers")
-        if consumers is None:
-            consumers = self._consumers = dict()
-            for n in self.order:
-                for a in n.args:
-                    consumers.setdefault(a.idx, []).append(n)
+        memo, consumers = self._affine_memo, self._consumers
         outputs = {o.idx for o in self.outputs}
         # nodes only the recomputed outputs reach are never visited by k_fwd's reverse pass
         legacy_live, stack = set(), [o for k, o in enumerate(self.outputs) if modes[k] == "legacy"]
@@ -421,7 +471,6 @@ class _Codegen:
             return mode
         virt_max = 12  # (64 -- the tracer's Laplacian regularisers re-evaluated by the gathers, 4 -> 1 stored arrays -- was measured in round 5: k_fwd 2.71 -> 2.19 ms, merged gather 7.26 -> 13.96 ms)
         used = {a.idx for n in self.order for a in n.args}
-        self.tr.state_locs = dict(getattr(self.tr, "state_locs", dict()))
         out_ids = [o.idx for o in self.outputs]
         for k, o in enumerate(self.outputs):
             if not self.need.get(o.idx, False) or o.idx in used or out_ids.count(o.idx) != 1:
@@ -652,29 +701,18 @@ class _Codegen:
         return out
 
     def _interior_copy(self, nodes, vw, reverse=False):
-        """Second emission of the body whose first emission just ended (self.pre / self.groups hold its row loads), with
-        the index predicates folded: ((forward lines, reverse lines), plan) or None when nothing folds."""
+        """Second emission of the body whose first emission just ended, with the index predicates folded: ((forward lines,
+        reverse lines), plan) or None when nothing folds.  (It visits the same reads in the same order, so the row loads it
+        requests are those the first emission left in self.pre / self.groups: its own are dropped.)"""
         plan = self._fold_plan(nodes, vw, windows=reverse)
         if plan is None:
             return None
-        keep = ("cots", "cut_nodes", "jac_store", "pg_decl", "pg_offset", "pgrads", "pg2_used")
-        saved = {k: getattr(self, k) for k in keep if hasattr(self, k)}
-        if reverse:
-            self.cots, self.cut_nodes, self.jac_store, self.pg_decl, self.pg_offset, self.pg2_used = [], [], [], [], dict(), set()
-        self.fold, self.lines, self.loads = plan[0], [], dict()
-        self.forward()
-        fwd, self.lines, rev = self.lines, [], []
-        if reverse:
-            self.reverse()
-            rev, self.lines = self.lines, []
-            same = ([n.idx for n in self.cots] == [n.idx for n in saved["cots"]] and self.pg_decl == saved["pg_decl"]
-                    and [n.idx for n in self.cut_nodes] == [n.idx for n in saved["cut_nodes"]] and self.jac_store == saved["jac_store"])
-            if not same:
-                raise RuntimeError("interior copy of the traced kernel stores other adjoints than the general one")
-        self.fold = None
-        for k, v in saved.items():
-            setattr(self, k, v)
-        self.pre = list(dict.fromkeys(self.pre))  # (row loads are requested again by the second emission)
+        with self._body(fold=plan[0], fresh_adjoints=reverse) as body:
+            self.forward()
+            fwd, rev = body.take(), []
+            if reverse:
+                self.reverse()
+                rev = body.take()
         return (fwd, rev), plan
 
     # ---- expressions ----------------------------------------------------------------------
@@ -741,10 +779,6 @@ class _Codegen:
         if key.startswith("@"):
             return "a.cot[{}]".format(self.pseudo_slot[key]), self.GL, self.gloc
         return "a.src[{}]".format(self._src_slot(key)), self._field_shape(key), self.state.fields[key].loc
-
-    def _begin(self):
-        """Fresh emission state of one kernel body."""
-        self.lines, self.pre, self.loads, self.groups = [], [], dict(), dict()
 
     def _emit_read(self, n):
         key, shift, loc, _ = n.attr
@@ -983,7 +1017,7 @@ class _Codegen:
         while pairs:
             order = self._sorted_with_pairs(pairs)
             if order is not None:
-                self.order = order
+                self.body.order = order
                 for a, b in pairs:
                     self.partner[a.idx], self.partner[b.idx] = b, a
                     self.pair_first.add(a.idx)
@@ -1041,7 +1075,7 @@ class _Codegen:
         return self.net_slot[key]
 
     def _launder_params(self, base, nl):
-        if getattr(self, "wregs", "mem") != "const":
+        if self.wregs != "const":
             return
         for l in range(nl):
             for c, ofs in (("w", "WOFS"), ("b", "BOFS")):
@@ -1185,7 +1219,6 @@ class _Codegen:
                 self.jac_store.append((k, "gs{}".format(k)))
                 continue
             acc(o, seed)
-        self.pgrads = dict()  # net key -> list of per-array lists of accumulator names
         for n in reversed(self.order):
             op, A = n.op, n.args
             if op == "mlp":
@@ -1475,15 +1508,11 @@ class _Codegen:
             exprs[key] = total
         return exprs
 
+    fwd_threads = 256  # threads of a workgroup of k_fwd
+
     def source(self):
         tdt = self.tr.torch_dtype
-        self.pg_decl, self.pg_offset = [], dict()
-        self.pg2_used = set()
-        self.jac_store = []
-        self.vw = self.vw_fwd
-        vw, last = self.vw, self.ndim - 1
-        self.tr.state_locs = dict(getattr(self.tr, "state_locs", dict()))
-        self._begin()
+        vw = self.vw
         interior = None
         march = None
         if self.share:
@@ -1491,15 +1520,13 @@ class _Codegen:
             fwd, rev = [], []
         else:
             self.forward()
-            fwd = self.lines
-            self.lines = []
+            fwd = self.body.take()
             self.reverse()
-            rev = self.lines
+            rev = self.body.take()
             # (not for kernels with a pointwise network: two copies of the network's forward and reverse pass cost the
             # registers of a second resident wave -- heat 256 x 512^2: 283 + 27 spilled to AGPRs, 3.29 -> 4.36 ms / epoch)
             has_net = any(n.op == "mlp" for n in self.order)
             interior = None if has_net else self._interior_copy(self.order, vw, reverse=True)
-        fwd_pre = self.pre + self._group_arrays()
         nout = len(self.outputs)
         self.npar = sum(len(g) for names in self.pgrads.values() for g in names)
         self.par_arrays = sum(2 * (len(layers) - 1) for _, layers in self.nets) + len(self.arrays)
@@ -1547,11 +1574,7 @@ class _Codegen:
         for (s, l), v in bofs.items():
             S.append("#define BOFS_{}_{} {}".format(s, l, v))
         # ---- k_fwd ---------------------------------------------------------------------------------------------
-        occ = 0  # register budget of k_fwd as waves per SIMD (0: the compiler's)
-        self.fwd_threads = 256
-
-        S.append('extern "C" __global__ __launch_bounds__({}) {}void k_fwd(const Args a) {{'.format(
-            self.fwd_threads, "__attribute__((amdgpu_waves_per_eu({0}, {0}))) ".format(occ) if occ else ""))
+        S.append('extern "C" __global__ __launch_bounds__({}) void k_fwd(const Args a) {{'.format(self.fwd_threads))
         S.append("  __shared__ T sm[{}];".format(self.fwd_threads // 64))
         for k in range(nout):
             S.append("  T s_{} = (T)0;".format(k))
@@ -1574,74 +1597,85 @@ class _Codegen:
         stream = self.ncot * self.total * esize > (128 << 20)  # beyond what the last-level cache keeps
         if march is not None:
             self._march_kernel(S, march, stored, stream)
-        threads = self.total // vw
-        if march is None:
-            flat = "l4" if vw == 4 else "l"
-            S.append(self._block_index(self.GL, vw))
-            if threads <= self.max_blocks * 256:  # one thread per point (or four points)
-                S.append("  const int {}r = bx_ * NB + threadIdx.x;".format(flat))
-                S.append("  if ({}r < {}) {{".format(flat, threads))
-            else:
-                S.append("  for (int {0}r = bx_ * NB + threadIdx.x; {0}r < {1}; {0}r += a.nblocks * NB) {{".format(flat, threads))
-            self._chunk_remap(S, self.GL, vw, flat + "r", flat)
-            self._index_prologue(S, self.GL, ["i{}".format(d) for d in range(self.ndim)], vw, flat)
-            if self.slab is not None:
-                S.append("  const int i{0}g = i{0} + a.off;".format(self.slab[0]))
-            S.extend(fwd_pre)
-            if vw == 4:
-                for slot in range(len(stored)):
-                    S.append("  T O{}[4];".format(slot))
-
-            def point_block(fwd_, rev_, inbox_):
-                B = []
-                self._loop_open(B, vw)
-                B.extend(self._inbox_lines(inbox_))
-                B.extend(fwd_)
-                B.extend(rev_)
-                for slot, (n, name) in enumerate(stored):
-                    if vw == 4:
-                        B.append("  O{}[p] = {};".format(slot, name))
-                    elif stream:
-                        B.append("  __builtin_nontemporal_store({}, &a.cot[{}][l]);".format(name, slot))
-                    else:
-                        B.append("  a.cot[{}][l] = {};".format(slot, name))
-                for k, (o_, raw) in enumerate(zip(self.outputs, self.raw)):
-                    term = self.r(o_) if raw else "{0} * {0}".format(self.r(o_))
-                    if self.out_lens[k] is not None:
-                        term = "(inbox{} ? {} : (T)0)".format(k, term)
-                    B.append("  s_{0} = s_{0} + {1};".format(k, term))
-                if vw == 4:
-                    B.append("  }")  # p
-                return B
-
-            if interior is None:
-                S.extend(point_block(fwd, rev, ()))
-            else:
-                (fwd_i, rev_i), (_, exc, inbox_i) = interior
-                S.append("  if (__all((int)({}))) {{".format(self._interior_cond(exc)))
-                S.extend(point_block(fwd_i, rev_i, inbox_i))
-                S.append("  } else {")
-                S.extend(point_block(fwd, rev, ()))
-                S.append("  }")
-            if vw == 4:
-                for slot in range(len(stored)):
-                    vec = "(T4){{O{0}[0], O{0}[1], O{0}[2], O{0}[3]}}".format(slot)
-                    if stream:
-                        S.append("  __builtin_nontemporal_store({}, (T4*)(a.cot[{}] + l4 * 4));".format(vec, slot))
-                    else:
-                        S.append("  *(T4*)(a.cot[{}] + l4 * 4) = {};".format(slot, vec))
-            S.append("  }")
+        else:
+            self._plain_kernel(S, fwd, rev, interior, stored, stream)
         for name in pg2:
             S.append("  {0} = {0} + ({1}2{2}.x + {1}2{2}.y);".format(name, name[:2], name[2:]))
-        bsum = "block_sum" if self.fwd_threads == 256 else "block_sum_w<{}>".format(self.fwd_threads // 64)
         for k in range(nout):
-            S.append("  {{ const T s = {1}(s_{0}, sm); if (threadIdx.x == 0) a.part[{0} * a.nblocks + blockIdx.x] = s; }}".format(k, bsum))
+            S.append("  {{ const T s = block_sum(s_{0}, sm); if (threadIdx.x == 0) a.part[{0} * a.nblocks + blockIdx.x] = s; }}".format(k))
         for k, name in enumerate(self.pg_decl):
-            S.append("  {{ const T s = {}({}, sm); if (threadIdx.x == 0) a.ppart[{} * a.nblocks + blockIdx.x] = s; }}".format(bsum, name, k))
+            S.append("  {{ const T s = block_sum({}, sm); if (threadIdx.x == 0) a.ppart[{} * a.nblocks + blockIdx.x] = s; }}".format(name, k))
         S.append("}")
-        # final reduction in two deterministic stages: k_final sums SEG segments of every row of
-        # partials (one workgroup each), k_loss combines them in order: out = [loss, terms..., norms...]
-        # and the parameter gradients
+        self._final_kernels(S, nout)
+        # ---- gathers -------------------------------------------------------------------------------------------
+        if mgather is not None:
+            self._march_gather_kernels(S, mgather)
+        self.gathers_done = mgather is not None
+        self._standard_gathers(S)
+        if self.want_jac:
+            self._jacobian_kernel(S)
+        self._launchers(S, nout, HEAD)
+        return "\n".join(HEAD + S) + "\n"
+
+    def _plain_kernel(self, S, fwd, rev, interior, stored, stream):
+        """Body of the plain forward kernel: a grid-stride loop over the points (or packs of four), the forward and reverse
+        lines of a point as they are or, where `interior` has them, behind the wave-uniform test for its folded copy."""
+        vw = self.vw
+        flat = "l4" if vw == 4 else "l"
+        S.append(self._block_index(self.GL, vw))
+        S.append("  for (int {0}r = bx_ * NB + threadIdx.x; {0}r < {1}; {0}r += a.nblocks * NB) {{".format(flat, self.total // vw))
+        self._chunk_remap(S, self.GL, vw, flat + "r", flat)
+        self._index_prologue(S, self.GL, ["i{}".format(d) for d in range(self.ndim)], vw, flat)
+        if self.slab is not None:
+            S.append("  const int i{0}g = i{0} + a.off;".format(self.slab[0]))
+        S.extend(self.pre + self._group_arrays())
+        if vw == 4:
+            for slot in range(len(stored)):
+                S.append("  T O{}[4];".format(slot))
+
+        def point_block(fwd_, rev_, inbox_):
+            B = []
+            self._loop_open(B, vw)
+            B.extend(self._inbox_lines(inbox_))
+            B.extend(fwd_)
+            B.extend(rev_)
+            for slot, (n, name) in enumerate(stored):
+                if vw == 4:
+                    B.append("  O{}[p] = {};".format(slot, name))
+                elif stream:
+                    B.append("  __builtin_nontemporal_store({}, &a.cot[{}][l]);".format(name, slot))
+                else:
+                    B.append("  a.cot[{}][l] = {};".format(slot, name))
+            for k, (o_, raw) in enumerate(zip(self.outputs, self.raw)):
+                term = self.r(o_) if raw else "{0} * {0}".format(self.r(o_))
+                if self.out_lens[k] is not None:
+                    term = "(inbox{} ? {} : (T)0)".format(k, term)
+                B.append("  s_{0} = s_{0} + {1};".format(k, term))
+            if vw == 4:
+                B.append("  }")  # p
+            return B
+
+        if interior is None:
+            S.extend(point_block(fwd, rev, ()))
+        else:
+            (fwd_i, rev_i), (_, exc, inbox_i) = interior
+            S.append("  if (__all((int)({}))) {{".format(self._interior_cond(exc)))
+            S.extend(point_block(fwd_i, rev_i, inbox_i))
+            S.append("  } else {")
+            S.extend(point_block(fwd, rev, ()))
+            S.append("  }")
+        if vw == 4:
+            for slot in range(len(stored)):
+                vec = "(T4){{O{0}[0], O{0}[1], O{0}[2], O{0}[3]}}".format(slot)
+                if stream:
+                    S.append("  __builtin_nontemporal_store({}, (T4*)(a.cot[{}] + l4 * 4));".format(vec, slot))
+                else:
+                    S.append("  *(T4*)(a.cot[{}] + l4 * 4) = {};".format(slot, vec))
+        S.append("  }")
+
+    def _final_kernels(self, S, nout):
+        """The final reduction in two deterministic stages: k_final sums SEG segments of every row of partials (one
+        workgroup each), k_loss combines them in order: out = [loss, terms..., norms...] and the parameter gradients."""
         nrows = nout + len(self.pg_decl)
         S.append("#define SEG 16")
         S.append('extern "C" __global__ __launch_bounds__(NB) void k_final(const Args a) {')
@@ -1671,149 +1705,6 @@ class _Codegen:
         S.append("  for (int k = 0; k < {}; ++k) loss = loss + a.out[1 + k];".format(nout))
         S.append("  a.out[0] = loss;")
         S.append("}")
-        # ---- gathers -------------------------------------------------------------------------------------------
-        if mgather is not None:
-            self._march_gather_kernels(S, mgather)
-        self.gathers_done = mgather is not None
-        self._standard_gathers(S)
-        if self.want_jac:
-            self._jacobian_kernel(S)
-        self._launchers(S, nout, HEAD)
-        return "\n".join(HEAD + S) + "\n"
-
-    def _jacobian_kernel(self, S):
-        """`k_jac`: what `Problem.eval_operator_grad` returns (reference core.py:1313-1361, the input of `linearize`,
-        core.py:1113-1217) as ONE pointwise kernel -- the value of every output and d output / d read for every distinct
-        read (key, shift, loc), i.e. the per-shift coefficient arrays of the Jacobian -- from the SYMBOLIC derivative of the
-        traced DAG (stencil_grad.GradBuilder with the unit seed), instead of one autograd pass per output over a graph
-        of torch elementwise kernels.  Operators whose outputs are windows of the grid, or that differentiate through
-        parameter arrays (dense Jacobian columns), keep the autograd route (TraceUnsupported).  Slab mode: the rank's owned
-        cells only, u read from the ghost-extended array and the wrap planes, one owned-shape array per item
-        (slab_traced.HipSlabKernels.jacobian)."""
-        tr = self.tr
-        items, self.jac_items = [], []  # jac_items[j] = (output position, None for its value | the read's attr)
-        for k, o in enumerate(self.outputs):
-            if o.win is not None or tuple(o.shape) != self.G or self.raw[k]:
-                raise TraceUnsupported("Jacobian kernel: output {} is not a plain residual on the whole grid".format(k))
-            nodes = stencil_grad.subdag(o)
-            if not stencil_grad.differentiable(nodes, self.need):
-                raise TraceUnsupported("Jacobian kernel: parameters below output {} (dense columns)".format(k))
-            gb = stencil_grad.GradBuilder(tr, self.G, self.need, stop=())
-            items.append(("@jv{}".format(k), gb.real(o)))
-            self.jac_items.append((k, None))
-            adj = gb.adjoints(o, gb.const(1.0), nodes) if self.need.get(o.idx, False) else dict()
-            for ridx in sorted(adj):
-                expr = adj[ridx]
-                if expr is None:
-                    continue
-                items.append(("@jd{}_{}".format(k, ridx), expr))
-                self.jac_items.append((k, tuple(tr.nodes[ridx].attr)))
-        if len(items) > 96:
-            raise TraceUnsupported("Jacobian kernel: {} arrays".format(len(items)))
-        saved = dict(self.gather_reads_sources)
-        S.append("struct JacP {{ T* p[{}]; }};".format(len(items)))
-        self.jac_blocks = self._gather_kernel(S, "k_jac", items, "const JacP jp, const AdamP ad", lambda k: "jp.p[{}]".format(k),
-                                              lambda k: "ad", owned=self.slab is not None)
-        self.gather_reads_sources = saved  # (bookkeeping of the optimizer fusion: the Jacobian kernel is not a gather)
-
-    def _standard_gathers(self, S):
-        if self.gathers_done:
-            return
-        self.gathers = []  # keys of the fields that need a gather launch
-        self.gather_reads_sources = dict()  # key -> the gather reads the fields' own arrays (not only stored adjoints)
-        self.direct = dict()  # key -> cot slot that already IS the gradient
-        by_key = dict()  # key -> [(slot, read attr, coefficient expression or None)]
-        for slot, n in enumerate(self.cots):
-            by_key.setdefault(n.attr[0], []).append((slot, n.attr, None))
-        for k, n in enumerate(self.cut_nodes):
-            for ridx, coeff in self.cut_set[n.idx].items():
-                attr = self.tr.nodes[ridx].attr
-                by_key.setdefault(attr[0], []).append((len(self.cots) + k, attr, coeff))
-        symbolic = dict()
-        if self.all_regular:
-            symbolic = self._gradient_terms()
-        self.gather_blocks = dict()
-        keys = list(by_key) + [k for k in symbolic if k not in by_key]
-        for key in keys:
-            reads = by_key.get(key, [])
-            floc = self.state.fields[key].loc
-            fshape = self._field_shape(key)
-            only_legacy = all(adj is None or not any(self.tr.nodes[r].attr[0] == key for r in adj) for adj in self.out_adj)
-            if (self.slab is None and only_legacy and len(reads) == 1 and reads[0][2] is None and not any(reads[0][1][1])
-                    and reads[0][1][2] == floc):
-                self.direct[key] = reads[0][0]
-                continue
-            gi = len(self.gathers)
-            self.gathers.append(key)
-            regular = tuple(fshape) == self.G and all(attr[2] == floc for _, attr, _ in reads)
-            if key in symbolic and regular and symbolic[key] is not None:
-                self._gather_symbolic(S, gi, key, symbolic[key])
-                continue
-            if self.slab is not None:
-                self._gather_slab(S, gi, key, reads, floc, fshape)
-                continue
-            tot = int(np.prod(fshape))
-            self.gather_blocks[gi] = (tot + 255) // 256
-            S.append('extern "C" __global__ __launch_bounds__(NB) void k_gat_{}(const Args a, T* __restrict__ g, const AdamP ad) {{'.format(gi))
-            S.append("  const int l = blockIdx.x * NB + threadIdx.x;")
-            S.append("  if (l >= {}) return;".format(tot))
-            rem = "l"
-            for d in reversed(range(self.ndim)):
-                if d == 0:
-                    S.append("  const int j0 = {};".format(rem))
-                else:
-                    S.append("  const int j{} = {} % {};".format(d, rem, fshape[d]))
-                    S.append("  const int q{} = {} / {};".format(d, rem, fshape[d]))
-                    rem = "q{}".format(d)
-            S.append("  T acc = (T)0;")
-            for entry, (slot, attr, coeff) in enumerate(reads):
-                _, shift, loc, _ = attr
-                idx, valid = [], []
-                for d in range(self.ndim):
-                    ns, nr = fshape[d], self.G[d]
-                    ext = max(ns, nr)
-                    s_ = shift[d] % ext
-                    if s_ > ext // 2:
-                        s_ -= ext
-                    pos = "j{}".format(d) if not (floc[d] == "c" and loc[d] == "n") else "(j{} + 1)".format(d)
-                    e = pos if s_ == 0 else "wrap({} - ({}), {})".format(pos, s_, ext)
-                    if floc[d] == "n" and loc[d] == "c":  # trimmed: the last padded position was dropped
-                        name = "t{}_{}".format(entry, d)
-                        S.append("  const int {} = {};".format(name, e))
-                        valid.append("{} < {}".format(name, nr))
-                        e = name
-                    idx.append(e)
-                load = "a.cot[{}][{}]".format(slot, self._offset(idx, self.G))
-                if coeff is not None:  # a cut array: the stored adjoint times d(node) / d(read)
-                    load = "({}) * {}".format(coeff, load)
-                if valid:
-                    load = "(({}) ? {} : (T)0)".format(" && ".join(valid), load)
-                S.append("  acc = acc + {};".format(load))
-            S.append("  g[l] = acc;")
-            S.append("  adam_apply(ad, l, acc);")
-            S.append("}")
-        # every symbolic gather in ONE launch: the fields' expressions share most of what they read (stored seeds, each
-        # other's arrays), a merged pass reads it once (tracer with three space dimensions: 52 -> 36 words per point)
-        self.merged = []
-        sym_keys = [key for key in self.gathers if key in symbolic and symbolic[key] is not None
-                    and tuple(self._field_shape(key)) == self.G
-                    and all(attr[2] == self.state.fields[key].loc for _, attr, _ in by_key.get(key, []))]
-        if len(sym_keys) >= 2:
-            self.merged = sym_keys
-            nk = len(sym_keys)
-            S.append("struct GatAll {{ T* g[{0}]; AdamP ad[{0}]; }};".format(nk))
-            nblocks_all = self._gather_kernel(S, "k_gat_all", [(key, symbolic[key]) for key in sym_keys], "const GatAll ga",
-                                              lambda k: "ga.g[{}]".format(k), lambda k: "ga.ad[{}]".format(k))
-            S.append('extern "C" int jit_gather_all(const Args* a, void* const* g, void* const* x, void* const* m, void* const* v,')
-            S.append('                               double alpha, double omb1, double omb2, double eps, const void* alpha_dev, void* stream) {')
-            S.append("  GatAll ga;")
-            S.append("  for (int k = 0; k < {}; ++k) {{".format(nk))
-            S.append("    ga.g[k] = (T*)g[k];")
-            S.append("    ga.ad[k] = AdamP{(T*)x[k], (T*)m[k], (T*)v[k], (T)alpha, (T)omb1, (T)omb2, (T)eps, (const T*)alpha_dev};")
-            S.append("  }")
-            S.append("  hipLaunchKernelGGL(k_gat_all, dim3({}), dim3(NB), 0, (hipStream_t)stream, *a, ga);".format(nblocks_all))
-            S.append("  return (int)hipGetLastError();")
-            S.append("}")
 
     def _launchers(self, S, nout, HEAD):
         # outputs in parameter space as one generated kernel (param_expr.py), when their tape has an elementwise form
@@ -1891,766 +1782,3 @@ class _Codegen:
         """The members of `struct ParArgs` (param_expr.emit): values and gradients of the arrays `par_index`, the terms."""
         K = max(1, len(self.par_index))
         return [Member("const T*", "val", K, _PTR), Member("T*", "grad", K, _PTR), Member("T*", "pout", None, _PTR)]
-
-    # ---- network evaluations shared by MARCHING (float kernels with a pointwise network at the faces) ---------------------
-    def _march_parts(self):
-        """Line groups of the marching forward kernel (see _march_kernel): per variant (general / interior) the forward
-        lines before and after the shared network values, and the reverse pass."""
-        a1, a2 = self.ndim - 2, self.ndim - 1
-        self.wregs = "const"
-        by_axis = {axis: (A, B) for A, B, axis in self.share}
-        (Ax, Bx), (Ay, By) = by_axis[a1], by_axis[a2]
-        shared = {x.idx for x in (Ax, Bx, Ay, By)}
-        late = set()
-        for n in self.order:
-            if (n.op == "mlp_out" and n.args[0].idx in shared) or any(a.idx in late for a in n.args):
-                late.add(n.idx)
-        early = {n.idx for n in self.order} - late
-        attr = Bx.attr
-        nlast = len(attr[2]) - 1
-        nz, nin = attr[2][nlast], len(Bx.args)
-        parts = dict(Ax=Ax, Bx=Bx, Ay=Ay, By=By, nz=nz, nin=nin, attr=attr, variants=[])
-        plan = self._fold_plan(self.order, 1, windows=True)
-        # a third copy for the strips that touch a wall of the LANE axis (2 of 9 at 512 columns): predicates of the other
-        # axes folded, those of the lane axis kept
-        plan_w = self._fold_plan(self.order, 4, windows=True) if plan is not None else None
-        if plan_w is not None and (plan_w[0] == plan[0] or a2 not in plan[1]):
-            plan_w = None  # (no predicate of the lane axis: the interior copy serves every strip)
-        parts["plan"], parts["plan_w"] = plan, plan_w
-        keep = ("cots", "cut_nodes", "jac_store", "pg_decl", "pg_offset", "pgrads", "pg2_used")
-        first = None
-        self.march_pref = dict()
-        for fold in ([None] if plan is None else ([None, plan[0]] + ([plan_w[0]] if plan_w is not None else []))):
-            self.fold, self.lines, self.loads = fold, [], dict()
-            self.march_live, self.march_used = (None if fold is None else self._live_under(fold)), set()
-            self.cots, self.cut_nodes, self.jac_store, self.pg_decl, self.pg_offset, self.pg2_used = [], [], [], [], dict(), set()
-            self.forward(only=early)
-            fwd1, self.lines = self.lines, []
-            xin = [(self.r(Bx.args[k]), self.r(By.args[k]), self.r(Ay.args[k])) for k in range(nin)]
-            self.forward(only=late)
-            fwd2, self.lines = self.lines, []
-            self.reverse()
-            rev, self.lines = self.lines, []
-            rev_text = "\n".join(rev)
-
-            def adjoint_of(call, j):
-                out = self.mlp_out_seen.get(call.idx, dict()).get(j)
-                return "g{}".format(out.idx) if out is not None and "T g{} ".format(out.idx) in rev_text else "(T)0"
-
-            adj = {name: [adjoint_of(call, j) for j in range(nz)] for name, call in (("ax", Ax), ("bx", Bx), ("ay", Ay), ("by", By))}
-            state = {k: getattr(self, k) for k in keep}
-            if first is None:
-                first = state
-            elif ([n.idx for n in state["cots"]] != [n.idx for n in first["cots"]] or state["pg_decl"] != first["pg_decl"]
-                  or [n.idx for n in state["cut_nodes"]] != [n.idx for n in first["cut_nodes"]]):
-                raise RuntimeError("interior copy of the traced kernel stores other adjoints than the general one")
-            parts["variants"].append(dict(fwd1=fwd1, fwd2=fwd2, rev=rev, xin=xin, adj=adj, used=set(self.march_used)))
-        self.fold, self.march_live = None, None
-        parts["pref"] = sorted(self.march_pref.values()) if self.march_pref else []
-        self.march_pref = None
-        for k, v in first.items():
-            setattr(self, k, v)
-        parts["gather"] = self._march_gather_plan()
-        # the pre-step of a row segment: the inputs of the LOWER face along the marching axis at the segment's first row
-        saved = (self.order, self.loads, self.pre, self.groups)
-        seen = dict()
-        for arg in Ax.args:
-            for n in stencil_grad.subdag(arg):
-                seen[n.idx] = n
-        self.order = [seen[i] for i in sorted(seen)]
-        self.loads, self.pre, self.groups, self.lines = dict(), [], dict(), []
-        self.forward()
-        parts["pre_lines"], parts["pre_in"] = self.lines, [self.r(arg) for arg in Ax.args]
-        seen = dict()
-        for arg in Ay.args:
-            for n in stencil_grad.subdag(arg):
-                seen[n.idx] = n
-        self.order = [seen[i] for i in sorted(seen)]
-        self.loads, self.pre, self.groups, self.lines = dict(), [], dict(), []
-        self.forward()
-        parts["pre_lines_y"], parts["pre_in_y"] = self.lines, [self.r(arg) for arg in Ay.args]
-        self.order, self.loads, self.pre, self.groups = saved
-        # the packed evaluation (prefix mu) and the reverse pass of the PREVIOUS step's evaluation (prefix mp)
-        self.lines = []
-        self._mlp_forward("mu", 2, attr, [("ux{}_0".format(k), "ux{}_1".format(k)) for k in range(nin)])
-        parts["mlp_fwd"], self.lines = self.lines, []
-        self._mlp_backward("mp", 2, attr, [("ud{}_0".format(j), "ud{}_1".format(j)) for j in range(nz)], False)
-        parts["mlp_bwd"], self.lines = self.lines, []
-        self._mlp_backward("mu", 2, attr, [("ud{}_0".format(j), "ud{}_1".format(j)) for j in range(nz)], False)
-        parts["mlp_bwd_mu"], self.lines = self.lines, []
-        layers = attr[2]
-        parts["acts"] = ["h{}_{}".format(l, i) for l in range(nlast) for i in range(layers[l])]  # what the reverse pass reads
-        return parts
-
-    def _march_gather_plan(self):
-        """The cotangents of the reads of a marching kernel summed IN the kernel over the marching axis (a three-row delay
-        line in registers) and over the lane axis (lane shifts) before they are stored: one array per (field, shift on the
-        leading axes) instead of one per stencil read -- heat with two space dimensions: 2 instead of 10 (32 bytes per
-        point less written by k_fwd and read again by the gather).  What crosses a segment of rows or a strip of columns
-        goes to small EDGE arrays which the final gather adds.  None when the reads do not have that shape."""
-        if self.cut_nodes or self.jac_store or not self.cots:
-            return None
-        a1, a2 = self.ndim - 2, self.ndim - 1
-        groups = dict()
-        for slot, n in enumerate(self.cots):
-            key, shift, loc, _ = n.attr
-            if not self._regular(n):
-                return None
-            cs = []
-            for d, sh in enumerate(shift):
-                ext = self.G[d]
-                v = sh % ext
-                cs.append(v - ext if v > ext // 2 else v)
-            sx, sy = cs[a1], cs[a2]
-            if abs(sx) > 1 or abs(sy) > 1 or (sx and sy):
-                return None
-            groups.setdefault((key, tuple(cs[:a1])), []).append((slot, sx, sy))
-        if any(adj is not None for adj in self.out_adj):
-            return None
-        return dict(groups=list(groups.items()))
-
-    def _march_gather_geometry(self):
-        a1, a2 = self.ndim - 2, self.ndim - 1
-        G1, G2 = self.G[a1], self.G[a2]
-        R = max(1, min(int(os.environ.get("ODIL_TRACE_MARCH_ROWS", 64)), G1, 64))  # (<= 64: one lane of the pre-step per row)
-        nseg, nstrip = (G1 + R - 1) // R, (G2 + 63) // 64
-        lead = int(np.prod(self.G[:a1])) if a1 > 0 else 1
-        return R, nseg, nstrip, lead
-
-    def _march_edge_offsets(self, ngroups):
-        """Element offsets into a.edge of the four edge arrays of every group: E_lo, E_hi [lead, nseg, G2] (rows that
-        cross a segment), F_lo, F_hi [lead, G1, nstrip] (columns that cross a strip); total size."""
-        a1, a2 = self.ndim - 2, self.ndim - 1
-        R, nseg, nstrip, lead = self._march_gather_geometry()
-        esz, fsz = lead * nseg * self.G[a2], lead * self.G[a1] * nstrip
-        offs, o = [], 0
-        for _ in range(ngroups):
-            offs.append((o, o + esz, o + 2 * esz, o + 2 * esz + fsz))
-            o += 2 * esz + 2 * fsz
-        return offs, o
-
-    def _march_gather_kernels(self, S, plan):
-        """The final gathers of a marching kernel with the in-kernel partial sums (_march_gather_plan): per field
-        g[j] = sum over its groups of (P + edge terms)[j - leading shift], four points of the last axis per thread."""
-        a1, a2 = self.ndim - 2, self.ndim - 1
-        G1, G2 = self.G[a1], self.G[a2]
-        R, nseg, nstrip, lead = self._march_gather_geometry()
-        groups = plan["groups"]
-        offs, _ = self._march_edge_offsets(len(groups))
-        vw = 4 if G2 % 4 == 0 else 1
-        keys = []
-        for (key, _), _ in groups:
-            if key not in keys:
-                keys.append(key)
-        self.gathers, self.direct, self.merged, self.gather_blocks = list(keys), dict(), [], dict()
-        self.gather_reads_sources = {key: [] for key in keys}
-        for gi, key in enumerate(keys):
-            threads = self.total // vw
-            self.gather_blocks[gi] = (threads + 255) // 256
-            S.append('extern "C" __global__ __launch_bounds__(NB) void k_gat_{}(const Args a, T* __restrict__ g, const AdamP ad) {{'.format(gi))
-            S.append("  const int lr = blockIdx.x * NB + threadIdx.x;")
-            S.append("  if (lr >= {}) return;".format(threads))
-            names = ["i{}".format(d) for d in range(self.ndim)]
-            self._index_prologue(S, self.G, names, vw, "lr")
-            if vw == 1:
-                S.append("  const int ib = i{};".format(a2))
-            S.append("  T acc[{}];".format(vw))
-            S.append("  for (int p = 0; p < {}; ++p) acc[p] = (T)0;".format(vw))
-            S.append("  const int seg = i{} / {};".format(a1, R))
-            for k, ((gkey, lshift), _) in enumerate(groups):
-                if gkey != key:
-                    continue
-                e_lo, e_hi, f_lo, f_hi = offs[k]
-                S.append("  {")
-                # the point this group's sums were formed at: j - leading shift (periodic)
-                lidx = []
-                for d in range(a1):
-                    lidx.append("i{}".format(d) if lshift[d] == 0 else "wrap(i{} - ({}), {})".format(d, lshift[d], self.G[d]))
-                lflat = self._offset(lidx, self.G[:a1]) if a1 > 0 else "0"
-                S.append("  const int lf = {};".format(lflat))
-                S.append("  const T* const P = a.cot[{}] + ((long)lf * {} + i{}) * {};".format(k, G1, a1, G2))
-                if vw == 4:
-                    S.append("  { const T4 q = *(const T4*)(P + ib); acc[0] += q.x; acc[1] += q.y; acc[2] += q.z; acc[3] += q.w; }")
-                else:
-                    S.append("  acc[0] += P[ib];")
-                # rows that received a contribution from the neighbouring segment
-                S.append("  if (i{0} % {1} == {1} - 1 || i{0} == {2}) {{".format(a1, R, G1 - 1))
-                S.append("    const T* const E = a.edge + {} + ((long)lf * {} + (seg + 1 == {} ? 0 : seg + 1)) * {};".format(e_lo, nseg, nseg, G2))
-                S.append("    for (int p = 0; p < {}; ++p) acc[p] += E[ib + p];".format(vw))
-                S.append("  }")
-                S.append("  if (i{} % {} == 0) {{".format(a1, R))
-                S.append("    const T* const E = a.edge + {} + ((long)lf * {} + (seg == 0 ? {} : seg - 1)) * {};".format(e_hi, nseg, nseg - 1, G2))
-                S.append("    for (int p = 0; p < {}; ++p) acc[p] += E[ib + p];".format(vw))
-                S.append("  }")
-                # columns that received a contribution from the neighbouring strip
-                S.append("  for (int p = 0; p < {}; ++p) {{".format(vw))
-                S.append("    const int c = ib + p, st = c / 64;")
-                S.append("    const T* const F = a.edge + ((long)lf * {} + i{}) * {};".format(G1, a1, nstrip))
-                S.append("    if (c % 64 == 63 || c == {}) acc[p] += F[{} + (st + 1 == {} ? 0 : st + 1)];".format(G2 - 1, f_lo, nstrip))
-                S.append("    if (c % 64 == 0) acc[p] += F[{} + (st == 0 ? {} : st - 1)];".format(f_hi, nstrip - 1))
-                S.append("  }")
-                S.append("  }")
-            o = "lr * 4" if vw == 4 else "lr"
-            if vw == 4:
-                if self.nt_streams:
-                    S.append("  __builtin_nontemporal_store((T4){{acc[0], acc[1], acc[2], acc[3]}}, (T4*)(g + {}));".format(o))
-                else:
-                    S.append("  *(T4*)(g + {}) = (T4){{acc[0], acc[1], acc[2], acc[3]}};".format(o))
-                S.append("  adam_apply4(ad, {}, acc);".format(o))
-            else:
-                S.append("  g[{}] = acc[0];".format(o))
-                S.append("  adam_apply(ad, {}, acc[0]);".format(o))
-            S.append("}")
-
-    def _march_kernel(self, S, parts, stored, stream):
-        """Body of the MARCHING forward kernel of an operator that evaluates one pointwise network at the faces of every
-        cell (heat with two space dimensions: reference examples/heat/heat.py:86-98 per axis).  The lower face of cell i is
-        the upper face of cell i - e (stencil_share.py proves it on the DAG), so half of the evaluations of the plain
-        kernel -- and of their reverse passes, two thirds of its instructions -- are repeats.  Here a WAVE owns a strip of
-        64 columns of the last axis and marches along the second-to-last axis over a segment of rows; every lane makes ONE
-        packed evaluation per point: (upper face along the marching axis, upper face along the lane axis).
-
-        * marching axis: the value of a point's upper face is carried in registers to the next row, where it is the lower
-          face; the adjoint it collects there is added to its own before the reverse pass of the evaluation, which
-          therefore runs ONE STEP LATE, from the previous step's activations (carried as well);
-        * lane axis: lane L takes its lower face from lane L - 1 and returns the adjoint to it by wave-wide lane shifts
-          (DPP: no LDS, no barrier);
-        * a segment starts with a PRE-STEP whose packed evaluation holds the lower faces nobody hands over: slot 0 the
-          marching axis' at the segment's first row (every lane its column), slot 1 the lane axis' at the strip's FIRST
-          column -- lane j for row r0 + j (a segment has at most 64 rows).  Lane 0 fetches its row's value with
-          v_readlane as the march goes and hands the adjoint back the same way; after the march a post-step repeats the
-          pre-step's forward pass from the kept inputs and runs its reverse pass with the collected adjoints.  (Until
-          this form a HELPER lane per wave evaluated the first column's lower face every step: 63 columns per wave,
-          nine waves per row of 512 where eight suffice.)
-
-        Values and adjoints of lanes without a point are masked; sums of network-parameter gradients are linear in the
-        adjoints, so a face shared by two waves (or two segments) simply contributes from both sides.  The body exists
-        twice: as traced, and with every index predicate folded to its interior value (_fold_plan); the branch is scalar
-        (row index, strip and leading indices are wave-uniform)."""
-        a1, a2 = self.ndim - 2, self.ndim - 1
-        G1, G2 = self.G[a1], self.G[a2]
-        R, nseg, nstrip, lead = self._march_gather_geometry()
-        nitems = lead * nseg * nstrip
-        nz, nin, attr = parts["nz"], parts["nin"], parts["attr"]
-        nl = len(attr[2]) - 1
-        Ax, Bx, Ay, By = parts["Ax"], parts["Bx"], parts["Ay"], parts["By"]
-        acts = parts["acts"]
-        S.append("  const int lane = threadIdx.x & 63;")
-        S.append("  const int wave_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);")
-        S.append("  for (int item = blockIdx.x * 4 + wave_; item < {}; item += a.nblocks * 4) {{".format(nitems))
-        S.append("  const int strip = item % {}, seg = (item / {}) % {};".format(nstrip, nstrip, nseg))
-        rem = "(item / {})".format(nstrip * nseg)
-        for d in reversed(range(a1)):
-            if d == 0:
-                S.append("  const int i0 = {};".format(rem))
-            else:
-                S.append("  const int i{} = {} % {};".format(d, rem, self.G[d]))
-                S.append("  const int q{}_ = {} / {};".format(d, rem, self.G[d]))
-                rem = "q{}_".format(d)
-        S.append("  const int r0 = seg * {0}, r1 = min(r0 + {0}, {1});".format(R, G1))
-        S.append("  const int p2 = strip * 64 + lane;")
-        S.append("  const bool valid = p2 < {};".format(G2))
-        S.append("  const int i{} = min(p2, {});".format(a2, G2 - 1))
-        # interior test, scalar: leading indices, strip range; the row is tested per step
-        plan, plan_w = parts["plan"], parts.get("plan_w")
-        outer, rowc, leadc = [], [], []
-        if plan is not None:
-            _, exc, _ = plan
-            for d, values in sorted(exc.items()):
-                if d < a1:
-                    outer.append(self._interior_cond({d: values}))
-                    leadc.append(outer[-1])
-                elif d == a1:
-                    rowc.append(self._interior_cond({d: values}))
-                else:  # no exceptional column among the strip's: [s0, s0 + 63]
-                    values, lo, hi = list(values), 0, G2 - 1
-                    while values and values[0] == lo:
-                        values.pop(0)
-                        lo += 1
-                    while values and values[-1] == hi:
-                        values.pop()
-                        hi -= 1
-                    if lo > 0:
-                        outer.append("strip * 64 >= {}".format(lo))
-                    if hi < G2 - 1:
-                        outer.append("strip * 64 + 63 <= {}".format(hi))
-                    outer.extend("!(strip * 64 <= {0} && {0} <= strip * 64 + 63)".format(e) for e in values)
-            S.append("  const bool interior_ = {};".format(" && ".join(outer) or "true"))
-            S.append("  const bool lead_ok_ = {};".format(" && ".join(leadc) or "true"))  # (the wall-strip copy's condition)
-        # carried state
-        mg = parts["gather"]
-        if mg is not None:
-            for k in range(len(mg["groups"])):
-                S.append("  T ap{0} = (T)0, ac{0} = (T)0;".format(k))  # sums of rows r - 1 and r so far
-        for j in range(nz):
-            S.append("  T kx{0} = (T)0, gbx{0} = (T)0, gy{0} = (T)0;".format(j))
-        for name in acts:
-            S.append("  T2 mp_{0} = (T2)(0.0f);".format(name))
-        # ---- pre-step: the LOWER faces the march cannot take from a neighbour -- slot 0: along the marching axis at row r0,
-        # own column; slot 1: along the lane axis at the strip's FIRST column, lane j for row r0 + j (the strip's lane 0
-        # fetches them with v_readlane as the march goes; its adjoints come back the same way and are passed through the
-        # network's reverse pass after the march, from a second forward pass over the kept inputs)
-        for k in range(nin):
-            S.append("  T axin{0}, ayin{0};".format(k))
-        S.append("  {")
-        S.append("  const int i{} = r0;".format(a1))
-        S.extend(parts["pre_lines"])
-        for k in range(nin):
-            S.append("  axin{} = {};".format(k, parts["pre_in"][k]))
-        S.append("  }")
-        S.append("  {")
-        S.append("  const int i{} = min(r0 + lane, r1 - 1);".format(a1))
-        S.append("  const int i{} = min(strip * 64, {});".format(a2, G2 - 1))
-        S.extend(parts["pre_lines_y"])
-        for k in range(nin):
-            S.append("  ayin{} = {};".format(k, parts["pre_in_y"][k]))
-        S.append("  }")
-        for j in range(nz):
-            S.append("  T kay{0}, gedge{0} = (T)0;".format(j))
-        S.append("  {")
-        for k in range(nin):
-            S.append("  const T ux{0}_0 = axin{0}, ux{0}_1 = ayin{0};".format(k))
-        S.extend(parts["mlp_fwd"])
-        for j in range(nz):
-            S.append("  kx{0} = mu_z{1}_{0}.x; kay{0} = mu_z{1}_{0}.y;".format(j, nl))
-        for name in acts:
-            S.append("  mp_{0} = mu_{0};".format(name))
-        S.append("  }")
-        # ---- the march ----------------------------------------------------------------------------------------------
-        # the field values a step reads are requested during the step before (the step's arithmetic covers their
-        # latency: two resident waves per SIMD cannot)
-        pref = parts["pref"]
-        if pref:
-            S.append("  T {};".format(", ".join("ldn_{}".format(k) for k, _ in pref)))
-            S.append("  {{ const int i{} = r0;".format(a1))
-            for k, e in pref:
-                S.append("    ldn_{} = {};".format(k, e))
-            S.append("  }")
-        S.append("  for (int i{0} = r0; i{0} < r1; ++i{0}) {{".format(a1))
-        S.append("  const int l = {};".format(self._offset(["i{}".format(d) for d in range(self.ndim)], self.G)))
-        if pref:
-            for k, _ in pref:
-                S.append("  const T ld_{0} = ldn_{0};".format(k))
-            S.append("  {{ const int inext_ = min(i{0} + 1, r1 - 1); {{ const int i{0} = inext_;".format(a1))
-            vs = parts["variants"]
-            row = " && ".join(rowc) or "true"
-            always = vs[1]["used"] if len(vs) > 1 else {k for k, _ in pref}
-            wall = (vs[2]["used"] | always) if len(vs) > 2 else None
-            for k, e in pref:
-                if k in always:
-                    S.append("    ldn_{} = {};".format(k, e))
-            if wall is not None and len(wall) > len(always):  # what the wall-strip copy reads beyond the interior one
-                S.append("    if (!(interior_ && {})) {{".format(row))
-                for k, e in pref:
-                    if k in wall and k not in always:
-                        S.append("      ldn_{} = {};".format(k, e))
-                S.append("    }")
-            rest = [(k, e) for k, e in pref if k not in (wall if wall is not None else always)]
-            if rest:  # what only the general copy of the body reads: when the next row takes that copy
-                S.append("    if (!({} && {})) {{".format("lead_ok_" if wall is not None else "interior_", row))
-                for k, e in rest:
-                    S.append("      ldn_{} = {};".format(k, e))
-                S.append("    }")
-            S.append("  } }")
-        for j in range(nz):
-            S.append("  T gax{0}, gbc{0}, gay{0}, gby{0}, zx{0};".format(j))
-        for name in acts:
-            S.append("  T2 mc_{};".format(name))
-        if mg is not None:
-            for k in range(len(mg["groups"])):
-                S.append("  T cm{0}, c0{0}, cp{0}, yl{0}, yr{0};".format(k))
-
-        mg = parts["gather"]
-
-        def body(var, inbox):
-            B = []
-            B.extend(self._inbox_lines(inbox))
-            B.extend(var["fwd1"])
-            for k, (bx, by, ay) in enumerate(var["xin"]):
-                B.append("  const T ux{0}_0 = {1}, ux{0}_1 = {2};".format(k, bx, by))
-            B.extend(parts["mlp_fwd"])
-            for name in acts:
-                B.append("  mc_{0} = mu_{0};".format(name))
-            for j in range(nz):
-                z = "mu_z{}_{}".format(nl, j)
-                B.append("  const T m{}_z{}_{} = kx{};".format(Ax.idx, nl, j, j))
-                B.append("  const T m{}_z{}_{} = {}.x;".format(Bx.idx, nl, j, z))
-                B.append("  const T m{}_z{}_{} = {}.y;".format(By.idx, nl, j, z))
-                # (two statements: a lane shift inside one arm of a conditional would run with lane 0 masked off, and a DPP
-                # read from a disabled lane is invalid -- lane 1 would get 0)
-                B.append("  const T ayp{0}_ = odil_lane_prev({1}.y), ay0{0}_ = odil_readlane(kay{0}, i{2} - r0);".format(j, z, a1))
-                B.append("  const T m{0}_z{1}_{2} = lane == 0 ? ay0{2}_ : ayp{2}_;".format(Ay.idx, nl, j))
-                B.append("  zx{} = {}.x;".format(j, z))
-            B.extend(var["fwd2"])
-            B.extend(var["rev"])
-            if mg is not None:
-                # partial sums of the read cotangents (_march_gather_plan): per group what this row gives to the rows
-                # r - 1, r, r + 1 (cm, c0, cp; c0 with the lane neighbours' shares) and to the neighbouring strips
-                for k, (_, members) in enumerate(mg["groups"]):
-                    gsum = lambda sel: " + ".join("g{}".format(self.cots[slot].idx) for slot, sx, sy in members if sel(sx, sy)) or None
-                    term = lambda e: "(valid ? {} : (T)0)".format(e) if e else None
-                    c0, cm, cp = gsum(lambda sx, sy: sx == 0 and sy == 0), gsum(lambda sx, sy: sx == -1), gsum(lambda sx, sy: sx == 1)
-                    yl, yr = gsum(lambda sx, sy: sy == -1), gsum(lambda sx, sy: sy == 1)  # to the column left / right
-                    B.append("  cm{} = {};".format(k, term(cm) or "(T)0"))
-                    B.append("  cp{} = {};".format(k, term(cp) or "(T)0"))
-                    B.append("  yl{} = {};".format(k, term(yl) or "(T)0"))
-                    B.append("  yr{} = {};".format(k, term(yr) or "(T)0"))
-                    B.append("  c0{} = {};".format(k, term(c0) or "(T)0"))
-            B.append("  if (valid) {")
-            for slot, (n, name) in enumerate(stored if mg is None else []):
-                if stream:
-                    B.append("    __builtin_nontemporal_store({}, &a.cot[{}][l]);".format(name, slot))
-                else:
-                    B.append("    a.cot[{}][l] = {};".format(slot, name))
-            for k, (o_, raw) in enumerate(zip(self.outputs, self.raw)):
-                term = self.r(o_) if raw else "{0} * {0}".format(self.r(o_))
-                if self.out_lens[k] is not None:
-                    term = "(inbox{} ? {} : (T)0)".format(k, term)
-                B.append("    s_{0} = s_{0} + {1};".format(k, term))
-            B.append("  }")
-            for j in range(nz):
-                B.append("  gax{0} = valid ? {1} : (T)0; gbc{0} = valid ? {2} : (T)0;".format(j, var["adj"]["ax"][j], var["adj"]["bx"][j]))
-                B.append("  gay{0} = valid ? {1} : (T)0; gby{0} = valid ? {2} : (T)0;".format(j, var["adj"]["ay"][j], var["adj"]["by"][j]))
-            return B
-
-        variants = parts["variants"]
-        if len(variants) == 1:
-            S.extend(body(variants[0], ()))
-        else:
-            S.append("  if (interior_ && {}) {{".format(" && ".join(rowc) or "true"))
-            S.extend(body(variants[1], plan[2]))
-            if len(variants) > 2:
-                S.append("  }} else if (lead_ok_ && {}) {{".format(" && ".join(rowc) or "true"))
-                S.extend(body(variants[2], plan_w[2]))
-            S.append("  } else {")
-            S.extend(body(variants[0], ()))
-            S.append("  }")
-        if mg is not None:
-            offs, _ = self._march_edge_offsets(len(mg["groups"]))
-            lead_flat = self._offset(["i{}".format(d) for d in range(a1)], self.G[:a1]) if a1 > 0 else "0"
-            S.append("  const long lf_ = {};".format(lead_flat))
-            S.append("  const int lastl_ = min(63, {} - strip * 64);".format(G2 - 1))  # the strip's last lane with a point
-            for k in range(len(mg["groups"])):
-                e_lo, e_hi, f_lo, f_hi = offs[k]
-                # the row's own sum: the lane neighbours' shares arrive by lane shifts; what leaves the strip goes to F
-                S.append("  const T fromr{0} = odil_lane_next(yl{0}), froml{0} = odil_lane_prev(yr{0});".format(k))
-                S.append("  const T row{0} = c0{0} + (valid ? froml{0} + fromr{0} : (T)0);".format(k))
-                S.append("  if (lane == 0) a.edge[{} + (lf_ * {} + i{}) * {} + strip] = yl{};".format(f_lo, G1, a1, nstrip, k))
-                S.append("  if (lane == lastl_) a.edge[{} + (lf_ * {} + i{}) * {} + strip] = yr{};".format(f_hi, G1, a1, nstrip, k))
-                # delay line along the marching axis: row r - 1 is complete (within the segment) once row r has given its share
-                S.append("  if (i{} > r0) {{ if (valid) {}; }}".format(
-                    a1, ("__builtin_nontemporal_store(ap{0} + cm{0}, &a.cot[{0}][l - {1}])" if stream else "a.cot[{0}][l - {1}] = ap{0} + cm{0}").format(k, G2)))
-                S.append("  else if (valid) a.edge[{} + (lf_ * {} + seg) * {} + i{}] = cm{};".format(e_lo, nseg, G2, a2, k))
-                S.append("  ap{0} = ac{0} + row{0}; ac{0} = cp{0};".format(k))
-        for j in range(nz):  # what lane 0 found for the strip's first lower face of this row: back to the lane that evaluated it
-            S.append("  {{ const T g0_ = odil_readlane(gay{0}, 0); gedge{0} = lane == i{1} - r0 ? g0_ : gedge{0}; }}".format(j, a1))
-        # reverse pass of the PREVIOUS step's evaluation: its own adjoints + what this row found for the carried face
-        S.append("  {")
-        for j in range(nz):
-            S.append("  const T ud{0}_0 = gbx{0} + gax{0}, ud{0}_1 = gy{0};".format(j))
-        S.extend(parts["mlp_bwd"])
-        S.append("  }")
-        for j in range(nz):
-            S.append("  kx{0} = zx{0}; gbx{0} = gbc{0}; gy{0} = gby{0} + odil_lane_next(gay{0});".format(j))
-        for name in acts:
-            S.append("  mp_{0} = mc_{0};".format(name))
-        S.append("  }")  # rows
-        if mg is not None:
-            # the segment's last row (what the next segment's first row gives it arrives through E_lo), and what the last
-            # row gives to the next segment's first row
-            offs, _ = self._march_edge_offsets(len(mg["groups"]))
-            lead_flat = self._offset(["i{}".format(d) for d in range(a1)], self.G[:a1]) if a1 > 0 else "0"
-            S.append("  if (valid) {")
-            S.append("    const long lf_ = {};".format(lead_flat))
-            last_l = self._offset(["i{}".format(d) if d != a1 else "(r1 - 1)" for d in range(self.ndim)], self.G)
-            S.append("    const int ll_ = {};".format(last_l))
-            for k in range(len(mg["groups"])):
-                e_lo, e_hi, f_lo, f_hi = offs[k]
-                S.append("    a.cot[{0}][ll_] = ap{0};".format(k))
-                S.append("    a.edge[{} + (lf_ * {} + seg) * {} + i{}] = ac{};".format(e_hi, nseg, G2, a2, k))
-            S.append("  }")
-        # flush: the last row's evaluation (its upper face along the marching axis belongs to the next segment too)
-        S.append("  {")
-        for j in range(nz):
-            S.append("  const T ud{0}_0 = gbx{0}, ud{0}_1 = gy{0};".format(j))
-        S.extend(parts["mlp_bwd"])
-        S.append("  }")
-        # post-step: the reverse pass of the pre-step's second slot (the lane axis' lower faces of the first column)
-        S.append("  {")
-        for k in range(nin):
-            S.append("  const T ux{0}_0 = axin{0}, ux{0}_1 = ayin{0};".format(k))
-        S.extend(parts["mlp_fwd"])
-        for j in range(nz):
-            S.append("  const T ud{0}_0 = (T)0, ud{0}_1 = lane < r1 - r0 ? gedge{0} : (T)0;".format(j))
-        S.append("  {")
-        S.extend(parts["mlp_bwd_mu"])
-        S.append("  }")
-        S.append("  }")
-        S.append("  }")  # items
-
-    def _gather_symbolic(self, S, gi, key, root):
-        """The gather of ONE regular field as a pointwise kernel over its gradient expression."""
-        self.gather_blocks[gi] = self._gather_kernel(S, "k_gat_{}".format(gi), [(key, root)],
-                                                     "T* __restrict__ g, const AdamP ad", lambda k: "g", lambda k: "ad")
-
-    def _gather_kernel(self, S, name, items, params, G_, AD_, owned=False):
-        """A pointwise kernel over the gradient expressions of `items` = [(field key, expression)] (one thread per
-        point, or per four points of the last axis): common sub-expressions and loads of the fields' expressions are
-        shared, every field's gradient is stored, and the optimizer's update applied, by the lane that holds it.
-        Slab mode: threads cover planes -2 .. n + 2 of the sharded axis; planes that exist in the rank's ghost-extended
-        gradient array are stored there (ghost planes: what this rank's cells contribute to the neighbour's), planes
-        beyond an end of the decomposition that a periodic read reached go to the wrap buffers (as the legacy slab
-        gather).  owned=True (slab mode, `k_jac`): threads cover the OWNED planes 0 .. n only, reads go through the same
-        ghost / wrap addressing, and every item is stored into an array of the owned shape; no optimizer update.
-        Returns the number of workgroups to launch."""
-        self.vw = self.vw_gat
-        vw, last = self.vw, self.ndim - 1
-        saved = (self.order, self.lines, self.pre, self.loads, self.groups)
-        seen = dict()
-        for _, root in items:
-            for n in stencil_grad.subdag(root):
-                seen[n.idx] = n
-        nodes = [seen[i] for i in sorted(seen)]
-        self.order = nodes
-        self._begin()
-        self.in_gather = True
-        self.forward()
-        body = self.lines
-        interior = self._interior_copy(nodes, vw)
-        self.in_gather = False
-        self.vw = self.vw_fwd
-        pre = self.pre + self._group_arrays()
-        values = [self.r(root) for _, root in items]
-        sources = sorted({n.attr[0] for n in nodes if n.op == "read" and not n.attr[0].startswith("@")})
-        for key, _ in items:
-            self.gather_reads_sources[key] = sorted(set(self.gather_reads_sources.get(key, [])) | set(sources))
-        self.order, self.lines, self.pre, self.loads, self.groups = saved
-        shape = list(self.G)
-        names = ["i{}".format(d) for d in range(self.ndim)]
-        if self.slab is not None:
-            ax, nloc = self.slab
-            shape[ax] = nloc if owned else nloc + 4
-            names[ax] = "jx"
-        threads = int(np.prod(shape)) // vw
-        if threads >= 2**31 - 1024:
-            raise TraceUnsupported("grid too large for 32-bit indexing")
-        flat = "l4" if vw == 4 else "l"
-        occ = 0
-        S.append('extern "C" __global__ __launch_bounds__(NB) {}void {}(const Args a, {}) {{'.format(
-            "__attribute__((amdgpu_waves_per_eu({0}, {0}))) ".format(occ) if occ else "", name, params))
-        S.append(self._block_index(shape, vw))
-        S.append("  const int {}r = bx_ * NB + threadIdx.x;".format(flat))
-        S.append("  if ({}r >= {}) return;".format(flat, threads))
-        self._chunk_remap(S, shape, vw, flat + "r", flat)
-        self._index_prologue(S, shape, names, vw, flat)
-        nblocks = (threads + 255) // 256
-        if self.slab is not None and owned:
-            S.append("  const int jo = jx;")
-            S.append("  const int i{}g = jo + a.off;".format(ax))
-        elif self.slab is not None:
-            S.append("  const int jo = jx - 2;")  # owned-relative position on the sharded axis
-            S.append("  const int i{}g = wrap(jo + a.off, {});".format(ax, self.G[ax]))
-        S.extend(pre)
-        for k in range(len(items)):
-            S.append("  T acc{}[{}];".format(k, vw))
-
-        def point_block(body_):
-            B = []
-            self._loop_open(B, vw)
-            B.extend(body_)
-            for k, value in enumerate(values):
-                B.append("  acc{}[{}] = {};".format(k, "p" if vw == 4 else "0", value))
-            if vw == 4:
-                B.append("  }")
-            return B
-
-        if interior is None:
-            S.extend(point_block(body))
-        else:
-            S.append("  if (__all((int)({}))) {{".format(self._interior_cond(interior[1][1])))
-            S.extend(point_block(interior[0][0]))
-            S.append("  } else {")
-            S.extend(point_block(body))
-            S.append("  }")
-        adam = "adam_apply4({ad}, {o}, acc{k});" if vw == 4 else "adam_apply({ad}, {o}, acc{k}[0]);"
-        put = "*(T4*)({dst} + {o}) = (T4){{acc{k}[0], acc{k}[1], acc{k}[2], acc{k}[3]}};" if vw == 4 else "{dst}[{o}] = acc{k}[0];"
-        if vw == 4 and self.nt_streams:  # (with the optimizer state, see adam_apply4)
-            put = "__builtin_nontemporal_store((T4){{acc{k}[0], acc{k}[1], acc{k}[2], acc{k}[3]}}, (T4*)({dst} + {o}));"
-        if self.slab is None:
-            o = "l4 * 4" if vw == 4 else "l"
-            for k in range(len(items)):
-                S.append("  " + put.format(dst=G_(k), o=o, k=k))
-                S.append("  " + adam.format(ad=AD_(k), o=o, k=k))
-            S.append("}")
-            return nblocks
-
-        def offset(along, extent):
-            full = [along if d == ax else ("ib" if (vw == 4 and d == last) else "i{}".format(d)) for d in range(self.ndim)]
-            ext = [extent if d == ax else self.G[d] for d in range(self.ndim)]
-            return self._offset(full, ext)
-
-        if owned:
-            S.append("  const int o = {};".format(offset("jo", nloc)))
-            for k in range(len(items)):
-                S.append("  " + put.format(dst=G_(k), o="o", k=k))
-            S.append("}")
-            return nblocks
-        S.append("  const int jl = jo + a.lo;")
-        # owned planes a.alo <= jo < a.ahi have their whole gradient here (no neighbour's cell reads them): the optimizer's
-        # update is applied on the spot; the planes next to an interface wait for the halo sum (slab_traced.py)
-        S.append("  if (jl >= 0 && jl < a.ea) {")
-        S.append("    const int o = {};".format(offset("jl", "a.ea")))
-        for k in range(len(items)):
-            S.append("    " + put.format(dst=G_(k), o="o", k=k))
-            S.append("    if (jo >= a.alo && jo < a.ahi) " + adam.format(ad=AD_(k), o="o", k=k))
-        S.append("  }")
-        S.append("  else if (jo < 0 && jo >= -a.hw) {")
-        S.append("    const int o = {};".format(offset("(jo + a.hw)", "a.hw")))
-        for k, (key, _) in enumerate(items):
-            S.append("    " + put.format(dst="a.gwlo[{}]".format(self.src_keys.index(key)), o="o", k=k))
-        S.append("  }")
-        S.append("  else if (jo >= {0} && jo < {0} + a.hw) {{".format(nloc))
-        S.append("    const int o = {};".format(offset("(jo - {})".format(nloc), "a.hw")))
-        for k, (key, _) in enumerate(items):
-            S.append("    " + put.format(dst="a.gwhi[{}]".format(self.src_keys.index(key)), o="o", k=k))
-        S.append("  }")
-        S.append("}")
-        return nblocks
-
-
-def _gather_slab(self, S, gi, key, reads, floc, fshape):
-    """Gather of one field on one rank's slab.  Threads cover planes -2 .. n + 2 of the sharded axis (owned
-    cells 0 .. n): g = sum_r cot_r[j - shift_r] over the OWNED cells that read j.  Planes that exist in the
-    rank's ghost-extended gradient array are stored there (ghost planes: the part of the neighbour's gradient
-    that this rank's cells produce, sent over and added by slab_traced.py); planes beyond a side WITHOUT ghosts
-    (the ends of the decomposition) that a periodic read reached go to the wrap buffers gwlo / gwhi."""
-    ax, nloc = self.slab
-    slot = self.src_keys.index(key)
-    per = [fshape[d] for d in range(self.ndim)]
-    S.append('extern "C" __global__ __launch_bounds__(NB) void k_gat_{}(const Args a, T* __restrict__ g, const AdamP ad) {{'.format(gi))
-    tot_per = int(np.prod([fshape[d] for d in range(self.ndim) if d != ax]))
-    # 32-bit index arithmetic whenever the thread space fits (divisions by constants: a 64-bit one costs ~4x)
-    it = "int" if tot_per * (nloc + 4) < 2**31 - 512 else "long"
-    S.append("  const {0} l = ({0})blockIdx.x * NB + threadIdx.x;".format(it))
-    S.append("  if (l >= ({}){} * {}) return;".format(it, tot_per, nloc + 4))
-    rem = "l"
-    for d in reversed(range(self.ndim)):
-        ext = (nloc + 4) if d == ax else per[d]
-        if d == 0:
-            S.append("  const int j0 = (int){};".format(rem))
-        else:
-            S.append("  const int j{} = (int)({} % {});".format(d, rem, ext))
-            S.append("  const {} q{} = {} / {};".format(it, d, rem, ext))
-            rem = "q{}".format(d)
-    S.append("  const int jo = j{} - 2;".format(ax))  # owned-relative position on the sharded axis
-    S.append("  T acc = (T)0;")
-    loads = []
-    for entry, (cslot, attr, coeff) in enumerate(reads):
-        _, shift, loc, _ = attr
-        idx, valid = [], []
-        for d in range(self.ndim):
-            ns, nr = fshape[d], self.G[d]
-            ext = max(ns, nr)
-            s_ = shift[d] % ext
-            if s_ > ext // 2:
-                s_ -= ext
-            if d == ax:
-                # the load is UNCONDITIONAL on a clamped position and masked afterwards: loads behind per-entry
-                # branches are issued one at a time (each waits for the previous one's branch)
-                name = "c{}".format(entry)
-                S.append("  const int {} = jo - ({});".format(name, s_))
-                valid.append("{0} >= 0 && {0} < {1}".format(name, nloc))
-                idx.append("min(max({}, 0), {})".format(name, nloc - 1))
-                continue
-            pos = "j{}".format(d) if not (floc[d] == "c" and loc[d] == "n") else "(j{} + 1)".format(d)
-            e = pos if s_ == 0 else "wrap({} - ({}), {})".format(pos, s_, ext)
-            if floc[d] == "n" and loc[d] == "c":
-                name = "t{}_{}".format(entry, d)
-                S.append("  const int {} = {};".format(name, e))
-                valid.append("{} < {}".format(name, nr))
-                e = "min({}, {})".format(name, nr - 1)  # (the masked load stays inside the array)
-            idx.append(e)
-        S.append("  const T w{} = a.cot[{}][{}];".format(entry, cslot, self._offset(idx, self.GL)))
-        loads.append((entry, coeff, " && ".join(valid)))
-    for entry, coeff, valid in loads:  # every load above is in flight before the first use
-        term = "w{}".format(entry) if coeff is None else "({}) * w{}".format(coeff, entry)
-        S.append("  acc = acc + (({}) ? {} : (T)0);".format(valid, term))
-
-    def offset(along, extent):
-        full = [along if d == ax else "j{}".format(d) for d in range(self.ndim)]
-        shape = [extent if d == ax else per[d] for d in range(self.ndim)]
-        return self._offset(full, shape)
-
-    S.append("  const int jl = jo + a.lo;")
-    # owned planes a.alo <= jo < a.ahi have their whole gradient here (no neighbour's cell reads them): the optimizer's
-    # update is applied on the spot; the planes next to an interface wait for the halo sum (slab_traced.py)
-    S.append("  if (jl >= 0 && jl < a.ea) {")
-    S.append("    const int o = {};".format(offset("jl", "a.ea")))
-    S.append("    g[o] = acc;")
-    S.append("    if (jo >= a.alo && jo < a.ahi) adam_apply(ad, o, acc);")
-    S.append("  }")
-    S.append("  else if (jo < 0 && jo >= -a.hw) a.gwlo[{}][{}] = acc;".format(slot, offset("(jo + a.hw)", "a.hw")))
-    S.append("  else if (jo >= {0} && jo < {0} + a.hw) a.gwhi[{1}][{2}] = acc;".format(nloc, slot, offset("(jo - {})".format(nloc), "a.hw")))
-    S.append("}")
-
-
-_Codegen._gather_slab = _gather_slab
-
-
-def _cache_dirs():
-    """In-tree cache first (travels with the checkout); a PRIVATE per-user directory if that is read-only."""
-    yield _CACHE_DIR
-    yield os.path.join(os.path.expanduser("~"), ".cache", "odil_amd_jit")
-
-
-def _trusted(d):
-    """A cache directory libraries may be LOADED from: the in-tree one (whoever can write there can rewrite this
-    module as well), or one owned by this user and writable by nobody else (a shared temp directory with a
-    predictable name could be pre-created by another user with a planted library in it)."""
-    if d == _CACHE_DIR:
-        return True
-    try:
-        st = os.stat(d)
-    except OSError:
-        return False
-    return st.st_uid == os.getuid() and not (st.st_mode & 0o022)
-
-
-def _compile(src, flags=None):
-    flags = flags or _HIPCC_FLAGS
-    tag = hashlib.sha256((src + " ".join(flags)).encode()).hexdigest()[:20]
-    name = "odil_jit_{}.so".format(tag)
-    for d in _cache_dirs():
-        if os.path.exists(os.path.join(d, name)) and _trusted(d):
-            try:
-                os.utime(os.path.join(d, name))  # last use: lets a cache be pruned by age (tools/final_r3.sh)
-            except OSError:
-                pass
-            return ctypes.CDLL(os.path.join(d, name)), os.path.join(d, name)
-    last = None
-    for d in _cache_dirs():
-        try:
-            os.makedirs(d, mode=0o700, exist_ok=True)
-            if not _trusted(d):
-                raise OSError("cache directory {} is not private to this user".format(d))
-            # source and library are written under temporary names and renamed: ranks that compile the same
-            # operator at the same time never read each other's half-written files
-            fd, hip_tmp = tempfile.mkstemp(suffix=".hip", dir=d)
-            with os.fdopen(fd, "w") as f:
-                f.write(src)
-            fd, tmp = tempfile.mkstemp(suffix=".so", dir=d)
-            os.close(fd)
-        except OSError as e:
-            last = e
-            continue
-        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        res = subprocess.run([hipcc] + flags + ["-o", tmp, hip_tmp], capture_output=True, text=True)
-        hip = os.path.join(d, "odil_jit_{}.hip".format(tag))
-        os.replace(hip_tmp, hip)  # kept beside the library for inspection
-        if res.returncode != 0:
-            os.unlink(tmp)
-            raise RuntimeError("hipcc failed for the traced operator ({}):\n{}".format(hip, res.stderr[-4000:]))
-        path = os.path.join(d, name)
-        os.replace(tmp, path)  # atomic: concurrent ranks compiling the same source do not collide
-        return ctypes.CDLL(path), path
-    raise FileNotFoundError("no writable private cache directory for traced operators: {}".format(last))

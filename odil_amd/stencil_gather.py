@@ -1,0 +1,341 @@
+"""The gathers of stencil_codegen.py: from the adjoints `k_fwd` stored to the gradient of every field (`k_gat_*`, one
+launch per field or `k_gat_all` for all of them), with the optimizer's update by the lane that forms the gradient, and the
+Jacobian coefficient arrays `k_jac`, which is a kernel of the same form.  (The gathers of a marching kernel: stencil_march.py.)
+"""
+
+import numpy as np
+
+from . import stencil_grad
+from .stencil_trace import TraceUnsupported
+
+
+class _GatherKernels:
+    """Methods of `stencil_codegen._Codegen`, emitted from `source()` after the forward kernel."""
+
+    def _standard_gathers(self, S):
+        if self.gathers_done:
+            return
+        self.gathers = []  # keys of the fields that need a gather launch
+        self.gather_reads_sources = dict()  # key -> the gather reads the fields' own arrays (not only stored adjoints)
+        self.direct = dict()  # key -> cot slot that already IS the gradient
+        by_key = dict()  # key -> [(slot, read attr, coefficient expression or None)]
+        for slot, n in enumerate(self.cots):
+            by_key.setdefault(n.attr[0], []).append((slot, n.attr, None))
+        for k, n in enumerate(self.cut_nodes):
+            for ridx, coeff in self.cut_set[n.idx].items():
+                attr = self.tr.nodes[ridx].attr
+                by_key.setdefault(attr[0], []).append((len(self.cots) + k, attr, coeff))
+        symbolic = dict()
+        if self.all_regular:
+            symbolic = self._gradient_terms()
+        self.gather_blocks = dict()
+        keys = list(by_key) + [k for k in symbolic if k not in by_key]
+        for key in keys:
+            reads = by_key.get(key, [])
+            floc = self.state.fields[key].loc
+            fshape = self._field_shape(key)
+            only_legacy = all(adj is None or not any(self.tr.nodes[r].attr[0] == key for r in adj) for adj in self.out_adj)
+            if (self.slab is None and only_legacy and len(reads) == 1 and reads[0][2] is None and not any(reads[0][1][1])
+                    and reads[0][1][2] == floc):
+                self.direct[key] = reads[0][0]
+                continue
+            gi = len(self.gathers)
+            self.gathers.append(key)
+            regular = tuple(fshape) == self.G and all(attr[2] == floc for _, attr, _ in reads)
+            if key in symbolic and regular and symbolic[key] is not None:
+                self._gather_symbolic(S, gi, key, symbolic[key])
+                continue
+            if self.slab is not None:
+                self._gather_slab(S, gi, key, reads, floc, fshape)
+                continue
+            tot = int(np.prod(fshape))
+            self.gather_blocks[gi] = (tot + 255) // 256
+            S.append('extern "C" __global__ __launch_bounds__(NB) void k_gat_{}(const Args a, T* __restrict__ g, const AdamP ad) {{'.format(gi))
+            S.append("  const int l = blockIdx.x * NB + threadIdx.x;")
+            S.append("  if (l >= {}) return;".format(tot))
+            rem = "l"
+            for d in reversed(range(self.ndim)):
+                if d == 0:
+                    S.append("  const int j0 = {};".format(rem))
+                else:
+                    S.append("  const int j{} = {} % {};".format(d, rem, fshape[d]))
+                    S.append("  const int q{} = {} / {};".format(d, rem, fshape[d]))
+                    rem = "q{}".format(d)
+            S.append("  T acc = (T)0;")
+            for entry, (slot, attr, coeff) in enumerate(reads):
+                _, shift, loc, _ = attr
+                idx, valid = [], []
+                for d in range(self.ndim):
+                    ns, nr = fshape[d], self.G[d]
+                    ext = max(ns, nr)
+                    s_ = shift[d] % ext
+                    if s_ > ext // 2:
+                        s_ -= ext
+                    pos = "j{}".format(d) if not (floc[d] == "c" and loc[d] == "n") else "(j{} + 1)".format(d)
+                    e = pos if s_ == 0 else "wrap({} - ({}), {})".format(pos, s_, ext)
+                    if floc[d] == "n" and loc[d] == "c":  # trimmed: the last padded position was dropped
+                        name = "t{}_{}".format(entry, d)
+                        S.append("  const int {} = {};".format(name, e))
+                        valid.append("{} < {}".format(name, nr))
+                        e = name
+                    idx.append(e)
+                load = "a.cot[{}][{}]".format(slot, self._offset(idx, self.G))
+                if coeff is not None:  # a cut array: the stored adjoint times d(node) / d(read)
+                    load = "({}) * {}".format(coeff, load)
+                if valid:
+                    load = "(({}) ? {} : (T)0)".format(" && ".join(valid), load)
+                S.append("  acc = acc + {};".format(load))
+            S.append("  g[l] = acc;")
+            S.append("  adam_apply(ad, l, acc);")
+            S.append("}")
+        # every symbolic gather in ONE launch: the fields' expressions share most of what they read (stored seeds, each
+        # other's arrays), a merged pass reads it once (tracer with three space dimensions: 52 -> 36 words per point)
+        self.merged = []
+        sym_keys = [key for key in self.gathers if key in symbolic and symbolic[key] is not None
+                    and tuple(self._field_shape(key)) == self.G
+                    and all(attr[2] == self.state.fields[key].loc for _, attr, _ in by_key.get(key, []))]
+        if len(sym_keys) >= 2:
+            self.merged = sym_keys
+            nk = len(sym_keys)
+            S.append("struct GatAll {{ T* g[{0}]; AdamP ad[{0}]; }};".format(nk))
+            nblocks_all = self._gather_kernel(S, "k_gat_all", [(key, symbolic[key]) for key in sym_keys], "const GatAll ga",
+                                              lambda k: "ga.g[{}]".format(k), lambda k: "ga.ad[{}]".format(k))
+            S.append('extern "C" int jit_gather_all(const Args* a, void* const* g, void* const* x, void* const* m, void* const* v,')
+            S.append('                               double alpha, double omb1, double omb2, double eps, const void* alpha_dev, void* stream) {')
+            S.append("  GatAll ga;")
+            S.append("  for (int k = 0; k < {}; ++k) {{".format(nk))
+            S.append("    ga.g[k] = (T*)g[k];")
+            S.append("    ga.ad[k] = AdamP{(T*)x[k], (T*)m[k], (T*)v[k], (T)alpha, (T)omb1, (T)omb2, (T)eps, (const T*)alpha_dev};")
+            S.append("  }")
+            S.append("  hipLaunchKernelGGL(k_gat_all, dim3({}), dim3(NB), 0, (hipStream_t)stream, *a, ga);".format(nblocks_all))
+            S.append("  return (int)hipGetLastError();")
+            S.append("}")
+
+    def _gather_symbolic(self, S, gi, key, root):
+        """The gather of ONE regular field as a pointwise kernel over its gradient expression."""
+        self.gather_blocks[gi] = self._gather_kernel(S, "k_gat_{}".format(gi), [(key, root)],
+                                                     "T* __restrict__ g, const AdamP ad", lambda k: "g", lambda k: "ad")
+
+    def _gather_kernel(self, S, name, items, params, G_, AD_, owned=False):
+        """A pointwise kernel over the gradient expressions of `items` = [(field key, expression)] (one thread per
+        point, or per four points of the last axis): common sub-expressions and loads of the fields' expressions are
+        shared, every field's gradient is stored, and the optimizer's update applied, by the lane that holds it.
+        Slab mode: threads cover planes -2 .. n + 2 of the sharded axis; planes that exist in the rank's ghost-extended
+        gradient array are stored there (ghost planes: what this rank's cells contribute to the neighbour's), planes
+        beyond an end of the decomposition that a periodic read reached go to the wrap buffers (as the legacy slab
+        gather).  owned=True (slab mode, `k_jac`): threads cover the OWNED planes 0 .. n only, reads go through the same
+        ghost / wrap addressing, and every item is stored into an array of the owned shape; no optimizer update.
+        Returns the number of workgroups to launch."""
+        vw, last = self.vw_gat, self.ndim - 1
+        seen = dict()
+        for _, root in items:
+            for n in stencil_grad.subdag(root):
+                seen[n.idx] = n
+        nodes = [seen[i] for i in sorted(seen)]
+        with self._body(order=nodes, vw=vw, in_gather=True) as gathered:
+            self.forward()
+            body = gathered.lines
+            interior = self._interior_copy(nodes, vw)
+            pre = gathered.pre + self._group_arrays()
+        values = [self.r(root) for _, root in items]
+        sources = sorted({n.attr[0] for n in nodes if n.op == "read" and not n.attr[0].startswith("@")})
+        for key, _ in items:
+            if not key.startswith("@"):  # (bookkeeping of the optimizer fusion: the items of the Jacobian kernel are no fields)
+                self.gather_reads_sources[key] = sorted(set(self.gather_reads_sources.get(key, [])) | set(sources))
+        shape = list(self.G)
+        names = ["i{}".format(d) for d in range(self.ndim)]
+        if self.slab is not None:
+            ax, nloc = self.slab
+            shape[ax] = nloc if owned else nloc + 4
+            names[ax] = "jx"
+        threads = int(np.prod(shape)) // vw
+        if threads >= 2**31 - 1024:
+            raise TraceUnsupported("grid too large for 32-bit indexing")
+        flat = "l4" if vw == 4 else "l"
+        S.append('extern "C" __global__ __launch_bounds__(NB) void {}(const Args a, {}) {{'.format(name, params))
+        S.append(self._block_index(shape, vw))
+        S.append("  const int {}r = bx_ * NB + threadIdx.x;".format(flat))
+        S.append("  if ({}r >= {}) return;".format(flat, threads))
+        self._chunk_remap(S, shape, vw, flat + "r", flat)
+        self._index_prologue(S, shape, names, vw, flat)
+        nblocks = (threads + 255) // 256
+        if self.slab is not None and owned:
+            S.append("  const int jo = jx;")
+            S.append("  const int i{}g = jo + a.off;".format(ax))
+        elif self.slab is not None:
+            S.append("  const int jo = jx - 2;")  # owned-relative position on the sharded axis
+            S.append("  const int i{}g = wrap(jo + a.off, {});".format(ax, self.G[ax]))
+        S.extend(pre)
+        for k in range(len(items)):
+            S.append("  T acc{}[{}];".format(k, vw))
+
+        def point_block(body_):
+            B = []
+            self._loop_open(B, vw)
+            B.extend(body_)
+            for k, value in enumerate(values):
+                B.append("  acc{}[{}] = {};".format(k, "p" if vw == 4 else "0", value))
+            if vw == 4:
+                B.append("  }")
+            return B
+
+        if interior is None:
+            S.extend(point_block(body))
+        else:
+            S.append("  if (__all((int)({}))) {{".format(self._interior_cond(interior[1][1])))
+            S.extend(point_block(interior[0][0]))
+            S.append("  } else {")
+            S.extend(point_block(body))
+            S.append("  }")
+        adam = "adam_apply4({ad}, {o}, acc{k});" if vw == 4 else "adam_apply({ad}, {o}, acc{k}[0]);"
+        put = "*(T4*)({dst} + {o}) = (T4){{acc{k}[0], acc{k}[1], acc{k}[2], acc{k}[3]}};" if vw == 4 else "{dst}[{o}] = acc{k}[0];"
+        if vw == 4 and self.nt_streams:  # (with the optimizer state, see adam_apply4)
+            put = "__builtin_nontemporal_store((T4){{acc{k}[0], acc{k}[1], acc{k}[2], acc{k}[3]}}, (T4*)({dst} + {o}));"
+        if self.slab is None:
+            o = "l4 * 4" if vw == 4 else "l"
+            for k in range(len(items)):
+                S.append("  " + put.format(dst=G_(k), o=o, k=k))
+                S.append("  " + adam.format(ad=AD_(k), o=o, k=k))
+            S.append("}")
+            return nblocks
+
+        def offset(along, extent):
+            full = [along if d == ax else ("ib" if (vw == 4 and d == last) else "i{}".format(d)) for d in range(self.ndim)]
+            ext = [extent if d == ax else self.G[d] for d in range(self.ndim)]
+            return self._offset(full, ext)
+
+        if owned:
+            S.append("  const int o = {};".format(offset("jo", nloc)))
+            for k in range(len(items)):
+                S.append("  " + put.format(dst=G_(k), o="o", k=k))
+            S.append("}")
+            return nblocks
+        S.append("  const int jl = jo + a.lo;")
+        # owned planes a.alo <= jo < a.ahi have their whole gradient here (no neighbour's cell reads them): the optimizer's
+        # update is applied on the spot; the planes next to an interface wait for the halo sum (slab_traced.py)
+        S.append("  if (jl >= 0 && jl < a.ea) {")
+        S.append("    const int o = {};".format(offset("jl", "a.ea")))
+        for k in range(len(items)):
+            S.append("    " + put.format(dst=G_(k), o="o", k=k))
+            S.append("    if (jo >= a.alo && jo < a.ahi) " + adam.format(ad=AD_(k), o="o", k=k))
+        S.append("  }")
+        S.append("  else if (jo < 0 && jo >= -a.hw) {")
+        S.append("    const int o = {};".format(offset("(jo + a.hw)", "a.hw")))
+        for k, (key, _) in enumerate(items):
+            S.append("    " + put.format(dst="a.gwlo[{}]".format(self.src_keys.index(key)), o="o", k=k))
+        S.append("  }")
+        S.append("  else if (jo >= {0} && jo < {0} + a.hw) {{".format(nloc))
+        S.append("    const int o = {};".format(offset("(jo - {})".format(nloc), "a.hw")))
+        for k, (key, _) in enumerate(items):
+            S.append("    " + put.format(dst="a.gwhi[{}]".format(self.src_keys.index(key)), o="o", k=k))
+        S.append("  }")
+        S.append("}")
+        return nblocks
+
+    def _gather_slab(self, S, gi, key, reads, floc, fshape):
+        """Gather of one field on one rank's slab.  Threads cover planes -2 .. n + 2 of the sharded axis (owned
+        cells 0 .. n): g = sum_r cot_r[j - shift_r] over the OWNED cells that read j.  Planes that exist in the
+        rank's ghost-extended gradient array are stored there (ghost planes: the part of the neighbour's gradient
+        that this rank's cells produce, sent over and added by slab_traced.py); planes beyond a side WITHOUT ghosts
+        (the ends of the decomposition) that a periodic read reached go to the wrap buffers gwlo / gwhi."""
+        ax, nloc = self.slab
+        slot = self.src_keys.index(key)
+        per = [fshape[d] for d in range(self.ndim)]
+        S.append('extern "C" __global__ __launch_bounds__(NB) void k_gat_{}(const Args a, T* __restrict__ g, const AdamP ad) {{'.format(gi))
+        tot_per = int(np.prod([fshape[d] for d in range(self.ndim) if d != ax]))
+        # 32-bit index arithmetic whenever the thread space fits (divisions by constants: a 64-bit one costs ~4x)
+        it = "int" if tot_per * (nloc + 4) < 2**31 - 512 else "long"
+        S.append("  const {0} l = ({0})blockIdx.x * NB + threadIdx.x;".format(it))
+        S.append("  if (l >= ({}){} * {}) return;".format(it, tot_per, nloc + 4))
+        rem = "l"
+        for d in reversed(range(self.ndim)):
+            ext = (nloc + 4) if d == ax else per[d]
+            if d == 0:
+                S.append("  const int j0 = (int){};".format(rem))
+            else:
+                S.append("  const int j{} = (int)({} % {});".format(d, rem, ext))
+                S.append("  const {} q{} = {} / {};".format(it, d, rem, ext))
+                rem = "q{}".format(d)
+        S.append("  const int jo = j{} - 2;".format(ax))  # owned-relative position on the sharded axis
+        S.append("  T acc = (T)0;")
+        loads = []
+        for entry, (cslot, attr, coeff) in enumerate(reads):
+            _, shift, loc, _ = attr
+            idx, valid = [], []
+            for d in range(self.ndim):
+                ns, nr = fshape[d], self.G[d]
+                ext = max(ns, nr)
+                s_ = shift[d] % ext
+                if s_ > ext // 2:
+                    s_ -= ext
+                if d == ax:
+                    # the load is UNCONDITIONAL on a clamped position and masked afterwards: loads behind per-entry
+                    # branches are issued one at a time (each waits for the previous one's branch)
+                    name = "c{}".format(entry)
+                    S.append("  const int {} = jo - ({});".format(name, s_))
+                    valid.append("{0} >= 0 && {0} < {1}".format(name, nloc))
+                    idx.append("min(max({}, 0), {})".format(name, nloc - 1))
+                    continue
+                pos = "j{}".format(d) if not (floc[d] == "c" and loc[d] == "n") else "(j{} + 1)".format(d)
+                e = pos if s_ == 0 else "wrap({} - ({}), {})".format(pos, s_, ext)
+                if floc[d] == "n" and loc[d] == "c":
+                    name = "t{}_{}".format(entry, d)
+                    S.append("  const int {} = {};".format(name, e))
+                    valid.append("{} < {}".format(name, nr))
+                    e = "min({}, {})".format(name, nr - 1)  # (the masked load stays inside the array)
+                idx.append(e)
+            S.append("  const T w{} = a.cot[{}][{}];".format(entry, cslot, self._offset(idx, self.GL)))
+            loads.append((entry, coeff, " && ".join(valid)))
+        for entry, coeff, valid in loads:  # every load above is in flight before the first use
+            term = "w{}".format(entry) if coeff is None else "({}) * w{}".format(coeff, entry)
+            S.append("  acc = acc + (({}) ? {} : (T)0);".format(valid, term))
+
+        def offset(along, extent):
+            full = [along if d == ax else "j{}".format(d) for d in range(self.ndim)]
+            shape = [extent if d == ax else per[d] for d in range(self.ndim)]
+            return self._offset(full, shape)
+
+        S.append("  const int jl = jo + a.lo;")
+        # owned planes a.alo <= jo < a.ahi have their whole gradient here (no neighbour's cell reads them): the optimizer's
+        # update is applied on the spot; the planes next to an interface wait for the halo sum (slab_traced.py)
+        S.append("  if (jl >= 0 && jl < a.ea) {")
+        S.append("    const int o = {};".format(offset("jl", "a.ea")))
+        S.append("    g[o] = acc;")
+        S.append("    if (jo >= a.alo && jo < a.ahi) adam_apply(ad, o, acc);")
+        S.append("  }")
+        S.append("  else if (jo < 0 && jo >= -a.hw) a.gwlo[{}][{}] = acc;".format(slot, offset("(jo + a.hw)", "a.hw")))
+        S.append("  else if (jo >= {0} && jo < {0} + a.hw) a.gwhi[{1}][{2}] = acc;".format(nloc, slot, offset("(jo - {})".format(nloc), "a.hw")))
+        S.append("}")
+
+    def _jacobian_kernel(self, S):
+        """`k_jac`: what `Problem.eval_operator_grad` returns (reference core.py:1313-1361, the input of `linearize`,
+        core.py:1113-1217) as ONE pointwise kernel -- the value of every output and d output / d read for every distinct
+        read (key, shift, loc), i.e. the per-shift coefficient arrays of the Jacobian -- from the SYMBOLIC derivative of the
+        traced DAG (stencil_grad.GradBuilder with the unit seed), instead of one autograd pass per output over a graph
+        of torch elementwise kernels.  Operators whose outputs are windows of the grid, or that differentiate through
+        parameter arrays (dense Jacobian columns), keep the autograd route (TraceUnsupported).  Slab mode: the rank's owned
+        cells only, u read from the ghost-extended array and the wrap planes, one owned-shape array per item
+        (slab_traced.HipSlabKernels.jacobian)."""
+        tr = self.tr
+        items, self.jac_items = [], []  # jac_items[j] = (output position, None for its value | the read's attr)
+        for k, o in enumerate(self.outputs):
+            if o.win is not None or tuple(o.shape) != self.G or self.raw[k]:
+                raise TraceUnsupported("Jacobian kernel: output {} is not a plain residual on the whole grid".format(k))
+            nodes = stencil_grad.subdag(o)
+            if not stencil_grad.differentiable(nodes, self.need):
+                raise TraceUnsupported("Jacobian kernel: parameters below output {} (dense columns)".format(k))
+            gb = stencil_grad.GradBuilder(tr, self.G, self.need, stop=())
+            items.append(("@jv{}".format(k), gb.real(o)))
+            self.jac_items.append((k, None))
+            adj = gb.adjoints(o, gb.const(1.0), nodes) if self.need.get(o.idx, False) else dict()
+            for ridx in sorted(adj):
+                expr = adj[ridx]
+                if expr is None:
+                    continue
+                items.append(("@jd{}_{}".format(k, ridx), expr))
+                self.jac_items.append((k, tuple(tr.nodes[ridx].attr)))
+        if len(items) > 96:
+            raise TraceUnsupported("Jacobian kernel: {} arrays".format(len(items)))
+        S.append("struct JacP {{ T* p[{}]; }};".format(len(items)))
+        self.jac_blocks = self._gather_kernel(S, "k_jac", items, "const JacP jp, const AdamP ad", lambda k: "jp.p[{}]".format(k),
+                                              lambda k: "ad", owned=self.slab is not None)

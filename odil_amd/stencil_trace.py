@@ -167,6 +167,7 @@ class Tracer:
         self.nodes = []
         self.cse = dict()
         self.tensors = []  # concrete device tensors referenced by 'tensor' leaves
+        self.state_locs = dict()  # field key -> location of its regular array (TraceContext; the generator adds its own)
 
     # ---- node construction ---------------------------------------------------------------
     def node(self, op, args=(), attr=None, shape=(), kind=_R, host=False, win=None):

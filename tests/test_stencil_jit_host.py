@@ -441,3 +441,35 @@ def test_args_layout_is_shared(cpu_mod, mode, case):
         _check_shared_layout(bound.source, "ParArgs", bound.cg.par_args_layout(), type(bound.par_args))
     else:
         assert "struct ParArgs" not in bound.source and not hasattr(bound, "par_args")
+
+
+def _outer_emission_state(cg, order):
+    return cg.order is order and cg.fold is None and not cg.in_gather and cg.vw == cg.vw_fwd
+
+
+def test_emission_state_is_restored(cpu_mod):
+    """The generator emits every further body (interior copies, gathers) with `_Codegen._body`, which installs the state of
+    that body and puts the enclosing one back: after `source()`, and after a body that raised, the state seen on the
+    generator is the outer one -- the node order of `k_fwd` (the same list), no folded predicates, not in a gather, the
+    forward kernel's points per thread."""
+    sys.path.insert(0, os.path.join(ROOT, "examples", "wave"))
+    import wave
+
+    from odil_amd.stencil_codegen import _Codegen
+    from odil_amd.stencil_trace import TraceUnsupported
+
+    problem, state = wave.make_problem(wave.parse_args(["--Nt", "8", "--Nx", "8"]))
+    tr, outs, raw, _, G = stencil_jit.trace_outputs(problem, state)
+    cg = _Codegen(tr, outs, raw, G, state)
+    order = cg.order
+    assert _outer_emission_state(cg, order)
+    source = cg.source()
+    assert "k_gat_" in source  # (bodies other than k_fwd's were emitted)
+    assert _outer_emission_state(cg, order)
+    lines = list(cg.lines)
+    bad = [tr.node("no_such_op", shape=G)]
+    with pytest.raises(TraceUnsupported):
+        with cg._body(order=bad, vw=4 // cg.vw_fwd, in_gather=True, fold=dict()) as body:
+            assert cg.order is bad and cg.in_gather and cg.fold is body.fold and cg.vw != cg.vw_fwd
+            cg.forward()
+    assert _outer_emission_state(cg, order) and cg.lines == lines

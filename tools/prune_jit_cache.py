@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Keeps odil_amd/_jit_cache to the generated kernels that are really loaded.
 
-Every cache hit touches its library (`stencil_codegen._compile`: os.utime), so after a run the libraries with a
+Every cache hit touches its library (`jit_cache._compile`: os.utime), so after a run the libraries with a
 modification time newer than a marker are exactly the ones that were used (hits and fresh builds alike):
 
     python tools/prune_jit_cache.py mark                       # on the GPU box, before the run
