@@ -453,6 +453,31 @@ int odil_poisson_small_epochs_f32(float* x, float* m, float* v, float* g, float*
                                   int nepochs, float one_minus_b1, float one_minus_b2, float eps, float* losses,
                                   float* norms, double* partials, void* stream);
 
+/* An ENSEMBLE of nbatch such problems in ONE launch: workgroup b runs member b for nepochs epochs -- exactly the
+ * per-workgroup code of odil_poisson_small_epochs on pointers offset by the member strides, so every member's result
+ * equals its single launch bit for bit.  Members never communicate (no atomics, no grid-wide synchronisation).
+ *   x, m, v, g, u   [nbatch] packed vectors, member b at b * state_stride elements (state_stride >= unknowns of a member)
+ *   fu, rhs         [nbatch] finest-level arrays, member b at b * field_stride (>= cells of the finest level)
+ *   alphas          member b's nepochs step sizes at b * alpha_stride; alpha_stride = 0: one table shared by all members
+ *   losses, norms   member b's nepochs values at b * out_stride (>= nepochs)
+ *   partials        reduction workspace, member b's at b * partials_stride doubles
+ *                   (>= odil_poisson_small_epochs_partials(shapes, ndim, elem_size))
+ * Shapes, h2 and the Adam constants are common to the ensemble.  Null pointers, nbatch < 1, strides smaller than a
+ * member, levels that do not halve and a partials workspace that is too small are refused before anything is launched. */
+int64_t odil_poisson_small_epochs_partials(const int64_t* shapes, int ndim, int elem_size);
+int odil_poisson_small_epochs_batch_f64(double* x, double* m, double* v, double* g, double* u, double* fu, const double* rhs,
+                                        int nbatch, int64_t state_stride, int64_t field_stride, const int64_t* shapes,
+                                        int nlvl, int ndim, const double* h2, const double* alphas, int64_t alpha_stride,
+                                        int nepochs, double one_minus_b1, double one_minus_b2, double eps, double* losses,
+                                        double* norms, int64_t out_stride, double* partials, int64_t partials_stride,
+                                        void* stream);
+int odil_poisson_small_epochs_batch_f32(float* x, float* m, float* v, float* g, float* u, float* fu, const float* rhs,
+                                        int nbatch, int64_t state_stride, int64_t field_stride, const int64_t* shapes,
+                                        int nlvl, int ndim, const float* h2, const float* alphas, int64_t alpha_stride,
+                                        int nepochs, float one_minus_b1, float one_minus_b2, float eps, float* losses,
+                                        float* norms, int64_t out_stride, double* partials, int64_t partials_stride,
+                                        void* stream);
+
 /* TWO sweeps of odil_stencil_var_smooth in mode 0, with the weights omega1 and then omega2, in ONE pass: the coefficient arrays -- 7 of
  * the 10 words a sweep moves in 3-D -- are read once for both, the intermediate iterate stays on the CU.  out != x;
  * bit-identical to two calls of odil_stencil_var_smooth.  The last extent must be even.  zc_hint: planes per workgroup

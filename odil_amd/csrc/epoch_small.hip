@@ -14,6 +14,8 @@
 // adam_update from the shared headers -- and the loss is summed in the order of the two-stage reduction (per-thread running
 // sums of the residual kernel's virtual workgroups, wave shuffle tree, four wave sums, k_final_reduce's tree over the
 // partials), so the trajectory is BIT-IDENTICAL to the multi-launch path (tests/test_trajectories.py).
+#include <atomic>
+
 #include "mg_transfer.h"
 #include "poisson.h"
 
@@ -198,14 +200,14 @@ __device__ __forceinline__ double small_wave_sum(double v) {
   return v;
 }
 
+// What ONE workgroup does for ONE problem: the body of the single launch and of every member of a batched one.
 // LDS: the state lives in shared memory for the whole launch -- a separate instantiation, so that its pointers are
 // LDS pointers to the compiler (ds_read / ds_write) and not generic ones (flat accesses cost a phase ~3x the latency)
 template <typename T, bool LDS>
-__global__ __launch_bounds__(kSmallThreads) void k_poisson_small_epochs(T* xg, T* mg, T* vg, T* gg, T* ug, T* fug,
-                                                                        const T* rhsg, const T* __restrict__ alphas,
-                                                                        T* __restrict__ losses, T* __restrict__ norms,
-                                                                        double* partials,
-                                                                        SmallArgs<T> a, H2<T> h) {
+__device__ __forceinline__ void small_epochs_body(T* xg, T* mg, T* vg, T* gg, T* ug, T* fug, const T* rhsg,
+                                                  const T* __restrict__ alphas, T* __restrict__ losses,
+                                                  T* __restrict__ norms, double* partials, const SmallArgs<T>& a,
+                                                  const H2<T>& h) {
   constexpr int V = VecOf<T>::N;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ double wave_sums[kSmallThreads / 64];
@@ -366,19 +368,57 @@ __global__ __launch_bounds__(kSmallThreads) void k_poisson_small_epochs(T* xg, T
   }
 }
 
+template <typename T, bool LDS>
+__global__ __launch_bounds__(kSmallThreads) void k_poisson_small_epochs(T* xg, T* mg, T* vg, T* gg, T* ug, T* fug,
+                                                                        const T* rhsg, const T* __restrict__ alphas,
+                                                                        T* __restrict__ losses, T* __restrict__ norms,
+                                                                        double* partials,
+                                                                        SmallArgs<T> a, H2<T> h) {
+  small_epochs_body<T, LDS>(xg, mg, vg, gg, ug, fug, rhsg, alphas, losses, norms, partials, a, h);
+}
+
+// Member strides of a batched launch, in elements of the arrays they step through
+struct SmallStrides {
+  int64_t state;   // x, m, v, g, u: the packed vectors of all levels
+  int64_t field;   // fu, rhs: the finest level
+  int64_t alpha;   // step sizes (0: one table for all members)
+  int64_t out;     // losses, norms
+  int64_t part;    // the reduction workspace (doubles)
+};
+
+// An ENSEMBLE of such problems: workgroup b runs member b -- the same body on pointers offset by the member strides.
+// Members share shapes, steps and the Adam constants and never meet: no atomics, no grid-wide synchronisation.
+template <typename T, bool LDS>
+__global__ __launch_bounds__(kSmallThreads) void k_poisson_small_epochs_batch(T* xg, T* mg, T* vg, T* gg, T* ug, T* fug,
+                                                                              const T* rhsg, const T* __restrict__ alphas,
+                                                                              T* __restrict__ losses, T* __restrict__ norms,
+                                                                              double* partials, SmallStrides st,
+                                                                              SmallArgs<T> a, H2<T> h) {
+  const int64_t b = blockIdx.x;
+  const int64_t so = b * st.state, fo = b * st.field, oo = b * st.out;
+  small_epochs_body<T, LDS>(xg + so, mg + so, vg + so, gg + so, ug + so, fug + fo, rhsg + fo, alphas + b * st.alpha,
+                            losses + oo, norms + oo, partials + b * st.part, a, h);
+}
+
+// dynamic LDS of the resident form: the state and the reduction workspace (per virtual workgroup: its sum, four wave sums)
 template <typename T>
-static int poisson_small_epochs(T* x, T* m, T* v, T* g, T* u, T* fu, const T* rhs, const int64_t* shapes, int nlvl,
-                                int ndim, const T* h2, const T* alphas, int nepochs, T omb1, T omb2, T eps, T* losses,
-                                T* norms, double* partials, void* stream) {
-  if (!x || !m || !v || !g || !u || !fu || !rhs || !shapes || !h2 || !alphas || !losses || !norms || !partials) {
-    set_error("poisson_small_epochs: null pointer");
-    return ODIL_E_INVAL;
-  }
+static size_t small_lds_bytes(const SmallArgs<T>& a) {
+  return small_state_bytes<T>(a.total, a.lv[0].size) + (size_t)a.grid * 5 * sizeof(double);
+}
+
+template <typename T>
+static int small_threads(const SmallArgs<T>& a) {
+  return (a.ndim == 1 && a.lv[0].size <= 512) ? kBlock : kSmallThreads;
+}
+
+// Levels, schedule and constants of a launch from its arguments; `what` names the entry point in the refusals.
+template <typename T>
+static int small_fill_args(const char* what, SmallArgs<T>& a, H2<T>& h, const int64_t* shapes, int nlvl, int ndim,
+                           const T* h2, int nepochs, T omb1, T omb2, T eps) {
   if (ndim < 1 || ndim > 2 || nlvl < 1 || nlvl > kSmallMaxLev || nepochs < 1) {
-    set_error("poisson_small_epochs: ndim %d (1 or 2), %d levels (<= %d), %d epochs", ndim, nlvl, kSmallMaxLev, nepochs);
+    set_error("%s: ndim %d (1 or 2), %d levels (<= %d), %d epochs", what, ndim, nlvl, kSmallMaxLev, nepochs);
     return ODIL_E_INVAL;
   }
-  SmallArgs<T> a;
   a.nlvl = nlvl, a.ndim = ndim, a.nepochs = nepochs;
   int off = 0;
   for (int l = 0; l < kSmallMaxLev; ++l) {
@@ -387,11 +427,11 @@ static int poisson_small_epochs(T* x, T* m, T* v, T* g, T* u, T* fu, const T* rh
     if (l >= nlvl) continue;
     const int64_t nz = ndim == 2 ? shapes[l * ndim] : 1, nx = shapes[l * ndim + ndim - 1];
     if (nz < (ndim == 2 ? 2 : 1) || nx < 2 || nz * nx > (1 << 22)) {
-      set_error("poisson_small_epochs: level %d of %lld x %lld cells", l, (long long)nz, (long long)nx);
+      set_error("%s: level %d of %lld x %lld cells", what, l, (long long)nz, (long long)nx);
       return ODIL_E_INVAL;
     }
     if (l > 0 && (2 * nx != a.lv[l - 1].nx || (ndim == 2 && 2 * nz != a.lv[l - 1].nz))) {
-      set_error("poisson_small_epochs: level %d does not halve level %d", l, l - 1);
+      set_error("%s: level %d does not halve level %d", what, l, l - 1);
       return ODIL_E_INVAL;
     }
     L.nz = (int)nz, L.nx = (int)nx, L.size = (int)(nz * nx), L.off = off;
@@ -411,33 +451,112 @@ static int poisson_small_epochs(T* x, T* m, T* v, T* g, T* u, T* fu, const T* rh
   const int64_t XS = (a.lv[0].nx + per - 1) / per;
   a.usched = make_unit_sched(a.lv[0].nz, 1, XS);
   a.grid = unit_grid(a.usched);
+  T hh[3] = {T(1), T(1), T(1)};
+  if (ndim == 2) hh[0] = h2[0], hh[2] = h2[1];
+  if (ndim == 1) hh[2] = h2[0];
+  h = make_h2<T>(hh);
+  a.lds = small_lds_bytes<T>(a) <= kSmallLdsBytes;
+  return 0;
+}
+
+// More dynamic LDS than the 64 KB a launch gets by default is a property of (kernel, DEVICE): raised once for each
+// device a kernel is launched on (`done`: one per kernel; racing threads at worst both raise it).
+constexpr int kSmallMaxDevices = 64;
+struct SmallLdsRaised {
+  std::atomic<bool> on[kSmallMaxDevices];
+};
+
+static bool small_raise_lds(const void* kernel, SmallLdsRaised& done) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  const bool tracked = dev >= 0 && dev < kSmallMaxDevices;  // (beyond: raised before every launch)
+  if (tracked && done.on[dev].load(std::memory_order_acquire)) return true;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallLdsBytes) != hipSuccess)
+    return false;
+  if (tracked) done.on[dev].store(true, std::memory_order_release);
+  return true;
+}
+
+template <typename T>
+static int poisson_small_epochs(T* x, T* m, T* v, T* g, T* u, T* fu, const T* rhs, const int64_t* shapes, int nlvl,
+                                int ndim, const T* h2, const T* alphas, int nepochs, T omb1, T omb2, T eps, T* losses,
+                                T* norms, double* partials, void* stream) {
+  if (!x || !m || !v || !g || !u || !fu || !rhs || !shapes || !h2 || !alphas || !losses || !norms || !partials) {
+    set_error("poisson_small_epochs: null pointer");
+    return ODIL_E_INVAL;
+  }
+  SmallArgs<T> a;
+  H2<T> h;
+  if (int err = small_fill_args<T>("poisson_small_epochs", a, h, shapes, nlvl, ndim, h2, nepochs, omb1, omb2, eps)) return err;
   if (a.grid * 5 > kMaxPartials) {
     set_error("poisson_small_epochs: %d partial sums exceed the reduction workspace", a.grid);
     return ODIL_E_INVAL;
   }
-  T hh[3] = {T(1), T(1), T(1)};
-  if (ndim == 2) hh[0] = h2[0], hh[2] = h2[1];
-  if (ndim == 1) hh[2] = h2[0];
-  const size_t need = small_state_bytes<T>(a.total, (int)n0) + (size_t)a.grid * 5 * sizeof(double);
-  a.lds = need <= kSmallLdsBytes;
-  const int threads = (ndim == 1 && n0 <= 512) ? kBlock : kSmallThreads;
+  const int threads = small_threads(a);
   if (a.lds) {
-    static bool raised = false;  // (more than the 64 KB a launch gets by default: once per process and instantiation)
-    if (!raised) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_poisson_small_epochs<T, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallLdsBytes) != hipSuccess) {
-        set_error("poisson_small_epochs: cannot raise the dynamic LDS limit");
-        return ODIL_E_LAUNCH;
-      }
-      raised = true;
+    static SmallLdsRaised raised;
+    if (!small_raise_lds(reinterpret_cast<const void*>(&k_poisson_small_epochs<T, true>), raised)) {
+      set_error("poisson_small_epochs: cannot raise the dynamic LDS limit");
+      return ODIL_E_LAUNCH;
     }
-    hipLaunchKernelGGL((k_poisson_small_epochs<T, true>), dim3(1), dim3(threads), need, (hipStream_t)stream, x, m, v, g, u, fu,
-                       rhs, alphas, losses, norms, partials, a, make_h2<T>(hh));
+    hipLaunchKernelGGL((k_poisson_small_epochs<T, true>), dim3(1), dim3(threads), small_lds_bytes<T>(a), (hipStream_t)stream,
+                       x, m, v, g, u, fu, rhs, alphas, losses, norms, partials, a, h);
   } else {
     hipLaunchKernelGGL((k_poisson_small_epochs<T, false>), dim3(1), dim3(threads), 0, (hipStream_t)stream, x, m, v, g, u, fu,
-                       rhs, alphas, losses, norms, partials, a, make_h2<T>(hh));
+                       rhs, alphas, losses, norms, partials, a, h);
   }
   return check_launch("k_poisson_small_epochs");
+}
+
+// B members in one launch: workgroup b runs member b (k_poisson_small_epochs_batch).  Everything is checked before
+// anything is launched: a stride shorter than a member would let one workgroup write into its neighbour's state.
+template <typename T>
+static int poisson_small_epochs_batch(T* x, T* m, T* v, T* g, T* u, T* fu, const T* rhs, int nbatch, int64_t state_stride,
+                                      int64_t field_stride, const int64_t* shapes, int nlvl, int ndim, const T* h2,
+                                      const T* alphas, int64_t alpha_stride, int nepochs, T omb1, T omb2, T eps, T* losses,
+                                      T* norms, int64_t out_stride, double* partials, int64_t partials_stride, void* stream) {
+  const char* what = "poisson_small_epochs_batch";
+  if (!x || !m || !v || !g || !u || !fu || !rhs || !shapes || !h2 || !alphas || !losses || !norms || !partials) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1) {
+    set_error("%s: %d members (at least 1)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  SmallArgs<T> a;
+  H2<T> h;
+  if (int err = small_fill_args<T>(what, a, h, shapes, nlvl, ndim, h2, nepochs, omb1, omb2, eps)) return err;
+  if (state_stride < a.total || field_stride < a.lv[0].size) {
+    set_error("%s: member strides %lld / %lld are smaller than a member (%d unknowns, %d cells)", what,
+              (long long)state_stride, (long long)field_stride, a.total, a.lv[0].size);
+    return ODIL_E_INVAL;
+  }
+  if ((alpha_stride != 0 && alpha_stride < nepochs) || out_stride < nepochs) {
+    set_error("%s: member strides %lld (step sizes; 0 = shared) / %lld (losses, norms) are smaller than %d epochs", what,
+              (long long)alpha_stride, (long long)out_stride, nepochs);
+    return ODIL_E_INVAL;
+  }
+  if (partials_stride < (int64_t)a.grid * 5) {
+    set_error("%s: partials workspace of %lld doubles per member is too small (%d needed)", what,
+              (long long)partials_stride, a.grid * 5);
+    return ODIL_E_INVAL;
+  }
+  const SmallStrides st{state_stride, field_stride, alpha_stride, out_stride, partials_stride};
+  const int threads = small_threads(a);
+  if (a.lds) {
+    static SmallLdsRaised raised;
+    if (!small_raise_lds(reinterpret_cast<const void*>(&k_poisson_small_epochs_batch<T, true>), raised)) {
+      set_error("%s: cannot raise the dynamic LDS limit", what);
+      return ODIL_E_LAUNCH;
+    }
+    hipLaunchKernelGGL((k_poisson_small_epochs_batch<T, true>), dim3(nbatch), dim3(threads), small_lds_bytes<T>(a),
+                       (hipStream_t)stream, x, m, v, g, u, fu, rhs, alphas, losses, norms, partials, st, a, h);
+  } else {
+    hipLaunchKernelGGL((k_poisson_small_epochs_batch<T, false>), dim3(nbatch), dim3(threads), 0, (hipStream_t)stream, x, m, v,
+                       g, u, fu, rhs, alphas, losses, norms, partials, st, a, h);
+  }
+  return check_launch("k_poisson_small_epochs_batch");
 }
 
 }  // namespace odil
@@ -461,6 +580,11 @@ int odil_poisson_small_epochs_resident(const int64_t* shapes, int nlvl, int ndim
   const size_t state = elem_size == 8 ? small_state_bytes<double>((int)total, (int)n0) : small_state_bytes<float>((int)total, (int)n0);
   return state + (size_t)unit_grid(us) * 5 * sizeof(double) <= kSmallLdsBytes ? 1 : 0;
 }
+int64_t odil_poisson_small_epochs_partials(const int64_t* shapes, int ndim, int elem_size) {
+  if (!shapes || ndim < 1 || ndim > 2 || (elem_size != 4 && elem_size != 8) || shapes[ndim - 1] < 1) return 0;
+  const int per = kBlock * (16 / elem_size);
+  return (int64_t)unit_grid(make_unit_sched(ndim == 2 ? shapes[0] : 1, 1, (shapes[ndim - 1] + per - 1) / per)) * 5;
+}
 int odil_poisson_small_epochs_f64(double* x, double* m, double* v, double* g, double* u, double* fu, const double* rhs,
                                   const int64_t* shapes, int nlvl, int ndim, const double* h2, const double* alphas,
                                   int nepochs, double one_minus_b1, double one_minus_b2, double eps, double* losses,
@@ -474,5 +598,25 @@ int odil_poisson_small_epochs_f32(float* x, float* m, float* v, float* g, float*
                                   float* norms, double* partials, void* stream) {
   return poisson_small_epochs<float>(x, m, v, g, u, fu, rhs, shapes, nlvl, ndim, h2, alphas, nepochs, one_minus_b1,
                                      one_minus_b2, eps, losses, norms, partials, stream);
+}
+int odil_poisson_small_epochs_batch_f64(double* x, double* m, double* v, double* g, double* u, double* fu, const double* rhs,
+                                        int nbatch, int64_t state_stride, int64_t field_stride, const int64_t* shapes,
+                                        int nlvl, int ndim, const double* h2, const double* alphas, int64_t alpha_stride,
+                                        int nepochs, double one_minus_b1, double one_minus_b2, double eps, double* losses,
+                                        double* norms, int64_t out_stride, double* partials, int64_t partials_stride,
+                                        void* stream) {
+  return poisson_small_epochs_batch<double>(x, m, v, g, u, fu, rhs, nbatch, state_stride, field_stride, shapes, nlvl, ndim,
+                                            h2, alphas, alpha_stride, nepochs, one_minus_b1, one_minus_b2, eps, losses,
+                                            norms, out_stride, partials, partials_stride, stream);
+}
+int odil_poisson_small_epochs_batch_f32(float* x, float* m, float* v, float* g, float* u, float* fu, const float* rhs,
+                                        int nbatch, int64_t state_stride, int64_t field_stride, const int64_t* shapes,
+                                        int nlvl, int ndim, const float* h2, const float* alphas, int64_t alpha_stride,
+                                        int nepochs, float one_minus_b1, float one_minus_b2, float eps, float* losses,
+                                        float* norms, int64_t out_stride, double* partials, int64_t partials_stride,
+                                        void* stream) {
+  return poisson_small_epochs_batch<float>(x, m, v, g, u, fu, rhs, nbatch, state_stride, field_stride, shapes, nlvl, ndim,
+                                           h2, alphas, alpha_stride, nepochs, one_minus_b1, one_minus_b2, eps, losses, norms,
+                                           out_stride, partials, partials_stride, stream);
 }
 }  // extern "C"

@@ -178,15 +178,7 @@ class PoissonEvaluator:
     def small_plan(self, arrays, m, v):
         """The packed vectors (x, m, v, g) when `arrays` / m / v are the level slices of packed vectors in level order and
         the problem is small enough for one workgroup; None otherwise."""
-        from ._lib import i64, load
-
-        if self.ndim > 2 or self.nlvl > 12 or len(arrays) != self.nlvl or not self.small_max_cells:
-            return None
-        flat = [int(n) for shape in self.shapes for n in shape]
-        resident = bool(load().odil_poisson_small_epochs_resident(i64(flat), self.nlvl, self.ndim, 8 if self.dtype == torch.float64 else 4))
-        if not resident and not self.small_force and not (self.ndim == 1 and self.sizes[0] <= self.small_max_cells):
-            return None
-        if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(self.shapes, self.shapes[1:])):  # (as the kernel requires)
+        if len(arrays) != self.nlvl or small_refusal(self.shapes, self.dtype, self.small_force, self.small_max_cells):
             return None
 
         def packed(levels):
@@ -207,6 +199,86 @@ class PoissonEvaluator:
             self._small_u = torch.empty(sum(self.sizes), dtype=self.dtype, device=self.device)
         ops.poisson_small_epochs(heads[0], heads[1], heads[2], heads[3], self._small_u, self.fu, self.rhs, self.shapes,
                                  self.h2, alphas, omb1, omb2, eps, losses, norms)
+
+
+class PoissonEnsemble:
+    """B recognised Poisson problems of one shape side by side: packed [B, unknowns] state, moments, gradient and synthesis
+    scratch, [B, cells] residuals and right-hand sides, and whole Adam epochs of every member in ONE launch with one
+    workgroup per member (odil_poisson_small_epochs_batch).  Member b computes what `PoissonEvaluator.small_epochs`
+    computes for it alone, bit for bit: the kernel runs the same per-workgroup code on offset pointers."""
+
+    def __init__(self, evaluators):
+        from ._lib import i64, load
+
+        reason = self.refusal(evaluators)
+        if reason is not None:
+            raise ValueError("ensemble member {}: {}".format(*reason))
+        ev = evaluators[0]
+        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
+        self.nbatch, self.total, self.cells = len(evaluators), sum(ev.sizes), ev.sizes[0]
+        self.names = [e.names for e in evaluators]
+        packed = lambda: torch.zeros((self.nbatch, self.total), dtype=self.dtype, device=self.device)
+        self.x, self.m, self.v, self.g = packed(), packed(), packed(), packed()
+        self.u = torch.empty_like(self.x)
+        self.fu = torch.empty((self.nbatch, self.cells), dtype=self.dtype, device=self.device)
+        self.rhs = torch.stack([e.rhs.reshape(-1) for e in evaluators])
+        npart = int(load().odil_poisson_small_epochs_partials(i64(self.shapes[0]), ev.ndim, self.x.element_size()))
+        self.partials = torch.empty((self.nbatch, npart), dtype=torch.float64, device=self.device)
+
+    @staticmethod
+    def refusal(evaluators):
+        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
+        if not evaluators:
+            return 0, "an ensemble needs at least one member"
+        first = evaluators[0]
+        for b, ev in enumerate(evaluators):
+            if not isinstance(ev, PoissonEvaluator):
+                return b, "the operator is not the recognised Poisson stencil"
+            reason = small_refusal(ev.shapes, ev.dtype, ev.small_force, ev.small_max_cells)
+            if reason is not None:
+                return b, reason
+            for what in ("cshape", "shapes", "dtype", "device"):
+                if getattr(ev, what) != getattr(first, what):
+                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
+            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
+                return b, "grid spacing differs from member 0's"
+        return None
+
+    def levels(self, packed, member):
+        """The level arrays of one member: views of a row of a packed [B, unknowns] tensor."""
+        return [t.view(s) for t, s in zip(packed[member].split(self.sizes), self.shapes)]
+
+    def epochs(self, alphas, losses, norms, omb1, omb2, eps):
+        """losses.shape[1] Adam epochs of every member in ONE launch.  alphas: [B, E] step sizes, or [E] shared by all
+        members; the loss every epoch evaluated and its square root land in losses / norms [B, E] (device tensors)."""
+        ops.poisson_small_epochs_batch(self.x, self.m, self.v, self.g, self.u, self.fu, self.rhs, self.shapes, self.h2,
+                                       alphas, omb1, omb2, eps, losses, norms, self.partials)
+
+
+def small_refusal(shapes, dtype, force=None, max_cells=None):
+    """Why levels of these shapes are not run as whole epochs by one workgroup (odil_poisson_small_epochs), or None when
+    they are: the predicate of `PoissonEvaluator.small_plan`.  (Asks the library, not a device: usable before any state
+    exists.)  force / max_cells: `small_force` / `small_max_cells` of the evaluator, default the class's."""
+    from ._lib import i64, load
+
+    force = PoissonEvaluator.small_force if force is None else force
+    max_cells = PoissonEvaluator.small_max_cells if max_cells is None else max_cells
+    ndim, nlvl = len(shapes[0]), len(shapes)
+    if not max_cells:
+        return "the one-workgroup epochs are switched off (small_max_cells = 0)"
+    if ndim > 2:
+        return "{}-D grid: the one-workgroup epochs run 1-D and 2-D grids".format(ndim)
+    if nlvl > 12:
+        return "{} levels: the one-workgroup epochs take at most 12".format(nlvl)
+    flat = [int(n) for shape in shapes for n in shape]
+    resident = bool(load().odil_poisson_small_epochs_resident(i64(flat), nlvl, ndim, 8 if dtype == torch.float64 else 4))
+    cells = math.prod(shapes[0])
+    if not resident and not force and not (ndim == 1 and cells <= max_cells):
+        return "{} cells are above the limit of the one-workgroup epochs (state resident in LDS, or 1-D up to {} cells)".format(
+            cells, max_cells)
+    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):  # (as the kernel requires)
+        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
+    return None
 
 
 def _close(a, b, rtol):

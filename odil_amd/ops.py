@@ -510,6 +510,30 @@ def poisson_small_epochs(x, m, v, g, u, fu, rhs, shapes, h2, alphas, omb1, omb2,
     return losses
 
 
+def poisson_small_epochs_batch(x, m, v, g, u, fu, rhs, shapes, h2, alphas, omb1, omb2, eps, losses, norms, partials):
+    """losses.shape[1] whole epochs of B small multigrid Poisson problems in ONE launch, one workgroup per member
+    (include/odil_hip.h: odil_poisson_small_epochs_batch).  x, m, v, g, u: [B, unknowns]; fu, rhs: [B, cells]; losses,
+    norms: [B, E]; alphas: [B, E], or [E] shared by all members; partials: [B, n] float64 reduction workspace.  Rows are
+    contiguous; the row strides are the member strides."""
+    nb, nep = int(losses.shape[0]), int(losses.shape[1])
+    for t in (x, m, v, g, u):
+        assert t.dim() == 2 and t.shape[0] == nb and t.stride(1) == 1 and t.stride(0) == x.stride(0) and t.dtype == x.dtype
+    for t in (fu, rhs):
+        assert t.shape[0] == nb and t.is_contiguous() and t.dtype == x.dtype
+    assert norms.shape == losses.shape and norms.stride() == losses.stride() and losses.stride(1) == 1
+    assert alphas.shape[-1] == nep and alphas.stride(-1) == 1 and (alphas.dim() == 1 or alphas.shape[0] == nb)
+    assert partials.dtype == torch.float64 and partials.shape[0] == nb and partials.stride(1) == 1
+    flat = [int(n) for shape in shapes for n in shape]
+    h2a, h2p = host_reals(h2, x.dtype)
+    dev = lambda t: c_void_p(t.data_ptr()) if t.is_cuda else ptr(t)  # (ptr refuses host memory; strided rows are fine here)
+    call("poisson_small_epochs_batch", x.dtype, dev(x), dev(m), dev(v), dev(g), dev(u), ptr(fu), ptr(rhs), c_int(nb),
+         c_int64(x.stride(0)), c_int64(fu[0].numel()), i64(flat), c_int(len(shapes)), c_int(len(shapes[0])), h2p,
+         dev(alphas), c_int64(alphas.stride(0) if alphas.dim() == 2 else 0), c_int(nep), float(omb1), float(omb2),
+         float(eps), dev(losses), dev(norms), c_int64(losses.stride(0)), dev(partials), c_int64(partials.stride(0)),
+         stream_ptr())
+    return losses
+
+
 def jacobi2_supported(shape, dtype):
     """Arrays whose rows are whole 16-byte packs (odil_poisson_jacobi2, odil_stencil_var_smooth2)."""
     pack = 2 if dtype == torch.float64 else 4

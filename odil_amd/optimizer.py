@@ -155,6 +155,19 @@ class _EpochGraph:
         return self.pinfo_type(**self.pinfo) if self.pinfo_type else self.pinfo
 
 
+def _adam_step_size(lr, beta_1, beta_2, t):
+    """The step size of Adam's t-th step with the bias corrections folded in (reference optimizer.py:313-315); all four
+    in the working precision."""
+    return lr * np.sqrt(1 - beta_2**t) / (1 - beta_1**t)
+
+
+def _whole_epochs_stop(callback, epoch, last):
+    """The last epoch of the whole-epoch launch that starts at `epoch`: the callback's next active epoch (a callback that
+    cannot tell is called after every epoch, as the reference does, optimizer.py:331-336), at most 4096 epochs on."""
+    nxt = getattr(callback, "next_active", None) if callback is not None else (lambda e: last)
+    return min(last, max(epoch, nxt(epoch - 1)) if nxt is not None else epoch, epoch + 4095)
+
+
 class AdamNativeOptimizer(Optimizer):
     def __init__(self, dtype=None, mod=None, **kwargs):
         super().__init__(name="adamn", displayname="AdamNative", dtype=dtype)
@@ -205,8 +218,7 @@ class AdamNativeOptimizer(Optimizer):
             return pinfo
 
         def step_size(epoch):
-            t = npdt(epoch - epoch_start + steps_done)
-            return lr * np.sqrt(1 - beta_2**t) / (1 - beta_1**t)  # optimizer.py:313-315
+            return _adam_step_size(lr, beta_1, beta_2, npdt(epoch - epoch_start + steps_done))
 
         first, last = epoch_start + 1, epoch_start + epochs
         epoch = first
@@ -220,8 +232,7 @@ class AdamNativeOptimizer(Optimizer):
                                  device=xf.device)
             runner = small(x, mviews, vviews, table, 1 - beta_1, 1 - beta_2, epsilon)
         while runner is not None and epoch <= last:
-            nxt = getattr(callback, "next_active", None) if callback is not None else (lambda e: last)
-            stop = min(last, max(epoch, nxt(epoch - 1)) if nxt is not None else epoch, epoch + 4095)
+            stop = _whole_epochs_stop(callback, epoch, last)
             pinfo = runner(epoch - first, stop - epoch + 1)
             self.evals += stop - epoch + 1
             epoch = stop + 1
@@ -262,6 +273,44 @@ class AdamNativeOptimizer(Optimizer):
         optinfo.evals = self.evals
         optinfo.m, optinfo.v = mviews, vviews
         return x, optinfo
+
+
+    def run_ensemble(self, ensemble, epochs, callback=None, lr=1e-3, lrs=None, epoch_start=0, beta_1=0.9, beta_2=0.999,
+                     epsilon=1e-7, **kwargs):
+        """`run` for every member of a `fused.PoissonEnsemble` at once: the members' state is the ensemble's packed x (the
+        moments start at zero), each launch runs the epochs up to the callback's next active epoch -- the chunks of the
+        single whole-epoch runner above -- for ALL members.  lrs: one step size per member (default: `lr` for all, one
+        table of step sizes shared by the members).  callback(epoch, losses, norms): [B] device vectors, what each
+        member's epoch `epoch` evaluated.  optinfo.losses / .norms: the [B, epochs] tables of the whole run."""
+        tdtype = ensemble.dtype
+        npdt = np.float64 if tdtype == torch.float64 else np.float32
+        beta_1, beta_2 = npdt(beta_1), npdt(beta_2)
+        first, last = epoch_start + 1, epoch_start + epochs
+        steps = lambda rate: [_adam_step_size(npdt(rate), beta_1, beta_2, npdt(e - epoch_start)) for e in range(first, last + 1)]
+        if lrs is not None and len(lrs) != ensemble.nbatch:
+            raise ValueError("{} step sizes for {} members".format(len(lrs), ensemble.nbatch))
+        table = np.array(steps(lr) if lrs is None else [steps(rate) for rate in lrs], dtype=np.float64)
+        table = torch.tensor(table, dtype=tdtype, device=ensemble.device)  # [E] shared, or [B, E]
+        losses = torch.empty((ensemble.nbatch, max(epochs, 0)), dtype=tdtype, device=ensemble.device)
+        norms = torch.empty_like(losses)
+        ensemble.m.zero_()
+        ensemble.v.zero_()
+        epoch = first
+        while epoch <= last:
+            stop = _whole_epochs_stop(callback, epoch, last)
+            a, b = epoch - first, stop - first + 1
+            ensemble.epochs(table[..., a:b], losses[:, a:b], norms[:, a:b], 1 - beta_1, 1 - beta_2, epsilon)
+            self.evals += stop - epoch + 1
+            epoch = stop + 1
+            if callback is not None and stop > 0:
+                callback(stop, losses[:, b - 1], norms[:, b - 1])
+        optinfo = Namespace()
+        optinfo.epochs = epochs
+        optinfo.evals = self.evals
+        optinfo.m = [ensemble.levels(ensemble.m, k) for k in range(ensemble.nbatch)]
+        optinfo.v = [ensemble.levels(ensemble.v, k) for k in range(ensemble.nbatch)]
+        optinfo.losses, optinfo.norms = losses, norms
+        return [ensemble.levels(ensemble.x, k) for k in range(ensemble.nbatch)], optinfo
 
 
 class GdOptimizer(Optimizer):

@@ -463,6 +463,88 @@ def optimize_grad(args, optname, problem, state, callback=None, **kwargs):
     return arrays, optinfo
 
 
+def optimize_ensemble(args, problems, states, callback=None, lrs=None, **kwargs):
+    """Adam on B small Poisson problems AT ONCE: every launch runs whole epochs of all members, one workgroup per member
+    (fused.PoissonEnsemble; a sweep over right-hand sides, initial guesses or step sizes of a problem that alone fills
+    1 / 256 of the device).  Every member ends where `optimize_grad(args, "adam", problem, state)` would leave it, bit for bit.
+
+    args.optimizer must be 'adam' / 'adamn'; lrs: one step size per member (default args.lr for all).
+    callback(member, state, epoch, pinfo): called for every member at args.epoch_start (the initial evaluation) and at
+    the epochs its `next_active(epoch)` attribute names (the cadence of `make_callback`; without the attribute: every
+    epoch), pinfo as `optimize_grad` reports it, device scalars read lazily.  The callback reads the state; arrays it
+    swaps in are not picked up.
+    Members must be the recognised Poisson operator, share cshape, level shapes, spacing, dtype and device, and be
+    small enough for the one-workgroup epochs (fused.small_refusal); anything else raises ValueError naming the first
+    offending member -- structure (shapes, size) is checked for all members before any operator is probed.
+    Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors."""
+    from . import fused
+
+    optname = getattr(args, "optimizer", "adam")
+    if optname not in ("adam", "adamn"):
+        raise ValueError("optimize_ensemble runs Adam ('adam' / 'adamn'), not optimizer '{}'".format(optname))
+    if not problems or len(problems) != len(states):
+        raise ValueError("optimize_ensemble: {} problems with {} states".format(len(problems), len(states)))
+    if lrs is not None and len(lrs) != len(problems):
+        raise ValueError("optimize_ensemble: {} step sizes for {} members".format(len(lrs), len(problems)))
+
+    def refuse(member, reason):
+        raise ValueError("optimize_ensemble: member {}: {}".format(member, reason))
+
+    first = None
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        domain = problem.domain
+        if not state.initialized:
+            refuse(b, "uninitialized state, use `state = domain.init_state(state)`")
+        if len(state.fields) != 1:
+            refuse(b, "{} unknown fields (the Poisson problem has one)".format(len(state.fields)))
+        arrays = domain.arrays_from_state(state)
+        shapes = [tuple(int(n) for n in a.shape) for a in arrays]
+        if shapes[0] != tuple(domain.cshape):
+            refuse(b, "the unknown is not a cell-centred field of the domain")
+        reason = fused.small_refusal(shapes, arrays[0].dtype)
+        if reason is not None:
+            refuse(b, reason)
+        kind = dict(shapes=shapes, dtype=arrays[0].dtype, device=arrays[0].device,
+                    spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
+        first = first or kind
+        for what, label in (("shapes", "level shapes"), ("dtype", "dtype"), ("device", "device"), ("spacing", "grid spacing")):
+            if kind[what] != first[what]:
+                refuse(b, "{} {} differ from member 0's {}".format(label, kind[what], first[what]))
+    evaluators = []
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        problem.recognise(state)
+        if getattr(problem, "_fused", None) is None:
+            refuse(b, "the operator is not the recognised Poisson stencil")
+        evaluators.append(problem._fused)
+    reason = fused.PoissonEnsemble.refusal(evaluators)
+    if reason is not None:
+        refuse(*reason)
+    ensemble = fused.PoissonEnsemble(evaluators)
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        levels = ensemble.levels(ensemble.x, b)
+        for dst, src in zip(levels, problem.domain.arrays_from_state(state)):
+            dst.copy_(src)
+        problem.domain.arrays_to_state(levels, state)  # (views of the packed state: always the current iterate)
+
+    for src, dst in [("adam_epsilon", "epsilon"), ("adam_beta_1", "beta_1"), ("adam_beta_2", "beta_2")]:
+        if getattr(args, src, None) is not None:
+            kwargs[dst] = getattr(args, src)
+    opt = make_optimizer(optname, dtype=problems[0].domain.dtype, mod=problems[0].domain.mod)
+    printlog("Running {} optimizer on an ensemble of {} members".format(opt.displayname, len(problems)))
+
+    def callback_wrap(epoch, losses, norms):
+        for b, (problem, state) in enumerate(zip(problems, states)):
+            callback(b, state, epoch, _pinfo(losses[b], [losses[b]], ensemble.names[b], [norms[b]]))
+
+    if callback:
+        callback_wrap.next_active = getattr(callback, "next_active", None)
+        for b, (problem, state) in enumerate(zip(problems, states)):  # (the report of the start, as optimize_grad makes it)
+            loss, _, terms, names, norms = problem.eval_loss_grad_device(state)
+            callback(b, state, args.epoch_start, _pinfo(loss, terms, names, norms))
+    return opt.run_ensemble(ensemble, epochs=args.epochs - args.epoch_start, callback=callback_wrap if callback else None,
+                            lr=args.lr, lrs=lrs, epoch_start=args.epoch_start, **kwargs)
+
+
 def optimize(args, optname, problem, state, callback, **kwargs):
     if optname == "newton":
         return optimize_newton(args, problem, state, callback, **kwargs)
