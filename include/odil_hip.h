@@ -478,6 +478,54 @@ int odil_poisson_small_epochs_batch_f32(float* x, float* m, float* v, float* g, 
                                         float* norms, int64_t out_stride, double* partials, int64_t partials_stride,
                                         void* stream);
 
+/* An ENSEMBLE of nbatch Poisson problems of ANY 1-D / 2-D size as batched launches: every launch of a single problem's
+ * epoch (odil_mg_synth, odil_poisson_residual, odil_poisson_adjoint_adam, odil_mg_synth_adj_adam) covers all members.
+ * Member b is blockIdx.y = b of the stencil kernels and runs exactly the single kernel's walk on pointers offset by
+ * the member strides; its partial sums go to row b of the partials workspace and are summed in the single launch's
+ * order, so losses and states equal the single run's bit for bit.  Members never communicate.
+ *   u, rhs, fu, g, x, m, v   member b at b * <its stride> elements (stride >= cells of a member and a multiple of 16
+ *                            bytes: every member must start where member 0's 16-byte packs do)
+ *   partials                 partials_len doubles, member b's row at b * partials_stride
+ *                            (partials_stride >= odil_poisson_batch_partials(shape, ndim, elem_size))
+ *   loss                     [nbatch] mean(fu[b]^2)
+ *   alpha_dev                DEVICE step sizes, member b's at b * alpha_stride; alpha_stride = 0: one for all members
+ * The synthesis needs no entry point of its own: odil_mg_synth on [nbatch, *shape] arrays with loc '.' + loc.
+ * odil_mg_synth_adj_adam_batch is odil_mg_synth_adj_adam with factors 1 on contiguous [nbatch, *shape] level arrays,
+ * `shapes` being the nlvl x ndim extents of ONE member, all axes cell-centred.
+ * Refused before anything is launched: null pointers, nbatch outside 1 ... 65535, ndim outside 1 ... 2, a member stride
+ * below a member's size or off the 16-byte grid, a partials workspace shorter than nbatch rows, and a batch whose
+ * transfer levels would not run the kernel that a single member's levels run.  odil_mg_batch_levels_ok answers the
+ * last question for both transfer chains from the shapes alone (0: they do; else the reason is the error text), so
+ * that a host can refuse such a batch before its first launch. */
+int odil_mg_batch_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch);
+int64_t odil_poisson_batch_partials(const int64_t* shape, int ndim, int elem_size);
+int odil_poisson_residual_batch_f64(const double* u, const double* rhs, double* fu, int nbatch, int64_t u_stride,
+                                    int64_t rhs_stride, int64_t fu_stride, const int64_t* shape, int ndim,
+                                    const double* h2, double* partials, int64_t partials_stride, int64_t partials_len,
+                                    double* loss, void* stream);
+int odil_poisson_residual_batch_f32(const float* u, const float* rhs, float* fu, int nbatch, int64_t u_stride,
+                                    int64_t rhs_stride, int64_t fu_stride, const int64_t* shape, int ndim, const float* h2,
+                                    double* partials, int64_t partials_stride, int64_t partials_len, float* loss,
+                                    void* stream);
+int odil_poisson_adjoint_adam_batch_f64(const double* fu, double* gu, double* x, double* m, double* v, int nbatch,
+                                        int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                        int64_t v_stride, const int64_t* shape, int ndim, const double* h2, double scale,
+                                        double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                        int64_t alpha_stride, void* stream);
+int odil_poisson_adjoint_adam_batch_f32(const float* fu, float* gu, float* x, float* m, float* v, int nbatch,
+                                        int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                        int64_t v_stride, const int64_t* shape, int ndim, const float* h2, float scale,
+                                        float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
+                                        int64_t alpha_stride, void* stream);
+int odil_mg_synth_adj_adam_batch_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                     int nbatch, double* const* x, double* const* m, double* const* v, double one_minus_b1,
+                                     double one_minus_b2, double eps, const double* alpha_dev, int64_t alpha_stride,
+                                     void* stream);
+int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                     int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
+                                     float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
+                                     void* stream);
+
 /* TWO sweeps of odil_stencil_var_smooth in mode 0, with the weights omega1 and then omega2, in ONE pass: the coefficient arrays -- 7 of
  * the 10 words a sweep moves in 3-D -- are read once for both, the intermediate iterate stays on the CU.  out != x;
  * bit-identical to two calls of odil_stencil_var_smooth.  The last extent must be even.  zc_hint: planes per workgroup

@@ -40,6 +40,10 @@ _SIGNATURES = {
     "poisson_small_epochs": [_P, _P, _P, _P, _P, _P, _P, _I64P, c_int, c_int, _P, _P, c_int, _R, _R, _R, _P, _P, _P, _P],
     "poisson_small_epochs_batch": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, _I64P, c_int, c_int, _P, _P, c_int64,
                                    c_int, _R, _R, _R, _P, _P, c_int64, _P, c_int64, _P],
+    "poisson_residual_batch": [_P, _P, _P, c_int, c_int64, c_int64, c_int64, _I64P, c_int, _P, _P, c_int64, c_int64, _P, _P],
+    "poisson_adjoint_adam_batch": [_P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, _I64P, c_int, _P,
+                                   _R, _R, _R, _R, _P, c_int64, _P],
+    "mg_synth_adj_adam_batch": [_P, _P, _I64P, c_int, c_int, c_int, _P, _P, _P, _R, _R, _R, _P, c_int64, _P],
     "poisson_jacobi": [_P, _P, _P, _I64P, c_int, _P, _R, _P],
     "poisson_jacobi2": [_P, _P, _P, _I64P, c_int, _P, _R, _R, c_int, _P],
     "poisson_jacobi2_synth": [_P, _P, _P, _P, _I64P, _P, _R, _R, c_int, _P],
@@ -94,7 +98,8 @@ _SIGNATURES_F64 = {
 EXPORTED = [
     "odil_last_error", "odil_version", "odil_device_count", "odil_reduce_workspace_bytes", "odil_dots_workspace_bytes",
     "odil_dense_block_workspace_bytes", "odil_dense_block_wide_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy",
-    "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials",
+    "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials", "odil_poisson_batch_partials",
+    "odil_mg_batch_levels_ok",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
 ] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
@@ -131,6 +136,10 @@ def load():
     lib.odil_poisson_small_epochs_resident.argtypes = [_I64P, c_int, c_int, c_int]
     lib.odil_poisson_small_epochs_partials.restype = c_int64
     lib.odil_poisson_small_epochs_partials.argtypes = [_I64P, c_int, c_int]
+    lib.odil_poisson_batch_partials.restype = c_int64
+    lib.odil_poisson_batch_partials.argtypes = [_I64P, c_int, c_int]
+    lib.odil_mg_batch_levels_ok.restype = c_int
+    lib.odil_mg_batch_levels_ok.argtypes = [_I64P, c_int, c_int, c_int]
     for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)
         fn = getattr(lib, name)
         fn.restype = c_int

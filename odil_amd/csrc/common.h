@@ -267,15 +267,18 @@ struct AdamArgs {
   T* v;
   T alpha, omb1, omb2, eps;
   const T* alpha_dev;  // optional: step size read from device memory (hipGraph replay of an epoch)
+  // ensembles ([B, *shape] level arrays): member b reads alpha_dev[b * alpha_stride]; 0: one step size for all
+  int64_t alpha_stride;
+  int member_axis;  // canonical axis of the transfer kernels that counts the members (1 or 2) when alpha_stride != 0
 };
 
 #ifdef __HIPCC__
 template <typename T>
-__device__ inline void adam_update(T& x, T& m, T& v, T g, const AdamArgs<T>& a) {
+__device__ inline void adam_update(T& x, T& m, T& v, T g, const AdamArgs<T>& a, int64_t member = 0) {
   // reference optimizer.py:316-318
   m = m + (g - m) * a.omb1;
   v = v + (g * g - v) * a.omb2;
-  const T alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
+  const T alpha = a.alpha_dev ? a.alpha_dev[member * a.alpha_stride] : a.alpha;
   x = x - (m * alpha) / (sqrt(v) + a.eps);
 }
 #endif

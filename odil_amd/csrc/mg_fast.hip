@@ -272,7 +272,8 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_fast(const T* __restrict_
     if (gscaled) gscaled[ci] = scale * v;
     if (ad.x) {
       T xv = ad.x[ci], mv = ad.m[ci], vv = ad.v[ci];
-      adam_update<T>(xv, mv, vv, gscaled ? scale * v : v, ad);
+      // (ensembles: the member is the plane of a '.cc' batch, the row of a '.c' batch)
+      adam_update<T>(xv, mv, vv, gscaled ? scale * v : v, ad, ad.member_axis == 2 ? jy : p);
       ad.x[ci] = xv;
       ad.m[ci] = mv;
       ad.v[ci] = vv;
@@ -304,6 +305,12 @@ static bool fast_setup(FastArgs& f, const InterpArgs& a, bool& yc) {
   if (!sched_ok(planes, ytiles, xtiles)) return false;
   f.sched = make_sched(planes, ytiles, xtiles);
   return true;
+}
+
+bool interp_fast_serves(const InterpArgs& a) {
+  FastArgs f;
+  bool yc;
+  return fast_setup(f, a, yc);
 }
 
 template <typename T>

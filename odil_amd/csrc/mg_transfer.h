@@ -145,6 +145,9 @@ template <typename T>
 int interp_adj_fast(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& a, T scale, hipStream_t stream,
                     const AdamArgs<T>& ad);
 
+// Would the fast kernels take this layout (the predicate of both functions above, nothing launched)?
+bool interp_fast_serves(const InterpArgs& a);
+
 // z-marching variants (mg_march.hip): exactly 'ccc' (3-D, all cell-centred).
 template <typename T>
 int interp_add_march(const T* coarse, const T* add, T* fine, const InterpArgs& a, T cscale, T ascale,

@@ -483,6 +483,13 @@ static int interp_adj(const T* gfine, T* gcoarse, T* gscaled, const int64_t* csh
     set_error("interp_adj: null pointer");
     return ODIL_E_INVAL;
   }
+  if (ad.x && ad.alpha_stride) {
+    // an ensemble with a step size per member: the fast kernel is the one that reads it (odil_mg_synth_adj_adam_batch
+    // has checked that it serves every level; never another arithmetic path, never a launch without the stride)
+    if (int r = interp_adj_fast<T>(gfine, gcoarse, gscaled, a, scale, (hipStream_t)stream, ad)) return r < 0 ? r : 0;
+    set_error("interp_adj: this layout has no kernel that reads a step size per member");
+    return ODIL_E_INVAL;
+  }
   if (a.loc[0] == kNode && a.loc[1] == kNone && a.loc[2] == kNone && a.loc[3] == kNone && a.cut_axis < 0) {
     const int64_t vol = a.cn[1] * a.cn[2] * a.cn[3];
     constexpr int NV = 16 / sizeof(T);
@@ -646,7 +653,7 @@ template <typename T>
 static int mg_synth_adj(const T* gu, T* const* grads, const T* factors, T* const* work, const int64_t* shapes,
                         int nlvl, int ndim, const char* loc, void* stream, T* const* ax = nullptr,
                         T* const* am = nullptr, T* const* av = nullptr, T alpha = T(0), T omb1 = T(0), T omb2 = T(0),
-                        T eps = T(0), const T* alpha_dev = nullptr) {
+                        T eps = T(0), const T* alpha_dev = nullptr, int64_t alpha_stride = 0, int member_axis = 0) {
   if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
   if (!gu || !grads) {
     set_error("mg_synth_adj: null pointer");
@@ -676,7 +683,7 @@ static int mg_synth_adj(const T* gu, T* const* grads, const T* factors, T* const
       unscaled = work[l];
       scaled = grads[l];
     }
-    AdamArgs<T> ad{nullptr, nullptr, nullptr, alpha, omb1, omb2, eps, alpha_dev};
+    AdamArgs<T> ad{nullptr, nullptr, nullptr, alpha, omb1, omb2, eps, alpha_dev, alpha_stride, member_axis};
     if (ax && ax[l]) {
       ad.x = ax[l];
       ad.m = am[l];
@@ -686,6 +693,73 @@ static int mg_synth_adj(const T* gu, T* const* grads, const T* factors, T* const
     gfine = unscaled;
   }
   return 0;
+}
+
+// Do all transfer levels of a batch of nbatch members ([nbatch, *shape] arrays, layout '.' + 'c' * ndim) run the fast
+// kernel that the levels of ONE member run?  Fills bshapes with the nlvl x (ndim + 1) batched extents.  Nothing is launched.
+static int batch_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, int nbatch, int64_t* bshapes) {
+  if (ndim < 1 || ndim > 2 || !shapes) {
+    set_error("%s: ndim %d (the ensemble runs 1-D and 2-D members) or null shapes", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1 ... 65535)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (nlvl < 2 || nlvl > ODIL_MAX_LEVELS) {
+    set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
+    return ODIL_E_INVAL;
+  }
+  const char* loc1 = ndim == 1 ? "c" : "cc";
+  const char* locb = ndim == 1 ? ".c" : ".cc";
+  for (int l = 0; l < nlvl; ++l) {
+    bshapes[l * (ndim + 1)] = nbatch;
+    for (int d = 0; d < ndim; ++d) bshapes[l * (ndim + 1) + 1 + d] = shapes[l * ndim + d];
+  }
+  if (int e = check_levels(shapes, nlvl, ndim, loc1)) return e;
+  for (int l = 1; l < nlvl; ++l) {
+    InterpArgs one, all;
+    if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc1)) return e;
+    if (int e = fill_interp_args(all, bshapes + l * (ndim + 1), ndim + 1, locb)) return e;
+    if (!interp_fast_serves(one) || !interp_fast_serves(all)) {
+      set_error("%s: level %d of %d members would not run the transfer kernel one member runs", what, l, nbatch);
+      return ODIL_E_INVAL;
+    }
+  }
+  return 0;
+}
+
+// mg_synth_adj with the updates, on [B, *shape] level arrays of B members (layout '.' + loc, all axes of a member
+// cell-centred): what B calls of the single form launch per level, in one launch per level.  Refuses, before anything
+// is launched, a batch whose levels would not all run the fast kernel a single member's levels run.
+template <typename T>
+static int mg_synth_adj_adam_batch(const T* gu, T* const* grads, const int64_t* shapes, int nlvl, int ndim, int nbatch,
+                                   T* const* ax, T* const* am, T* const* av, T omb1, T omb2, T eps, const T* alpha_dev,
+                                   int64_t alpha_stride, void* stream) {
+  static const char* what = "mg_synth_adj_adam_batch";
+  if (ndim < 1 || ndim > 2) {
+    set_error("%s: ndim %d (the ensemble runs 1-D and 2-D members)", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (!gu || !grads || !shapes || !ax || !am || !av || !alpha_dev) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (alpha_stride < 0) {
+    set_error("%s: step-size stride %lld is negative", what, (long long)alpha_stride);
+    return ODIL_E_INVAL;
+  }
+  int64_t bshapes[ODIL_MAX_LEVELS * 3];
+  if (int e = batch_levels_check(what, shapes, nlvl, ndim, nbatch, bshapes)) return e;
+  const char* locb = ndim == 1 ? ".c" : ".cc";
+  for (int l = 1; l < nlvl; ++l)
+    if (!grads[l] || !ax[l] || !am[l] || !av[l]) {
+      set_error("%s: null level array (level %d)", what, l);
+      return ODIL_E_INVAL;
+    }
+  // the member axis of the canonical 4-D view: 1 for '.cc' (a plane per member), 2 for '.c' (a row per member)
+  return mg_synth_adj<T>(gu, grads, nullptr, nullptr, bshapes, nlvl, ndim + 1, locb, stream, ax, am, av, T(0), omb1, omb2,
+                         eps, alpha_dev, alpha_stride, ndim == 2 ? 1 : 2);
 }
 
 }  // namespace odil
@@ -793,6 +867,24 @@ int odil_mg_synth_adj_adam_f32(const float* gu, float* const* grads, const float
                                float eps, const float* alpha_dev, void* stream) {
   return mg_synth_adj<float>(gu, grads, factors, work, shapes, nlvl, ndim, loc, stream, x, m, v, alpha, one_minus_b1,
                              one_minus_b2, eps, alpha_dev);
+}
+int odil_mg_batch_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch) {
+  int64_t bshapes[ODIL_MAX_LEVELS * 3];
+  return batch_levels_check("mg_batch_levels", shapes, nlvl, ndim, nbatch, bshapes);
+}
+int odil_mg_synth_adj_adam_batch_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                     int nbatch, double* const* x, double* const* m, double* const* v, double one_minus_b1,
+                                     double one_minus_b2, double eps, const double* alpha_dev, int64_t alpha_stride,
+                                     void* stream) {
+  return mg_synth_adj_adam_batch<double>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2, eps,
+                                         alpha_dev, alpha_stride, stream);
+}
+int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                     int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
+                                     float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
+                                     void* stream) {
+  return mg_synth_adj_adam_batch<float>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2, eps,
+                                        alpha_dev, alpha_stride, stream);
 }
 
 }  // extern "C"

@@ -25,9 +25,8 @@ struct StencilArgs {
 // the marched array is loaded once by its owner (+ once per y-neighbour, an L2 hit inside
 // the XCD).  Loads of the next plane are issued before the current plane is consumed.
 template <typename T, bool FULL>
-__global__ __launch_bounds__(kBlock) void k_poisson_residual(const T* __restrict__ u, const T* __restrict__ rhs,
-                                                            T* __restrict__ fu, StencilArgs a, H2<T> h,
-                                                            double* __restrict__ partials) {
+__device__ inline void poisson_residual_unit(const T* __restrict__ u, const T* __restrict__ rhs, T* __restrict__ fu,
+                                             const StencilArgs& a, const H2<T>& h, double* __restrict__ partials) {
   constexpr int V = VecOf<T>::N;
   const int64_t Z = a.n[0], Y = a.n[1], X = a.n[2];
   const int64_t sy = X, sz = Y * X;
@@ -105,6 +104,29 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual(const T* __restrict
   }
   const double total = block_sum(local);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+template <typename T, bool FULL>
+__global__ __launch_bounds__(kBlock) void k_poisson_residual(const T* __restrict__ u, const T* __restrict__ rhs,
+                                                            T* __restrict__ fu, StencilArgs a, H2<T> h,
+                                                            double* __restrict__ partials) {
+  poisson_residual_unit<T, FULL>(u, rhs, fu, a, h, partials);
+}
+
+// An ensemble of B members of one shape: member blockIdx.y runs the walk above on its own arrays and writes its partial
+// sums to its own row of the [B, grid] workspace, so its loss is summed in the order of its single launch.
+struct BatchStrides {
+  int64_t s[5];  // elements between members: (u, rhs, fu) of the residual, (fu, g, x, m, v) of the adjoint
+};
+
+template <typename T, bool FULL>
+__global__ __launch_bounds__(kBlock) void k_poisson_residual_batch(const T* __restrict__ u, const T* __restrict__ rhs,
+                                                                  T* __restrict__ fu, BatchStrides st, StencilArgs a,
+                                                                  H2<T> h, double* __restrict__ partials,
+                                                                  int64_t partials_stride) {
+  const int64_t b = blockIdx.y;
+  poisson_residual_unit<T, FULL>(u + b * st.s[0], rhs + b * st.s[1], fu + b * st.s[2], a, h,
+                                 partials + b * partials_stride);
 }
 
 // One damped-Jacobi sweep of the same operator, x_out = x - omega (A x - b) / diag(A), in ONE pass
@@ -303,8 +325,8 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual_restrict(const T* _
 }
 
 template <typename T, bool FULL>
-__global__ __launch_bounds__(kBlock) void k_poisson_adjoint(const T* __restrict__ fu, T* __restrict__ gu,
-                                                           StencilArgs a, H2<T> h, T scale, AdamArgs<T> ad) {
+__device__ inline void poisson_adjoint_unit(const T* __restrict__ fu, T* __restrict__ gu, const StencilArgs& a,
+                                            const H2<T>& h, T scale, const AdamArgs<T>& ad, int64_t member) {
   constexpr int V = VecOf<T>::N;
   const int64_t Z = a.n[0], Y = a.n[1], X = a.n[2];
   const int64_t sy = X, sz = Y * X;
@@ -364,7 +386,7 @@ __global__ __launch_bounds__(kBlock) void k_poisson_adjoint(const T* __restrict_
       load_vec<T, V, FULL, true>(ad.m + pz + c_off, valid, mv);
       load_vec<T, V, FULL, true>(ad.v + pz + c_off, valid, vv);
 #pragma unroll
-      for (int i = 0; i < V; ++i) adam_update<T>(xv[i], mv[i], vv[i], out[i], ad);
+      for (int i = 0; i < V; ++i) adam_update<T>(xv[i], mv[i], vv[i], out[i], ad, member);
       store_vec<T, V, FULL, true>(ad.x + pz + c_off, valid, xv);
       store_vec<T, V, FULL, true>(ad.m + pz + c_off, valid, mv);
       store_vec<T, V, FULL, true>(ad.v + pz + c_off, valid, vv);
@@ -375,6 +397,24 @@ __global__ __launch_bounds__(kBlock) void k_poisson_adjoint(const T* __restrict_
       fc[i] = fp[i];
     }
   }
+}
+
+template <typename T, bool FULL>
+__global__ __launch_bounds__(kBlock) void k_poisson_adjoint(const T* __restrict__ fu, T* __restrict__ gu,
+                                                           StencilArgs a, H2<T> h, T scale, AdamArgs<T> ad) {
+  poisson_adjoint_unit<T, FULL>(fu, gu, a, h, scale, ad, 0);
+}
+
+// The ensemble form: member blockIdx.y on its own arrays, its step size at alpha_dev[member * alpha_stride].
+template <typename T, bool FULL>
+__global__ __launch_bounds__(kBlock) void k_poisson_adjoint_batch(const T* __restrict__ fu, T* __restrict__ gu,
+                                                                 BatchStrides st, StencilArgs a, H2<T> h, T scale,
+                                                                 AdamArgs<T> ad) {
+  const int64_t b = blockIdx.y;
+  ad.x += b * st.s[2];
+  ad.m += b * st.s[3];
+  ad.v += b * st.s[4];
+  poisson_adjoint_unit<T, FULL>(fu + b * st.s[0], gu ? gu + b * st.s[1] : nullptr, a, h, scale, ad, b);
 }
 
 template <typename T>
@@ -572,6 +612,107 @@ static int poisson_adjoint(const T* fu, T* gu, const int64_t* shape, int ndim, c
   return check_launch("k_poisson_adjoint");
 }
 
+// What the batched launchers refuse before anything is launched (the ensemble forms of residual and adjoint).
+template <typename T>
+static int batch_args(const char* what, StencilArgs& a, T h[3], const int64_t* shape, int ndim, const T* h2, int nbatch,
+                      const int64_t* strides, int nstrides) {
+  if (ndim < 1 || ndim > 2) {
+    set_error("%s: ndim %d (the ensemble runs 1-D and 2-D members)", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (!shape || !h2) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1 ... 65535, one grid row each)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (int e = fill_args<T>(a, shape, ndim, h2, h)) return e;
+  const int64_t cells = a.n[0] * a.n[1] * a.n[2];
+  for (int k = 0; k < nstrides; ++k) {
+    if (strides[k] < cells) {
+      set_error("%s: member stride %lld is smaller than a member (%lld cells)", what, (long long)strides[k],
+                (long long)cells);
+      return ODIL_E_INVAL;
+    }
+    // (the 16 B accesses of the packed rows assume member 0's alignment for every member)
+    if ((strides[k] * (int64_t)sizeof(T)) % 16 != 0) {
+      set_error("%s: member stride %lld is not a multiple of 16 bytes", what, (long long)strides[k]);
+      return ODIL_E_INVAL;
+    }
+  }
+  return 0;
+}
+
+template <typename T>
+static int poisson_residual_batch(const T* u, const T* rhs, T* fu, int nbatch, int64_t u_stride, int64_t rhs_stride,
+                                  int64_t fu_stride, const int64_t* shape, int ndim, const T* h2, double* partials,
+                                  int64_t partials_stride, int64_t partials_len, T* loss, void* stream) {
+  static const char* what = "poisson_residual_batch";
+  if (!u || !rhs || !fu || !partials || !loss) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  StencilArgs a;
+  T h[3];
+  BatchStrides st = {{u_stride, rhs_stride, fu_stride, 0, 0}};
+  if (int e = batch_args<T>(what, a, h, shape, ndim, h2, nbatch, st.s, 3)) return e;
+  a.loss_z0 = 0;
+  a.loss_z1 = a.n[0];
+  const int grid = unit_grid(a.usched);
+  if (partials_stride < grid || partials_stride >= ((int64_t)1 << 31)) {
+    set_error("%s: partials workspace too small: rows of %lld doubles, a member needs %d", what,
+              (long long)partials_stride, grid);
+    return ODIL_E_INVAL;
+  }
+  if (partials_len < (int64_t)(nbatch - 1) * partials_stride + grid) {
+    set_error("%s: partials workspace too small: %lld doubles are fewer than %d rows of %lld", what,
+              (long long)partials_len, nbatch, (long long)partials_stride);
+    return ODIL_E_INVAL;
+  }
+  if (a.n[2] % VecOf<T>::N == 0)
+    hipLaunchKernelGGL((k_poisson_residual_batch<T, true>), dim3(grid, nbatch), dim3(kBlock), 0, (hipStream_t)stream, u,
+                       rhs, fu, st, a, make_h2<T>(h), partials, partials_stride);
+  else
+    hipLaunchKernelGGL((k_poisson_residual_batch<T, false>), dim3(grid, nbatch), dim3(kBlock), 0, (hipStream_t)stream,
+                       u, rhs, fu, st, a, make_h2<T>(h), partials, partials_stride);
+  if (int e = check_launch("k_poisson_residual_batch")) return e;
+  return launch_final_reduce<T>(partials, grid, (int)partials_stride, nbatch, (double)(a.n[0] * a.n[1] * a.n[2]), loss,
+                                (hipStream_t)stream);
+}
+
+template <typename T>
+static int poisson_adjoint_adam_batch(const T* fu, T* gu, T* x, T* m, T* v, int nbatch, int64_t fu_stride,
+                                      int64_t g_stride, int64_t x_stride, int64_t m_stride, int64_t v_stride,
+                                      const int64_t* shape, int ndim, const T* h2, T scale, T omb1, T omb2, T eps,
+                                      const T* alpha_dev, int64_t alpha_stride, void* stream) {
+  static const char* what = "poisson_adjoint_adam_batch";
+  if (!fu || !x || !m || !v || !alpha_dev) {  // (gu == NULL: the gradient is consumed by the update, not stored)
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (alpha_stride < 0) {
+    set_error("%s: step-size stride %lld is negative", what, (long long)alpha_stride);
+    return ODIL_E_INVAL;
+  }
+  StencilArgs a;
+  T h[3];
+  BatchStrides st = {{fu_stride, g_stride, x_stride, m_stride, v_stride}};
+  if (!gu) st.s[1] = fu_stride;  // (not used)
+  if (int e = batch_args<T>(what, a, h, shape, ndim, h2, nbatch, st.s, 5)) return e;
+  a.loss_z0 = a.loss_z1 = 0;
+  const AdamArgs<T> ad{x, m, v, T(0), omb1, omb2, eps, alpha_dev, alpha_stride, 0};
+  const dim3 grid(unit_grid(a.usched), nbatch);
+  if (a.n[2] % VecOf<T>::N == 0)
+    hipLaunchKernelGGL((k_poisson_adjoint_batch<T, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, fu, gu, st, a,
+                       make_h2<T>(h), scale, ad);
+  else
+    hipLaunchKernelGGL((k_poisson_adjoint_batch<T, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, fu, gu, st, a,
+                       make_h2<T>(h), scale, ad);
+  return check_launch("k_poisson_adjoint_batch");
+}
+
 template <typename T>
 static int poisson_jacobi(const T* u, const T* rhs, T* uout, const int64_t* shape, int ndim, const T* h2, T omega,
                           void* stream) {
@@ -748,6 +889,48 @@ int odil_poisson_adjoint_adam_f32(const float* fu, float* gu, float* x, float* m
   }
   return poisson_adjoint<float>(fu, gu, shape, ndim, h2, scale, stream,
                                 AdamArgs<float>{x, m, v, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev});
+}
+int64_t odil_poisson_batch_partials(const int64_t* shape, int ndim, int elem_size) {
+  if (!shape || ndim < 1 || ndim > 2 || (elem_size != 4 && elem_size != 8)) return 0;
+  StencilArgs a;
+  const double one[2] = {1.0, 1.0};
+  const float onef[2] = {1.f, 1.f};
+  double h[3];
+  float hf[3];
+  const int e = elem_size == 8 ? fill_args<double>(a, shape, ndim, one, h) : fill_args<float>(a, shape, ndim, onef, hf);
+  return e ? 0 : unit_grid(a.usched);
+}
+int odil_poisson_residual_batch_f64(const double* u, const double* rhs, double* fu, int nbatch, int64_t u_stride,
+                                    int64_t rhs_stride, int64_t fu_stride, const int64_t* shape, int ndim,
+                                    const double* h2, double* partials, int64_t partials_stride, int64_t partials_len,
+                                    double* loss, void* stream) {
+  return poisson_residual_batch<double>(u, rhs, fu, nbatch, u_stride, rhs_stride, fu_stride, shape, ndim, h2, partials,
+                                        partials_stride, partials_len, loss, stream);
+}
+int odil_poisson_residual_batch_f32(const float* u, const float* rhs, float* fu, int nbatch, int64_t u_stride,
+                                    int64_t rhs_stride, int64_t fu_stride, const int64_t* shape, int ndim, const float* h2,
+                                    double* partials, int64_t partials_stride, int64_t partials_len, float* loss,
+                                    void* stream) {
+  return poisson_residual_batch<float>(u, rhs, fu, nbatch, u_stride, rhs_stride, fu_stride, shape, ndim, h2, partials,
+                                       partials_stride, partials_len, loss, stream);
+}
+int odil_poisson_adjoint_adam_batch_f64(const double* fu, double* gu, double* x, double* m, double* v, int nbatch,
+                                        int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                        int64_t v_stride, const int64_t* shape, int ndim, const double* h2, double scale,
+                                        double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                        int64_t alpha_stride, void* stream) {
+  return poisson_adjoint_adam_batch<double>(fu, gu, x, m, v, nbatch, fu_stride, g_stride, x_stride, m_stride, v_stride,
+                                            shape, ndim, h2, scale, one_minus_b1, one_minus_b2, eps, alpha_dev,
+                                            alpha_stride, stream);
+}
+int odil_poisson_adjoint_adam_batch_f32(const float* fu, float* gu, float* x, float* m, float* v, int nbatch,
+                                        int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                        int64_t v_stride, const int64_t* shape, int ndim, const float* h2, float scale,
+                                        float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
+                                        int64_t alpha_stride, void* stream) {
+  return poisson_adjoint_adam_batch<float>(fu, gu, x, m, v, nbatch, fu_stride, g_stride, x_stride, m_stride, v_stride,
+                                           shape, ndim, h2, scale, one_minus_b1, one_minus_b2, eps, alpha_dev,
+                                           alpha_stride, stream);
 }
 int odil_poisson_jacobi_f64(const double* u, const double* rhs, double* uout, const int64_t* shape, int ndim,
                             const double* h2, double omega, void* stream) {

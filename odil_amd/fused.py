@@ -255,6 +255,126 @@ class PoissonEnsemble:
                                        alphas, omb1, omb2, eps, losses, norms, self.partials)
 
 
+class PoissonLaunchEnsemble:
+    """B recognised Poisson problems of one shape and ANY 1-D / 2-D size side by side, as batched launches: an epoch is the
+    launches of `PoissonEvaluator.loss_grad_arrays(adam=...)` for a 2-D problem -- synthesis, residual + loss, adjoint +
+    update of level 0, transposed prolongations + updates of the other levels -- each covering all B members
+    (odil_mg_synth on [B, *shape] arrays, odil_poisson_residual_batch, odil_poisson_adjoint_adam_batch,
+    odil_mg_synth_adj_adam_batch).  Level-major storage: x, m, v, g are lists of one [B, *shape] tensor per level.  Member
+    b computes what its single run computes, bit for bit: the same per-thread arithmetic, the same summation order.
+    pad: extra elements between the members of the arrays that only the stencil kernels touch (fu, rhs, m[0], v[0])."""
+
+    def __init__(self, evaluators, pad=0):
+        reason = self.refusal(evaluators)
+        if reason is not None:
+            raise ValueError("ensemble member {}: {}".format(*reason))
+        ev = evaluators[0]
+        # (both transfer chains of the batch must run the kernel a single member runs: asked before the first launch)
+        reason = _levels_refusal(ev.shapes, len(evaluators))
+        if reason is not None:
+            raise ValueError("ensemble of {} members: {}".format(len(evaluators), reason))
+        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
+        self.cshape, self.ndim, self.loc, self.scale = ev.cshape, ev.ndim, "." + ev.loc, float(ev.scale)
+        self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
+        self.names = [e.names for e in evaluators]
+        nb, kw = self.nbatch, dict(dtype=self.dtype, device=self.device)
+
+        def members(shape, wide=0):
+            cells = math.prod(shape)
+            base = torch.zeros(nb * (cells + wide), **kw)
+            strides = [math.prod(shape[k + 1:]) for k in range(len(shape))]
+            return base.as_strided((nb,) + tuple(shape), [cells + wide] + strides)
+
+        level = lambda wide0=0: [members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
+        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
+        self.u, self.fu, self.rhs = members(self.cshape), members(self.cshape, pad), members(self.cshape, pad)
+        self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
+        self.work = ([None] + [members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
+        npart = ops.poisson_batch_partials(self.cshape, self.dtype)
+        self.partials = torch.empty((nb, npart), dtype=torch.float64, device=self.device)
+        self.loss, self.norm = torch.zeros(nb, **kw), torch.zeros(nb, **kw)
+
+    @staticmethod
+    def refusal(evaluators):
+        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
+        if not evaluators:
+            return 0, "an ensemble needs at least one member"
+        first = evaluators[0]
+        for b, ev in enumerate(evaluators):
+            if not isinstance(ev, PoissonEvaluator):
+                return b, "the operator is not the recognised Poisson stencil"
+            reason = launches_refusal(ev.shapes, ev.dtype)
+            if reason is not None:
+                return b, reason
+            for what in ("cshape", "shapes", "dtype", "device"):
+                if getattr(ev, what) != getattr(first, what):
+                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
+            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
+                return b, "grid spacing differs from member 0's"
+        return None
+
+    def levels(self, packed, member):
+        """The level arrays of one member: views of the [B, *shape] level tensors."""
+        return [t[member] for t in packed]
+
+    def epoch(self, alphas, omb1, omb2, eps):
+        """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
+        losses the epoch evaluated (before its update) land in self.loss."""
+        ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+        ops.poisson_residual_batch(self.u, self.rhs, self.h2, self.fu, self.loss, self.partials)
+        ops.poisson_adjoint_adam_batch(self.fu, self.h2, self.scale, self.g[0], self.x[0], self.m[0], self.v[0], alphas, omb1,
+                                       omb2, eps)
+        ops.mg_synth_adj_adam_batch(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+
+    def epochs(self, alphas, losses, norms, omb1, omb2, eps):
+        """losses.shape[1] epochs (the interface of PoissonEnsemble.epochs).  alphas: [B, E], or [E] shared by all members."""
+        for e in range(losses.shape[1]):
+            self.epoch(alphas[..., e].contiguous().view(-1), omb1, omb2, eps)
+            torch.sqrt(self.loss, out=self.norm)
+            losses[:, e].copy_(self.loss)
+            norms[:, e].copy_(self.norm)
+
+
+def _levels_refusal(shapes, nbatch):
+    """The library's answer (odil_mg_batch_levels_ok): why the transfer levels of `nbatch` members of these level shapes
+    would not run the kernels one member's run (level count, extents, refinement, schedule limits), or None."""
+    from ._lib import i64, load
+
+    lib = load()
+    flat = [int(n) for shape in shapes for n in shape]
+    if lib.odil_mg_batch_levels_ok(i64(flat), len(shapes), len(shapes[0]), int(nbatch)) == 0:
+        return None
+    return lib.odil_last_error().decode()
+
+
+def launches_refusal(shapes, dtype=None):
+    """Why levels of these shapes are not run as batched launches (PoissonLaunchEnsemble), or None when they are.  From the
+    shapes (and, for the alignment of the members, the dtype) alone; the limits of the kernels are the library's."""
+    ndim, nlvl = len(shapes[0]), len(shapes)
+    if ndim > 2:
+        return ("{}-D grid: the batched launches run 1-D and 2-D grids (a 3-D run fuses the synthesis into its residual "
+                "and the first transpose into its adjoint)".format(ndim))
+    if nlvl < 2:
+        return "1 level: the batched launches need a multigrid field of at least 2 levels"
+    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):
+        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
+    if any(n < 2 for n in shapes[-1]):
+        return "levels {}: every extent must be at least 2".format([tuple(s) for s in shapes])
+    if dtype is not None and (math.prod(shapes[0]) * (8 if dtype == torch.float64 else 4)) % 16:
+        return "a member of {} cells is not a multiple of 16 bytes (members lie back to back)".format(math.prod(shapes[0]))
+    return _levels_refusal(shapes, 1)
+
+
+def ensemble_form(form, shapes, dtype):
+    """'workgroup' or 'launches': the form `util.optimize_ensemble(form=...)` runs members of these level shapes in.  A
+    function of shapes and dtype alone; 'auto' takes the one-workgroup epochs when `small_refusal` admits the members."""
+    if form not in ("workgroup", "launches", "auto"):
+        raise ValueError("optimize_ensemble: form '{}' is none of 'workgroup', 'launches', 'auto'".format(form))
+    if form == "auto":
+        return "workgroup" if small_refusal(shapes, dtype) is None else "launches"
+    return form
+
+
 def small_refusal(shapes, dtype, force=None, max_cells=None):
     """Why levels of these shapes are not run as whole epochs by one workgroup (odil_poisson_small_epochs), or None when
     they are: the predicate of `PoissonEvaluator.small_plan`.  (Asks the library, not a device: usable before any state

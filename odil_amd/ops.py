@@ -534,6 +534,66 @@ def poisson_small_epochs_batch(x, m, v, g, u, fu, rhs, shapes, h2, alphas, omb1,
     return losses
 
 
+def poisson_batch_partials(shape, dtype):
+    """Doubles of reduction workspace one member of `poisson_residual_batch` needs (0: not a 1-D / 2-D shape it takes)."""
+    return int(_lib.load().odil_poisson_batch_partials(i64(shape), c_int(len(shape)), 8 if dtype == torch.float64 else 4))
+
+
+def _members(t, nb, shape):
+    """(device pointer, member stride in elements) of a [B, *shape] tensor whose members are contiguous."""
+    assert t.shape[0] == nb and tuple(t.shape[1:]) == tuple(shape) and t[0].is_contiguous(), (t.shape, t.stride())
+    if not t.is_cuda:
+        raise _lib.OdilHipError("tensor is on '{}': the HIP kernels need device memory (no CPU fallback)".format(t.device))
+    return c_void_p(t.data_ptr()), c_int64(t.stride(0) if nb > 1 else max(t.stride(0), t[0].numel()))
+
+
+def poisson_residual_batch(u, rhs, h2, fu, loss, partials):
+    """fu[b] = Lap(u[b]) - rhs[b] and loss[b] = mean(fu[b]**2) for the B members of [B, *shape] arrays in ONE launch (+ one
+    reduction launch); member b computes what `poisson_residual` computes for it alone, bit for bit.  The leading
+    strides are the member strides; partials: [B, >= poisson_batch_partials] float64; loss: [B] contiguous."""
+    nb, shape = int(u.shape[0]), tuple(u.shape[1:])
+    assert u.dtype == rhs.dtype == fu.dtype == loss.dtype and loss.shape == (nb,)
+    assert partials.dtype == torch.float64 and partials.dim() == 2 and partials.shape[0] == nb and partials.stride(1) == 1
+    (up, us), (rp, rs), (fp, fs) = _members(u, nb, shape), _members(rhs, nb, shape), _members(fu, nb, shape)
+    h2a, h2p = host_reals(h2, u.dtype)
+    plen = (nb - 1) * partials.stride(0) + partials.shape[1]
+    call("poisson_residual_batch", u.dtype, up, rp, fp, c_int(nb), us, rs, fs, i64(shape), c_int(len(shape)), h2p,
+         c_void_p(partials.data_ptr()), c_int64(max(partials.stride(0), partials.shape[1])), c_int64(plen), ptr(loss),
+         stream_ptr())
+    return fu, loss
+
+
+def poisson_adjoint_adam_batch(fu, h2, scale, out, x, m, v, alphas, one_minus_b1, one_minus_b2, eps):
+    """`poisson_adjoint_adam` for the B members of [B, *shape] arrays in ONE launch.  alphas: DEVICE step sizes, [B] (one
+    per member) or one element (shared); out = None: the gradient is not stored."""
+    nb, shape = int(fu.shape[0]), tuple(fu.shape[1:])
+    assert alphas.dtype == fu.dtype and alphas.is_cuda and alphas.numel() in (1, nb) and alphas.is_contiguous()
+    (fp, fs), (xp, xs), (mp, ms), (vp, vs) = (_members(t, nb, shape) for t in (fu, x, m, v))
+    gp, gs = _members(out, nb, shape) if out is not None else (None, fs)
+    h2a, h2p = host_reals(h2, fu.dtype)
+    call("poisson_adjoint_adam_batch", fu.dtype, fp, gp, xp, mp, vp, c_int(nb), fs, gs, xs, ms, vs, i64(shape),
+         c_int(len(shape)), h2p, float(scale), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
+         c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
+    return out
+
+
+def mg_synth_adj_adam_batch(gu, shapes, grads, x, m, v, alphas, one_minus_b1, one_minus_b2, eps):
+    """`mg_synth_adj_adam` on contiguous [B, *shape] level arrays (all axes of a member cell-centred; `shapes`: the level
+    shapes of ONE member): one launch per level for all members.  alphas: as in `poisson_adjoint_adam_batch`."""
+    nb, nlvl = int(gu.shape[0]), len(shapes)
+    assert alphas.dtype == gu.dtype and alphas.numel() in (1, nb)
+    assert tuple(gu.shape) == (nb,) + tuple(shapes[0]) and gu.is_contiguous()
+    for arrs in (grads, x, m, v):  # (the launcher takes contiguous [B, *shape] level arrays: no strides travel)
+        assert all(tuple(t.shape) == (nb,) + tuple(s) and t.is_contiguous() and t.dtype == gu.dtype
+                   for t, s in zip(arrs[1:], shapes[1:]))
+    none0 = lambda arrs: ptr_array([None] + list(arrs[1:]))
+    flat = [int(n) for s in shapes for n in s]
+    call("mg_synth_adj_adam_batch", gu.dtype, ptr(gu), ptr_array(grads), i64(flat), c_int(nlvl), c_int(len(shapes[0])),
+         c_int(nb), none0(x), none0(m), none0(v), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
+         c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
+    return grads
+
+
 def jacobi2_supported(shape, dtype):
     """Arrays whose rows are whole 16-byte packs (odil_poisson_jacobi2, odil_stencil_var_smooth2)."""
     pack = 2 if dtype == torch.float64 else 4

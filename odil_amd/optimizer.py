@@ -109,15 +109,17 @@ class _EpochGraph:
         self.refresh = getattr(loss_grad, "refresh", None)  # called before every replay
         self.begin, self.end = getattr(loss_grad, "graph_begin", None), getattr(loss_grad, "graph_end", None)
         self.nrows = len(step_sizes)
+        # (a row per epoch: one step size, or -- an ensemble with a step size per member -- a row of them)
         self.table = torch.tensor(np.array(step_sizes, dtype=np.float64), dtype=dtype, device=device)
         self.index = torch.zeros(1, dtype=torch.int64, device=device)
-        self.alpha = torch.zeros(1, dtype=dtype, device=device)
+        self.alpha = torch.zeros((1,) + tuple(self.table.shape[1:]), dtype=dtype, device=device)
         self.graph, self.pinfo = None, None
 
     def _body(self):
         torch.index_select(self.table, 0, self.index, out=self.alpha)
+        pinfo = self.step(self.alpha)  # (may file its results under self.index: the row of this epoch)
         self.index.add_(1)
-        return self.step(self.alpha)
+        return pinfo
 
     def capture(self):
         from .util import printlog
@@ -289,6 +291,11 @@ class AdamNativeOptimizer(Optimizer):
         steps = lambda rate: [_adam_step_size(npdt(rate), beta_1, beta_2, npdt(e - epoch_start)) for e in range(first, last + 1)]
         if lrs is not None and len(lrs) != ensemble.nbatch:
             raise ValueError("{} step sizes for {} members".format(len(lrs), ensemble.nbatch))
+        from .fused import PoissonLaunchEnsemble
+
+        if isinstance(ensemble, PoissonLaunchEnsemble):  # (batched launches, epoch by epoch)
+            return self._run_ensemble_launches(ensemble, epochs, callback, steps(lr) if lrs is None else [steps(r) for r in lrs],
+                                               epoch_start, 1 - beta_1, 1 - beta_2, epsilon)
         table = np.array(steps(lr) if lrs is None else [steps(rate) for rate in lrs], dtype=np.float64)
         table = torch.tensor(table, dtype=tdtype, device=ensemble.device)  # [E] shared, or [B, E]
         losses = torch.empty((ensemble.nbatch, max(epochs, 0)), dtype=tdtype, device=ensemble.device)
@@ -311,6 +318,56 @@ class AdamNativeOptimizer(Optimizer):
         optinfo.v = [ensemble.levels(ensemble.v, k) for k in range(ensemble.nbatch)]
         optinfo.losses, optinfo.norms = losses, norms
         return [ensemble.levels(ensemble.x, k) for k in range(ensemble.nbatch)], optinfo
+
+
+    def _run_ensemble_launches(self, ensemble, epochs, callback, table, epoch_start, omb1, omb2, epsilon):
+        """`run_ensemble` for a `fused.PoissonLaunchEnsemble`: every epoch is the launches of a single run, each covering
+        all members.  table: [E] step sizes shared by the members, or [B][E].  The epoch's step sizes are selected, and its
+        [B] losses and norms filed into column e of the [B, E] tables, by the device index of `_EpochGraph` -- eagerly or,
+        under the `_graph_wanted` policy, replayed as one hipGraph (one stream: the launches are a chain); the same body
+        either way, so both give the same bits.  Chunks and callback cadence as in `run_ensemble`."""
+        tdtype, device, nb = ensemble.dtype, ensemble.device, ensemble.nbatch
+        first, last = epoch_start + 1, epoch_start + epochs
+        losses = torch.empty((nb, max(epochs, 0)), dtype=tdtype, device=device)
+        norms = torch.empty_like(losses)
+        for t in ensemble.m + ensemble.v:
+            t.zero_()
+        rows = np.array(table, dtype=np.float64)
+        rows = rows.T if rows.ndim == 2 else rows  # a row per epoch
+
+        def step(alpha):
+            ensemble.epoch(alpha.view(-1), omb1, omb2, epsilon)
+            torch.sqrt(ensemble.loss, out=ensemble.norm)
+            losses.index_copy_(1, runner.index, ensemble.loss.view(nb, 1))
+            norms.index_copy_(1, runner.index, ensemble.norm.view(nb, 1))
+
+        runner = _EpochGraph(step, list(rows) if epochs > 0 else [0.0], tdtype, device, None)
+        safe = Namespace(graph_safe=lambda: True)
+        replay = False
+        epoch = first
+        while epoch <= last:
+            stop = _whole_epochs_stop(callback, epoch, last)
+            while epoch <= stop:
+                if not replay and epoch == first + 2 and last - epoch + 1 > 4 and _graph_wanted(
+                        nb * ensemble.total, safe, epochs):
+                    at = runner.index.clone()
+                    replay = runner.capture()
+                    runner.index.copy_(at)  # (a failed capture resets the index; a capture does not advance it)
+                if replay:
+                    runner.replay()
+                else:
+                    runner._body()
+                self.evals += 1
+                epoch += 1
+            if callback is not None and stop > 0:
+                callback(stop, losses[:, stop - first], norms[:, stop - first])
+        optinfo = Namespace()
+        optinfo.epochs = epochs
+        optinfo.evals = self.evals
+        optinfo.m = [ensemble.levels(ensemble.m, k) for k in range(nb)]
+        optinfo.v = [ensemble.levels(ensemble.v, k) for k in range(nb)]
+        optinfo.losses, optinfo.norms, optinfo.ensemble = losses, norms, ensemble
+        return [ensemble.levels(ensemble.x, k) for k in range(nb)], optinfo
 
 
 class GdOptimizer(Optimizer):

@@ -463,10 +463,14 @@ def optimize_grad(args, optname, problem, state, callback=None, **kwargs):
     return arrays, optinfo
 
 
-def optimize_ensemble(args, problems, states, callback=None, lrs=None, **kwargs):
+def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="workgroup", **kwargs):
     """Adam on B small Poisson problems AT ONCE: every launch runs whole epochs of all members, one workgroup per member
     (fused.PoissonEnsemble; a sweep over right-hand sides, initial guesses or step sizes of a problem that alone fills
     1 / 256 of the device).  Every member ends where `optimize_grad(args, "adam", problem, state)` would leave it, bit for bit.
+
+    form: 'workgroup' (the default) is the above.  'launches' runs members of ANY 1-D / 2-D size with at least two levels
+    (fused.PoissonLaunchEnsemble, fused.launches_refusal): every epoch is the launches of a single run, each covering all
+    members.  'auto': 'workgroup' where `fused.small_refusal` admits the members, 'launches' otherwise.
 
     args.optimizer must be 'adam' / 'adamn'; lrs: one step size per member (default args.lr for all).
     callback(member, state, epoch, pinfo): called for every member at args.epoch_start (the initial evaluation) and at
@@ -474,7 +478,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, **kwargs)
     epoch), pinfo as `optimize_grad` reports it, device scalars read lazily.  The callback reads the state; arrays it
     swaps in are not picked up.
     Members must be the recognised Poisson operator, share cshape, level shapes, spacing, dtype and device, and be
-    small enough for the one-workgroup epochs (fused.small_refusal); anything else raises ValueError naming the first
+    admitted by the form that runs them (fused.small_refusal: small enough for the one-workgroup epochs;
+    fused.launches_refusal: 1-D / 2-D, at least two levels that halve); anything else raises ValueError naming the first
     offending member -- structure (shapes, size) is checked for all members before any operator is probed.
     Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors."""
     from . import fused
@@ -490,6 +495,7 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, **kwargs)
     def refuse(member, reason):
         raise ValueError("optimize_ensemble: member {}: {}".format(member, reason))
 
+    fused.ensemble_form(form, [(2,)], torch.float64)  # (any other value of `form` raises here)
     first = None
     for b, (problem, state) in enumerate(zip(problems, states)):
         domain = problem.domain
@@ -501,7 +507,9 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, **kwargs)
         shapes = [tuple(int(n) for n in a.shape) for a in arrays]
         if shapes[0] != tuple(domain.cshape):
             refuse(b, "the unknown is not a cell-centred field of the domain")
-        reason = fused.small_refusal(shapes, arrays[0].dtype)
+        if b == 0:
+            form = fused.ensemble_form(form, shapes, arrays[0].dtype)
+        reason = fused.small_refusal(shapes, arrays[0].dtype) if form == "workgroup" else fused.launches_refusal(shapes, arrays[0].dtype)
         if reason is not None:
             refuse(b, reason)
         kind = dict(shapes=shapes, dtype=arrays[0].dtype, device=arrays[0].device,
@@ -516,10 +524,11 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, **kwargs)
         if getattr(problem, "_fused", None) is None:
             refuse(b, "the operator is not the recognised Poisson stencil")
         evaluators.append(problem._fused)
-    reason = fused.PoissonEnsemble.refusal(evaluators)
+    kind = fused.PoissonEnsemble if form == "workgroup" else fused.PoissonLaunchEnsemble
+    reason = kind.refusal(evaluators)
     if reason is not None:
         refuse(*reason)
-    ensemble = fused.PoissonEnsemble(evaluators)
+    ensemble = kind(evaluators)
     for b, (problem, state) in enumerate(zip(problems, states)):
         levels = ensemble.levels(ensemble.x, b)
         for dst, src in zip(levels, problem.domain.arrays_from_state(state)):

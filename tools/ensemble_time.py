@@ -9,6 +9,10 @@ HIP events around each, a warm-up, then alternating repetitions; min / median / 
 compare against the kernel as it was before the batched form existed); default: this checkout's own.  The members'
 results of both sides are compared bit for bit once per B before anything is timed.
 --grid: extents of the finest level (1 or 2 numbers); N = 4096 in float64 is the global-memory form.
+--form launches: the batched-launch ensemble (fused.PoissonLaunchEnsemble, any 1-D / 2-D size) instead: one epoch of B
+members replayed as a hipGraph against B back-to-back replays of a single member's epoch
+(PoissonEvaluator.loss_grad_arrays(adam=...), the launches of `optimize_grad`), alternating, each at least --seconds long;
+with the bytes an epoch moves (from the shapes) as a share of 8 TB/s.
 """
 import argparse
 import ctypes
@@ -33,6 +37,8 @@ p.add_argument("--dtype", choices=("f64", "f32"), default="f64")
 p.add_argument("--epochs", type=int, default=1024)
 p.add_argument("--members", type=int, nargs="+", default=[1, 64, 256, 512])
 p.add_argument("--reps", type=int, default=5)
+p.add_argument("--form", choices=("workgroup", "launches"), default="workgroup")
+p.add_argument("--seconds", type=float, default=0.5)
 opt = p.parse_args()
 
 dev = torch.device("cuda:0")
@@ -62,6 +68,67 @@ workspace = ops.reduce_workspace(dev)
 
 def events():
     return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+
+def time_launches(B):
+    """One row: us per epoch of the ensemble's replayed epoch and of B back-to-back replays of a single member's."""
+    gen = torch.Generator().manual_seed(B)
+    rhs = torch.randn((B,) + cshape, generator=gen, dtype=torch.float64).to(dtype).to(dev)
+    evs = [fused.PoissonEvaluator(cshape, shapes, rhs[b], h2, dtype=dtype, device=dev) for b in range(B)]
+    ens = fused.PoissonLaunchEnsemble(evs)
+    alpha = table[:1].clone()
+    for t in ens.x:
+        t.copy_((0.1 * torch.randn(tuple(t.shape), generator=gen, dtype=torch.float64)).to(dtype))
+    one = evs[0]
+    x1, m1, v1 = ([t[0].clone() for t in arrs] for arrs in (ens.x, ens.m, ens.v))
+
+    def captured(fn):
+        fn(), fn()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            fn()
+        return graph
+
+    g_ens = captured(lambda: ens.epoch(alpha, omb1, omb2, eps))
+    g_one = captured(lambda: one.loss_grad_arrays(x1, adam=(m1, v1, alpha, omb1, omb2, eps)))
+
+    def timed(graph, count):
+        torch.cuda.synchronize()
+        a, b = events()
+        a.record()
+        for _ in range(count):
+            graph.replay()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e3 / count  # us per replay
+
+    ne = max(4, int(opt.seconds * 1e6 / timed(g_ens, 20)) + 1)
+    no = max(4 * B, (int(opt.seconds * 1e6 / timed(g_one, 20)) // B + 1) * B)
+    te, ts = [], []
+    for _ in range(opt.reps):
+        te.append(timed(g_ens, ne))
+        ts.append(timed(g_one, no) * B)
+    # bytes of an epoch from the shapes: synthesis (read x_l, coarse; write fine), residual (u, rhs, fu), adjoint + update
+    # (fu, g, 3 read + 3 written of x, m, v), transposes + updates (read fine g, write g, 6 of x, m, v) per level
+    cells = [int(np.prod(s)) for s in shapes]
+    words = 3 * cells[0] + 8 * cells[0] + sum(2 * f + c for f, c in zip(cells, cells[1:])) + sum(f + 7 * c for f, c in zip(cells, cells[1:]))
+    nbytes = B * words * (8 if opt.dtype == "f64" else 4)
+    med = statistics.median(te)
+    print(json.dumps(dict(form="launches", members=B, grid=list(cshape), levels=nlvl, dtype=opt.dtype, replays=[ne, no],
+                          ensemble_us_per_epoch=[round(f(te), 2) for f in (min, statistics.median, max)],
+                          singles_us_per_epoch=[round(f(ts), 2) for f in (min, statistics.median, max)],
+                          single_us_per_epoch=round(statistics.median(ts) / B, 2),
+                          singles_over_ensemble=round(statistics.median(ts) / med, 2),
+                          mbytes_per_epoch=round(nbytes / 1e6, 2), tb_per_s=round(nbytes / med / 1e6, 3),
+                          share_of_8_tb_per_s=round(nbytes / med / 1e6 / 8, 3))), flush=True)
+
+
+if opt.form == "launches":
+    print("device:", torch.cuda.get_device_name(0), "| grid", cshape, "levels", nlvl, opt.dtype, "| form: launches", flush=True)
+    for B in opt.members:
+        time_launches(B)
+    sys.exit(0)
 
 
 print("device:", torch.cuda.get_device_name(0), "| grid", cshape, "levels", nlvl, opt.dtype, "epochs", E,
