@@ -275,7 +275,7 @@ class _Codegen(_MarchKernels, _GatherKernels):
         self.par_outputs, self.par_numel, self.par_keys = None, dict(), dict()  # (parameter_outputs)
         # what source() leaves for the host: defined from the start, empty until then
         self.ncot, self.par_arrays, self.edge_numel, self.gathers_done = 0, 0, 0, False
-        self.jac_items, self.merged, self.par_index = [], [], []
+        self.jac_items, self.jac_exprs, self.merged, self.par_index = [], [], [], []
         # reachable nodes
         live = set()
         stack = list(outputs)

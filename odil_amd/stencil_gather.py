@@ -336,6 +336,7 @@ class _GatherKernels:
                 self.jac_items.append((k, tuple(tr.nodes[ridx].attr)))
         if len(items) > 96:
             raise TraceUnsupported("Jacobian kernel: {} arrays".format(len(items)))
+        self.jac_exprs = [expr for _, expr in items]  # (what the kernel evaluates for jac_items[j]: tests/test_jacobian_kernel_host.py)
         S.append("struct JacP {{ T* p[{}]; }};".format(len(items)))
         self.jac_blocks = self._gather_kernel(S, "k_jac", items, "const JacP jp, const AdamP ad", lambda k: "jp.p[{}]".format(k),
                                               lambda k: "ad", owned=self.slab is not None)
