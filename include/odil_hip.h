@@ -256,13 +256,20 @@ int odil_poisson_jacobi2_synth_f32(const float* coarse, const float* x, const fl
  * synthesised level-1 array of shape cshape (3-D, all axes cell-centred), w0 / rhs / fu: the fine
  * arrays of shape 2 * cshape, h2: squared FINE steps.  fu is bit-identical to
  * odil_interp_add + odil_poisson_residual.  Loss = sum over the fine planes z0 <= z < z1 (z1 < 0:
- * all) of fu^2 / denom (denom <= 0: the array size), as odil_poisson_residual_slab. */
+ * all) of fu^2 / denom (denom <= 0: the array size), as odil_poisson_residual_slab.  fu == NULL: loss only.
+ * `partials`: odil_reduce_workspace_bytes() scratch; `column_sums`: scratch of column_sums_size >=
+ * odil_poisson_residual_synth_workspace_bytes(cshape) bytes (0: a shape the entry point refuses) -- the sum of squares
+ * of every coarse column and z-chunk, which a second launch reduces in a fixed order (deterministic; nothing is
+ * allocated by the call). */
+size_t odil_poisson_residual_synth_workspace_bytes(const int64_t* cshape);
 int odil_poisson_residual_synth_f64(const double* coarse, const double* w0, const double* rhs, double* fu,
                                     const int64_t* cshape, const double* h2, int64_t z0, int64_t z1, double denom,
-                                    double* partials, double* loss, void* stream);
+                                    double* partials, double* column_sums, size_t column_sums_size, double* loss,
+                                    void* stream);
 int odil_poisson_residual_synth_f32(const float* coarse, const float* w0, const float* rhs, float* fu,
                                     const int64_t* cshape, const float* h2, int64_t z0, int64_t z1, double denom,
-                                    double* partials, float* loss, void* stream);
+                                    double* partials, double* column_sums, size_t column_sums_size, float* loss,
+                                    void* stream);
 
 /* One damped-Jacobi sweep (odil_poisson_jacobi) of u = x + P coarse with the prolongation formed in registers:
  * the coarse-grid correction of a V-cycle and its first post-smoothing sweep in one pass, xout != x.  Equal, bit for

@@ -49,7 +49,7 @@ _SIGNATURES = {
     "poisson_jacobi2_synth": [_P, _P, _P, _P, _I64P, _P, _R, _R, c_int, _P],
     "poisson_residual_restrict": [_P, _P, _P, _I64P, c_int, _P, _R, _P, _P, _P],
     "poisson_residual_restrict_slab": [_P, _P, _P, _I64P, c_int, _P, _R, c_int64, c_int64, c_double, _P, _P, _P],
-    "poisson_residual_synth": [_P, _P, _P, _P, _I64P, _P, c_int64, c_int64, c_double, _P, _P, _P],
+    "poisson_residual_synth": [_P, _P, _P, _P, _I64P, _P, c_int64, c_int64, c_double, _P, _P, c_size_t, _P, _P],
     "poisson_jacobi_synth": [_P, _P, _P, _P, _I64P, _P, _R, _P],
     "poisson_residual_slab": [_P, _P, _P, _I64P, c_int, _P, c_int64, c_int64, c_double, _P, _P, _P],
     "poisson_adjoint": [_P, _P, _I64P, c_int, _P, _R, _P],
@@ -99,7 +99,7 @@ EXPORTED = [
     "odil_last_error", "odil_version", "odil_device_count", "odil_reduce_workspace_bytes", "odil_dots_workspace_bytes",
     "odil_dense_block_workspace_bytes", "odil_dense_block_wide_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy",
     "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials", "odil_poisson_batch_partials",
-    "odil_mg_batch_levels_ok",
+    "odil_mg_batch_levels_ok", "odil_poisson_residual_synth_workspace_bytes",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
 ] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
@@ -140,6 +140,8 @@ def load():
     lib.odil_poisson_batch_partials.argtypes = [_I64P, c_int, c_int]
     lib.odil_mg_batch_levels_ok.restype = c_int
     lib.odil_mg_batch_levels_ok.argtypes = [_I64P, c_int, c_int, c_int]
+    lib.odil_poisson_residual_synth_workspace_bytes.restype = c_size_t
+    lib.odil_poisson_residual_synth_workspace_bytes.argtypes = [_I64P]
     for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)
         fn = getattr(lib, name)
         fn.restype = c_int

@@ -129,16 +129,10 @@ struct UnitSched {
   int per_xcd;      // units per XCD (grid = 8 * per_xcd), or total units when axis < 0
 };
 
-// `target_units`: how many workgroups the launch should at least be cut into.  Kernels that prime a
-// window of planes before their first step (P^T: two extra fine-plane reductions per chunk) ask for
-// fewer, longer chunks.
-inline UnitSched make_unit_sched(int64_t Z, int64_t Y, int64_t XS, int64_t target_units = 2 * kGridCap) {
+// The schedule with `zc` planes per z-chunk.
+inline UnitSched make_unit_sched_chunked(int64_t Z, int64_t Y, int64_t XS, int zc) {
   UnitSched s;
-  int64_t zc = (Z * Y * XS) / target_units;
-  if (zc < 1) zc = 1;
-  if (zc > 64) zc = 64;
-  if (zc > Z) zc = Z;
-  s.ZC = (int)zc;
+  s.ZC = zc;
   s.ZCH = (int)((Z + zc - 1) / zc);
   s.Y = (int)Y;
   s.XS = (int)XS;
@@ -158,6 +152,17 @@ inline UnitSched make_unit_sched(int64_t Z, int64_t Y, int64_t XS, int64_t targe
     s.per_xcd = s.ZCH * s.Y * s.XS;
   }
   return s;
+}
+
+// `target_units`: how many workgroups the launch should at least be cut into.  Kernels that prime a
+// window of planes before their first step (P^T: two extra fine-plane reductions per chunk) ask for
+// fewer, longer chunks.
+inline UnitSched make_unit_sched(int64_t Z, int64_t Y, int64_t XS, int64_t target_units = 2 * kGridCap) {
+  int64_t zc = (Z * Y * XS) / target_units;
+  if (zc < 1) zc = 1;
+  if (zc > 64) zc = 64;
+  if (zc > Z) zc = Z;
+  return make_unit_sched_chunked(Z, Y, XS, (int)zc);
 }
 
 inline int unit_grid(const UnitSched& s) { return s.axis < 0 ? s.per_xcd : s.per_xcd * kNumXcd; }

@@ -1,95 +1,19 @@
-// Poisson residual with the LAST prolongation of the multigrid synthesis fused in:
-//   u = w_0 + P s_1   (reference core.py:245-263, last step)   is never written to memory,
-//   fu = Lap(u) - rhs (reference examples/poisson/poisson.py:57-113) is evaluated from it directly.
+// One damped-Jacobi sweep of the Poisson operator with the LAST prolongation of a V-cycle fused in:
+//   u = x + P x_c   (reference core.py:245-263, last step)   is never written to memory,
+//   the sweep of A u = rhs (reference examples/poisson/poisson.py:57-113) is evaluated from it directly.
+// (The residual of the Adam epoch with the same prolongation fused in is poisson_synth_tile.hip.)
 //
 // The walk is the one of k_interp_add_march: a thread owns a coarse column (jy, jx), keeps the
 // 3 x 3 x 3 ghosted coarse neighbourhood in registers and steps through the coarse planes.  That
 // neighbourhood determines u on the 4 x 4 x 4 fine patch around the thread's 2 x 2 x 2 fine cells,
 // which is everything the 7-point stencil of those cells reads: own values for the planes below and
 // above slide through registers, edge neighbours are recomputed (P costs 8 multiply-adds per
-// value; the kernel stays HBM-bound), and only w_0 is loaded at those positions.  Every u is formed
-// by exactly the arithmetic of the transfer kernel (same order, same constants), so fu is
-// bit-identical to the two-kernel path.  Saves writing and re-reading u: 2 of the 16.4 words per
-// grid-point update of the epoch.
-#include "mg_march.h"
-#include "poisson.h"
+// value; the kernel stays HBM-bound), and only x is loaded at those positions.  Every u is formed
+// by exactly the arithmetic of the transfer kernel (same order, same constants), so the result is
+// bit-identical to the two-kernel path.
+#include "poisson_synth.h"
 
 namespace odil {
-
-// Interpolated coarse contribution at fine offset (ez, ey, ex) in {-1, 0, 1, 2}^3 relative to the
-// fine cell (2jz, 2jy, 2jx): coarse base (e + 2) / 2 - 1 and parity e & 1 per axis; reference
-// order (rz, ry, rx), weights parity == r ? 1 : 3, scaled by the exact 1/64.
-template <typename T, int EZ, int EY, int EX>
-__device__ inline T synth_val(const T (&v)[3][3][3]) {
-  constexpr int bz = (EZ + 2) / 2 - 1, by = (EY + 2) / 2 - 1, bx = (EX + 2) / 2 - 1;
-  constexpr int sz = EZ & 1, sy = EY & 1, sx = EX & 1;
-  T s = T(0);
-#pragma unroll
-  for (int rz = 0; rz < 2; ++rz)
-#pragma unroll
-    for (int ry = 0; ry < 2; ++ry)
-#pragma unroll
-      for (int rx = 0; rx < 2; ++rx) {
-        const int w = (sz == rz ? 1 : 3) * (sy == ry ? 1 : 3) * (sx == rx ? 1 : 3);
-        s = s + T(w) * v[bz + sz + rz][by + sy + ry][bx + sx + rx];  // window index 0..2 <-> coarse j-1..j+1
-      }
-  return s * (T(1) / T(64));
-}
-
-// own 2 x 2 of fine plane 2jz + EZ: u = w0 + P
-template <typename T, int EZ>
-__device__ inline void synth_own(const T (&v)[3][3][3], const PackN<T, 2> (&w)[2], T (&u)[2][2]) {
-  u[0][0] = T(1) * w[0].e[0] + synth_val<T, EZ, 0, 0>(v);
-  u[0][1] = T(1) * w[0].e[1] + synth_val<T, EZ, 0, 1>(v);
-  u[1][0] = T(1) * w[1].e[0] + synth_val<T, EZ, 1, 0>(v);
-  u[1][1] = T(1) * w[1].e[1] + synth_val<T, EZ, 1, 1>(v);
-}
-
-struct SynthArgs {
-  MarchArgs m;
-  int64_t loss_z0, loss_z1;  // fine planes that enter the loss
-};
-
-// Residual of the four own cells of fine plane fz = 2jz + EZ (EZ in {0, 1}).
-//   uc: own values, ub / ua: own values of the planes below / above,
-//   wy[2]: w0 packs of rows 2jy-1 and 2jy+2, wx[2][2]: w0 at x = 2jx-1 / 2jx+2 of the two own rows.
-// JAC: f is the damped-Jacobi update q - (A u - rhs) wd instead of the residual, wd[iy][ix] = omega / diag of the plane.
-template <typename T, int EZ, bool JAC = false>
-__device__ inline void residual_plane(const T (&v)[3][3][3], const T (&uc)[2][2], const T (&ub)[2][2],
-                                      const T (&ua)[2][2], const PackN<T, 2> (&wy)[2], const T (&wx)[2][2],
-                                      const PackN<T, 2> (&r)[2], int fz, int fy0, int fx0, int FZ, int FY, int FX,
-                                      const H2<T>& h, T (&f)[2][2], const T (*wd)[2][2] = nullptr) {
-  // edge neighbours: rows 2jy-1 and 2jy+2 at the own x, columns 2jx-1 and 2jx+2 at the own rows
-  T ylo[2], yhi[2], xlo[2], xhi[2];
-  ylo[0] = T(1) * wy[0].e[0] + synth_val<T, EZ, -1, 0>(v);
-  ylo[1] = T(1) * wy[0].e[1] + synth_val<T, EZ, -1, 1>(v);
-  yhi[0] = T(1) * wy[1].e[0] + synth_val<T, EZ, 2, 0>(v);
-  yhi[1] = T(1) * wy[1].e[1] + synth_val<T, EZ, 2, 1>(v);
-  xlo[0] = T(1) * wx[0][0] + synth_val<T, EZ, 0, -1>(v);
-  xlo[1] = T(1) * wx[1][0] + synth_val<T, EZ, 1, -1>(v);
-  xhi[0] = T(1) * wx[0][1] + synth_val<T, EZ, 0, 2>(v);
-  xhi[1] = T(1) * wx[1][1] + synth_val<T, EZ, 1, 2>(v);
-#pragma unroll
-  for (int iy = 0; iy < 2; ++iy)
-#pragma unroll
-    for (int ix = 0; ix < 2; ++ix) {
-      const int y = fy0 + iy, x = fx0 + ix;
-      const T q = uc[iy][ix];
-      const T ym = iy == 0 ? ylo[ix] : uc[0][ix], yp = iy == 0 ? uc[1][ix] : yhi[ix];
-      const T xm = ix == 0 ? xlo[iy] : uc[iy][0], xp = ix == 0 ? uc[iy][1] : xhi[iy];
-      T acc = axis_term<T>(q, ub[iy][ix], ua[iy][ix], fz == 0, fz == FZ - 1, h, 0);
-      acc = acc + axis_term<T>(q, ym, yp, y == 0, y == FY - 1, h, 1);
-      acc = acc + axis_term<T>(q, xm, xp, x == 0, x == FX - 1, h, 2);
-      if constexpr (JAC) {  // k_poisson_jacobi's expression
-        const bool zw = fz == 0 || fz == FZ - 1, yw = y == 0 || y == FY - 1, xw = x == 0 || x == FX - 1;
-        const T w = zw ? (yw ? (xw ? wd[1][1][1] : wd[1][1][0]) : (xw ? wd[1][0][1] : wd[1][0][0]))
-                       : (yw ? (xw ? wd[0][1][1] : wd[0][1][0]) : (xw ? wd[0][0][1] : wd[0][0][0]));
-        f[iy][ix] = q - (acc - r[iy].e[ix]) * w;
-      }
-      else
-        f[iy][ix] = acc - r[iy].e[ix];
-    }
-}
 
 // The same value in every lane, kept in scalar registers.
 __device__ __forceinline__ double uniform_value(double x) {
@@ -116,20 +40,16 @@ __device__ __forceinline__ void jacobi_weight_table(const H2<T>& h, T omega, T (
       }
 }
 
-// JAC: one damped-Jacobi sweep of the same operator on u = w0 + P coarse instead of its residual (the first
-// post-smoothing sweep of a V-cycle with the coarse-grid correction formed in registers: x + P x_c is never
-// stored, 3 1/8 words per cell instead of 5 1/8); fu receives the new iterate, no loss.
-template <typename T, bool JAC = false>
-__global__ __launch_bounds__(kBlock) void k_poisson_residual_synth(const T* __restrict__ coarse,
-                                                                   const T* __restrict__ w0,
-                                                                   const T* __restrict__ rhs, T* __restrict__ fu,
-                                                                   SynthArgs sa, H2<T> h,
-                                                                   double* __restrict__ partials, T omega = T(0)) {
-  const MarchArgs& a = sa.m;
+// The first post-smoothing sweep of a V-cycle with the coarse-grid correction formed in registers: u = w0 + P coarse
+// is never stored, 3 1/8 words per cell instead of 5 1/8; fu receives the new iterate.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_poisson_jacobi_synth(const T* __restrict__ coarse,
+                                                                 const T* __restrict__ w0,
+                                                                 const T* __restrict__ rhs, T* __restrict__ fu,
+                                                                 MarchArgs a, H2<T> h, T omega) {
   const int cnz = a.cn[0], cny = a.cn[1], cnx = a.cn[2];
   const int FZ = a.fn[0], FY = a.fn[1], FX = a.fn[2];
   const int64_t cplane = (int64_t)cny * cnx, fplane = (int64_t)FY * FX;
-  double local = 0.0;
   int zc, yt, xt;
   const bool have = unit_decode(a.usched, zc, yt, xt);
   const int lx = threadIdx.x % a.tx, ly = threadIdx.x / a.tx;
@@ -147,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual_synth(const T* __re
     // omega / diag of the four own cells on a plane away from the z walls (k_poisson_jacobi: the diagonal is
     // sum over axes of (-2 / h^2) (1 + walls touched)); the two wall planes of the array form theirs where needed
     T wdt[2][2][2];
-    if constexpr (JAC) jacobi_weight_table<T>(h, omega, wdt);
+    jacobi_weight_table<T>(h, omega, wdt);
     T v[3][3][3];
     load_plane<T, 1>(coarse, z0 - 1, cnz, cplane, cnx, ty, tx, T(1), v[0]);
     load_plane<T, 1>(coarse, z0, cnz, cplane, cnx, ty, tx, T(1), v[1]);
@@ -199,31 +119,16 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual_synth(const T* __re
       synth_own<T, 1>(v, wC, uC);
       synth_own<T, 2>(v, wD, uD);
       T fB[2][2], fC[2][2];
-      if constexpr (JAC) {
-        residual_plane<T, 0, true>(v, uB, uA, uC, wyB, wxB, rB, fzB, fy0, fx0, FZ, FY, FX, h, fB, wdt);
-        residual_plane<T, 1, true>(v, uC, uB, uD, wyC, wxC, rC, fzC, fy0, fx0, FZ, FY, FX, h, fC, wdt);
-      } else {
-        residual_plane<T, 0>(v, uB, uA, uC, wyB, wxB, rB, fzB, fy0, fx0, FZ, FY, FX, h, fB);
-        residual_plane<T, 1>(v, uC, uB, uD, wyC, wxC, rC, fzC, fy0, fx0, FZ, FY, FX, h, fC);
+      residual_plane<T, 0, true>(v, uB, uA, uC, wyB, wxB, rB, fzB, fy0, fx0, FZ, FY, FX, h, fB, wdt);
+      residual_plane<T, 1, true>(v, uC, uB, uD, wyC, wxC, rC, fzC, fy0, fx0, FZ, FY, FX, h, fC, wdt);
+#pragma unroll
+      for (int iy = 0; iy < 2; ++iy) {
+        PackN<T, 2> o;
+        o.e[0] = fB[iy][0], o.e[1] = fB[iy][1];
+        stream_st<T, 2>(fu + pB + row0 + iy * FX, o, true);
+        o.e[0] = fC[iy][0], o.e[1] = fC[iy][1];
+        stream_st<T, 2>(fu + pC + row0 + iy * FX, o, true);
       }
-      if (fu) {
-#pragma unroll
-        for (int iy = 0; iy < 2; ++iy) {
-          PackN<T, 2> o;
-          o.e[0] = fB[iy][0], o.e[1] = fB[iy][1];
-          stream_st<T, 2>(fu + pB + row0 + iy * FX, o, true);
-          o.e[0] = fC[iy][0], o.e[1] = fC[iy][1];
-          stream_st<T, 2>(fu + pC + row0 + iy * FX, o, true);
-        }
-      }
-      const bool inB = fzB >= sa.loss_z0 && fzB < sa.loss_z1, inC = fzC >= sa.loss_z0 && fzC < sa.loss_z1;
-#pragma unroll
-      for (int iy = 0; iy < 2; ++iy)
-#pragma unroll
-        for (int ix = 0; ix < 2; ++ix) {
-          if (inB) local += (double)(fB[iy][ix] * fB[iy][ix]);
-          if (inC) local += (double)(fC[iy][ix] * fC[iy][ix]);
-        }
 #pragma unroll
       for (int iy = 0; iy < 2; ++iy)
 #pragma unroll
@@ -240,68 +145,21 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual_synth(const T* __re
         }
     }
   }
-  if constexpr (!JAC) {
-    const double total = block_sum(local);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
-  }
 }
 
 template <typename T>
-static int poisson_residual_synth(const T* coarse, const T* w0, const T* rhs, T* fu, const int64_t* cshape,
-                                  const T* h2, int64_t z0, int64_t z1, double denom, double* partials, T* loss,
-                                  void* stream, bool jacobi = false, T omega = T(0)) {
-  if (!coarse || !w0 || !rhs || (!jacobi && (!partials || !loss)) || (jacobi && (!fu || fu == w0))) {
-    set_error("poisson_residual_synth: null pointer (or the Jacobi sweep in place)");
+static int poisson_jacobi_synth(const T* coarse, const T* x, const T* rhs, T* xout, const int64_t* cshape, const T* h2,
+                                T omega, void* stream) {
+  if (!coarse || !x || !rhs || !xout || xout == x) {
+    set_error("poisson_jacobi_synth: null pointer (or the sweep in place)");
     return ODIL_E_INVAL;
   }
   SynthArgs sa;
-  MarchArgs& m = sa.m;
-  for (int i = 0; i < 3; ++i) {
-    if (cshape[i] < 2 || cshape[i] >= (1 << 29)) {
-      set_error("poisson_residual_synth: coarse extent %lld on axis %d", (long long)cshape[i], i);
-      return ODIL_E_INVAL;
-    }
-    m.cn[i] = (int)cshape[i];
-    m.fn[i] = 2 * m.cn[i];
-  }
-  if (!((reinterpret_cast<uintptr_t>(w0) | reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(fu)) %
-            (2 * sizeof(T)) ==
-        0)) {
-    set_error("poisson_residual_synth: arrays must be aligned to %d bytes", (int)(2 * sizeof(T)));
-    return ODIL_E_INVAL;
-  }
-  m.cut_lo = m.cut_hi = 0;
-  m.lead_loc = 0;
-  m.lead_cn = m.lead_fn = 1;
-  m.nt = (int64_t)m.fn[0] * m.fn[1] * m.fn[2] * (int64_t)sizeof(T) > kStreamBytes;
-  int tx = 1;
-  while (tx < m.cn[2] && tx < kBlock) tx *= 2;
-  m.tx = tx;
-  m.ty = kBlock / tx;
-  const int64_t ytiles = (m.cn[1] + m.ty - 1) / m.ty, xtiles = (m.cn[2] + m.tx - 1) / m.tx;
-  if ((int64_t)m.cn[0] * ytiles * xtiles >= ((int64_t)1 << 31)) {
-    set_error("poisson_residual_synth: grid too large for one launch");
-    return ODIL_E_INVAL;
-  }
-  m.usched = make_unit_sched(m.cn[0], ytiles, xtiles);
-  const int grid = unit_grid(m.usched);
-  if (grid > kMaxPartials) {
-    set_error("poisson_residual_synth: %d workgroups exceed the reduction workspace", grid);
-    return ODIL_E_INVAL;
-  }
-  sa.loss_z0 = z0;
-  sa.loss_z1 = z1 < 0 ? m.fn[0] : z1;
+  if (int e = synth_geometry<T>(x, rhs, xout, cshape, sa)) return e;
   T hh[3] = {h2[0], h2[1], h2[2]};
-  if (jacobi) {
-    hipLaunchKernelGGL((k_poisson_residual_synth<T, true>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, coarse,
-                       w0, rhs, fu, sa, make_h2<T>(hh), partials, omega);
-    return check_launch("k_poisson_residual_synth<jacobi>");
-  }
-  hipLaunchKernelGGL((k_poisson_residual_synth<T, false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, coarse, w0,
-                     rhs, fu, sa, make_h2<T>(hh), partials, T(0));
-  if (int e = check_launch("k_poisson_residual_synth")) return e;
-  const double size = denom > 0.0 ? denom : (double)m.fn[0] * m.fn[1] * m.fn[2];
-  return launch_final_reduce<T>(partials, grid, 0, 1, size, loss, (hipStream_t)stream);
+  hipLaunchKernelGGL((k_poisson_jacobi_synth<T>), dim3(unit_grid(sa.m.usched)), dim3(kBlock), 0, (hipStream_t)stream,
+                     coarse, x, rhs, xout, sa.m, make_h2<T>(hh), omega);
+  return check_launch("k_poisson_jacobi_synth");
 }
 
 }  // namespace odil
@@ -309,24 +167,12 @@ static int poisson_residual_synth(const T* coarse, const T* w0, const T* rhs, T*
 using namespace odil;
 
 extern "C" {
-int odil_poisson_residual_synth_f64(const double* coarse, const double* w0, const double* rhs, double* fu,
-                                    const int64_t* cshape, const double* h2, int64_t z0, int64_t z1, double denom,
-                                    double* partials, double* loss, void* stream) {
-  return poisson_residual_synth<double>(coarse, w0, rhs, fu, cshape, h2, z0, z1, denom, partials, loss, stream);
-}
-int odil_poisson_residual_synth_f32(const float* coarse, const float* w0, const float* rhs, float* fu,
-                                    const int64_t* cshape, const float* h2, int64_t z0, int64_t z1, double denom,
-                                    double* partials, float* loss, void* stream) {
-  return poisson_residual_synth<float>(coarse, w0, rhs, fu, cshape, h2, z0, z1, denom, partials, loss, stream);
-}
 int odil_poisson_jacobi_synth_f64(const double* coarse, const double* x, const double* rhs, double* xout,
                                   const int64_t* cshape, const double* h2, double omega, void* stream) {
-  return poisson_residual_synth<double>(coarse, x, rhs, xout, cshape, h2, 0, -1, 0.0, nullptr, nullptr, stream, true,
-                                        omega);
+  return poisson_jacobi_synth<double>(coarse, x, rhs, xout, cshape, h2, omega, stream);
 }
 int odil_poisson_jacobi_synth_f32(const float* coarse, const float* x, const float* rhs, float* xout,
                                   const int64_t* cshape, const float* h2, float omega, void* stream) {
-  return poisson_residual_synth<float>(coarse, x, rhs, xout, cshape, h2, 0, -1, 0.0, nullptr, nullptr, stream, true,
-                                       omega);
+  return poisson_jacobi_synth<float>(coarse, x, rhs, xout, cshape, h2, omega, stream);
 }
 }  // extern "C"

@@ -26,6 +26,19 @@ def reduce_workspace(device, nquant=1):
     return ws
 
 
+_column_sums = {}
+
+
+def residual_synth_workspace(device, cshape):
+    """Per-device scratch of poisson_residual_synth (f64 sums of squares per coarse column and z-chunk): allocated once,
+    replaced only by a larger one."""
+    need = _lib.load().odil_poisson_residual_synth_workspace_bytes(i64(cshape)) // 8
+    ws = _column_sums.get(str(device))
+    if ws is None or ws.numel() < need:
+        ws = _column_sums[str(device)] = torch.empty(max(need, 1), dtype=torch.float64, device=device)
+    return ws
+
+
 def fine_shape(cshape, loc):
     return tuple({"c": 2 * s, "n": 2 * s - 1, ".": s}[l] for s, l in zip(cshape, loc))
 
@@ -652,10 +665,11 @@ def poisson_residual_synth(coarse, w0, rhs, h2, fu=None, loss=None, zrange=None,
     if loss is None:
         loss = torch.empty((), dtype=w0.dtype, device=w0.device)
     h2a, h2p = host_reals(h2, w0.dtype)
+    sums = residual_synth_workspace(w0.device, coarse.shape)
     call(
         "poisson_residual_synth", w0.dtype, ptr(coarse), ptr(w0), ptr(rhs), ptr(fu), i64(coarse.shape), h2p,
         c_int64(zrange[0] if zrange else 0), c_int64(zrange[1] if zrange else -1), c_double(float(denom or 0.0)),
-        ptr(reduce_workspace(w0.device)), ptr(loss), stream_ptr(),
+        ptr(reduce_workspace(w0.device)), ptr(sums), c_size_t(sums.numel() * 8), ptr(loss), stream_ptr(),
     )
     return fu, loss
 
