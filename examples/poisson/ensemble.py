@@ -3,10 +3,12 @@
 right-hand side (`--vary rhs`: the reference solution scaled and noise added to the imposed data) or by their initial
 guess (`--vary guess`), all in ONE launch per chunk of epochs, one workgroup per member (`odil.util.optimize_ensemble`).
 Alone, a problem of this size uses one of the device's 256 compute units.  Larger members (2-D N = 64 ... 256, long 1-D
-grids) run with `--form launches`: the launches of a single run's epoch, each covering all members.
+grids) run with `--form launches`: the launches of a single run's epoch, each covering all members; 3-D members run the
+same way with `--form volumes` (or `--form auto`, which picks the form from the members' shapes).
 
     python examples/poisson/ensemble.py --ndim 1 --N 256 --members 64 --epochs 1000 --vary rhs
     python examples/poisson/ensemble.py --ndim 2 --N 128 --members 64 --epochs 1000 --form launches
+    python examples/poisson/ensemble.py --ndim 3 --N 32 --members 64 --epochs 1000 --form volumes
 """
 
 import os
@@ -29,8 +31,9 @@ def parse_args(argv=None):
     own.add_argument("--vary", choices=("rhs", "guess"), default="rhs", help="What differs between the members")
     own.add_argument("--noise", type=float, default=0.1, help="Amplitude of the noise on the right-hand side / the guess")
     own.add_argument("--lr_spread", type=float, default=1.0, help="Step sizes from lr / spread to lr * spread over the members")
-    own.add_argument("--form", choices=("workgroup", "launches", "auto"), default="workgroup",
-                     help="One workgroup per member (small members), batched launches (any 1-D / 2-D size), or whichever fits")
+    own.add_argument("--form", choices=("workgroup", "launches", "volumes", "auto"), default="workgroup",
+                     help="One workgroup per member (small members), batched launches (any 1-D / 2-D size), batched launches "
+                          "of 3-D members, or whichever fits")
     mine, rest = own.parse_known_args(argv)
     args = poisson.parse_args(["--ndim", "1", "--N", "256"] + rest)
     for key, value in vars(mine).items():

@@ -533,6 +533,66 @@ int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const
                                      float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
                                      void* stream);
 
+/* An ENSEMBLE of nbatch 3-D Poisson problems of one shape as batched launches: every launch of a single 3-D problem's
+ * epoch (odil_mg_synth on the coarse levels, odil_poisson_residual_synth, odil_poisson_adjoint_adam,
+ * odil_mg_synth_adj_adam) covers all members.  Member b is blockIdx.y = b of the residual and stencil kernels and runs
+ * exactly the single kernel's walk on pointers offset by the member strides; its column sums and partial sums go to its
+ * own part of the workspaces and are reduced in the single launch's order (k_synth_loss_replay, the final reduction),
+ * so losses and states equal the single run's bit for bit.  Members never communicate.
+ *   coarse                   [nbatch, *cshape] contiguous: the synthesis of the levels 1 ... (level 1 itself when nlvl = 2)
+ *   w0, rhs, fu, g, x, m, v  member b at b * <its stride> elements (stride >= cells of a member and a multiple of 16
+ *                            bytes); shape = 2 * cshape
+ *   partials                 partials_len doubles, member b's row at b * partials_stride
+ *                            (partials_stride >= odil_poisson_residual_synth_batch_partials(cshape))
+ *   column_sums              nbatch * odil_poisson_residual_synth_batch_workspace_bytes(cshape) bytes (the query: per member)
+ *   loss                     [nbatch] mean(fu[b]^2) over the full plane range (there is no slab form)
+ *   alpha_dev                DEVICE step sizes, member b's at b * alpha_stride; alpha_stride = 0: one for all members
+ * odil_poisson_adjoint_adam_volumes is odil_poisson_adjoint_adam_batch for ndim = 3 (gu = NULL: the gradient is not
+ * stored).  odil_mg_synth_adj_adam_volumes is odil_mg_synth_adj_adam with factors 1 on contiguous [nbatch, *shape] level
+ * arrays as '.ccc', `shapes` being the nlvl x 3 extents of ONE member: a level runs the rows, tile, marching or fast
+ * kernel that the same level of a single volume runs, and that kernel reads the step size of its volume.
+ * Refused before anything is launched: null pointers, nbatch outside 1 ... 65535, ndim != 3, a member stride below a
+ * member's size or off the 16-byte grid, a partials or column-sum workspace that is too short, a grid beyond one launch,
+ * gradient arrays off the 16-byte grid, and a batch one of whose transfer levels would not run the kernel that level of
+ * a single member runs.  odil_mg_volumes_levels_ok answers the last question from the shapes, nbatch and the element
+ * size alone (0: they do; else the reason is the error text).
+ * odil_interp_adj_kind names the transposed prolongation odil_interp_adj runs for a coarse shape and layout on arrays
+ * aligned to 16 bytes, nothing launched: 0 the generic kernel, 1 the fast kernel, 2 a node-centred marching kernel, 3 the
+ * row-marching kernel (float), 4 the LDS-tile kernel, 5 the z-marching kernel; negative: an error.  Kernels 3, 4 and 5
+ * round differently in float. */
+int odil_interp_adj_kind(const int64_t* cshape, int ndim, const char* loc, int elem_size);
+int odil_mg_volumes_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch, int elem_size);
+size_t odil_poisson_residual_synth_batch_workspace_bytes(const int64_t* cshape);
+int64_t odil_poisson_residual_synth_batch_partials(const int64_t* cshape);
+int odil_poisson_residual_synth_batch_f64(const double* coarse, const double* w0, const double* rhs, double* fu,
+                                          int nbatch, int64_t w0_stride, int64_t rhs_stride, int64_t fu_stride,
+                                          const int64_t* cshape, int ndim, const double* h2, double* partials,
+                                          int64_t partials_stride, int64_t partials_len, double* column_sums,
+                                          size_t column_sums_size, double* loss, void* stream);
+int odil_poisson_residual_synth_batch_f32(const float* coarse, const float* w0, const float* rhs, float* fu, int nbatch,
+                                          int64_t w0_stride, int64_t rhs_stride, int64_t fu_stride,
+                                          const int64_t* cshape, int ndim, const float* h2, double* partials,
+                                          int64_t partials_stride, int64_t partials_len, double* column_sums,
+                                          size_t column_sums_size, float* loss, void* stream);
+int odil_poisson_adjoint_adam_volumes_f64(const double* fu, double* gu, double* x, double* m, double* v, int nbatch,
+                                          int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                          int64_t v_stride, const int64_t* shape, int ndim, const double* h2,
+                                          double scale, double one_minus_b1, double one_minus_b2, double eps,
+                                          const double* alpha_dev, int64_t alpha_stride, void* stream);
+int odil_poisson_adjoint_adam_volumes_f32(const float* fu, float* gu, float* x, float* m, float* v, int nbatch,
+                                          int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                          int64_t v_stride, const int64_t* shape, int ndim, const float* h2, float scale,
+                                          float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
+                                          int64_t alpha_stride, void* stream);
+int odil_mg_synth_adj_adam_volumes_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       int nbatch, double* const* x, double* const* m, double* const* v,
+                                       double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                       int64_t alpha_stride, void* stream);
+int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
+                                       float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
+                                       void* stream);
+
 /* TWO sweeps of odil_stencil_var_smooth in mode 0, with the weights omega1 and then omega2, in ONE pass: the coefficient arrays -- 7 of
  * the 10 words a sweep moves in 3-D -- are read once for both, the intermediate iterate stays on the CU.  out != x;
  * bit-identical to two calls of odil_stencil_var_smooth.  The last extent must be even.  zc_hint: planes per workgroup

@@ -44,6 +44,11 @@ _SIGNATURES = {
     "poisson_adjoint_adam_batch": [_P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, _I64P, c_int, _P,
                                    _R, _R, _R, _R, _P, c_int64, _P],
     "mg_synth_adj_adam_batch": [_P, _P, _I64P, c_int, c_int, c_int, _P, _P, _P, _R, _R, _R, _P, c_int64, _P],
+    "poisson_residual_synth_batch": [_P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _I64P, c_int, _P, _P, c_int64,
+                                     c_int64, _P, c_size_t, _P, _P],
+    "poisson_adjoint_adam_volumes": [_P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, _I64P, c_int,
+                                     _P, _R, _R, _R, _R, _P, c_int64, _P],
+    "mg_synth_adj_adam_volumes": [_P, _P, _I64P, c_int, c_int, c_int, _P, _P, _P, _R, _R, _R, _P, c_int64, _P],
     "poisson_jacobi": [_P, _P, _P, _I64P, c_int, _P, _R, _P],
     "poisson_jacobi2": [_P, _P, _P, _I64P, c_int, _P, _R, _R, c_int, _P],
     "poisson_jacobi2_synth": [_P, _P, _P, _P, _I64P, _P, _R, _R, c_int, _P],
@@ -100,6 +105,8 @@ EXPORTED = [
     "odil_dense_block_workspace_bytes", "odil_dense_block_wide_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy",
     "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials", "odil_poisson_batch_partials",
     "odil_mg_batch_levels_ok", "odil_poisson_residual_synth_workspace_bytes",
+    "odil_mg_volumes_levels_ok", "odil_interp_adj_kind", "odil_poisson_residual_synth_batch_workspace_bytes",
+    "odil_poisson_residual_synth_batch_partials",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
 ] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
@@ -142,6 +149,14 @@ def load():
     lib.odil_mg_batch_levels_ok.argtypes = [_I64P, c_int, c_int, c_int]
     lib.odil_poisson_residual_synth_workspace_bytes.restype = c_size_t
     lib.odil_poisson_residual_synth_workspace_bytes.argtypes = [_I64P]
+    lib.odil_interp_adj_kind.restype = c_int
+    lib.odil_interp_adj_kind.argtypes = [_I64P, c_int, c_char_p, c_int]
+    lib.odil_mg_volumes_levels_ok.restype = c_int
+    lib.odil_mg_volumes_levels_ok.argtypes = [_I64P, c_int, c_int, c_int, c_int]
+    lib.odil_poisson_residual_synth_batch_workspace_bytes.restype = c_size_t
+    lib.odil_poisson_residual_synth_batch_workspace_bytes.argtypes = [_I64P]
+    lib.odil_poisson_residual_synth_batch_partials.restype = c_int64
+    lib.odil_poisson_residual_synth_batch_partials.argtypes = [_I64P]
     for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)
         fn = getattr(lib, name)
         fn.restype = c_int

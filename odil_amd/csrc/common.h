@@ -274,7 +274,9 @@ struct AdamArgs {
   const T* alpha_dev;  // optional: step size read from device memory (hipGraph replay of an epoch)
   // ensembles ([B, *shape] level arrays): member b reads alpha_dev[b * alpha_stride]; 0: one step size for all
   int64_t alpha_stride;
-  int member_axis;  // canonical axis of the transfer kernels that counts the members (1 or 2) when alpha_stride != 0
+  // canonical axis of the transfer kernels that counts the members when alpha_stride != 0: 1 ('.cc'), 2 ('.c'), or
+  // 0 ('.ccc': the leading volumes of the marching kernels)
+  int member_axis;
 };
 
 #ifdef __HIPCC__

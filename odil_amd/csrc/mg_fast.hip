@@ -272,8 +272,8 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_fast(const T* __restrict_
     if (gscaled) gscaled[ci] = scale * v;
     if (ad.x) {
       T xv = ad.x[ci], mv = ad.m[ci], vv = ad.v[ci];
-      // (ensembles: the member is the plane of a '.cc' batch, the row of a '.c' batch)
-      adam_update<T>(xv, mv, vv, gscaled ? scale * v : v, ad, ad.member_axis == 2 ? jy : p);
+      // (ensembles: the member is the plane of a '.cc' batch, the row of a '.c' batch, the volume of a '.ccc' batch)
+      adam_update<T>(xv, mv, vv, gscaled ? scale * v : v, ad, ad.member_axis == 2 ? jy : (ad.member_axis == 1 ? p : c0));
       ad.x[ci] = xv;
       ad.m[ci] = mv;
       ad.v[ci] = vv;

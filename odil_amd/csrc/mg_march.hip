@@ -1044,6 +1044,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_tile(const T* __restrict_
   gfine += fvol;
   c.gfine = gfine, c.gcoarse = gcoarse + cvol, c.gscaled = gscaled ? gscaled + cvol : nullptr;
   if (ad.x) ad.x += cvol, ad.m += cvol, ad.v += cvol;
+  if (ad.alpha_dev) ad.alpha_dev += (int64_t)blockIdx.y * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   c.scale = scale;
   c.z0 = zc * a.usched.ZC;
   const int z1 = c.z0 + a.usched.ZC < c.cnz ? c.z0 + a.usched.ZC : c.cnz;
@@ -1404,6 +1405,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_march_lead(const T* __res
   const bool node = a.lead_loc == kNode;
   int z0, z1, jy, jx0;
   if (!march_decode<CX>(a, z0, z1, jy, jx0)) return;
+  if (ad.alpha_dev) ad.alpha_dev += (int64_t)J0 * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   Adj6 ax[CX];
   column_taps<CX>(jx0, cnx, ax);
   const Adj6 ay = adj6(jy, cny);
@@ -1749,6 +1751,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_rows(const float* __restr
   const int64_t r = w / a.nzg;
   const int yc = (int)(r % a.nyc);
   const int64_t lead = r / a.nyc;
+  if (ad.alpha_dev) ad.alpha_dev += lead * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane >> a.lxlog, lx = lane & ((1 << a.lxlog) - 1), pw = 64 >> a.lxlog;
   const int cz_first = (zg * (kBlock / 64) + wave) * pw;
@@ -1774,10 +1777,10 @@ static bool adj_rows_enabled() {
   return !e || atoi(e) != 0;
 }
 
-// Launches k_interp_adj_rows when the volumes qualify; false: the caller keeps its kernel.
+// The work items of k_interp_adj_rows when the volumes qualify (fine16 / coarse8: the fine array is aligned to 16
+// bytes, the coarse one to 8); false: the caller keeps its kernel.
 template <typename T>
-static bool adj_rows_launch(const T* gfine, T* gcoarse, T* gscaled, const MarchArgs& m, T scale, hipStream_t stream,
-                            const AdamArgs<T>& ad) {
+static bool adj_rows_plan(const MarchArgs& m, bool fine16, bool coarse8, RowsArgs& r) {
   if constexpr (sizeof(T) != 4) {
     return false;
   } else {
@@ -1786,11 +1789,10 @@ static bool adj_rows_launch(const T* gfine, T* gcoarse, T* gscaled, const MarchA
     if (fnx != 64 && fnx != 128 && fnx != 256) return false;
     for (int i = 0; i < 3; ++i)
       if (m.fn[i] != 2 * m.cn[i] || m.cn[i] < 4) return false;
-    if (!aligned_to(gfine, 16) || !aligned_to(gcoarse, 8)) return false;
+    if (!fine16 || !coarse8) return false;
     // results are stored as 8-byte packs at gcoarse + lead * cvol + ...: an odd leading stride (a strided view handed
     // to odil_interp_adj_ld) would misalign every odd leading index
     if (m.lead_fn > 1 && (m.lead_cstride % 2) != 0) return false;
-    RowsArgs r;
     for (int i = 0; i < 3; ++i) r.cn[i] = m.cn[i], r.fn[i] = m.fn[i];
     r.lxlog = fnx == 256 ? 6 : (fnx == 128 ? 5 : 4);
     const int planes_per_group = (kBlock / 64) * (64 >> r.lxlog);
@@ -1805,6 +1807,19 @@ static bool adj_rows_launch(const T* gfine, T* gcoarse, T* gscaled, const MarchA
     if (r.per_xcd * kNumXcd >= ((int64_t)1 << 31)) return false;
     r.fvol = (int64_t)m.fn[0] * m.fn[1] * m.fn[2];
     r.cvol = m.lead_cstride;
+    return true;
+  }
+}
+
+// Launches k_interp_adj_rows when the volumes qualify; false: the caller keeps its kernel.
+template <typename T>
+static bool adj_rows_launch(const T* gfine, T* gcoarse, T* gscaled, const MarchArgs& m, T scale, hipStream_t stream,
+                            const AdamArgs<T>& ad) {
+  if constexpr (sizeof(T) != 4) {
+    return false;
+  } else {
+    RowsArgs r;
+    if (!adj_rows_plan<T>(m, aligned_to(gfine, 16), aligned_to(gcoarse, 8), r)) return false;
     hipLaunchKernelGGL(k_interp_adj_rows, dim3((unsigned)(r.per_xcd * kNumXcd)), dim3(kBlock), 0, stream, gfine, gcoarse,
                        gscaled, r, scale, ad);
     return true;
@@ -1829,17 +1844,38 @@ static bool adj_tile_enabled() {
   return !e || atoi(e) != 0;
 }
 
+// every chunk primes its window with two extra fine-plane reductions: prefer chunks of >= 8 planes
+static bool adj_small_level(const InterpArgs& a) { return a.cn[0] * a.cn[1] * a.cn[2] * a.cn[3] <= ((int64_t)1 << 22); }
+
+// (a strided coarse result is written by the kernels that index it through m.lead_cstride only, and never with a
+// scaled copy / an update of arrays of another layout: the caller checks the latter)
+static bool adj_tile_serves(const MarchArgs& m, const InterpArgs& a, int cx) {
+  return cx == 1 && m.cn[1] >= 2 * kTileY && m.cn[2] >= 2 * kTileX && adj_tile_enabled() && !a.coarse_ld;
+}
+
+// The kernel adj_launch<T, 1> runs for this layout on arrays aligned to 16 bytes; nothing is launched.  The decisions
+// are those of adj_launch below, through the same predicates.
+template <typename T>
+int interp_adj_kind(const InterpArgs& a) {
+  MarchArgs m;
+  if (!march_setup(m, a, 1, adj_small_level(a) ? ODIL_ADJ_UNITS_SMALL : ODIL_ADJ_UNITS))
+    return interp_fast_serves(a) ? kAdjFast : kAdjGeneric;
+  if (m.lead_fn != 1 ? m.lead_loc == kNode : a.loc[1] == kNode) return kAdjNode;
+  RowsArgs r;
+  if (adj_rows_plan<T>(m, true, true, r)) return kAdjRows;
+  return adj_tile_serves(m, a, 1) ? kAdjTile : kAdjMarch;
+}
+template int interp_adj_kind<double>(const InterpArgs&);
+template int interp_adj_kind<float>(const InterpArgs&);
+
 template <typename T, int CX>
 static int adj_launch(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& a, T scale, hipStream_t stream,
                       const AdamArgs<T>& ad) {
   MarchArgs m;
-  // every chunk primes its window with two extra fine-plane reductions: prefer chunks of >= 8 planes
-  const bool small_level = a.cn[0] * a.cn[1] * a.cn[2] * a.cn[3] <= ((int64_t)1 << 22);
+  const bool small_level = adj_small_level(a);
   if (!march_setup(m, a, CX, small_level ? ODIL_ADJ_UNITS_SMALL : ODIL_ADJ_UNITS)) return 0;
   const dim3 grid(unit_grid(m.usched), m.lead_cn);
-  // (a strided coarse result is written by the kernels that index it through m.lead_cstride only, and never with a
-  // scaled copy / an update of arrays of another layout: the caller checks the latter)
-  const bool tile_ok = CX == 1 && m.cn[1] >= 2 * kTileY && m.cn[2] >= 2 * kTileX && adj_tile_enabled() && !a.coarse_ld;
+  const bool tile_ok = adj_tile_serves(m, a, CX);
   // float: two coarse columns per thread (16 B per lane everywhere) when the rows allow it
   const bool tile_wide = sizeof(T) == 4 && m.cn[2] % 2 == 0 && m.cn[2] >= 4 * kTileX && aligned_to(gfine, 16);
   const int tile_cols = kTileX * (tile_wide ? 2 : 1);

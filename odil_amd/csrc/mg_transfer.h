@@ -156,4 +156,11 @@ template <typename T>
 int interp_adj_march(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& a, T scale, hipStream_t stream,
                      const AdamArgs<T>& ad);
 
+// The transposed prolongation interp_adj runs for a layout whose arrays are aligned to 16 bytes (nothing launched):
+// the rows / tile / march kernels of mg_march.hip (their summation orders differ), a node-centred marching kernel, the
+// fast kernel of mg_fast.hip, or the generic kernel.
+enum AdjKind { kAdjGeneric = 0, kAdjFast, kAdjNode, kAdjRows, kAdjTile, kAdjMarch };
+template <typename T>
+int interp_adj_kind(const InterpArgs& a);
+
 }  // namespace odil

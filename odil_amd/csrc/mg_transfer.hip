@@ -485,7 +485,10 @@ static int interp_adj(const T* gfine, T* gcoarse, T* gscaled, const int64_t* csh
   }
   if (ad.x && ad.alpha_stride) {
     // an ensemble with a step size per member: the fast kernel is the one that reads it (odil_mg_synth_adj_adam_batch
-    // has checked that it serves every level; never another arithmetic path, never a launch without the stride)
+    // has checked that it serves every level; never another arithmetic path, never a launch without the stride); the
+    // volumes of a '.ccc' ensemble (member_axis 0) go through the marching kernels first, as a single volume does
+    if (ad.member_axis == 0 && a.loc[0] == kNone && !coarse_ld)
+      if (int r = interp_adj_march<T>(gfine, gcoarse, gscaled, a, scale, (hipStream_t)stream, ad)) return r < 0 ? r : 0;
     if (int r = interp_adj_fast<T>(gfine, gcoarse, gscaled, a, scale, (hipStream_t)stream, ad)) return r < 0 ? r : 0;
     set_error("interp_adj: this layout has no kernel that reads a step size per member");
     return ODIL_E_INVAL;
@@ -762,6 +765,85 @@ static int mg_synth_adj_adam_batch(const T* gu, T* const* grads, const int64_t* 
                          eps, alpha_dev, alpha_stride, ndim == 2 ? 1 : 2);
 }
 
+// Does every transfer level of nbatch 3-D members ([nbatch, *shape] arrays, layout '.ccc', aligned to 16 bytes) run
+// the transposed prolongation that the same level of ONE member ('ccc') runs -- rows, tile, march or fast kernel, each
+// with a summation order of its own?  Their chunks and grids depend on the leading extent, a coarse value is formed by
+// one thread from its own window either way.  The generic kernel (its update is a launch of its own that reads one step
+// size) is refused.  Fills bshapes with the nlvl x 4 batched extents.  Nothing is launched.
+template <typename T>
+static int volumes_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, int nbatch,
+                                int64_t* bshapes) {
+  if (ndim != 3 || !shapes) {
+    set_error("%s: ndim %d (this ensemble runs 3-D members) or null shapes", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1 ... 65535)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (nlvl < 2 || nlvl > ODIL_MAX_LEVELS) {
+    set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
+    return ODIL_E_INVAL;
+  }
+  for (int l = 0; l < nlvl; ++l) {
+    bshapes[l * 4] = nbatch;
+    for (int d = 0; d < 3; ++d) bshapes[l * 4 + 1 + d] = shapes[l * 3 + d];
+  }
+  if (int e = check_levels(shapes, nlvl, 3, "ccc")) return e;
+  for (int l = 1; l < nlvl; ++l) {
+    InterpArgs one, all;
+    if (int e = fill_interp_args(one, shapes + l * 3, 3, "ccc")) return e;
+    if (int e = fill_interp_args(all, bshapes + l * 4, 4, ".ccc")) return e;
+    const int k1 = interp_adj_kind<T>(one), kb = interp_adj_kind<T>(all);
+    if (k1 != kb || k1 == kAdjGeneric || k1 == kAdjNode) {
+      set_error("%s: level %d of %d members would not run the transfer kernel one member runs", what, l, nbatch);
+      return ODIL_E_INVAL;
+    }
+  }
+  return 0;
+}
+
+// mg_synth_adj with the updates on [B, *shape] level arrays of B 3-D members (layout '.ccc'): the launches of a
+// single volume's chain, each covering all members, member b with its own step size.
+template <typename T>
+static int mg_synth_adj_adam_volumes(const T* gu, T* const* grads, const int64_t* shapes, int nlvl, int ndim, int nbatch,
+                                     T* const* ax, T* const* am, T* const* av, T omb1, T omb2, T eps,
+                                     const T* alpha_dev, int64_t alpha_stride, void* stream) {
+  static const char* what = "mg_synth_adj_adam_volumes";
+  if (ndim != 3) {
+    set_error("%s: ndim %d (this ensemble runs 3-D members)", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (!gu || !grads || !shapes || !ax || !am || !av || !alpha_dev) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (alpha_stride < 0) {
+    set_error("%s: step-size stride %lld is negative", what, (long long)alpha_stride);
+    return ODIL_E_INVAL;
+  }
+  int64_t bshapes[ODIL_MAX_LEVELS * 4];
+  if (int e = volumes_levels_check<T>(what, shapes, nlvl, ndim, nbatch, bshapes)) return e;
+  for (int l = 1; l < nlvl; ++l)
+    if (!grads[l] || !ax[l] || !am[l] || !av[l]) {
+      set_error("%s: null level array (level %d)", what, l);
+      return ODIL_E_INVAL;
+    }
+  // (the answer above is that of arrays aligned to 16 bytes; a level of a member is a multiple of 8 elements)
+  for (int l = 0; l < nlvl; ++l) {
+    const T* g = l == 0 ? gu : grads[l];
+    if (reinterpret_cast<uintptr_t>(g) % 16 != 0) {
+      set_error("%s: gradient array of level %d is not aligned to 16 bytes", what, l);
+      return ODIL_E_INVAL;
+    }
+  }
+  // grads[0] is gu itself or not wanted: the chain reads gu
+  T* g0[ODIL_MAX_LEVELS];
+  for (int l = 0; l < nlvl; ++l) g0[l] = l == 0 ? nullptr : grads[l];
+  return mg_synth_adj<T>(gu, g0, nullptr, nullptr, bshapes, nlvl, 4, ".ccc", stream, ax, am, av, T(0), omb1, omb2, eps,
+                         alpha_dev, alpha_stride, 0);
+}
+
 }  // namespace odil
 
 using namespace odil;
@@ -871,6 +953,39 @@ int odil_mg_synth_adj_adam_f32(const float* gu, float* const* grads, const float
 int odil_mg_batch_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch) {
   int64_t bshapes[ODIL_MAX_LEVELS * 3];
   return batch_levels_check("mg_batch_levels", shapes, nlvl, ndim, nbatch, bshapes);
+}
+int odil_interp_adj_kind(const int64_t* cshape, int ndim, const char* loc, int elem_size) {
+  InterpArgs a;
+  if (!cshape || (elem_size != 8 && elem_size != 4)) {
+    set_error("interp_adj_kind: null shape or element size %d (8 or 4)", elem_size);
+    return ODIL_E_INVAL;
+  }
+  if (int e = fill_interp_args(a, cshape, ndim, loc)) return e;
+  if (a.loc[0] == kNode && a.loc[1] == kNone && a.loc[2] == kNone && a.loc[3] == kNone) return kAdjNode;
+  return elem_size == 8 ? interp_adj_kind<double>(a) : interp_adj_kind<float>(a);
+}
+int odil_mg_volumes_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch, int elem_size) {
+  int64_t bshapes[ODIL_MAX_LEVELS * 4];
+  if (elem_size != 8 && elem_size != 4) {
+    set_error("mg_volumes_levels: element size %d (8 or 4)", elem_size);
+    return ODIL_E_INVAL;
+  }
+  return elem_size == 8 ? volumes_levels_check<double>("mg_volumes_levels", shapes, nlvl, ndim, nbatch, bshapes)
+                        : volumes_levels_check<float>("mg_volumes_levels", shapes, nlvl, ndim, nbatch, bshapes);
+}
+int odil_mg_synth_adj_adam_volumes_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       int nbatch, double* const* x, double* const* m, double* const* v,
+                                       double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                       int64_t alpha_stride, void* stream) {
+  return mg_synth_adj_adam_volumes<double>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2,
+                                           eps, alpha_dev, alpha_stride, stream);
+}
+int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
+                                       float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
+                                       void* stream) {
+  return mg_synth_adj_adam_volumes<float>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2,
+                                          eps, alpha_dev, alpha_stride, stream);
 }
 int odil_mg_synth_adj_adam_batch_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
                                      int nbatch, double* const* x, double* const* m, double* const* v, double one_minus_b1,

@@ -144,4 +144,11 @@ inline H2<T> make_h2(const T h[3]) {
   return r;
 }
 
+// An ensemble of B members of one shape: member blockIdx.y runs the single walk on its own arrays.
+struct BatchStrides {
+  // elements between members: (u, rhs, fu) of the residual, (fu, g, x, m, v) of the adjoint, (w0, rhs, fu, coarse,
+  // column sums) of the residual with the last prolongation fused in
+  int64_t s[5];
+};
+
 }  // namespace odil

@@ -115,10 +115,6 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual(const T* __restrict
 
 // An ensemble of B members of one shape: member blockIdx.y runs the walk above on its own arrays and writes its partial
 // sums to its own row of the [B, grid] workspace, so its loss is summed in the order of its single launch.
-struct BatchStrides {
-  int64_t s[5];  // elements between members: (u, rhs, fu) of the residual, (fu, g, x, m, v) of the adjoint
-};
-
 template <typename T, bool FULL>
 __global__ __launch_bounds__(kBlock) void k_poisson_residual_batch(const T* __restrict__ u, const T* __restrict__ rhs,
                                                                   T* __restrict__ fu, BatchStrides st, StencilArgs a,
@@ -615,8 +611,12 @@ static int poisson_adjoint(const T* fu, T* gu, const int64_t* shape, int ndim, c
 // What the batched launchers refuse before anything is launched (the ensemble forms of residual and adjoint).
 template <typename T>
 static int batch_args(const char* what, StencilArgs& a, T h[3], const int64_t* shape, int ndim, const T* h2, int nbatch,
-                      const int64_t* strides, int nstrides) {
-  if (ndim < 1 || ndim > 2) {
+                      const int64_t* strides, int nstrides, bool volumes = false) {
+  if (volumes && ndim != 3) {
+    set_error("%s: ndim %d (this ensemble runs 3-D members)", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (!volumes && (ndim < 1 || ndim > 2)) {
     set_error("%s: ndim %d (the ensemble runs 1-D and 2-D members)", what, ndim);
     return ODIL_E_INVAL;
   }
@@ -686,8 +686,8 @@ template <typename T>
 static int poisson_adjoint_adam_batch(const T* fu, T* gu, T* x, T* m, T* v, int nbatch, int64_t fu_stride,
                                       int64_t g_stride, int64_t x_stride, int64_t m_stride, int64_t v_stride,
                                       const int64_t* shape, int ndim, const T* h2, T scale, T omb1, T omb2, T eps,
-                                      const T* alpha_dev, int64_t alpha_stride, void* stream) {
-  static const char* what = "poisson_adjoint_adam_batch";
+                                      const T* alpha_dev, int64_t alpha_stride, void* stream, bool volumes = false) {
+  const char* what = volumes ? "poisson_adjoint_adam_volumes" : "poisson_adjoint_adam_batch";
   if (!fu || !x || !m || !v || !alpha_dev) {  // (gu == NULL: the gradient is consumed by the update, not stored)
     set_error("%s: null pointer", what);
     return ODIL_E_INVAL;
@@ -700,7 +700,7 @@ static int poisson_adjoint_adam_batch(const T* fu, T* gu, T* x, T* m, T* v, int 
   T h[3];
   BatchStrides st = {{fu_stride, g_stride, x_stride, m_stride, v_stride}};
   if (!gu) st.s[1] = fu_stride;  // (not used)
-  if (int e = batch_args<T>(what, a, h, shape, ndim, h2, nbatch, st.s, 5)) return e;
+  if (int e = batch_args<T>(what, a, h, shape, ndim, h2, nbatch, st.s, 5, volumes)) return e;
   a.loss_z0 = a.loss_z1 = 0;
   const AdamArgs<T> ad{x, m, v, T(0), omb1, omb2, eps, alpha_dev, alpha_stride, 0};
   const dim3 grid(unit_grid(a.usched), nbatch);
@@ -922,6 +922,24 @@ int odil_poisson_adjoint_adam_batch_f64(const double* fu, double* gu, double* x,
   return poisson_adjoint_adam_batch<double>(fu, gu, x, m, v, nbatch, fu_stride, g_stride, x_stride, m_stride, v_stride,
                                             shape, ndim, h2, scale, one_minus_b1, one_minus_b2, eps, alpha_dev,
                                             alpha_stride, stream);
+}
+int odil_poisson_adjoint_adam_volumes_f64(const double* fu, double* gu, double* x, double* m, double* v, int nbatch,
+                                          int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                          int64_t v_stride, const int64_t* shape, int ndim, const double* h2,
+                                          double scale, double one_minus_b1, double one_minus_b2, double eps,
+                                          const double* alpha_dev, int64_t alpha_stride, void* stream) {
+  return poisson_adjoint_adam_batch<double>(fu, gu, x, m, v, nbatch, fu_stride, g_stride, x_stride, m_stride, v_stride,
+                                            shape, ndim, h2, scale, one_minus_b1, one_minus_b2, eps, alpha_dev,
+                                            alpha_stride, stream, true);
+}
+int odil_poisson_adjoint_adam_volumes_f32(const float* fu, float* gu, float* x, float* m, float* v, int nbatch,
+                                          int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,
+                                          int64_t v_stride, const int64_t* shape, int ndim, const float* h2, float scale,
+                                          float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
+                                          int64_t alpha_stride, void* stream) {
+  return poisson_adjoint_adam_batch<float>(fu, gu, x, m, v, nbatch, fu_stride, g_stride, x_stride, m_stride, v_stride,
+                                           shape, ndim, h2, scale, one_minus_b1, one_minus_b2, eps, alpha_dev,
+                                           alpha_stride, stream, true);
 }
 int odil_poisson_adjoint_adam_batch_f32(const float* fu, float* gu, float* x, float* m, float* v, int nbatch,
                                         int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,

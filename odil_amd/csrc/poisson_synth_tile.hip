@@ -75,12 +75,13 @@ struct StepLoads {
   T ring[2];                               // w0 of the thread's pair of ring cells
 };
 
+// The walk of one workgroup over its tile and z-chunk of ONE volume (the single launch, and member blockIdx.y of the
+// ensemble launch on its own pointers).
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_poisson_residual_tile(const T* __restrict__ coarse,
-                                                                  const T* __restrict__ w0,
-                                                                  const T* __restrict__ rhs, T* __restrict__ fu,
-                                                                  SynthTileArgs a, H2<T> h,
-                                                                  double* __restrict__ column_sums) {
+__device__ __forceinline__ void residual_tile_walk(const T* __restrict__ coarse, const T* __restrict__ w0,
+                                                   const T* __restrict__ rhs, T* __restrict__ fu,
+                                                   const SynthTileArgs& a, const H2<T>& h,
+                                                   double* __restrict__ column_sums) {
   __shared__ T cs[3][kCoarseCells];
   __shared__ T fs[2][kFineRows * kFinePitch];
   const int cnz = a.cn[0], cny = a.cn[1], cnx = a.cn[2];
@@ -307,10 +308,31 @@ __global__ __launch_bounds__(kBlock) void k_poisson_residual_tile(const T* __res
   if (valid) column_sums[((int64_t)zc * cny + jy) * cnx + jx] = local;
 }
 
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_poisson_residual_tile(const T* __restrict__ coarse,
+                                                                  const T* __restrict__ w0,
+                                                                  const T* __restrict__ rhs, T* __restrict__ fu,
+                                                                  SynthTileArgs a, H2<T> h,
+                                                                  double* __restrict__ column_sums) {
+  residual_tile_walk<T>(coarse, w0, rhs, fu, a, h, column_sums);
+}
+
+// The ensemble form: member blockIdx.y on its own arrays (element strides: w0, rhs, fu, coarse, column sums).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_poisson_residual_tile_batch(const T* __restrict__ coarse,
+                                                                        const T* __restrict__ w0,
+                                                                        const T* __restrict__ rhs, T* __restrict__ fu,
+                                                                        BatchStrides st, SynthTileArgs a, H2<T> h,
+                                                                        double* __restrict__ column_sums) {
+  const int64_t b = blockIdx.y;
+  residual_tile_walk<T>(coarse + b * st.s[3], w0 + b * st.s[0], rhs + b * st.s[1], fu + b * st.s[2], a, h,
+                        column_sums + b * st.s[4]);
+}
+
 // The workgroup reduction of the marching layout over the column sums: workgroup b sums the threads of its unit in
 // block_sum's order into partials[b].
-__global__ __launch_bounds__(kBlock) void k_synth_loss_replay(const double* __restrict__ column_sums, MarchArgs a,
-                                                              double* __restrict__ partials) {
+__device__ __forceinline__ void synth_loss_replay(const double* __restrict__ column_sums, const MarchArgs& a,
+                                                  double* __restrict__ partials) {
   const int cny = a.cn[1], cnx = a.cn[2];
   double local = 0.0;
   int zc, yt, xt;
@@ -320,6 +342,20 @@ __global__ __launch_bounds__(kBlock) void k_synth_loss_replay(const double* __re
   if (have && jy < cny && jx < cnx) local = column_sums[((int64_t)zc * cny + jy) * cnx + jx];
   const double total = block_sum(local);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kBlock) void k_synth_loss_replay(const double* __restrict__ column_sums, MarchArgs a,
+                                                              double* __restrict__ partials) {
+  synth_loss_replay(column_sums, a, partials);
+}
+
+// The ensemble form: member blockIdx.y reduces its own column sums into its own row of the [B, grid] partial sums.
+__global__ __launch_bounds__(kBlock) void k_synth_loss_replay_batch(const double* __restrict__ column_sums,
+                                                                    int64_t sums_stride, MarchArgs a,
+                                                                    double* __restrict__ partials,
+                                                                    int64_t partials_stride) {
+  const int64_t b = blockIdx.y;
+  synth_loss_replay(column_sums + b * sums_stride, a, partials + b * partials_stride);
 }
 
 static size_t column_sums_bytes(const SynthArgs& sa) {
@@ -367,6 +403,88 @@ static int poisson_residual_synth(const T* coarse, const T* w0, const T* rhs, T*
   return launch_final_reduce<T>(partials, grid, 0, 1, size, loss, (hipStream_t)stream);
 }
 
+// The ensemble form of poisson_residual_synth: nbatch members of one shape, each launch covering all of them.  Member
+// b's loss is summed in the order of its single run: its own column sums, its own row of partial sums, one row of the
+// final reduction.
+template <typename T>
+static int poisson_residual_synth_batch(const T* coarse, const T* w0, const T* rhs, T* fu, int nbatch, int64_t w0_stride,
+                                        int64_t rhs_stride, int64_t fu_stride, const int64_t* cshape, int ndim,
+                                        const T* h2, double* partials, int64_t partials_stride, int64_t partials_len,
+                                        double* column_sums, size_t column_sums_size, T* loss, void* stream) {
+  static const char* what = "poisson_residual_synth_batch";
+  if (ndim != 3) {
+    set_error("%s: ndim %d (this ensemble runs 3-D members)", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  if (!coarse || !w0 || !rhs || !fu || !cshape || !h2 || !partials || !column_sums || !loss) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1 ... 65535, one grid row each)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  SynthArgs sa;
+  if (int e = synth_geometry<T>(w0, rhs, fu, cshape, sa)) return e;
+  const MarchArgs& m = sa.m;
+  const int64_t cells = (int64_t)m.fn[0] * m.fn[1] * m.fn[2];
+  const int64_t strides[3] = {w0_stride, rhs_stride, fu_stride};
+  for (int k = 0; k < 3; ++k) {
+    if (strides[k] < cells) {
+      set_error("%s: member stride %lld is smaller than a member (%lld cells)", what, (long long)strides[k],
+                (long long)cells);
+      return ODIL_E_INVAL;
+    }
+    // (the 16 B accesses of the own pairs assume member 0's alignment for every member)
+    if ((strides[k] * (int64_t)sizeof(T)) % 16 != 0) {
+      set_error("%s: member stride %lld is not a multiple of 16 bytes", what, (long long)strides[k]);
+      return ODIL_E_INVAL;
+    }
+  }
+  const int grid = unit_grid(m.usched);
+  if (grid > kMaxPartials) {
+    set_error("%s: %d workgroups exceed the reduction workspace", what, grid);
+    return ODIL_E_INVAL;
+  }
+  if (partials_stride < grid || partials_stride >= ((int64_t)1 << 31)) {
+    set_error("%s: partials workspace too small: rows of %lld doubles, a member needs %d", what,
+              (long long)partials_stride, grid);
+    return ODIL_E_INVAL;
+  }
+  if (partials_len < (int64_t)(nbatch - 1) * partials_stride + grid) {
+    set_error("%s: partials workspace too small: %lld doubles are fewer than %d rows of %lld", what,
+              (long long)partials_len, nbatch, (long long)partials_stride);
+    return ODIL_E_INVAL;
+  }
+  const size_t per_member = column_sums_bytes(sa);
+  if (column_sums_size / (size_t)nbatch < per_member) {
+    set_error("%s: column sums need %lld bytes per member, %lld given for %d members", what, (long long)per_member,
+              (long long)column_sums_size, nbatch);
+    return ODIL_E_INVAL;
+  }
+  SynthTileArgs ta;
+  for (int i = 0; i < 3; ++i) ta.cn[i] = m.cn[i];
+  const int64_t ytiles = (m.cn[1] + kTileY - 1) / kTileY, xtiles = (m.cn[2] + kTileX - 1) / kTileX;
+  if ((int64_t)m.usched.ZCH * (ytiles + kNumXcd) * xtiles >= ((int64_t)1 << 31)) {
+    set_error("%s: grid too large for one launch", what);
+    return ODIL_E_INVAL;
+  }
+  ta.usched = make_unit_sched_chunked(m.cn[0], ytiles, xtiles, m.usched.ZC);
+  ta.loss_z0 = 0;
+  ta.loss_z1 = m.fn[0];
+  T hh[3] = {h2[0], h2[1], h2[2]};
+  const int64_t sums_stride = (int64_t)(per_member / sizeof(double));
+  const BatchStrides st = {{w0_stride, rhs_stride, fu_stride, (int64_t)m.cn[0] * m.cn[1] * m.cn[2], sums_stride}};
+  hipLaunchKernelGGL((k_poisson_residual_tile_batch<T>), dim3(unit_grid(ta.usched), nbatch), dim3(kBlock), 0,
+                     (hipStream_t)stream, coarse, w0, rhs, fu, st, ta, make_h2<T>(hh), column_sums);
+  if (int e = check_launch("k_poisson_residual_tile_batch")) return e;
+  hipLaunchKernelGGL(k_synth_loss_replay_batch, dim3(grid, nbatch), dim3(kBlock), 0, (hipStream_t)stream, column_sums,
+                     sums_stride, m, partials, partials_stride);
+  if (int e = check_launch("k_synth_loss_replay_batch")) return e;
+  return launch_final_reduce<T>(partials, grid, (int)partials_stride, nbatch, (double)m.fn[0] * m.fn[1] * m.fn[2], loss,
+                                (hipStream_t)stream);
+}
+
 }  // namespace odil
 
 using namespace odil;
@@ -376,6 +494,33 @@ size_t odil_poisson_residual_synth_workspace_bytes(const int64_t* cshape) {
   SynthArgs sa;
   if (!cshape || synth_geometry<double>(nullptr, nullptr, nullptr, cshape, sa)) return 0;
   return column_sums_bytes(sa);
+}
+size_t odil_poisson_residual_synth_batch_workspace_bytes(const int64_t* cshape) {
+  return odil_poisson_residual_synth_workspace_bytes(cshape);  // per member
+}
+int64_t odil_poisson_residual_synth_batch_partials(const int64_t* cshape) {
+  SynthArgs sa;
+  if (!cshape || synth_geometry<double>(nullptr, nullptr, nullptr, cshape, sa)) return 0;
+  const int grid = unit_grid(sa.m.usched);
+  return grid > kMaxPartials ? 0 : grid;
+}
+int odil_poisson_residual_synth_batch_f64(const double* coarse, const double* w0, const double* rhs, double* fu,
+                                          int nbatch, int64_t w0_stride, int64_t rhs_stride, int64_t fu_stride,
+                                          const int64_t* cshape, int ndim, const double* h2, double* partials,
+                                          int64_t partials_stride, int64_t partials_len, double* column_sums,
+                                          size_t column_sums_size, double* loss, void* stream) {
+  return poisson_residual_synth_batch<double>(coarse, w0, rhs, fu, nbatch, w0_stride, rhs_stride, fu_stride, cshape, ndim,
+                                              h2, partials, partials_stride, partials_len, column_sums, column_sums_size,
+                                              loss, stream);
+}
+int odil_poisson_residual_synth_batch_f32(const float* coarse, const float* w0, const float* rhs, float* fu, int nbatch,
+                                          int64_t w0_stride, int64_t rhs_stride, int64_t fu_stride,
+                                          const int64_t* cshape, int ndim, const float* h2, double* partials,
+                                          int64_t partials_stride, int64_t partials_len, double* column_sums,
+                                          size_t column_sums_size, float* loss, void* stream) {
+  return poisson_residual_synth_batch<float>(coarse, w0, rhs, fu, nbatch, w0_stride, rhs_stride, fu_stride, cshape, ndim,
+                                             h2, partials, partials_stride, partials_len, column_sums, column_sums_size,
+                                             loss, stream);
 }
 int odil_poisson_residual_synth_f64(const double* coarse, const double* w0, const double* rhs, double* fu,
                                     const int64_t* cshape, const double* h2, int64_t z0, int64_t z1, double denom,

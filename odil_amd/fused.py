@@ -255,7 +255,54 @@ class PoissonEnsemble:
                                        alphas, omb1, omb2, eps, losses, norms, self.partials)
 
 
-class PoissonLaunchEnsemble:
+class BatchedLaunches:
+    """What the ensembles that run as batched launches share (PoissonLaunchEnsemble, PoissonVolumeEnsemble): level-major
+    [B, *shape] storage, the refusal of members that differ, and epochs one at a time -- the interface
+    `AdamNativeOptimizer.run_ensemble` drives."""
+
+    shape_refusal = None  # (shapes, dtype) -> reason or None: the form's predicate
+
+    @staticmethod
+    def members(nb, shape, wide=0, **kw):
+        """Zeroed [nb, *shape] tensor with `wide` extra elements between its contiguous members."""
+        cells = math.prod(shape)
+        base = torch.zeros(nb * (cells + wide), **kw)
+        strides = [math.prod(shape[k + 1:]) for k in range(len(shape))]
+        return base.as_strided((nb,) + tuple(shape), [cells + wide] + strides)
+
+    @classmethod
+    def refusal(cls, evaluators):
+        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
+        if not evaluators:
+            return 0, "an ensemble needs at least one member"
+        first = evaluators[0]
+        for b, ev in enumerate(evaluators):
+            if not isinstance(ev, PoissonEvaluator):
+                return b, "the operator is not the recognised Poisson stencil"
+            reason = cls.shape_refusal(ev.shapes, ev.dtype)
+            if reason is not None:
+                return b, reason
+            for what in ("cshape", "shapes", "dtype", "device"):
+                if getattr(ev, what) != getattr(first, what):
+                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
+            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
+                return b, "grid spacing differs from member 0's"
+        return None
+
+    def levels(self, packed, member):
+        """The level arrays of one member: views of the [B, *shape] level tensors."""
+        return [t[member] for t in packed]
+
+    def epochs(self, alphas, losses, norms, omb1, omb2, eps):
+        """losses.shape[1] epochs (the interface of PoissonEnsemble.epochs).  alphas: [B, E], or [E] shared by all members."""
+        for e in range(losses.shape[1]):
+            self.epoch(alphas[..., e].contiguous().view(-1), omb1, omb2, eps)
+            torch.sqrt(self.loss, out=self.norm)
+            losses[:, e].copy_(self.loss)
+            norms[:, e].copy_(self.norm)
+
+
+class PoissonLaunchEnsemble(BatchedLaunches):
     """B recognised Poisson problems of one shape and ANY 1-D / 2-D size side by side, as batched launches: an epoch is the
     launches of `PoissonEvaluator.loss_grad_arrays(adam=...)` for a 2-D problem -- synthesis, residual + loss, adjoint +
     update of level 0, transposed prolongations + updates of the other levels -- each covering all B members
@@ -278,13 +325,7 @@ class PoissonLaunchEnsemble:
         self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
         self.names = [e.names for e in evaluators]
         nb, kw = self.nbatch, dict(dtype=self.dtype, device=self.device)
-
-        def members(shape, wide=0):
-            cells = math.prod(shape)
-            base = torch.zeros(nb * (cells + wide), **kw)
-            strides = [math.prod(shape[k + 1:]) for k in range(len(shape))]
-            return base.as_strided((nb,) + tuple(shape), [cells + wide] + strides)
-
+        members = lambda shape, wide=0: self.members(nb, shape, wide, **kw)
         level = lambda wide0=0: [members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
         self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
         self.u, self.fu, self.rhs = members(self.cshape), members(self.cshape, pad), members(self.cshape, pad)
@@ -294,28 +335,7 @@ class PoissonLaunchEnsemble:
         self.partials = torch.empty((nb, npart), dtype=torch.float64, device=self.device)
         self.loss, self.norm = torch.zeros(nb, **kw), torch.zeros(nb, **kw)
 
-    @staticmethod
-    def refusal(evaluators):
-        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
-        if not evaluators:
-            return 0, "an ensemble needs at least one member"
-        first = evaluators[0]
-        for b, ev in enumerate(evaluators):
-            if not isinstance(ev, PoissonEvaluator):
-                return b, "the operator is not the recognised Poisson stencil"
-            reason = launches_refusal(ev.shapes, ev.dtype)
-            if reason is not None:
-                return b, reason
-            for what in ("cshape", "shapes", "dtype", "device"):
-                if getattr(ev, what) != getattr(first, what):
-                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
-            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
-                return b, "grid spacing differs from member 0's"
-        return None
-
-    def levels(self, packed, member):
-        """The level arrays of one member: views of the [B, *shape] level tensors."""
-        return [t[member] for t in packed]
+    shape_refusal = staticmethod(lambda shapes, dtype: launches_refusal(shapes, dtype))
 
     def epoch(self, alphas, omb1, omb2, eps):
         """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
@@ -326,13 +346,99 @@ class PoissonLaunchEnsemble:
                                        omb2, eps)
         ops.mg_synth_adj_adam_batch(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
 
-    def epochs(self, alphas, losses, norms, omb1, omb2, eps):
-        """losses.shape[1] epochs (the interface of PoissonEnsemble.epochs).  alphas: [B, E], or [E] shared by all members."""
-        for e in range(losses.shape[1]):
-            self.epoch(alphas[..., e].contiguous().view(-1), omb1, omb2, eps)
-            torch.sqrt(self.loss, out=self.norm)
-            losses[:, e].copy_(self.loss)
-            norms[:, e].copy_(self.norm)
+
+class PoissonVolumeEnsemble(BatchedLaunches):
+    """B recognised 3-D Poisson problems of one shape side by side, as batched launches: an epoch is the launches of
+    `PoissonEvaluator.loss_grad_arrays(adam=...)` for a 3-D problem through its separate kernels -- synthesis of the
+    coarse levels, residual with the last prolongation fused in + loss, adjoint + update of level 0, transposed
+    prolongations + updates of the other levels -- each covering all B members (odil_mg_synth on [B, *shape] arrays,
+    odil_poisson_residual_synth_batch, odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_volumes).  Level-major
+    storage as in PoissonLaunchEnsemble.  Member b computes what its single run computes, bit for bit -- also where the
+    single run takes the one-pass adjoint + first transpose launch, which equals the separate kernels bit for bit.
+    pad: extra elements between the members of the arrays that only the stencil kernels touch (fu, rhs, m[0], v[0])."""
+
+    def __init__(self, evaluators, pad=0):
+        reason = self.refusal(evaluators)
+        if reason is not None:
+            raise ValueError("ensemble member {}: {}".format(*reason))
+        ev = evaluators[0]
+        # (every transfer level of the batch must run the kernel that level of a single member runs: asked before the
+        # first launch)
+        reason = _volume_levels_refusal(ev.shapes, len(evaluators), ev.dtype)
+        if reason is not None:
+            raise ValueError("ensemble of {} members: {}".format(len(evaluators), reason))
+        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
+        self.cshape, self.ndim, self.loc, self.scale = ev.cshape, ev.ndim, "." + ev.loc, float(ev.scale)
+        self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
+        self.names = [e.names for e in evaluators]
+        nb, kw = self.nbatch, dict(dtype=self.dtype, device=self.device)
+        members = lambda shape, wide=0: self.members(nb, shape, wide, **kw)
+        level = lambda wide0=0: [members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
+        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
+        self.fu, self.rhs = members(self.cshape, pad), members(self.cshape, pad)
+        self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
+        # synthesis scratch of the levels 1 ... nlvl - 2 (level 1: the coarse operand of the residual)
+        self.work = [None] + [members(s) for s in self.shapes[1:-1]] + [None]
+        nsums, npart = ops.residual_synth_batch_workspace(self.shapes[1])
+        self.sums = torch.empty((nb, nsums), dtype=torch.float64, device=self.device)
+        self.partials = torch.empty((nb, npart), dtype=torch.float64, device=self.device)
+        self.loss, self.norm = torch.zeros(nb, **kw), torch.zeros(nb, **kw)
+
+    shape_refusal = staticmethod(lambda shapes, dtype: volumes_refusal(shapes, dtype))
+
+    def epoch(self, alphas, omb1, omb2, eps):
+        """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
+        losses the epoch evaluated (before its update) land in self.loss."""
+        if self.nlvl > 2:
+            coarse = ops.mg_synth(self.x[1:], self.loc, work=[None] + self.work[2:], out=self.work[1])
+        else:
+            coarse = self.x[1]
+        ops.poisson_residual_synth_batch(coarse, self.x[0], self.rhs, self.h2, self.fu, self.loss, self.partials, self.sums)
+        ops.poisson_adjoint_adam_volumes(self.fu, self.h2, self.scale, self.g[0], self.x[0], self.m[0], self.v[0], alphas,
+                                         omb1, omb2, eps)
+        ops.mg_synth_adj_adam_volumes(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+
+
+def _volume_levels_refusal(shapes, nbatch, dtype):
+    """The library's answer (odil_mg_volumes_levels_ok): why a transfer level of `nbatch` 3-D members of these level
+    shapes would not run the kernel that level of one member runs, or None."""
+    from ._lib import i64, load
+
+    lib = load()
+    flat = [int(n) for shape in shapes for n in shape]
+    if lib.odil_mg_volumes_levels_ok(i64(flat), len(shapes), len(shapes[0]), int(nbatch),
+                                     4 if dtype == torch.float32 else 8) == 0:
+        return None
+    return lib.odil_last_error().decode()
+
+
+def volumes_refusal(shapes, dtype=None):
+    """Why levels of these shapes are not run as batched launches of 3-D members (PoissonVolumeEnsemble), or None when
+    they are.  From the shapes (and, for the alignment of the members and the transfer kernels, the dtype) alone; the
+    limits of the kernels are the library's."""
+    ndim, nlvl = len(shapes[0]), len(shapes)
+    if ndim != 3:
+        return "{}-D grid: the batched launches of volumes run 3-D grids".format(ndim)
+    if nlvl < 2:
+        return "1 level: the batched launches need a multigrid field of at least 2 levels"
+    if dtype is not None and (math.prod(shapes[0]) * (8 if dtype == torch.float64 else 4)) % 16:
+        return "a member of {} cells is not a multiple of 16 bytes (members lie back to back)".format(math.prod(shapes[0]))
+    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):
+        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
+    if any(n < 4 for n in shapes[0]):
+        return "levels {}: every extent of the finest level must be at least 4".format([tuple(s) for s in shapes])
+    if any(n < 2 for n in shapes[-1]):
+        return "levels {}: every extent must be at least 2".format([tuple(s) for s in shapes])
+    if dtype == torch.float32 and ops.adjoint_transpose_supported(shapes[0]):
+        # a single run of this shape takes the one-pass adjoint + first transpose launch, which sums the transpose in
+        # the LDS-tile kernel's order; the ensemble runs the separate kernels, and where the separate first transpose
+        # is the row-marching kernel (float rows of 64 ... 256 cells) it rounds differently in the last bits
+        from ._lib import i64, load
+
+        if load().odil_interp_adj_kind(i64(shapes[1]), 3, b"ccc", 4) == 3:
+            return ("levels {}: a float32 run of this shape takes the one-pass adjoint + transpose launch, and the "
+                    "separate row-marching transpose of the ensemble rounds differently").format([tuple(s) for s in shapes])
+    return _volume_levels_refusal(shapes, 1, dtype)
 
 
 def _levels_refusal(shapes, nbatch):
@@ -366,11 +472,14 @@ def launches_refusal(shapes, dtype=None):
 
 
 def ensemble_form(form, shapes, dtype):
-    """'workgroup' or 'launches': the form `util.optimize_ensemble(form=...)` runs members of these level shapes in.  A
-    function of shapes and dtype alone; 'auto' takes the one-workgroup epochs when `small_refusal` admits the members."""
-    if form not in ("workgroup", "launches", "auto"):
-        raise ValueError("optimize_ensemble: form '{}' is none of 'workgroup', 'launches', 'auto'".format(form))
+    """'workgroup', 'launches' or 'volumes': the form `util.optimize_ensemble(form=...)` runs members of these level
+    shapes in.  A function of shapes and dtype alone; 'auto' takes 'volumes' for 3-D members, else the one-workgroup
+    epochs when `small_refusal` admits the members."""
+    if form not in ("workgroup", "launches", "volumes", "auto"):
+        raise ValueError("optimize_ensemble: form '{}' is none of 'workgroup', 'launches', 'volumes', 'auto'".format(form))
     if form == "auto":
+        if len(shapes[0]) == 3:
+            return "volumes"
         return "workgroup" if small_refusal(shapes, dtype) is None else "launches"
     return form
 

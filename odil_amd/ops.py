@@ -607,6 +607,66 @@ def mg_synth_adj_adam_batch(gu, shapes, grads, x, m, v, alphas, one_minus_b1, on
     return grads
 
 
+def residual_synth_batch_workspace(cshape):
+    """(float64 column sums, float64 partial sums) ONE member of `poisson_residual_synth_batch` needs, in elements; (0, 0):
+    not a coarse shape it takes."""
+    lib = _lib.load()
+    return (int(lib.odil_poisson_residual_synth_batch_workspace_bytes(i64(cshape))) // 8,
+            int(lib.odil_poisson_residual_synth_batch_partials(i64(cshape))))
+
+
+def poisson_residual_synth_batch(coarse, w0, rhs, h2, fu, loss, partials, sums):
+    """`poisson_residual_synth` for the B members of [B, *shape] arrays in ONE launch (+ the loss replay and the final
+    reduction, one launch each): fu[b] = Lap(w0[b] + P coarse[b]) - rhs[b], loss[b] = mean(fu[b]**2), bit for bit what the
+    single form computes for member b alone.  coarse: contiguous [B, *cshape]; the leading strides of w0, rhs, fu are the
+    member strides; partials: [B, >= partial sums of a member] float64; sums: [B, >= column sums of a member] float64
+    contiguous (residual_synth_batch_workspace); loss: [B] contiguous."""
+    nb, cshape, shape = int(w0.shape[0]), tuple(coarse.shape[1:]), tuple(w0.shape[1:])
+    assert coarse.is_contiguous() and coarse.shape[0] == nb and shape == tuple(2 * s for s in cshape)
+    assert coarse.dtype == w0.dtype == rhs.dtype == fu.dtype == loss.dtype and loss.shape == (nb,) and loss.is_contiguous()
+    assert partials.dtype == torch.float64 and partials.dim() == 2 and partials.shape[0] == nb and partials.stride(1) == 1
+    assert sums.dtype == torch.float64 and sums.dim() == 2 and sums.shape[0] == nb and sums.is_contiguous()
+    (wp, ws), (rp, rs), (fp, fs) = _members(w0, nb, shape), _members(rhs, nb, shape), _members(fu, nb, shape)
+    h2a, h2p = host_reals(h2, w0.dtype)
+    plen = (nb - 1) * partials.stride(0) + partials.shape[1]
+    call("poisson_residual_synth_batch", w0.dtype, ptr(coarse), wp, rp, fp, c_int(nb), ws, rs, fs, i64(cshape),
+         c_int(len(cshape)), h2p, c_void_p(partials.data_ptr()), c_int64(max(partials.stride(0), partials.shape[1])),
+         c_int64(plen), ptr(sums), c_size_t(sums.numel() * 8), ptr(loss), stream_ptr())
+    return fu, loss
+
+
+def poisson_adjoint_adam_volumes(fu, h2, scale, out, x, m, v, alphas, one_minus_b1, one_minus_b2, eps):
+    """`poisson_adjoint_adam` for the B 3-D members of [B, *shape] arrays in ONE launch.  alphas: DEVICE step sizes, [B]
+    (one per member) or one element (shared); out = None: the gradient is not stored."""
+    nb, shape = int(fu.shape[0]), tuple(fu.shape[1:])
+    assert alphas.dtype == fu.dtype and alphas.is_cuda and alphas.numel() in (1, nb) and alphas.is_contiguous()
+    (fp, fs), (xp, xs), (mp, ms), (vp, vs) = (_members(t, nb, shape) for t in (fu, x, m, v))
+    gp, gs = _members(out, nb, shape) if out is not None else (None, fs)
+    h2a, h2p = host_reals(h2, fu.dtype)
+    call("poisson_adjoint_adam_volumes", fu.dtype, fp, gp, xp, mp, vp, c_int(nb), fs, gs, xs, ms, vs, i64(shape),
+         c_int(len(shape)), h2p, float(scale), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
+         c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
+    return out
+
+
+def mg_synth_adj_adam_volumes(gu, shapes, grads, x, m, v, alphas, one_minus_b1, one_minus_b2, eps):
+    """`mg_synth_adj_adam` on contiguous [B, *shape] level arrays of B 3-D members (`shapes`: the level shapes of ONE
+    member): the launches of a single volume's chain, each for all members.  alphas: as in `poisson_adjoint_adam_volumes`.
+    grads[0] is not written (the chain reads gu)."""
+    nb, nlvl = int(gu.shape[0]), len(shapes)
+    assert alphas.dtype == gu.dtype and alphas.numel() in (1, nb) and alphas.is_contiguous()
+    assert tuple(gu.shape) == (nb,) + tuple(shapes[0]) and gu.is_contiguous()
+    for arrs in (grads, x, m, v):  # (the launcher takes contiguous [B, *shape] level arrays: no strides travel)
+        assert all(tuple(t.shape) == (nb,) + tuple(s) and t.is_contiguous() and t.dtype == gu.dtype
+                   for t, s in zip(arrs[1:], shapes[1:]))
+    none0 = lambda arrs: ptr_array([None] + list(arrs[1:]))
+    flat = [int(n) for s in shapes for n in s]
+    call("mg_synth_adj_adam_volumes", gu.dtype, ptr(gu), none0(grads), i64(flat), c_int(nlvl), c_int(len(shapes[0])),
+         c_int(nb), none0(x), none0(m), none0(v), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
+         c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
+    return grads
+
+
 def jacobi2_supported(shape, dtype):
     """Arrays whose rows are whole 16-byte packs (odil_poisson_jacobi2, odil_stencil_var_smooth2)."""
     pack = 2 if dtype == torch.float64 else 4

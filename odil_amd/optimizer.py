@@ -291,9 +291,9 @@ class AdamNativeOptimizer(Optimizer):
         steps = lambda rate: [_adam_step_size(npdt(rate), beta_1, beta_2, npdt(e - epoch_start)) for e in range(first, last + 1)]
         if lrs is not None and len(lrs) != ensemble.nbatch:
             raise ValueError("{} step sizes for {} members".format(len(lrs), ensemble.nbatch))
-        from .fused import PoissonLaunchEnsemble
+        from .fused import BatchedLaunches
 
-        if isinstance(ensemble, PoissonLaunchEnsemble):  # (batched launches, epoch by epoch)
+        if isinstance(ensemble, BatchedLaunches):  # (batched launches, epoch by epoch)
             return self._run_ensemble_launches(ensemble, epochs, callback, steps(lr) if lrs is None else [steps(r) for r in lrs],
                                                epoch_start, 1 - beta_1, 1 - beta_2, epsilon)
         table = np.array(steps(lr) if lrs is None else [steps(rate) for rate in lrs], dtype=np.float64)
@@ -321,7 +321,7 @@ class AdamNativeOptimizer(Optimizer):
 
 
     def _run_ensemble_launches(self, ensemble, epochs, callback, table, epoch_start, omb1, omb2, epsilon):
-        """`run_ensemble` for a `fused.PoissonLaunchEnsemble`: every epoch is the launches of a single run, each covering
+        """`run_ensemble` for a `fused.PoissonLaunchEnsemble` or a `fused.PoissonVolumeEnsemble`: every epoch is the launches of a single run, each covering
         all members.  table: [E] step sizes shared by the members, or [B][E].  The epoch's step sizes are selected, and its
         [B] losses and norms filed into column e of the [B, E] tables, by the device index of `_EpochGraph` -- eagerly or,
         under the `_graph_wanted` policy, replayed as one hipGraph (one stream: the launches are a chain); the same body

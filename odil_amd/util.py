@@ -470,7 +470,9 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
 
     form: 'workgroup' (the default) is the above.  'launches' runs members of ANY 1-D / 2-D size with at least two levels
     (fused.PoissonLaunchEnsemble, fused.launches_refusal): every epoch is the launches of a single run, each covering all
-    members.  'auto': 'workgroup' where `fused.small_refusal` admits the members, 'launches' otherwise.
+    members.  'volumes' runs 3-D members with at least two levels the same way (fused.PoissonVolumeEnsemble,
+    fused.volumes_refusal).  'auto': 'volumes' for 3-D members; else 'workgroup' where `fused.small_refusal` admits the
+    members, 'launches' otherwise.
 
     args.optimizer must be 'adam' / 'adamn'; lrs: one step size per member (default args.lr for all).
     callback(member, state, epoch, pinfo): called for every member at args.epoch_start (the initial evaluation) and at
@@ -479,7 +481,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     swaps in are not picked up.
     Members must be the recognised Poisson operator, share cshape, level shapes, spacing, dtype and device, and be
     admitted by the form that runs them (fused.small_refusal: small enough for the one-workgroup epochs;
-    fused.launches_refusal: 1-D / 2-D, at least two levels that halve); anything else raises ValueError naming the first
+    fused.launches_refusal: 1-D / 2-D, at least two levels that halve; fused.volumes_refusal: 3-D, at least two levels
+    that halve, a finest extent of at least 4); anything else raises ValueError naming the first
     offending member -- structure (shapes, size) is checked for all members before any operator is probed.
     Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors."""
     from . import fused
@@ -509,7 +512,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
             refuse(b, "the unknown is not a cell-centred field of the domain")
         if b == 0:
             form = fused.ensemble_form(form, shapes, arrays[0].dtype)
-        reason = fused.small_refusal(shapes, arrays[0].dtype) if form == "workgroup" else fused.launches_refusal(shapes, arrays[0].dtype)
+        predicate = dict(workgroup=fused.small_refusal, launches=fused.launches_refusal, volumes=fused.volumes_refusal)[form]
+        reason = predicate(shapes, arrays[0].dtype)
         if reason is not None:
             refuse(b, reason)
         kind = dict(shapes=shapes, dtype=arrays[0].dtype, device=arrays[0].device,
@@ -524,7 +528,7 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
         if getattr(problem, "_fused", None) is None:
             refuse(b, "the operator is not the recognised Poisson stencil")
         evaluators.append(problem._fused)
-    kind = fused.PoissonEnsemble if form == "workgroup" else fused.PoissonLaunchEnsemble
+    kind = dict(workgroup=fused.PoissonEnsemble, launches=fused.PoissonLaunchEnsemble, volumes=fused.PoissonVolumeEnsemble)[form]
     reason = kind.refusal(evaluators)
     if reason is not None:
         refuse(*reason)
