@@ -1,6 +1,7 @@
 """Random straight-line stencil operators shared by the GPU parity test of the generated kernels
-(tests/test_workloads_gpu.py), the CPU check of the symbolic gradient expressions (tests/test_stencil_grad_host.py) and the
-tests of the generated Jacobian kernel (tests/test_jacobian_kernel_host.py, tests/test_jacobian_kernel_gpu.py)."""
+(tests/test_workloads_gpu.py), the CPU check of the symbolic gradient expressions (tests/test_stencil_grad_host.py), the
+tests of the generated Jacobian kernel (tests/test_jacobian_kernel_host.py, tests/test_jacobian_kernel_gpu.py) and the 1-D,
+2-D and 3-D cases that run the folded copies of the generated kernels (tests/traced_cases.py)."""
 
 import numpy as np
 
