@@ -9,6 +9,11 @@ same way with `--form volumes` (or `--form auto`, which picks the form from the 
     python examples/poisson/ensemble.py --ndim 1 --N 256 --members 64 --epochs 1000 --vary rhs
     python examples/poisson/ensemble.py --ndim 2 --N 128 --members 64 --epochs 1000 --form launches
     python examples/poisson/ensemble.py --ndim 3 --N 32 --members 64 --epochs 1000 --form volumes
+
+With `--optimizer newton` (plain unknowns, `--multigrid 0`) every epoch is ONE launch that runs the whole Newton step of
+every member, one workgroup per member (`odil.util.optimize_newton_ensemble`):
+
+    python examples/poisson/ensemble.py --ndim 3 --N 16 --members 64 --multigrid 0 --optimizer newton --linsolver multigrid --epochs 1
 """
 
 import os
@@ -74,6 +79,20 @@ def main():
 
     every = args.report_every or args.epochs
     callback.next_active = lambda epoch: (epoch // every + 1) * every
+    if args.optimizer == "newton":
+        # one launch per epoch runs the whole Newton step of every member (one workgroup per member)
+        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback)
+        if args.epochs > args.epoch_start:
+            status = [optinfo.solver.status(b) for b in range(args.members)]
+            printlog("\nlast Newton step, per member:")
+            for b, st in enumerate(status):
+                printlog("member {:3d}: {} cycles, relative residual {:.2e}{}".format(
+                    b, st["niter"], st["residual"] / max(st["bnorm"], 1e-300), "" if st["converged"] else " (not converged)"))
+            summary = "{} converged members of {}".format(sum(bool(st["converged"]) for st in status), args.members)
+            printlog(summary)
+            if not args.echo:  # (the log goes to train.log: the verdict also to the terminal)
+                print(summary)
+        return
     arrays, optinfo = odil.util.optimize_ensemble(args, problems, states, callback, lrs=lrs, form=args.form)
     if args.epochs > args.epoch_start:
         printlog("\nloss at the last epoch, per member:")

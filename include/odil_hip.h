@@ -623,6 +623,39 @@ int odil_stencil_vcycle_tail_f32(const float* coeffs, const int64_t* shapes, con
                                  const float* xin, const float* b, float* xout, float* work, int64_t work_len,
                                  const float* inv, int ninv, const float* wpre, int npre, const float* wpost, int npost,
                                  int fmg, void* stream);
+/* Whole multigrid SOLVES of an ENSEMBLE in one launch: `nbatch` (1..65535) small systems of one shape, one workgroup per
+ * member, every member walking its hierarchy from the FINEST level with the phases of odil_stencil_vcycle_tail: member b's
+ * iterate after k cycles equals k launches of that entry point on its arrays alone, bit for bit.  The workgroup forms the
+ * residual norm before every cycle and stops on its own: no host read-back inside the solve.  Members never communicate.
+ *   coeffs, shapes, halve, nlev, ndim, inv, ninv, wpre, wpost   as odil_stencil_vcycle_tail, per member
+ *   *_stride   elements between members;  coeff_stride / inv_stride 0: one operator / one coarsest inverse for all
+ *   x, b       per member the unknowns and the right-hand side of the finest level (x != b)
+ *   work       per member odil_stencil_solve_batch_work(shapes, nlev, ndim) = 3 * (cells of all levels) values;
+ *              work_len >= (nbatch - 1) work_stride + one member
+ *   start      0: zero iterate;  1: the content of x;  2: nested iteration (fmg of odil_stencil_vcycle_tail)
+ *   mode       0: solve A x = b.  1: Newton step, x holds u: u <- u - d with A d = A u - b (start 0 or 2); A u - b is
+ *              accumulated in double and rounded once (_f32: the residual of an iterative refinement in the wider type)
+ *   history    per member >= maxcycles + 2 DOUBLES (also _f32): [0] mean(rhs^2) of the system solved, [1 + k]
+ *              mean((A x_k - rhs)^2) before cycle k.  Every thread sums the squares of cells tid, tid + 1024, ... in double,
+ *              a fixed-order tree combines them (lanes of a wave, then the 16 waves): deterministic, independent of nbatch
+ *   outcome    [nbatch, 2]: cycles run, stop reason -- 0 converged (history[1 + k] <= tol^2 history[0]), 1 k == maxcycles
+ *              (0..1000), 2 stagnated (k >= 3 and history[1 + k] >= 0.98^2 history[k]), 3 a non-finite norm
+ * Malformed arguments are refused before any launch.  (No reference counterpart: the reference solves one system at a time
+ * with SuperLU / pyamg, linsolver.py:17-26, 61-72.) */
+int odil_stencil_solve_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve, int nlev,
+                                 int ndim, int nbatch, double* x, int64_t x_stride, const double* b, int64_t b_stride,
+                                 double* work, int64_t work_stride, int64_t work_len, const double* inv, int64_t inv_stride,
+                                 int ninv, const double* wpre, int npre, const double* wpost, int npost, int start, int mode,
+                                 int maxcycles, double tol, double* history, int64_t history_stride, int* outcome,
+                                 void* stream);
+int odil_stencil_solve_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve, int nlev,
+                                 int ndim, int nbatch, float* x, int64_t x_stride, const float* b, int64_t b_stride,
+                                 float* work, int64_t work_stride, int64_t work_len, const float* inv, int64_t inv_stride,
+                                 int ninv, const float* wpre, int npre, const float* wpost, int npost, int start, int mode,
+                                 int maxcycles, float tol, double* history, int64_t history_stride, int* outcome,
+                                 void* stream);
+/* work elements per member of odil_stencil_solve_batch; 0 if the shapes are malformed */
+int64_t odil_stencil_solve_batch_work(const int64_t* shapes, int nlev, int ndim);
 /* Mixed-precision iterative refinement of the multigrid Newton solve (gmg.py; no reference counterpart -- the reference's
  * direct solver is double throughout): float32 V-cycles inside a float64 residual loop.  narrow_scale: y32 = s x64 with
  * s = a / sqrt(*msq) (msq: device scalar, the mean square the residual kernel just wrote; NULL: s = a); widen_axpy:

@@ -82,6 +82,8 @@ _SIGNATURES = {
     "stencil_var_coarsen": [_P, _P, _I64P, c_int, _P],
     "stencil_var_coarsen_axes": [_P, _P, _I64P, c_int, _P, _P],
     "stencil_vcycle_tail": [_P, _I64P, _P, c_int, c_int, _P, _P, _P, _P, c_int64, _P, c_int, _P, c_int, _P, c_int, c_int, _P],
+    "stencil_solve_batch": [_P, c_int64, _I64P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P,
+                            c_int64, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _R, _P, c_int64, _P, _P],
     "max_abs_diff": [_P, _P, c_int64, _P, _P, _P],
     "max_abs_rows": [_P, c_int, c_int64, _P, _P, _P],
     "csr_assemble": [_P, _I64P, c_int, _I64P, c_int, c_int64, _P, _P, _P, _P],
@@ -106,7 +108,7 @@ EXPORTED = [
     "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials", "odil_poisson_batch_partials",
     "odil_mg_batch_levels_ok", "odil_poisson_residual_synth_workspace_bytes",
     "odil_mg_volumes_levels_ok", "odil_interp_adj_kind", "odil_poisson_residual_synth_batch_workspace_bytes",
-    "odil_poisson_residual_synth_batch_partials",
+    "odil_poisson_residual_synth_batch_partials", "odil_stencil_solve_batch_work",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
 ] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
@@ -157,6 +159,8 @@ def load():
     lib.odil_poisson_residual_synth_batch_workspace_bytes.argtypes = [_I64P]
     lib.odil_poisson_residual_synth_batch_partials.restype = c_int64
     lib.odil_poisson_residual_synth_batch_partials.argtypes = [_I64P]
+    lib.odil_stencil_solve_batch_work.restype = c_int64
+    lib.odil_stencil_solve_batch_work.argtypes = [_I64P, c_int, c_int]
     for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)
         fn = getattr(lib, name)
         fn.restype = c_int

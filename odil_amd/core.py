@@ -1020,8 +1020,10 @@ class Problem:
                 for _ in range(2):  # warm-up: allocator, lazy initialisation, workspace tensors
                     self._eval_loss_grad_generic(static_state)
             torch.cuda.current_stream().wait_stream(side)
+            from .runtime import graph_capture
+
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with graph_capture(graph):
                 out = self._eval_loss_grad_generic(static_state)
         finally:
             self.tracers = saved

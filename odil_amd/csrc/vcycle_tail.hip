@@ -334,6 +334,351 @@ static int vcycle_tail(const T* coeffs, const int64_t* shapes, const int* halve,
   return check_launch("k_vcycle_tail");
 }
 
+// ---- whole SOLVES of an ensemble: one workgroup per member ---------------------------------------------------------------
+// B small systems A_b x_b = rhs_b (or Newton steps u_b <- u_b - d_b, A_b d_b = A_b u_b - rhs_b) in ONE launch.  Workgroup b
+// walks member b's hierarchy from the FINEST level with the phases above (same functions, same order: member b's iterate
+// after k cycles is that of k launches of k_vcycle_tail on its arrays, bit for bit), forms the residual's mean square
+// before every cycle and stops on its own -- no host read-back inside the solve.  Members never communicate.
+constexpr int kSolveMaxCycles = 1000;
+// (k_vcycle_tail takes extents up to 4096; a 1-D member of 32768 cells is one row: tail_div is exact for i < 2^22)
+constexpr int kSolveMaxExtent = 32768;
+
+template <typename T>
+struct SolveArgs {
+  TailArgs<T> t;
+  int64_t coeff_stride, x_stride, b_stride, work_stride, inv_stride, history_stride;
+  int start, mode, maxcycles;
+  double tol2;
+};
+
+// the sum of every thread's `s` in a fixed order (lanes of a wave by halving distances, then the 16 waves through LDS),
+// returned to every thread; red: 16 doubles of LDS
+__device__ __forceinline__ double solve_block_sum(double s, double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[wave] = s;
+  __syncthreads();
+  double v[16];
+#pragma unroll
+  for (int w = 0; w < 16; ++w) v[w] = red[w];
+#pragma unroll
+  for (int half = 8; half > 0; half >>= 1)
+#pragma unroll
+    for (int w = 0; w < half; ++w) v[w] = v[w] + v[w + half];
+  __syncthreads();  // (red is free for the next sum)
+  return v[0];
+}
+
+template <typename T>
+__global__ __launch_bounds__(kTailThreads) void k_stencil_solve_batch(const T* __restrict__ coeffs_all, T* x_all,
+                                                                      const T* __restrict__ b_all, T* work_all,
+                                                                      const T* __restrict__ inv_all, double* history_all,
+                                                                      int* outcome, SolveArgs<T> s) {
+  const TailArgs<T>& a = s.t;
+  const int64_t member = blockIdx.x;
+  const T* coeffs = coeffs_all + member * s.coeff_stride;
+  T* xm = x_all + member * s.x_stride;
+  const T* bm = b_all + member * s.b_stride;
+  T* work = work_all + member * s.work_stride;
+  const T* inv = inv_all + member * s.inv_stride;
+  double* history = history_all + member * s.history_stride;
+  const int last = a.nlev - 1;
+  const TailLevel& L0 = a.lv[0];
+  __shared__ double red[16];
+  __shared__ int stop_shared;
+
+  // Where the iterate of a level lives: two bits per level in ONE register of every thread, derived from the kernel's
+  // arguments and workgroup-uniform control flow alone (no pointers in LDS that one thread writes while another reads).
+  // 0: the zero vector (nothing stored), 1 / 2: the level's two buffers in `work`, 3: the member's x (finest level only)
+  unsigned where = 0;
+  auto get = [&](int l) -> int { return (int)((where >> (2 * l)) & 3u); };
+  auto set = [&](int l, int v) { where = (where & ~(3u << (2 * l))) | ((unsigned)v << (2 * l)); };
+  auto buf = [&](int l, int v) -> T* { return v == 1 ? work + a.lv[l].x : v == 2 ? work + a.lv[l].t : xm; };
+  auto cur = [&](int l) -> const T* { return get(l) == 0 ? nullptr : buf(l, get(l)); };
+  auto other = [&](int l) -> int { return get(l) == 1 ? 2 : 1; };
+  // the right-hand side of the system solved: b, or in a Newton step r = A u - b (the finest level's third slot of `work`)
+  T* rwork = work + L0.b;
+  const T* rhs0 = s.mode ? rwork : bm;
+  auto rhs = [&](int l) -> const T* { return l == 0 ? rhs0 : work + a.lv[l].b; };
+
+  auto coarsest = [&]() {
+    const TailLevel& L = a.lv[last];
+    T* out = buf(last, 1);
+    const T* b = rhs(last);
+    for (int r = threadIdx.x; r < L.size; r += kTailThreads) {
+      T acc = T(0);
+      for (int j = 0; j < L.size; ++j) acc = acc + inv[(int64_t)r * L.size + j] * b[j];
+      out[r] = acc;
+    }
+    __syncthreads();
+    set(last, 1);
+  };
+  // (the body of k_vcycle_tail's vcycle)
+  auto vcycle = [&](int top) {
+    for (int l = top; l < last; ++l) {
+      const TailLevel& L = a.lv[l];
+      const T* c = coeffs + L.c;
+      if (l > top) set(l, 0);
+      for (int k = 0; k < a.npre; ++k) {
+        const int dst = other(l);
+        tail_sweep<T>(c, cur(l), get(l) == 0, rhs(l), buf(l, dst), a.wpre[k], L, a);
+        set(l, dst);
+      }
+      tail_restrict<T>(c, cur(l), get(l) == 0, rhs(l), work + a.lv[l + 1].b, L, a.lv[l + 1], a, true);
+    }
+    coarsest();
+    for (int l = last - 1; l >= top; --l) {
+      const TailLevel& L = a.lv[l];
+      const T* c = coeffs + L.c;
+      if (get(l) == 0) {
+        tail_prolong<T>(cur(l + 1), nullptr, false, buf(l, 1), L, a.lv[l + 1]);
+        set(l, 1);
+      } else {
+        const int dst = other(l);
+        tail_prolong<T>(cur(l + 1), cur(l), true, buf(l, dst), L, a.lv[l + 1]);
+        set(l, dst);
+      }
+      for (int k = 0; k < a.npost; ++k) {
+        const int dst = other(l);
+        tail_sweep<T>(c, cur(l), false, rhs(l), buf(l, dst), a.wpost[k], L, a);
+        set(l, dst);
+      }
+    }
+  };
+
+  // 1. Newton step: r = A u - b.  The terms of tail_apply in its order, but accumulated in DOUBLE and rounded once: u is
+  // O(1) and r shrinks from step to step, so in float32 the roundings of the products c u (eps |c u|, not eps |r|) would
+  // set the floor of the Newton iterate -- the residual of an iterative refinement is formed in the wider type.  (double:
+  // the same operations as tail_apply)
+  if (s.mode) {
+    const T* c = coeffs + L0.c;
+    const int stride[3] = {L0.n[1] * L0.n[2], L0.n[2], 1};
+    for (int i = threadIdx.x; i < L0.size; i += kTailThreads) {
+      int id[3];
+      tail_decode(i, L0, id);
+      double acc = (double)c[i] * (double)xm[i];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        if (!a.has[d]) continue;
+        const int n = L0.n[d];
+        const int im = id[d] == 0 ? i + (n - 1) * stride[d] : i - stride[d];
+        const int ip = id[d] == n - 1 ? i - (n - 1) * stride[d] : i + stride[d];
+        acc = acc + (double)c[(int64_t)a.slot[d] * L0.size + i] * (double)xm[im];
+        acc = acc + (double)c[(int64_t)(a.slot[d] + 1) * L0.size + i] * (double)xm[ip];
+      }
+      rwork[i] = (T)(acc - (double)bm[i]);
+    }
+    __syncthreads();
+  }
+  // 2. mean(rhs^2)
+  const double rcells = 1.0 / (double)L0.size;
+  double sum = 0.0;
+  for (int i = threadIdx.x; i < L0.size; i += kTailThreads) {
+    const double v = (double)rhs0[i];
+    sum += v * v;
+  }
+  const double bsq = solve_block_sum(sum, red) * rcells;
+  if (threadIdx.x == 0) history[0] = bsq;
+  // 3. the start iterate
+  if (s.start == 2) {
+    for (int l = 0; l < last; ++l)
+      tail_restrict<T>(nullptr, nullptr, true, rhs(l), work + a.lv[l + 1].b, a.lv[l], a.lv[l + 1], a, false);
+    coarsest();
+    for (int l = last - 1; l >= 0; --l) {
+      tail_prolong<T>(cur(l + 1), nullptr, false, buf(l, 1), a.lv[l], a.lv[l + 1]);
+      set(l, 1);
+      vcycle(l);
+    }
+  } else if (s.start == 1) {
+    set(0, 3);
+  }
+  // 4. cycles until a stop rule fires (k <= maxcycles <= kSolveMaxCycles: the loop is bounded whatever the numbers do)
+  int k = 0, reason = 1;
+  double prev = bsq;
+  for (; k <= s.maxcycles; ++k) {
+    sum = 0.0;
+    {
+      const T* xc = cur(0);
+      const bool zero = get(0) == 0;
+      for (int i = threadIdx.x; i < L0.size; i += kTailThreads) {
+        int id[3];
+        tail_decode(i, L0, id);
+        const double v = (double)(tail_apply<T>(coeffs + L0.c, xc, zero, L0, a, i, id) - rhs0[i]);
+        sum += v * v;
+      }
+    }
+    const double rsq = solve_block_sum(sum, red) * rcells;
+    // the decision is taken ONCE and read by every thread after a barrier: every exit of this loop is workgroup-uniform
+    if (threadIdx.x == 0) {
+      history[1 + k] = rsq;
+      int why = -1;
+      if (!__builtin_isfinite(rsq) || !__builtin_isfinite(bsq)) why = 3;
+      else if (rsq <= s.tol2 * bsq) why = 0;
+      else if (k == s.maxcycles) why = 1;
+      else if (k >= 3 && rsq >= (0.98 * 0.98) * prev) why = 2;
+      stop_shared = why;
+    }
+    __syncthreads();
+    const int why = stop_shared;
+    __syncthreads();  // (read by all before thread 0 writes the next decision)
+    if (why >= 0) {
+      reason = why;
+      break;
+    }
+    prev = rsq;
+    if (last == 0)
+      coarsest();
+    else
+      vcycle(0);
+  }
+  if (threadIdx.x == 0) {
+    outcome[2 * member] = k;
+    outcome[2 * member + 1] = reason;
+  }
+  // 5. the result: x, or u - d
+  const T* res = cur(0);
+  if (s.mode) {
+    if (res != nullptr)
+      for (int i = threadIdx.x; i < L0.size; i += kTailThreads) xm[i] = xm[i] - res[i];
+  } else if (res != xm) {
+    for (int i = threadIdx.x; i < L0.size; i += kTailThreads) xm[i] = res != nullptr ? res[i] : T(0);
+  }
+}
+
+// the level table of `shapes` / `halve` (what vcycle_tail builds); false with the error set
+template <typename T>
+static bool solve_levels(TailArgs<T>& a, const int64_t* shapes, const int* halve, int nlev, int ndim, int64_t* ncoeff,
+                         int64_t* nwork) {
+  a.nlev = nlev, a.ndim = ndim;
+  for (int d = 0; d < 3; ++d) {
+    const int i = d - (3 - ndim);
+    a.has[d] = i >= 0 ? 1 : 0;
+    a.slot[d] = i >= 0 ? 1 + 2 * i : 0;
+  }
+  int64_t coff = 0, woff = 0;
+  for (int l = 0; l < kTailMaxLev; ++l) {
+    TailLevel& L = a.lv[l];
+    L.size = 0, L.c = 0, L.x = L.t = L.b = 0;
+    for (int d = 0; d < 3; ++d) L.n[d] = 1, L.halve[d] = 0, L.rn[d] = 1.0f;
+    if (l >= nlev) continue;
+    int64_t size = 1;
+    for (int d = 0; d < 3; ++d) {
+      const int i = d - (3 - ndim);
+      if (i < 0) continue;
+      const int64_t n = shapes[l * ndim + i];
+      if (n < 1 || n > kSolveMaxExtent) {
+        set_error("stencil_solve_batch: extent %lld of level %d", (long long)n, l);
+        return false;
+      }
+      L.n[d] = (int)n;
+      L.rn[d] = 1.0f / (float)n;
+      size *= n;
+      if (l + 1 < nlev) {
+        L.halve[d] = halve[l * ndim + i] != 0;
+        const int64_t nc = shapes[(l + 1) * ndim + i];
+        if ((L.halve[d] && (n % 2 || nc != n / 2)) || (!L.halve[d] && nc != n)) {
+          set_error("stencil_solve_batch: level %d does not follow from level %d along axis %d", l + 1, l, i);
+          return false;
+        }
+      }
+    }
+    if (size > (1 << 20)) {
+      set_error("stencil_solve_batch: level %d has %lld cells (one workgroup walks the hierarchy)", l, (long long)size);
+      return false;
+    }
+    L.size = (int)size;
+    L.c = coff;
+    coff += (int64_t)(2 * ndim + 1) * size;
+    L.x = woff, L.t = woff + size, L.b = woff + 2 * size;
+    woff += 3 * size;
+  }
+  *ncoeff = coff, *nwork = woff;
+  return true;
+}
+
+template <typename T>
+static int stencil_solve_batch(const T* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve, int nlev,
+                               int ndim, int nbatch, T* x, int64_t x_stride, const T* b, int64_t b_stride, T* work,
+                               int64_t work_stride, int64_t work_len, const T* inv, int64_t inv_stride, int ninv,
+                               const T* wpre, int npre, const T* wpost, int npost, int start, int mode, int maxcycles,
+                               double tol, double* history, int64_t history_stride, int* outcome, void* stream) {
+  if (nlev < 1 || nlev > kTailMaxLev || ndim < 1 || ndim > 3 || npre < 0 || npre > 4 || npost < 0 || npost > 4) {
+    set_error("stencil_solve_batch: bad arguments (1..%d levels, ndim 1..3, at most 4 sweeps per side)", kTailMaxLev);
+    return ODIL_E_INVAL;
+  }
+  if (!shapes || (nlev > 1 && !halve) || !coeffs || !x || !b || !work || !inv || !history || !outcome ||
+      (npre && !wpre) || (npost && !wpost)) {
+    set_error("stencil_solve_batch: null pointer");
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("stencil_solve_batch: %d members (1..65535: one workgroup each)", nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (start < 0 || start > 2 || mode < 0 || mode > 1 || (mode == 1 && start == 1)) {
+    set_error("stencil_solve_batch: start %d, mode %d (start 0..2, mode 0..1; a Newton step starts from 0 or 2)", start, mode);
+    return ODIL_E_INVAL;
+  }
+  if (maxcycles < 0 || maxcycles > kSolveMaxCycles) {
+    set_error("stencil_solve_batch: maxcycles %d (0..%d)", maxcycles, kSolveMaxCycles);
+    return ODIL_E_INVAL;
+  }
+  if (!(tol >= 0.0)) {
+    set_error("stencil_solve_batch: negative tol");
+    return ODIL_E_INVAL;
+  }
+  if (x == b) {
+    set_error("stencil_solve_batch: x must not alias b");
+    return ODIL_E_INVAL;
+  }
+  if (coeff_stride < 0 || x_stride < 0 || b_stride < 0 || work_stride < 0 || inv_stride < 0 || history_stride < 0) {
+    set_error("stencil_solve_batch: negative stride");
+    return ODIL_E_INVAL;
+  }
+  SolveArgs<T> s;
+  TailArgs<T>& a = s.t;
+  int64_t ncoeff = 0, nwork = 0;
+  if (!solve_levels<T>(a, shapes, halve, nlev, ndim, &ncoeff, &nwork)) return ODIL_E_INVAL;
+  const int64_t cells = a.lv[0].size;
+  if (ninv != a.lv[nlev - 1].size) {
+    set_error("stencil_solve_batch: the coarsest level has %d unknowns, the inverse %d", a.lv[nlev - 1].size, ninv);
+    return ODIL_E_INVAL;
+  }
+  if (x_stride < cells || b_stride < cells || work_stride < nwork) {
+    set_error("stencil_solve_batch: stride smaller than a member (x %lld, b %lld of %lld cells; work %lld of %lld values)",
+              (long long)x_stride, (long long)b_stride, (long long)cells, (long long)work_stride, (long long)nwork);
+    return ODIL_E_INVAL;
+  }
+  if (work_len < (int64_t)(nbatch - 1) * work_stride + nwork) {
+    set_error("stencil_solve_batch: work array of %lld values, %lld needed", (long long)work_len,
+              (long long)((int64_t)(nbatch - 1) * work_stride + nwork));
+    return ODIL_E_INVAL;
+  }
+  if ((coeff_stride != 0 && coeff_stride < ncoeff) || (inv_stride != 0 && inv_stride < (int64_t)ninv * ninv)) {
+    set_error("stencil_solve_batch: coeff_stride %lld / inv_stride %lld neither 0 (shared) nor a member's %lld / %lld values",
+              (long long)coeff_stride, (long long)inv_stride, (long long)ncoeff, (long long)ninv * ninv);
+    return ODIL_E_INVAL;
+  }
+  if (history_stride < (int64_t)maxcycles + 2) {
+    set_error("stencil_solve_batch: history_stride %lld smaller than maxcycles + 2 = %d", (long long)history_stride,
+              maxcycles + 2);
+    return ODIL_E_INVAL;
+  }
+  a.ninv = ninv;
+  a.npre = npre, a.npost = npost, a.fmg = start == 2;
+  for (int k = 0; k < 4; ++k) {
+    a.wpre[k] = k < npre ? wpre[k] : T(0);
+    a.wpost[k] = k < npost ? wpost[k] : T(0);
+  }
+  s.coeff_stride = coeff_stride, s.x_stride = x_stride, s.b_stride = b_stride, s.work_stride = work_stride;
+  s.inv_stride = inv_stride, s.history_stride = history_stride;
+  s.start = start, s.mode = mode, s.maxcycles = maxcycles, s.tol2 = tol * tol;
+  hipLaunchKernelGGL((k_stencil_solve_batch<T>), dim3(nbatch), dim3(kTailThreads), 0, (hipStream_t)stream, coeffs, x, b,
+                     work, inv, history, outcome, s);
+  return check_launch("k_stencil_solve_batch");
+}
+
 }  // namespace odil
 
 using namespace odil;
@@ -352,5 +697,40 @@ int odil_stencil_vcycle_tail_f32(const float* coeffs, const int64_t* shapes, con
                                  int fmg, void* stream) {
   return vcycle_tail<float>(coeffs, shapes, halve, nlev, ndim, xin, b, xout, work, work_len, inv, ninv, wpre, npre, wpost,
                             npost, fmg, stream);
+}
+int odil_stencil_solve_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve, int nlev,
+                                 int ndim, int nbatch, double* x, int64_t x_stride, const double* b, int64_t b_stride,
+                                 double* work, int64_t work_stride, int64_t work_len, const double* inv, int64_t inv_stride,
+                                 int ninv, const double* wpre, int npre, const double* wpost, int npost, int start, int mode,
+                                 int maxcycles, double tol, double* history, int64_t history_stride, int* outcome,
+                                 void* stream) {
+  return stencil_solve_batch<double>(coeffs, coeff_stride, shapes, halve, nlev, ndim, nbatch, x, x_stride, b, b_stride, work,
+                                     work_stride, work_len, inv, inv_stride, ninv, wpre, npre, wpost, npost, start, mode,
+                                     maxcycles, tol, history, history_stride, outcome, stream);
+}
+int odil_stencil_solve_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve, int nlev,
+                                 int ndim, int nbatch, float* x, int64_t x_stride, const float* b, int64_t b_stride,
+                                 float* work, int64_t work_stride, int64_t work_len, const float* inv, int64_t inv_stride,
+                                 int ninv, const float* wpre, int npre, const float* wpost, int npost, int start, int mode,
+                                 int maxcycles, float tol, double* history, int64_t history_stride, int* outcome,
+                                 void* stream) {
+  return stencil_solve_batch<float>(coeffs, coeff_stride, shapes, halve, nlev, ndim, nbatch, x, x_stride, b, b_stride, work,
+                                    work_stride, work_len, inv, inv_stride, ninv, wpre, npre, wpost, npost, start, mode,
+                                    maxcycles, (double)tol, history, history_stride, outcome, stream);
+}
+int64_t odil_stencil_solve_batch_work(const int64_t* shapes, int nlev, int ndim) {
+  if (!shapes || nlev < 1 || nlev > kTailMaxLev || ndim < 1 || ndim > 3) return 0;
+  int64_t total = 0;
+  for (int l = 0; l < nlev; ++l) {
+    int64_t size = 1;
+    for (int i = 0; i < ndim; ++i) {
+      const int64_t n = shapes[l * ndim + i];
+      if (n < 1 || n > kSolveMaxExtent) return 0;
+      size *= n;
+    }
+    if (size > (1 << 20)) return 0;
+    total += 3 * size;
+  }
+  return total;
 }
 }  // extern "C"

@@ -510,6 +510,31 @@ def small_refusal(shapes, dtype, force=None, max_cells=None):
     return None
 
 
+def newton_refusal(cshape, h2, dtype):
+    """Why a Poisson problem of these cells and squared spacings is not a member of a Newton ensemble (one workgroup per
+    member walks its whole multigrid hierarchy: gmg.EnsembleGMG, odil_stencil_solve_batch), or None when it is.  Host
+    arithmetic only: usable before any state exists."""
+    from .gmg import EnsembleGMG
+
+    cshape = tuple(int(n) for n in cshape)
+    ndim = len(cshape)
+    if not 1 <= ndim <= 3:
+        return "{}-D grid: the one-workgroup Newton solves run 1-D to 3-D grids".format(ndim)
+    npdt = np.float64 if dtype == torch.float64 else np.float32
+    shapes, _, locs, _ = EnsembleGMG.plan(cshape, h2, npdt)
+    if any(loc != "c" * ndim for loc in locs):
+        return "cells too far from cubes: the hierarchy {} halves some axes only".format(shapes)
+    cells = math.prod(cshape)
+    if cells > EnsembleGMG.max_cells:
+        return "{} cells are above the limit of the one-workgroup Newton solves ({})".format(cells, EnsembleGMG.max_cells)
+    if len(shapes) > EnsembleGMG.max_levels:
+        return "{} levels: the one-workgroup Newton solves take at most {}".format(len(shapes), EnsembleGMG.max_levels)
+    if math.prod(shapes[-1]) > EnsembleGMG.max_coarsest:
+        return "the coarsest level {} has {} unknowns, above the {} of the dense coarsest solve".format(
+            shapes[-1], math.prod(shapes[-1]), EnsembleGMG.max_coarsest)
+    return None
+
+
 def _close(a, b, rtol):
     scale = max(float(b.abs().max()), 1e-300)
     return float((a - b).abs().max()) <= rtol * scale

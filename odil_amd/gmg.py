@@ -45,6 +45,22 @@ def jacobi_weights(ndim, n):
     return chebyshev_weights(n, 1.0 / ndim, 2.0)
 
 
+def poisson_hierarchy(shape, h2, npdt, min_size=2):
+    """(shapes, h2s, locs) of the rediscretised Poisson hierarchy below `shape` (host arithmetic only; the rule is
+    described in `PoissonGMG.__init__`)."""
+    shapes, h2s, locs = [tuple(shape)], [[npdt(v) for v in h2]], []
+    while True:
+        cur, h = shapes[-1], h2s[-1]
+        hmin = min(float(v) for v in h)
+        halve = [float(v) <= 2.0 * hmin for v in h]
+        if not all(n % 2 == 0 and n // 2 >= min_size for n, on in zip(cur, halve) if on):
+            break
+        shapes.append(tuple(n // 2 if on else n for n, on in zip(cur, halve)))
+        h2s.append([v * npdt(4) if on else v for v, on in zip(h, halve)])
+        locs.append("".join("c" if on else "." for on in halve))
+    return shapes, h2s, locs
+
+
 class PoissonGMG:
     nu_default = (2, 2)  # pre- / post-smoothing sweeps of a cycle
 
@@ -55,22 +71,13 @@ class PoissonGMG:
         self.loc = "c" * self.ndim
         self.dtype, self.device = dtype, device
         npdt = np.float64 if dtype == torch.float64 else np.float32
-        self.shapes, self.h2s = [tuple(shape)], [[npdt(v) for v in h2]]
         # SEMI-coarsening while the cells are far from cubes: point smoothing only damps what oscillates along the strongly
         # coupled axes (the small spacings), so only those are halved -- the axes whose h^2 is within a factor 2 of the
         # smallest -- until the spacings meet; from there on (and from the start on a grid of cubes) every axis is halved.
         # 1024 x 64 on the unit square: (512, 64), (256, 64), (128, 64), (64, 64), (32, 32), ...  With full coarsening the
         # cycles lost their rate at cells 1 : 2 (24 passes with the Krylov hand-over), 1 : 4 (70 - 110) and failed at 1 : 16.
-        self.locs = []  # per transition lvl -> lvl + 1: 'c' on the halved axes, '.' on the others
-        while True:
-            cur, h = self.shapes[-1], self.h2s[-1]
-            hmin = min(float(v) for v in h)
-            halve = [float(v) <= 2.0 * hmin for v in h]
-            if not all(n % 2 == 0 and n // 2 >= min_size for n, on in zip(cur, halve) if on):
-                break
-            self.shapes.append(tuple(n // 2 if on else n for n, on in zip(cur, halve)))
-            self.h2s.append([v * npdt(4) if on else v for v, on in zip(h, halve)])
-            self.locs.append("".join("c" if on else "." for on in halve))
+        # locs: per transition lvl -> lvl + 1: 'c' on the halved axes, '.' on the others
+        self.shapes, self.h2s, self.locs = poisson_hierarchy(shape, h2, npdt, min_size)
         self.finish_init(omega, nu1, nu2, lite)
 
     def finish_init(self, omega, nu1, nu2, lite):
@@ -647,6 +654,103 @@ class StencilGMG(PoissonGMG):
         ops.interp_add(xc_new, self.locs[lvl], add=x, out=out)  # x + P x_c
         self.spare[lvl] = x
         return self.sweeps(lvl, out, b, self.weights(self.nu2) if post else [])
+
+
+class EnsembleGMG:
+    """B small systems of ONE shape solved side by side, every solve of all members in ONE launch with one workgroup per
+    member (odil_stencil_solve_batch): residual, nested-iteration start, V-cycles down to the tolerance, the convergence
+    decision and -- for a Newton step -- the update, without a host read-back in between.  Member b's iterate after k
+    cycles is that of k launches of `ops.stencil_vcycle_tail` on its arrays alone, bit for bit.
+
+    EnsembleGMG(shape, h2, dtype, device, nbatch): the constant-coefficient Poisson operator, shared by all members --
+    levels, spacings, `poisson_jac_coeffs` and the coarsest inverse are those of the `PoissonGMG` hierarchy (min_size stops
+    the coarsening earlier; by default where at most `max_levels` levels remain).
+    EnsembleGMG([hierarchy, ...]): one hierarchy per member (`StencilGMG` objects of one shape, or anything with `shapes`,
+    `locs`, `tail_coeffs`, `coarse_inverse`, `weights`, `nu1`, `nu2`): their operators and inverses are packed per member."""
+
+    max_cells = 32768    # cells of a member's finest level (32^3, 128^2, 1-D up to 32768)
+    max_levels = 8       # kTailMaxLev of csrc/vcycle_tail.hip
+    max_coarsest = 512   # unknowns of the coarsest level (its dense inverse is applied by one workgroup)
+    method = "gmg-vcycle, one workgroup per member"
+
+    @classmethod
+    def plan(cls, shape, h2, npdt, min_size=None):
+        """(shapes, h2s, locs, min_size) of the hierarchy a member of this shape gets: PoissonGMG's, cut after
+        `max_levels` levels when it is longer (host arithmetic only)."""
+        shapes, h2s, locs = poisson_hierarchy(shape, h2, npdt, 2 if min_size is None else min_size)
+        if min_size is None:
+            min_size = 2
+            if len(shapes) > cls.max_levels:
+                # (stops PoissonGMG at that level: no halved extent of it reaches min_size again)
+                min_size = min(shapes[cls.max_levels - 1])
+                shapes, h2s, locs = poisson_hierarchy(shape, h2, npdt, min_size)
+        return shapes, h2s, locs, min_size
+
+    def __init__(self, shape, h2=None, dtype=None, device=None, nbatch=None, min_size=None):
+        if isinstance(shape, (list, tuple)) and shape and not isinstance(shape[0], (int, np.integer)):
+            members = list(shape)
+            first = members[0]
+            for b, h in enumerate(members):
+                if [tuple(s) for s in h.shapes] != [tuple(s) for s in first.shapes] or list(h.locs) != list(first.locs) \
+                        or h.dtype != first.dtype or (h.nu1, h.nu2) != (first.nu1, first.nu2):
+                    raise ValueError("ensemble member {}: its hierarchy differs from member 0's".format(b))
+            self.nbatch, self.dtype, self.device = len(members), first.dtype, first.device
+            self.shapes, self.locs = [tuple(s) for s in first.shapes], list(first.locs)
+            self.coeffs = torch.stack([torch.cat([h.tail_coeffs(l).reshape(-1) for l in range(len(self.shapes))])
+                                       for h in members]).contiguous()
+            self.inv = torch.stack([h.coarse_inverse() for h in members]).contiguous()
+            self.base = first
+        else:
+            npdt = np.float64 if dtype == torch.float64 else np.float32
+            min_size = self.plan(shape, h2, npdt, min_size)[3]
+            self.base = base = PoissonGMG(shape, h2, dtype, device, min_size=min_size)
+            self.nbatch, self.dtype, self.device = int(nbatch), dtype, device
+            self.shapes, self.locs = [tuple(s) for s in base.shapes], list(base.locs)
+            self.coeffs = torch.cat([base.tail_coeffs(l).reshape(-1) for l in range(base.nlvl)])
+            self.inv = base.coarse_inverse()
+        self.halve = [[c == "c" for c in loc] for loc in self.locs]
+        self.wpre, self.wpost = self.base.weights(self.base.nu1), self.base.weights(self.base.nu2)
+        self.cells = math.prod(self.shapes[0])
+        need = ops.stencil_solve_batch_work(self.shapes)
+        if not need or len(self.shapes) > self.max_levels or math.prod(self.shapes[-1]) > self.max_coarsest:
+            raise ValueError("EnsembleGMG: levels {} are not walked by one workgroup (at most {} levels, a coarsest level "
+                             "of at most {} unknowns)".format(self.shapes, self.max_levels, self.max_coarsest))
+        self.work = torch.empty((self.nbatch, need), dtype=self.dtype, device=self.device)
+        self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
+                                                    self.wpre, self.wpost)
+        self._out = dict()      # maxcycles -> (history, outcome) device tensors
+        self.history = None     # [B, maxcycles + 2], [B, 2] of the last launch on the host
+        self.outcome = None
+
+    def _run(self, x, b, tol, maxcycles, start, mode):
+        assert tuple(x.shape) == tuple(b.shape) == (self.nbatch,) + self.shapes[0], (x.shape, b.shape)
+        out = self._out.get(maxcycles)
+        if out is None:
+            out = self._out[maxcycles] = (
+                torch.zeros((self.nbatch, maxcycles + 2), dtype=torch.float64, device=self.device),
+                torch.zeros((self.nbatch, 2), dtype=torch.int32, device=self.device))
+        self._launch(x, b, out[0], out[1], start, mode, maxcycles, tol)
+        # ONE read-back per solve of the whole ensemble, after the launch
+        self.history, self.outcome = out[0].cpu().numpy(), out[1].cpu().numpy()
+        return x
+
+    def solve(self, b, x, tol=1e-10, maxcycles=60, start=2):
+        """A_b x_b = b_b for every member, in place in x [B, *shape] (start 0: from zero, 1: from the content of x, 2: by
+        nested iteration) to mean((A x - b)^2) <= tol^2 mean(b^2), at most `maxcycles` cycles each; `status` tells."""
+        return self._run(x, b, tol, maxcycles, start, 0)
+
+    def newton_step(self, u, rhs, tol=1e-10, maxcycles=60, start=2):
+        """u_b <- u_b - d_b with A_b d_b = A_b u_b - rhs_b for every member, in place in u [B, *shape]."""
+        return self._run(u, rhs, tol, maxcycles, start, 1)
+
+    def status(self, member):
+        """What `PoissonGMG.solve` reports, for one member of the last launch."""
+        k, why = (int(v) for v in self.outcome[member])
+        hist = self.history[member]
+        res = math.sqrt(max(float(hist[1 + k]), 0.0) * self.cells) if hist[1 + k] == hist[1 + k] else float("nan")
+        bn = math.sqrt(max(float(hist[0]), 0.0) * self.cells) if hist[0] == hist[0] else float("nan")
+        return dict(residual=res, bnorm=bn, niter=k, converged=why == 0, stagnated=bool(why == 2 and res < bn),
+                    method=self.method)
 
 
 def stencil_coefficients(items, shape, period=None, dtype=None, device=None):

@@ -309,6 +309,77 @@ def stencil_vcycle_tail_plan(coeffs, shapes, halve, work, inv, wpre, wpost):
     return launch
 
 
+def stencil_solve_batch_work(shapes):
+    """Work elements per member of `stencil_solve_batch` (0: malformed shapes)."""
+    flat = [int(n) for shape in shapes for n in shape]
+    return int(_lib.load().odil_stencil_solve_batch_work(i64(flat), c_int(len(shapes)), c_int(len(shapes[0]))))
+
+
+def _member_stride(t, need, shared_ok=False):
+    """Elements between the members of a packed tensor [B, ...] whose members are contiguous (0: one member shared by all)."""
+    if shared_ok and t.dim() == 1:
+        return 0
+    assert t.dim() >= 2 and t[0].is_contiguous() and t[0].numel() >= need, (tuple(t.shape), need)
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t[0].numel())
+
+
+def _base_ptr(t):
+    """Device pointer of the first element of a packed tensor (its members are contiguous, the whole need not be)."""
+    if not t.is_cuda:
+        raise _lib.OdilHipError("tensor is on '{}': the HIP kernels need device memory (no CPU fallback)".format(t.device))
+    return c_void_p(t.data_ptr())
+
+
+def stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpost):
+    """`stencil_solve_batch` with everything that does not change between calls prepared once (as
+    `stencil_vcycle_tail_plan`): -> launch(x, b, history, outcome, start, mode, maxcycles, tol).
+    coeffs: flat [ncoeff] (one operator for all members) or [B, ncoeff]; inv: [n, n] or [B, n, n]; work: [B, >= need];
+    x, b: [B, *shape] with contiguous members (any leading stride); history: [B, >= maxcycles + 2] float64; outcome:
+    [B, 2] int32."""
+    import ctypes
+
+    nlev, ndim = len(shapes), len(shapes[0])
+    cells, ninv = math.prod(shapes[0]), math.prod(shapes[-1])
+    shapes64 = i64([int(n) for shape in shapes for n in shape])
+    mask = (ctypes.c_int * max(1, (nlev - 1) * ndim))(*[int(bool(h)) for tr in halve for h in tr])
+    maskp = ctypes.cast(mask, ctypes.c_void_p)
+    wa, wap = host_reals(list(wpre) or [0.0], coeffs.dtype)
+    wb, wbp = host_reals(list(wpost) or [0.0], coeffs.dtype)
+    need = stencil_solve_batch_work(shapes)
+    ncoeff = (2 * ndim + 1) * sum(math.prod(s) for s in shapes)
+    cstride = _member_stride(coeffs, ncoeff, shared_ok=True)
+    istride = 0 if inv.dim() == 2 else _member_stride(inv, ninv * ninv)
+    wstride = _member_stride(work, need)
+    assert work.shape[0] == nbatch and work.is_contiguous() and coeffs.dtype == work.dtype == inv.dtype
+    assert coeffs.is_contiguous() and inv.is_contiguous() and tuple(inv.shape[-2:]) == (ninv, ninv)
+    assert (coeffs.numel() >= ncoeff if cstride == 0 else coeffs.shape[0] == nbatch) and (istride == 0 or inv.shape[0] == nbatch)
+    head = (_base_ptr(coeffs), c_int64(cstride), shapes64, maskp, c_int(nlev), c_int(ndim), c_int(nbatch))
+    mid = (ptr(work), c_int64(wstride), c_int64(work.numel()), _base_ptr(inv), c_int64(istride), c_int(ninv), wap,
+           c_int(len(wpre)), wbp, c_int(len(wpost)))
+    keep = (coeffs, work, inv, mask, wa, wb, shapes64)  # (the arrays the pointers point into)
+    dtype = coeffs.dtype
+
+    def launch(x, b, history, outcome, start=2, mode=0, maxcycles=60, tol=0.0):
+        assert x.dtype == b.dtype == dtype and x.shape[0] == b.shape[0] == nbatch
+        assert history.dtype == torch.float64 and history.shape[0] == nbatch and history.is_contiguous()
+        assert outcome.dtype == torch.int32 and tuple(outcome.shape) == (nbatch, 2) and outcome.is_contiguous()
+        call("stencil_solve_batch", dtype, *head, _base_ptr(x), c_int64(_member_stride(x, cells)),
+             _base_ptr(b), c_int64(_member_stride(b, cells)), *mid, c_int(start), c_int(mode), c_int(maxcycles),
+             float(tol), ptr(history), c_int64(history.shape[1]), ptr(outcome), stream_ptr())
+        return x
+
+    launch.keep = keep
+    return launch
+
+
+def stencil_solve_batch(coeffs, shapes, halve, x, b, work, inv, wpre, wpost, history, outcome, start=2, mode=0, maxcycles=60,
+                        tol=0.0):
+    """Whole multigrid solves (mode 1: Newton steps) of x.shape[0] small systems in ONE launch, one workgroup per member
+    (include/odil_hip.h: odil_stencil_solve_batch); the arguments of `stencil_solve_batch_plan`."""
+    return stencil_solve_batch_plan(coeffs, shapes, halve, x.shape[0], work, inv, wpre, wpost)(
+        x, b, history, outcome, start, mode, maxcycles, tol)
+
+
 def restrict_adj(gcoarse, loc, fshape):
     """R^T gcoarse (cotangent of restrict_to_coarser) for a fine array of shape `fshape`."""
     fshape = tuple(int(s) for s in fshape)

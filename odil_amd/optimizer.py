@@ -124,11 +124,13 @@ class _EpochGraph:
     def capture(self):
         from .util import printlog
 
+        from .runtime import graph_capture
+
         try:
             graph = torch.cuda.CUDAGraph()
             if self.begin is not None:
                 self.begin(self.nrows)
-            with torch.cuda.graph(graph):
+            with graph_capture(graph):  # (no collection of the interpreter in the middle of the capture)
                 pinfo = self._body()
             # the report of an epoch is a dict of DEVICE scalars that a lazy wrapper converts (and
             # caches) on first read: keep the raw tensors, hand out a fresh wrapper per replay
@@ -901,6 +903,7 @@ class LbfgsbOptimizer(Optimizer):
                 return loss, grads, (raw[0](**raw[1]) if raw[0] is not None else raw[1])
             ev["count"] += 1
             if want_graph and ev["count"] == 3:
+                from .runtime import graph_capture
                 from .util import printlog
 
                 try:
@@ -910,7 +913,7 @@ class LbfgsbOptimizer(Optimizer):
                         ev["begun"] = True
                     if refresh is not None:
                         refresh()
-                    with torch.cuda.graph(graph):
+                    with graph_capture(graph):
                         loss, grads, pinfo = loss_grad(xviews)
                     kind = type(pinfo) if isinstance(pinfo, dict) else None
                     raw = {k: dict.__getitem__(pinfo, k) for k in dict.keys(pinfo)} if kind else pinfo

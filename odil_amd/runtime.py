@@ -15,6 +15,8 @@ TRACE    1 (default): trace every other operator once and run it as one generate
 `tf` and `jax` are None (reference examples test them to pick code paths).
 """
 
+import contextlib
+import gc
 import os
 import sys
 
@@ -54,6 +56,25 @@ def get_mod():
             torch.cuda.set_device(local_rank)
         _mod = ModRocm()
     return _mod
+
+
+@contextlib.contextmanager
+def graph_capture(graph):
+    """`torch.cuda.graph(graph)` with the interpreter's cyclic collector run before and held off during the capture.  A
+    dead reference cycle that holds the graph of an EARLIER run (an epoch closure and its runner refer to each other) is
+    freed whenever the collector happens to run; releasing a graph's memory pool while a stream captures aborts the
+    process.  (torch.cuda.graph collected before every capture in earlier releases; it no longer does by default.)"""
+    import torch
+
+    gc.collect()
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if collecting:
+            gc.enable()
 
 
 def __getattr__(name):

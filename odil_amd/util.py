@@ -558,6 +558,109 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
                             lr=args.lr, lrs=lrs, epoch_start=args.epoch_start, **kwargs)
 
 
+def optimize_newton_ensemble(args, problems, states, callback=None):
+    """Newton on B small Poisson problems AT ONCE: every epoch is ONE launch that runs the whole Newton step of all
+    members, one workgroup per member (gmg.EnsembleGMG.newton_step: residual, nested-iteration start, V-cycles down to the
+    tolerance, the convergence decision and the update, no host read-back in between).  Every member ends at the Newton
+    iterate `optimize_newton(args, problem, state)` reaches for it alone, to the tolerance of the linear solve.
+
+    args.linsolver must be 'direct' or 'multigrid', without damping; tolerance and cycle budget are those of the
+    single-problem multigrid route (linsolver.cycle_budget, at least 50 eps of the working precision).
+    callback(member, state, epoch, pinfo): called for every member at args.epoch_start (the initial evaluation) and at the
+    epochs its `next_active(epoch)` attribute names (without the attribute: every epoch); pinfo as `optimize_newton`
+    reports it, after a step with pinfo["linsolver"] = the member's solver status.
+    Members must be the recognised Poisson operator with one plain `Field` unknown (no multigrid decomposition), share
+    cshape, spacing, dtype and device and be admitted by `fused.newton_refusal`; anything else raises ValueError naming the
+    first offending member -- structure is checked for all members before any operator is probed.
+    Returns ([arrays of member b], optinfo); optinfo.cycles / .residuals: [B, epochs] cycles run and final residual norms."""
+    from . import fused
+    from . import linsolver as ls
+
+    if not problems or len(problems) != len(states):
+        raise ValueError("optimize_newton_ensemble: {} problems with {} states".format(len(problems), len(states)))
+    linsolver = getattr(args, "linsolver", "direct")
+    if linsolver not in ("direct", "multigrid"):
+        raise ValueError("optimize_newton_ensemble: linsolver '{}' (the one-workgroup Newton solves serve 'direct' and "
+                         "'multigrid')".format(linsolver))
+    if getattr(args, "linsolver_damp", 0) or getattr(args, "linsolver_dampdiag", 0):
+        raise ValueError("optimize_newton_ensemble: damping (linsolver_damp / linsolver_dampdiag) is not served: the cycles "
+                         "solve M d = r, which has the solution of the normal equations only without it")
+
+    def refuse(member, reason):
+        raise ValueError("optimize_newton_ensemble: member {}: {}".format(member, reason))
+
+    first = None
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        domain = problem.domain
+        if not state.initialized:
+            refuse(b, "uninitialized state, use `state = domain.init_state(state)`")
+        if len(state.fields) != 1:
+            refuse(b, "{} unknown fields (the Poisson problem has one)".format(len(state.fields)))
+        (field,) = state.fields.values()
+        if type(field) is not Field:
+            refuse(b, "the unknown is a {} (a plain Field is needed: no multigrid decomposition)".format(type(field).__name__))
+        cshape = tuple(int(n) for n in domain.cshape)
+        if tuple(int(n) for n in field.array.shape) != cshape or field.loc != "c" * domain.ndim:
+            refuse(b, "the unknown is not a cell-centred field of the domain")
+        dtype = field.array.dtype
+        npdt = np.float64 if dtype == torch.float64 else np.float32
+        kind = dict(cshape=cshape, dtype=dtype, device=field.array.device,
+                    spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
+        reason = fused.newton_refusal(cshape, [npdt(v) ** 2 for v in kind["spacing"]], dtype)
+        if reason is not None:
+            refuse(b, reason)
+        first = first or kind
+        for what, label in (("cshape", "cells"), ("dtype", "dtype"), ("device", "device"), ("spacing", "grid spacing")):
+            if kind[what] != first[what]:
+                refuse(b, "{} {} differ from member 0's {}".format(label, kind[what], first[what]))
+    evaluators = []
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        problem.recognise(state)
+        ev = getattr(problem, "_fused", None)
+        if ev is None or ev.nlvl != 1:
+            refuse(b, "the operator is not the recognised Poisson stencil")
+        evaluators.append(ev)
+    ev = evaluators[0]
+    nb = len(problems)
+    solver = gmg.EnsembleGMG(ev.cshape, ev.h2, ev.dtype, ev.device, nb)
+    u = torch.stack([problem.domain.arrays_from_state(state)[0].to(ev.dtype) for problem, state in zip(problems, states)])
+    rhs = torch.stack([e.rhs.reshape(ev.cshape) for e in evaluators])
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        problem.domain.arrays_to_state([u[b]], state)  # (views of the packed iterate: always the current one)
+    tol, maxcycles = ls.cycle_budget(linsolver, getattr(args, "linsolver_tol", 1e-10), getattr(args, "linsolver_maxiter", None))
+    tol = max(tol, 50 * float(torch.finfo(ev.dtype).eps))
+    printlog("Running Newton optimizer on an ensemble of {} members".format(nb))
+
+    def report(epoch, stepped):
+        for b, (problem, state) in enumerate(zip(problems, states)):
+            loss, _, terms, names, norms = problem.eval_loss_grad_device(state)
+            pinfo = _pinfo(loss, terms, names, norms)
+            if stepped:
+                pinfo["linsolver"] = solver.status(b)
+            callback(b, state, epoch, pinfo)
+
+    nepochs = max(args.epochs - args.epoch_start, 0)
+    cycles = np.zeros((nb, nepochs), dtype=np.int64)
+    residuals = np.zeros((nb, nepochs))
+    next_active = getattr(callback, "next_active", None) if callback else None
+    due = None
+    if callback:
+        report(args.epoch_start, False)
+        due = next_active(args.epoch_start) if next_active else args.epoch_start + 1
+    for epoch in range(args.epoch_start, args.epochs):
+        solver.newton_step(u, rhs, tol=tol, maxcycles=maxcycles)
+        k = epoch - args.epoch_start
+        cycles[:, k] = solver.outcome[:, 0]
+        residuals[:, k] = [solver.status(b)["residual"] for b in range(nb)]
+        if getattr(args, "linsolver_verbose", 0):
+            printlog([solver.status(b) for b in range(nb)])
+        if callback and epoch + 1 >= due:
+            report(epoch + 1, True)
+            due = next_active(epoch + 1) if next_active else epoch + 2
+    arrays = [problem.domain.arrays_from_state(state) for problem, state in zip(problems, states)]
+    return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver)
+
+
 def optimize(args, optname, problem, state, callback, **kwargs):
     if optname == "newton":
         return optimize_newton(args, problem, state, callback, **kwargs)
