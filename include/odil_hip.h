@@ -220,6 +220,27 @@ int odil_poisson_adjoint_transpose_adam_f32(const float* fu, float* g0, float* g
                                             const float* h2, float scale, float* x0, float* m0, float* v0, float* x1,
                                             float* m1, float* v1, float alpha, float one_minus_b1, float one_minus_b2,
                                             float eps, const float* alpha_dev, int cut_lo, int cut_hi, void* stream);
+/* The same launch with an explicit cut of the coarse z axis (Z = fshape[0] / 2 planes) into units of work: planes
+ * [0, Zs) in chunks of L, planes [Zs, Z) in chunks of S, 1 <= S <= L <= 64, 0 <= Zs <= Z; the long chunks are
+ * dispatched first.  Every plan gives the same bits; L <= 0 takes the plan the entry points above take, which
+ * odil_tile_sched_rule(fshape, 0, plan) writes to plan[0 .. 2] = (L, Zs, S) (Zs == Z: one tier); kind 1: the plan of
+ * odil_interp_adj on a 'ccc' array of doubles of that fine shape, where the LDS-tile kernel serves it. */
+int odil_poisson_adjoint_transpose_adam_plan_f64(const double* fu, double* g0, double* g1, const int64_t* fshape,
+                                                 const double* h2, double scale, double* x0, double* m0, double* v0,
+                                                 double* x1, double* m1, double* v1, double alpha, double one_minus_b1,
+                                                 double one_minus_b2, double eps, const double* alpha_dev, int cut_lo,
+                                                 int cut_hi, int L, int Zs, int S, void* stream);
+int odil_poisson_adjoint_transpose_adam_plan_f32(const float* fu, float* g0, float* g1, const int64_t* fshape,
+                                                 const float* h2, float scale, float* x0, float* m0, float* v0, float* x1,
+                                                 float* m1, float* v1, float alpha, float one_minus_b1,
+                                                 float one_minus_b2, float eps, const float* alpha_dev, int cut_lo,
+                                                 int cut_hi, int L, int Zs, int S, void* stream);
+int odil_tile_sched_rule(const int64_t* fshape, int kind, int* plan);
+/* Host only: the units of that schedule for Z planes and Y x XS tiles.  Returns the number of workgroups (-1: not a
+ * plan) and writes (z0, z1, y, xs) of workgroup b to units[4 b ..], -1 four times for a workgroup without a unit,
+ * for b < capacity.  It walks the kernels' own decode. */
+int64_t odil_tile_sched_units(int64_t Z, int64_t Y, int64_t XS, int L, int64_t Zs, int S, int32_t* units,
+                              int64_t capacity);
 /* One damped-Jacobi sweep of that operator: uout = u - omega (A u - rhs) / diag(A), uout != u.  The
  * smoother of the geometric multigrid that solves the Newton system of the Poisson stencil
  * (reference linsolver.py:61-72 hands that system to pyamg).  u == NULL here and in the two-sweep form below: the sweeps

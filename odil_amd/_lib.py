@@ -61,6 +61,8 @@ _SIGNATURES = {
     "poisson_adjoint_adam": [_P, _P, _P, _P, _P, _I64P, c_int, _P, _R, _R, _R, _R, _R, _P, _P],
     "poisson_adjoint_transpose_adam": [_P, _P, _P, _I64P, _P, _R, _P, _P, _P, _P, _P, _P, _R, _R, _R, _R, _P, c_int,
                                        c_int, _P],
+    "poisson_adjoint_transpose_adam_plan": [_P, _P, _P, _I64P, _P, _R, _P, _P, _P, _P, _P, _P, _R, _R, _R, _R, _P, c_int,
+                                            c_int, c_int, c_int, c_int, _P],
     "poisson_jac_coeffs": [_P, _I64P, c_int, _P, _P],
     "poisson_jac_match": [_P, _I64P, c_int, _P, _P, _P, _P],
     "adam_step": [_P, _P, _P, _P, c_int64, _R, _R, _R, _R, _P, _P],
@@ -108,7 +110,8 @@ EXPORTED = [
     "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials", "odil_poisson_batch_partials",
     "odil_mg_batch_levels_ok", "odil_poisson_residual_synth_workspace_bytes",
     "odil_mg_volumes_levels_ok", "odil_interp_adj_kind", "odil_poisson_residual_synth_batch_workspace_bytes",
-    "odil_poisson_residual_synth_batch_partials", "odil_stencil_solve_batch_work",
+    "odil_poisson_residual_synth_batch_partials", "odil_stencil_solve_batch_work", "odil_tile_sched_rule",
+    "odil_tile_sched_units",
 ] + [
     "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
 ] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
@@ -161,6 +164,10 @@ def load():
     lib.odil_poisson_residual_synth_batch_partials.argtypes = [_I64P]
     lib.odil_stencil_solve_batch_work.restype = c_int64
     lib.odil_stencil_solve_batch_work.argtypes = [_I64P, c_int, c_int]
+    lib.odil_tile_sched_rule.restype = c_int
+    lib.odil_tile_sched_rule.argtypes = [_I64P, c_int, ctypes.POINTER(c_int)]
+    lib.odil_tile_sched_units.restype = c_int64
+    lib.odil_tile_sched_units.argtypes = [c_int64, c_int64, c_int64, c_int, c_int64, c_int, _P, c_int64]
     for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)
         fn = getattr(lib, name)
         fn.restype = c_int

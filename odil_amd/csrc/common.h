@@ -129,11 +129,11 @@ struct UnitSched {
   int per_xcd;      // units per XCD (grid = 8 * per_xcd), or total units when axis < 0
 };
 
-// The schedule with `zc` planes per z-chunk.
-inline UnitSched make_unit_sched_chunked(int64_t Z, int64_t Y, int64_t XS, int zc) {
+// The schedule of `nchunks` z-chunks (of `zc` planes, as far as this struct knows).
+inline UnitSched make_unit_sched_of_chunks(int64_t nchunks, int64_t Y, int64_t XS, int zc) {
   UnitSched s;
   s.ZC = zc;
-  s.ZCH = (int)((Z + zc - 1) / zc);
+  s.ZCH = (int)nchunks;
   s.Y = (int)Y;
   s.XS = (int)XS;
   if (Y >= 4 * kNumXcd) {
@@ -154,6 +154,11 @@ inline UnitSched make_unit_sched_chunked(int64_t Z, int64_t Y, int64_t XS, int z
   return s;
 }
 
+// The schedule with `zc` planes per z-chunk.
+inline UnitSched make_unit_sched_chunked(int64_t Z, int64_t Y, int64_t XS, int zc) {
+  return make_unit_sched_of_chunks((Z + zc - 1) / zc, Y, XS, zc);
+}
+
 // `target_units`: how many workgroups the launch should at least be cut into.  Kernels that prime a
 // window of planes before their first step (P^T: two extra fine-plane reductions per chunk) ask for
 // fewer, longer chunks.
@@ -168,17 +173,23 @@ inline UnitSched make_unit_sched(int64_t Z, int64_t Y, int64_t XS, int64_t targe
 inline int unit_grid(const UnitSched& s) { return s.axis < 0 ? s.per_xcd : s.per_xcd * kNumXcd; }
 
 #ifdef __HIPCC__
-// Returns false when this workgroup has no unit (padding of an uneven chunk).
-__device__ inline bool unit_decode(const UnitSched& s, int& zc, int& y, int& xs) {
+#define ODIL_HD __host__ __device__
+#else
+#define ODIL_HD
+#endif
+
+// The unit of workgroup `b`; false when it has none (padding of an uneven chunk).  Closed form: the host restates
+// nothing (odil_tile_sched_units lists a schedule through this very function).
+ODIL_HD inline bool unit_decode_at(const UnitSched& s, int b, int& zc, int& y, int& xs) {
   if (s.axis < 0) {
-    const int i = blockIdx.x;
+    const int i = b;
     xs = i % s.XS;
     const int r = i / s.XS;
     y = r % s.Y;
     zc = r / s.Y;
     return true;
   }
-  const int k = blockIdx.x % kNumXcd, i = blockIdx.x / kNumXcd;
+  const int k = b % kNumXcd, i = b / kNumXcd;
   xs = i % s.XS;
   const int r = i / s.XS;
   if (s.axis == 1) {
@@ -194,7 +205,57 @@ __device__ inline bool unit_decode(const UnitSched& s, int& zc, int& y, int& xs)
   zc = ru / s.Y;
   return zc < s.ZCH;
 }
+
+#ifdef __HIPCC__
+// Returns false when this workgroup has no unit.
+__device__ inline bool unit_decode(const UnitSched& s, int& zc, int& y, int& xs) {
+  return unit_decode_at(s, (int)blockIdx.x, zc, y, xs);
+}
 #endif
+
+// ---------------------------------------------------------------------------
+// Two-tier schedule of the LDS-tile transposes (k_poisson_adjoint_tile, k_interp_adj_tile).
+//
+// Every unit of those kernels primes its window with two pairs of fine planes that belong to the chunk
+// below: long chunks re-read less.  The last round of units of a launch drains raggedly, the CUs idle
+// for up to a whole unit: short chunks drain evenly.  So coarse planes [0, Zs) are cut into chunks of L
+// and [Zs, Z) into chunks of S <= L (the last chunk of either tier ragged), and the chunk index of the
+// UnitSched order counts the long chunks first, in ascending z, then the short ones: workgroups are
+// dispatched in blockIdx order, the short units run last.  Where a chunk is cut does not enter the
+// arithmetic of those kernels (mg_march.hip: tile_stage), so every plan gives the same bits.
+// L == S, Zs == 0 and Zs == Z are one tier: the units of make_unit_sched_chunked(Z, Y, XS, L).
+// ---------------------------------------------------------------------------
+struct TierSched {
+  UnitSched u;  // ZCH = NL + NS chunks, ZC = L
+  int Z, Zs;    // planes; planes of the long tier
+  int S;        // planes per short chunk
+  int NL;       // number of long chunks
+};
+
+inline bool tier_plan_ok(int64_t Z, int L, int64_t Zs, int S) { return S >= 1 && S <= L && Zs >= 0 && Zs <= Z; }
+
+inline TierSched make_tier_sched(int64_t Z, int64_t Y, int64_t XS, int L, int64_t Zs, int S) {
+  if (L > Z) L = (int)Z;
+  if (S > L) S = L;
+  if (Zs == 0) L = S;               // no long tier
+  if (L == S || Zs >= Z) Zs = Z, S = L;  // one tier
+  TierSched t;
+  t.Z = (int)Z, t.Zs = (int)Zs, t.S = S;
+  t.NL = (int)((Zs + L - 1) / L);
+  t.u = make_unit_sched_of_chunks(t.NL + (Z - Zs + S - 1) / S, Y, XS, L);
+  return t;
+}
+
+// Coarse planes [z0, z1) and the tile (y, xs) of workgroup `b`; false when it has no unit.
+ODIL_HD inline bool tier_decode_at(const TierSched& t, int b, int& z0, int& z1, int& y, int& xs) {
+  int zc;
+  if (!unit_decode_at(t.u, b, zc, y, xs)) return false;
+  const bool lng = zc < t.NL;
+  const int len = lng ? t.u.ZC : t.S, end = lng ? t.Zs : t.Z;
+  z0 = lng ? zc * len : t.Zs + (zc - t.NL) * len;
+  z1 = z0 + len < end ? z0 + len : end;
+  return true;
+}
 
 #ifdef __HIPCC__
 struct RowIter {

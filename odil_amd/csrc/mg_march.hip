@@ -1024,8 +1024,8 @@ __device__ __forceinline__ void tile_stage(const TileCtx<T>& c, typename TileVec
 // float kernel with one column ran at 1.8 TB/s on the space part of the 4-D tracer transposes).
 template <typename T, int CX>
 __global__ __launch_bounds__(kBlock) void k_interp_adj_tile(const T* __restrict__ gfine, T* __restrict__ gcoarse,
-                                                            T* __restrict__ gscaled, MarchArgs a, T scale,
-                                                            AdamArgs<T> ad) {
+                                                            T* __restrict__ gscaled, MarchArgs a, TierSched ts,
+                                                            T scale, AdamArgs<T> ad) {
   typedef typename TileVec<T, CX>::type P2;  // a native vector type: staged values stay in registers
   constexpr int NV = 2 * CX;
   // row-major over (row, pack) with rows of kTileRS packs; the loads are padded to a whole number of packs per
@@ -1033,8 +1033,8 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_tile(const T* __restrict_
   __shared__ P2 tile[2][kTileLds];
   __shared__ float wtab[12 * (CX + 1) * kBlock];  // weight tables of the threads next to a wall
   const int cny = a.cn[1], fny = a.fn[1], fnx = a.fn[2];
-  int zc, yt, xt;
-  if (!unit_decode(a.usched, zc, yt, xt)) return;  // whole workgroup
+  int z0, z1, yt, xt;  // (the chunk comes from the two-tier schedule, not from a.usched)
+  if (!tier_decode_at(ts, (int)blockIdx.x, z0, z1, yt, xt)) return;  // whole workgroup
   TileCtx<T> c;
   c.cnz = a.cn[0], c.cnx = a.cn[2], c.fnz = a.fn[0];
   c.cut_lo = a.cut_lo, c.cut_hi = a.cut_hi;
@@ -1046,8 +1046,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_tile(const T* __restrict_
   if (ad.x) ad.x += cvol, ad.m += cvol, ad.v += cvol;
   if (ad.alpha_dev) ad.alpha_dev += (int64_t)blockIdx.y * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   c.scale = scale;
-  c.z0 = zc * a.usched.ZC;
-  const int z1 = c.z0 + a.usched.ZC < c.cnz ? c.z0 + a.usched.ZC : c.cnz;
+  c.z0 = z0;
   tile_column(c.lx, c.ly);
   c.jy = yt * kTileY + c.ly, c.jx = (xt * kTileX + c.lx) * CX;  // first of this thread's CX columns
   c.owner = c.jy < cny && c.jx < c.cnx;  // (CX = 2 needs an even cnx: both columns exist or neither)
@@ -1149,8 +1148,8 @@ __device__ __forceinline__ T lap_inner(T fb, T fm, T fp, const H2<T>& h, int ax)
 // hyper-parameters (one set in scalar registers: the kernel spills them).
 template <typename T, bool MUL, bool G0>
 __global__ __launch_bounds__(kBlock) void k_poisson_adjoint_tile(const T* __restrict__ fu, T* __restrict__ g0out_,
-                                                                 T* __restrict__ gcoarse, MarchArgs a, H2<T> h,
-                                                                 T scale, AdamArgs<T> ad0, T* __restrict__ x1,
+                                                                 T* __restrict__ gcoarse, MarchArgs a, TierSched ts,
+                                                                 H2<T> h, T scale, AdamArgs<T> ad0, T* __restrict__ x1,
                                                                  T* __restrict__ m1, T* __restrict__ v1) {
   T* const g0out = G0 ? g0out_ : nullptr;
   AdamArgs<T> ad1 = ad0;
@@ -1159,8 +1158,8 @@ __global__ __launch_bounds__(kBlock) void k_poisson_adjoint_tile(const T* __rest
   __shared__ P2 ring[4 * kFuPacks];      // scale * fu, planes z & 3
   __shared__ P2 gt[2][kTileR * kTileRS]; // g0 of the current pair of planes
   const int cny = a.cn[1], fny = a.fn[1], fnx = a.fn[2];
-  int zc, yt, xt;
-  if (!unit_decode(a.usched, zc, yt, xt)) return;  // whole workgroup
+  int z0, z1, yt, xt;  // (the chunk comes from the two-tier schedule, not from a.usched)
+  if (!tier_decode_at(ts, (int)blockIdx.x, z0, z1, yt, xt)) return;  // whole workgroup
   if constexpr (MUL) h.mul_ok[0] = h.mul_ok[1] = h.mul_ok[2] = 1;  // (the wall rows lose their divide as well)
   // the step size of a replayed epoch lives in device memory: one read per workgroup, not one per cell
   if (ad0.alpha_dev) ad0.alpha = *ad0.alpha_dev;
@@ -1172,8 +1171,7 @@ __global__ __launch_bounds__(kBlock) void k_poisson_adjoint_tile(const T* __rest
   c.cut_lo = a.cut_lo, c.cut_hi = a.cut_hi;
   c.cplane = (int64_t)cny * c.cnx, c.fplane = (int64_t)fny * fnx;
   c.scale = T(1);
-  c.z0 = zc * a.usched.ZC;
-  const int z1 = c.z0 + a.usched.ZC < c.cnz ? c.z0 + a.usched.ZC : c.cnz;
+  c.z0 = z0;
   tile_column(c.lx, c.ly);
   c.jy = yt * kTileY + c.ly, c.jx = xt * kTileX + c.lx;
   c.owner = c.jy < cny && c.jx < c.cnx;
@@ -1828,15 +1826,51 @@ static bool adj_rows_launch(const T* gfine, T* gcoarse, T* gscaled, const MarchA
 
 // ODIL_ADJ_TILE=0 keeps the register-window kernel on every level (read per call: the tests compare both)
 template <typename T>
-static void launch_adj_tile(dim3 grid, bool wide, hipStream_t stream, const T* gfine, T* gcoarse, T* gscaled,
+static void launch_adj_tile(const TierSched& ts, bool wide, hipStream_t stream, const T* gfine, T* gcoarse, T* gscaled,
                             const MarchArgs& m, T scale, const AdamArgs<T>& ad) {
+  const dim3 grid(unit_grid(ts.u), m.lead_cn);
   if constexpr (sizeof(T) == 4) {
     if (wide) {
-      hipLaunchKernelGGL((k_interp_adj_tile<T, 2>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, gscaled, m, scale, ad);
+      hipLaunchKernelGGL((k_interp_adj_tile<T, 2>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, gscaled, m, ts, scale,
+                         ad);
       return;
     }
   }
-  hipLaunchKernelGGL((k_interp_adj_tile<T, 1>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, gscaled, m, scale, ad);
+  hipLaunchKernelGGL((k_interp_adj_tile<T, 1>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, gscaled, m, ts, scale, ad);
+}
+
+// The plan of a tile launch, from the shape alone.  `target_units` is the single-tier cut the launch had before
+// (make_unit_sched); its chunk length c stays the shortest long chunk.  The kernels hold two workgroups per CU, so
+// kTileSlots units are resident.  The short tier is the last planes, worth kTierTailRounds rounds of slots in chunks
+// of kTierShort planes.  L is the length at which ALL planes would fill kTierBulkRounds rounds of slots (at most 64):
+// the long tier, being the short planes short of that, ends in a ragged chunk, and the slots that take it are the
+// ones free for the short units -- every slot then ends at about the same time.  A long tier of whole rounds with
+// none to spare is the layout to avoid: 512^3 with (L, Zs, S) = (48, 240, 4) leaves half of the slots idle for a
+// 48-plane unit, +2.8 % on the launch, where (32, 240, 4) gives -3.5 .. -3.9 %.  Shapes whose rows do not split over
+// the XCDs, whose launch has under two rounds of units, or whose chunks are no longer than the short ones keep the
+// single tier unchanged.  (docs/rounds/kernel_log_r12.md: the sweep these constants come from)
+constexpr int kTileSlots = 512;
+constexpr int kTierShort = 4, kTierTailRounds = 2, kTierBulkRounds = 4;
+
+static void tile_plan_rule(int64_t Z, int64_t ytiles, int64_t xtiles, int64_t target_units, int& L, int64_t& Zs, int& S) {
+  const UnitSched one = make_unit_sched(Z, ytiles, xtiles, target_units);
+  L = S = one.ZC, Zs = Z;
+  const int64_t tiles = ytiles * xtiles;
+  if (one.axis != 1 || one.ZC <= kTierShort || (int64_t)one.ZCH * tiles < 2 * kTileSlots) return;
+  const int64_t short_chunks = kTierTailRounds * kTileSlots / tiles > 1 ? kTierTailRounds * kTileSlots / tiles : 1;
+  const int64_t tail = kTierShort * short_chunks;
+  if (tail + one.ZC > Z) return;
+  const int64_t round_planes = (int64_t)kTileSlots * kTierBulkRounds;
+  int64_t len = (Z * tiles + round_planes - 1) / round_planes;
+  len = len < one.ZC ? one.ZC : (len > 64 ? 64 : len);
+  L = (int)len, Zs = Z - tail, S = kTierShort;
+}
+
+static TierSched tile_plan(int64_t Z, int64_t ytiles, int64_t xtiles, int64_t target_units) {
+  int L, S;
+  int64_t Zs;
+  tile_plan_rule(Z, ytiles, xtiles, target_units, L, Zs, S);
+  return make_tier_sched(Z, ytiles, xtiles, L, Zs, S);
 }
 
 static bool adj_tile_enabled() {
@@ -1891,8 +1925,10 @@ static int adj_launch(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& 
       m.ty = kTileY;
       // the batch supplies the parallelism: long chunks (every chunk primes its window with two extra pairs of planes)
       const int64_t per_volume = kGridCap / m.lead_cn > 2 * ytiles * xtiles ? kGridCap / m.lead_cn : 2 * ytiles * xtiles;
+      // (one tier: the volumes of a batch end at different times anyway)
       m.usched = make_unit_sched(m.cn[0], ytiles, xtiles, per_volume);
-      launch_adj_tile<T>(dim3(unit_grid(m.usched), m.lead_cn), tile_wide, stream, gfine, gcoarse, gscaled, m, scale, ad);
+      launch_adj_tile<T>(make_tier_sched(m.cn[0], ytiles, xtiles, m.usched.ZC, m.cn[0], m.usched.ZC), tile_wide, stream,
+                         gfine, gcoarse, gscaled, m, scale, ad);
     } else
       hipLaunchKernelGGL((k_interp_adj_march_lead<T, CX, 1>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, gscaled,
                          m, scale, ad);
@@ -1905,8 +1941,9 @@ static int adj_launch(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& 
     const int64_t ytiles = (m.cn[1] + kTileY - 1) / kTileY, xtiles = (m.cn[2] + tile_cols - 1) / tile_cols;
     m.tx = kTileX;
     m.ty = kTileY;
-    m.usched = make_unit_sched(m.cn[0], ytiles, xtiles, small_level ? ODIL_ADJ_UNITS_SMALL : ODIL_TILE_UNITS);
-    launch_adj_tile<T>(dim3(unit_grid(m.usched)), tile_wide, stream, gfine, gcoarse, gscaled, m, scale, ad);
+    const TierSched ts = tile_plan(m.cn[0], ytiles, xtiles, small_level ? ODIL_ADJ_UNITS_SMALL : ODIL_TILE_UNITS);
+    m.usched = ts.u;
+    launch_adj_tile<T>(ts, tile_wide, stream, gfine, gcoarse, gscaled, m, scale, ad);
   } else
     hipLaunchKernelGGL((k_interp_adj_march<T, CX>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, gscaled, m, scale,
                        ad);
@@ -1917,7 +1954,7 @@ static int adj_launch(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& 
 template <typename T>
 int poisson_adjoint_transpose(const T* fu, T* g0, T* g1, const int64_t* fshape, const T* h2, T scale,
                               const AdamArgs<T>& ad0, const AdamArgs<T>& ad1, int cut_lo, int cut_hi,
-                              hipStream_t stream) {
+                              hipStream_t stream, const int* plan) {
   if (!fu || !g1 || !fshape || !h2) {
     set_error("poisson_adjoint_transpose: null pointer (fu, g1, shape, h2)");
     return ODIL_E_INVAL;
@@ -1946,16 +1983,31 @@ int poisson_adjoint_transpose(const T* fu, T* g0, T* g1, const int64_t* fshape, 
     set_error("poisson_adjoint_transpose: grid too large for one launch");
     return ODIL_E_INVAL;
   }
-  // workgroups per launch: 512^3 epoch 2.84 / 2.80 / 2.75 / 2.81 / 3.03 ms for 1024 / 2048 / 4096 / 8192 / 16384 (shorter
-  // chunks re-prime their windows more often, longer ones leave the phases of resident workgroups in step)
-  m.usched = make_unit_sched(m.cn[0], ytiles, xtiles, 2 * kGridCap);
+  // The z cut of the launch (common.h: TierSched).  One chunk length for the whole launch was a compromise -- 512^3
+  // epoch 2.84 / 2.80 / 2.75 / 2.81 / 3.03 ms for 1024 / 2048 / 4096 / 8192 / 16384 units: shorter chunks re-prime their
+  // windows more often, longer ones leave the last round of units to drain raggedly.  Found with two tiers (kernel
+  // log r12): the ragged end is the cost that counts.  Units of 64 planes without a short tier are 4 - 5 % slower than
+  // units of 16, with the last 16 planes in chunks of 4 they are 3.5 - 4.7 % FASTER; units of 16 gain 3 % from the
+  // same tail.  The priming reads fall with the unit count but buy little time.  512^3: (L, Zs, S) = (32, 240, 4).
+  TierSched ts;
+  if (plan) {
+    if (!tier_plan_ok(m.cn[0], plan[0], plan[1], plan[2]) || plan[0] > 64) {
+      set_error("poisson_adjoint_transpose: plan (L %d, Zs %d, S %d) needs 1 <= S <= L <= 64, 0 <= Zs <= %d", plan[0],
+                plan[1], plan[2], m.cn[0]);
+      return ODIL_E_INVAL;
+    }
+    ts = make_tier_sched(m.cn[0], ytiles, xtiles, plan[0], plan[1], plan[2]);
+  } else {
+    ts = tile_plan(m.cn[0], ytiles, xtiles, 2 * kGridCap);
+  }
+  m.usched = ts.u;
   T h[3] = {h2[0], h2[1], h2[2]};
   const H2<T> hh = make_h2<T>(h);
   // (the C ABI passes one set of hyper-parameters for both levels)
   const bool mul = hh.mul_ok[0] && hh.mul_ok[1] && hh.mul_ok[2];
-  const dim3 grid(unit_grid(m.usched));
-#define ODIL_LAUNCH_ADJ_TILE(MUL, G0)                                                                             \
-  hipLaunchKernelGGL((k_poisson_adjoint_tile<T, MUL, G0>), grid, dim3(kBlock), 0, stream, fu, g0, g1, m, hh, scale, \
+  const dim3 grid(unit_grid(ts.u));
+#define ODIL_LAUNCH_ADJ_TILE(MUL, G0)                                                                                 \
+  hipLaunchKernelGGL((k_poisson_adjoint_tile<T, MUL, G0>), grid, dim3(kBlock), 0, stream, fu, g0, g1, m, ts, hh, scale, \
                      ad0, ad1.x, ad1.m, ad1.v)
   if (mul && !g0) ODIL_LAUNCH_ADJ_TILE(true, false);
   else if (mul) ODIL_LAUNCH_ADJ_TILE(true, true);
@@ -1966,9 +2018,25 @@ int poisson_adjoint_transpose(const T* fu, T* g0, T* g1, const int64_t* fshape, 
 }
 
 template int poisson_adjoint_transpose<double>(const double*, double*, double*, const int64_t*, const double*, double,
-                                               const AdamArgs<double>&, const AdamArgs<double>&, int, int, hipStream_t);
+                                               const AdamArgs<double>&, const AdamArgs<double>&, int, int, hipStream_t,
+                                               const int*);
 template int poisson_adjoint_transpose<float>(const float*, float*, float*, const int64_t*, const float*, float,
-                                              const AdamArgs<float>&, const AdamArgs<float>&, int, int, hipStream_t);
+                                              const AdamArgs<float>&, const AdamArgs<float>&, int, int, hipStream_t,
+                                              const int*);
+
+// The plan a launch on the fine `fshape` takes by itself: kind 0, poisson_adjoint_transpose; kind 1, the transpose of
+// a 'ccc' array of doubles on k_interp_adj_tile (adj_launch; the target of its cut as there).
+static int tile_sched_rule(const int64_t* fshape, int kind, int* plan) {
+  const int64_t Z = fshape[0] / 2, cny = fshape[1] / 2, cnx = fshape[2] / 2;
+  const int64_t ytiles = (cny + kTileY - 1) / kTileY, xtiles = (cnx + kTileX - 1) / kTileX;
+  const bool small_level = Z * cny * cnx <= ((int64_t)1 << 22);
+  int L, S;
+  int64_t Zs;
+  tile_plan_rule(Z, ytiles, xtiles, kind == 0 ? 2 * kGridCap : (small_level ? ODIL_ADJ_UNITS_SMALL : ODIL_TILE_UNITS), L, Zs,
+                 S);
+  plan[0] = L, plan[1] = (int)Zs, plan[2] = S;
+  return 0;
+}
 
 template <typename T>
 int interp_add_march(const T* coarse, const T* add, T* fine, const InterpArgs& a, T cscale, T ascale,
@@ -1999,21 +2067,58 @@ template int interp_adj_march<float>(const float*, float*, float*, const InterpA
 using namespace odil;
 
 extern "C" {
+int odil_poisson_adjoint_transpose_adam_plan_f64(const double* fu, double* g0, double* g1, const int64_t* fshape,
+                                                 const double* h2, double scale, double* x0, double* m0, double* v0,
+                                                 double* x1, double* m1, double* v1, double alpha, double one_minus_b1,
+                                                 double one_minus_b2, double eps, const double* alpha_dev, int cut_lo,
+                                                 int cut_hi, int L, int Zs, int S, void* stream) {
+  const AdamArgs<double> a0{x0, m0, v0, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
+  const AdamArgs<double> a1{x1, m1, v1, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
+  const int plan[3] = {L, Zs, S};
+  return poisson_adjoint_transpose<double>(fu, g0, g1, fshape, h2, scale, a0, a1, cut_lo, cut_hi, (hipStream_t)stream,
+                                           L > 0 ? plan : nullptr);
+}
+int odil_poisson_adjoint_transpose_adam_plan_f32(const float* fu, float* g0, float* g1, const int64_t* fshape,
+                                                 const float* h2, float scale, float* x0, float* m0, float* v0, float* x1,
+                                                 float* m1, float* v1, float alpha, float one_minus_b1,
+                                                 float one_minus_b2, float eps, const float* alpha_dev, int cut_lo,
+                                                 int cut_hi, int L, int Zs, int S, void* stream) {
+  const AdamArgs<float> a0{x0, m0, v0, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
+  const AdamArgs<float> a1{x1, m1, v1, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
+  const int plan[3] = {L, Zs, S};
+  return poisson_adjoint_transpose<float>(fu, g0, g1, fshape, h2, scale, a0, a1, cut_lo, cut_hi, (hipStream_t)stream,
+                                          L > 0 ? plan : nullptr);
+}
 int odil_poisson_adjoint_transpose_adam_f64(const double* fu, double* g0, double* g1, const int64_t* fshape,
                                             const double* h2, double scale, double* x0, double* m0, double* v0,
                                             double* x1, double* m1, double* v1, double alpha, double one_minus_b1,
                                             double one_minus_b2, double eps, const double* alpha_dev, int cut_lo,
                                             int cut_hi, void* stream) {
-  const AdamArgs<double> a0{x0, m0, v0, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
-  const AdamArgs<double> a1{x1, m1, v1, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
-  return poisson_adjoint_transpose<double>(fu, g0, g1, fshape, h2, scale, a0, a1, cut_lo, cut_hi, (hipStream_t)stream);
+  return odil_poisson_adjoint_transpose_adam_plan_f64(fu, g0, g1, fshape, h2, scale, x0, m0, v0, x1, m1, v1, alpha,
+                                                      one_minus_b1, one_minus_b2, eps, alpha_dev, cut_lo, cut_hi, 0, 0, 0,
+                                                      stream);
 }
 int odil_poisson_adjoint_transpose_adam_f32(const float* fu, float* g0, float* g1, const int64_t* fshape,
                                             const float* h2, float scale, float* x0, float* m0, float* v0, float* x1,
                                             float* m1, float* v1, float alpha, float one_minus_b1, float one_minus_b2,
                                             float eps, const float* alpha_dev, int cut_lo, int cut_hi, void* stream) {
-  const AdamArgs<float> a0{x0, m0, v0, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
-  const AdamArgs<float> a1{x1, m1, v1, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev};
-  return poisson_adjoint_transpose<float>(fu, g0, g1, fshape, h2, scale, a0, a1, cut_lo, cut_hi, (hipStream_t)stream);
+  return odil_poisson_adjoint_transpose_adam_plan_f32(fu, g0, g1, fshape, h2, scale, x0, m0, v0, x1, m1, v1, alpha,
+                                                      one_minus_b1, one_minus_b2, eps, alpha_dev, cut_lo, cut_hi, 0, 0, 0,
+                                                      stream);
+}
+int odil_tile_sched_rule(const int64_t* fshape, int kind, int* plan) {
+  if (!fshape || !plan || fshape[0] < 4 || fshape[1] < 4 || fshape[2] < 4 || kind < 0 || kind > 1) return ODIL_E_INVAL;
+  return tile_sched_rule(fshape, kind, plan);
+}
+int64_t odil_tile_sched_units(int64_t Z, int64_t Y, int64_t XS, int L, int64_t Zs, int S, int32_t* units, int64_t capacity) {
+  if (Z < 1 || Y < 1 || XS < 1 || !tier_plan_ok(Z, L, Zs, S)) return -1;
+  const TierSched ts = make_tier_sched(Z, Y, XS, L, Zs, S);
+  const int64_t grid = unit_grid(ts.u);
+  for (int64_t b = 0; units && b < grid && b < capacity; ++b) {
+    int z0 = -1, z1 = -1, y = -1, xs = -1;
+    if (!tier_decode_at(ts, (int)b, z0, z1, y, xs)) z0 = z1 = y = xs = -1;
+    units[4 * b] = z0, units[4 * b + 1] = z1, units[4 * b + 2] = y, units[4 * b + 3] = xs;
+  }
+  return grid;
 }
 }

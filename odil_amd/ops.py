@@ -6,7 +6,7 @@ semantics follow the reference functions cited in include/odil_hip.h.
 """
 
 import math
-from ctypes import c_double, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_double, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -834,10 +834,12 @@ def adjoint_transpose_supported(shape):
 
 
 def poisson_adjoint_transpose(fu, h2, scale, g1, g0=None, adam0=None, adam1=None, alpha=0.0, one_minus_b1=0.0,
-                              one_minus_b2=0.0, eps=0.0, cut=(False, False)):
+                              one_minus_b2=0.0, eps=0.0, cut=(False, False), plan=None):
     """g0 = J^T (scale * fu) (stored only if `g0` is given), g1 = P^T g0, and the Adam steps of the finest level
     (adam0 = (x, m, v)) and of the next one (adam1) inside the same launch: g0 never goes through memory.
-    cut=(lo, hi): that end of axis 0 is a slab interface (ghost planes), not a wall."""
+    cut=(lo, hi): that end of axis 0 is a slab interface (ghost planes), not a wall.
+    plan=(L, Zs, S): the cut of the coarse z axis into units of work (include/odil_hip.h:
+    odil_poisson_adjoint_transpose_adam_plan; the same bits for every plan); None: the library's rule."""
     assert fu.dim() == 3 and tuple(g1.shape) == tuple(n // 2 for n in fu.shape) and fu.is_contiguous()
     h2a, h2p = host_reals(h2, fu.dtype)
     a, adev = _step_size(alpha, fu.dtype)
@@ -845,12 +847,45 @@ def poisson_adjoint_transpose(fu, h2, scale, g1, g0=None, adam0=None, adam1=None
     a1 = adam1 if adam1 is not None else (None, None, None)
     for t in list(a0) + list(a1):
         assert t is None or (t.is_contiguous() and t.dtype == fu.dtype)
+    if plan is not None:
+        L, Zs, S = (int(p) for p in plan)
+        if not 1 <= S <= L <= 64 or not 0 <= Zs <= g1.shape[0]:
+            raise ValueError("plan (L, Zs, S) = {} needs 1 <= S <= L <= 64 and 0 <= Zs <= {}".format(plan, g1.shape[0]))
+        call(
+            "poisson_adjoint_transpose_adam_plan", fu.dtype, ptr(fu), ptr(g0), ptr(g1), i64(fu.shape), h2p, float(scale),
+            ptr(a0[0]), ptr(a0[1]), ptr(a0[2]), ptr(a1[0]), ptr(a1[1]), ptr(a1[2]), a, float(one_minus_b1),
+            float(one_minus_b2), float(eps), adev, c_int(1 if cut[0] else 0), c_int(1 if cut[1] else 0), c_int(L),
+            c_int(Zs), c_int(S), stream_ptr(),
+        )
+        return g1
     call(
         "poisson_adjoint_transpose_adam", fu.dtype, ptr(fu), ptr(g0), ptr(g1), i64(fu.shape), h2p, float(scale),
         ptr(a0[0]), ptr(a0[1]), ptr(a0[2]), ptr(a1[0]), ptr(a1[1]), ptr(a1[2]), a, float(one_minus_b1),
         float(one_minus_b2), float(eps), adev, c_int(1 if cut[0] else 0), c_int(1 if cut[1] else 0), stream_ptr(),
     )
     return g1
+
+
+def adjoint_transpose_plan(shape, transpose_only=False):
+    """(L, Zs, S) that poisson_adjoint_transpose takes by itself on a fine array of `shape` (Zs == shape[0] // 2: one
+    tier of chunks of L planes); transpose_only: that of interp_adj(..., "ccc") on float64 where its LDS-tile kernel runs."""
+    out = (c_int * 3)()
+    if _lib.load().odil_tile_sched_rule(i64(shape), 1 if transpose_only else 0, out) != 0:
+        raise ValueError("adjoint_transpose_plan: shape {}".format(tuple(shape)))
+    return tuple(out)
+
+
+def tile_sched_units(Z, Y, XS, L, Zs, S):
+    """[(z0, z1, y, xs) or None per workgroup] of the two-tier schedule of the tile transposes, by the kernels' own decode
+    run on the host (include/odil_hip.h: odil_tile_sched_units)."""
+    lib = _lib.load()
+    grid = lib.odil_tile_sched_units(Z, Y, XS, L, Zs, S, None, 0)
+    if grid < 0:
+        raise ValueError("tile_sched_units: ({}, {}, {}) is not a plan for {} planes".format(L, Zs, S, Z))
+    buf = (c_int32 * (4 * grid))()
+    lib.odil_tile_sched_units(Z, Y, XS, L, Zs, S, buf, grid)
+    flat = list(buf)
+    return [None if flat[4 * b] < 0 else tuple(flat[4 * b:4 * b + 4]) for b in range(grid)]
 
 
 def poisson_jac_match(arrays, shape, h2):
