@@ -1,4 +1,7 @@
-"""ctypes binding of the C-ABI library `libodil_hip.so` (include/odil_hip.h).
+"""ctypes binding of the C-ABI library `libodil_hip.so`, derived from its header include/odil_hip.h.
+
+The header is the one text the binding follows: `declarations` parses its prototypes and `load` gives every exported
+function the return and argument types found there.  A new entry point needs nothing in this file.
 
 The library is the product's only compute path.  There is no CPU fallback: if the
 shared object is missing, or a call is made with tensors that are not on a HIP
@@ -7,124 +10,87 @@ device, the call raises.
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ODIL_HIP_LIB") or os.path.join(_HERE, "libodil_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "odil_hip.h")
 
-_P = c_void_p
-_I64P = ctypes.POINTER(c_int64)
+# The subset of C that the header is written in.  Pointers are spelled with one space around every `*` here, as
+# `declarations` normalises them.
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "size_t": c_size_t, "double": c_double,
+            "float": c_float}
+_RETURNS = {"int": c_int, "int64_t": c_int64, "size_t": c_size_t, "const char *": c_char_p}
+_PROTOTYPE = re.compile(r"(.+?) (odil_\w+) \( (.*?) ?\)")
+_PARAMETER = re.compile(r"(const )?(void|char|{})( \*( const \*)?)? (?!const$)[A-Za-z_]\w*".format("|".join(_SCALARS)))
 
-# name -> argument types with R standing for the real type (c_double / c_float).
-_R = "real"
-_SIGNATURES = {
-    "interp_add": [_P, _P, _P, _I64P, c_int, c_char_p, _R, _R, _P],
-    "interp_adj": [_P, _P, _P, _I64P, c_int, c_char_p, _R, _P],
-    "interp_add_ld": [_P, c_int64, _P, _P, _I64P, c_int, c_char_p, _R, _R, _P],
-    "interp_adj_ld": [_P, _P, c_int64, _I64P, c_int, c_char_p, _P],
-    "interp_adj_cut": [_P, _P, _P, _I64P, c_int, c_char_p, _R, c_int, c_int, _P],
-    "interp_adj_cut_adam": [_P, _P, _I64P, c_int, c_char_p, c_int, c_int, _P, _P, _P, _R, _R, _R, _R, _P, _P],
-    "restrict": [_P, _P, _I64P, c_int, c_char_p, _P],
-    "restrict_adj": [_P, _P, _I64P, c_int, c_char_p, _P],
-    "conv_valid": [_P, _P, _P, _I64P, _I64P, _I64P, _I64P, c_int, c_int, _P],
-    "mg_synth": [_P, _P, _P, _P, _I64P, c_int, c_int, c_char_p, _P],
-    "mg_synth_adj": [_P, _P, _P, _P, _I64P, c_int, c_int, c_char_p, _P],
-    "mg_synth_adj_adam": [_P, _P, _P, _P, _I64P, c_int, c_int, c_char_p, _P, _P, _P, _R, _R, _R, _R, _P, _P],
-    "field_gather": [_P, _P, _I64P, c_int, c_char_p, c_char_p, _I64P, _P],
-    "field_scatter": [_P, _P, _I64P, c_int, c_char_p, c_char_p, _I64P, c_int, _P],
-    "mean_reduce": [_P, c_int64, c_int, _P, _P, _P],
-    "poisson_residual": [_P, _P, _P, _I64P, c_int, _P, _P, _P, _P],
-    "poisson_small_epochs": [_P, _P, _P, _P, _P, _P, _P, _I64P, c_int, c_int, _P, _P, c_int, _R, _R, _R, _P, _P, _P, _P],
-    "poisson_small_epochs_batch": [_P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, _I64P, c_int, c_int, _P, _P, c_int64,
-                                   c_int, _R, _R, _R, _P, _P, c_int64, _P, c_int64, _P],
-    "poisson_residual_batch": [_P, _P, _P, c_int, c_int64, c_int64, c_int64, _I64P, c_int, _P, _P, c_int64, c_int64, _P, _P],
-    "poisson_adjoint_adam_batch": [_P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, _I64P, c_int, _P,
-                                   _R, _R, _R, _R, _P, c_int64, _P],
-    "mg_synth_adj_adam_batch": [_P, _P, _I64P, c_int, c_int, c_int, _P, _P, _P, _R, _R, _R, _P, c_int64, _P],
-    "poisson_residual_synth_batch": [_P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _I64P, c_int, _P, _P, c_int64,
-                                     c_int64, _P, c_size_t, _P, _P],
-    "poisson_adjoint_adam_volumes": [_P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, _I64P, c_int,
-                                     _P, _R, _R, _R, _R, _P, c_int64, _P],
-    "mg_synth_adj_adam_volumes": [_P, _P, _I64P, c_int, c_int, c_int, _P, _P, _P, _R, _R, _R, _P, c_int64, _P],
-    "poisson_jacobi": [_P, _P, _P, _I64P, c_int, _P, _R, _P],
-    "poisson_jacobi2": [_P, _P, _P, _I64P, c_int, _P, _R, _R, c_int, _P],
-    "poisson_jacobi2_synth": [_P, _P, _P, _P, _I64P, _P, _R, _R, c_int, _P],
-    "poisson_residual_restrict": [_P, _P, _P, _I64P, c_int, _P, _R, _P, _P, _P],
-    "poisson_residual_restrict_slab": [_P, _P, _P, _I64P, c_int, _P, _R, c_int64, c_int64, c_double, _P, _P, _P],
-    "poisson_residual_synth": [_P, _P, _P, _P, _I64P, _P, c_int64, c_int64, c_double, _P, _P, c_size_t, _P, _P],
-    "poisson_jacobi_synth": [_P, _P, _P, _P, _I64P, _P, _R, _P],
-    "poisson_residual_slab": [_P, _P, _P, _I64P, c_int, _P, c_int64, c_int64, c_double, _P, _P, _P],
-    "poisson_adjoint": [_P, _P, _I64P, c_int, _P, _R, _P],
-    "poisson_adjoint_adam": [_P, _P, _P, _P, _P, _I64P, c_int, _P, _R, _R, _R, _R, _R, _P, _P],
-    "poisson_adjoint_transpose_adam": [_P, _P, _P, _I64P, _P, _R, _P, _P, _P, _P, _P, _P, _R, _R, _R, _R, _P, c_int,
-                                       c_int, _P],
-    "poisson_adjoint_transpose_adam_plan": [_P, _P, _P, _I64P, _P, _R, _P, _P, _P, _P, _P, _P, _R, _R, _R, _R, _P, c_int,
-                                            c_int, c_int, c_int, c_int, _P],
-    "poisson_jac_coeffs": [_P, _I64P, c_int, _P, _P],
-    "poisson_jac_match": [_P, _I64P, c_int, _P, _P, _P, _P],
-    "adam_step": [_P, _P, _P, _P, c_int64, _R, _R, _R, _R, _P, _P],
-    "adam_step_pieces": [_P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _R, _R, _R, _R, _P, _P],
-    "planes_copy": [_P, _P, _P, c_int, c_int64, c_int, c_int, _P],
-    "axpy": [_P, _P, c_int64, _R, _P],
-    "scale": [_P, _P, c_int64, _R, _P, _P],
-    "addcmul": [_P, _P, _P, c_int64, c_int, _P],
-    "dots": [_P, c_int64, c_int, _P, c_int64, _P, _P, _P],
-    "dots3": [_P, c_int64, c_int, _P, _P, _P, c_int64, _P, _P, _P],
-    "lbfgs_probe": [_P, _P, c_int64, _P, _P, _P],
-    "lincomb": [_P, _R, _P, c_int64, c_int, _P, c_int64, _P],
-    "stencil_apply": [_P, _I64P, c_int, _P, _P, _I64P, c_int, c_int, _P],
-    "stencil_march": [_P, _I64P, c_int, c_int, _P, _P, _I64P, c_int, c_int, c_int, _P],
-    "stencil_var_smooth": [_P, _P, _P, _P, _I64P, c_int, _R, c_int, _P],
-    "stencil_var_smooth2": [_P, _P, _P, _P, _I64P, c_int, _R, _R, c_int, _P],
-    "stencil_var_residual_restrict": [_P, _P, _P, _P, _I64P, c_int, _R, _P, _P, _P],
-    "stencil_var_residual_restrict_slab": [_P, _P, _P, _P, _I64P, c_int, _R, c_int64, c_int64, c_double, _P, _P, _P],
-    "stencil_var_coarsen": [_P, _P, _I64P, c_int, _P],
-    "stencil_var_coarsen_axes": [_P, _P, _I64P, c_int, _P, _P],
-    "stencil_vcycle_tail": [_P, _I64P, _P, c_int, c_int, _P, _P, _P, _P, c_int64, _P, c_int, _P, c_int, _P, c_int, c_int, _P],
-    "stencil_solve_batch": [_P, c_int64, _I64P, _P, c_int, c_int, c_int, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P,
-                            c_int64, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, _R, _P, c_int64, _P, _P],
-    "max_abs_diff": [_P, _P, c_int64, _P, _P, _P],
-    "max_abs_rows": [_P, c_int, c_int64, _P, _P, _P],
-    "csr_assemble": [_P, _I64P, c_int, _I64P, c_int, c_int64, _P, _P, _P, _P],
-    "dense_block_xty": [_P, _P, c_int64, c_int, c_int, c_int64, c_int64, _P, _P, _P],
-    "dense_block_xty_wide": [_P, _P, c_int64, c_int, c_int, c_int64, c_int64, _P, _P, c_size_t, _P],
-    "dense_block_gram": [_P, c_int64, c_int, c_int64, _P, _P, _P],
-    "bmg_apply": [_P, _P, _I64P, _P, _P, _P, _P, c_int, _R, _P],
-    "bmg_assemble": [_P, _P, _P, _I64P, _I64P, _P, _P],
-    "bmg_transfer": [_I64P, _I64P, _P, _P, _P, _P, c_int, _P],
-    "bmg_galerkin": [_I64P, _I64P, _P, _P, _P, _P, c_int, c_int64, _P, _P],
-}
 
-# float64-only entry points (no _f32 twin): name -> argument types
-_SIGNATURES_F64 = {
-    "bmg_coarse_dense": [_P, _P, _I64P, c_int64, c_int64, _P, _P],
-    "bmg_coarse_chol": [_P, c_int64, c_int64, c_double, _P, _P, _P, _P],
-}
+def declarations(text):
+    """{name: (restype, [argtypes])} of every prototype in the text of a header like include/odil_hip.h, in its order.
+    Scalars map to the ctypes type of the same width, `const char*` to c_char_p, every other pointer to c_void_p (the C
+    type does not tell a host array from a device pointer).  Anything that is not a comment, a preprocessor line, the
+    `extern "C"` wrapper or a prototype of the header's subset of C raises ValueError: nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r'^[ \t]*(#.*|extern\s+"C"\s*\{|\})[ \t]*$', " ", text, flags=re.M)
+    *statements, rest = text.replace("*", " * ").replace("(", " ( ").replace(")", " ) ").split(";")
+    if rest.strip():
+        raise ValueError("C-ABI header: text after the last prototype: {!r}".format(rest.strip()))
+    found = dict()
+    for statement in statements:
+        statement = " ".join(statement.split())
+        match = _PROTOTYPE.fullmatch(statement)
+        if match is None or match.group(1) not in _RETURNS or match.group(2) in found:
+            raise ValueError("C-ABI header: not a prototype the binding understands: {!r}".format(statement))
+        parameters = [] if match.group(3) in ("", "void") else match.group(3).split(",")
+        argtypes = [_argtype(parameter.strip()) for parameter in parameters]
+        if None in argtypes:
+            raise ValueError("C-ABI header: parameter {!r} not understood in: {!r}".format(
+                parameters[argtypes.index(None)].strip(), statement))
+        found[match.group(2)] = (_RETURNS[match.group(1)], argtypes)
+    return found
 
-EXPORTED = [
-    "odil_last_error", "odil_version", "odil_device_count", "odil_reduce_workspace_bytes", "odil_dots_workspace_bytes",
-    "odil_dense_block_workspace_bytes", "odil_dense_block_wide_workspace_bytes", "odil_narrow_scale", "odil_widen_axpy",
-    "odil_poisson_small_epochs_resident", "odil_poisson_small_epochs_partials", "odil_poisson_batch_partials",
-    "odil_mg_batch_levels_ok", "odil_poisson_residual_synth_workspace_bytes",
-    "odil_mg_volumes_levels_ok", "odil_interp_adj_kind", "odil_poisson_residual_synth_batch_workspace_bytes",
-    "odil_poisson_residual_synth_batch_partials", "odil_stencil_solve_batch_work", "odil_tile_sched_rule",
-    "odil_tile_sched_units",
-] + [
-    "odil_{}_{}".format(name, suffix) for name in _SIGNATURES for suffix in ("f64", "f32")
-] + ["odil_{}_f64".format(name) for name in _SIGNATURES_F64]
+
+def _argtype(parameter):
+    """The ctypes type of `T name`, `[const] T * name` or `[const] T * const * name`; None for anything else."""
+    form = _PARAMETER.fullmatch(parameter)
+    const, base, pointer = form.group(1, 2, 3) if form else (None, None, None)
+    if pointer:
+        return c_char_p if (const, base, pointer) == ("const ", "char", " *") else c_void_p
+    return None if const else _SCALARS.get(base)
+
 
 _lib = None
+_declared = None  # declarations(the header), read once
 
 
 class OdilHipError(RuntimeError):
     pass
 
 
+def _header_declarations():
+    global _declared
+    if _declared is None:
+        if not os.path.exists(HEADER_PATH):
+            raise OdilHipError(
+                "C-ABI header {} is missing: the binding of libodil_hip.so is derived from it.".format(HEADER_PATH))
+        with open(HEADER_PATH) as f:
+            _declared = declarations(f.read())
+    return _declared
+
+
+def __getattr__(name):
+    if name == "EXPORTED":  # every entry point the header declares, hence the library exports
+        return list(_header_declarations())
+    raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))
+
+
 def load():
-    """Loads the shared library (once).  Raises if it has not been built."""
+    """Loads the shared library (once) and types its functions as the header declares them.  Raises if it has not been
+    built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -133,54 +99,11 @@ def load():
             "HIP extension not built: {} is missing. Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C odil_amd/csrc`. There is no CPU fallback.".format(LIB_PATH)
         )
+    declared = _header_declarations()
     lib = ctypes.CDLL(LIB_PATH)
-    lib.odil_last_error.restype = c_char_p
-    lib.odil_last_error.argtypes = []
-    lib.odil_version.restype = c_int
-    lib.odil_device_count.restype = c_int
-    lib.odil_reduce_workspace_bytes.restype = c_size_t
-    lib.odil_dots_workspace_bytes.restype = c_size_t
-    lib.odil_dots_workspace_bytes.argtypes = [c_int]
-    lib.odil_dense_block_workspace_bytes.restype = c_size_t
-    lib.odil_dense_block_wide_workspace_bytes.restype = c_size_t
-    lib.odil_dense_block_wide_workspace_bytes.argtypes = [c_int, c_int]
-    lib.odil_poisson_small_epochs_resident.restype = c_int
-    lib.odil_poisson_small_epochs_resident.argtypes = [_I64P, c_int, c_int, c_int]
-    lib.odil_poisson_small_epochs_partials.restype = c_int64
-    lib.odil_poisson_small_epochs_partials.argtypes = [_I64P, c_int, c_int]
-    lib.odil_poisson_batch_partials.restype = c_int64
-    lib.odil_poisson_batch_partials.argtypes = [_I64P, c_int, c_int]
-    lib.odil_mg_batch_levels_ok.restype = c_int
-    lib.odil_mg_batch_levels_ok.argtypes = [_I64P, c_int, c_int, c_int]
-    lib.odil_poisson_residual_synth_workspace_bytes.restype = c_size_t
-    lib.odil_poisson_residual_synth_workspace_bytes.argtypes = [_I64P]
-    lib.odil_interp_adj_kind.restype = c_int
-    lib.odil_interp_adj_kind.argtypes = [_I64P, c_int, c_char_p, c_int]
-    lib.odil_mg_volumes_levels_ok.restype = c_int
-    lib.odil_mg_volumes_levels_ok.argtypes = [_I64P, c_int, c_int, c_int, c_int]
-    lib.odil_poisson_residual_synth_batch_workspace_bytes.restype = c_size_t
-    lib.odil_poisson_residual_synth_batch_workspace_bytes.argtypes = [_I64P]
-    lib.odil_poisson_residual_synth_batch_partials.restype = c_int64
-    lib.odil_poisson_residual_synth_batch_partials.argtypes = [_I64P]
-    lib.odil_stencil_solve_batch_work.restype = c_int64
-    lib.odil_stencil_solve_batch_work.argtypes = [_I64P, c_int, c_int]
-    lib.odil_tile_sched_rule.restype = c_int
-    lib.odil_tile_sched_rule.argtypes = [_I64P, c_int, ctypes.POINTER(c_int)]
-    lib.odil_tile_sched_units.restype = c_int64
-    lib.odil_tile_sched_units.argtypes = [c_int64, c_int64, c_int64, c_int, c_int64, c_int, _P, c_int64]
-    for name in ("odil_narrow_scale", "odil_widen_axpy"):  # (mixed precision: no type suffix)
+    for name, (restype, argtypes) in declared.items():
         fn = getattr(lib, name)
-        fn.restype = c_int
-        fn.argtypes = [_P, _P, c_int64, c_double, _P, _P]
-    for name, sig in _SIGNATURES.items():
-        for suffix, real in (("f64", c_double), ("f32", c_float)):
-            fn = getattr(lib, "odil_{}_{}".format(name, suffix))
-            fn.restype = c_int
-            fn.argtypes = [real if a is _R else a for a in sig]
-    for name, sig in _SIGNATURES_F64.items():
-        fn = getattr(lib, "odil_{}_f64".format(name))
-        fn.restype = c_int
-        fn.argtypes = sig
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -29,6 +29,164 @@ def test_library_exports_every_declared_symbol():
     assert lib.odil_reduce_workspace_bytes() >= 4096 * 8
 
 
+SNIPPET = """
+/* A comment that names odil_fake(int x); declares nothing,
+ * over however many lines. */
+#ifdef __cplusplus
+extern "C" {
+#endif
+// nor does int odil_fake2(void); here
+const char* odil_text(void);
+int odil_none();
+#define ODIL_SOMETHING (-1) /* odil_fake3(int y); */
+size_t odil_three_lines(double* const* x, const float* const* y,
+                        const char* loc, char* buf, int32_t k,
+                        size_t n, float a, double b, void* stream);
+int64_t odil_count(const int64_t* shape, int *plan, int ndim, int64_t n);
+#ifdef __cplusplus
+}
+#endif
+"""
+
+
+def test_declarations_of_a_snippet():
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+
+    from odil_amd import _lib
+
+    found = _lib.declarations(SNIPPET)
+    assert list(found) == ["odil_text", "odil_none", "odil_three_lines", "odil_count"]
+    assert found == {
+        "odil_text": (c_char_p, []),
+        "odil_none": (c_int, []),
+        "odil_three_lines": (c_size_t, [c_void_p, c_void_p, c_char_p, c_void_p, c_int32, c_size_t, c_float, c_double,
+                                        c_void_p]),
+        "odil_count": (c_int64, [c_void_p, c_void_p, c_int, c_int64]),
+    }
+    assert _lib.declarations("") == {} and _lib.declarations("/* int odil_fake(void); */\n#define X 1\n") == {}
+
+
+@pytest.mark.parametrize("bad", [
+    "int odil_bad(struct foo x);",
+    "int odil_bad(const double* u, struct foo* x);",
+    "int odil_bad(int);",  # a parameter without a name
+    "int odil_bad(const int n);",
+    "int odil_bad(char c);",
+    "int odil_bad(void* const p);",
+    "int odil_bad(double** x);",
+    "int odil_bad(int (*f)(int));",
+    "int odil_bad(int n, ...);",
+    "void odil_bad(int n);",
+    "double odil_bad(void);",
+    "unsigned odil_bad(void);",
+    "int other_bad(int n);",
+    "struct odil_bad { int n; };",
+    "typedef int odil_bad;",
+    "int odil_bad(int n)",  # no semicolon
+    "int odil_bad(int n); int odil_bad(int n);",  # declared twice
+])
+def test_declarations_refuse_what_they_do_not_understand(bad):
+    """Nothing outside the header's subset of C is skipped: a declaration that is not understood must not become a
+    function without argument types."""
+    from odil_amd import _lib
+
+    with pytest.raises(ValueError, match="bad"):
+        _lib.declarations("int odil_good(int n);\n" + bad + "\n")
+
+
+def test_a_missing_header_is_reported_by_load(monkeypatch, tmp_path):
+    from odil_amd import _lib
+
+    missing = str(tmp_path / "include" / "odil_hip.h")
+    monkeypatch.setattr(_lib, "HEADER_PATH", missing)
+    monkeypatch.setattr(_lib, "_declared", None)
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(_lib.OdilHipError, match=re.escape(missing)):
+        _lib.load()
+
+
+def test_literal_signatures_of_six_entry_points():
+    """Written out from include/odil_hip.h by hand, not by the parser: the two longest argument lists and one entry point
+    of every other kind (host query, no parameters, no type suffix, float64 only)."""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+
+    from odil_amd import _lib
+
+    P, I, L = c_void_p, c_int, c_int64
+    expected = {
+        "odil_stencil_solve_batch_f32": (I, [P, L, P, P, I, I, I, P, L, P, L, P, L, L, P, L, I, P, I, P, I, I, I, I, c_float,
+                                             P, L, P, P]),
+        "odil_poisson_small_epochs_batch_f64": (I, [P, P, P, P, P, P, P, I, L, L, P, I, I, P, P, L, I, c_double, c_double,
+                                                    c_double, P, P, L, P, L, P]),
+        "odil_tile_sched_units": (L, [L, L, L, I, L, I, P, L]),
+        "odil_last_error": (c_char_p, []),
+        "odil_narrow_scale": (I, [P, P, L, c_double, P, P]),
+        "odil_bmg_coarse_chol_f64": (I, [P, L, L, c_double, P, P, P, P]),
+    }
+    assert len(expected["odil_stencil_solve_batch_f32"][1]) == 29
+    assert len(expected["odil_poisson_small_epochs_batch_f64"][1]) == 26
+    lib = _lib.load()
+    for name, (restype, argtypes) in expected.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == argtypes, name
+
+
+def test_every_exported_function_is_typed():
+    """Every entry point carries argument types (an empty list, not None, where it has no parameters) and the header's
+    return type; the return type and the number of parameters are read here by a regex of this test's own."""
+    from ctypes import c_char_p, c_int, c_int64, c_size_t
+
+    from odil_amd import _lib
+
+    lib = _lib.load()
+    text = open(os.path.join(ROOT, "include", "odil_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    returns = {"int": c_int, "int64_t": c_int64, "size_t": c_size_t, "const char*": c_char_p}
+    derived = _lib.declarations(open(os.path.join(ROOT, "include", "odil_hip.h")).read())
+    assert sorted(derived) == sorted(_lib.EXPORTED) and len(_lib.EXPORTED) >= 159
+    for name in _lib.EXPORTED:
+        fn = getattr(lib, name)
+        (returned, parameters), = re.findall(r"^((?:const )?\w+\*?) {}\(([^()]*)\);".format(name), text, flags=re.M)
+        count = 0 if parameters.strip() in ("", "void") else parameters.count(",") + 1
+        assert fn.argtypes is not None and len(fn.argtypes) == count, name
+        assert fn.restype is returns[returned], name
+        assert (fn.restype, list(fn.argtypes)) == derived[name], name
+
+
+# the parameters that are `double` in the _f64 AND the _f32 prototype: `denom` of the slab forms (a count of cells)
+DOUBLE_IN_BOTH = {
+    "odil_poisson_residual_slab": [8],
+    "odil_poisson_residual_restrict_slab": [9],
+    "odil_poisson_residual_synth": [8],
+    "odil_stencil_var_residual_restrict_slab": [9],
+}
+F64_ONLY = ["odil_bmg_coarse_dense", "odil_bmg_coarse_chol"]
+
+
+def test_f64_and_f32_twins_take_the_same_arguments():
+    """The header's own two copies of every typed entry point: equal once c_double and c_float are exchanged."""
+    from ctypes import c_double, c_float
+
+    from odil_amd import _lib
+
+    lib = _lib.load()
+    swap = {c_double: c_float, c_float: c_double}
+    bases = sorted({name[:-4] for name in _lib.EXPORTED if name.endswith(("_f64", "_f32"))})
+    assert len(bases) >= 70 and set(DOUBLE_IN_BOTH) <= set(bases) and set(F64_ONLY) <= set(bases)
+    for base in bases:
+        assert base + "_f64" in _lib.EXPORTED, base
+        if base in F64_ONLY:
+            assert base + "_f32" not in _lib.EXPORTED, base
+            continue
+        wide, narrow = getattr(lib, base + "_f64"), getattr(lib, base + "_f32")
+        assert wide.restype is narrow.restype, base
+        kept = DOUBLE_IN_BOTH.get(base, [])
+        assert [wide.argtypes[i] for i in kept] == [c_double] * len(kept), base
+        exchanged = [a if i in kept else swap.get(a, a) for i, a in enumerate(wide.argtypes)]
+        assert exchanged == list(narrow.argtypes), base
+
+
 def test_host_side_validation_reports_errors():
     from ctypes import c_int, c_void_p
 

@@ -33,8 +33,8 @@ def test_library_header_and_bindings_agree_on_the_new_entry_points():
         assert name in declared, name
     for name in _lib.EXPORTED:
         assert hasattr(lib, name) and name in declared, name
-    for name in ("poisson_residual_synth_batch", "poisson_adjoint_adam_volumes", "mg_synth_adj_adam_volumes"):
-        assert name in _lib._SIGNATURES, name
+    for name in [n + s for n in NEW for s in ("_f64", "_f32")]:
+        assert getattr(lib, name).argtypes, name
 
 
 def test_a_long_member_has_several_z_chunks_of_column_sums():

@@ -58,9 +58,8 @@ omb1, omb2, eps = float(1 - npdt(0.9)), float(1 - npdt(0.999)), 1e-7
 # the yardstick's single-problem entry point
 lib = ctypes.CDLL(opt.single_lib) if opt.single_lib else _lib.load()
 single = getattr(lib, "odil_poisson_small_epochs_" + opt.dtype)
-real = ctypes.c_double if opt.dtype == "f64" else ctypes.c_float
-single.restype = ctypes.c_int
-single.argtypes = [real if a is _lib._R else a for a in _lib._SIGNATURES["poisson_small_epochs"]]
+with open(_lib.HEADER_PATH) as f:
+    single.restype, single.argtypes = _lib.declarations(f.read())["odil_poisson_small_epochs_" + opt.dtype]
 h2a, h2p = _lib.host_reals(h2, dtype)
 shapes_c = _lib.i64(flat)
 workspace = ops.reduce_workspace(dev)
