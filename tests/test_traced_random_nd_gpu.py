@@ -29,44 +29,37 @@ def _np64(t):
     return t.detach().cpu().numpy().astype(np.float64) if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
 
 
-def _traced(problem, state, monkeypatch):
+def _traced(problem, state, monkeypatch, groups=1):
+    """The evaluator of the problem on its generated kernels: a `TracedOperator`, or (groups > 1: outputs on that many
+    grids) a `TracedGroups` of that many kernel sets."""
     monkeypatch.setattr(odil.runtime, "enable_trace", True)
     problem.recognise(state)
-    from odil_amd.stencil_jit import TracedOperator
+    from odil_amd.stencil_jit import TracedGroups, TracedOperator
 
-    assert isinstance(problem._traced, TracedOperator), "the case must run on its generated kernels"
+    assert isinstance(problem._traced, TracedOperator if groups == 1 else TracedGroups), "the case must run on its generated kernels"
+    assert groups == 1 or len(problem._traced.parts) == groups
     return problem._traced
 
 
-def check_loss_grad(case, monkeypatch, mode="chosen", **env):
-    """One case on the traced path, twice (equal bits: the reductions are ordered), against the reference.  Returns
-    (problem, state, reference)."""
+def check_loss_grad(case, monkeypatch, mode="chosen", label="traced-nd", **env):
+    """One case on the traced path, twice (equal bits: the reductions are ordered), against the reference: the four
+    measures of `traced_cases.measures` (the fields' arrays are all but the `Array`).  Returns (problem, state, reference)."""
     tol = TOL[case.dtype]
     with tc.environment(case, **env):
         problem, state, operator, rows = tc.build(case)
         ref = tc.reference(case, problem, state, rows)
-        _traced(problem, state, monkeypatch)
+        _traced(problem, state, monkeypatch, len(case.output_locs))
         loss, grads, terms, names, norms = problem.eval_loss_grad(state)
         grads = [g.clone() for g in grads]  # (views of a buffer the next call overwrites)
         loss2, grads2, terms2, _, norms2 = problem.eval_loss_grad(state)
-    rloss, rterms, rgrads, rvalues, rnames = ref
-    assert list(names) == list(rnames) and len(grads) == len(rgrads) and len(terms) == len(rterms)
+    assert list(names) == list(ref[4])
     assert np.array_equal(loss, loss2) and all(np.array_equal(a, b) for a, b in zip(list(terms) + list(norms), list(terms2) + list(norms2)))
     assert all(torch.equal(a, b) for a, b in zip(grads, grads2))
-    scale = max(float(np.max(np.abs(g))) for g in rgrads)
-    e_loss = abs(float(loss) - rloss) / abs(rloss)
-    e_term = max(abs(float(t) - r) / abs(r) for t, r in zip(terms, rterms))
-    errs = [float(np.max(np.abs(_np64(g).reshape(r.shape) - r))) for g, r in zip(grads, rgrads)]
-    e_grad = max(errs) / scale
-    # ... and the fields' arrays (all but the last, `coeff`) relative to THEIR largest entry: the gradient of a parameter is
-    # a sum over the grid, up to 1e4 times an entry of a field's gradient, and would hide an error of the gathers
-    fscale = max(float(np.max(np.abs(g))) for g in rgrads[:-1])
-    e_field = max(errs[:-1]) / fscale
-    print("traced-nd {} {}: loss {:.2e} terms {:.2e} gradients {:.2e} field gradients {:.2e}".format(
-        case.id, mode, e_loss, e_term, e_grad, e_field))
-    assert np.isfinite(rloss) and rloss > 0 and fscale > 0 and all(r > 0 for r in rterms)
+    (e_loss, e_term, e_grad, e_field), per_array = tc.measures(loss, terms, grads, ref)
+    print("{} {} {}: loss {:.2e} terms {:.2e} gradients {:.2e} field gradients {:.2e}".format(
+        label, case.id, mode, e_loss, e_term, e_grad, e_field))
     assert e_loss <= tol and e_term <= tol, (e_loss, e_term)
-    assert e_grad <= tol and e_field <= tol, ([e / scale for e in errs], [e / fscale for e in errs[:-1]])
+    assert e_grad <= tol and e_field <= tol, per_array
     return problem, state, ref
 
 
@@ -94,14 +87,13 @@ def test_recompute_modes_equal_the_float64_reference(cid, mode, monkeypatch):
 ALPHA, OMB1, OMB2, EPS = 0.5, 0.5, 0.25, 1e-7  # (large on purpose: an error of the gradient shows in x, m and v undamped)
 
 
-@pytest.mark.parametrize("cid", tc.ADAM_CASES)
-def test_adam_inside_the_gathers_equals_the_formula(cid, monkeypatch):
+def check_adam_inside_the_gathers(case, monkeypatch, label="traced-nd"):
     """`TracedOperator.eval_loss_grad_adam` with the update forced on small grids: from random m (of the gradient's size)
     and positive v, the arrays the gathers and the multigrid chain update equal m + (g - m) (1 - b1), v + (g^2 - v) (1 - b2),
     x - alpha m / (sqrt(v) + eps) (optimizer.py; reference optimizer.py:316-318) evaluated in float64 NumPy on the
     REFERENCE gradient, in the max norm relative to the largest entry of x, m and v respectively; the other arrays keep
-    their bits, and the number of updated arrays is what the layout of the state predicts (traced_cases.adam_prediction)."""
-    case = tc.BY_ID[cid]
+    their bits, and the number of updated arrays is what the layout of the state predicts (traced_cases.adam_prediction).
+    Returns that number."""
     tol = TOL[case.dtype]
     monkeypatch.setenv("ODIL_FUSE_ADAM_SMALL", "1")
     with tc.environment(case):
@@ -119,7 +111,7 @@ def test_adam_inside_the_gathers_equals_the_formula(cid, monkeypatch):
         res = tro.eval_loss_grad_adam(state, m, v, ALPHA, OMB1, OMB2, EPS)
         torch.cuda.synchronize()
     done, why = tc.adam_prediction(case, tro.cg)
-    print("traced-nd {} adam: {} leading arrays ({})".format(case.id, done, why))
+    print("{} {} adam: {} leading arrays ({})".format(label, case.id, done, why))
     if done == 0:
         assert res is None, why
     else:
@@ -139,5 +131,12 @@ def test_adam_inside_the_gathers_equals_the_formula(cid, monkeypatch):
         x1 = x0 - (m1 * ALPHA) / (np.sqrt(v1) + EPS)
         for name, got, want in (("x", x[k], x1), ("m", m[k], m1), ("v", v[k], v1)):
             worst[name] = max(worst[name], float(np.max(np.abs(_np64(got) - want))) / float(np.max(np.abs(want))))
-    print("traced-nd {} adam: x {x:.2e} m {m:.2e} v {v:.2e}".format(case.id, **worst))
+    print("{} {} adam: x {x:.2e} m {m:.2e} v {v:.2e}".format(label, case.id, **worst))
     assert max(worst.values()) <= tol, worst
+    return done
+
+
+@pytest.mark.parametrize("cid", tc.ADAM_CASES)
+def test_adam_inside_the_gathers_equals_the_formula(cid, monkeypatch):
+    """The six cases of the 1-D .. 3-D table (`check_adam_inside_the_gathers`)."""
+    check_adam_inside_the_gathers(tc.BY_ID[cid], monkeypatch)

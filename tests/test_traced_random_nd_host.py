@@ -55,12 +55,9 @@ def test_gradient_expressions_equal_the_float64_reference(cpu_mod, cid):
             assert np.max(np.abs(a - b)) <= 1e-11 * scale, (key, level, np.max(np.abs(a - b)) / scale, cg.out_mode)
 
 
-@pytest.mark.parametrize("cid", IDS)
-def test_folded_predicates_hold_away_from_the_exceptional_indices(cpu_mod, cid):
-    """Every kernel with a fold plan: each folded predicate has its fold constant, and each folded window test holds, at
-    every grid point none of whose indices is exceptional -- the points of the wavefronts that take the interior copy."""
-    case = tc.BY_ID[cid]
-    problem, state, operator, cg, kernels = census_of(case)
+def check_folded_predicates(problem, cg, kernels):
+    """Every kernel of one kernel set with a fold plan: each folded predicate has its fold constant, and each folded window
+    test holds, at every grid point none of whose indices is exceptional.  Returns the number of predicates checked."""
     G, checked = cg.G, 0
     ev = DagEval(cg.tr, G, dict(), problem.tracers)  # (index predicates read no array)
     for kernel in kernels:
@@ -81,7 +78,15 @@ def test_folded_predicates_hold_away_from_the_exceptional_indices(cpu_mod, cid):
             index = np.broadcast_to(np.arange(G[d]).reshape([-1 if e == d else 1 for e in range(len(G))]), G)
             assert np.all(index[away] < cg.out_lens[k][d]), (kernel["kernel"], k, d)
             checked += 1
-    assert checked
+    return checked
+
+
+@pytest.mark.parametrize("cid", IDS)
+def test_folded_predicates_hold_away_from_the_exceptional_indices(cpu_mod, cid):
+    """Every kernel with a fold plan: each folded predicate has its fold constant, and each folded window test holds, at
+    every grid point none of whose indices is exceptional -- the points of the wavefronts that take the interior copy."""
+    problem, state, operator, cg, kernels = census_of(tc.BY_ID[cid])
+    assert check_folded_predicates(problem, cg, kernels)
 
 
 @pytest.mark.parametrize("cid", IDS)

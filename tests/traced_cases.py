@@ -1,7 +1,10 @@
 """Random straight-line programs (tests/random_ops.py) on grids large enough for the FOLDED copy of the generated kernels
 to run (TEST INFRASTRUCTURE, no tests in here): the table of cases, the builder of one case, its float64 CPU reference
 (oracle/odil_generic.py) and a census of the wavefronts that take the interior copy of every generated kernel
-(stencil_codegen._interior_copy).  Shared by tests/test_traced_random_nd_host.py and tests/test_traced_random_nd_gpu.py.
+(stencil_codegen._interior_copy).  Shared by tests/test_traced_random_nd_host.py and tests/test_traced_random_nd_gpu.py
+(the table CASES: everything on the cell grid, 1-D .. 3-D) and by tests/test_traced_staggered_host.py and
+tests/test_traced_staggered_gpu.py (the table STAGGERED_CASES at the end: fields, reads and outputs at several locations,
+2-D .. 4-D).
 
 A wavefront of `k_fwd` or of a gather takes the folded copy only when none of its 64 x vw points has an exceptional index,
 so the copy runs only on grids with rows or planes longer than a wavefront: the shapes below are the smallest of that kind
@@ -27,14 +30,34 @@ _CHUNKED = (("ODIL_TRACE_CHUNK_MB", "0.05"),)  # (3, 64, 256): chunks of 16 rows
 
 
 class Case:
-    def __init__(self, seed, shape, dtype=F64, multigrid=False, env=()):
+    def __init__(self, seed, shape, dtype=F64, multigrid=False, env=(), locs=None, out_locs=None, mg_nlvl=None):
+        """locs: the locations of the fields "a" and "b", out_locs: the grids of the outputs (tests/random_ops.py; both None:
+        everything on the cell grid), mg_nlvl: the levels of the multigrid fields (default 2)."""
         self.seed, self.shape, self.dtype, self.multigrid, self.env = seed, tuple(shape), dtype, bool(multigrid), tuple(env)
-        assert not multigrid or all(n % 2 == 0 for n in shape), "two multigrid levels need even extents"
+        self.locs, self.out_locs = None if locs is None else tuple(locs), None if out_locs is None else tuple(out_locs)
+        self.mg_nlvl, self.levels = mg_nlvl, (mg_nlvl or 2) if multigrid else 1
+        assert (locs is None) == (out_locs is None) and (mg_nlvl is None or multigrid)
+        assert all(n % 2 ** (self.levels - 1) == 0 for n in shape), "every multigrid level halves the extents"
 
     @property
     def id(self):
-        return "s{}-{}-{}{}{}".format(self.seed, "x".join(map(str, self.shape)), "f32" if self.dtype == F32 else "f64",
-                                      "-mg" if self.multigrid else "", "-chunked" if self.env else "")
+        where = "" if self.locs is None else "-{}-{}".format(".".join(self.locs), "+".join(self.out_locs))
+        return "s{}-{}-{}{}{}{}".format(self.seed, "x".join(map(str, self.shape)), "f32" if self.dtype == F32 else "f64",
+                                        "-mg{}".format("" if self.levels == 2 else self.levels) if self.multigrid else "",
+                                        "-chunked" if self.env else "", where)
+
+    @property
+    def field_locs(self):
+        return self.locs or ("c" * self.ndim,) * 2
+
+    @property
+    def output_locs(self):
+        return self.out_locs or ("c" * self.ndim,)
+
+    @property
+    def converts(self):
+        """A read changes location: some field does not live on some output grid."""
+        return any(a != b for a in self.field_locs for b in self.output_locs)
 
     @property
     def ndim(self):
@@ -114,26 +137,28 @@ def environment(case, **more):
 
 
 def build(case, device=None, dtype=None):
-    """(problem, state, operator, rows): the program `random_operator(seed, params=True, ndim)` on two cell-centred fields
-    "a", "b" (multigrid fields of two levels when the case says so) and the `Array` "coeff", with random imposed rows of
-    shape `shape[1:]`.  Every number is drawn on the CPU in float64 (seeded by the case's seed), rounded to the case's dtype
-    and placed on `device` (default: the device of the current `mod`).  dtype=np.float64 on a float32 case: the float64
-    problem on the SAME float32-rounded numbers."""
+    """(problem, state, operator, rows): the program `random_operator(seed, params=True, ndim, out_locs, locs)` on two fields
+    "a", "b" at the case's locations (cell-centred by default; multigrid fields of the case's levels when it says so) and
+    the `Array` "coeff", with random imposed rows of the shape of the first output grid without axis 0.  Every number is
+    drawn on the CPU in float64 (seeded by the case's seed), rounded to the case's dtype and placed on `device` (default:
+    the device of the current `mod`).  dtype=np.float64 on a float32 case: the float64 problem on the SAME float32-rounded
+    numbers."""
     ndim, shape = case.ndim, case.shape
     dtype = dtype or case.dtype
-    domain = odil.Domain(cshape=shape, dimnames=("t", "x", "y")[:ndim], dtype=dtype, multigrid=case.multigrid,
-                         mg_nlvl=2 if case.multigrid else None)
+    domain = odil.Domain(cshape=shape, dimnames=("t", "x", "y", "z")[:ndim], dtype=dtype, multigrid=case.multigrid,
+                         mg_nlvl=case.levels if case.multigrid else None)
+    assert not case.multigrid or domain.mg_nlvl == case.levels, "the extents do not allow the levels the case asks for"
     device = device or domain.mod.device
-    state = odil.State(fields={"a": odil.Field(None, loc="c" * ndim), "b": odil.Field(None, loc="c" * ndim),
+    state = odil.State(fields={"a": odil.Field(None, loc=case.field_locs[0]), "b": odil.Field(None, loc=case.field_locs[1]),
                                "coeff": odil.Array([0.7, -0.4, 1.3])})
     state = domain.init_state(state)
     rounded = torch.float64 if case.dtype == F64 else torch.float32
     final = torch.float64 if dtype == F64 else torch.float32
     gen = torch.Generator(device="cpu").manual_seed(100 + case.seed)
     draw = lambda s: torch.randn(tuple(s), generator=gen, dtype=torch.float64).to(rounded).to(final).to(device)
-    rows = draw(shape[1:])
+    rows = draw(domain.get_field_shape(case.output_locs[0])[1:])
     domain.arrays_to_state([draw(a.shape) for a in domain.arrays_from_state(state)], state)
-    operator = random_operator(case.seed, params=True, ndim=ndim)
+    operator = random_operator(case.seed, params=True, ndim=ndim, out_locs=case.out_locs, locs=case.locs)
     return odil.Problem(operator, domain, extra=rows), state, operator, rows
 
 
@@ -144,18 +169,48 @@ def reference(case, problem, state, rows):
     """(loss, terms, grads in `arrays_from_state` order, output values, names) of the case in float64 on the CPU -- for a
     float32 case the float64 evaluation of the float32-rounded inputs.  Computed once per case, read-only."""
     if case.id not in _REFERENCE:
-        domain = problem.domain
-        geom = og.Geometry(domain.cshape, domain.dimnames, np.asarray(domain.lower, dtype=np.float64),
-                           np.asarray(domain.upper, dtype=np.float64), np.float64)
-        loss, grads, terms, names, values = og.eval_loss_grad(
-            problem.operator, geom, og.fields_of_state(domain, state), rows.detach().cpu().double(),
-            mg_axes=domain.mg_axes if case.multigrid else None)
-        grads = [np.asarray(g, dtype=np.float64) for g in grads]
-        values = [np.asarray(v, dtype=np.float64) for v in values]
-        for a in grads + values:
-            a.setflags(write=False)
-        _REFERENCE[case.id] = (loss, tuple(terms), tuple(grads), tuple(values), tuple(names))
+        _REFERENCE[case.id] = cpu_evaluation(case, problem, state, rows, np.float64)
     return _REFERENCE[case.id]
+
+
+def cpu_evaluation(case, problem, state, rows, dtype):
+    """(loss, terms, grads, values, names) of `oracle.odil_generic.eval_loss_grad` in `dtype` on the CPU, the results widened
+    to float64 and read-only.  dtype=np.float32 on a float32 case (geometry, fields and rows in float): the evaluation
+    whose distance from the float64 one says how much of the float32 bound rounding alone may use."""
+    domain = problem.domain
+    geom = og.Geometry(domain.cshape, domain.dimnames, np.asarray(domain.lower, dtype=dtype),
+                       np.asarray(domain.upper, dtype=dtype), dtype)
+    fields = og.fields_of_state(domain, state)
+    for f in fields.values():
+        for name in ("array", "terms"):
+            if name in f:
+                f[name] = [np.asarray(t, dtype=dtype) for t in f[name]] if name == "terms" else np.asarray(f[name], dtype=dtype)
+    extra = rows.detach().cpu().to(torch.float64 if dtype == np.float64 else torch.float32)
+    loss, grads, terms, names, values = og.eval_loss_grad(problem.operator, geom, fields, extra,
+                                                          mg_axes=domain.mg_axes if case.multigrid else None)
+    grads = [np.asarray(g, dtype=np.float64) for g in grads]
+    values = [np.asarray(v, dtype=np.float64) for v in values]
+    for a in grads + values:
+        a.setflags(write=False)
+    return (loss, tuple(terms), tuple(grads), tuple(values), tuple(names))
+
+
+def measures(loss, terms, grads, ref):
+    """(loss, terms, gradients, field gradients), plus the per-array figures: the loss and the worst term relative to the
+    reference value; every gradient array in the max norm relative to the largest entry of ALL reference gradients; and the
+    fields' arrays (all but the `Array` "coeff", the last) relative to the largest entry among themselves -- the gradient
+    of a parameter is a sum over the grid, up to 1e4 times an entry of a field's gradient, and would hide an error of
+    the gathers."""
+    rloss, rterms, rgrads = ref[:3]
+    to64 = lambda t: t.detach().cpu().numpy().astype(np.float64) if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
+    assert len(grads) == len(rgrads) and len(terms) == len(rterms)
+    scale = max(float(np.max(np.abs(g))) for g in rgrads)
+    fscale = max(float(np.max(np.abs(g))) for g in rgrads[:-1])
+    assert np.isfinite(rloss) and rloss > 0 and fscale > 0 and all(r > 0 for r in rterms)
+    errs = [float(np.max(np.abs(to64(g).reshape(r.shape) - r))) for g, r in zip(grads, rgrads)]
+    e_loss = abs(float(loss) - rloss) / abs(rloss)
+    e_term = max(abs(float(t) - r) / abs(r) for t, r in zip(terms, rterms))
+    return (e_loss, e_term, max(errs) / scale, max(errs[:-1]) / fscale), ([e / scale for e in errs], [e / fscale for e in errs[:-1]])
 
 
 def regular_arrays(problem, state):
@@ -230,11 +285,11 @@ def wave_census(cg, vw, exc):
     return int(ok.all(axis=1).sum()), waves
 
 
-def census(problem, state):
+def census(problem, state, only=None):
     """(cg, source, kernels): the generator after `source()` and, per generated kernel that may have an interior copy, a dict
     kernel, nodes, vw, reverse, plan, interior (wavefronts that take the folded copy), waves (all), remapped (chunk remap
-    in force), uniform (wave-uniform index prologue emitted)."""
-    tr, outs, raw, names, G = stencil_jit.trace_outputs(problem, state)
+    in force), uniform (wave-uniform index prologue emitted).  only: the positions of one shape group of the outputs."""
+    tr, outs, raw, names, G = stencil_jit.trace_outputs(problem, state, only)
     cg = _Codegen(tr, outs, raw, G, state)
     with interior_copies_recorded() as calls:
         source = cg.source()
@@ -249,6 +304,15 @@ def census(problem, state):
             c["waves"] = -(-(int(np.prod(cg.GL)) // c["vw"]) // 64)
         assert ("__all((int)(" in text) == (c["plan"] is not None), c["kernel"]
     return cg, source, calls
+
+
+def census_groups(problem, state):
+    """[(cg, source, kernels)], one per kernel set: an operator whose outputs live on grids of several shapes is traced
+    once per shape group, as `stencil_jit.TracedGroups` does."""
+    try:
+        return [census(problem, state)]
+    except stencil_jit.TraceGroups as e:
+        return [census(problem, state, only=positions) for positions in e.groups]
 
 
 def both_copies(kernel):
@@ -274,7 +338,7 @@ def adam_prediction(case, cg):
     for a plain `Field`, when no gather of the epoch re-reads the array the update would overwrite; the fields after the
     first that is not are left to the optimizer.  done == 0: the call returns None."""
     reread = {k for keys in cg.gather_reads_sources.values() for k in keys}
-    done, per = 0, 2 if case.multigrid else 1
+    done, per = 0, case.levels
     for key in ("a", "b"):
         if key not in cg.gathers:
             return done, "'{}' has no gather (its stored adjoint is its gradient)".format(key)
@@ -288,3 +352,77 @@ def adam_prediction(case, cg):
 # four points per thread, and one whose gathers re-read the field they would update (nothing fuses: the call returns None)
 ADAM_CASES = ["s61-1001-f32", "s70-1001-f64", "s80-40x64-f64-mg", "s97-20x150-f32-mg", "s76-10x16x64-f32", "s80-10x12x150-f64-mg"]
 assert all(i in BY_ID for i in ADAM_CASES)
+
+
+# ---- the staggered and four-dimensional table ------------------------------------------------------------------------------
+# Fields that do not live on the grid of the outputs (every read pads 'c' -> 'n' or trims 'n' -> 'c', the gathers are the
+# irregular ones), node-centred grids with odd extents, outputs on two grids (one kernel set each) and the (t, x, y, z)
+# layout of the tracer problem: four `nccc` arrays ARE its unknowns.  Seeds >= 100 (0 .. 99 belong to the tables above);
+# the shapes are the smallest per row for which the conditions of tests/test_traced_staggered_host.py hold (a wavefront of
+# `k_fwd` with no exceptional index beside one with), at most 50 000 points each; a case that cannot meet them is replaced HERE
+_MG3 = dict(multigrid=True, mg_nlvl=3)
+_CHUNKED_4D = (("ODIL_TRACE_CHUNK_MB", "0.05"),)  # (3, 16, 16, 64): chunks of axis 1
+STAGGERED_CASES = [
+    # G = 41 x 65, one point per thread, both fields padded along one axis each
+    Case(100, (40, 64), F64, locs=("nc", "cn"), out_locs=("nn",)),
+    Case(105, (40, 64), F64, locs=("nc", "cn"), out_locs=("nn",)),
+    Case(110, (40, 64), F32, locs=("nc", "cn"), out_locs=("nn",)),
+    # three multigrid levels with a node axis (13, 7, 4 rows), four points per thread, wave-uniform prologue
+    Case(105, (12, 256), F64, locs=("cc", "nc"), out_locs=("nc",), **_MG3),
+    Case(110, (12, 256), F32, locs=("cc", "nc"), out_locs=("nc",), **_MG3),
+    Case(116, (12, 256), F64, locs=("cc", "nc"), out_locs=("nc",), **_MG3),
+    # two kernel sets: each field is regular in one of them, padded or trimmed in the other
+    Case(105, (16, 64), F64, locs=("cc", "nc"), out_locs=("cc", "nc")),
+    Case(113, (16, 64), F32, locs=("cc", "nc"), out_locs=("cc", "nc")),
+    Case(105, (10, 16, 64), F64, locs=("ccc", "ncc"), out_locs=("ccc", "ncc")),
+    # three dimensions: trimmed reads along the first and the last axis
+    Case(100, (10, 16, 64), F64, locs=("ncc", "ccn"), out_locs=("ccc",)),
+    Case(105, (10, 16, 64), F32, locs=("ncc", "ccn"), out_locs=("ccc",)),
+    # ... padded and trimmed reads in one program, one point per thread
+    Case(100, (10, 12, 150), F64, locs=("ccc", "ncn"), out_locs=("ncc",)),
+    Case(105, (10, 12, 150), F32, locs=("ccc", "ncn"), out_locs=("ncc",)),
+    Case(109, (10, 12, 150), F64, locs=("ccc", "ncn"), out_locs=("ncc",)),
+    # the tracer's layout, G = 3 x 8 x 8 x 64: nothing converts, so rolls, imposed rows and windows stay in the programs
+    Case(150, (2, 8, 8, 64), F32, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    Case(105, (2, 8, 8, 64), F64, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    Case(123, (2, 8, 8, 64), F64, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    # four dimensions, a trimmed first axis: wave-uniform prologue / a last extent that is no multiple of 64
+    Case(100, (2, 4, 8, 256), F64, locs=("nccc", "cccc"), out_locs=("cccc",)),
+    Case(105, (2, 4, 8, 256), F32, locs=("nccc", "cccc"), out_locs=("cccc",)),
+    Case(100, (2, 4, 8, 152), F64, locs=("nccc", "ccnc"), out_locs=("cccc",)),
+    Case(110, (2, 4, 8, 152), F32, locs=("nccc", "ccnc"), out_locs=("cccc",)),
+    # multigrid `nccc` fields (two levels: 5 and 3 time levels): the transposes come after the merged gather
+    Case(102, (4, 8, 8, 64), F64, True, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    Case(105, (4, 8, 8, 64), F32, True, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    Case(123, (4, 8, 8, 64), F64, True, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    # the chunk remap with a fourth index
+    Case(100, (2, 16, 16, 64), F64, env=_CHUNKED_4D, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    Case(105, (2, 16, 16, 64), F32, env=_CHUNKED_4D, locs=("nccc", "nccc"), out_locs=("nccc",)),
+    # cell-centred fields, node-centred outputs: EVERY read converts
+    Case(105, (40, 64), F64, locs=("cc", "cc"), out_locs=("nn",)),
+    Case(113, (40, 64), F32, locs=("cc", "cc"), out_locs=("nn",)),
+]
+STAGGERED_BY_ID = {c.id: c for c in STAGGERED_CASES}
+assert len(STAGGERED_BY_ID) == len(STAGGERED_CASES) <= 28 and not set(STAGGERED_BY_ID) & set(BY_ID)
+assert all(c.seed >= 100 and int(np.prod(c.shape)) <= 50000 for c in STAGGERED_CASES)
+
+
+def conversions(cg, state):
+    """(a live read pads 'c' -> 'n', a live read trims 'n' -> 'c', the fields whose gather is the irregular one) of one
+    kernel set: what the staggered table is there to reach."""
+    pairs = [(f, l) for n in cg.tr.nodes if n.op == "read" and n.attr[0] in state.fields
+             for f, l in zip(state.fields[n.attr[0]].loc, n.attr[2])]
+    irregular = sorted(key for key in cg.gathers if tuple(cg._field_shape(key)) != tuple(cg.G))
+    return ("c", "n") in pairs, ("n", "c") in pairs, irregular
+
+
+# two cases per dimension that also run in the two other recompute modes
+STAGGERED_RECOMPUTE_CASES = [
+    "s105-40x64-f64-nc.cn-nn", "s105-16x64-f64-cc.nc-cc+nc",
+    "s100-10x16x64-f64-ncc.ccn-ccc", "s109-10x12x150-f64-ccc.ncn-ncc",
+    "s123-2x8x8x64-f64-nccc.nccc-nccc", "s100-2x4x8x152-f64-nccc.ccnc-cccc",
+]
+# Adam inside the gathers on the tracer's layout (every field regular): plain fields that no gather re-reads, and multigrid
+# fields whose merged gather runs both of its copies
+STAGGERED_ADAM_CASES = ["s150-2x8x8x64-f32-nccc.nccc-nccc", "s123-4x8x8x64-f64-mg-nccc.nccc-nccc"]
+assert all(i in STAGGERED_BY_ID for i in STAGGERED_RECOMPUTE_CASES + STAGGERED_ADAM_CASES)
