@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""A sweep over the conductivity of examples/diffusion/diffusion.py solved side by side: B members with the conductivity
+1 + a_b (k - 1), the amplitude a_b running from 1 / B to 1 over the members, every Newton step of all members in ONE
+solve launch, one workgroup per member (`odil.util.optimize_newton_ensemble`, its route for variable-coefficient
+stencils).  With `--beta > 0` the operator is nonlinear,  div(k grad u) - beta u^3 = f,  and the members' multigrid
+hierarchies are set up again every step.  The time per step is printed beside that of the same members as single
+`optimize_newton` runs, one after the other (`--single 0` skips those).
+
+    python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --kind smooth --epochs 2
+    python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --beta 1 --epochs 4
+"""
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import odil_amd as odil  # noqa: E402
+import diffusion  # noqa: E402
+from odil_amd import printlog  # noqa: E402
+
+
+def operator(ctx):
+    """div(k grad u) - beta u^3 - rhs on top of diffusion.flux_divergence (beta = 0: diffusion.operator)."""
+    mod, extra = ctx.mod, ctx.extra
+    dirs = range(ctx.domain.ndim)
+    st = [ctx.field("u")]
+    for i in dirs:
+        st.append(ctx.field("u", *[-1 if j == i else 0 for j in dirs]))
+        st.append(ctx.field("u", *[1 if j == i else 0 for j in dirs]))
+    fu = diffusion.flux_divergence(st, extra.kfaces, dirs, ctx.indices(), ctx.size(), ctx.step(), mod, extra.args.sigma)
+    if extra.beta:
+        fu = fu - extra.beta * (st[0] * st[0] * st[0])
+    return [fu - extra.rhs]
+
+
+def parse_args(argv=None):
+    own = argparse.ArgumentParser(add_help=False)
+    own.add_argument("--members", type=int, default=16, help="Problems in the ensemble")
+    own.add_argument("--beta", type=float, default=0.0, help="Strength of the nonlinear term: div(k grad u) - beta u^3 = f")
+    own.add_argument("--single", type=int, default=1, help="Also run the members as single optimize_newton runs and time them")
+    mine, rest = own.parse_known_args(argv)
+    args = diffusion.parse_args(["--ndim", "2", "--N", "16", "--epochs", "2"] + rest)
+    for key, value in vars(mine).items():
+        setattr(args, key, value)
+    return args
+
+
+def make_member(args, b):
+    """Member b: conductivity 1 + a_b (k - 1), a_b = (b + 1) / members; the right-hand side is the discrete operator of
+    that member on the reference solution, so every member has the same solution."""
+    problem, state = diffusion.make_problem(args)
+    domain, extra = problem.domain, problem.extra
+    mod = domain.mod
+    amp = (b + 1) / args.members
+    extra.kfaces = [tuple(1 + amp * (k - 1) for k in pair) for pair in extra.kfaces]
+    extra.beta = float(args.beta)
+    ndim = domain.ndim
+    st = [extra.ref_u]
+    for i in range(ndim):
+        st += [mod.roll(extra.ref_u, 1, i), mod.roll(extra.ref_u, -1, i)]
+    extra.rhs = diffusion.flux_divergence(st, extra.kfaces, range(ndim), domain.indices(), domain.size(), domain.step(), mod,
+                                          args.sigma)
+    if args.beta:
+        extra.rhs = extra.rhs - extra.beta * (extra.ref_u * extra.ref_u * extra.ref_u)
+    return odil.Problem(operator, domain, extra), state
+
+
+def make_members(args):
+    built = [make_member(args, b) for b in range(args.members)]
+    return [p for p, _ in built], [s for _, s in built]
+
+
+def synchronize():
+    import torch
+
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+
+
+def main():
+    args = parse_args()
+    odil.setup_outdir(args)
+    nsteps = max(args.epochs - args.epoch_start, 1)
+
+    def callback(member, state, epoch, pinfo):
+        if member == 0:
+            printlog("\nepoch={:05d}".format(epoch))
+        printlog("member {:3d}: loss {:.6e}".format(member, float(np.array(pinfo["loss"]))))
+
+    every = args.report_every or args.epochs
+    callback.next_active = lambda epoch: (epoch // every + 1) * every
+    problems, states = make_members(args)
+    guess = [problem.domain.arrays_from_state(state)[0].clone() for problem, state in zip(problems, states)]
+
+    def restart():
+        for problem, state, u in zip(problems, states, guess):
+            problem.domain.arrays_to_state([u.clone()], state)
+        synchronize()
+
+    arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback)
+    if args.single:  # (the same steps again, now that every member's operator is traced and its kernels are loaded)
+        restart()
+        start = time.perf_counter()
+        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states)
+        synchronize()
+        together = (time.perf_counter() - start) / nsteps
+    status = [optinfo.solver.status(b) for b in range(args.members)] if optinfo.solver is not None else []
+    printlog("\nroute '{}', last Newton step, per member:".format(optinfo.route))
+    for b, (problem, state, st) in enumerate(zip(problems, states, status)):
+        printlog("member {:3d}: {} cycles, relative residual {:.2e}{}, error u:{:.5g}".format(
+            b, st["niter"], st["residual"] / max(st["bnorm"], 1e-300), "" if st["converged"] else " (not converged)",
+            diffusion.error_rms(problem.domain, problem.extra, state, "u")))
+    lines = ["{} converged members of {}".format(sum(bool(st["converged"]) for st in status), args.members)]
+    if args.single:
+        lines.append("ensemble: {:.3f} ms per Newton step of all members".format(1e3 * together))
+        restart()
+        odil.util.optimize_newton(args, problems[0], states[0])  # (the kernels of the single route, loaded once)
+        restart()
+        start = time.perf_counter()
+        for problem, state in zip(problems, states):
+            odil.util.optimize_newton(args, problem, state)
+        synchronize()
+        alone = (time.perf_counter() - start) / nsteps
+        lines.append("single runs: {:.3f} ms per Newton step of all members, {:.1f} x the ensemble".format(
+            1e3 * alone, alone / together))
+    for line in lines:
+        printlog(line)
+        if not args.echo:  # (the log goes to train.log: the verdict also to the terminal)
+            print(line)
+
+
+if __name__ == "__main__":
+    main()

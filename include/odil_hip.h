@@ -456,6 +456,29 @@ int odil_stencil_var_coarsen_axes_f64(const double* coeffs, double* coarse, cons
                                       void* stream);
 int odil_stencil_var_coarsen_axes_f32(const float* coeffs, float* coarse, const int64_t* shape, int ndim, const int* halve,
                                       void* stream);
+/* The set-up of the hierarchies of an ENSEMBLE (gmg.EnsembleGMG.from_coeffs): `nbatch` (1..65535) operators of one shape,
+ * member b's 2 ndim + 1 coefficient arrays starting b * coeff_stride ELEMENTS after member 0's (coeff_stride >= one
+ * member), every entry point ONE launch whatever nbatch.  Malformed arguments are refused before any launch.  (No
+ * reference counterpart: the reference sets up one solver at a time, linsolver.py:61-72.)
+ *   coarsen_batch   the coarse operator of every member, written coarse_stride elements apart: per member bit-identical to
+ *                   odil_stencil_var_coarsen where halve is NULL or all ones, to odil_stencil_var_coarsen_axes otherwise
+ *                   (the same device code on the member's arrays)
+ *   strength_batch  out[b, k] = max |c| of member b's off-centre array 1 + k (k < 2 ndim): the values of odil_max_abs_rows
+ *                   on those arrays (a maximum is exact in any order; a NaN propagates), one workgroup per (member, array)
+ *   dense_batch     dense[b, r, j] = (A_b e_j)[r], the dense n x n matrix of member b's operator with periodic wrap, n =
+ *                   cells <= 512: entry by entry the value mode 1 of odil_stencil_var_smooth gives for the unit vectors */
+int odil_stencil_var_coarsen_batch_f64(const double* coeffs, int64_t coeff_stride, double* coarse, int64_t coarse_stride,
+                                       const int64_t* shape, int ndim, const int* halve, int nbatch, void* stream);
+int odil_stencil_var_coarsen_batch_f32(const float* coeffs, int64_t coeff_stride, float* coarse, int64_t coarse_stride,
+                                       const int64_t* shape, int ndim, const int* halve, int nbatch, void* stream);
+int odil_stencil_strength_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                    double* out, void* stream);
+int odil_stencil_strength_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                    float* out, void* stream);
+int odil_stencil_dense_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                 double* dense, void* stream);
+int odil_stencil_dense_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                 float* dense, void* stream);
 
 /* WHOLE EPOCHS of the multigrid Poisson problem (1-D or 2-D, all axes cell-centred) in ONE launch: one workgroup walks
  * synthesis, residual + loss, adjoint, transposed prolongations and the Adam update of every level -- the 17 dependent

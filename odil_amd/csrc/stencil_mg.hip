@@ -169,12 +169,11 @@ __global__ __launch_bounds__(kBlock) void k_svar_residual_restrict(const T* __re
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
-// one thread per coarse cell: the coarse coefficients (see the header of this file)
+// the coarse coefficients of coarse cell I (see the header of this file); c, cc: the arrays of ONE operator (the kernels
+// below hand in the single operator of a launch or one member of an ensemble)
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_svar_coarsen(const T* __restrict__ c, T* __restrict__ cc, SvarArgs a,
-                                                        SvarArgs ca) {
-  const int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (I >= ca.size) return;
+__device__ inline void svar_coarsen_cell(const T* __restrict__ c, T* __restrict__ cc, const SvarArgs& a, const SvarArgs& ca,
+                                         int64_t I) {
   int64_t cid[3];
   svar_decode(I, ca, cid);
   const int64_t stride[3] = {a.n[1] * a.n[2], a.n[2], 1};
@@ -261,6 +260,15 @@ __global__ __launch_bounds__(kBlock) void k_svar_coarsen(const T* __restrict__ c
   cc[I] = diag2 + diag10;
 }
 
+// one thread per coarse cell
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_svar_coarsen(const T* __restrict__ c, T* __restrict__ cc, SvarArgs a,
+                                                        SvarArgs ca) {
+  const int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (I >= ca.size) return;
+  svar_coarsen_cell<T>(c, cc, a, ca, I);
+}
+
 // SEMI-coarsening: only the axes with a.halve are merged (the strongly coupled axes of an anisotropic operator; the
 // others keep their cells until the couplings are of one size).  Same split of A; the factor 1/2 of the second-order part
 // belongs to the axes whose spacing doubles, so A2 is taken apart axis by axis: the couplings of axis d with their share
@@ -268,10 +276,8 @@ __global__ __launch_bounds__(kBlock) void k_svar_coarsen(const T* __restrict__ c
 // wall closure) goes with the incomplete axis -- 1/2 when one of those is merged.  With every axis merged this is
 // k_svar_coarsen (which stays the kernel of that case: bit-identical hierarchies for grids of cubes).
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_svar_coarsen_axes(const T* __restrict__ c, T* __restrict__ cc, SvarArgs a,
-                                                             SvarArgs ca) {
-  const int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (I >= ca.size) return;
+__device__ inline void svar_coarsen_axes_cell(const T* __restrict__ c, T* __restrict__ cc, const SvarArgs& a,
+                                              const SvarArgs& ca, int64_t I) {
   int64_t cid[3];
   svar_decode(I, ca, cid);
   const int64_t stride[3] = {a.n[1] * a.n[2], a.n[2], 1};
@@ -370,6 +376,88 @@ __global__ __launch_bounds__(kBlock) void k_svar_coarsen_axes(const T* __restric
     cc[(int64_t)(ca.slot[d] + 1) * ca.size + I] = sp + np;
   }
   cc[I] = diag2 + diag10;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_svar_coarsen_axes(const T* __restrict__ c, T* __restrict__ cc, SvarArgs a,
+                                                             SvarArgs ca) {
+  const int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (I >= ca.size) return;
+  svar_coarsen_axes_cell<T>(c, cc, a, ca, I);
+}
+
+// ENSEMBLES (gmg.EnsembleGMG.from_coeffs): the set-up of every member's hierarchy in launches that do not grow with the
+// number of members.  blockIdx.y = the member; its arrays start member * stride elements after the first member's.
+
+// the coarse operator of every member: the device bodies above on the member's arrays (AXES: some axes only)
+template <typename T, bool AXES>
+__global__ __launch_bounds__(kBlock) void k_svar_coarsen_batch(const T* __restrict__ c, int64_t cstride, T* __restrict__ cc,
+                                                              int64_t ccstride, SvarArgs a, SvarArgs ca) {
+  const int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (I >= ca.size) return;
+  const T* cm = c + (int64_t)blockIdx.y * cstride;
+  T* ccm = cc + (int64_t)blockIdx.y * ccstride;
+  if (AXES)
+    svar_coarsen_axes_cell<T>(cm, ccm, a, ca, I);
+  else
+    svar_coarsen_cell<T>(cm, ccm, a, ca, I);
+}
+
+// max |c| of every off-centre coefficient array of every member: one workgroup per (array, member), strided maxima and a
+// fixed-order tree (k_max_abs_rows without its second launch; a maximum does not depend on the order, a NaN stays)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_svar_strength_batch(const T* __restrict__ c, int64_t cstride, int64_t size,
+                                                               T* __restrict__ out) {
+  const T* row = c + (int64_t)blockIdx.y * cstride + (int64_t)(1 + blockIdx.x) * size;
+  double m = 0.0;
+  for (int64_t i = threadIdx.x; i < size; i += kBlock) {
+    const double v = fabs((double)row[i]);
+    m = v > m || v != v ? v : m;
+  }
+  __shared__ double sm[kBlock];
+  sm[threadIdx.x] = m;
+  __syncthreads();
+  for (int off = kBlock / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) {
+      const double o = sm[threadIdx.x + off];
+      if (o > sm[threadIdx.x] || o != o) sm[threadIdx.x] = o;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = (T)sm[0];
+}
+
+// the dense matrix of every member's operator, one thread per entry (row r, column j) = (A e_j)[r]: the sum of svar_apply
+// over the unit vector e_j, term by term in its order, then -(0 - .) as gmg.StencilGMG.coarse_column forms it from the
+// residual kernel.  (At most two terms are not zero -- -e_a and +e_a on an axis of extent 2 -- so the order is immaterial.)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_svar_dense_batch(const T* __restrict__ c, int64_t cstride, SvarArgs a,
+                                                            T* __restrict__ dense) {
+  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= a.size * a.size) return;
+  const int64_t i = e / a.size, j = e - i * a.size;
+  const T* cm = c + (int64_t)blockIdx.y * cstride;
+  int64_t id[3];
+  svar_decode(i, a, id);
+  const int64_t stride[3] = {a.n[1] * a.n[2], a.n[2], 1};
+  const int first = a.has[0] ? 0 : (a.has[1] ? 1 : 2);
+  T acc = cm[i] * T(i == j ? 1 : 0);
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    if (!a.has[d]) continue;
+    const int64_t n = a.n[d];
+    const int64_t im = id[d] == 0 ? i + (n - 1) * stride[d] : i - stride[d];
+    const int64_t ip = id[d] == n - 1 ? i - (n - 1) * stride[d] : i + stride[d];
+    acc = acc + cm[(int64_t)a.slot[d] * a.size + i] * T(im == j ? 1 : 0);
+    if (d != first) acc = acc + cm[(int64_t)(a.slot[d] + 1) * a.size + i] * T(ip == j ? 1 : 0);
+  }
+  {
+    const int d = first;
+    const int64_t n = a.n[d];
+    const int64_t ip = id[d] == n - 1 ? i - (n - 1) * stride[d] : i + stride[d];
+    acc = acc + cm[(int64_t)(a.slot[d] + 1) * a.size + i] * T(ip == j ? 1 : 0);
+  }
+  dense[(int64_t)blockIdx.y * a.size * a.size + e] = -(T(0) - acc);
 }
 
 // max |a - b| and max |b| over n entries (recognition of a known operator from its coefficient arrays: one pass over
@@ -601,6 +689,100 @@ static int svar_coarsen(const T* coeffs, T* coarse, const int64_t* shape, int nd
   return check_launch("k_svar_coarsen");
 }
 
+// what the ensemble launchers share: the members (the grid's y extent) and the finest arrays of one of them
+static int svar_batch_fill(SvarArgs& a, const int64_t* shape, int ndim, int nbatch, int64_t coeff_stride, const char* what) {
+  if (!shape) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (int e = svar_fill(a, shape, ndim, what)) return e;
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1..65535: the member is a grid dimension)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (a.size > (int64_t)1 << 24) {
+    set_error("%s: too many cells per member", what);
+    return ODIL_E_INVAL;
+  }
+  if (coeff_stride < (2 * ndim + 1) * a.size) {
+    set_error("%s: coeff_stride %lld is smaller than a member (%lld)", what, (long long)coeff_stride,
+              (long long)((2 * ndim + 1) * a.size));
+    return ODIL_E_INVAL;
+  }
+  return 0;
+}
+
+template <typename T>
+static int svar_coarsen_batch(const T* coeffs, int64_t coeff_stride, T* coarse, int64_t coarse_stride, const int64_t* shape,
+                              int ndim, const int* halve, int nbatch, void* stream) {
+  const char* what = "stencil_var_coarsen_batch";
+  SvarArgs a, ca;
+  if (int e = svar_batch_fill(a, shape, ndim, nbatch, coeff_stride, what)) return e;
+  bool all = true, any = false;
+  if (halve)
+    for (int i = 0; i < ndim; ++i) {
+      a.halve[i + 3 - ndim] = halve[i] != 0;
+      all = all && halve[i] != 0;
+      any = any || halve[i] != 0;
+    }
+  if (halve && !any) {
+    set_error("%s: no axis to merge", what);
+    return ODIL_E_INVAL;
+  }
+  if (int e = svar_coarse(a, ca, what)) return e;
+  if (coarse_stride < (2 * ndim + 1) * ca.size) {
+    set_error("%s: coarse_stride %lld is smaller than a member (%lld)", what, (long long)coarse_stride,
+              (long long)((2 * ndim + 1) * ca.size));
+    return ODIL_E_INVAL;
+  }
+  if (!coeffs || !coarse) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  const dim3 grid((unsigned)((ca.size + kBlock - 1) / kBlock), (unsigned)nbatch);
+  if (all)
+    hipLaunchKernelGGL((k_svar_coarsen_batch<T, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, coeffs, coeff_stride,
+                       coarse, coarse_stride, a, ca);
+  else
+    hipLaunchKernelGGL((k_svar_coarsen_batch<T, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, coeffs, coeff_stride,
+                       coarse, coarse_stride, a, ca);
+  return check_launch("k_svar_coarsen_batch");
+}
+
+template <typename T>
+static int svar_strength_batch(const T* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch, T* out,
+                               void* stream) {
+  const char* what = "stencil_strength_batch";
+  SvarArgs a;
+  if (int e = svar_batch_fill(a, shape, ndim, nbatch, coeff_stride, what)) return e;
+  if (!coeffs || !out) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  hipLaunchKernelGGL((k_svar_strength_batch<T>), dim3((unsigned)(2 * ndim), (unsigned)nbatch), dim3(kBlock), 0,
+                     (hipStream_t)stream, coeffs, coeff_stride, a.size, out);
+  return check_launch("k_svar_strength_batch");
+}
+
+template <typename T>
+static int svar_dense_batch(const T* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch, T* dense,
+                            void* stream) {
+  const char* what = "stencil_dense_batch";
+  SvarArgs a;
+  if (int e = svar_batch_fill(a, shape, ndim, nbatch, coeff_stride, what)) return e;
+  if (a.size > 512) {
+    set_error("%s: %lld unknowns per member (at most 512: a dense matrix)", what, (long long)a.size);
+    return ODIL_E_INVAL;
+  }
+  if (!coeffs || !dense) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  const dim3 grid((unsigned)((a.size * a.size + kBlock - 1) / kBlock), (unsigned)nbatch);
+  hipLaunchKernelGGL((k_svar_dense_batch<T>), grid, dim3(kBlock), 0, (hipStream_t)stream, coeffs, coeff_stride, a, dense);
+  return check_launch("k_svar_dense_batch");
+}
+
 }  // namespace odil
 
 using namespace odil;
@@ -659,5 +841,29 @@ int odil_stencil_var_coarsen_axes_f64(const double* coeffs, double* coarse, cons
 int odil_stencil_var_coarsen_axes_f32(const float* coeffs, float* coarse, const int64_t* shape, int ndim, const int* halve,
                                       void* stream) {
   return svar_coarsen<float>(coeffs, coarse, shape, ndim, halve, stream);
+}
+int odil_stencil_var_coarsen_batch_f64(const double* coeffs, int64_t coeff_stride, double* coarse, int64_t coarse_stride,
+                                       const int64_t* shape, int ndim, const int* halve, int nbatch, void* stream) {
+  return svar_coarsen_batch<double>(coeffs, coeff_stride, coarse, coarse_stride, shape, ndim, halve, nbatch, stream);
+}
+int odil_stencil_var_coarsen_batch_f32(const float* coeffs, int64_t coeff_stride, float* coarse, int64_t coarse_stride,
+                                       const int64_t* shape, int ndim, const int* halve, int nbatch, void* stream) {
+  return svar_coarsen_batch<float>(coeffs, coeff_stride, coarse, coarse_stride, shape, ndim, halve, nbatch, stream);
+}
+int odil_stencil_strength_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                    double* out, void* stream) {
+  return svar_strength_batch<double>(coeffs, coeff_stride, shape, ndim, nbatch, out, stream);
+}
+int odil_stencil_strength_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                    float* out, void* stream) {
+  return svar_strength_batch<float>(coeffs, coeff_stride, shape, ndim, nbatch, out, stream);
+}
+int odil_stencil_dense_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                 double* dense, void* stream) {
+  return svar_dense_batch<double>(coeffs, coeff_stride, shape, ndim, nbatch, dense, stream);
+}
+int odil_stencil_dense_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
+                                 float* dense, void* stream) {
+  return svar_dense_batch<float>(coeffs, coeff_stride, shape, ndim, nbatch, dense, stream);
 }
 }

@@ -535,6 +535,34 @@ def newton_refusal(cshape, h2, dtype):
     return None
 
 
+def newton_stencil_refusal(cshape, dtype):
+    """Why a single-field (2 d + 1)-point operator on these cells is not a member of a Newton ensemble of
+    variable-coefficient problems (gmg.EnsembleGMG.from_coeffs), or None -- as far as the shape alone tells: 1-D to 3-D,
+    extents >= 4 (the limit of `gmg.recognise_stencil`), at most `EnsembleGMG.max_cells` cells, and a coarsest level that
+    CAN come below `EnsembleGMG.max_coarsest` unknowns (every axis halved while it is even).  How many levels the
+    coefficients ask for, and the coarsest level they stop at, `from_coeffs` reports.  Host arithmetic only."""
+    from .gmg import EnsembleGMG
+
+    cshape = tuple(int(n) for n in cshape)
+    ndim = len(cshape)
+    if not 1 <= ndim <= 3:
+        return "{}-D grid: the one-workgroup Newton solves run 1-D to 3-D grids".format(ndim)
+    if dtype not in (torch.float64, torch.float32):
+        return "dtype {}: the kernels run float64 and float32".format(dtype)
+    if any(n < 4 for n in cshape):
+        return "extents {}: a stencil operator is recognised on 4 cells per axis or more".format(cshape)
+    cells = math.prod(cshape)
+    if cells > EnsembleGMG.max_cells:
+        return "{} cells are above the limit of the one-workgroup Newton solves ({})".format(cells, EnsembleGMG.max_cells)
+    least = list(cshape)
+    for _ in range(EnsembleGMG.max_levels - 1):
+        least = [n // 2 if n % 2 == 0 and n // 2 >= 2 else n for n in least]
+    if math.prod(least) > EnsembleGMG.max_coarsest:
+        return "the coarsest level {} has {} unknowns, above the {} of the dense coarsest solve".format(
+            tuple(least), math.prod(least), EnsembleGMG.max_coarsest)
+    return None
+
+
 def _close(a, b, rtol):
     scale = max(float(b.abs().max()), 1e-300)
     return float((a - b).abs().max()) <= rtol * scale

@@ -666,7 +666,9 @@ class EnsembleGMG:
     levels, spacings, `poisson_jac_coeffs` and the coarsest inverse are those of the `PoissonGMG` hierarchy (min_size stops
     the coarsening earlier; by default where at most `max_levels` levels remain).
     EnsembleGMG([hierarchy, ...]): one hierarchy per member (`StencilGMG` objects of one shape, or anything with `shapes`,
-    `locs`, `tail_coeffs`, `coarse_inverse`, `weights`, `nu1`, `nu2`): their operators and inverses are packed per member."""
+    `locs`, `tail_coeffs`, `coarse_inverse`, `weights`, `nu1`, `nu2`): their operators and inverses are packed per member.
+    EnsembleGMG.from_coeffs(coeffs [B, 2 d + 1, *shape]): the same per-member hierarchies, set up for all members at once
+    in launches that do not grow with B; `rebuild` repeats the set-up in place (every Newton step of a nonlinear operator)."""
 
     max_cells = 32768    # cells of a member's finest level (32^3, 128^2, 1-D up to 32768)
     max_levels = 8       # kTailMaxLev of csrc/vcycle_tail.hip
@@ -721,6 +723,128 @@ class EnsembleGMG:
         self._out = dict()      # maxcycles -> (history, outcome) device tensors
         self.history = None     # [B, maxcycles + 2], [B, 2] of the last launch on the host
         self.outcome = None
+
+    @classmethod
+    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2):
+        """One variable-coefficient operator per member, coeffs [B, 2 d + 1, *shape]: level by level what
+        `StencilGMG(coeffs[b])` builds for every member -- coefficient arrays and coarsest pseudo-inverse bit for bit -- in
+        launches whose number does not depend on B: per level ONE strength launch and one read-back of [B, 2 d] (the
+        semi-coarsening decision of `StencilGMG.__init__`; none in 1-D), per transition ONE coarsen launch, then ONE launch
+        for the dense coarsest matrices and one read-back; the pseudo-inverses are `StencilGMG.invert` per member on the
+        host in float64.  The kernel walks one set of shapes: every member must take member 0's decision on every level,
+        else ValueError (no object is made).  Coarsening stops under StencilGMG's rule or at `max_levels` levels."""
+        self = cls.__new__(cls)
+        nb, ndim = int(coeffs.shape[0]), coeffs.dim() - 2
+        if nb < 1 or not 1 <= ndim <= 3 or coeffs.shape[1] != 2 * ndim + 1:
+            raise ValueError("EnsembleGMG.from_coeffs: coefficients {} are not [B, 2 d + 1, *shape] with d <= 3".format(
+                tuple(coeffs.shape)))
+        shape = tuple(int(n) for n in coeffs.shape[2:])
+        if math.prod(shape) > cls.max_cells:
+            raise ValueError("EnsembleGMG.from_coeffs: {} cells are above the limit of the one-workgroup solves ({})".format(
+                math.prod(shape), cls.max_cells))
+        self.nbatch, self.dtype, self.device, self.ndim = nb, coeffs.dtype, coeffs.device, ndim
+        self.nu1 = PoissonGMG.nu_default[0] if nu1 is None else nu1
+        self.nu2 = PoissonGMG.nu_default[1] if nu2 is None else nu2
+        self.min_size, self.base = min_size, None
+        self.method = "gmg-vcycle (variable coefficients), one workgroup per member"
+        self.wpre, self.wpost = jacobi_weights(ndim, self.nu1), jacobi_weights(ndim, self.nu2)
+        self.cells = math.prod(shape)
+        self._strength = torch.empty((nb, 2 * ndim), dtype=self.dtype, device=self.device)
+        self._out, self.history, self.outcome = dict(), None, None
+        self._shape0 = shape
+        self._plan(coeffs.reshape(nb, -1))
+        return self
+
+    def _decide(self, level, lvl, shape):
+        """The `halve` of `StencilGMG.__init__` for the level `level` [B, (2 d + 1) cells] of every member (one launch, one
+        read-back), or None where its coarsening stops; ValueError when a member decides otherwise than member 0."""
+        if len(shape) == 1:
+            halve = [True]
+        else:
+            size = ops.stencil_strength_batch(level, shape, out=self._strength).cpu().numpy().astype(np.float64)
+            strength = np.minimum(size[:, 0::2], size[:, 1::2])
+            every = strength >= 0.5 * strength.max(axis=1, keepdims=True)
+            blocked = np.array([not (n % 2 == 0 and n // 2 >= self.min_size) for n in shape])
+            if (every & blocked).any(axis=1).all():
+                return None  # (every member's coarsening stops here, whichever axes it would merge)
+            differ = np.nonzero((every != every[0]).any(axis=1))[0]
+            if len(differ):
+                b = int(differ[0])
+                raise ValueError("EnsembleGMG: member {} merges the axes {} on level {}, member 0 the axes {}: the members of an "
+                                 "ensemble walk one set of levels".format(b, [bool(v) for v in every[b]], lvl,
+                                                                          [bool(v) for v in every[0]]))
+            halve = [bool(v) for v in every[0]]
+            if not any(halve):
+                raise ValueError("EnsembleGMG: the couplings of level {} are not finite".format(lvl))
+        if not all(n % 2 == 0 and n // 2 >= self.min_size for n, on in zip(shape, halve) if on):
+            return None
+        return halve
+
+    def _plan(self, fine):
+        """Builds shapes, the packed hierarchy [B, ncoeff], the inverses, the work array and the launch plan from the finest
+        coefficients [B, (2 d + 1) cells]; the object is changed only once everything stands."""
+        shapes, halves, levels = [self._shape0], [], [fine]
+        while len(shapes) < self.max_levels:
+            halve = self._decide(levels[-1], len(shapes) - 1, shapes[-1])
+            if halve is None:
+                break
+            levels.append(ops.stencil_var_coarsen_batch(levels[-1], shapes[-1], halve))
+            shapes.append(tuple(n // 2 if on else n for n, on in zip(shapes[-1], halve)))
+            halves.append(halve)
+        ninv = math.prod(shapes[-1])
+        need = ops.stencil_solve_batch_work(shapes)
+        if not need or ninv > self.max_coarsest:
+            raise ValueError("EnsembleGMG: levels {} are not walked by one workgroup (at most {} levels, a coarsest level "
+                             "of at most {} unknowns)".format(shapes, self.max_levels, self.max_coarsest))
+        coeffs = torch.cat(levels, dim=1).contiguous()
+        dense = torch.empty((self.nbatch, ninv, ninv), dtype=self.dtype, device=self.device)
+        inv = torch.empty_like(dense)
+        self._invert(levels[-1], shapes[-1], dense, inv)
+        self.shapes, self.halve = shapes, halves
+        self.locs = ["".join("c" if on else "." for on in halve) for halve in halves]
+        self.coeffs, self.inv, self._dense = coeffs, inv, dense
+        sizes = [(2 * self.ndim + 1) * math.prod(s) for s in shapes]
+        self._offsets = [sum(sizes[:l]) for l in range(len(sizes) + 1)]
+        self.work = torch.empty((self.nbatch, need), dtype=self.dtype, device=self.device)
+        self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
+                                                    self.wpre, self.wpost)
+
+    def _invert(self, coarsest, shape, dense, inv):
+        """inv[b] = StencilGMG.invert(the dense matrix of member b's coarsest operator): one launch, one read-back, the
+        pseudo-inverses on the host in float64, one copy back."""
+        amat = ops.stencil_dense_batch(coarsest, shape, out=dense).cpu().numpy().astype(np.float64)
+        host = np.stack([StencilGMG.invert(amat[b]) for b in range(self.nbatch)])
+        inv.copy_(torch.as_tensor(host, dtype=self.dtype))
+
+    def level(self, lvl):
+        """[B, (2 d + 1) cells of level lvl]: the coefficient arrays of every member on that level (a view)."""
+        return self.coeffs[:, self._offsets[lvl]:self._offsets[lvl + 1]]
+
+    @property
+    def fine(self):
+        """[B, 2 d + 1, *shape]: the finest coefficient arrays inside the packed hierarchy (a view; `rebuild()` after
+        writing them)."""
+        return self.level(0).unflatten(1, (2 * self.ndim + 1,) + self.shapes[0])
+
+    def rebuild(self, coeffs=None):
+        """The set-up again for new finest coefficients [B, 2 d + 1, *shape] (None: already written into `fine`), into the
+        buffers and the launch plan of this object: no device allocation, the same launches as `from_coeffs`.  When the
+        members -- all of them -- decide on other axes than before, the hierarchy is planned anew (new buffers); members
+        that disagree raise ValueError as in `from_coeffs`, and the coarse levels then hold no valid operator until the next
+        successful rebuild."""
+        if coeffs is not None:
+            assert tuple(coeffs.shape) == tuple(self.fine.shape) and coeffs.dtype == self.dtype
+            self.fine.copy_(coeffs)
+        nlev = len(self.shapes)
+        for lvl in range(nlev):
+            halve = self._decide(self.level(lvl), lvl, self.shapes[lvl]) if lvl + 1 < self.max_levels else None
+            if halve != (self.halve[lvl] if lvl + 1 < nlev else None):
+                self._plan(self.level(0).clone())  # (other levels than before)
+                return self
+            if halve is not None:
+                ops.stencil_var_coarsen_batch(self.level(lvl), self.shapes[lvl], halve, out=self.level(lvl + 1))
+        self._invert(self.level(nlev - 1), self.shapes[-1], self._dense, self.inv)
+        return self
 
     def _run(self, x, b, tol, maxcycles, start, mode):
         assert tuple(x.shape) == tuple(b.shape) == (self.nbatch,) + self.shapes[0], (x.shape, b.shape)

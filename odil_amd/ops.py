@@ -267,6 +267,60 @@ def stencil_var_coarsen(coeffs, halve=None):
     return out
 
 
+def _packed_members(t, need):
+    """(pointer, member stride in elements) of a packed tensor [B, >= need] with contiguous members (any leading stride)."""
+    assert t.dim() == 2 and t.shape[1] >= need and (t.shape[1] == 1 or t.stride(1) == 1), (tuple(t.shape), need)
+    return _base_ptr(t), c_int64(int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]))
+
+
+def stencil_var_coarsen_batch(coeffs, shape, halve=None, out=None):
+    """`stencil_var_coarsen` for every member of an ensemble in ONE launch (include/odil_hip.h:
+    odil_stencil_var_coarsen_batch).  coeffs: [B, >= (2 d + 1) cells], member b's arrays of `shape` at the start of row b;
+    out: [B, >= (2 d + 1) coarse cells] likewise (default: a new tensor without padding).  Rows may be views into wider
+    buffers (the levels of one packed hierarchy)."""
+    import ctypes
+
+    shape = tuple(int(n) for n in shape)
+    ndim, nb = len(shape), coeffs.shape[0]
+    halve = [True] * ndim if halve is None else [bool(h) for h in halve]
+    cshape = tuple(n // 2 if h else n for n, h in zip(shape, halve))
+    if out is None:
+        out = torch.empty((nb, (2 * ndim + 1) * math.prod(cshape)), dtype=coeffs.dtype, device=coeffs.device)
+    assert out.shape[0] == nb and out.dtype == coeffs.dtype
+    cp, cs = _packed_members(coeffs, (2 * ndim + 1) * math.prod(shape))
+    op, os_ = _packed_members(out, (2 * ndim + 1) * math.prod(cshape))
+    mask = (ctypes.c_int * ndim)(*[int(h) for h in halve])
+    call("stencil_var_coarsen_batch", coeffs.dtype, cp, cs, op, os_, i64(shape), c_int(ndim),
+         ctypes.cast(mask, ctypes.c_void_p), c_int(nb), stream_ptr())
+    return out
+
+
+def stencil_strength_batch(coeffs, shape, out=None):
+    """[B, 2 d]: max |c| of every off-centre coefficient array of every member in ONE launch -- `max_abs_rows(c[1:])` per
+    member (odil_stencil_strength_batch).  coeffs as in `stencil_var_coarsen_batch`."""
+    shape = tuple(int(n) for n in shape)
+    ndim, nb = len(shape), coeffs.shape[0]
+    if out is None:
+        out = torch.empty((nb, 2 * ndim), dtype=coeffs.dtype, device=coeffs.device)
+    assert tuple(out.shape) == (nb, 2 * ndim) and out.dtype == coeffs.dtype
+    cp, cs = _packed_members(coeffs, (2 * ndim + 1) * math.prod(shape))
+    call("stencil_strength_batch", coeffs.dtype, cp, cs, i64(shape), c_int(ndim), c_int(nb), ptr(out), stream_ptr())
+    return out
+
+
+def stencil_dense_batch(coeffs, shape, out=None):
+    """[B, n, n]: the dense matrix of every member's operator (n = cells <= 512, column j = A e_j with periodic wrap) in ONE
+    launch (odil_stencil_dense_batch).  coeffs as in `stencil_var_coarsen_batch`."""
+    shape = tuple(int(n) for n in shape)
+    ndim, nb, n = len(shape), coeffs.shape[0], math.prod(shape)
+    if out is None:
+        out = torch.empty((nb, n, n), dtype=coeffs.dtype, device=coeffs.device)
+    assert tuple(out.shape) == (nb, n, n) and out.dtype == coeffs.dtype
+    cp, cs = _packed_members(coeffs, (2 * ndim + 1) * n)
+    call("stencil_dense_batch", coeffs.dtype, cp, cs, i64(shape), c_int(ndim), c_int(nb), ptr(out), stream_ptr())
+    return out
+
+
 def stencil_vcycle_tail(coeffs, shapes, halve, xin, b, xout, work, inv, wpre, wpost, fmg=False):
     """The coarse tail of a multigrid cycle in one launch (include/odil_hip.h: odil_stencil_vcycle_tail).  coeffs: one
     flat tensor holding the coefficient arrays of every tail level; shapes: their extents, finest first; halve: per

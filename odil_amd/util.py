@@ -569,10 +569,24 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
     callback(member, state, epoch, pinfo): called for every member at args.epoch_start (the initial evaluation) and at the
     epochs its `next_active(epoch)` attribute names (without the attribute: every epoch); pinfo as `optimize_newton`
     reports it, after a step with pinfo["linsolver"] = the member's solver status.
-    Members must be the recognised Poisson operator with one plain `Field` unknown (no multigrid decomposition), share
+    Members have one plain `Field` unknown (no multigrid decomposition), are the recognised Poisson operator (else below), share
     cshape, spacing, dtype and device and be admitted by `fused.newton_refusal`; anything else raises ValueError naming the
     first offending member -- structure is checked for all members before any operator is probed.
-    Returns ([arrays of member b], optinfo); optinfo.cycles / .residuals: [B, epochs] cycles run and final residual norms."""
+
+    When not every member is that Poisson operator, ALL members take the route for variable-coefficient stencils
+    (optinfo.route == "stencil", and `solver.method` says so): any operator of one plain cell-centred `Field` whose Jacobian
+    is a (2 d + 1)-point stencil -- variable conductivities, reaction and nonlinear terms -- admitted by
+    `fused.newton_stencil_refusal`, same cshape, spacing, dtype and device.  Per epoch: every member is linearised
+    (`linearize_device`, `gmg.recognise_stencil`: B launches of the generated Jacobian kernel -- a batched one would be a
+    change of the generator), the coefficient arrays and f(u) go into packed buffers allocated once, the hierarchies of all
+    members are set up again in launches that do not grow with B (`gmg.EnsembleGMG.rebuild`: two per level, one for the
+    dense coarsest matrices; the pseudo-inverses on the host), ONE launch solves M_b d_b = f_b(u_b) for all members and one
+    forms u -= d.  A member whose Jacobian is no such stencil raises ValueError naming it at the first epoch, before any
+    member is updated; so do members whose hierarchies do not coarsen along the same axes.  There is NO fallback to the
+    normal-equation routes when a member's cycles do not contract (`optimize_newton` has one): the member's status
+    reports converged=False or stagnated, and the caller decides.
+    Returns ([arrays of member b], optinfo); optinfo.cycles / .residuals: [B, epochs] cycles run and final residual norms;
+    optinfo.route: "poisson" or "stencil"."""
     from . import fused
     from . import linsolver as ls
 
@@ -589,6 +603,7 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
     def refuse(member, reason):
         raise ValueError("optimize_newton_ensemble: member {}: {}".format(member, reason))
 
+    routes = dict(poisson=None, stencil=None)  # per route the first (member, reason) it refuses while the other admits
     first = None
     for b, (problem, state) in enumerate(zip(problems, states)):
         domain = problem.domain
@@ -606,9 +621,16 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
         npdt = np.float64 if dtype == torch.float64 else np.float32
         kind = dict(cshape=cshape, dtype=dtype, device=field.array.device,
                     spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
+        # (which route runs is known only once the operators are probed: a member that neither admits is refused here, one
+        # that a single route refuses once the route is known -- still before any state changes)
         reason = fused.newton_refusal(cshape, [npdt(v) ** 2 for v in kind["spacing"]], dtype)
-        if reason is not None:
+        other = fused.newton_stencil_refusal(cshape, dtype)
+        if reason is not None and other is not None:
             refuse(b, reason)
+        if reason is not None and routes["poisson"] is None:
+            routes["poisson"] = (b, reason)
+        if other is not None and routes["stencil"] is None:
+            routes["stencil"] = (b, other)
         first = first or kind
         for what, label in (("cshape", "cells"), ("dtype", "dtype"), ("device", "device"), ("spacing", "grid spacing")):
             if kind[what] != first[what]:
@@ -617,9 +639,13 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
     for b, (problem, state) in enumerate(zip(problems, states)):
         problem.recognise(state)
         ev = getattr(problem, "_fused", None)
-        if ev is None or ev.nlvl != 1:
-            refuse(b, "the operator is not the recognised Poisson stencil")
-        evaluators.append(ev)
+        evaluators.append(ev if ev is not None and ev.nlvl == 1 else None)
+    if any(ev is None for ev in evaluators):
+        if routes["stencil"] is not None:
+            refuse(*routes["stencil"])
+        return _newton_ensemble_stencil(args, problems, states, callback, first, linsolver)
+    if routes["poisson"] is not None:
+        refuse(*routes["poisson"])
     ev = evaluators[0]
     nb = len(problems)
     solver = gmg.EnsembleGMG(ev.cshape, ev.h2, ev.dtype, ev.device, nb)
@@ -658,7 +684,77 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
             report(epoch + 1, True)
             due = next_active(epoch + 1) if next_active else epoch + 2
     arrays = [problem.domain.arrays_from_state(state) for problem, state in zip(problems, states)]
-    return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver)
+    return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver,
+                                      route="poisson")
+
+
+def _newton_ensemble_stencil(args, problems, states, callback, kind, linsolver):
+    """The route of `optimize_newton_ensemble` for members that are not all the Poisson operator (its docstring); the
+    members have passed its checks, `kind` is what they share."""
+    from . import linsolver as ls
+
+    nb, cshape, dtype, device = len(problems), kind["cshape"], kind["dtype"], kind["device"]
+    ndim = len(cshape)
+    stage = torch.empty((nb, 2 * ndim + 1) + cshape, dtype=dtype, device=device)  # (the Jacobians of the first step)
+    r = torch.empty((nb,) + cshape, dtype=dtype, device=device)
+    d = torch.zeros_like(r)
+
+    def linearise(target):
+        """r[b] = f_b(u_b) and target[b] = the coefficient arrays of member b's Jacobian, for every member."""
+        for b, (problem, state) in enumerate(zip(problems, states)):
+            vector, matrix = problem.linearize_device(state)
+            coeffs = gmg.recognise_stencil(matrix)
+            if coeffs is None or tuple(coeffs.shape[1:]) != cshape:
+                raise ValueError("optimize_newton_ensemble: member {}: its Jacobian is not a (2 d + 1)-point stencil of one "
+                                 "cell-centred plain Field".format(b))
+            target[b].copy_(coeffs)
+            r[b].view(-1).copy_(vector.reshape(-1))
+
+    nepochs = max(args.epochs - args.epoch_start, 0)
+    solver = None
+    if nepochs:  # (the first linearisation before anything changes: a member that has no stencil Jacobian is named here)
+        linearise(stage)
+        solver = gmg.EnsembleGMG.from_coeffs(stage)
+    del stage
+    u = torch.stack([problem.domain.arrays_from_state(state)[0].to(dtype) for problem, state in zip(problems, states)])
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        problem.domain.arrays_to_state([u[b]], state)  # (views of the packed iterate: always the current one)
+    tol, maxcycles = ls.cycle_budget(linsolver, getattr(args, "linsolver_tol", 1e-10), getattr(args, "linsolver_maxiter", None))
+    tol = max(tol, 50 * float(torch.finfo(dtype).eps))
+    printlog("Running Newton optimizer on an ensemble of {} members (variable-coefficient stencils)".format(nb))
+
+    def report(epoch, stepped):
+        for b, (problem, state) in enumerate(zip(problems, states)):
+            loss, _, terms, names, norms = problem.eval_loss_grad_device(state)
+            pinfo = _pinfo(loss, terms, names, norms)
+            if stepped:
+                pinfo["linsolver"] = solver.status(b)
+            callback(b, state, epoch, pinfo)
+
+    cycles = np.zeros((nb, nepochs), dtype=np.int64)
+    residuals = np.zeros((nb, nepochs))
+    next_active = getattr(callback, "next_active", None) if callback else None
+    due = None
+    if callback:
+        report(args.epoch_start, False)
+        due = next_active(args.epoch_start) if next_active else args.epoch_start + 1
+    for epoch in range(args.epoch_start, args.epochs):
+        if epoch > args.epoch_start:
+            linearise(solver.fine)
+            solver.rebuild()
+        solver.solve(r, d, tol=tol, maxcycles=maxcycles, start=2)  # M_b d_b = r_b, the convention of optimize_newton
+        ops.axpy(u.view(-1), d.view(-1), -1.0)                     # u -= d for all members
+        k = epoch - args.epoch_start
+        cycles[:, k] = solver.outcome[:, 0]
+        residuals[:, k] = [solver.status(b)["residual"] for b in range(nb)]
+        if getattr(args, "linsolver_verbose", 0):
+            printlog([solver.status(b) for b in range(nb)])
+        if callback and epoch + 1 >= due:
+            report(epoch + 1, True)
+            due = next_active(epoch + 1) if next_active else epoch + 2
+    arrays = [problem.domain.arrays_from_state(state) for problem, state in zip(problems, states)]
+    return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver,
+                                      route="stencil")
 
 
 def optimize(args, optname, problem, state, callback, **kwargs):
