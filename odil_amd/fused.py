@@ -201,7 +201,32 @@ class PoissonEvaluator:
                                  self.h2, alphas, omb1, omb2, eps, losses, norms)
 
 
-class PoissonEnsemble:
+class _Members:
+    """What every ensemble class answers before it holds anything: whether these evaluators run side by side."""
+
+    shape_refusal = None  # (evaluator) -> reason or None: the predicate of the class's form
+
+    @classmethod
+    def refusal(cls, evaluators):
+        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
+        if not evaluators:
+            return 0, "an ensemble needs at least one member"
+        first = evaluators[0]
+        for b, ev in enumerate(evaluators):
+            if not isinstance(ev, PoissonEvaluator):
+                return b, "the operator is not the recognised Poisson stencil"
+            reason = cls.shape_refusal(ev)
+            if reason is not None:
+                return b, reason
+            for what in ("cshape", "shapes", "dtype", "device"):
+                if getattr(ev, what) != getattr(first, what):
+                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
+            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
+                return b, "grid spacing differs from member 0's"
+        return None
+
+
+class PoissonEnsemble(_Members):
     """B recognised Poisson problems of one shape side by side: packed [B, unknowns] state, moments, gradient and synthesis
     scratch, [B, cells] residuals and right-hand sides, and whole Adam epochs of every member in ONE launch with one
     workgroup per member (odil_poisson_small_epochs_batch).  Member b computes what `PoissonEvaluator.small_epochs`
@@ -225,24 +250,7 @@ class PoissonEnsemble:
         npart = int(load().odil_poisson_small_epochs_partials(i64(self.shapes[0]), ev.ndim, self.x.element_size()))
         self.partials = torch.empty((self.nbatch, npart), dtype=torch.float64, device=self.device)
 
-    @staticmethod
-    def refusal(evaluators):
-        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
-        if not evaluators:
-            return 0, "an ensemble needs at least one member"
-        first = evaluators[0]
-        for b, ev in enumerate(evaluators):
-            if not isinstance(ev, PoissonEvaluator):
-                return b, "the operator is not the recognised Poisson stencil"
-            reason = small_refusal(ev.shapes, ev.dtype, ev.small_force, ev.small_max_cells)
-            if reason is not None:
-                return b, reason
-            for what in ("cshape", "shapes", "dtype", "device"):
-                if getattr(ev, what) != getattr(first, what):
-                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
-            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
-                return b, "grid spacing differs from member 0's"
-        return None
+    shape_refusal = staticmethod(lambda ev: small_refusal(ev.shapes, ev.dtype, ev.small_force, ev.small_max_cells))
 
     def levels(self, packed, member):
         """The level arrays of one member: views of a row of a packed [B, unknowns] tensor."""
@@ -255,39 +263,38 @@ class PoissonEnsemble:
                                        alphas, omb1, omb2, eps, losses, norms, self.partials)
 
 
-class BatchedLaunches:
+class BatchedLaunches(_Members):
     """What the ensembles that run as batched launches share (PoissonLaunchEnsemble, PoissonVolumeEnsemble): level-major
     [B, *shape] storage, the refusal of members that differ, and epochs one at a time -- the interface
     `AdamNativeOptimizer.run_ensemble` drives."""
 
-    shape_refusal = None  # (shapes, dtype) -> reason or None: the form's predicate
+    def __init__(self, evaluators, pad, levels_refusal):
+        """What both forms hold: x, m, v, g (one [B, *shape] tensor per level), fu, rhs, loss and norm.
+        levels_refusal(shapes, nbatch, dtype): the library's answer why a transfer level of the batch would not run the
+        kernel that level of a single member runs, or None -- asked before the first launch."""
+        reason = self.refusal(evaluators)
+        if reason is not None:
+            raise ValueError("ensemble member {}: {}".format(*reason))
+        ev = evaluators[0]
+        reason = levels_refusal(ev.shapes, len(evaluators), ev.dtype)
+        if reason is not None:
+            raise ValueError("ensemble of {} members: {}".format(len(evaluators), reason))
+        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
+        self.cshape, self.ndim, self.loc, self.scale = ev.cshape, ev.ndim, "." + ev.loc, float(ev.scale)
+        self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
+        self.names = [e.names for e in evaluators]
+        level = lambda wide0=0: [self.members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
+        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
+        self.fu, self.rhs = self.members(self.cshape, pad), self.members(self.cshape, pad)
+        self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
+        self.loss, self.norm = (torch.zeros(self.nbatch, dtype=self.dtype, device=self.device) for _ in range(2))
 
-    @staticmethod
-    def members(nb, shape, wide=0, **kw):
-        """Zeroed [nb, *shape] tensor with `wide` extra elements between its contiguous members."""
+    def members(self, shape, wide=0):
+        """Zeroed [B, *shape] tensor with `wide` extra elements between its contiguous members."""
         cells = math.prod(shape)
-        base = torch.zeros(nb * (cells + wide), **kw)
+        base = torch.zeros(self.nbatch * (cells + wide), dtype=self.dtype, device=self.device)
         strides = [math.prod(shape[k + 1:]) for k in range(len(shape))]
-        return base.as_strided((nb,) + tuple(shape), [cells + wide] + strides)
-
-    @classmethod
-    def refusal(cls, evaluators):
-        """(member, reason) of the first member that keeps these evaluators from running as one ensemble, else None."""
-        if not evaluators:
-            return 0, "an ensemble needs at least one member"
-        first = evaluators[0]
-        for b, ev in enumerate(evaluators):
-            if not isinstance(ev, PoissonEvaluator):
-                return b, "the operator is not the recognised Poisson stencil"
-            reason = cls.shape_refusal(ev.shapes, ev.dtype)
-            if reason is not None:
-                return b, reason
-            for what in ("cshape", "shapes", "dtype", "device"):
-                if getattr(ev, what) != getattr(first, what):
-                    return b, "{} {} differs from member 0's {}".format(what, getattr(ev, what), getattr(first, what))
-            if [float(a) for a in ev.h2] != [float(a) for a in first.h2]:
-                return b, "grid spacing differs from member 0's"
-        return None
+        return base.as_strided((self.nbatch,) + tuple(shape), [cells + wide] + strides)
 
     def levels(self, packed, member):
         """The level arrays of one member: views of the [B, *shape] level tensors."""
@@ -312,30 +319,13 @@ class PoissonLaunchEnsemble(BatchedLaunches):
     pad: extra elements between the members of the arrays that only the stencil kernels touch (fu, rhs, m[0], v[0])."""
 
     def __init__(self, evaluators, pad=0):
-        reason = self.refusal(evaluators)
-        if reason is not None:
-            raise ValueError("ensemble member {}: {}".format(*reason))
-        ev = evaluators[0]
-        # (both transfer chains of the batch must run the kernel a single member runs: asked before the first launch)
-        reason = _levels_refusal(ev.shapes, len(evaluators))
-        if reason is not None:
-            raise ValueError("ensemble of {} members: {}".format(len(evaluators), reason))
-        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
-        self.cshape, self.ndim, self.loc, self.scale = ev.cshape, ev.ndim, "." + ev.loc, float(ev.scale)
-        self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
-        self.names = [e.names for e in evaluators]
-        nb, kw = self.nbatch, dict(dtype=self.dtype, device=self.device)
-        members = lambda shape, wide=0: self.members(nb, shape, wide, **kw)
-        level = lambda wide0=0: [members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
-        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
-        self.u, self.fu, self.rhs = members(self.cshape), members(self.cshape, pad), members(self.cshape, pad)
-        self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
-        self.work = ([None] + [members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
+        super().__init__(evaluators, pad, lambda shapes, nbatch, dtype: _levels_refusal(shapes, nbatch))
+        self.u = self.members(self.cshape)
+        self.work = ([None] + [self.members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
         npart = ops.poisson_batch_partials(self.cshape, self.dtype)
-        self.partials = torch.empty((nb, npart), dtype=torch.float64, device=self.device)
-        self.loss, self.norm = torch.zeros(nb, **kw), torch.zeros(nb, **kw)
+        self.partials = torch.empty((self.nbatch, npart), dtype=torch.float64, device=self.device)
 
-    shape_refusal = staticmethod(lambda shapes, dtype: launches_refusal(shapes, dtype))
+    shape_refusal = staticmethod(lambda ev: launches_refusal(ev.shapes, ev.dtype))
 
     def epoch(self, alphas, omb1, omb2, eps):
         """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
@@ -358,33 +348,14 @@ class PoissonVolumeEnsemble(BatchedLaunches):
     pad: extra elements between the members of the arrays that only the stencil kernels touch (fu, rhs, m[0], v[0])."""
 
     def __init__(self, evaluators, pad=0):
-        reason = self.refusal(evaluators)
-        if reason is not None:
-            raise ValueError("ensemble member {}: {}".format(*reason))
-        ev = evaluators[0]
-        # (every transfer level of the batch must run the kernel that level of a single member runs: asked before the
-        # first launch)
-        reason = _volume_levels_refusal(ev.shapes, len(evaluators), ev.dtype)
-        if reason is not None:
-            raise ValueError("ensemble of {} members: {}".format(len(evaluators), reason))
-        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
-        self.cshape, self.ndim, self.loc, self.scale = ev.cshape, ev.ndim, "." + ev.loc, float(ev.scale)
-        self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
-        self.names = [e.names for e in evaluators]
-        nb, kw = self.nbatch, dict(dtype=self.dtype, device=self.device)
-        members = lambda shape, wide=0: self.members(nb, shape, wide, **kw)
-        level = lambda wide0=0: [members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
-        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
-        self.fu, self.rhs = members(self.cshape, pad), members(self.cshape, pad)
-        self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
+        super().__init__(evaluators, pad, _volume_levels_refusal)
         # synthesis scratch of the levels 1 ... nlvl - 2 (level 1: the coarse operand of the residual)
-        self.work = [None] + [members(s) for s in self.shapes[1:-1]] + [None]
+        self.work = [None] + [self.members(s) for s in self.shapes[1:-1]] + [None]
         nsums, npart = ops.residual_synth_batch_workspace(self.shapes[1])
-        self.sums = torch.empty((nb, nsums), dtype=torch.float64, device=self.device)
-        self.partials = torch.empty((nb, npart), dtype=torch.float64, device=self.device)
-        self.loss, self.norm = torch.zeros(nb, **kw), torch.zeros(nb, **kw)
+        self.sums = torch.empty((self.nbatch, nsums), dtype=torch.float64, device=self.device)
+        self.partials = torch.empty((self.nbatch, npart), dtype=torch.float64, device=self.device)
 
-    shape_refusal = staticmethod(lambda shapes, dtype: volumes_refusal(shapes, dtype))
+    shape_refusal = staticmethod(lambda ev: volumes_refusal(ev.shapes, ev.dtype))
 
     def epoch(self, alphas, omb1, omb2, eps):
         """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
@@ -399,36 +370,64 @@ class PoissonVolumeEnsemble(BatchedLaunches):
         ops.mg_synth_adj_adam_volumes(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
 
 
-def _volume_levels_refusal(shapes, nbatch, dtype):
-    """The library's answer (odil_mg_volumes_levels_ok): why a transfer level of `nbatch` 3-D members of these level
-    shapes would not run the kernel that level of one member runs, or None."""
+def _library_refusal(entry, shapes, *more):
+    """None when the library's `entry(shapes, levels, ndim, *more)` returns 0, else its error text."""
     from ._lib import i64, load
 
     lib = load()
     flat = [int(n) for shape in shapes for n in shape]
-    if lib.odil_mg_volumes_levels_ok(i64(flat), len(shapes), len(shapes[0]), int(nbatch),
-                                     4 if dtype == torch.float32 else 8) == 0:
+    if getattr(lib, entry)(i64(flat), len(shapes), len(shapes[0]), *more) == 0:
         return None
     return lib.odil_last_error().decode()
+
+
+def _volume_levels_refusal(shapes, nbatch, dtype):
+    """The library's answer (odil_mg_volumes_levels_ok): why a transfer level of `nbatch` 3-D members of these level
+    shapes would not run the kernel that level of one member runs, or None."""
+    return _library_refusal("odil_mg_volumes_levels_ok", shapes, int(nbatch), 4 if dtype == torch.float32 else 8)
+
+
+def _levels_refusal(shapes, nbatch):
+    """The library's answer (odil_mg_batch_levels_ok): why the transfer levels of `nbatch` members of these level shapes
+    would not run the kernels one member's run (level count, extents, refinement, schedule limits), or None."""
+    return _library_refusal("odil_mg_batch_levels_ok", shapes, int(nbatch))
+
+
+# The shape-only refusals that the forms share: each the reason, or None where it does not apply.  Every predicate below
+# asks for those it needs, in its own order.
+def _too_few_levels(shapes):
+    if len(shapes) < 2:
+        return "1 level: the batched launches need a multigrid field of at least 2 levels"
+
+
+def _not_halving(shapes):
+    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):
+        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
+
+
+def _coarsest_too_small(shapes):
+    if any(n < 2 for n in shapes[-1]):
+        return "levels {}: every extent must be at least 2".format([tuple(s) for s in shapes])
+
+
+def _unaligned_members(shapes, dtype):
+    cells = math.prod(shapes[0])
+    if dtype is not None and (cells * (8 if dtype == torch.float64 else 4)) % 16:
+        return "a member of {} cells is not a multiple of 16 bytes (members lie back to back)".format(cells)
 
 
 def volumes_refusal(shapes, dtype=None):
     """Why levels of these shapes are not run as batched launches of 3-D members (PoissonVolumeEnsemble), or None when
     they are.  From the shapes (and, for the alignment of the members and the transfer kernels, the dtype) alone; the
     limits of the kernels are the library's."""
-    ndim, nlvl = len(shapes[0]), len(shapes)
-    if ndim != 3:
-        return "{}-D grid: the batched launches of volumes run 3-D grids".format(ndim)
-    if nlvl < 2:
-        return "1 level: the batched launches need a multigrid field of at least 2 levels"
-    if dtype is not None and (math.prod(shapes[0]) * (8 if dtype == torch.float64 else 4)) % 16:
-        return "a member of {} cells is not a multiple of 16 bytes (members lie back to back)".format(math.prod(shapes[0]))
-    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):
-        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
-    if any(n < 4 for n in shapes[0]):
-        return "levels {}: every extent of the finest level must be at least 4".format([tuple(s) for s in shapes])
-    if any(n < 2 for n in shapes[-1]):
-        return "levels {}: every extent must be at least 2".format([tuple(s) for s in shapes])
+    if len(shapes[0]) != 3:
+        return "{}-D grid: the batched launches of volumes run 3-D grids".format(len(shapes[0]))
+    reason = _too_few_levels(shapes) or _unaligned_members(shapes, dtype) or _not_halving(shapes)
+    if reason is None and any(n < 4 for n in shapes[0]):
+        reason = "levels {}: every extent of the finest level must be at least 4".format([tuple(s) for s in shapes])
+    reason = reason or _coarsest_too_small(shapes)
+    if reason is not None:
+        return reason
     if dtype == torch.float32 and ops.adjoint_transpose_supported(shapes[0]):
         # a single run of this shape takes the one-pass adjoint + first transpose launch, which sums the transpose in
         # the LDS-tile kernel's order; the ensemble runs the separate kernels, and where the separate first transpose
@@ -441,34 +440,14 @@ def volumes_refusal(shapes, dtype=None):
     return _volume_levels_refusal(shapes, 1, dtype)
 
 
-def _levels_refusal(shapes, nbatch):
-    """The library's answer (odil_mg_batch_levels_ok): why the transfer levels of `nbatch` members of these level shapes
-    would not run the kernels one member's run (level count, extents, refinement, schedule limits), or None."""
-    from ._lib import i64, load
-
-    lib = load()
-    flat = [int(n) for shape in shapes for n in shape]
-    if lib.odil_mg_batch_levels_ok(i64(flat), len(shapes), len(shapes[0]), int(nbatch)) == 0:
-        return None
-    return lib.odil_last_error().decode()
-
-
 def launches_refusal(shapes, dtype=None):
     """Why levels of these shapes are not run as batched launches (PoissonLaunchEnsemble), or None when they are.  From the
     shapes (and, for the alignment of the members, the dtype) alone; the limits of the kernels are the library's."""
-    ndim, nlvl = len(shapes[0]), len(shapes)
-    if ndim > 2:
+    if len(shapes[0]) > 2:
         return ("{}-D grid: the batched launches run 1-D and 2-D grids (a 3-D run fuses the synthesis into its residual "
-                "and the first transpose into its adjoint)".format(ndim))
-    if nlvl < 2:
-        return "1 level: the batched launches need a multigrid field of at least 2 levels"
-    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):
-        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
-    if any(n < 2 for n in shapes[-1]):
-        return "levels {}: every extent must be at least 2".format([tuple(s) for s in shapes])
-    if dtype is not None and (math.prod(shapes[0]) * (8 if dtype == torch.float64 else 4)) % 16:
-        return "a member of {} cells is not a multiple of 16 bytes (members lie back to back)".format(math.prod(shapes[0]))
-    return _levels_refusal(shapes, 1)
+                "and the first transpose into its adjoint)".format(len(shapes[0])))
+    return (_too_few_levels(shapes) or _not_halving(shapes) or _coarsest_too_small(shapes)
+            or _unaligned_members(shapes, dtype) or _levels_refusal(shapes, 1))
 
 
 def ensemble_form(form, shapes, dtype):
@@ -505,9 +484,7 @@ def small_refusal(shapes, dtype, force=None, max_cells=None):
     if not resident and not force and not (ndim == 1 and cells <= max_cells):
         return "{} cells are above the limit of the one-workgroup epochs (state resident in LDS, or 1-D up to {} cells)".format(
             cells, max_cells)
-    if any(tuple(2 * n for n in b) != tuple(a) for a, b in zip(shapes, shapes[1:])):  # (as the kernel requires)
-        return "levels {} do not halve exactly".format([tuple(s) for s in shapes])
-    return None
+    return _not_halving(shapes)  # (as the kernel requires)
 
 
 def newton_refusal(cshape, h2, dtype):

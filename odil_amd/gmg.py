@@ -668,12 +668,22 @@ class EnsembleGMG:
     EnsembleGMG([hierarchy, ...]): one hierarchy per member (`StencilGMG` objects of one shape, or anything with `shapes`,
     `locs`, `tail_coeffs`, `coarse_inverse`, `weights`, `nu1`, `nu2`): their operators and inverses are packed per member.
     EnsembleGMG.from_coeffs(coeffs [B, 2 d + 1, *shape]): the same per-member hierarchies, set up for all members at once
-    in launches that do not grow with B; `rebuild` repeats the set-up in place (every Newton step of a nonlinear operator)."""
+    in launches that do not grow with B; `rebuild` repeats the set-up in place (every Newton step of a nonlinear operator).
+
+    However it was made, an object has these attributes (`core`; `solve`, `newton_step`, `status` and the drivers of
+    ensemble.py rely on nothing else):
+        nbatch, dtype, device, ndim, shapes, locs, halve, coeffs, inv, wpre, wpost, nu1, nu2, cells, work, method
+    shapes: the levels, fine to coarse; halve / locs: per transition the axes that are halved, as booleans / as 'c' and
+    '.'; coeffs: the operators of all levels, flat [ncoeff] when the members share them, else [B, ncoeff]; inv: the
+    coarsest inverse [n, n] or [B, n, n]; wpre / wpost: the weights of the nu1 / nu2 sweeps before / after the coarse
+    correction; cells: of the finest level; work: [B, need] scratch of the launch; method: what `status` reports.
+    Only an object made by `from_coeffs` has `fine`, `level` and `rebuild` (ValueError on the others)."""
 
     max_cells = 32768    # cells of a member's finest level (32^3, 128^2, 1-D up to 32768)
     max_levels = 8       # kTailMaxLev of csrc/vcycle_tail.hip
     max_coarsest = 512   # unknowns of the coarsest level (its dense inverse is applied by one workgroup)
-    method = "gmg-vcycle, one workgroup per member"
+    core = ("nbatch", "dtype", "device", "ndim", "shapes", "locs", "halve", "coeffs", "inv", "wpre", "wpost", "nu1", "nu2",
+            "cells", "work", "method")
 
     @classmethod
     def plan(cls, shape, h2, npdt, min_size=None):
@@ -688,7 +698,13 @@ class EnsembleGMG:
                 shapes, h2s, locs = poisson_hierarchy(shape, h2, npdt, min_size)
         return shapes, h2s, locs, min_size
 
-    def __init__(self, shape, h2=None, dtype=None, device=None, nbatch=None, min_size=None):
+    def __init__(self, shape, h2=None, dtype=None, device=None, nbatch=None, min_size=None, nu1=None, nu2=None):
+        self._strength = None  # (the scratch of the set-up launches: only `from_coeffs` objects have one)
+        if torch.is_tensor(shape):
+            self.method = "gmg-vcycle (variable coefficients), one workgroup per member"
+            self._init_coeffs(shape, nu1, nu2, 2 if min_size is None else min_size)
+            return
+        self.method = "gmg-vcycle, one workgroup per member"
         if isinstance(shape, (list, tuple)) and shape and not isinstance(shape[0], (int, np.integer)):
             members = list(shape)
             first = members[0]
@@ -696,33 +712,20 @@ class EnsembleGMG:
                 if [tuple(s) for s in h.shapes] != [tuple(s) for s in first.shapes] or list(h.locs) != list(first.locs) \
                         or h.dtype != first.dtype or (h.nu1, h.nu2) != (first.nu1, first.nu2):
                     raise ValueError("ensemble member {}: its hierarchy differs from member 0's".format(b))
-            self.nbatch, self.dtype, self.device = len(members), first.dtype, first.device
-            self.shapes, self.locs = [tuple(s) for s in first.shapes], list(first.locs)
-            self.coeffs = torch.stack([torch.cat([h.tail_coeffs(l).reshape(-1) for l in range(len(self.shapes))])
-                                       for h in members]).contiguous()
-            self.inv = torch.stack([h.coarse_inverse() for h in members]).contiguous()
-            self.base = first
+            self.nbatch = len(members)
+            coeffs = torch.stack([torch.cat([h.tail_coeffs(l).reshape(-1) for l in range(len(first.shapes))])
+                                  for h in members]).contiguous()
+            inv = torch.stack([h.coarse_inverse() for h in members]).contiguous()
         else:
             npdt = np.float64 if dtype == torch.float64 else np.float32
             min_size = self.plan(shape, h2, npdt, min_size)[3]
-            self.base = base = PoissonGMG(shape, h2, dtype, device, min_size=min_size)
-            self.nbatch, self.dtype, self.device = int(nbatch), dtype, device
-            self.shapes, self.locs = [tuple(s) for s in base.shapes], list(base.locs)
-            self.coeffs = torch.cat([base.tail_coeffs(l).reshape(-1) for l in range(base.nlvl)])
-            self.inv = base.coarse_inverse()
-        self.halve = [[c == "c" for c in loc] for loc in self.locs]
-        self.wpre, self.wpost = self.base.weights(self.base.nu1), self.base.weights(self.base.nu2)
-        self.cells = math.prod(self.shapes[0])
-        need = ops.stencil_solve_batch_work(self.shapes)
-        if not need or len(self.shapes) > self.max_levels or math.prod(self.shapes[-1]) > self.max_coarsest:
-            raise ValueError("EnsembleGMG: levels {} are not walked by one workgroup (at most {} levels, a coarsest level "
-                             "of at most {} unknowns)".format(self.shapes, self.max_levels, self.max_coarsest))
-        self.work = torch.empty((self.nbatch, need), dtype=self.dtype, device=self.device)
-        self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
-                                                    self.wpre, self.wpost)
-        self._out = dict()      # maxcycles -> (history, outcome) device tensors
-        self.history = None     # [B, maxcycles + 2], [B, 2] of the last launch on the host
-        self.outcome = None
+            first = PoissonGMG(shape, h2, dtype, device, min_size=min_size)
+            self.nbatch = int(nbatch)
+            coeffs = torch.cat([first.tail_coeffs(l).reshape(-1) for l in range(first.nlvl)])
+            inv = first.coarse_inverse()
+        self.dtype, self.device, self.ndim = first.dtype, first.device, len(first.shapes[0])
+        self.nu1, self.nu2, self.wpre, self.wpost = first.nu1, first.nu2, first.weights(first.nu1), first.weights(first.nu2)
+        self._finish([tuple(s) for s in first.shapes], [[c == "c" for c in loc] for loc in first.locs], coeffs, inv)
 
     @classmethod
     def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2):
@@ -733,27 +736,49 @@ class EnsembleGMG:
         for the dense coarsest matrices and one read-back; the pseudo-inverses are `StencilGMG.invert` per member on the
         host in float64.  The kernel walks one set of shapes: every member must take member 0's decision on every level,
         else ValueError (no object is made).  Coarsening stops under StencilGMG's rule or at `max_levels` levels."""
-        self = cls.__new__(cls)
+        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size)
+
+    def _init_coeffs(self, coeffs, nu1, nu2, min_size):
         nb, ndim = int(coeffs.shape[0]), coeffs.dim() - 2
         if nb < 1 or not 1 <= ndim <= 3 or coeffs.shape[1] != 2 * ndim + 1:
             raise ValueError("EnsembleGMG.from_coeffs: coefficients {} are not [B, 2 d + 1, *shape] with d <= 3".format(
                 tuple(coeffs.shape)))
         shape = tuple(int(n) for n in coeffs.shape[2:])
-        if math.prod(shape) > cls.max_cells:
+        if math.prod(shape) > self.max_cells:
             raise ValueError("EnsembleGMG.from_coeffs: {} cells are above the limit of the one-workgroup solves ({})".format(
-                math.prod(shape), cls.max_cells))
+                math.prod(shape), self.max_cells))
         self.nbatch, self.dtype, self.device, self.ndim = nb, coeffs.dtype, coeffs.device, ndim
         self.nu1 = PoissonGMG.nu_default[0] if nu1 is None else nu1
         self.nu2 = PoissonGMG.nu_default[1] if nu2 is None else nu2
-        self.min_size, self.base = min_size, None
-        self.method = "gmg-vcycle (variable coefficients), one workgroup per member"
         self.wpre, self.wpost = jacobi_weights(ndim, self.nu1), jacobi_weights(ndim, self.nu2)
-        self.cells = math.prod(shape)
+        self._min_size, self._shape0 = min_size, shape
         self._strength = torch.empty((nb, 2 * ndim), dtype=self.dtype, device=self.device)
-        self._out, self.history, self.outcome = dict(), None, None
-        self._shape0 = shape
         self._plan(coeffs.reshape(nb, -1))
-        return self
+
+    def _work_elements(self, shapes):
+        """Work elements per member of the launch that walks these levels; ValueError when one workgroup does not."""
+        need = ops.stencil_solve_batch_work(shapes)
+        if not need or len(shapes) > self.max_levels or math.prod(shapes[-1]) > self.max_coarsest:
+            raise ValueError("EnsembleGMG: levels {} are not walked by one workgroup (at most {} levels, a coarsest level "
+                             "of at most {} unknowns)".format(shapes, self.max_levels, self.max_coarsest))
+        return need
+
+    def _finish(self, shapes, halves, coeffs, inv):
+        """The end of every construction (and of a `rebuild` that plans anew): the levels, their packed operators and
+        coarsest inverses become the object's, with the work array and the launch plan that go with them; nothing is
+        changed when one workgroup does not walk these levels."""
+        need = self._work_elements(shapes)
+        self.shapes, self.halve = shapes, halves
+        self.locs = ["".join("c" if on else "." for on in halve) for halve in halves]
+        self.coeffs, self.inv, self.cells = coeffs, inv, math.prod(shapes[0])
+        self.work = torch.empty((self.nbatch, need), dtype=self.dtype, device=self.device)
+        self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
+                                                    self.wpre, self.wpost)
+        self._out = dict()      # maxcycles -> (history, outcome) device tensors
+        self.history = None     # [B, maxcycles + 2], [B, 2] of the last launch on the host
+        self.outcome = None
+        missing = [name for name in self.core if not hasattr(self, name)]
+        assert not missing, "EnsembleGMG lacks {}".format(missing)
 
     def _decide(self, level, lvl, shape):
         """The `halve` of `StencilGMG.__init__` for the level `level` [B, (2 d + 1) cells] of every member (one launch, one
@@ -764,7 +789,7 @@ class EnsembleGMG:
             size = ops.stencil_strength_batch(level, shape, out=self._strength).cpu().numpy().astype(np.float64)
             strength = np.minimum(size[:, 0::2], size[:, 1::2])
             every = strength >= 0.5 * strength.max(axis=1, keepdims=True)
-            blocked = np.array([not (n % 2 == 0 and n // 2 >= self.min_size) for n in shape])
+            blocked = np.array([not (n % 2 == 0 and n // 2 >= self._min_size) for n in shape])
             if (every & blocked).any(axis=1).all():
                 return None  # (every member's coarsening stops here, whichever axes it would merge)
             differ = np.nonzero((every != every[0]).any(axis=1))[0]
@@ -776,13 +801,13 @@ class EnsembleGMG:
             halve = [bool(v) for v in every[0]]
             if not any(halve):
                 raise ValueError("EnsembleGMG: the couplings of level {} are not finite".format(lvl))
-        if not all(n % 2 == 0 and n // 2 >= self.min_size for n, on in zip(shape, halve) if on):
+        if not all(n % 2 == 0 and n // 2 >= self._min_size for n, on in zip(shape, halve) if on):
             return None
         return halve
 
     def _plan(self, fine):
-        """Builds shapes, the packed hierarchy [B, ncoeff], the inverses, the work array and the launch plan from the finest
-        coefficients [B, (2 d + 1) cells]; the object is changed only once everything stands."""
+        """Builds shapes, the packed hierarchy [B, ncoeff] and the inverses from the finest coefficients
+        [B, (2 d + 1) cells]; the object is changed only once everything stands."""
         shapes, halves, levels = [self._shape0], [], [fine]
         while len(shapes) < self.max_levels:
             halve = self._decide(levels[-1], len(shapes) - 1, shapes[-1])
@@ -791,23 +816,16 @@ class EnsembleGMG:
             levels.append(ops.stencil_var_coarsen_batch(levels[-1], shapes[-1], halve))
             shapes.append(tuple(n // 2 if on else n for n, on in zip(shapes[-1], halve)))
             halves.append(halve)
+        self._work_elements(shapes)  # (before the dense matrices of a coarsest level that is too large are formed)
         ninv = math.prod(shapes[-1])
-        need = ops.stencil_solve_batch_work(shapes)
-        if not need or ninv > self.max_coarsest:
-            raise ValueError("EnsembleGMG: levels {} are not walked by one workgroup (at most {} levels, a coarsest level "
-                             "of at most {} unknowns)".format(shapes, self.max_levels, self.max_coarsest))
         coeffs = torch.cat(levels, dim=1).contiguous()
         dense = torch.empty((self.nbatch, ninv, ninv), dtype=self.dtype, device=self.device)
         inv = torch.empty_like(dense)
         self._invert(levels[-1], shapes[-1], dense, inv)
-        self.shapes, self.halve = shapes, halves
-        self.locs = ["".join("c" if on else "." for on in halve) for halve in halves]
-        self.coeffs, self.inv, self._dense = coeffs, inv, dense
+        self._finish(shapes, halves, coeffs, inv)
+        self._dense = dense
         sizes = [(2 * self.ndim + 1) * math.prod(s) for s in shapes]
         self._offsets = [sum(sizes[:l]) for l in range(len(sizes) + 1)]
-        self.work = torch.empty((self.nbatch, need), dtype=self.dtype, device=self.device)
-        self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
-                                                    self.wpre, self.wpost)
 
     def _invert(self, coarsest, shape, dense, inv):
         """inv[b] = StencilGMG.invert(the dense matrix of member b's coarsest operator): one launch, one read-back, the
@@ -818,6 +836,8 @@ class EnsembleGMG:
 
     def level(self, lvl):
         """[B, (2 d + 1) cells of level lvl]: the coefficient arrays of every member on that level (a view)."""
+        if self._strength is None:  # (`fine` and `rebuild` come through here too)
+            raise ValueError("EnsembleGMG: only an object made by from_coeffs has `fine`, `level` and `rebuild`")
         return self.coeffs[:, self._offsets[lvl]:self._offsets[lvl + 1]]
 
     @property
