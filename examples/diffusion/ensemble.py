@@ -3,11 +3,14 @@
 1 + a_b (k - 1), the amplitude a_b running from 1 / B to 1 over the members, every Newton step of all members in ONE
 solve launch, one workgroup per member (`odil.util.optimize_newton_ensemble`, its route for variable-coefficient
 stencils).  With `--beta > 0` the operator is nonlinear,  div(k grad u) - beta u^3 = f,  and the members' multigrid
-hierarchies are set up again every step.  The time per step is printed beside that of the same members as single
+hierarchies are set up again every step.  Every step linearises all members in one generated launch (`--linearize
+batched`, `odil.util.linearize_ensemble`) or member by member (`--linearize members`); the linearisation's share of a step
+is printed from device events around it.  The time per step is printed beside that of the same members as single
 `optimize_newton` runs, one after the other (`--single 0` skips those).
 
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --kind smooth --epochs 2
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --beta 1 --epochs 4
+    python examples/diffusion/ensemble.py --members 256 --ndim 2 --N 64 --linearize members --single 0
 """
 
 import argparse
@@ -43,6 +46,8 @@ def parse_args(argv=None):
     own.add_argument("--members", type=int, default=16, help="Problems in the ensemble")
     own.add_argument("--beta", type=float, default=0.0, help="Strength of the nonlinear term: div(k grad u) - beta u^3 = f")
     own.add_argument("--single", type=int, default=1, help="Also run the members as single optimize_newton runs and time them")
+    own.add_argument("--linearize", type=str, default="batched", choices=("batched", "members"),
+                     help="Linearise all members in one generated launch, or member by member")
     mine, rest = own.parse_known_args(argv)
     args = diffusion.parse_args(["--ndim", "2", "--N", "16", "--epochs", "2"] + rest)
     for key, value in vars(mine).items():
@@ -102,11 +107,14 @@ def main():
             problem.domain.arrays_to_state([u.clone()], state)
         synchronize()
 
-    arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback)
-    if args.single:  # (the same steps again, now that every member's operator is traced and its kernels are loaded)
+    arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback, linearize=args.linearize)
+    import torch
+
+    together, timed = None, optinfo.route == "stencil" and torch.cuda.is_available()
+    if args.epochs > args.epoch_start:  # (the same steps again, now that every member's operator is traced and its kernels are loaded)
         restart()
         start = time.perf_counter()
-        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states)
+        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, linearize=args.linearize, time_linearize=timed)
         synchronize()
         together = (time.perf_counter() - start) / nsteps
     status = [optinfo.solver.status(b) for b in range(args.members)] if optinfo.solver is not None else []
@@ -116,8 +124,13 @@ def main():
             b, st["niter"], st["residual"] / max(st["bnorm"], 1e-300), "" if st["converged"] else " (not converged)",
             diffusion.error_rms(problem.domain, problem.extra, state, "u")))
     lines = ["{} converged members of {}".format(sum(bool(st["converged"]) for st in status), args.members)]
-    if args.single:
+    if together is not None:
         lines.append("ensemble: {:.3f} ms per Newton step of all members".format(1e3 * together))
+    if together is not None and optinfo.linearize_ms is not None:
+        share = float(np.mean(optinfo.linearize_ms))
+        lines.append("linearisation ({}, {} launches per step): {:.3f} ms per step, {:.0f} % of a step".format(
+            args.linearize, int(optinfo.linearize_launches[-1]), share, 100 * share / (1e3 * together)))
+    if args.single and together is not None:
         restart()
         odil.util.optimize_newton(args, problems[0], states[0])  # (the kernels of the single route, loaded once)
         restart()

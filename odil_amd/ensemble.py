@@ -1,16 +1,18 @@
 """Drivers that run B problems side by side: `optimize_ensemble` (Adam) and `optimize_newton_ensemble` (Newton).  The
 reference runs a sweep as B processes and has no counterpart; `util` re-exports both names next to `optimize_grad` /
 `optimize_newton`, whose single runs every member reproduces.  Written once for both drivers: `_check_members`; for both
-Newton routes: `_newton_loop`.  `printlog` and `_pinfo` are `util`'s (one log sink).
+Newton routes: `_newton_loop`.  `linearize_ensemble` (`EnsembleLinearizer`) is the linearisation of the Newton driver's
+stencil route, all members in one generated launch.  `printlog` and `_pinfo` are `util`'s (one log sink).
 """
 
 import argparse
+import os
 
 import numpy as np
 import torch
 
 from . import gmg, ops, util
-from .core import Field
+from .core import Field, Problem
 from .optimizer import make_optimizer
 
 # what members are compared by -> how a refusal calls it
@@ -41,6 +43,19 @@ def _check_members(who, problems, states, describe):
             if value != first[what]:
                 refuse(b, "{} {} differ from member 0's {}".format(_LABELS[what], value, first[what]))
     return first, refuse
+
+
+def _plain_field(b, problem, state, refuse):
+    """What the Newton routes compare of member b, whose unknown must be ONE plain cell-centred `Field` of the domain."""
+    domain = problem.domain
+    (field,) = state.fields.values()
+    if type(field) is not Field:
+        refuse(b, "the unknown is a {} (a plain Field is needed: no multigrid decomposition)".format(type(field).__name__))
+    cshape = tuple(int(n) for n in domain.cshape)
+    if tuple(int(n) for n in field.array.shape) != cshape or field.loc != "c" * domain.ndim:
+        refuse(b, "the unknown is not a cell-centred field of the domain")
+    return dict(cshape=cshape, dtype=field.array.dtype, device=field.array.device,
+                spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
 
 
 def _evaluate(problem, state):
@@ -132,7 +147,7 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
                             lr=args.lr, lrs=lrs, epoch_start=args.epoch_start, **kwargs)
 
 
-def optimize_newton_ensemble(args, problems, states, callback=None):
+def optimize_newton_ensemble(args, problems, states, callback=None, linearize="batched", time_linearize=False):
     """Newton on B small Poisson problems AT ONCE: every epoch is ONE launch that runs the whole Newton step of all
     members, one workgroup per member (gmg.EnsembleGMG.newton_step: residual, nested-iteration start, V-cycles down to the
     tolerance, the convergence decision and the update, no host read-back in between).  Every member ends at the Newton
@@ -150,40 +165,42 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
     When not every member is that Poisson operator, ALL members take the route for variable-coefficient stencils
     (optinfo.route == "stencil", and `solver.method` says so): any operator of one plain cell-centred `Field` whose Jacobian
     is a (2 d + 1)-point stencil -- variable conductivities, reaction and nonlinear terms -- admitted by
-    `fused.newton_stencil_refusal`, same cshape, spacing, dtype and device.  Per epoch: every member is linearised
-    (`linearize_device`, `gmg.recognise_stencil`: B launches of the generated Jacobian kernel -- a batched one would be a
-    change of the generator), the coefficient arrays and f(u) go into packed buffers allocated once, the hierarchies of all
-    members are set up again in launches that do not grow with B (`gmg.EnsembleGMG.rebuild`: two per level, one for the
-    dense coarsest matrices; the pseudo-inverses on the host), ONE launch solves M_b d_b = f_b(u_b) for all members and one
-    forms u -= d.  A member whose Jacobian is no such stencil raises ValueError naming it at the first epoch, before any
+    `fused.newton_stencil_refusal`, same cshape, spacing, dtype and device.  Per epoch: all members are linearised by ONE
+    launch of the generated Jacobian kernel per group of members whose operators generate the same source
+    (`linearize_ensemble`: `k_jac_batch` writes f(u) and the coefficient arrays straight into packed buffers allocated once;
+    a member without a generated Jacobian, or whose reads share a stencil point, is linearised on its own), the hierarchies
+    of all members are set up again in launches that do not grow with B (`gmg.EnsembleGMG.rebuild`: two per level, one for
+    the dense coarsest matrices; the pseudo-inverses on the host), ONE launch solves M_b d_b = f_b(u_b) for all members and
+    one forms u -= d.  A member whose Jacobian is no such stencil raises ValueError naming it at the first epoch, before any
     member is updated; so do members whose hierarchies do not coarsen along the same axes.  There is NO fallback to the
     normal-equation routes when a member's cycles do not contract (`optimize_newton` has one): the member's status
     reports converged=False or stagnated, and the caller decides.
+
+    linearize (stencil route): "batched" is the above; "members" linearises member by member (`linearize_device`,
+    `gmg.recognise_stencil`, copies into the packed buffers: B launches of `k_jac`) -- the same iterates, cycle counts and
+    statuses bit for bit, kept as the reference of the tests and of timings.  time_linearize: device events around every
+    linearisation, read after the last epoch (optinfo.linearize_ms).
     Returns ([arrays of member b], optinfo); optinfo.cycles / .residuals: [B, epochs] cycles run and final residual norms;
-    optinfo.route: "poisson" or "stencil"."""
+    optinfo.route: "poisson" or "stencil"; optinfo.linearize_launches: [epochs] Jacobian launches made per step (zeros on
+    the Poisson route, which has no linearisation); optinfo.linearize_ms: [epochs] device time of the linearisations, None
+    unless time_linearize."""
     from . import fused
 
     linsolver = getattr(args, "linsolver", "direct")
     if linsolver not in ("direct", "multigrid"):
         raise ValueError("optimize_newton_ensemble: linsolver '{}' (the one-workgroup Newton solves serve 'direct' and "
                          "'multigrid')".format(linsolver))
+    if linearize not in ("batched", "members"):
+        raise ValueError("optimize_newton_ensemble: linearize '{}' ('batched' or 'members')".format(linearize))
     if getattr(args, "linsolver_damp", 0) or getattr(args, "linsolver_dampdiag", 0):
         raise ValueError("optimize_newton_ensemble: damping (linsolver_damp / linsolver_dampdiag) is not served: the cycles "
                          "solve M d = r, which has the solution of the normal equations only without it")
     refused = dict(poisson=None, stencil=None)  # per route the first (member, reason) it refuses while the other admits
 
     def describe(b, problem, state, refuse):
-        domain = problem.domain
-        (field,) = state.fields.values()
-        if type(field) is not Field:
-            refuse(b, "the unknown is a {} (a plain Field is needed: no multigrid decomposition)".format(type(field).__name__))
-        cshape = tuple(int(n) for n in domain.cshape)
-        if tuple(int(n) for n in field.array.shape) != cshape or field.loc != "c" * domain.ndim:
-            refuse(b, "the unknown is not a cell-centred field of the domain")
-        dtype = field.array.dtype
+        kind = _plain_field(b, problem, state, refuse)
+        cshape, dtype = kind["cshape"], kind["dtype"]
         npdt = np.float64 if dtype == torch.float64 else np.float32
-        kind = dict(cshape=cshape, dtype=dtype, device=field.array.device,
-                    spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
         # (which route runs is known only once the operators are probed: a member that neither admits is refused here, one
         # that a single route refuses once the route is known -- still before any state changes)
         reasons = dict(poisson=fused.newton_refusal(cshape, [npdt(v) ** 2 for v in kind["spacing"]], dtype),
@@ -208,24 +225,27 @@ def optimize_newton_ensemble(args, problems, states, callback=None):
         ev = evaluators[0]
         solver = gmg.EnsembleGMG(ev.cshape, ev.h2, ev.dtype, ev.device, len(evaluators))
         rhs = torch.stack([e.rhs.reshape(ev.cshape) for e in evaluators])
-        step = lambda u, first, tol, maxcycles: solver.newton_step(u, rhs, tol=tol, maxcycles=maxcycles)
+
+        def step(u, first, tol, maxcycles):  # (no linearisation: nothing to report)
+            solver.newton_step(u, rhs, tol=tol, maxcycles=maxcycles)
     else:
-        solver, step = _stencil_route(args, problems, states, kind)
+        solver, step = _stencil_route(args, problems, states, kind, linearize, time_linearize)
     return _newton_loop(args, problems, states, callback, linsolver, kind["dtype"], route, solver, step)
 
 
-def _stencil_route(args, problems, states, kind):
+def _stencil_route(args, problems, states, kind, linearize="batched", timed=False):
     """(solver, step) of the route for members that are not all the Poisson operator (the docstring of
     `optimize_newton_ensemble`); the members have passed its checks, `kind` is what they share.  Linearises once here,
-    before any state changes: a member that has no stencil Jacobian is named first.  Without an epoch to run, no solver."""
+    before any state changes: a member that has no stencil Jacobian is named first.  Without an epoch to run, no solver.
+    step returns (Jacobian launches made, the pair of events around the linearisation or None)."""
     nb, cshape, dtype, device = len(problems), kind["cshape"], kind["dtype"], kind["device"]
     ndim = len(cshape)
     stage = torch.empty((nb, 2 * ndim + 1) + cshape, dtype=dtype, device=device)  # (the Jacobians of the first step)
     r = torch.empty((nb,) + cshape, dtype=dtype, device=device)
     d = torch.zeros_like(r)
 
-    def linearise(target):
-        """r[b] = f_b(u_b) and target[b] = the coefficient arrays of member b's Jacobian, for every member."""
+    def members(target):
+        """r[b] = f_b(u_b) and target[b] = the coefficient arrays of member b's Jacobian, member by member."""
         for b, (problem, state) in enumerate(zip(problems, states)):
             vector, matrix = problem.linearize_device(state)
             coeffs = gmg.recognise_stencil(matrix)
@@ -234,27 +254,194 @@ def _stencil_route(args, problems, states, kind):
                                  "cell-centred plain Field".format(b))
             target[b].copy_(coeffs)
             r[b].view(-1).copy_(vector.reshape(-1))
+        return nb
 
-    solver = None
+    batched = None
+
+    def linearise(target):
+        nonlocal batched
+        events = None
+        if timed:
+            events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            events[0].record()
+        if linearize == "members":
+            launches = members(target)
+        else:
+            if batched is None:  # (the members' plan: traced once per list of problems, kept with them)
+                batched = _held_linearizer(problems, states, kind, "optimize_newton_ensemble")
+            launches = batched(states, coeffs=target, values=r)[2].launches
+        if timed:
+            events[1].record()
+        return launches, events
+
+    solver, first = None, None
     if args.epochs > args.epoch_start:
-        linearise(stage)
+        first = linearise(stage)
         solver = gmg.EnsembleGMG.from_coeffs(stage)
     del stage
 
-    def step(u, first, tol, maxcycles):
-        if not first:
-            linearise(solver.fine)
+    def step(u, is_first, tol, maxcycles):
+        made = first
+        if not is_first:
+            made = linearise(solver.fine)
             solver.rebuild()
         solver.solve(r, d, tol=tol, maxcycles=maxcycles, start=2)  # M_b d_b = r_b, the convention of optimize_newton
         ops.axpy(u.view(-1), d.view(-1), -1.0)                     # u -= d for all members
+        return made
 
     return solver, step
+
+
+def _jacobians_generated(device):
+    """Whether `Problem.eval_operator_grad` takes the generated Jacobian kernel (its own condition) for members on `device`."""
+    from . import runtime
+
+    return bool(runtime.enable_trace and int(os.environ.get("ODIL_TRACE_JAC", 1)) and torch.cuda.is_available()
+                and device.type == "cuda")
+
+
+def _stencil_member(b, problem, state, refuse):
+    """`describe` of `_check_members` for members of the stencil route alone."""
+    from . import fused
+
+    kind = _plain_field(b, problem, state, refuse)
+    reason = fused.newton_stencil_refusal(kind["cshape"], kind["dtype"])
+    if reason is not None:
+        refuse(b, reason)
+    return kind
+
+
+class EnsembleLinearizer:
+    """The linearisation of B members of the stencil route, planned once: which members share a launch, where every
+    array of the generated Jacobian kernel goes.  Members are traced with the batched form of the Jacobian kernel
+    (`stencil_jit.trace_jacobian(batch=True)`); those whose generated sources are equal load one library and are linearised
+    by ONE launch of its `k_jac_batch` (stencil_bind.JacobianBatch), which writes f(u) into values[b] and d f / d read into
+    the slot of coeffs[b] that `gmg.stencil_slot_plan` names -- no intermediate buffer, no copy.  Members without a
+    generated Jacobian (ODIL_TRACE_JAC=0, an operator the generator refuses) or whose reads land twice in one slot go
+    through `linearize_device` and `gmg.recognise_stencil` on their own (`single`: {member: reason})."""
+
+    def __init__(self, problems, states, who="linearize_ensemble", kind=None):
+        """kind: what `_check_members` returned for these members when the caller has checked them already."""
+        def refuse(member, reason):
+            raise ValueError("{}: member {}: {}".format(who, member, reason))
+
+        if kind is None:
+            kind, refuse = _check_members(who, problems, states, _stencil_member)
+        self.who, self.kind, self.problems, self.nb = who, kind, list(problems), len(problems)
+        self._plan(states, refuse)
+
+    def _plan(self, states, refuse):
+        from . import stencil_jit
+        from .stencil_bind import JacobianBatch
+
+        cshape = self.kind["cshape"]
+        self.traced, self.plans, self.single = [None] * self.nb, [None] * self.nb, dict()
+        self.generated = _jacobians_generated(self.kind["device"])
+        for b, (problem, state) in enumerate(zip(self.problems, states)):
+            if not self.generated:
+                self.single[b] = "no generated Jacobian kernel (tracing or ODIL_TRACE_JAC switched off, or no device)"
+                continue
+            if any(getattr(type(problem), name, None) is not getattr(Problem, name) for name in ("linearize_device", "eval_operator_grad")):
+                self.single[b] = "no generated Jacobian kernel: the member linearises itself (its own `linearize_device`)"
+                continue
+            traced = stencil_jit.trace_jacobian(problem, state, batch=True)
+            if traced is None:
+                self.single[b] = "no generated Jacobian kernel for its operator"
+                continue
+            try:
+                plan = gmg.stencil_slot_plan(traced.cg.jac_items, traced.G, {k: f.loc for k, f in state.fields.items()})
+                if tuple(traced.G) != cshape:
+                    raise ValueError("its residual lives on a grid {}".format(tuple(traced.G)))
+            except ValueError as e:
+                refuse(b, "its Jacobian is not a (2 d + 1)-point stencil of one cell-centred plain Field ({})".format(e))
+            if plan.single is not None:
+                self.single[b] = plan.single
+                continue
+            self.traced[b], self.plans[b] = traced, plan
+        by_lib = dict()
+        for b, traced in enumerate(self.traced):
+            if traced is not None:
+                by_lib.setdefault(traced.lib_path, []).append(b)
+        self.groups = list(by_lib.values())
+        self.batches = [JacobianBatch([self.traced[b] for b in group]) for group in self.groups]
+        self._tables = None  # ((address and strides of the buffers), per group the pointer table of its launch)
+        # slots that no read of a member writes: zero arrays, filled in one launch per slot for all members that miss it
+        self.missing = []
+        for slot in range(2 * len(cshape) + 1):
+            who = [b for b, plan in enumerate(self.plans) if plan is not None and slot in plan.missing]
+            if who:
+                self.missing.append((slot, slice(None) if len(who) == self.nb else torch.tensor(who, device=self.kind["device"])))
+
+    def __call__(self, states, coeffs=None, values=None):
+        """(values [B, *cshape], coeffs [B, 2 d + 1, *cshape], info) at `states`; coeffs / values: the buffers to write
+        (each member's arrays contiguous; e.g. `gmg.EnsembleGMG.fine`), allocated when None.  Slots that no read of a
+        member writes are zero-filled, one launch per such slot (the kernel never touches them; on every call: a buffer
+        the caller has rewritten cannot be told from the one filled before).
+        info.launches: Jacobian launches made, info.groups: the members of each shared launch, info.single: [(member,
+        reason)] linearised on their own."""
+        kind, nb = self.kind, self.nb
+        cshape, ndim = kind["cshape"], len(kind["cshape"])
+        if len(states) != nb:
+            raise ValueError("{}: {} problems with {} states".format(self.who, nb, len(states)))
+        if coeffs is None:
+            coeffs = torch.empty((nb, 2 * ndim + 1) + cshape, dtype=kind["dtype"], device=kind["device"])
+        if values is None:
+            values = torch.empty((nb,) + cshape, dtype=kind["dtype"], device=kind["device"])
+        for name, t, want in (("coeffs", coeffs, (nb, 2 * ndim + 1) + cshape), ("values", values, (nb,) + cshape)):
+            if tuple(t.shape) != want or t.dtype != kind["dtype"] or t.device != kind["device"]:
+                raise ValueError("{}: `{}` is not a {} tensor of shape {} on {}".format(self.who, name, kind["dtype"], want,
+                                                                                     kind["device"]))
+        for slot, who in self.missing:
+            coeffs[who, slot] = 0
+        ident = tuple((t.data_ptr(), tuple(t.stride())) for t in (coeffs, values))
+        if self._tables is None or self._tables[0] != ident:  # (the pointers of these buffers: once, not B (2 d + 2) views per call)
+            self._tables = (ident, [batch.pointer_table(
+                [[values[b] if slot is None else coeffs[b, slot] for slot in self.plans[b].slots] for b in group])
+                for group, batch in zip(self.groups, self.batches)])
+        for group, batch, table in zip(self.groups, self.batches, self._tables[1]):
+            batch.launch([states[b] for b in group], table)
+        for b in sorted(self.single):
+            vector, matrix = self.problems[b].linearize_device(states[b])
+            found = gmg.recognise_stencil(matrix)
+            if found is None or tuple(found.shape[1:]) != cshape:
+                raise ValueError("{}: member {}: its Jacobian is not a (2 d + 1)-point stencil of one cell-centred plain "
+                                 "Field".format(self.who, b))
+            coeffs[b].copy_(found)
+            values[b].view(-1).copy_(vector.reshape(-1))
+        info = argparse.Namespace(launches=len(self.groups) + len(self.single), groups=[list(g) for g in self.groups],
+                                  single=[(b, self.single[b]) for b in sorted(self.single)])
+        return values, coeffs, info
+
+
+def linearize_ensemble(problems, states, coeffs=None, values=None):
+    """f_b(u_b) and the Jacobian's coefficient arrays of B members of the stencil route of `optimize_newton_ensemble`, all
+    members whose operators generate the same kernels in ONE launch: (values [B, *cshape], coeffs [B, 2 d + 1, *cshape] in
+    the layout of `gmg.stencil_coefficients`, info) -- `EnsembleLinearizer`, which this makes on the first call for a list
+    of problems and reuses afterwards (kept on problems[0]; traced operators that no longer match the states are traced
+    again).  Members are checked as the driver checks them (`fused.newton_stencil_refusal`: one plain cell-centred `Field`,
+    same cshape, spacing, dtype and device); a refusal is a ValueError naming the first offending member, before any
+    operator is traced."""
+    kind, _ = _check_members("linearize_ensemble", problems, states, _stencil_member)
+    return _held_linearizer(problems, states, kind, "linearize_ensemble")(states, coeffs=coeffs, values=values)
+
+
+def _held_linearizer(problems, states, kind, who):
+    """The `EnsembleLinearizer` of these (checked) members: the one kept on problems[0] when it was planned for the same
+    problem objects, the same kind and states its traced operators still match, else a new one."""
+    held = getattr(problems[0], "_ensemble_linearizer", None)
+    if not (held is not None and held.kind == kind and held.generated == _jacobians_generated(kind["device"])
+            and len(held.problems) == len(problems) and all(p is q for p, q in zip(held.problems, problems))
+            and all(t is None or t.matches(state) for t, state in zip(held.traced, states))):
+        held = problems[0]._ensemble_linearizer = EnsembleLinearizer(problems, states, who=who, kind=kind)
+    held.who = who
+    return held
 
 
 def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solver, step):
     """What the Newton routes share.  route: "poisson" / "stencil"; solver: its gmg.EnsembleGMG (None only when no epoch
     runs); step(u, first, tol, maxcycles) advances the packed iterate u [B, *cshape] by one Newton step of every member
-    (first: at args.epoch_start) and leaves solver.outcome / status(b) behind."""
+    (first: at args.epoch_start) and leaves solver.outcome / status(b) behind; it returns None or (Jacobian launches it
+    made, None or the pair of timing events around its linearisation)."""
     from . import linsolver as ls
 
     nb = len(problems)
@@ -276,14 +463,18 @@ def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solv
     nepochs = max(args.epochs - args.epoch_start, 0)
     cycles = np.zeros((nb, nepochs), dtype=np.int64)
     residuals = np.zeros((nb, nepochs))
+    launches, events = np.zeros(nepochs, dtype=np.int64), []
     next_active = getattr(callback, "next_active", None) if callback else None
     due = None
     if callback:
         report(args.epoch_start, False)
         due = next_active(args.epoch_start) if next_active else args.epoch_start + 1
     for epoch in range(args.epoch_start, args.epochs):
-        step(u, epoch == args.epoch_start, tol, maxcycles)
+        made = step(u, epoch == args.epoch_start, tol, maxcycles)
         k = epoch - args.epoch_start
+        if made is not None:
+            launches[k] = made[0]
+            events.append(made[1])
         cycles[:, k] = solver.outcome[:, 0]
         residuals[:, k] = [solver.status(b)["residual"] for b in range(nb)]
         if getattr(args, "linsolver_verbose", 0):
@@ -292,5 +483,9 @@ def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solv
             report(epoch + 1, True)
             due = next_active(epoch + 1) if next_active else epoch + 2
     arrays = [problem.domain.arrays_from_state(state) for problem, state in zip(problems, states)]
+    linearize_ms = None
+    if events and all(pair is not None for pair in events):
+        torch.cuda.synchronize()
+        linearize_ms = np.array([pair[0].elapsed_time(pair[1]) for pair in events])
     return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver,
-                                      route=route)
+                                      route=route, linearize_launches=launches, linearize_ms=linearize_ms)

@@ -16,6 +16,7 @@ latter is solved here by V-cycles built only from the HIP kernels of the hot pat
 Convergence is checked on the true residual with the deterministic dot products.
 """
 
+import collections
 import math
 
 import ctypes
@@ -928,6 +929,53 @@ def stencil_coefficients(items, shape, period=None, dtype=None, device=None):
             coeffs[slot].view(-1).copy_(coeff.reshape(-1))
             seen.add(slot)
     return coeffs
+
+
+SlotPlan = collections.namedtuple("SlotPlan", "slots missing single")
+
+
+def stencil_slot_plan(jac_items, shape, fields=None):
+    """Where the arrays of a generated Jacobian kernel (`_Codegen.jac_items`: (output, None) for the value of an output,
+    (output, (key, shift, loc, frozen)) for d output / d read) go in the layout of `stencil_coefficients`, decided on the
+    host once: SlotPlan(slots, missing, single).  slots[j]: None for the value (it goes to the residual array), else the
+    slot 0, -e_0, +e_0, -e_1, ... of [2 d + 1, *shape]; missing: the slots no item writes (zero arrays); single: None when
+    the items land in distinct slots -- the kernel may then write straight into the packed arrays -- else the reason why
+    the arrays must pass through `stencil_coefficients` (duplicate normalised shifts are summed there).
+    The checks are those of `recognise_stencil`, and what it answers with None raises ValueError here: one output, one
+    plain cell-centred field (fields: {key: location} of the state's fields, when known), d <= 3, extents >= 4, every shift
+    0 or a unit vector modulo the extents, the centre present."""
+    shape = tuple(int(n) for n in shape)
+    ndim = len(shape)
+    if fields is not None and (len(fields) != 1 or next(iter(fields.values())) != "c" * ndim):
+        raise ValueError("not one cell-centred field: {}".format(dict(fields)))
+    if ndim > 3 or any(n < 4 for n in shape):
+        raise ValueError("grid {}: at most three dimensions, extents of at least 4".format(shape))
+    if {k for k, _ in jac_items} != {0} or sum(attr is None for _, attr in jac_items) != 1:
+        raise ValueError("{} outputs (one residual array is needed)".format(len({k for k, _ in jac_items})))
+    want = [(0,) * ndim]
+    for i in range(ndim):
+        want += [tuple(-1 if j == i else 0 for j in range(ndim)), tuple(1 if j == i else 0 for j in range(ndim))]
+    slots, keys = [], set()
+    for _, attr in jac_items:
+        if attr is None:
+            slots.append(None)
+            continue
+        key, shift, loc = attr[:3]
+        keys.add(key)
+        norm = tuple(((int(s) + n // 2) % n) - n // 2 for s, n in zip(shift, shape))
+        if loc != "c" * ndim or len(shift) != ndim or norm not in want:
+            raise ValueError("the read of '{}' at shift {} ({}) is not a point of the (2 d + 1)-point stencil".format(
+                key, tuple(shift), loc))
+        slots.append(want.index(norm))
+    if len(keys) != 1 or 0 not in slots:
+        raise ValueError("no derivative with respect to the cell itself" if len(keys) == 1 else
+                         "derivatives with respect to {} fields".format(len(keys)))
+    used = [s for s in slots if s is not None]
+    single = None
+    if len(set(used)) != len(used):
+        twice = next(s for s in used if used.count(s) > 1)
+        single = "{} reads at the normalised shift {}: their coefficient arrays are summed".format(used.count(twice), want[twice])
+    return SlotPlan(slots, [s for s in range(len(want)) if s not in used], single)
 
 
 def recognise_stencil(op):

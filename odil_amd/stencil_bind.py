@@ -8,6 +8,7 @@ The argument blocks (`struct Args`, `struct ParArgs`) are described once, by the
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import ops, param_expr
@@ -19,7 +20,8 @@ _PP = ctypes.POINTER(ctypes.c_void_p)
 _ADAM = [_P] * 3 + [ctypes.c_double] * 4 + [_P]  # x, m, v, alpha, 1 - beta_1, 1 - beta_2, eps, alpha on the device
 _ARGTYPES = dict(  # (launchers of stencil_codegen._launchers; all end with the stream)
     jit_fwd=[_P, _P], jit_gather=[ctypes.c_int, _P, _P, _P], jit_gather_adam=[ctypes.c_int, _P, _P] + _ADAM + [_P],
-    jit_gather_all=[_P] + [_PP] * 4 + _ADAM[3:] + [_P], jit_jac=[_P, _PP, _P], jit_par=[_P, _P, _P])
+    jit_gather_all=[_P] + [_PP] * 4 + _ADAM[3:] + [_P], jit_jac=[_P, _PP, _P], jit_jac_batch=[_P, _P, ctypes.c_int, _P],
+    jit_par=[_P, _P, _P])
 
 
 def field_ranges(domain, state):
@@ -178,3 +180,73 @@ class StencilBinding:
                 raise RuntimeError("parameter arrays must be contiguous {} tensors".format(self.dtype))
             self.par_args.val[s_], self.par_args.grad[s_] = val.data_ptr(), grad.data_ptr()
         self._launch("jit_par", ctypes.byref(self.args), ctypes.byref(self.par_args))
+
+
+class JacobianBatch:
+    """ONE launch of `k_jac_batch` for members of an ensemble whose operators generated the same source (so
+    `jit_cache._compile` handed them the same library): every member keeps its own trace, argument block and host scalars,
+    only the launch is shared.  The launch reads the members' argument blocks and output pointers from DEVICE memory: per
+    call they are gathered from the members' ctypes structs into pinned host memory and copied on the current stream.
+
+    Two linearisations may be queued back to back without a synchronise (the hazard `TracedOperator.graph_upload`
+    describes for host scalars): the staging is a ring of `depth` slots, each a pinned block, a device block and an event
+    recorded behind the launch that read it.  A slot is refilled only after its event has completed, so neither the
+    pending copy nor a queued launch ever sees a block the host has since rewritten; with all slots in flight the host
+    waits for the oldest."""
+
+    depth = 4
+
+    def __init__(self, members):
+        """members: the `TracedOperator`s (generated with jac="batch") of one group, in the order of the launch."""
+        first = members[0]
+        if any(m.lib_path != first.lib_path for m in members):
+            raise ValueError("JacobianBatch: members of one launch share one generated library")
+        if not hasattr(first.lib, "jit_jac_batch"):
+            raise RuntimeError("these kernels were generated without the batched Jacobian kernel (jac=\"batch\")")
+        self.members, self.lib = list(members), first.lib
+        self.nitems = len(first.cg.jac_items)
+        self.asize = ctypes.sizeof(first.args)
+        nb = len(members)
+        self.abytes = nb * self.asize  # (a multiple of 8: the block holds pointers)
+        nbytes = self.abytes + nb * self.nitems * ctypes.sizeof(_P)
+        device = first.out.device
+        self.slots = [dict(host=torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+                           dev=torch.empty(nbytes, dtype=torch.uint8, device=device), done=None) for _ in range(self.depth)]
+        self.next = 0
+
+    def pointer_table(self, outputs):
+        """The members' output pointers as the launch wants them ([B, items] addresses), from outputs[b][j], the contiguous
+        array item j of member b goes to: made once per set of buffers, `launch` copies the bytes."""
+        table = np.empty((len(self.members), self.nitems), dtype=np.uint64)
+        for b, (member, outs) in enumerate(zip(self.members, outputs)):
+            assert len(outs) == self.nitems
+            for j, t in enumerate(outs):
+                if not t.is_contiguous() or t.dtype != member.dtype or tuple(t.shape) != tuple(member.G) or not t.is_cuda:
+                    raise RuntimeError("JacobianBatch: outputs are contiguous {} arrays of shape {} on the device".format(
+                        member.dtype, tuple(member.G)))
+                table[b, j] = t.data_ptr()
+        return table
+
+    def launch(self, states, table):
+        """k_jac_batch for `states` (one per member) into the arrays of `table` (`pointer_table`; the caller keeps them
+        alive)."""
+        slot = self.slots[self.next]
+        self.next = (self.next + 1) % self.depth
+        if slot["done"] is not None:
+            slot["done"].synchronize()  # (the launch that read this slot has run: its blocks may be rewritten)
+        base = slot["host"].data_ptr()
+        keep = []
+        for b, (member, state) in enumerate(zip(self.members, states)):
+            keep.append(member.bind_fields(state))
+            ctypes.memmove(base + b * self.asize, ctypes.addressof(member.args), self.asize)
+        assert table.shape == (len(self.members), self.nitems) and table.dtype == np.uint64 and table.flags.c_contiguous
+        ctypes.memmove(base + self.abytes, table.ctypes.data, table.nbytes)
+        slot["dev"].copy_(slot["host"], non_blocking=True)
+        dev = slot["dev"].data_ptr()
+        rc = self.lib.jit_jac_batch(dev, dev + self.abytes, len(self.members), ops.stream_ptr())
+        if rc != 0:
+            raise RuntimeError("generated kernel launch failed (jit_jac_batch): hip error {}".format(rc))
+        if slot["done"] is None:
+            slot["done"] = torch.cuda.Event()
+        slot["done"].record()
+        del keep

@@ -238,7 +238,8 @@ class _Codegen(_MarchKernels, _GatherKernels):
             "cots", "cut_nodes", "jac_store", "pg_decl", "pg_offset", "pgrads", "pg2_used"))
 
     def __init__(self, tr, outputs, raw, shape, state, slab=None, jac=False):
-        """jac: also emit `k_jac`, the Jacobian coefficient arrays (`_jacobian_kernel`).
+        """jac: also emit `k_jac`, the Jacobian coefficient arrays (`_jacobian_kernel`); "batch": and `k_jac_batch`, the
+        same body for the members of an ensemble in one launch (a library of its own: what True emits does not change).
         slab = (axis, n): the kernels of ONE RANK of a slab decomposition along grid axis `axis` (n owned
         cells of it per rank; odil_amd/slab_traced.py).  Threads then cover the owned cells only; the index of
         that axis seen by index leaves, constant arrays and windows is the GLOBAL one (i + a.off); sources are
@@ -271,7 +272,9 @@ class _Codegen(_MarchKernels, _GatherKernels):
                         largest = max(largest, int(t.numel()))
         if largest >= 2**31 - 1024:
             raise TraceUnsupported("grid too large for 32-bit indexing")
-        self.want_jac = bool(jac)
+        self.want_jac, self.jac_batch = bool(jac), jac == "batch"
+        if self.jac_batch and slab is not None:
+            raise TraceUnsupported("batched Jacobian kernel of a slab rank")
         self.par_outputs, self.par_numel, self.par_keys = None, dict(), dict()  # (parameter_outputs)
         # what source() leaves for the host: defined from the start, empty until then
         self.ncot, self.par_arrays, self.edge_numel, self.gathers_done = 0, 0, 0, False
@@ -1747,6 +1750,14 @@ class _Codegen(_MarchKernels, _GatherKernels):
             S.append("  for (int k = 0; k < {}; ++k) jp.p[k] = (T*)ptrs[k];".format(len(self.jac_items)))
             S.append("  const AdamP ad = {nullptr, nullptr, nullptr, (T)0, (T)0, (T)0, (T)0, nullptr};")
             S.append("  hipLaunchKernelGGL(k_jac, dim3({}), dim3(NB), 0, (hipStream_t)stream, *a, jp, ad);".format(self.jac_blocks))
+            S.append("  return (int)hipGetLastError();")
+            S.append("}")
+        if self.jac_items and self.jac_batch:
+            # args_dev: `nmembers` argument blocks back to back, ptrs_dev: their JacP, both in DEVICE memory
+            S.append('extern "C" int jit_jac_batch(const void* args_dev, const void* ptrs_dev, int nmembers, void* stream) {')
+            S.append("  if (nmembers < 1 || nmembers > 65535) return -1;")
+            S.append("  hipLaunchKernelGGL(k_jac_batch, dim3({}, nmembers), dim3(NB), 0, (hipStream_t)stream, (const Args*)args_dev, "
+                     "(const JacP*)ptrs_dev);".format(self.jac_blocks))
             S.append("  return (int)hipGetLastError();")
             S.append("}")
         # the argument block: sized last (the gradient expressions add host scalars of their own)

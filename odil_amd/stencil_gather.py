@@ -1,6 +1,7 @@
 """The gathers of stencil_codegen.py: from the adjoints `k_fwd` stored to the gradient of every field (`k_gat_*`, one
 launch per field or `k_gat_all` for all of them), with the optimizer's update by the lane that forms the gradient, and the
-Jacobian coefficient arrays `k_jac`, which is a kernel of the same form.  (The gathers of a marching kernel: stencil_march.py.)
+Jacobian coefficient arrays `k_jac`, which is a kernel of the same form, with `k_jac_batch`, its body for the members of an
+ensemble in one launch.  (The gathers of a marching kernel: stencil_march.py.)
 """
 
 import numpy as np
@@ -338,5 +339,25 @@ class _GatherKernels:
             raise TraceUnsupported("Jacobian kernel: {} arrays".format(len(items)))
         self.jac_exprs = [expr for _, expr in items]  # (what the kernel evaluates for jac_items[j]: tests/test_jacobian_kernel_host.py)
         S.append("struct JacP {{ T* p[{}]; }};".format(len(items)))
+        first = len(S)
         self.jac_blocks = self._gather_kernel(S, "k_jac", items, "const JacP jp, const AdamP ad", lambda k: "jp.p[{}]".format(k),
                                               lambda k: "ad", owned=self.slab is not None)
+        if self.jac_batch:
+            self._jacobian_batch_kernel(S, S[first + 1:])
+
+    def _jacobian_batch_kernel(self, S, body):
+        """`k_jac_batch`: the body of `k_jac` (its lines as emitted, after the signature) for the B members of an ensemble
+        whose operators gave this same source, on a grid (jac_blocks, B): workgroup (x, b) is workgroup x of member b's
+        `k_jac`.  Every member has its own argument block and output pointers, in DEVICE memory (`ab[b]`, `jb[b]`:
+        stencil_bind.JacobianBatch).  blockIdx.y is uniform over the workgroup and the blocks are not written while the
+        kernel runs: they are read through the constant address space, i.e. by scalar loads of the members the body uses
+        (no per-lane copy of the struct, no scratch), as `k_jac` reads its kernel arguments.  The XCD regrouping of
+        `_block_index` reads gridDim.x / blockIdx.x only: every member keeps the schedule of its single launch."""
+        S.append("typedef const __attribute__((address_space(4))) Args ArgsC;")
+        S.append("typedef const __attribute__((address_space(4))) JacP JacPC;")
+        S.append('extern "C" __global__ __launch_bounds__(NB) void k_jac_batch(const Args* __restrict__ ab, '
+                 'const JacP* __restrict__ jb) {')
+        S.append("  ArgsC& a = *(ArgsC*)(ab + blockIdx.y);")
+        S.append("  JacPC& jp = *(JacPC*)(jb + blockIdx.y);")
+        S.append("  const AdamP ad = {nullptr, nullptr, nullptr, (T)0, (T)0, (T)0, (T)0, nullptr};")
+        S.extend(body)

@@ -123,7 +123,7 @@ class TracedOperator(StencilBinding):
 
     def __init__(self, problem, state, only=None, jac=False):
         """jac: also generate `k_jac`, the Jacobian coefficient arrays of `Problem.eval_operator_grad` (a library of its own:
-        the Newton driver asks for it, the gradient optimizers never pay for it)."""
+        the Newton driver asks for it, the gradient optimizers never pay for it); "batch": and `k_jac_batch` (`_Codegen`)."""
         from .core import Field, MultigridField
         from .util import printlog
 
@@ -299,6 +299,31 @@ class TracedOperator(StencilBinding):
                 raise RuntimeError("Array unknown '{}' must be a contiguous {} tensor".format(key, self.tr.torch_dtype))
             self.args.par[i] = arr.data_ptr()
             i += 1
+        return keep
+
+    def bind_fields(self, state):
+        """`_bind` for the shared launches of an ensemble (stencil_bind.JacobianBatch: B calls per Newton step, all host
+        time).  Where every source is the contiguous array of a plain `Field`, the kernels read no parameter arrays and no
+        graph is being replayed, binding is the pointers and the host scalars: no synthesis, no streams to join.  Anything
+        else goes through `_bind`."""
+        from .core import Field
+
+        cg, dt = self.cg, self.tr.torch_dtype
+        if cg.nets or cg.arrays or self._hs_rows is not None:
+            return self._bind(state)
+        if self._signature(state) != self.signature:
+            raise RuntimeError("state structure changed since the operator was traced")
+        keep = []
+        for key in cg.src_keys:
+            field = state.fields[key]
+            if type(field) is not Field or not field.array.is_contiguous() or field.array.dtype != dt or not field.array.is_cuda:
+                return self._bind(state)
+            keep.append(field.array)
+        for i, u in enumerate(keep):
+            self.args.src[i] = u.data_ptr()
+        self.args.hs = None
+        if cg.hs:
+            self.refresh_host_scalars()
         return keep
 
     def eval_loss_grad_adam(self, state, m, v, alpha, omb1, omb2, eps):
@@ -526,16 +551,17 @@ class TracedGroups:
         return loss, list(self.gviews), terms, self.names, norms
 
 
-def trace_jacobian(problem, state):
+def trace_jacobian(problem, state, batch=False):
     """A TracedOperator with the Jacobian kernel for `Problem.eval_operator_grad`, or None (reason logged) when the operator
-    has no pointwise form or its Jacobian needs dense columns / windows (the autograd route then stays)."""
+    has no pointwise form or its Jacobian needs dense columns / windows (the autograd route then stays).  batch: with the
+    batched form `k_jac_batch` as well (a library of its own, for `ensemble.linearize_ensemble`)."""
     from .core import Field
     from .util import printlog
 
     if not all(isinstance(f, Field) for f in state.fields.values()):
         return None  # (`linearize` takes plain fields; parameter arrays mean dense Jacobian columns)
     try:
-        return TracedOperator(problem, state, jac=True)
+        return TracedOperator(problem, state, jac="batch" if batch else True)
     except TraceUnsupported as e:
         printlog("odil_amd: Jacobian not generated ({}); eval_operator_grad uses autograd".format(e))
     except FileNotFoundError as e:

@@ -471,4 +471,4 @@ def optimize(args, optname, problem, state, callback, **kwargs):
 
 # B problems side by side: the drivers live in ensemble.py (no counterpart in the reference) and keep their names here.
 # (at the end: ensemble.py uses this module's printlog and _pinfo)
-from .ensemble import optimize_ensemble, optimize_newton_ensemble  # noqa: E402, F401
+from .ensemble import linearize_ensemble, optimize_ensemble, optimize_newton_ensemble  # noqa: E402, F401

@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 for sub in ("poisson", "heat", "velocity_from_tracer", "wave", "heat_tmax", "infer_constant", "basic", "diffusion"):
     sys.path.insert(0, os.path.join(ROOT, "examples", sub))
 
-CONFIGS = [  # (example module, argv, slab: None or (axis, ranks)[, also emit k_jac])
+CONFIGS = [  # (example module, argv, slab: None or (axis, ranks)[, also emit k_jac: True, or "batch" for k_jac_batch as well])
     ("wave", ["--Nt", "8", "--Nx", "8"], None),                                                      # __graft_entry__.build()
     ("wave", ["--Nt", "8", "--Nx", "16"], None),                                                     # __graft_entry__.smoke()
     ("fields", [], None),                                                                            # one kernel set per field location
@@ -37,6 +37,7 @@ _HEAT = ["--Nt", "8", "--Nx", "16", "--infer_k", "1"]
 SMALL = [  # --all: seconds each
     ("wave", ["--Nt", "8", "--Nx", "8"], None, True),                                                # k_jac
     ("diffusion", ["--ndim", "3", "--N", "16"], (0, 2), True),                                       # k_jac of one slab rank
+    ("diffusion", ["--ndim", "2", "--N", "16"], None, "batch"),                                      # k_jac_batch (ensembles)
     ("heat", _HEAT + ["--kwreg", "0.3", "--kwregdecay", "100"], None),                               # k_par (param_expr)
     ("heat", _HEAT + ["--kwreg", "0.3", "--kwregdecay", "100"], (1, 2)),                             # ... of one slab rank
     ("heat_tmax", ["--Nt", "8", "--Nx", "16"], None),                                                # a one-point window, an Array
@@ -68,11 +69,11 @@ def main():
             n = problem.domain.cshape[slab[0]] // slab[1]
             path = slab_traced.HipSlabKernels(problem, state, slab[0], n, "cpu", jac=bool(jac)).lib_path
         elif jac:
-            path = stencil_jit.TracedOperator(problem, state, jac=True).lib_path
+            path = stencil_jit.TracedOperator(problem, state, jac=jac[0]).lib_path
         else:
             path = stencil_jit.trace(problem, state).lib_path
             path = path[0] if isinstance(path, list) else path
-        what = " ".join(argv) + ("" if slab is None else " [slab {}/{}]".format(*slab)) + (" [k_jac]" if jac else "")
+        what = " ".join(argv) + ("" if slab is None else " [slab {}/{}]".format(*slab)) + (" [k_jac{}]".format("_batch" if jac[0] == "batch" else "") if jac else "")
         print("{:12s} {:60s} {}  {:.1f} s".format(modname, what, os.path.basename(path), time.time() - t0), flush=True)
         del problem, state
     if not a.quick:
