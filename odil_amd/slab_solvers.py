@@ -723,22 +723,8 @@ class SlabTracedLbfgs:
 
     def __init__(self, run):
         self.run = run
-        own, rep = [], []
-        dev = run.device
-        for e in run.entries:
-            shapes = [lv.shape for lv in e["levels"]] if "levels" in e else e["shapes"]
-            pos = e["start"]
-            for k, shape in enumerate(shapes):
-                cnt = int(np.prod(shape)) if len(shape) else 1
-                index = torch.arange(pos, pos + cnt, dtype=torch.int64, device=dev).view(tuple(shape))
-                if "levels" in e and not e["levels"][k].replicated:
-                    own.append(e["levels"][k].owned(index).reshape(-1))
-                else:
-                    rep.append(index.reshape(-1))
-                pos += cnt
-        self.n_own = int(sum(t.numel() for t in own))
-        self.index = torch.cat(own + rep) if own or rep else torch.zeros(0, dtype=torch.int64, device=dev)
-        self.n = int(self.index.numel())
+        self.index = run.layout.local_index(run.device)
+        self.n_own, self.n = run.layout.n_owned, run.layout.n_unknowns_local
         self.nfev = 0
 
     def pack(self, flat, out=None):
@@ -755,9 +741,9 @@ class SlabTracedLbfgs:
         """This rank's share of the loss of the last evaluation (the ranks' shares add up to the loss)."""
         run = self.run
         part = run.kern.partial_terms().to(torch.float64).sum()
-        if getattr(run.kern, "par_outputs", None) is not None and hasattr(run.kern, "pout") and run.rank == 0:
-            for q in range(len(run.kern.par_outputs)):  # evaluated by every rank alike: counted once
-                part = part + run.kern.pout[2 * q].to(torch.float64)
+        for _, value in run.par_terms():  # (counted once: `SlabTracedAdam.par_terms`)
+            if value is not None:
+                part = part + value.to(torch.float64)
         return part
 
     def minimize(self, comm, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0, callback=None, vectors=None):
@@ -775,7 +761,7 @@ class SlabTracedLbfgs:
 
         res = lbfgsb_minimize(x, fg, vec, maxiter, m=m, maxls=maxls, pgtol=pgtol, factr=factr, callback=callback)
         self.unpack(x, run.x)
-        run._x_synced = False  # the ghost planes of the unknowns are refreshed by whoever evaluates next
+        run.unknowns_changed()
         return res
 
 
@@ -846,7 +832,7 @@ class SlabTracedNewton:
 
     def __init__(self, run, linsolver="multigrid", tol=1e-10, maxiter=None):
         self.run = run
-        if len(run.entries) != 1 or run.entries[0]["kind"] != "field" or run.axis != 0:
+        if len(run.entries) != 1 or run.entries[0].kind != "field" or run.axis != 0:
             raise NotImplementedError("Newton on the slab decomposition: one Field cut along axis 0")
         if not getattr(run.kern, "jac_items", None):
             raise RuntimeError("SlabTracedNewton needs slab kernels generated with their Jacobian kernel (jac=True)")
@@ -858,7 +844,7 @@ class SlabTracedNewton:
     def step(self, comm):
         run = self.run
         e = run.entries[0]
-        lv = e["levels"][0]
+        lv = e.levels[0]
         if not self._evaluated:  # (else the evaluation that ended the last step left u and the wrap planes of this state)
             drive(run.evaluate_gen(), comm)
         buf = run.kern.jacobian(run.u, *run.wrap_planes())
@@ -886,8 +872,8 @@ class SlabTracedNewton:
         if not cycles_accepted(st, bnorm=1.0):  # (the single-GPU rule; this status carries the RELATIVE residual)
             raise RuntimeError("Newton on the slab decomposition: multigrid stopped at relative residual {:.3e} after {} "
                                "cycles (tolerance {:.1e}); the step is not applied".format(st["residual"], st["niter"], self.tol))
-        hip_ops.axpy(lv.owned(e["x"][0]), d, -1.0)
-        run._x_synced = False
+        hip_ops.axpy(lv.owned(e.x[0]), d, -1.0)
+        run.unknowns_changed()
         drive(run.evaluate_gen(), comm)  # the loss of the new state, and the sources of the next step
         self._evaluated = True
         return self.status

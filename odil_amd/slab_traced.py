@@ -93,17 +93,196 @@ class _Level:
         hi = a.shape[self.axis] - (self.g_hi - 1 if self.g_hi else 0)
         return a.narrow(self.axis, lo, hi - lo)
 
-    def plane_desc(self, start, pos):
-        """(base, outer, ostride, inner) of the plane at owned-relative position `pos` inside the packed vector whose
-        entry `start` is this array's first element: `outer` runs of `inner` contiguous elements (ops.PlaneList)."""
+    def plane_desc(self, start, pos, count=1):
+        """(base, outer, ostride, inner) of the `count` planes from owned-relative position `pos` inside the packed vector
+        whose entry `start` is this array's first element: `outer` runs of `inner` contiguous elements (ops.PlaneList)."""
         outer = math.prod(self.shape[:self.axis])
         inner = self.plane // outer
-        return (start + (self.g_lo + pos) * inner, outer, self.shape[self.axis] * inner, inner)
+        return (start + (self.g_lo + pos) * inner, outer, self.shape[self.axis] * inner, inner * count)
+
+
+class _Entry:
+    """One unknown of the state in the packed vectors.  kind "mg" / "field": grid arrays, one `_Level` each in `levels`
+    (`loc`: the field's); kind "par": the arrays of a network / Array, whole on every rank (`levels` is empty).  `shapes`:
+    of its arrays as this rank stores them, one after the other from entry `start`.  `factors`: the multigrid factors
+    when one of them is not 1, else None.  `init`: the state's arrays (initial values; dropped once copied).  x, m, v, g, h:
+    one view per array of the run's packed vectors, attached by `SlabTracedAdam`."""
+
+    def __init__(self, key, kind, init, levels=(), loc=None, factors=None):
+        self.key, self.kind, self.init, self.levels, self.loc, self.factors = key, kind, list(init), list(levels), loc, factors
+        self.shapes = [lv.shape for lv in levels] if levels else [tuple(a.shape) for a in init]
+        self.start = None
+        self.x = self.m = self.v = self.g = self.h = ()
+
+    @property
+    def synthesised(self):
+        """Whether what the kernels read is u = w_0 + P(w_1 + ...), an array of its own, and not the unknown itself."""
+        return self.kind == "mg" and len(self.levels) > 1
+
+    def arrays(self):
+        """(first entry, size, shape, level or None) of each of its arrays."""
+        pos = self.start
+        for k, shape in enumerate(self.shapes):
+            yield pos, math.prod(shape), shape, self.levels[k] if self.levels else None
+            pos += math.prod(shape)
+
+
+class SlabLayout:
+    """Where one rank's unknowns live -- host arithmetic only: no device allocation, no kernels.
+
+    entries, by_key   the `_Entry` of every field of the state, in `Domain.arrays_from_state` order
+    total             length of a packed vector
+    rep               [(start, size)] of the replicated (agglomerated) level arrays
+    n_owned, n_unknowns_local   entries of the owned planes of the sharded arrays; those plus every entry the rank holds
+                      whole (replicated levels, parameters)
+    The plane descriptors (`_Level.plane_desc`; side "lo" / "hi", absent at an end of the decomposition), every list in the
+    order of the sharded level arrays in the packed vector:
+    x_send, x_recv    the unknowns' halo: the owned boundary plane of every array out, the inner ghost plane in
+    g_send, g_add     the gradients' halo-add, [0] the finest level of every field, [1] the coarser levels: per array the
+                      inner ghost plane THEN the owned boundary plane out; added to the owned boundary plane THEN the inner
+                      ghost plane (the second of each pair is the redundant update's, see SlabTracedAdam)."""
+
+    def __init__(self, domain, state, axis, rank, world):
+        from .core import Field, MultigridField
+
+        grid = {k: f for k, f in state.fields.items() if isinstance(f, (Field, MultigridField))}
+        if axis is None:
+            ok = [d for d in range(domain.ndim) if all(f.loc[d] == "c" for f in grid.values())]
+            if not ok:
+                raise ValueError("no axis on which every field is cell-centred")
+            axis = ok[0]
+        N = domain.cshape[axis]
+        if N % world:
+            raise ValueError("{} cells on axis {} over {} ranks".format(N, axis, world))
+        self.axis, self.rank, self.world, self.n = axis, rank, world, N // world
+        self.entries = [self._entry(domain, key, f) for key, f in state.fields.items()]
+        self.by_key = {e.key: e for e in self.entries}
+        self.total = 0
+        for e in self.entries:
+            e.start = self.total
+            self.total += sum(math.prod(s) for s in e.shapes)
+        arrays = [a for e in self.entries for a in e.arrays()]
+        # (first entry, level, whether it is the field's finest) of every array cut into slabs
+        self.sharded = [(pos, lv, k == 0) for e in self.entries for k, (pos, _, _, lv) in enumerate(e.arrays())
+                        if lv is not None and not lv.replicated]
+        self.rep = [(pos, cnt) for pos, cnt, _, lv in arrays if lv is not None and lv.replicated]
+        self.n_owned = sum(lv.n * lv.plane for _, lv, _ in self.sharded)
+        self.n_unknowns_local = self.n_owned + sum(cnt for _, cnt, _, lv in arrays if lv is None or lv.replicated)
+        self.global_cells = math.prod(domain.cshape)
+        self.local_cells = self.global_cells // world
+        self.x_send, self.x_recv = dict(), dict()
+        self.g_send, self.g_add = (dict(), dict()), (dict(), dict())
+        for side in ["lo"] * (rank > 0) + ["hi"] * (rank < world - 1):
+            # (finest?, owned boundary plane, inner ghost plane) of every sharded array at this side
+            pairs = [(top, lv.plane_desc(pos, 0 if side == "lo" else lv.n - 1),
+                      lv.plane_desc(pos, -1 if side == "lo" else lv.n)) for pos, lv, top in self.sharded]
+            self.x_send[side] = [own for _, own, _ in pairs]
+            self.x_recv[side] = [ghost for _, _, ghost in pairs]
+            # the same planes split by level for the gradients' halo-add: the finest levels (97 % of the bytes) travel WHILE
+            # the transposes run down the levels, the coarser ones after them.  The message carries what this rank's cells
+            # contribute to the neighbour's boundary plane (the ghost plane) and, for the redundant ghost updates, this
+            # rank's own boundary plane of the partial gradient, which completes the receiver's inner ghost plane
+            for k in (0, 1):
+                self.g_send[k][side] = [d for top, own, ghost in pairs if top == (k == 0) for d in (ghost, own)]
+                self.g_add[k][side] = [d for top, own, ghost in pairs if top == (k == 0) for d in (own, ghost)]
+
+    def _entry(self, domain, key, f):
+        """The entry of field `key`, or the reason why the decomposition cannot hold it."""
+        from .core import Array, Field, MultigridField, NeuralNet
+
+        axis, rank, world = self.axis, self.rank, self.world
+        N = domain.cshape[axis]
+        if isinstance(f, MultigridField):
+            factors = [float(x) for x in (f.factors or domain.mg_factors or [1] * len(f.terms))]
+            mgloc = domain._mg_loc(f)
+            if mgloc[axis] != "c":
+                raise ValueError("field '{}' is not refined / cell-centred on the sharded axis".format(key))
+            levels = [_Level(tuple(t.array.shape), axis, rank, world) for t in f.terms]
+            for l in range(len(levels) - 2, -1, -1):  # a rank's planes must be whole coarse cells at the transition
+                if levels[l + 1].replicated and not levels[l].replicated and levels[l].n % 2:
+                    levels[l] = _Level(tuple(f.terms[l].array.shape), axis, rank, world, replicate=True)
+            if levels[0].replicated or any(a.replicated and not b.replicated for a, b in zip(levels, levels[1:])):
+                raise ValueError("field '{}': {} cells on the sharded axis over {} ranks".format(key, N, world))
+            # u = f_0 w_0 + P(f_1 w_1 + P(...)) (reference core.py:245-263); None: every factor is 1
+            if len(levels) == 1 and factors[0] != 1.0:
+                raise NotImplementedError("slab decomposition of a one-level multigrid field with a factor")
+            return _Entry(key, "mg", [t.array for t in f.terms], levels, mgloc,
+                          None if all(x == 1.0 for x in factors) else factors)
+        if isinstance(f, Field):
+            if f.loc[axis] != "c":
+                raise ValueError("field '{}' is not cell-centred on the sharded axis".format(key))
+            levels = [_Level(tuple(f.array.shape), axis, rank, world)]
+            if levels[0].replicated:
+                raise ValueError("field '{}': {} cells on the sharded axis over {} ranks".format(key, N, world))
+            return _Entry(key, "field", [f.array], levels, f.loc)
+        if isinstance(f, (NeuralNet, Array)):
+            return _Entry(key, "par", domain.arrays_from_field(f))
+        raise TypeError(type(f).__name__)
+
+    def local_index(self, device=None):
+        """Indices into a packed vector of what `n_unknowns_local` counts: the owned planes of the sharded arrays (`n_owned`
+        entries), then what every rank holds whole."""
+        own, rep = [], [torch.zeros(0, dtype=torch.int64, device=device)]
+        for e in self.entries:
+            for pos, cnt, shape, lv in e.arrays():
+                index = torch.arange(pos, pos + cnt, dtype=torch.int64, device=device).view(shape)
+                if lv is not None and not lv.replicated:
+                    own.append(lv.owned(index).reshape(-1))
+                else:
+                    rep.append(index.reshape(-1))
+        return torch.cat(own + rep)
+
+
+def fused_update_plan(layout, keys, reread=()):
+    """The optimizer's update inside the gathers.  A gather completes the gradient of the owned planes 1 .. n - 2 of its
+    array (plane 0 / n - 1 wait for the neighbour's share or the periodic closure): the kernels that can, update those
+    entries where they form the gradient, and the launches at the end of the epoch cover the rest of the packed vector --
+    the two end pieces of every such array (strided when the sharded axis is not the leading one) and the ranges between
+    the arrays (coarser levels, fields without a gather, parameters).
+    keys: the fields whose gathers can update in place; reread: those whose own arrays the gathers read again.
+    -> (fused: key -> (first, last + 1) owned plane updated by the gather, post_flat: [(begin, end)] for `ops.adam_step`,
+    post_pieces: [(start, size, npieces, stride, offset, count)] for `ops.adam_step_pieces` on [start, start + size))."""
+    fused, post_flat, post_pieces, spans = dict(), [], [], []
+    for e in (layout.by_key[key] for key in keys):
+        lv = e.levels[0]
+        if lv.n < 4:
+            continue
+        if not e.synthesised and e.key in reread:
+            continue  # the array a gather reads IS the unknown: no launch of this epoch may update it
+        if e.factors:
+            continue  # the gather forms h_0, the gradient is f_0 h_0
+        fused[e.key] = (1, lv.n - 1)
+        spans.append((e.start, lv.size))
+        _, outer, stride, inner = lv.plane_desc(0, 0)
+        first, last = lv.g_lo + 1, lv.g_lo + lv.n - 1  # planes [0, first) and [last, extent) of the array
+        post_pieces.append((e.start, lv.size, outer, stride, 0, first * inner))
+        post_pieces.append((e.start, lv.size, outer, stride, last * inner, (lv.shape[lv.axis] - last) * inner))
+    at = 0
+    for start, size in sorted(spans):
+        if start > at:
+            post_flat.append((at, start))
+        at = start + size
+    if at < layout.total:
+        post_flat.append((at, layout.total))
+    return fused, post_flat, post_pieces
 
 
 class HipSlabKernels(StencilBinding):
     """The generated kernels of one rank (stencil_codegen in slab mode) and their buffers: the binding of stencil_bind.py,
-    plus the geometry of the rank's slab and the wrap planes across the ends of the decomposition."""
+    plus the geometry of the rank's slab and the wrap planes across the ends of the decomposition.
+
+    THE INTERFACE `SlabTracedAdam` drives (a stand-in handed in as `kernels=` declares all of it, see
+    tests/slab_traced_double.py):
+      halo                      planes the operator reads away along the sharded axis (0 or 1)
+      src_keys, gather_keys     grid fields the kernels read / whose gradient a gather forms
+      merged                    the gather keys that `gather_all` serves in one launch (empty: `gather` per key)
+      reread                    fields whose own arrays the gathers read again
+      fused_adam                whether `gather(..., adam=)` / `gather_all(..., hyper)` can apply the optimizer's update
+      param_groups, pgrad       key -> (offset, lengths) of the parameter gradients in the flat partial sums `pgrad`
+      par_outputs               outputs in parameter space, or None; with them `pout` and `launch_par`
+      set_geometry, set_params, forward, gather, partial_terms
+    and, for Newton only (jac=True), jac_items and jacobian.  Of `ops` the driver calls interp_add, interp_adj_best,
+    adam_step, adam_step_pieces (only with `fused_adam`) and PlaneList."""
 
     def __init__(self, problem, state, axis, n, device, jac=False):
         """jac: also generate `k_jac` (`jacobian`), in a library of its own -- the library of the gradient optimizers keeps
@@ -216,6 +395,22 @@ class HipSlabKernels(StencilBinding):
         self.par([values_of(key)[j] for key, j in where], [grads_of(key)[j] for key, j in where])
 
 
+class _Section:
+    """`with _Section(timers, name):` puts the launches inside between the event pair that `timers.section(name)` hands
+    out (bench.py's Timers); timers None: nothing is recorded."""
+
+    def __init__(self, timers, name):
+        self.begin, self.end = timers.section(name) if timers is not None else (None, None)
+
+    def __enter__(self):
+        if self.begin is not None:
+            self.begin.record()
+
+    def __exit__(self, *exc):
+        if self.end is not None:
+            self.end.record()
+
+
 class SlabTracedAdam:
     """One rank of the slab-decomposed Adam loop of a traced operator.
 
@@ -223,253 +418,147 @@ class SlabTracedAdam:
     do not carry the sharded unknowns' time axis); state: the global state's STRUCTURE; its arrays give the
     initial values when they are real tensors and zeros when they live on the 'meta' device."""
 
+    # REDUNDANT GHOST UPDATES: every rank applies the optimizer's update to its inner
+    # ghost planes as well as to its own planes -- the gradient message carries, besides the sender's contribution to
+    # the receiver's boundary plane, the sender's own boundary plane of the partial gradient, so both ranks hold
+    # the same complete gradient of the shared planes (a + b on one side, b + a on the other: the same bits) and
+    # make the same update with the same library kernel; the exchange of the updated unknowns at the start of every
+    # epoch disappears (one initial synchronisation of the ghost planes remains, and one after `unknowns_changed`).
+    # Same bytes, one exchange fewer.
+    redundant = True
+
     def __init__(self, problem, state, rank, world, axis=None, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
                  device=None, kernels=None):
-        from .core import Array, Field, MultigridField, NeuralNet
-
         domain = problem.domain
         self.problem, self.domain, self.rank, self.world = problem, domain, rank, world
         self.device = device if device is not None else domain.mod.device
-        dtype = torch.float64 if np.dtype(domain.dtype) == np.float64 else torch.float32
-        self.dtype = dtype
-        self.npdt = np.float64 if dtype == torch.float64 else np.float32
-        grid = {k: f for k, f in state.fields.items() if isinstance(f, (Field, MultigridField))}
-        if axis is None:
-            ok = [d for d in range(domain.ndim) if all(f.loc[d] == "c" for f in grid.values())]
-            if not ok:
-                raise ValueError("no axis on which every field is cell-centred")
-            axis = ok[0]
-        self.axis = axis
-        N = domain.cshape[axis]
-        if N % world:
-            raise ValueError("{} cells on axis {} over {} ranks".format(N, axis, world))
-        self.n = N // world
-        # ---- layout of the packed vector ---------------------------------------------------------
-        self.entries = []  # (key, kind, [levels] or [shapes])
-        sizes = []
-        for key, f in state.fields.items():
-            if isinstance(f, MultigridField):
-                factors = [float(x) for x in (f.factors or domain.mg_factors or [1] * len(f.terms))]
-                mgloc = domain._mg_loc(f)
-                if mgloc[axis] != "c":
-                    raise ValueError("field '{}' is not refined / cell-centred on the sharded axis".format(key))
-                levels = [_Level(tuple(t.array.shape), axis, rank, world) for t in f.terms]
-                for l in range(len(levels) - 2, -1, -1):  # a rank's planes must be whole coarse cells at the transition
-                    if levels[l + 1].replicated and not levels[l].replicated and levels[l].n % 2:
-                        levels[l] = _Level(tuple(f.terms[l].array.shape), axis, rank, world, replicate=True)
-                if levels[0].replicated or any(a.replicated and not b.replicated for a, b in zip(levels, levels[1:])):
-                    raise ValueError("field '{}': {} cells on the sharded axis over {} ranks".format(key, N, world))
-                init = [t.array for t in f.terms]
-                # u = f_0 w_0 + P(f_1 w_1 + P(...)) (reference core.py:245-263); None: every factor is 1
-                if len(levels) == 1 and factors[0] != 1.0:
-                    raise NotImplementedError("slab decomposition of a one-level multigrid field with a factor")
-                self.entries.append(dict(key=key, kind="mg", levels=levels, loc=mgloc, init=init,
-                                         factors=None if all(x == 1.0 for x in factors) else factors))
-                sizes += [lv.size for lv in levels]
-            elif isinstance(f, Field):
-                if f.loc[axis] != "c":
-                    raise ValueError("field '{}' is not cell-centred on the sharded axis".format(key))
-                levels = [_Level(tuple(f.array.shape), axis, rank, world)]
-                if levels[0].replicated:
-                    raise ValueError("field '{}': {} cells on the sharded axis over {} ranks".format(key, N, world))
-                self.entries.append(dict(key=key, kind="field", levels=levels, loc=f.loc, init=[f.array]))
-                sizes.append(levels[0].size)
-            elif isinstance(f, (NeuralNet, Array)):
-                arrays = domain.arrays_from_field(f)
-                self.entries.append(dict(key=key, kind="par", shapes=[tuple(a.shape) for a in arrays], init=arrays))
-                sizes += [int(a.numel()) for a in arrays]
-            else:
-                raise TypeError(type(f).__name__)
-        total = sum(sizes)
-        mk = lambda: torch.zeros(total, dtype=dtype, device=self.device)
+        self.dtype = torch.float64 if np.dtype(domain.dtype) == np.float64 else torch.float32
+        self.npdt = np.float64 if self.dtype == torch.float64 else np.float32
+        lay = self.layout = SlabLayout(domain, state, axis, rank, world)
+        self.axis, self.n, self.entries, self.by_key = lay.axis, lay.n, lay.entries, lay.by_key
+        self.n_unknowns_local, self.local_cells, self.global_cells = lay.n_unknowns_local, lay.local_cells, lay.global_cells
+        self._packed_vectors()
+        self._exchange_lists()
+        self.kern = (kernels or HipSlabKernels)(problem, state, lay.axis, lay.n, self.device)
+        self.h = self.kern.halo
+        if self.h > 1:
+            raise TraceUnsupported("reads {} cells away along the sharded axis (the exchange keeps 1 plane)".format(self.h))
+        self._source_buffers()
+        self._wrap_lists()
+        lv0 = self.by_key[self.kern.src_keys[0]].levels[0]
+        self.kern.set_geometry(lv0.off, lv0.g_lo, lv0.shape[lay.axis])
+        self.kern.set_params(lambda key: self.by_key[key].x)
+        self.lr, self.b1, self.b2, self.eps = self.npdt(lr), self.npdt(beta_1), self.npdt(beta_2), epsilon
+        self.t = 0
+        self.has_params = any(e.kind == "par" for e in self.entries) and bool(self.kern.param_groups)
+        self._fused, self._post_flat, self._post_pieces = fused_update_plan(
+            lay, self.kern.gather_keys if self.kern.fused_adam else (), self.kern.reread)
+
+    # ---- set-up ----------------------------------------------------------------------------------------
+    def _packed_vectors(self):
+        """x, m, v, g: all unknowns of the rank, the optimizer's moments and the gradient, each ONE vector with a view per
+        array on the entries; the state's values copied into x."""
+        mk = lambda: torch.zeros(self.layout.total, dtype=self.dtype, device=self.device)
         self.x, self.m, self.v, self.g = mk(), mk(), mk(), mk()
         # fields with multigrid factors: the UNSCALED cotangents h_l = (P^T)^l g_u travel down the levels, the gradient
         # of level l is g_l = f_l h_l -- a second packed vector with the layout of g
-        scaled = any(e.get("factors") for e in self.entries)
-        self.hvec = mk() if scaled else None
-        pos = 0
-        self._rep = []  # (start, size) of the replicated level arrays in the packed vectors
-        # REDUNDANT GHOST UPDATES: every rank applies the optimizer's update to its inner
-        # ghost planes as well as to its own planes -- the gradient message carries, besides the sender's contribution to
-        # the receiver's boundary plane, the sender's own boundary plane of the partial gradient, so both ranks hold
-        # the same complete gradient of the shared planes (a + b on one side, b + a on the other: the same bits) and
-        # make the same update with the same library kernel; the exchange of the updated unknowns at the start of every
-        # epoch disappears (one initial synchronisation of the ghost planes remains).  Same bytes, one exchange fewer.
-        self.redundant = True
-        self._x_synced = False
-        send_own = dict(lo=[], hi=[])  # plane descriptors (ops.PlaneList): owned boundary planes / inner ghost planes
-        recv_ghost = dict(lo=[], hi=[])
-        # the same planes split by level for the gradients' halo-add: the finest levels (97 % of the bytes) travel WHILE
-        # the transposes run down the levels, the coarser ones after them
-        own0, own1, ghost0, ghost1 = (dict(lo=[], hi=[]) for _ in range(4))
+        self.hvec = mk() if any(e.factors for e in self.entries) else None
+        self._x_synced = False  # whether the inner ghost planes of x hold the neighbours' boundary planes
         for e in self.entries:
-            shapes = [lv.shape for lv in e["levels"]] if "levels" in e else e["shapes"]
-            views = dict(x=[], m=[], v=[], g=[], h=[])
-            e["start"] = pos
-            for k, shape in enumerate(shapes):
-                cnt = math.prod(shape)
-                for name, buf in (("x", self.x), ("m", self.m), ("v", self.v), ("g", self.g)):
-                    views[name].append(buf[pos:pos + cnt].view(shape))
-                # where the gathers / transposes write: g itself, or the unscaled twin when the field has factors
-                views["h"].append((self.hvec if e.get("factors") else self.g)[pos:pos + cnt].view(shape))
-                src = e["init"][k]
+            spans = [(slice(pos, pos + cnt), shape) for pos, cnt, shape, _ in e.arrays()]
+            views = lambda buf: [buf[s].view(shape) for s, shape in spans]
+            e.x, e.m, e.v, e.g = views(self.x), views(self.m), views(self.v), views(self.g)
+            # where the gathers / transposes write: g itself, or the unscaled twin when the field has factors
+            e.h = views(self.hvec) if e.factors else e.g
+            for xk, src, lv in zip(e.x, e.init, e.levels or [None] * len(e.x)):
                 if src is not None and src.device.type != "meta":
-                    if "levels" in e:
-                        lv = e["levels"][k]
-                        src = src.narrow(axis, lv.off - lv.g_lo, lv.shape[axis])
-                    views["x"][k].copy_(src.to(device=self.device, dtype=dtype))
-                if "levels" in e and e["levels"][k].replicated:
-                    self._rep.append((pos, cnt))
-                elif "levels" in e:
-                    lv = e["levels"][k]
-                    own, ghost = (own0, ghost0) if k == 0 else (own1, ghost1)
-                    # `ghost`: what the gradient message to that side carries; `own`: where the message FROM that side is
-                    # added.  With redundant ghost updates the message also carries the sender's own boundary plane (its
-                    # partial gradient), which completes the receiver's copy of that plane -- its inner ghost plane
-                    if rank > 0:
-                        send_own["lo"].append(lv.plane_desc(pos, 0))
-                        recv_ghost["lo"].append(lv.plane_desc(pos, -1))
-                        own["lo"].append(lv.plane_desc(pos, 0))
-                        ghost["lo"].append(lv.plane_desc(pos, -1))
-                        if self.redundant:
-                            ghost["lo"].append(lv.plane_desc(pos, 0))
-                            own["lo"].append(lv.plane_desc(pos, -1))
-                    if rank < world - 1:
-                        send_own["hi"].append(lv.plane_desc(pos, lv.n - 1))
-                        recv_ghost["hi"].append(lv.plane_desc(pos, lv.n))
-                        own["hi"].append(lv.plane_desc(pos, lv.n - 1))
-                        ghost["hi"].append(lv.plane_desc(pos, lv.n))
-                        if self.redundant:
-                            ghost["hi"].append(lv.plane_desc(pos, lv.n - 1))
-                            own["hi"].append(lv.plane_desc(pos, lv.n))
-                pos += cnt
-            e.update(views)
-            del e["init"]
-        # one launch packs / unpacks / adds every plane of every level and field of an exchange (odil_planes_copy); the
-        # send buffers of the two exchange points are allocated once
-        mk_list = lambda planes: hip_ops.PlaneList(planes, self.device) if planes else None
-        self._own = {s: mk_list(send_own[s]) for s in ("lo", "hi")}
-        self._ghost = {s: mk_list(recv_ghost[s]) for s in ("lo", "hi")}
-        mk_buf = lambda pl: None if pl is None else torch.empty(pl.count, dtype=dtype, device=self.device)
-        self._send_x = {s: mk_buf(self._own[s]) for s in ("lo", "hi")}
-        self._g_split = [({s: mk_list(o[s]) for s in ("lo", "hi")}, {s: mk_list(g_[s]) for s in ("lo", "hi")})
-                         for o, g_ in ((own0, ghost0), (own1, ghost1))]
-        self._send_g = [{s: mk_buf(ghost[s]) for s in ("lo", "hi")} for _, ghost in self._g_split]
-        self.by_key = {e["key"]: e for e in self.entries}
-        self.n_unknowns_local = sum(lv.n * lv.plane for e in self.entries if "levels" in e for lv in e["levels"]
-                                    if not lv.replicated) + sum(
-            math.prod(s) for e in self.entries if "shapes" in e for s in e["shapes"])
-        self.local_cells = math.prod(domain.cshape) // world
-        self.global_cells = math.prod(domain.cshape)
-        # ---- kernels and their buffers -------------------------------------------------------------
-        self.kern = kernels(problem, state, axis, self.n, self.device) if kernels is not None else HipSlabKernels(
-            problem, state, axis, self.n, self.device)
-        h = self.kern.halo
-        if h > 1:
-            raise TraceUnsupported("reads {} cells away along the sharded axis (the exchange keeps 1 plane)".format(h))
-        self.h = h
-        self.u, self.work, self.wrap = dict(), dict(), dict()
-        # the periodic closure's planes (`h` planes per field at each end): the four sets -- u received from across
-        # the low / high end, gradient contributions the gathers write for across them -- are each ONE buffer with
-        # a view per field, so a set travels as one message without a pack (or is filled by one copy)
-        hw = max(h, 1)
-        wsizes = {key: math.prod(hw if d == axis else s_ for d, s_ in enumerate(self.by_key[key]["levels"][0].shape))
-                  for key in self.kern.src_keys}
-        self._wrapbuf = {name: torch.zeros(sum(wsizes.values()), dtype=dtype, device=self.device)
-                         for name in ("lo", "hi", "glo", "ghi")}
+                    if lv is not None:
+                        src = src.narrow(self.axis, lv.off - lv.g_lo, lv.shape[self.axis])
+                    xk.copy_(src.to(device=self.device, dtype=self.dtype))
+            e.init = None
+
+    def _exchange_lists(self):
+        """The layout's plane descriptors on the device: one launch packs / unpacks / adds every plane of every level and
+        field of an exchange (odil_planes_copy); the send buffers of the exchange points are allocated once."""
+        lay = self.layout
+        lists = lambda descs: {s: hip_ops.PlaneList(d, self.device) for s, d in descs.items() if d}
+        bufs = lambda pls: {s: torch.empty(pl.count, dtype=self.dtype, device=self.device) for s, pl in pls.items()}
+        self._x_send, self._x_recv = lists(lay.x_send), lists(lay.x_recv)
+        self._send_x = bufs(self._x_send)
+        self._g_add, self._g_send = zip(*((lists(add), lists(send)) for add, send in zip(lay.g_add, lay.g_send)))
+        self._send_g = [bufs(pls) for pls in self._g_send]
+
+    def _source_buffers(self):
+        """What the kernels read besides the unknowns.  The periodic closure's planes (`h` planes per field at each end):
+        the four sets -- u received from across the low / high end, gradient contributions the gathers write for across
+        them -- are each ONE buffer with a view per field, so a set travels as one message without a pack (or is filled
+        by one copy).  The synthesised arrays u of the multigrid fields are views of ONE buffer too; the levels between
+        the finest and the coarsest get work arrays."""
+        mk = lambda shape: torch.zeros(shape, dtype=self.dtype, device=self.device)
+        keys, hw = self.kern.src_keys, max(self.h, 1)
+        lv0 = {key: self.by_key[key].levels[0] for key in keys}
+        wshape = {key: tuple(hw if d == self.axis else s for d, s in enumerate(lv0[key].shape)) for key in keys}
+        self._wsize = {key: math.prod(wshape[key]) for key in keys}
+        self._wrapbuf = {name: mk(sum(self._wsize.values())) for name in ("lo", "hi", "glo", "ghi")}
+        self.u, self.work, self.wrap, self._ustart = dict(), dict(), dict(), dict()
         woff = 0
-        for key in self.kern.src_keys:
+        for key in keys:
             e = self.by_key[key]
-            lv0 = e["levels"][0]
-            wshape = tuple(hw if d == axis else s_ for d, s_ in enumerate(lv0.shape))
-            self.wrap[key] = {name: buf[woff:woff + wsizes[key]].view(wshape) for name, buf in self._wrapbuf.items()}
-            woff += wsizes[key]
-            if e["kind"] == "mg" and len(e["levels"]) > 1:
-                self.u[key] = None  # a view of ONE buffer for all synthesised arrays, below
-                self.work[key] = [None] + [torch.zeros(lv.shape, dtype=dtype, device=self.device)
-                                           for lv in e["levels"][1:-1]] + [None]
+            self.wrap[key] = {name: buf[woff:woff + self._wsize[key]].view(wshape[key]) for name, buf in self._wrapbuf.items()}
+            woff += self._wsize[key]
+            if e.synthesised:
+                self.work[key] = [None] + [mk(lv.shape) for lv in e.levels[1:-1]] + [None]
             else:
-                self.u[key] = e["x"][0]
-        synth = [key for key in self.kern.src_keys if self.u[key] is None]
-        self._uflat = torch.zeros(sum(self.by_key[key]["levels"][0].size for key in synth), dtype=dtype, device=self.device)
-        uoff, ustart = 0, dict()
+                self.u[key] = e.x[0]
+        synth = [key for key in keys if self.by_key[key].synthesised]
+        self._uflat = mk(sum(lv0[key].size for key in synth))
+        uoff = 0
         for key in synth:
-            lv0 = self.by_key[key]["levels"][0]
-            self.u[key] = self._uflat[uoff:uoff + lv0.size].view(lv0.shape)
-            ustart[key] = uoff
-            uoff += lv0.size
+            self.u[key] = self._uflat[uoff:uoff + lv0[key].size].view(lv0[key].shape)
+            self._ustart[key] = uoff
+            uoff += lv0[key].size
+
+    def _wrap_lists(self):
+        """The plane lists of the periodic closure (none when the operator reads no neighbour along the sharded axis)."""
+        keys, h = self.kern.src_keys, self.h
+        lv0 = {key: self.by_key[key].levels[0] for key in keys}
+        end = lambda key, side: 0 if side == "lo" else lv0[key].n - h
         # the end planes of the synthesised arrays that close the periodic direction, as ONE message per side packed by
         # one launch (odil_planes_copy) -- when every source field is synthesised; else slices + torch.cat
         self._wrap_pack = None
-        if h and len(synth) == len(self.kern.src_keys):
-            self._wrap_pack = dict()
-            for side in ("lo", "hi"):
-                descs = []
-                for key in self.kern.src_keys:
-                    lv0 = self.by_key[key]["levels"][0]
-                    descs.append(lv0.plane_desc(ustart[key], 0 if side == "lo" else lv0.n - h))
-                self._wrap_pack[side] = hip_ops.PlaneList(descs, self.device)
+        if h and all(self.by_key[key].synthesised for key in keys):
+            self._wrap_pack = {side: hip_ops.PlaneList([lv0[key].plane_desc(self._ustart[key], end(key, side)) for key in keys],
+                                                       self.device) for side in ("lo", "hi")}
         # where the wrap contributions of the gradients land: the first / last `h` owned planes of every gathered
-        # field's finest level, in message order (odil_planes_copy, mode add)
-        self._wrap_add = dict()
-        if h:
-            for side, pos in (("lo", 0), ("hi", None)):
-                off, lists = 0, []
-                for key in self.kern.src_keys:
-                    e = self.by_key[key]
-                    lv = e["levels"][0]
-                    if key in self.kern.gather_keys:
-                        first_plane = 0 if pos == 0 else lv.n - h
-                        if hasattr(hip_ops.PlaneList, "_run"):
-                            base, outer, ostride, inner = lv.plane_desc(e["start"], first_plane)
-                            lists.append((hip_ops.PlaneList([(base, outer, ostride, inner * h)], self.device, start=off),
-                                          bool(e.get("factors"))))
-                        else:  # (CPU double of the plane kernels: tests over gloo)
-                            lists.append((key, lv, first_plane))
-                            assert len(lists[-1]) == 3
-                    off += wsizes[key]
-                self._wrap_add[side] = lists
-        lv0 = self.by_key[self.kern.src_keys[0]]["levels"][0]
-        self.kern.set_geometry(lv0.off, lv0.g_lo, lv0.shape[axis])
-        self.kern.set_params(lambda key: self.by_key[key]["x"])
-        self.lr, self.b1, self.b2, self.eps = self.npdt(lr), self.npdt(beta_1), self.npdt(beta_2), epsilon
-        self.t = 0
-        self.has_params = any(e["kind"] == "par" for e in self.entries) and bool(self.kern.param_groups)
-        # ---- the optimizer's update inside the gathers ------------------------------------------------
-        # A gather completes the gradient of the owned planes 1 .. n - 2 of its array (plane 0 / n - 1 wait for the
-        # neighbour's share or the periodic closure): the kernels that can, update those entries where they form the
-        # gradient, and the launches at the end of the epoch cover the rest of the packed vector -- the two end pieces of
-        # every such array (strided when the sharded axis is not the leading one) and the ranges between the arrays
-        # (coarser levels, fields without a gather, parameters).
-        self._fused, self._post_flat, self._post_pieces = dict(), [], []
-        if getattr(self.kern, "fused_adam", False):
-            spans = []
-            for key in self.kern.gather_keys:
+        # field's finest level, in message order (odil_planes_copy, mode add): side -> [(list, packed vector)]
+        self._wrap_add = dict(lo=[], hi=[])
+        for side in ("lo", "hi") if h else ():
+            off = 0
+            for key in keys:
                 e = self.by_key[key]
-                lv = e["levels"][0]
-                if lv.n < 4:
-                    continue
-                if self.u[key] is e["x"][0] and key in getattr(self.kern, "reread", ()):
-                    continue  # the array a gather reads IS the unknown: no launch of this epoch may update it
-                if e.get("factors"):
-                    continue  # the gather forms h_0, the gradient is f_0 h_0
-                self._fused[key] = (1, lv.n - 1)
-                spans.append((e["start"], lv.size))
-                outer = math.prod(lv.shape[:axis])
-                inner = lv.plane // outer
-                stride = lv.shape[axis] * inner
-                first, last = lv.g_lo + 1, lv.g_lo + lv.n - 1  # planes [0, first) and [last, extent) of the array
-                self._post_pieces.append((e["start"], lv.size, outer, stride, 0, first * inner))
-                self._post_pieces.append((e["start"], lv.size, outer, stride, last * inner, (lv.shape[axis] - last) * inner))
-            at = 0
-            for start, size in sorted(spans):
-                if start > at:
-                    self._post_flat.append((at, start))
-                at = start + size
-            if at < total:
-                self._post_flat.append((at, total))
+                if key in self.kern.gather_keys:
+                    desc = lv0[key].plane_desc(e.start, end(key, side), h)
+                    self._wrap_add[side].append((hip_ops.PlaneList([desc], self.device, start=off),
+                                                 self.hvec if e.factors else self.g))
+                off += self._wsize[key]
 
     # ---- pieces of the epoch -------------------------------------------------------------------------
+    def unknowns_changed(self):
+        """For whoever writes the owned planes of `x` from outside an epoch: the inner ghost planes are refreshed by the
+        next evaluation."""
+        self._x_synced = False
+
+    @staticmethod
+    def _pack(lists, vec, bufs):
+        """The (lo, hi) messages of an exchange: the planes of `lists` out of the packed vector `vec` (None: no neighbour)."""
+        return tuple(lists[s].pack(vec, bufs[s]) if s in lists else None for s in ("lo", "hi"))
+
+    @staticmethod
+    def _unpack(lists, vec, received, add):
+        for side, recv in zip(("lo", "hi"), received):
+            if recv is not None:
+                (lists[side].unpack_add if add else lists[side].unpack)(vec, recv)
+
     def _field_streams(self, keys):
         """One side stream per field for the TRANSPOSE chains: the small, latency-bound
         launches at the coarse end of one field's chain overlap the long launches of another's -- config 5 as one rank:
@@ -495,40 +584,31 @@ class SlabTracedAdam:
     def _synthesise(self):
         for key in self.kern.src_keys:
             e = self.by_key[key]
-            L = len(e["levels"])
-            if e["kind"] != "mg" or L == 1:
+            if not e.synthesised:
                 continue
-            coarse = e["x"][L - 1]
-            fac = e.get("factors") or [1.0] * L
+            L = len(e.levels)
+            coarse = e.x[L - 1]
+            fac = e.factors or [1.0] * L
             cscale = fac[L - 1]
             for l in range(L - 2, -1, -1):
                 out = self.u[key] if l == 0 else self.work[key][l]
-                fine, lvc = e["levels"][l], e["levels"][l + 1]
+                fine, lvc = e.levels[l], e.levels[l + 1]
                 if lvc.replicated and not fine.replicated:  # this rank's window of the replicated coarse field
                     operand = coarse.narrow(self.axis, *lvc.window_of(fine))
                 else:
                     operand = lvc.inner(coarse)
                 # (a view of the level array without its outer ghost planes: read in place by the marching kernels)
-                hip_ops.interp_add(operand, e["loc"], add=e["x"][l], coarse_scale=cscale, add_scale=fac[l], out=out)
+                hip_ops.interp_add(operand, e.loc, add=e.x[l], coarse_scale=cscale, add_scale=fac[l], out=out)
                 coarse, cscale = out, 1.0
 
-    def _end_planes(self, arrays, side):
-        """The h owned planes at the low ('lo') / high end of each source field's array, packed."""
+    def _end_planes(self, side):
+        """The h owned planes of u at the low ('lo') / high end of each source field, as one message (for source fields
+        that are no synthesised arrays, which `_wrap_pack` does not cover)."""
         parts = []
         for key in self.kern.src_keys:
-            lv = self.by_key[key]["levels"][0]
-            a = arrays(key)
-            parts.append(lv.planes(a, 0 if side == "lo" else lv.n - self.h, self.h).reshape(-1))
+            lv = self.by_key[key].levels[0]
+            parts.append(lv.planes(self.u[key], 0 if side == "lo" else lv.n - self.h, self.h).reshape(-1))
         return torch.cat(parts)
-
-    def _split_planes(self, buf):
-        out, off = dict(), 0
-        for key in self.kern.src_keys:
-            shape = self.wrap[key]["lo"].shape
-            cnt = math.prod(shape)
-            out[key] = buf[off:off + cnt].view(shape)
-            off += cnt
-        return out
 
     def _transpose_chain(self):
         plan, join = self._field_streams(list(self.kern.gather_keys))
@@ -539,63 +619,56 @@ class SlabTracedAdam:
 
     def _transpose_field(self, key):
         e = self.by_key[key]
-        fac = e.get("factors")
-        for l in range(1, len(e["levels"])):
-            lv, fine = e["levels"][l], e["levels"][l - 1]
+        fac = e.factors
+        for l in range(1, len(e.levels)):
+            lv, fine = e.levels[l], e.levels[l - 1]
             if lv.replicated and not fine.replicated:
                 # this rank's share of the replicated level: zero but for the window its planes reach
-                e["h"][l].zero_()
+                e.h[l].zero_()
                 if fac:
-                    e["g"][l].zero_()
+                    e.g[l].zero_()
                 view = lambda a: a.narrow(self.axis, *lv.window_of(fine))
             else:
                 view = lv.inner
-            dst = view(e["h"][l])
-            best = getattr(hip_ops, "interp_adj_best", hip_ops.interp_adj)
-            best(e["h"][l - 1], e["loc"], tuple(dst.shape), out=dst)  # (in place, also into a strided view)
+            dst = view(e.h[l])
+            hip_ops.interp_adj_best(e.h[l - 1], e.loc, tuple(dst.shape), out=dst)  # (in place, also into a strided view)
             if fac:
-                torch.mul(dst, fac[l], out=view(e["g"][l]))
+                torch.mul(dst, fac[l], out=view(e.g[l]))
 
-    def _sources_gen(self, refresh, tic, toc):
+    def _sources_gen(self, refresh, timers=None):
         """What the generated kernels read, as a generator that yields at its exchanges: the inner ghost planes of the
-        unknowns (refresh=True, or the first time), the synthesised arrays u and the wrap planes across the ends."""
-        rank, world, h = self.rank, self.world, self.h
-        first, last = rank == 0, rank == world - 1
+        unknowns (refresh=True, or when they are not in step with the neighbours), the synthesised arrays u and the wrap
+        planes across the ends."""
         if refresh or not self._x_synced:
-            # the neighbours' boundary planes of the unknowns -> inner ghost planes: every epoch, or once at the start
-            # when the ghost planes are updated redundantly afterwards
-            b = tic("halo")
-            lo, hi = self._own["lo"], self._own["hi"]
-            recv_lo, recv_hi = yield ("halo", None if lo is None else lo.pack(self.x, self._send_x["lo"]),
-                                      None if hi is None else hi.pack(self.x, self._send_x["hi"]))
-            if recv_lo is not None:
-                self._ghost["lo"].unpack(self.x, recv_lo)
-            if recv_hi is not None:
-                self._ghost["hi"].unpack(self.x, recv_hi)
-            self._x_synced = True
-            toc(b)
-        b = tic("mg_synth")
-        self._synthesise()
-        toc(b)
-        if h:
-            b = tic("halo")
-            ufield = lambda key: self.u[key]
-            if self._wrap_pack is not None and world == 1:
-                # one rank: its high planes ARE what lies across the low end -- packed straight into place
-                self._wrap_pack["hi"].pack(self._uflat, self._wrapbuf["lo"])
-                self._wrap_pack["lo"].pack(self._uflat, self._wrapbuf["hi"])
-                recv_lo = recv_hi = None
-            elif self._wrap_pack is not None:
-                recv_lo, recv_hi = yield ("wrap", self._wrap_pack["lo"].pack(self._uflat) if first else None,
-                                          self._wrap_pack["hi"].pack(self._uflat) if last else None)
-            else:
-                recv_lo, recv_hi = yield ("wrap", self._end_planes(ufield, "lo") if first else None,
-                                          self._end_planes(ufield, "hi") if last else None)
-            if recv_lo is not None:
-                self._wrapbuf["lo"].copy_(recv_lo.reshape(-1))
-            if recv_hi is not None:
-                self._wrapbuf["hi"].copy_(recv_hi.reshape(-1))
-            toc(b)
+            # the neighbours' boundary planes of the unknowns -> inner ghost planes: once, and whenever somebody else has
+            # changed the unknowns -- the epochs update the ghost planes redundantly
+            with _Section(timers, "halo"):
+                received = yield ("halo",) + self._pack(self._x_send, self.x, self._send_x)
+                self._unpack(self._x_recv, self.x, received, add=False)
+                self._x_synced = True
+        with _Section(timers, "mg_synth"):
+            self._synthesise()
+        if self.h:
+            with _Section(timers, "halo"):
+                yield from self._wrap_sources_gen()
+
+    def _wrap_sources_gen(self):
+        """The end planes of u across the periodic closure into the wrap buffers."""
+        first, last = self.rank == 0, self.rank == self.world - 1
+        if self._wrap_pack is not None and self.world == 1:
+            # one rank: its high planes ARE what lies across the low end -- packed straight into place
+            self._wrap_pack["hi"].pack(self._uflat, self._wrapbuf["lo"])
+            self._wrap_pack["lo"].pack(self._uflat, self._wrapbuf["hi"])
+            return
+        if self._wrap_pack is not None:
+            end = lambda side: self._wrap_pack[side].pack(self._uflat)
+        else:
+            end = self._end_planes
+        recv_lo, recv_hi = yield ("wrap", end("lo") if first else None, end("hi") if last else None)
+        if recv_lo is not None:
+            self._wrapbuf["lo"].copy_(recv_lo.reshape(-1))
+        if recv_hi is not None:
+            self._wrapbuf["hi"].copy_(recv_hi.reshape(-1))
 
     def wrap_planes(self):
         """(wlo, whi): src key -> the wrap planes of u across the low / high end (filled by the last exchange)."""
@@ -605,9 +678,79 @@ class SlabTracedAdam:
         """The loss terms of the current unknowns (forward kernel only, no gradient), as a generator that yields at its
         exchanges; afterwards the ghost planes, u and the wrap planes hold this state (what `HipSlabKernels.jacobian`
         reads)."""
-        nothing = lambda name: None
-        yield from self._sources_gen(True, nothing, nothing)
+        yield from self._sources_gen(True)
         self.kern.forward(self.u, *self.wrap_planes())
+
+    def _hyper(self):
+        """(alpha, 1 - beta_1, 1 - beta_2, epsilon) of the update this epoch makes (reference optimizer.py:311-319)."""
+        t = self.npdt(self.t + 1)
+        alpha = self.lr * np.sqrt(1 - self.b2**t) / (1 - self.b1**t)
+        return (alpha, 1 - self.b1, 1 - self.b2, self.eps)
+
+    def _gathers(self, fused, hyper):
+        """The ghost-extended gradient of every gathered field's finest level (h_0) and its wrap contributions; the
+        fields of `fused` updated on the planes whose gradient is complete.  hyper None: no update."""
+        arrays = lambda key: (self.by_key[key].h[0], self.wrap[key]["glo"], self.wrap[key]["ghi"])
+        xmv = lambda key: (self.by_key[key].x[0], self.by_key[key].m[0], self.by_key[key].v[0])
+        merged = list(self.kern.merged)
+        spans = {fused[key] for key in merged if key in fused}
+        if merged and len(spans) <= 1:  # one launch for all of them (the fused planes are the same for every field)
+            items = [(key,) + arrays(key) + (xmv(key) if key in fused else None,) for key in merged]
+            self.kern.gather_all(items, hyper, spans.pop() if spans else (0, 0))
+        else:
+            merged = []
+        for key in self.kern.gather_keys:
+            if key in merged:
+                continue
+            if key in fused:
+                self.kern.gather(key, *arrays(key), adam=xmv(key) + hyper + fused[key])
+            else:
+                self.kern.gather(key, *arrays(key))
+
+    def _wrap_add_gen(self):
+        """The gathers' contributions across the periodic closure, added where they belong."""
+        first, last = self.rank == 0, self.rank == self.world - 1
+        received = yield ("wrap", self._wrapbuf["glo"] if first else None, self._wrapbuf["ghi"] if last else None)
+        # what arrives from across the low end belongs to this rank's FIRST owned planes, and vice versa
+        for side, recv in zip(("lo", "hi"), received):
+            if recv is not None:
+                for plist, vec in self._wrap_add[side]:
+                    plist.unpack_add(vec, recv.reshape(-1))
+
+    def _scale_finest(self):
+        """g_0 = f_0 h_0 (ghost planes included: this rank's share of the neighbour's)."""
+        for key in self.kern.gather_keys:
+            e = self.by_key[key]
+            if e.factors:
+                torch.mul(e.h[0], e.factors[0], out=e.g[0])
+
+    def _sum_replicated_gen(self):
+        """Agglomerated levels: the ranks' shares summed (every rank then updates alike)."""
+        rep = self.layout.rep
+        if rep and self.world > 1:
+            total = yield ("sum", torch.cat([self.g[a:a + c] for a, c in rep]), None)
+            off = 0
+            for a, c in rep:
+                self.g[a:a + c].copy_(total[off:off + c])
+                off += c
+
+    def _param_sums_gen(self):
+        """The parameter gradients of networks / Arrays summed over the ranks, into the entries' gradient views."""
+        if self.has_params:
+            total = yield ("sum", self.kern.pgrad.clone(), None)
+            for key, (ofs, lens) in self.kern.param_groups.items():
+                for view, cnt in zip(self.by_key[key].g, lens):
+                    view.copy_(total[ofs:ofs + cnt].view(view.shape))
+                    ofs += cnt
+
+    def _adam_tail(self, hyper):
+        """Adam on what no gather has updated (`fused_update_plan`)."""
+        for lo, hi in self._post_flat:
+            hip_ops.adam_step(self.x[lo:hi], self.m[lo:hi], self.v[lo:hi], self.g[lo:hi], *hyper)
+        for start, size, pieces, stride, offset, count in self._post_pieces:
+            span = slice(start, start + size)
+            hip_ops.adam_step_pieces(self.x[span], self.m[span], self.v[span], self.g[span], pieces, stride, offset,
+                                     count, *hyper)
 
     # ---- one epoch -------------------------------------------------------------------------------------
     def epoch_gen(self, timers=None, update=True):
@@ -615,122 +758,35 @@ class SlabTracedAdam:
         quasi-Newton driver of slab_solvers.py) -- the ghost planes of the unknowns are refreshed first (somebody else
         changed the unknowns), no launch applies an update, and self.g is left complete on the owned planes, on the
         replicated levels and on the parameters."""
-        rank, world, h = self.rank, self.world, self.h
-        first, last = rank == 0, rank == world - 1
-        fused = self._fused if update else dict()
-
-        def tic(name):
-            if timers is None:
-                return None
-            a, b = timers.section(name)
-            a.record()
-            return b
-
-        def toc(b):
-            if b is not None:
-                b.record()
-
-        yield from self._sources_gen(not (update and self.redundant and self._x_synced), tic, toc)
-        b = tic("forward")
-        self.kern.forward(self.u, *self.wrap_planes())
-        toc(b)
-        t = self.npdt(self.t + 1)
-        alpha = self.lr * np.sqrt(1 - self.b2**t) / (1 - self.b1**t)
-        hyper = (alpha, 1 - self.b1, 1 - self.b2, self.eps)
-        b = tic("gather")
-        merged = list(getattr(self.kern, "merged", []))
-        spans = {fused[key] for key in merged if key in fused}
-        if merged and len(spans) <= 1:  # one launch for all of them (the fused planes are the same for every field)
-            items = []
-            for key in merged:
-                w, e = self.wrap[key], self.by_key[key]
-                items.append((key, e["h"][0], w["glo"], w["ghi"],
-                              (e["x"][0], e["m"][0], e["v"][0]) if key in fused else None))
-            self.kern.gather_all(items, hyper if update else None, spans.pop() if spans else (0, 0))
-        else:
-            merged = []
-        for key in self.kern.gather_keys:
-            if key in merged:
-                continue
-            w, e = self.wrap[key], self.by_key[key]
-            if key in fused:
-                self.kern.gather(key, e["h"][0], w["glo"], w["ghi"],
-                                 adam=(e["x"][0], e["m"][0], e["v"][0]) + hyper + fused[key])
-            else:
-                self.kern.gather(key, e["h"][0], w["glo"], w["ghi"])
-        toc(b)
-        if h and self.kern.gather_keys:
-            b = tic("halo")
-            recv_lo, recv_hi = yield ("wrap", self._wrapbuf["glo"] if first else None, self._wrapbuf["ghi"] if last else None)
-            # what arrives from across the low end belongs to this rank's FIRST owned planes, and vice versa
-            for recv, side in ((recv_lo, "lo"), (recv_hi, "hi")):
-                if recv is None:
-                    continue
-                parts = None
-                for item in self._wrap_add[side]:
-                    if len(item) == 3:
-                        parts = parts or self._split_planes(recv)
-                        key, lv, first_plane = item
-                        lv.planes(self.by_key[key]["h"][0], first_plane, h).add_(parts[key])
-                    else:
-                        plist, scaled = item
-                        plist.unpack_add(self.hvec if scaled else self.g, recv.reshape(-1))
-            toc(b)
-        for key in self.kern.gather_keys:  # g_0 = f_0 h_0 (ghost planes included: this rank's share of the neighbour's)
-            e = self.by_key[key]
-            if e.get("factors"):
-                torch.mul(e["h"][0], e["factors"][0], out=e["g"][0])
+        yield from self._sources_gen(not update, timers)
+        with _Section(timers, "forward"):
+            self.kern.forward(self.u, *self.wrap_planes())
+        hyper = self._hyper()
+        with _Section(timers, "gather"):
+            self._gathers(self._fused if update else dict(), hyper if update else None)
+        if self.h and self.kern.gather_keys:
+            with _Section(timers, "halo"):
+                yield from self._wrap_add_gen()
+        self._scale_finest()
         # the gradients' halo-add in two messages: the finest levels' ghost planes are final now -- they are POSTED and
         # travel while the transposes run down the levels (which read this rank's partial arrays only); the coarser
         # levels' planes follow after the chain
-        b = tic("halo")
-        (own0, ghost0), (own1, ghost1) = self._g_split
-        pack = lambda lists, bufs, side: None if lists[side] is None else lists[side].pack(self.g, bufs[side])
-        token = yield ("post", pack(ghost0, self._send_g[0], "lo"), pack(ghost0, self._send_g[0], "hi"))
-        toc(b)
-        b = tic("mg_synth_adj")
-        self._transpose_chain()
-        toc(b)
-        b = tic("halo")
-        recv_lo, recv_hi = yield ("wait", token, None)
-        if recv_lo is not None:
-            own0["lo"].unpack_add(self.g, recv_lo)
-        if recv_hi is not None:
-            own0["hi"].unpack_add(self.g, recv_hi)
-        recv_lo, recv_hi = yield ("halo", pack(ghost1, self._send_g[1], "lo"), pack(ghost1, self._send_g[1], "hi"))
-        if recv_lo is not None:
-            own1["lo"].unpack_add(self.g, recv_lo)
-        if recv_hi is not None:
-            own1["hi"].unpack_add(self.g, recv_hi)
-        if self._rep and world > 1:  # agglomerated levels: the ranks' shares summed (every rank then updates alike)
-            total = yield ("sum", torch.cat([self.g[a:a + c] for a, c in self._rep]), None)
-            off = 0
-            for a, c in self._rep:
-                self.g[a:a + c].copy_(total[off:off + c])
-                off += c
-        toc(b)
-        if self.has_params:
-            total = yield ("sum", self.kern.pgrad.clone(), None)
-            for key, (ofs, lens) in self.kern.param_groups.items():
-                for view, cnt in zip(self.by_key[key]["g"], lens):
-                    view.copy_(total[ofs:ofs + cnt].view(view.shape))
-                    ofs += cnt
-        if getattr(self.kern, "par_outputs", None) is not None:
-            self.kern.launch_par(lambda key: self.by_key[key]["x"], lambda key: self.by_key[key]["g"])
-        if not update:
-            return
-        self.t += 1
-        b = tic("adam")
-        if not self._fused:
-            hip_ops.adam_step(self.x, self.m, self.v, self.g, *hyper)
-        else:
-            for lo, hi in self._post_flat:
-                hip_ops.adam_step(self.x[lo:hi], self.m[lo:hi], self.v[lo:hi], self.g[lo:hi], *hyper)
-            for start, size, pieces, stride, offset, count in self._post_pieces:
-                span = slice(start, start + size)
-                hip_ops.adam_step_pieces(self.x[span], self.m[span], self.v[span], self.g[span], pieces, stride, offset,
-                                         count, *hyper)
-        toc(b)
+        with _Section(timers, "halo"):
+            token = yield ("post",) + self._pack(self._g_send[0], self.g, self._send_g[0])
+        with _Section(timers, "mg_synth_adj"):
+            self._transpose_chain()
+        with _Section(timers, "halo"):
+            self._unpack(self._g_add[0], self.g, (yield ("wait", token, None)), add=True)
+            received = yield ("halo",) + self._pack(self._g_send[1], self.g, self._send_g[1])
+            self._unpack(self._g_add[1], self.g, received, add=True)
+            yield from self._sum_replicated_gen()
+        yield from self._param_sums_gen()
+        if self.kern.par_outputs is not None:
+            self.kern.launch_par(lambda key: self.by_key[key].x, lambda key: self.by_key[key].g)
+        if update:
+            self.t += 1
+            with _Section(timers, "adam"):
+                self._adam_tail(hyper)
 
     def epoch(self, comm, timers=None):
         gen = self.epoch_gen(timers)
@@ -741,17 +797,23 @@ class SlabTracedAdam:
         except StopIteration:
             pass
 
+    def par_terms(self, combined=False):
+        """[(position among the loss terms, value or None)] of the parameter-space outputs.  Every rank evaluates them
+        alike, so they are counted ONCE: by rank 0 (emulated ranks sum their last_loss(), quasi-Newton ranks their local
+        losses), or by every rank when its terms are `combined` over the ranks already; None: not counted here."""
+        if self.kern.par_outputs is None:
+            return []
+        counted = self.rank == 0 or combined
+        return [(k, self.kern.pout[2 * q] if counted else None) for q, (k, _) in enumerate(self.kern.par_outputs)]
+
     def last_terms(self, comm=None):
         """Global loss terms of the last evaluation (one small all-reduce)."""
         part = self.kern.partial_terms().clone()
         if comm is not None:
             part = comm.exchange("sum", part, None)
         terms = [float(v) for v in part]
-        if getattr(self.kern, "par_outputs", None) is not None and hasattr(self.kern, "pout"):
-            # parameter-space outputs are evaluated by every rank alike: counted ONCE (emulated ranks sum their
-            # last_loss(): rank 0 carries them)
-            for q, (k, _) in enumerate(self.kern.par_outputs):
-                terms.insert(k, float(self.kern.pout[2 * q]) if self.rank == 0 or comm is not None else 0.0)
+        for k, value in self.par_terms(combined=comm is not None):
+            terms.insert(k, 0.0 if value is None else float(value))
         return terms
 
     def last_loss(self, comm=None):
@@ -761,10 +823,7 @@ class SlabTracedAdam:
         """This rank's part of every unknown array, in `Domain.arrays_from_state` order."""
         res = []
         for e in self.entries:
-            if "levels" in e:
-                res += [lv.owned(a) for lv, a in zip(e["levels"], e["x"])]
-            else:
-                res += list(e["x"])
+            res += [lv.owned(a) for lv, a in zip(e.levels, e.x)] if e.levels else list(e.x)
         return res
 
 

@@ -44,6 +44,8 @@ def make_kernels(local_extra):
 
     class CpuSlabKernels:
         halo = 1
+        # (no merged gathers, no update inside the gathers, no outputs in parameter space)
+        merged, reread, fused_adam, par_outputs = (), (), False, None
 
         def __init__(self, problem, state, axis, n, device):
             from odil_amd.core import Field, MultigridField

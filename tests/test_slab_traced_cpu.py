@@ -86,7 +86,7 @@ def worker(rank, world, which, epochs, port, out, nx_rank=8):
         # the planes two ranks share: the boundary planes of a rank and the inner ghost planes of its neighbours
         shared = []
         for e in run.entries:
-            for lv, a in zip(e.get("levels", []), e.get("x", [])):
+            for lv, a in zip(e.levels, e.x):
                 if lv.replicated:
                     continue
                 shared.append(dict(own_lo=lv.planes(a, 0).clone().numpy(), own_hi=lv.planes(a, lv.n - 1).clone().numpy(),
