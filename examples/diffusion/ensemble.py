@@ -6,11 +6,14 @@ stencils).  With `--beta > 0` the operator is nonlinear,  div(k grad u) - beta u
 hierarchies are set up again every step.  Every step linearises all members in one generated launch (`--linearize
 batched`, `odil.util.linearize_ensemble`) or member by member (`--linearize members`); the linearisation's share of a step
 is printed from device events around it.  The time per step is printed beside that of the same members as single
-`optimize_newton` runs, one after the other (`--single 0` skips those).
+`optimize_newton` runs, one after the other (`--single 0` skips those).  `--form launches` runs members that are too large
+for one workgroup (256^2, 64^3, 128^3): the levels above 32768 cells as launches that cover all members, the convergence
+decision on the device (`gmg.EnsembleLaunchGMG`); `--form auto` takes it only where `--form workgroup` refuses.
 
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --kind smooth --epochs 2
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --beta 1 --epochs 4
     python examples/diffusion/ensemble.py --members 256 --ndim 2 --N 64 --linearize members --single 0
+    python examples/diffusion/ensemble.py --members 16 --ndim 2 --N 256 --form launches --linsolver multigrid
 """
 
 import argparse
@@ -48,6 +51,8 @@ def parse_args(argv=None):
     own.add_argument("--single", type=int, default=1, help="Also run the members as single optimize_newton runs and time them")
     own.add_argument("--linearize", type=str, default="batched", choices=("batched", "members"),
                      help="Linearise all members in one generated launch, or member by member")
+    own.add_argument("--form", type=str, default="workgroup", choices=("workgroup", "launches", "auto"),
+                     help="One workgroup per member, batched launches for members beyond one workgroup, or whichever serves")
     mine, rest = own.parse_known_args(argv)
     args = diffusion.parse_args(["--ndim", "2", "--N", "16", "--epochs", "2"] + rest)
     for key, value in vars(mine).items():
@@ -107,18 +112,19 @@ def main():
             problem.domain.arrays_to_state([u.clone()], state)
         synchronize()
 
-    arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback, linearize=args.linearize)
+    arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback, linearize=args.linearize, form=args.form)
     import torch
 
     together, timed = None, optinfo.route == "stencil" and torch.cuda.is_available()
     if args.epochs > args.epoch_start:  # (the same steps again, now that every member's operator is traced and its kernels are loaded)
         restart()
         start = time.perf_counter()
-        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, linearize=args.linearize, time_linearize=timed)
+        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, linearize=args.linearize, time_linearize=timed,
+                                                               form=args.form)
         synchronize()
         together = (time.perf_counter() - start) / nsteps
     status = [optinfo.solver.status(b) for b in range(args.members)] if optinfo.solver is not None else []
-    printlog("\nroute '{}', last Newton step, per member:".format(optinfo.route))
+    printlog("\nroute '{}', form '{}', last Newton step, per member:".format(optinfo.route, optinfo.form))
     for b, (problem, state, st) in enumerate(zip(problems, states, status)):
         printlog("member {:3d}: {} cycles, relative residual {:.2e}{}, error u:{:.5g}".format(
             b, st["niter"], st["residual"] / max(st["bnorm"], 1e-300), "" if st["converged"] else " (not converged)",

@@ -14,6 +14,11 @@ With `--optimizer newton` (plain unknowns, `--multigrid 0`) every epoch is ONE l
 every member, one workgroup per member (`odil.util.optimize_newton_ensemble`):
 
     python examples/poisson/ensemble.py --ndim 3 --N 16 --members 64 --multigrid 0 --optimizer newton --linsolver multigrid --epochs 1
+
+Members beyond one workgroup (256^2, 64^3) take `--form launches` there too (or `--form auto`): the stencil route of the
+Newton driver with the large levels as launches that cover all members (`gmg.EnsembleLaunchGMG`):
+
+    python examples/poisson/ensemble.py --ndim 2 --N 256 --members 16 --multigrid 0 --optimizer newton --linsolver multigrid --epochs 1 --form launches
 """
 
 import os
@@ -81,7 +86,7 @@ def main():
     callback.next_active = lambda epoch: (epoch // every + 1) * every
     if args.optimizer == "newton":
         # one launch per epoch runs the whole Newton step of every member (one workgroup per member)
-        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback)
+        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback, form=args.form)
         if args.epochs > args.epoch_start:
             status = [optinfo.solver.status(b) for b in range(args.members)]
             printlog("\nlast Newton step, per member:")

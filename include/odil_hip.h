@@ -479,6 +479,50 @@ int odil_stencil_dense_batch_f64(const double* coeffs, int64_t coeff_stride, con
                                  double* dense, void* stream);
 int odil_stencil_dense_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
                                  float* dense, void* stream);
+/* The CYCLE of an ensemble on levels too large for one workgroup (gmg.EnsembleLaunchGMG): the conventions of the set-up
+ * entry points above (the member on blockIdx.y, nbatch 1..65535, every *_stride in ELEMENTS and >= one member, malformed
+ * arguments refused before any launch).  A member runs the device code of the single entry point on its own arrays: its
+ * output is bit-identical to that entry point on them alone.  No workgroup waits for, signals or reads what another one
+ * writes: no grid barrier, no counter, no atomic.  `active`: NULL, or int[nbatch] on the device; the workgroups of a member
+ * with active[b] == 0 return before any load or store.  (No reference counterpart: the reference solves one system at a
+ * time, linsolver.py:17-26, 61-72.)
+ *   smooth_batch   odil_stencil_var_smooth for every member: mode 0 the damped Jacobi sweep (x == NULL: from the zero
+ *                  vector; out != x), mode 1 out = b - A x.  partials (mode 0 only): NULL, or double[nbatch, P] with P =
+ *                  odil_stencil_var_smooth_batch_parts(shape, ndim): workgroup p of member b leaves the sum, in double, of
+ *                  (A x - b)^2 over its cells -- the residual of the sweep's INPUT (x == NULL: b^2), which the sweep forms
+ *                  anyway.  P and the cells of a workgroup depend on the shape alone, never on nbatch.
+ *   smooth_batch_parts   P (one partial sum per 256 cells), 0 for malformed shapes
+ *   residual_restrict_batch   coarse = scale * sum over the 2^ndim children of (b - A x) for every member: every axis
+ *                  merged, even extents, even strides between members (the two children along the last axis are read as
+ *                  one aligned pack); no norm
+ *   cycle_decide_batch   the decision before cycle k, one workgroup per member still active: history[b, 1 + k] = (the
+ *                  member's nparts partial sums, added in a fixed order) / cells; with partials0 != NULL also history[b, 0]
+ *                  from those; then the stop rules of odil_stencil_solve_batch, verbatim -- 0 converged (history[1 + k] <=
+ *                  tol^2 history[0]), 1 k == maxcycles, 2 stagnated (k >= 3 and history[1 + k] >= 0.98^2 history[k]), 3 a
+ *                  non-finite norm.  A member that stops gets outcome[b] = (k, reason) and active[b] = 0; a member that is
+ *                  inactive already is left alone.  A second one-workgroup launch then counts the active members into
+ *                  *nactive (device memory).  Everything is double or int: no type suffix. */
+int odil_stencil_var_smooth_batch_f64(const double* coeffs, int64_t coeff_stride, const double* x, int64_t x_stride,
+                                      const double* b, int64_t b_stride, double* out, int64_t out_stride, const int64_t* shape,
+                                      int ndim, int nbatch, double omega, int mode, const int* active, double* partials,
+                                      void* stream);
+int odil_stencil_var_smooth_batch_f32(const float* coeffs, int64_t coeff_stride, const float* x, int64_t x_stride,
+                                      const float* b, int64_t b_stride, float* out, int64_t out_stride, const int64_t* shape,
+                                      int ndim, int nbatch, float omega, int mode, const int* active, double* partials,
+                                      void* stream);
+int64_t odil_stencil_var_smooth_batch_parts(const int64_t* shape, int ndim);
+int odil_stencil_var_residual_restrict_batch_f64(const double* coeffs, int64_t coeff_stride, const double* x, int64_t x_stride,
+                                                 const double* b, int64_t b_stride, double* coarse, int64_t coarse_stride,
+                                                 const int64_t* shape, int ndim, int nbatch, double scale, const int* active,
+                                                 void* stream);
+int odil_stencil_var_residual_restrict_batch_f32(const float* coeffs, int64_t coeff_stride, const float* x, int64_t x_stride,
+                                                 const float* b, int64_t b_stride, float* coarse, int64_t coarse_stride,
+                                                 const int64_t* shape, int ndim, int nbatch, float scale, const int* active,
+                                                 void* stream);
+int odil_stencil_cycle_decide_batch(const double* partials, int64_t partials_stride, const double* partials0,
+                                    int64_t partials0_stride, int nparts, int nbatch, int64_t cells, int k, int maxcycles,
+                                    double tol, double* history, int64_t history_stride, int* outcome, int* active,
+                                    int* nactive, void* stream);
 
 /* WHOLE EPOCHS of the multigrid Poisson problem (1-D or 2-D, all axes cell-centred) in ONE launch: one workgroup walks
  * synthesis, residual + loss, adjoint, transposed prolongations and the Adam update of every level -- the 17 dependent

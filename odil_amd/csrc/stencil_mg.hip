@@ -85,86 +85,107 @@ __device__ inline T svar_apply(const T* __restrict__ c, const T* __restrict__ x,
   return acc;
 }
 
+// one cell of a sweep (MODE 0: from x, 2: from the zero vector) or of the residual (MODE 1) on the arrays of ONE operator (the
+// kernels below hand in the single operator of a launch or one member of an ensemble).  Returns A x - b of the sweep's
+// input (MODE 1: b - A x, what it stores): the term a sweep forms anyway, whose squares the ensemble sums on the way.
+template <typename T, int MODE>
+__device__ inline T svar_smooth_cell(const T* __restrict__ c, const T* __restrict__ x, const T* __restrict__ b,
+                                     T* __restrict__ out, const SvarArgs& a, T omega, int64_t i) {
+  if (MODE == 2) {  // the sweep from the ZERO vector: x is not read (A 0 = 0; finite coefficients: the same bits)
+    const T d = T(0) - b[i];
+    out[i] = T(0) - omega * d / c[i];
+    return d;
+  }
+  int64_t id[3];
+  svar_decode(i, a, id);
+  const T ax = svar_apply<T>(c, x, a, i, id);
+  if (MODE == 0) {
+    const T d = ax - b[i];
+    out[i] = x[i] - omega * d / c[i];
+    return d;
+  }
+  const T r = b[i] - ax;
+  out[i] = r;
+  return r;
+}
+
 template <typename T, int MODE>
 __global__ __launch_bounds__(kBlock) void k_svar_smooth(const T* __restrict__ c, const T* __restrict__ x,
                                                        const T* __restrict__ b, T* __restrict__ out, SvarArgs a,
                                                        T omega) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.size) return;
-  int64_t id[3];
-  svar_decode(i, a, id);
-  if (MODE == 2) {  // the sweep from the ZERO vector: x is not read (A 0 = 0; finite coefficients: the same bits)
-    out[i] = T(0) - omega * (T(0) - b[i]) / c[i];
-    return;
-  }
-  const T ax = svar_apply<T>(c, x, a, i, id);
-  if (MODE == 0) {
-    out[i] = x[i] - omega * (ax - b[i]) / c[i];
-  } else {
-    out[i] = b[i] - ax;
-  }
+  svar_smooth_cell<T, MODE>(c, x, b, out, a, omega, i);
 }
 
 // one thread per COARSE cell; its two children along x are one 16-byte (f64) pack of every stream: the coefficient
 // arrays, b and x are read once, fully coalesced (adjacent threads, adjacent packs); the y / z neighbour rows of x come
 // as packs too (cache hits of the neighbouring threads' own rows), the two x neighbours outside the pack as scalars
+template <typename T, bool NORM>
+__device__ __forceinline__ void svar_residual_restrict_cell(const T* __restrict__ c, const T* __restrict__ x,
+                                                           const T* __restrict__ b, T* __restrict__ coarse,
+                                                           const SvarArgs& a, const SvarArgs& ca, T scale, int64_t I,
+                                                           int64_t lz0, int64_t lz1, double& local) {
+  // (NORM: the squares of the children's residuals on the planes lz0 <= z < lz1 are added to `local` one by one, in double)
+  typedef typename Vec2<T>::type T2;
+  const int64_t Z = a.n[0], Y = a.n[1], X = a.n[2];
+  const int64_t sy = X, sz = Y * X;
+  int64_t cid[3];
+  svar_decode(I, ca, cid);
+  T sum = T(0);
+  const int k0 = a.has[0] ? 2 : 1, k1 = a.has[1] ? 2 : 1;
+  const int64_t x0 = 2 * cid[2];
+  const int64_t xl = x0 == 0 ? X - 1 : x0 - 1, xr = x0 + 2 >= X ? 0 : x0 + 2;
+  for (int p = 0; p < k0; ++p)
+    for (int q = 0; q < k1; ++q) {
+      const int64_t z = a.has[0] ? 2 * cid[0] + p : 0, y = a.has[1] ? 2 * cid[1] + q : 0;
+      const int64_t row = z * sz + y * sy, i = row + x0;
+      const T2 xc = *(const T2*)(x + i);
+      const T2 c0 = *(const T2*)(c + i);
+      const T2 bb = *(const T2*)(b + i);
+      const T2 cxm = *(const T2*)(c + (int64_t)a.slot[2] * a.size + i);
+      const T2 cxp = *(const T2*)(c + (int64_t)(a.slot[2] + 1) * a.size + i);
+      const T wl = x[row + xl], er = x[row + xr];
+      T2 ax = c0 * xc;
+      ax.x = ax.x + cxm.x * wl;
+      ax.x = ax.x + cxp.x * xc.y;
+      ax.y = ax.y + cxm.y * xc.x;
+      ax.y = ax.y + cxp.y * er;
+      if (a.has[1]) {
+        const int64_t ym = (y == 0 ? Y - 1 : y - 1) * sy + z * sz + x0, yp = (y == Y - 1 ? 0 : y + 1) * sy + z * sz + x0;
+        const T2 cm = *(const T2*)(c + (int64_t)a.slot[1] * a.size + i);
+        const T2 cp = *(const T2*)(c + (int64_t)(a.slot[1] + 1) * a.size + i);
+        ax = ax + cm * *(const T2*)(x + ym);
+        ax = ax + cp * *(const T2*)(x + yp);
+      }
+      if (a.has[0]) {
+        const int64_t zm = (z == 0 ? Z - 1 : z - 1) * sz + y * sy + x0, zp = (z == Z - 1 ? 0 : z + 1) * sz + y * sy + x0;
+        const T2 cm = *(const T2*)(c + (int64_t)a.slot[0] * a.size + i);
+        const T2 cp = *(const T2*)(c + (int64_t)(a.slot[0] + 1) * a.size + i);
+        ax = ax + cm * *(const T2*)(x + zm);
+        ax = ax + cp * *(const T2*)(x + zp);
+      }
+      const T2 r = bb - ax;
+      if (NORM && z >= lz0 && z < lz1) local += (double)(r.x * r.x) + (double)(r.y * r.y);  // (slab form: own planes only)
+      sum = sum + r.x;
+      sum = sum + r.y;
+    }
+  coarse[I] = scale * sum;
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_svar_residual_restrict(const T* __restrict__ c, const T* __restrict__ x,
                                                                   const T* __restrict__ b, T* __restrict__ coarse,
                                                                   SvarArgs a, SvarArgs ca, T scale,
                                                                   double* __restrict__ partials, int64_t lz0,
                                                                   int64_t lz1) {
-  typedef typename Vec2<T>::type T2;
   // a contiguous chunk of coarse cells per workgroup: the order of the partial sums does not depend on the grid
   const int64_t per = (ca.size + gridDim.x - 1) / gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * per;
   const int64_t hi = lo + per < ca.size ? lo + per : ca.size;
-  const int64_t Z = a.n[0], Y = a.n[1], X = a.n[2];
-  const int64_t sy = X, sz = Y * X;
   double local = 0.0;
-  for (int64_t I = lo + threadIdx.x; I < hi; I += kBlock) {
-    int64_t cid[3];
-    svar_decode(I, ca, cid);
-    T sum = T(0);
-    const int k0 = a.has[0] ? 2 : 1, k1 = a.has[1] ? 2 : 1;
-    const int64_t x0 = 2 * cid[2];
-    const int64_t xl = x0 == 0 ? X - 1 : x0 - 1, xr = x0 + 2 >= X ? 0 : x0 + 2;
-    for (int p = 0; p < k0; ++p)
-      for (int q = 0; q < k1; ++q) {
-        const int64_t z = a.has[0] ? 2 * cid[0] + p : 0, y = a.has[1] ? 2 * cid[1] + q : 0;
-        const int64_t row = z * sz + y * sy, i = row + x0;
-        const T2 xc = *(const T2*)(x + i);
-        const T2 c0 = *(const T2*)(c + i);
-        const T2 bb = *(const T2*)(b + i);
-        const T2 cxm = *(const T2*)(c + (int64_t)a.slot[2] * a.size + i);
-        const T2 cxp = *(const T2*)(c + (int64_t)(a.slot[2] + 1) * a.size + i);
-        const T wl = x[row + xl], er = x[row + xr];
-        T2 ax = c0 * xc;
-        ax.x = ax.x + cxm.x * wl;
-        ax.x = ax.x + cxp.x * xc.y;
-        ax.y = ax.y + cxm.y * xc.x;
-        ax.y = ax.y + cxp.y * er;
-        if (a.has[1]) {
-          const int64_t ym = (y == 0 ? Y - 1 : y - 1) * sy + z * sz + x0, yp = (y == Y - 1 ? 0 : y + 1) * sy + z * sz + x0;
-          const T2 cm = *(const T2*)(c + (int64_t)a.slot[1] * a.size + i);
-          const T2 cp = *(const T2*)(c + (int64_t)(a.slot[1] + 1) * a.size + i);
-          ax = ax + cm * *(const T2*)(x + ym);
-          ax = ax + cp * *(const T2*)(x + yp);
-        }
-        if (a.has[0]) {
-          const int64_t zm = (z == 0 ? Z - 1 : z - 1) * sz + y * sy + x0, zp = (z == Z - 1 ? 0 : z + 1) * sz + y * sy + x0;
-          const T2 cm = *(const T2*)(c + (int64_t)a.slot[0] * a.size + i);
-          const T2 cp = *(const T2*)(c + (int64_t)(a.slot[0] + 1) * a.size + i);
-          ax = ax + cm * *(const T2*)(x + zm);
-          ax = ax + cp * *(const T2*)(x + zp);
-        }
-        const T2 r = bb - ax;
-        if (z >= lz0 && z < lz1) local += (double)(r.x * r.x) + (double)(r.y * r.y);  // (slab form: own planes only)
-        sum = sum + r.x;
-        sum = sum + r.y;
-      }
-    coarse[I] = scale * sum;
-  }
+  for (int64_t I = lo + threadIdx.x; I < hi; I += kBlock)
+    svar_residual_restrict_cell<T, true>(c, x, b, coarse, a, ca, scale, I, lz0, lz1, local);
   const double total = block_sum(local);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
@@ -458,6 +479,99 @@ __global__ __launch_bounds__(kBlock) void k_svar_dense_batch(const T* __restrict
     acc = acc + cm[(int64_t)(a.slot[d] + 1) * a.size + i] * T(ip == j ? 1 : 0);
   }
   dense[(int64_t)blockIdx.y * a.size * a.size + e] = -(T(0) - acc);
+}
+
+// ---- the cycle of an ensemble on levels too large for one workgroup (gmg.EnsembleLaunchGMG) ---------------------------
+// Every member runs the device body of the single kernel on its own arrays; no workgroup waits for, signals or reads what
+// another one writes.  `active` (NULL: all): a member with active[member] == 0 is skipped whole -- one uniform scalar read
+// per workgroup, then no load and no store.
+
+// a sweep or the residual of every member.  NORM: workgroup p of member m leaves the sum over its kBlock cells of
+// (A x - b)^2 of the sweep's INPUT, squared and added in double (lanes of a wave, then the waves: block_sum), in
+// partials[m, p]; the map from workgroups to cells is that of the grid, which depends on the shape alone.
+template <typename T, int MODE, bool NORM>
+__global__ __launch_bounds__(kBlock) void k_svar_smooth_batch(const T* __restrict__ c, int64_t cstride,
+                                                             const T* __restrict__ x, int64_t xstride,
+                                                             const T* __restrict__ b, int64_t bstride, T* __restrict__ out,
+                                                             int64_t ostride, SvarArgs a, T omega,
+                                                             const int* __restrict__ active,
+                                                             double* __restrict__ partials) {
+  const int64_t m = blockIdx.y;
+  if (active != nullptr && active[m] == 0) return;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  T d = T(0);
+  if (i < a.size)
+    d = svar_smooth_cell<T, MODE>(c + m * cstride, MODE == 2 ? nullptr : x + m * xstride, b + m * bstride,
+                                  out + m * ostride, a, omega, i);
+  if (NORM) {  // (every thread of the workgroup arrives: the exits above are uniform)
+    const double total = block_sum((double)d * (double)d);
+    if (threadIdx.x == 0) partials[m * gridDim.x + blockIdx.x] = total;
+  }
+}
+
+// the coarse right-hand side of every member, one thread per coarse cell (no norm: the sweep before has it)
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_svar_residual_restrict_batch(const T* __restrict__ c, int64_t cstride,
+                                                                        const T* __restrict__ x, int64_t xstride,
+                                                                        const T* __restrict__ b, int64_t bstride,
+                                                                        T* __restrict__ coarse, int64_t ostride, SvarArgs a,
+                                                                        SvarArgs ca, T scale,
+                                                                        const int* __restrict__ active) {
+  const int64_t m = blockIdx.y;
+  if (active != nullptr && active[m] == 0) return;
+  const int64_t I = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (I >= ca.size) return;
+  double unused = 0.0;
+  svar_residual_restrict_cell<T, false>(c + m * cstride, x + m * xstride, b + m * bstride, coarse + m * ostride, a, ca, scale,
+                                        I, 0, 0, unused);
+}
+
+// The decision of every member before cycle k, one workgroup per member: thread t adds the partial sums t, t + kBlock, ...
+// in that order, block_sum combines the threads (lanes of a wave, then the waves) -- a fixed order for a given number of
+// partial sums.  The stop rules are those of the one-workgroup solve (vcycle_tail.hip: k_stencil_solve_batch), verbatim.
+__global__ __launch_bounds__(kBlock) void k_cycle_decide_batch(const double* __restrict__ partials, int64_t pstride,
+                                                              const double* __restrict__ partials0, int64_t p0stride,
+                                                              int nparts, double cells, int k, int maxcycles, double tol2,
+                                                              double* __restrict__ history, int64_t hstride,
+                                                              int* __restrict__ outcome, int* __restrict__ active) {
+  const int64_t m = blockIdx.x;
+  if (active[m] == 0) return;
+  double sum = 0.0;
+  for (int p = threadIdx.x; p < nparts; p += kBlock) sum += partials[m * pstride + p];
+  const double rsq = block_sum(sum) / cells;
+  double bsq = 0.0;
+  if (partials0 != nullptr) {  // (uniform)
+    double sum0 = 0.0;
+    for (int p = threadIdx.x; p < nparts; p += kBlock) sum0 += partials0[m * p0stride + p];
+    bsq = block_sum(sum0) / cells;
+  }
+  if (threadIdx.x != 0) return;
+  double* h = history + m * hstride;
+  if (partials0 != nullptr)
+    h[0] = bsq;
+  else
+    bsq = h[0];
+  const double prev = h[k];
+  h[1 + k] = rsq;
+  int why = -1;
+  if (!__builtin_isfinite(rsq) || !__builtin_isfinite(bsq)) why = 3;
+  else if (rsq <= tol2 * bsq) why = 0;
+  else if (k == maxcycles) why = 1;
+  else if (k >= 3 && rsq >= (0.98 * 0.98) * prev) why = 2;
+  if (why >= 0) {
+    outcome[2 * m] = k;
+    outcome[2 * m + 1] = why;
+    active[m] = 0;
+  }
+}
+
+// the members still active, counted by ONE workgroup in a launch of its own (the launch above has finished: nothing here
+// is read while another workgroup writes it); integers: exact in any order
+__global__ __launch_bounds__(kBlock) void k_count_active(const int* __restrict__ active, int nbatch, int* __restrict__ count) {
+  double n = 0.0;
+  for (int m = threadIdx.x; m < nbatch; m += kBlock) n += active[m] != 0 ? 1.0 : 0.0;
+  const double total = block_sum(n);
+  if (threadIdx.x == 0) *count = (int)total;
 }
 
 // max |a - b| and max |b| over n entries (recognition of a known operator from its coefficient arrays: one pass over
@@ -783,6 +897,124 @@ static int svar_dense_batch(const T* coeffs, int64_t coeff_stride, const int64_t
   return check_launch("k_svar_dense_batch");
 }
 
+// partial sums per member of a batched sweep: one per workgroup of kBlock cells (a function of the shape alone)
+static int64_t svar_smooth_batch_parts(const int64_t* shape, int ndim) {
+  if (!shape || ndim < 1 || ndim > 3) return 0;
+  int64_t size = 1;
+  for (int i = 0; i < ndim; ++i) {
+    if (shape[i] < 1 || shape[i] > (int64_t)1 << 24) return 0;
+    size *= shape[i];
+    if (size > (int64_t)1 << 24) return 0;
+  }
+  return (size + kBlock - 1) / kBlock;
+}
+
+static int svar_vector_stride(const char* what, const char* name, int64_t stride, int64_t size) {
+  if (stride < size) {
+    set_error("%s: %s_stride %lld is smaller than a member (%lld)", what, name, (long long)stride, (long long)size);
+    return ODIL_E_INVAL;
+  }
+  return 0;
+}
+
+template <typename T>
+static int svar_smooth_batch(const T* coeffs, int64_t coeff_stride, const T* x, int64_t x_stride, const T* b, int64_t b_stride,
+                             T* out, int64_t out_stride, const int64_t* shape, int ndim, int nbatch, T omega, int mode,
+                             const int* active, double* partials, void* stream) {
+  const char* what = "stencil_var_smooth_batch";
+  SvarArgs a;
+  if (int e = svar_batch_fill(a, shape, ndim, nbatch, coeff_stride, what)) return e;
+  if (mode != 0 && mode != 1) {
+    set_error("%s: mode %d (0: sweep, 1: residual)", what, mode);
+    return ODIL_E_INVAL;
+  }
+  if (!coeffs || (!x && mode != 0) || !b || !out || x == out) {  // (x == NULL with mode 0: the sweep starts from zero)
+    set_error("%s: null pointer or in-place sweep", what);
+    return ODIL_E_INVAL;
+  }
+  if (partials && mode != 0) {
+    set_error("%s: partial sums go with mode 0", what);
+    return ODIL_E_INVAL;
+  }
+  if (x)
+    if (int e = svar_vector_stride(what, "x", x_stride, a.size)) return e;
+  if (int e = svar_vector_stride(what, "b", b_stride, a.size)) return e;
+  if (int e = svar_vector_stride(what, "out", out_stride, a.size)) return e;
+  const dim3 grid((unsigned)((a.size + kBlock - 1) / kBlock), (unsigned)nbatch);
+#define ODIL_SMOOTH_BATCH(MODE, NORM)                                                                                        \
+  hipLaunchKernelGGL((k_svar_smooth_batch<T, MODE, NORM>), grid, dim3(kBlock), 0, (hipStream_t)stream, coeffs, coeff_stride, \
+                     x, x_stride, b, b_stride, out, out_stride, a, omega, active, partials)
+  if (mode == 1)
+    ODIL_SMOOTH_BATCH(1, false);
+  else if (!x && partials)
+    ODIL_SMOOTH_BATCH(2, true);
+  else if (!x)
+    ODIL_SMOOTH_BATCH(2, false);
+  else if (partials)
+    ODIL_SMOOTH_BATCH(0, true);
+  else
+    ODIL_SMOOTH_BATCH(0, false);
+#undef ODIL_SMOOTH_BATCH
+  return check_launch("k_svar_smooth_batch");
+}
+
+template <typename T>
+static int svar_residual_restrict_batch(const T* coeffs, int64_t coeff_stride, const T* x, int64_t x_stride, const T* b,
+                                        int64_t b_stride, T* coarse, int64_t coarse_stride, const int64_t* shape, int ndim,
+                                        int nbatch, T scale, const int* active, void* stream) {
+  const char* what = "stencil_var_residual_restrict_batch";
+  SvarArgs a, ca;
+  if (int e = svar_batch_fill(a, shape, ndim, nbatch, coeff_stride, what)) return e;
+  if (int e = svar_coarse(a, ca, what)) return e;
+  if (!coeffs || !x || !b || !coarse) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (int e = svar_vector_stride(what, "x", x_stride, a.size)) return e;
+  if (int e = svar_vector_stride(what, "b", b_stride, a.size)) return e;
+  if (int e = svar_vector_stride(what, "coarse", coarse_stride, ca.size)) return e;
+  if (nbatch > 1 && ((coeff_stride | x_stride | b_stride) & 1)) {  // (the two children along x are one aligned pack)
+    set_error("%s: odd stride between members (coeff %lld, x %lld, b %lld): the cell pairs are read as aligned packs", what,
+              (long long)coeff_stride, (long long)x_stride, (long long)b_stride);
+    return ODIL_E_INVAL;
+  }
+  const dim3 grid((unsigned)((ca.size + kBlock - 1) / kBlock), (unsigned)nbatch);
+  hipLaunchKernelGGL((k_svar_residual_restrict_batch<T>), grid, dim3(kBlock), 0, (hipStream_t)stream, coeffs, coeff_stride, x,
+                     x_stride, b, b_stride, coarse, coarse_stride, a, ca, scale, active);
+  return check_launch("k_svar_residual_restrict_batch");
+}
+
+static int cycle_decide_batch(const double* partials, int64_t partials_stride, const double* partials0,
+                              int64_t partials0_stride, int nparts, int nbatch, int64_t cells, int k, int maxcycles,
+                              double tol, double* history, int64_t history_stride, int* outcome, int* active, int* nactive,
+                              void* stream) {
+  const char* what = "stencil_cycle_decide_batch";
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1..65535: the member is a grid dimension)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (!partials || !history || !outcome || !active || !nactive) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (nparts < 1 || nparts > kMaxPartials || cells < 1 || partials_stride < nparts || (partials0 && partials0_stride < nparts)) {
+    set_error("%s: %d partial sums %lld / %lld apart for %lld cells", what, nparts, (long long)partials_stride,
+              (long long)partials0_stride, (long long)cells);
+    return ODIL_E_INVAL;
+  }
+  if (maxcycles < 0 || k < 0 || k > maxcycles || history_stride < (int64_t)maxcycles + 2 || !(tol >= 0.0)) {
+    set_error("%s: cycle %d of at most %d, tolerance %g, history_stride %lld (>= maxcycles + 2)", what, k, maxcycles, tol,
+              (long long)history_stride);
+    return ODIL_E_INVAL;
+  }
+  hipLaunchKernelGGL(k_cycle_decide_batch, dim3((unsigned)nbatch), dim3(kBlock), 0, (hipStream_t)stream, partials,
+                     partials_stride, partials0, partials0_stride, nparts, (double)cells, k, maxcycles, tol * tol, history,
+                     history_stride, outcome, active);
+  if (int e = check_launch("k_cycle_decide_batch")) return e;
+  hipLaunchKernelGGL(k_count_active, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, active, nbatch, nactive);
+  return check_launch("k_count_active");
+}
+
 }  // namespace odil
 
 using namespace odil;
@@ -865,5 +1097,41 @@ int odil_stencil_dense_batch_f64(const double* coeffs, int64_t coeff_stride, con
 int odil_stencil_dense_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shape, int ndim, int nbatch,
                                  float* dense, void* stream) {
   return svar_dense_batch<float>(coeffs, coeff_stride, shape, ndim, nbatch, dense, stream);
+}
+int odil_stencil_var_smooth_batch_f64(const double* coeffs, int64_t coeff_stride, const double* x, int64_t x_stride,
+                                      const double* b, int64_t b_stride, double* out, int64_t out_stride, const int64_t* shape,
+                                      int ndim, int nbatch, double omega, int mode, const int* active, double* partials,
+                                      void* stream) {
+  return svar_smooth_batch<double>(coeffs, coeff_stride, x, x_stride, b, b_stride, out, out_stride, shape, ndim, nbatch, omega,
+                                   mode, active, partials, stream);
+}
+int odil_stencil_var_smooth_batch_f32(const float* coeffs, int64_t coeff_stride, const float* x, int64_t x_stride,
+                                      const float* b, int64_t b_stride, float* out, int64_t out_stride, const int64_t* shape,
+                                      int ndim, int nbatch, float omega, int mode, const int* active, double* partials,
+                                      void* stream) {
+  return svar_smooth_batch<float>(coeffs, coeff_stride, x, x_stride, b, b_stride, out, out_stride, shape, ndim, nbatch, omega,
+                                  mode, active, partials, stream);
+}
+int64_t odil_stencil_var_smooth_batch_parts(const int64_t* shape, int ndim) { return svar_smooth_batch_parts(shape, ndim); }
+int odil_stencil_var_residual_restrict_batch_f64(const double* coeffs, int64_t coeff_stride, const double* x, int64_t x_stride,
+                                                 const double* b, int64_t b_stride, double* coarse, int64_t coarse_stride,
+                                                 const int64_t* shape, int ndim, int nbatch, double scale, const int* active,
+                                                 void* stream) {
+  return svar_residual_restrict_batch<double>(coeffs, coeff_stride, x, x_stride, b, b_stride, coarse, coarse_stride, shape,
+                                              ndim, nbatch, scale, active, stream);
+}
+int odil_stencil_var_residual_restrict_batch_f32(const float* coeffs, int64_t coeff_stride, const float* x, int64_t x_stride,
+                                                 const float* b, int64_t b_stride, float* coarse, int64_t coarse_stride,
+                                                 const int64_t* shape, int ndim, int nbatch, float scale, const int* active,
+                                                 void* stream) {
+  return svar_residual_restrict_batch<float>(coeffs, coeff_stride, x, x_stride, b, b_stride, coarse, coarse_stride, shape,
+                                             ndim, nbatch, scale, active, stream);
+}
+int odil_stencil_cycle_decide_batch(const double* partials, int64_t partials_stride, const double* partials0,
+                                    int64_t partials0_stride, int nparts, int nbatch, int64_t cells, int k, int maxcycles,
+                                    double tol, double* history, int64_t history_stride, int* outcome, int* active,
+                                    int* nactive, void* stream) {
+  return cycle_decide_batch(partials, partials_stride, partials0, partials0_stride, nparts, nbatch, cells, k, maxcycles, tol,
+                            history, history_stride, outcome, active, nactive, stream);
 }
 }

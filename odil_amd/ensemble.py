@@ -147,7 +147,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
                             lr=args.lr, lrs=lrs, epoch_start=args.epoch_start, **kwargs)
 
 
-def optimize_newton_ensemble(args, problems, states, callback=None, linearize="batched", time_linearize=False):
+def optimize_newton_ensemble(args, problems, states, callback=None, linearize="batched", time_linearize=False,
+                             form="workgroup"):
     """Newton on B small Poisson problems AT ONCE: every epoch is ONE launch that runs the whole Newton step of all
     members, one workgroup per member (gmg.EnsembleGMG.newton_step: residual, nested-iteration start, V-cycles down to the
     tolerance, the convergence decision and the update, no host read-back in between).  Every member ends at the Newton
@@ -183,9 +184,22 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
     Returns ([arrays of member b], optinfo); optinfo.cycles / .residuals: [B, epochs] cycles run and final residual norms;
     optinfo.route: "poisson" or "stencil"; optinfo.linearize_launches: [epochs] Jacobian launches made per step (zeros on
     the Poisson route, which has no linearisation); optinfo.linearize_ms: [epochs] device time of the linearisations, None
-    unless time_linearize."""
+    unless time_linearize; optinfo.form: the form that ran.
+
+    form: 'workgroup' (the default) is all of the above, its refusals included: every member fits ONE workgroup
+    (`gmg.EnsembleGMG.max_cells` cells: 32^3, 128^2).  'launches' runs members of any size that
+    `fused.newton_launches_refusal` admits (256^2, 64^3, 128^3, ...): ALL members take the stencil route
+    (optinfo.route == "stencil") with `gmg.EnsembleLaunchGMG` -- Poisson members included, whose Jacobian is a (2 d + 1)-point
+    stencil like any other -- where every phase of the cycle on the levels too large for one workgroup is one launch that
+    covers all members, the levels below are walked by one workgroup per member, and the convergence decision of every
+    member stays on the device (one int per cycle read back for the whole ensemble).  `solver.method` is "gmg-vcycle
+    (variable coefficients), batched launches".  Still no fallback to the normal equations, and damping stays refused.
+    'auto': 'workgroup' where its checks admit the members, 'launches' otherwise.  Any other value raises ValueError before
+    any member is looked at."""
     from . import fused
 
+    if form not in ("workgroup", "launches", "auto"):
+        raise ValueError("optimize_newton_ensemble: form '{}' is none of 'workgroup', 'launches', 'auto'".format(form))
     linsolver = getattr(args, "linsolver", "direct")
     if linsolver not in ("direct", "multigrid"):
         raise ValueError("optimize_newton_ensemble: linsolver '{}' (the one-workgroup Newton solves serve 'direct' and "
@@ -196,17 +210,30 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         raise ValueError("optimize_newton_ensemble: damping (linsolver_damp / linsolver_dampdiag) is not served: the cycles "
                          "solve M d = r, which has the solution of the normal equations only without it")
     refused = dict(poisson=None, stencil=None)  # per route the first (member, reason) it refuses while the other admits
+    launches = dict(refused=None, needed=form == "launches")  # (form 'launches' / 'auto': what the batched launches say)
 
     def describe(b, problem, state, refuse):
         kind = _plain_field(b, problem, state, refuse)
         cshape, dtype = kind["cshape"], kind["dtype"]
         npdt = np.float64 if dtype == torch.float64 else np.float32
+        if form != "workgroup":
+            reason = fused.newton_launches_refusal(cshape, dtype)
+            if reason is not None and form == "launches":
+                refuse(b, reason)
+            if reason is not None and launches["refused"] is None:
+                launches["refused"] = (b, reason)
+            if form == "launches":
+                return kind
         # (which route runs is known only once the operators are probed: a member that neither admits is refused here, one
         # that a single route refuses once the route is known -- still before any state changes)
         reasons = dict(poisson=fused.newton_refusal(cshape, [npdt(v) ** 2 for v in kind["spacing"]], dtype),
                        stencil=fused.newton_stencil_refusal(cshape, dtype))
         if None not in reasons.values():
-            refuse(b, reasons["poisson"])
+            if form == "auto" and launches["refused"] is None:  # (no one-workgroup route: the batched launches serve it)
+                launches["needed"] = True
+                return kind
+            refuse(b, reasons["poisson"] if form == "workgroup" else "{}; as batched launches: {}".format(
+                reasons["poisson"], launches["refused"][1]))
         for route, reason in reasons.items():
             if reason is not None and refused[route] is None:
                 refused[route] = (b, reason)
@@ -219,8 +246,13 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         ev = getattr(problem, "_fused", None)
         evaluators.append(ev if ev is not None and ev.nlvl == 1 else None)
     route = "stencil" if any(ev is None for ev in evaluators) else "poisson"
-    if refused[route] is not None:
+    if form == "auto" and refused[route] is not None and launches["refused"] is None:
+        launches["needed"] = True  # (the one-workgroup route these operators take refuses a member)
+    if launches["needed"]:
+        route = "stencil"
+    elif refused[route] is not None:
         refuse(*refused[route])
+    ran = "launches" if launches["needed"] else "workgroup"
     if route == "poisson":  # (one launch per epoch: the whole Newton step on the packed iterate and right-hand sides)
         ev = evaluators[0]
         solver = gmg.EnsembleGMG(ev.cshape, ev.h2, ev.dtype, ev.device, len(evaluators))
@@ -229,14 +261,16 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         def step(u, first, tol, maxcycles):  # (no linearisation: nothing to report)
             solver.newton_step(u, rhs, tol=tol, maxcycles=maxcycles)
     else:
-        solver, step = _stencil_route(args, problems, states, kind, linearize, time_linearize)
-    return _newton_loop(args, problems, states, callback, linsolver, kind["dtype"], route, solver, step)
+        solver, step = _stencil_route(args, problems, states, kind, linearize, time_linearize,
+                                      gmg.EnsembleLaunchGMG if ran == "launches" else gmg.EnsembleGMG)
+    return _newton_loop(args, problems, states, callback, linsolver, kind["dtype"], route, solver, step, ran)
 
 
-def _stencil_route(args, problems, states, kind, linearize="batched", timed=False):
+def _stencil_route(args, problems, states, kind, linearize="batched", timed=False, hierarchy=gmg.EnsembleGMG):
     """(solver, step) of the route for members that are not all the Poisson operator (the docstring of
     `optimize_newton_ensemble`); the members have passed its checks, `kind` is what they share.  Linearises once here,
     before any state changes: a member that has no stencil Jacobian is named first.  Without an epoch to run, no solver.
+    hierarchy: the class whose `from_coeffs` makes the solver (gmg.EnsembleGMG, or gmg.EnsembleLaunchGMG for form 'launches').
     step returns (Jacobian launches made, the pair of events around the linearisation or None)."""
     nb, cshape, dtype, device = len(problems), kind["cshape"], kind["dtype"], kind["device"]
     ndim = len(cshape)
@@ -277,7 +311,7 @@ def _stencil_route(args, problems, states, kind, linearize="batched", timed=Fals
     solver, first = None, None
     if args.epochs > args.epoch_start:
         first = linearise(stage)
-        solver = gmg.EnsembleGMG.from_coeffs(stage)
+        solver = hierarchy.from_coeffs(stage)
     del stage
 
     def step(u, is_first, tol, maxcycles):
@@ -437,8 +471,9 @@ def _held_linearizer(problems, states, kind, who):
     return held
 
 
-def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solver, step):
-    """What the Newton routes share.  route: "poisson" / "stencil"; solver: its gmg.EnsembleGMG (None only when no epoch
+def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solver, step, form="workgroup"):
+    """What the Newton routes share.  route: "poisson" / "stencil"; form: "workgroup" / "launches", reported as
+    optinfo.form; solver: its gmg.EnsembleGMG or gmg.EnsembleLaunchGMG (None only when no epoch
     runs); step(u, first, tol, maxcycles) advances the packed iterate u [B, *cshape] by one Newton step of every member
     (first: at args.epoch_start) and leaves solver.outcome / status(b) behind; it returns None or (Jacobian launches it
     made, None or the pair of timing events around its linearisation)."""
@@ -488,4 +523,4 @@ def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solv
         torch.cuda.synchronize()
         linearize_ms = np.array([pair[0].elapsed_time(pair[1]) for pair in events])
     return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver,
-                                      route=route, linearize_launches=launches, linearize_ms=linearize_ms)
+                                      route=route, form=form, linearize_launches=launches, linearize_ms=linearize_ms)

@@ -540,6 +540,39 @@ def newton_stencil_refusal(cshape, dtype):
     return None
 
 
+def newton_launches_refusal(cshape, dtype):
+    """Why a single-field (2 d + 1)-point operator on these cells is not a member of a Newton ensemble run as batched
+    launches (gmg.EnsembleLaunchGMG), or None -- as far as the shape alone tells: 1-D to 3-D, float64 / float32, extents
+    >= 4 (the limit of `gmg.recognise_stencil`), at most `EnsembleLaunchGMG.max_member_cells` cells (the limit per member
+    of the batched launches, below 2^31), and levels that CAN end in a one-workgroup tail (every axis halved while it is
+    even): a level of at most `tail_max_cells` cells below the finest, from which at most `EnsembleGMG.max_levels` levels
+    lead to at most `EnsembleGMG.max_coarsest` unknowns.  Which levels the coefficients ask for, `from_coeffs` reports.
+    Host arithmetic only."""
+    from .gmg import EnsembleLaunchGMG
+
+    cshape = tuple(int(n) for n in cshape)
+    ndim = len(cshape)
+    if not 1 <= ndim <= 3:
+        return "{}-D grid: the batched Newton solves run 1-D to 3-D grids".format(ndim)
+    if dtype not in (torch.float64, torch.float32):
+        return "dtype {}: the kernels run float64 and float32".format(dtype)
+    if any(n < 4 for n in cshape):
+        return "extents {}: a stencil operator is recognised on 4 cells per axis or more".format(cshape)
+    cells = math.prod(cshape)
+    if cells > EnsembleLaunchGMG.max_member_cells:
+        return "{} cells are above the limit per member of the batched Newton solves ({})".format(
+            cells, EnsembleLaunchGMG.max_member_cells)
+    shapes = [cshape]
+    while EnsembleLaunchGMG._tail_room(shapes, EnsembleLaunchGMG.tail_max_cells) and any(
+            n % 2 == 0 and n // 2 >= 2 for n in shapes[-1]):
+        shapes.append(tuple(n // 2 if n % 2 == 0 and n // 2 >= 2 else n for n in shapes[-1]))
+    try:
+        EnsembleLaunchGMG.split(shapes)
+    except ValueError as e:
+        return str(e).split(": ", 1)[1]
+    return None
+
+
 def _close(a, b, rtol):
     scale = max(float(b.abs().max()), 1e-300)
     return float((a - b).abs().max()) <= rtol * scale

@@ -745,9 +745,7 @@ class EnsembleGMG:
             raise ValueError("EnsembleGMG.from_coeffs: coefficients {} are not [B, 2 d + 1, *shape] with d <= 3".format(
                 tuple(coeffs.shape)))
         shape = tuple(int(n) for n in coeffs.shape[2:])
-        if math.prod(shape) > self.max_cells:
-            raise ValueError("EnsembleGMG.from_coeffs: {} cells are above the limit of the one-workgroup solves ({})".format(
-                math.prod(shape), self.max_cells))
+        self._check_fine(shape)
         self.nbatch, self.dtype, self.device, self.ndim = nb, coeffs.dtype, coeffs.device, ndim
         self.nu1 = PoissonGMG.nu_default[0] if nu1 is None else nu1
         self.nu2 = PoissonGMG.nu_default[1] if nu2 is None else nu2
@@ -755,6 +753,20 @@ class EnsembleGMG:
         self._min_size, self._shape0 = min_size, shape
         self._strength = torch.empty((nb, 2 * ndim), dtype=self.dtype, device=self.device)
         self._plan(coeffs.reshape(nb, -1))
+
+    def _check_fine(self, shape):
+        """ValueError when members of this finest shape cannot be served (before anything is allocated)."""
+        if math.prod(shape) > self.max_cells:
+            raise ValueError("EnsembleGMG.from_coeffs: {} cells are above the limit of the one-workgroup solves ({})".format(
+                math.prod(shape), self.max_cells))
+
+    def _may_coarsen(self, shapes):
+        """Whether a hierarchy that has the levels `shapes` so far may get one more."""
+        return len(shapes) < self.max_levels
+
+    def _pack(self, levels):
+        """[B, ncoeff]: the levels [B, (2 d + 1) cells of the level] of every member, one after another."""
+        return torch.cat(levels, dim=1).contiguous()
 
     def _work_elements(self, shapes):
         """Work elements per member of the launch that walks these levels; ValueError when one workgroup does not."""
@@ -810,7 +822,7 @@ class EnsembleGMG:
         """Builds shapes, the packed hierarchy [B, ncoeff] and the inverses from the finest coefficients
         [B, (2 d + 1) cells]; the object is changed only once everything stands."""
         shapes, halves, levels = [self._shape0], [], [fine]
-        while len(shapes) < self.max_levels:
+        while self._may_coarsen(shapes):
             halve = self._decide(levels[-1], len(shapes) - 1, shapes[-1])
             if halve is None:
                 break
@@ -819,7 +831,7 @@ class EnsembleGMG:
             halves.append(halve)
         self._work_elements(shapes)  # (before the dense matrices of a coarsest level that is too large are formed)
         ninv = math.prod(shapes[-1])
-        coeffs = torch.cat(levels, dim=1).contiguous()
+        coeffs = self._pack(levels)
         dense = torch.empty((self.nbatch, ninv, ninv), dtype=self.dtype, device=self.device)
         inv = torch.empty_like(dense)
         self._invert(levels[-1], shapes[-1], dense, inv)
@@ -858,7 +870,7 @@ class EnsembleGMG:
             self.fine.copy_(coeffs)
         nlev = len(self.shapes)
         for lvl in range(nlev):
-            halve = self._decide(self.level(lvl), lvl, self.shapes[lvl]) if lvl + 1 < self.max_levels else None
+            halve = self._decide(self.level(lvl), lvl, self.shapes[lvl]) if self._may_coarsen(self.shapes[:lvl + 1]) else None
             if halve != (self.halve[lvl] if lvl + 1 < nlev else None):
                 self._plan(self.level(0).clone())  # (other levels than before)
                 return self
@@ -896,6 +908,253 @@ class EnsembleGMG:
         bn = math.sqrt(max(float(hist[0]), 0.0) * self.cells) if hist[0] == hist[0] else float("nan")
         return dict(residual=res, bnorm=bn, niter=k, converged=why == 0, stagnated=bool(why == 2 and res < bn),
                     method=self.method)
+
+
+def mean_children(r, loc, out=None):
+    """The mean of the merged children: r [..., *shape] -> [..., *shape halved on the 'c' axes of loc] (the R of the
+    aggregation-built coarse operators, `StencilGMG.restrict`).  Axis by axis the sum of the even and the odd cells, then
+    one scaling: elementwise launches only, so the bits of a member do not depend on what else the array holds."""
+    lead = r.dim() - len(loc)
+    for a, l in enumerate(loc):
+        if l == "c":
+            even, odd = [slice(None)] * r.dim(), [slice(None)] * r.dim()
+            even[lead + a], odd[lead + a] = slice(0, None, 2), slice(1, None, 2)
+            r = r[tuple(even)] + r[tuple(odd)]
+    return torch.mul(r, 1.0 / 2 ** loc.count("c"), out=out)
+
+
+class EnsembleLaunchGMG(EnsembleGMG):
+    """B systems of ONE shape that are too large for one workgroup each, solved side by side: the hierarchy of
+    `EnsembleGMG.from_coeffs` (the same batched set-up, member 0's coarsening decisions, ValueError for a member that
+    decides otherwise), split in two.  The finest level and every further level of more than `tail_max_cells` cells are
+    LAUNCH levels: each phase of `StencilGMG`'s cycle is one launch there that covers all members (the member on
+    blockIdx.y: odil_stencil_var_smooth_batch, odil_stencil_var_residual_restrict_batch, `ops.interp_add` on [B, *shape]).
+    The levels below form the TAIL, at most `max_levels` levels down to at most `max_coarsest` unknowns, walked by one
+    workgroup per member (odil_stencil_solve_batch).  ValueError naming the levels when they do not split that way.
+
+    The cycle is StencilGMG's: nu1 / nu2 sweeps with `jacobi_weights`, the mean of the merged children down (a transition
+    that merges some axes only: the residual, then `mean_children`), `interp_add` up, in 3-D two cycles on level 1.  A
+    coarse correction on the tail's top level is odil_stencil_solve_batch with start 0, tol 0 and maxcycles 1 (2 where
+    level 1 is the tail's top in 3-D).  A cycle of member b reads its iterate from x and only its LAST post-smoothing
+    sweep writes x; everything in between is scratch.
+
+    `solve` keeps the contract of `EnsembleGMG.solve` -- start codes, stop rules, `status`, `history`, `outcome` -- with
+    the decision on the device: the first pre-smoothing sweep of cycle k leaves partial sums of (A x_k - b)^2, and
+    odil_stencil_cycle_decide_batch turns them into history[b, 1 + k], applies the stop rules and clears active[b] of a
+    member that stops.  Every later launch skips such a member whole, so its x stays x_k.  The host reads ONE int per cycle,
+    the number of active members (copied while the rest of the cycle runs), and nothing else until `history` and `outcome`
+    after the solve.  FROZEN MEMBERS STILL RUN THROUGH THE TAIL LAUNCH and through `interp_add` (neither can skip
+    members); what these compute for them lands in scratch and is discarded.  A member's iterate, history and outcome do
+    not depend on nbatch, on its position, or on when other members stop.
+
+    Attributes as `EnsembleGMG.core`; besides: nlaunch (number of launch levels), tail_shapes.  `newton_step` is not
+    served (the Newton driver solves M d = f and updates on its own)."""
+
+    tail_max_cells = EnsembleGMG.max_cells  # levels of at most this many cells go to the one-workgroup tail (never the finest)
+    method_name = "gmg-vcycle (variable coefficients), batched launches"
+    max_member_cells = 1 << 24  # (the member is a grid dimension of the batched launches: their limit per member)
+
+    def __init__(self, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None):
+        self._strength = None
+        self.method = self.method_name
+        if tail_max_cells is not None:
+            self.tail_max_cells = int(tail_max_cells)
+        for name, nu in (("nu1", nu1), ("nu2", nu2)):
+            if nu is not None and not 1 <= nu <= 4:
+                raise ValueError("EnsembleLaunchGMG: {} = {} (1..4 sweeps: the first one carries the norm, the tail takes at "
+                                 "most 4)".format(name, nu))
+        self._init_coeffs(coeffs, nu1, nu2, min_size)
+
+    @classmethod
+    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None):
+        """coeffs [B, 2 d + 1, *shape]; tail_max_cells: None for the class's."""
+        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size, tail_max_cells=tail_max_cells)
+
+    @classmethod
+    def split(cls, shapes, tail_max_cells=None):
+        """The number of launch levels of a hierarchy `shapes` (fine to coarse): the finest, and the further levels while
+        they have more than tail_max_cells cells; the rest is the tail.  ValueError naming the levels when there is no tail,
+        or one workgroup does not walk it (host arithmetic only)."""
+        limit = cls.tail_max_cells if tail_max_cells is None else tail_max_cells
+        shapes = [tuple(int(n) for n in s) for s in shapes]
+        first = next((l for l in range(1, len(shapes)) if math.prod(shapes[l]) <= limit), len(shapes))
+        tail = shapes[first:]
+        if not tail:
+            raise ValueError("EnsembleLaunchGMG: levels {} have no level of at most {} cells below the finest for the "
+                             "one-workgroup tail".format(shapes, limit))
+        if len(tail) > cls.max_levels or math.prod(tail[-1]) > cls.max_coarsest:
+            raise ValueError("EnsembleLaunchGMG: the tail {} of the levels {} is not walked by one workgroup (at most {} "
+                             "levels, a coarsest level of at most {} unknowns)".format(tail, shapes, cls.max_levels,
+                                                                                      cls.max_coarsest))
+        return first
+
+    @classmethod
+    def plan(cls, shape, tail_max_cells=None, min_size=2):
+        """(launch shapes, tail shapes) of members whose every transition merges every axis (what coefficients of equal
+        strength along the axes decide): StencilGMG's rule, stopped where the tail has `max_levels` levels.  Host
+        arithmetic only; ValueError as `split`."""
+        limit = cls.tail_max_cells if tail_max_cells is None else tail_max_cells
+        shapes = [tuple(int(n) for n in shape)]
+        while cls._tail_room(shapes, limit) and all(n % 2 == 0 and n // 2 >= min_size for n in shapes[-1]):
+            shapes.append(tuple(n // 2 for n in shapes[-1]))
+        first = cls.split(shapes, limit)
+        return shapes[:first], shapes[first:]
+
+    @classmethod
+    def _tail_room(cls, shapes, limit):
+        first = next((l for l in range(1, len(shapes)) if math.prod(shapes[l]) <= limit), len(shapes))
+        return len(shapes) - first < cls.max_levels
+
+    def _check_fine(self, shape):
+        if math.prod(shape) > self.max_member_cells:
+            raise ValueError("EnsembleLaunchGMG.from_coeffs: {} cells per member are above the limit of the batched launches "
+                             "({})".format(math.prod(shape), self.max_member_cells))
+
+    def _may_coarsen(self, shapes):
+        return self._tail_room(shapes, self.tail_max_cells)
+
+    def _pack(self, levels):
+        """(rows of an even number of elements: the batched residual + restriction reads cell pairs as aligned packs)"""
+        row = sum(level.shape[1] for level in levels)
+        if row % 2:
+            levels = levels + [torch.zeros((self.nbatch, 1), dtype=self.dtype, device=self.device)]
+        return torch.cat(levels, dim=1).contiguous()
+
+    def _work_elements(self, shapes):
+        first = self.split(shapes, self.tail_max_cells)
+        need = ops.stencil_solve_batch_work(shapes[first:])
+        if not need:
+            raise ValueError("EnsembleLaunchGMG: the tail {} is not walked by one workgroup".format(shapes[first:]))
+        return need
+
+    def _finish(self, shapes, halves, coeffs, inv):
+        need = self._work_elements(shapes)
+        nb, dtype, device = self.nbatch, self.dtype, self.device
+        self.shapes, self.halve = shapes, halves
+        self.locs = ["".join("c" if on else "." for on in halve) for halve in halves]
+        self.coeffs, self.inv, self.cells = coeffs, inv, math.prod(shapes[0])
+        self.nlaunch = first = self.split(shapes, self.tail_max_cells)
+        self.tail_shapes = shapes[first:]
+        self.work = torch.empty((nb, need), dtype=dtype, device=device)
+        sizes = [(2 * self.ndim + 1) * math.prod(s) for s in shapes]
+        tail_coeffs = coeffs[:, sum(sizes[:first]):sum(sizes)]
+        self._launch = ops.stencil_solve_batch_plan(tail_coeffs, self.tail_shapes, halves[first:], nb, self.work, inv,
+                                                    self.wpre, self.wpost)
+
+        def arrays(lvl):
+            return torch.zeros((nb,) + shapes[lvl], dtype=dtype, device=device)
+
+        # per launch level: iterate (level 0: the caller's x), right-hand side (level 0: the caller's b), two scratch
+        # arrays; the tail's top level: iterate and right-hand side
+        self._x = [None] + [arrays(l) for l in range(1, first + 1)]
+        self._b = [None] + [arrays(l) for l in range(1, first + 1)]
+        self._s = [(arrays(l), arrays(l)) for l in range(first)]
+        nparts = ops.stencil_var_smooth_batch_parts(shapes[0])
+        self._partials = torch.zeros((nb, nparts), dtype=torch.float64, device=device)
+        self._partials0 = torch.zeros((nb, nparts), dtype=torch.float64, device=device)
+        self._active = torch.ones(nb, dtype=torch.int32, device=device)
+        self._nactive = torch.zeros(1, dtype=torch.int32, device=device)
+        self._nactive_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._decided = torch.cuda.Event()
+        self._tail_out = (torch.zeros((nb, 4), dtype=torch.float64, device=device),
+                          torch.zeros((nb, 2), dtype=torch.int32, device=device))
+        self._out = dict()
+        self.history = None
+        self.outcome = None
+        missing = [name for name in self.core if not hasattr(self, name)]
+        assert not missing, "EnsembleLaunchGMG lacks {}".format(missing)
+
+    def _tail_solve(self, start, maxcycles):
+        """The tail's top level: x <- its nested-iteration start (start 2, maxcycles 0) or `maxcycles` cycles from zero
+        (start 0), for every member, frozen ones included (their result is discarded)."""
+        top = self.nlaunch
+        self._launch(self._x[top], self._b[top], self._tail_out[0], self._tail_out[1], start, 0, maxcycles, 0.0)
+        return self._x[top]
+
+    def _cycle(self, lvl, x, b, zero=False, decide=None):
+        """One cycle of every active member on launch level lvl, from x (zero: from the zero vector) into x.
+        decide: called after the first pre-smoothing sweep, which then leaves its partial sums; True ends the cycle there."""
+        c, active = self.level(lvl), self._active
+        scratch = self._s[lvl]
+        cur = None if zero else x
+        for j, w in enumerate(self.wpre):
+            dst = scratch[j % 2]
+            ops.stencil_var_smooth_batch(c, cur, b, w, dst, active=active,
+                                         partials=self._partials if decide is not None and j == 0 else None)
+            cur = dst
+            if decide is not None and j == 0 and decide():
+                return
+        other = scratch[len(self.wpre) % 2]
+        bc = self._b[lvl + 1]
+        if all(self.halve[lvl]):
+            ops.stencil_var_residual_restrict_batch(c, cur, b, 1.0 / 2 ** self.ndim, bc, active=active)
+        else:
+            ops.stencil_var_smooth_batch(c, cur, b, 0.0, other, mode=1, active=active)
+            mean_children(other, self.locs[lvl], out=bc)
+        twice = lvl == 0 and self.ndim == 3 and len(self.shapes) > 2  # (`StencilGMG.finish_cycle`)
+        if lvl + 1 == self.nlaunch:
+            xc = self._tail_solve(0, 2 if twice else 1)
+        else:
+            xc = self._x[lvl + 1]
+            self._cycle(lvl + 1, xc, bc, zero=True)
+            if twice:
+                self._cycle(lvl + 1, xc, bc)
+        ops.interp_add(xc, "." + self.locs[lvl], add=cur, out=other)  # x + P x_c
+        cur, other = other, cur
+        for j, w in enumerate(self.wpost):
+            dst = x if j == len(self.wpost) - 1 else other
+            ops.stencil_var_smooth_batch(c, cur, b, w, dst, active=active)
+            cur, other = dst, cur
+
+    def _nested(self, b, x):
+        """The nested-iteration start into x: b restricted down the launch levels, the tail's own start on its top level,
+        then every launch level one cycle from the interpolated solution of the level below."""
+        for lvl in range(self.nlaunch):
+            mean_children(b if lvl == 0 else self._b[lvl], self.locs[lvl], out=self._b[lvl + 1])
+        self._tail_solve(2, 0)
+        for lvl in range(self.nlaunch - 1, -1, -1):
+            xl, bl = (x, b) if lvl == 0 else (self._x[lvl], self._b[lvl])
+            ops.interp_add(self._x[lvl + 1], "." + self.locs[lvl], out=xl)
+            self._cycle(lvl, xl, bl)
+
+    def solve(self, b, x, tol=1e-10, maxcycles=60, start=2):
+        """`EnsembleGMG.solve`: A_b x_b = b_b for every member, in place in x [B, *shape] (contiguous, as b)."""
+        assert tuple(x.shape) == tuple(b.shape) == (self.nbatch,) + self.shapes[0], (x.shape, b.shape)
+        assert x.is_contiguous() and b.is_contiguous() and x.dtype == b.dtype == self.dtype and start in (0, 1, 2)
+        out = self._out.get(maxcycles)
+        if out is None:
+            out = self._out[maxcycles] = (
+                torch.zeros((self.nbatch, maxcycles + 2), dtype=torch.float64, device=self.device),
+                torch.zeros((self.nbatch, 2), dtype=torch.int32, device=self.device))
+        history, outcome = out
+        self._active.fill_(1)
+        if start == 0:
+            x.zero_()  # (what a member keeps that stops before its first cycle)
+            bsq = self._partials  # (the first sweep starts from zero: its partial sums are those of b^2)
+        else:
+            if start == 2:
+                self._nested(b, x)
+            # (b^2 by a sweep from zero into scratch: three words per cell, once per solve)
+            bsq = self._partials0
+            ops.stencil_var_smooth_batch(self.level(0), None, b, 1.0, self._s[0][0], partials=bsq)
+        for k in range(maxcycles + 1):
+            def decide():
+                ops.stencil_cycle_decide_batch(self._partials, self.cells, k, maxcycles, tol, history, outcome, self._active,
+                                               self._nactive, partials0=bsq if k == 0 else None)
+                self._nactive_host.copy_(self._nactive, non_blocking=True)
+                self._decided.record()
+                return k == maxcycles  # (every member stops there at the latest: nothing of this cycle is left to run)
+
+            self._cycle(0, x, b, zero=start == 0 and k == 0, decide=decide)
+            self._decided.synchronize()  # (ONE int per cycle; the rest of the cycle is in flight meanwhile)
+            if int(self._nactive_host[0]) == 0:
+                break
+        # ONE read-back of history and outcome per solve of the whole ensemble
+        self.history, self.outcome = history.cpu().numpy(), outcome.cpu().numpy()
+        return x
+
+    def newton_step(self, u, rhs, tol=1e-10, maxcycles=60, start=2):
+        raise ValueError("EnsembleLaunchGMG: newton_step is not served (solve M d = f with `solve`, then update)")
 
 
 def stencil_coefficients(items, shape, period=None, dtype=None, device=None):

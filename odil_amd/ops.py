@@ -321,6 +321,74 @@ def stencil_dense_batch(coeffs, shape, out=None):
     return out
 
 
+def stencil_var_smooth_batch_parts(shape):
+    """Partial sums per member that `stencil_var_smooth_batch` writes for members of `shape` (0: malformed shape)."""
+    return int(_lib.load().odil_stencil_var_smooth_batch_parts(i64(shape), c_int(len(shape))))
+
+
+def _active_ptr(active, nb):
+    if active is not None:
+        assert active.dtype == torch.int32 and tuple(active.shape) == (nb,) and active.is_contiguous()
+    return ptr(active)
+
+
+def stencil_var_smooth_batch(coeffs, x, b, omega, out, mode=0, active=None, partials=None):
+    """`stencil_var_smooth` (mode 0; x = None: from the zero vector) or `stencil_var_residual` (mode 1) for every member of
+    an ensemble in ONE launch (include/odil_hip.h: odil_stencil_var_smooth_batch).  coeffs: [B, >= (2 d + 1) cells] as in
+    `stencil_var_coarsen_batch`; x, b, out: [B, *shape] with contiguous members (any leading stride), out is not x.
+    active: None or int32 [B], members with a zero are skipped whole.  partials (mode 0): None or float64 [B, P], P =
+    `stencil_var_smooth_batch_parts(shape)`: per workgroup the sum of (A x - b)^2 of the sweep's input."""
+    nb, shape = b.shape[0], tuple(int(n) for n in b.shape[1:])
+    ndim, cells = len(shape), math.prod(shape)
+    assert tuple(out.shape) == tuple(b.shape) and out.dtype == b.dtype == coeffs.dtype and coeffs.shape[0] == nb
+    assert x is None or (tuple(x.shape) == tuple(b.shape) and x.dtype == b.dtype)
+    if partials is not None:
+        assert partials.dtype == torch.float64 and partials.is_contiguous()
+        assert tuple(partials.shape) == (nb, stencil_var_smooth_batch_parts(shape)), tuple(partials.shape)
+    cp, cs = _packed_members(coeffs, (2 * ndim + 1) * cells)
+    call("stencil_var_smooth_batch", b.dtype, cp, cs, None if x is None else _base_ptr(x),
+         c_int64(0 if x is None else _member_stride(x, cells)), _base_ptr(b), c_int64(_member_stride(b, cells)), _base_ptr(out),
+         c_int64(_member_stride(out, cells)), i64(shape), c_int(ndim), c_int(nb), float(omega), c_int(mode),
+         _active_ptr(active, nb), ptr(partials), stream_ptr())
+    return out
+
+
+def stencil_var_residual_restrict_batch(coeffs, x, b, scale, out, active=None):
+    """out = scale * (sum over the 2^d children of b - A x) for every member in ONE launch (odil_stencil_var_residual_
+    restrict_batch): every axis merged, even extents, no norm.  Arrays as in `stencil_var_smooth_batch`; out: [B, *shape / 2]."""
+    nb, shape = x.shape[0], tuple(int(n) for n in x.shape[1:])
+    ndim, cells = len(shape), math.prod(shape)
+    assert tuple(out.shape) == (nb,) + tuple(n // 2 for n in shape) and tuple(b.shape) == tuple(x.shape)
+    assert out.dtype == b.dtype == x.dtype == coeffs.dtype and coeffs.shape[0] == nb
+    cp, cs = _packed_members(coeffs, (2 * ndim + 1) * cells)
+    call("stencil_var_residual_restrict_batch", x.dtype, cp, cs, _base_ptr(x), c_int64(_member_stride(x, cells)), _base_ptr(b),
+         c_int64(_member_stride(b, cells)), _base_ptr(out), c_int64(_member_stride(out, cells // 2**ndim)), i64(shape),
+         c_int(ndim), c_int(nb), float(scale), _active_ptr(active, nb), stream_ptr())
+    return out
+
+
+def stencil_cycle_decide_batch(partials, cells, k, maxcycles, tol, history, outcome, active, nactive, partials0=None):
+    """The decision of every active member before cycle k (odil_stencil_cycle_decide_batch): history[b, 1 + k] from the
+    member's partial sums [B, P] (history[b, 0] from partials0 when given), the stop rules of `stencil_solve_batch`,
+    outcome [B, 2] and active [B] (int32) updated for the members that stop, the members still active counted into nactive
+    (int32, one element).  Everything stays on the device."""
+    nb = partials.shape[0]
+    assert partials.dtype == torch.float64 and partials.dim() == 2 and partials.is_contiguous()
+    assert partials0 is None or (partials0.dtype == torch.float64 and partials0.shape == partials.shape
+                                 and partials0.is_contiguous())
+    assert history.dtype == torch.float64 and history.shape[0] == nb and history.is_contiguous()
+    assert outcome.dtype == torch.int32 and tuple(outcome.shape) == (nb, 2) and outcome.is_contiguous()
+    assert nactive.dtype == torch.int32 and nactive.numel() == 1
+    lib = _lib.load()
+    status = lib.odil_stencil_cycle_decide_batch(
+        ptr(partials), c_int64(partials.shape[1]), ptr(partials0), c_int64(partials.shape[1]), c_int(partials.shape[1]),
+        c_int(nb), c_int64(int(cells)), c_int(k), c_int(maxcycles), c_double(float(tol)), ptr(history),
+        c_int64(history.shape[1]), ptr(outcome), _active_ptr(active, nb), ptr(nactive), stream_ptr())
+    if status != 0:
+        raise _lib.OdilHipError("odil_stencil_cycle_decide_batch: {}".format(lib.odil_last_error().decode()))
+    return nactive
+
+
 def stencil_vcycle_tail(coeffs, shapes, halve, xin, b, xout, work, inv, wpre, wpost, fmg=False):
     """The coarse tail of a multigrid cycle in one launch (include/odil_hip.h: odil_stencil_vcycle_tail).  coeffs: one
     flat tensor holding the coefficient arrays of every tail level; shapes: their extents, finest first; halve: per
@@ -405,7 +473,9 @@ def stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpo
     istride = 0 if inv.dim() == 2 else _member_stride(inv, ninv * ninv)
     wstride = _member_stride(work, need)
     assert work.shape[0] == nbatch and work.is_contiguous() and coeffs.dtype == work.dtype == inv.dtype
-    assert coeffs.is_contiguous() and inv.is_contiguous() and tuple(inv.shape[-2:]) == (ninv, ninv)
+    # (coeffs [B, ncoeff] may be columns of a wider buffer -- the tail of a hierarchy whose finer levels run as launches)
+    assert (coeffs.is_contiguous() if cstride == 0 else coeffs.dim() == 2) and inv.is_contiguous()
+    assert tuple(inv.shape[-2:]) == (ninv, ninv)
     assert (coeffs.numel() >= ncoeff if cstride == 0 else coeffs.shape[0] == nbatch) and (istride == 0 or inv.shape[0] == nbatch)
     head = (_base_ptr(coeffs), c_int64(cstride), shapes64, maskp, c_int(nlev), c_int(ndim), c_int(nbatch))
     mid = (ptr(work), c_int64(wstride), c_int64(work.numel()), _base_ptr(inv), c_int64(istride), c_int(ninv), wap,
