@@ -10,10 +10,16 @@ is printed from device events around it.  The time per step is printed beside th
 for one workgroup (256^2, 64^3, 128^3): the levels above 32768 cells as launches that cover all members, the convergence
 decision on the device (`gmg.EnsembleLaunchGMG`); `--form auto` takes it only where `--form workgroup` refuses.
 
+`--optimizer adam` runs the same sweep with Adam (`odil.util.optimize_ensemble(form="auto")`, its route for traced stencil
+operators: every launch of an epoch covers all members; `--multigrid 1` for a multigrid-decomposed unknown) and prints the
+time per epoch of all members beside that of the same members as single `optimize_grad` runs one after the other, the two
+alternating `--repeat` times, with the host time `stencil_bind.EpochBatch` spends per epoch.
+
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --kind smooth --epochs 2
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --beta 1 --epochs 4
     python examples/diffusion/ensemble.py --members 256 --ndim 2 --N 64 --linearize members --single 0
     python examples/diffusion/ensemble.py --members 16 --ndim 2 --N 256 --form launches --linsolver multigrid
+    python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --optimizer adam --multigrid 1 --epochs 200
 """
 
 import argparse
@@ -53,6 +59,7 @@ def parse_args(argv=None):
                      help="Linearise all members in one generated launch, or member by member")
     own.add_argument("--form", type=str, default="workgroup", choices=("workgroup", "launches", "auto"),
                      help="One workgroup per member, batched launches for members beyond one workgroup, or whichever serves")
+    own.add_argument("--repeat", type=int, default=3, help="--optimizer adam: timed repetitions of the ensemble and the single runs")
     mine, rest = own.parse_known_args(argv)
     args = diffusion.parse_args(["--ndim", "2", "--N", "16", "--epochs", "2"] + rest)
     for key, value in vars(mine).items():
@@ -92,6 +99,68 @@ def synchronize():
         torch.cuda.synchronize()
 
 
+def main_adam(args, callback):
+    """The sweep with Adam: all members per launch against the same members one after the other."""
+    nsteps = max(args.epochs - args.epoch_start, 1)
+    problems, states = make_members(args)
+    guess = [[a.clone() for a in problem.domain.arrays_from_state(state)] for problem, state in zip(problems, states)]
+
+    def restart():
+        for problem, state, arrays in zip(problems, states, guess):
+            problem.domain.arrays_to_state([a.clone() for a in arrays], state)
+        synchronize()
+
+    def timed(run):
+        restart()
+        start = time.perf_counter()
+        run()
+        synchronize()
+        return 1e3 * (time.perf_counter() - start) / nsteps
+
+    def together():
+        return odil.util.optimize_ensemble(args, problems, states, form="auto")
+
+    def alone():
+        for problem, state in zip(problems, states):
+            odil.util.optimize_grad(args, "adam", problem, state)
+
+    # the warm-up: every operator traced, every kernel of both routes loaded, the report of the sweep
+    arrays, optinfo = odil.util.optimize_ensemble(args, problems, states, callback, form="auto")
+    printlog("\nroute '{}', form '{}'".format(optinfo.route, optinfo.form))
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        printlog("member {:3d}: loss {:.6e}, error u:{:.5g}".format(
+            b, float(optinfo.losses[b, -1]) if nsteps and optinfo.losses.numel() else float("nan"),
+            diffusion.error_rms(problem.domain, problem.extra, state, "u")))
+    batches = getattr(getattr(optinfo, "ensemble", None), "batches", [])
+    times, host = dict(ensemble=[], single=[]), []
+    if args.single:
+        timed(lambda: odil.util.optimize_grad(args, "adam", problems[0], states[0]))
+    for _ in range(max(args.repeat, 1) if args.epochs > args.epoch_start else 0):
+        spent, calls = sum(batch.host_seconds for batch in batches), sum(batch.launches for batch in batches)
+        times["ensemble"].append(timed(together))
+        calls = sum(batch.launches for batch in batches) - calls
+        host.append((1e6 * (sum(batch.host_seconds for batch in batches) - spent) / max(calls, 1), calls))
+        if args.single:
+            times["single"].append(timed(alone))
+    span = lambda values: "{:.3f} - {:.3f}".format(min(values), max(values))
+    lines = []
+    if times["ensemble"]:
+        lines.append("ensemble of {} members: {} ms per Adam epoch of all members ({} repetitions)".format(
+            args.members, span(times["ensemble"]), len(times["ensemble"])))
+        if batches:
+            # (epochs replayed as a graph make no call: the launches were captured once)
+            lines.append("host time in EpochBatch: {} us per call, {} calls in {} epochs (the argument blocks uploaded {} "
+                         "times in all)".format(span([us for us, _ in host]), host[-1][1], nsteps,
+                                                sum(batch.uploads for batch in batches)))
+    if times["single"]:
+        lines.append("single runs: {} ms per Adam epoch of all members, {:.1f} x the ensemble (best of each)".format(
+            span(times["single"]), min(times["single"]) / min(times["ensemble"])))
+    for line in lines:
+        printlog(line)
+        if not args.echo:
+            print(line)
+
+
 def main():
     args = parse_args()
     odil.setup_outdir(args)
@@ -104,6 +173,8 @@ def main():
 
     every = args.report_every or args.epochs
     callback.next_active = lambda epoch: (epoch // every + 1) * every
+    if args.optimizer in ("adam", "adamn"):
+        return main_adam(args, callback)
     problems, states = make_members(args)
     guess = [problem.domain.arrays_from_state(state)[0].clone() for problem, state in zip(problems, states)]
 

@@ -351,6 +351,18 @@ int odil_adam_step_pieces_f64(double* x, double* m, double* v, const double* g, 
 int odil_adam_step_pieces_f32(float* x, float* m, float* v, const float* g, int64_t npieces, int64_t stride,
                               int64_t offset, int64_t count, float alpha, float one_minus_b1, float one_minus_b2,
                               float eps, const float* alpha_dev, void* stream);
+/* The same update on the `nbatch` (1 ... 65535) members of [nbatch, n] arrays, member b at b * stride of each array (the
+ * strides, in elements, are at least n: members may be padded): the level-0 update of an ensemble of traced operators,
+ * whose gradient a generated gather forms.  Member b reads its step size from the DEVICE array alpha_dev[b *
+ * alpha_stride] (alpha_stride 0: one step size for all members) and computes the bits odil_adam_step computes on its
+ * own arrays. */
+int odil_adam_step_batch_f64(double* x, double* m, double* v, const double* g, int nbatch, int64_t n, int64_t x_stride,
+                             int64_t m_stride, int64_t v_stride, int64_t g_stride, double one_minus_b1,
+                             double one_minus_b2, double eps, const double* alpha_dev, int64_t alpha_stride,
+                             void* stream);
+int odil_adam_step_batch_f32(float* x, float* m, float* v, const float* g, int nbatch, int64_t n, int64_t x_stride,
+                             int64_t m_stride, int64_t v_stride, int64_t g_stride, float one_minus_b1,
+                             float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride, void* stream);
 /* Planes of ghost-extended arrays <-> contiguous message buffers of the slab exchanges (odil_amd/slab.py,
  * slab_traced.py; no reference counterpart).  `descs`: DEVICE array of ndesc (<= 65535) records
  * of five int64 {base, outer, ostride, inner, boff}: plane k of the message is `outer` runs of `inner` contiguous

@@ -158,6 +158,69 @@ static int adam_pieces(T* x, T* m, T* v, const T* g, int64_t npieces, int64_t st
   return check_launch("k_adam_pieces");
 }
 
+// Adam on the B members of [B, n] arrays, member b at b * stride of each array (members may be padded): the level-0
+// update of an ensemble whose gradient is formed by a launch that does not apply it.  blockIdx.y counts the members;
+// the arithmetic is adam_update of common.h with member b's step size alpha_dev[b * alpha_stride].
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_adam_batch(T* __restrict__ x, T* __restrict__ m, T* __restrict__ v,
+                                                      const T* __restrict__ g, int64_t n, int64_t xs, int64_t ms,
+                                                      int64_t vs, int64_t gs, AdamArgs<T> ad, int vec_ok) {
+  constexpr int V = Vec16<T>::N;
+  typedef typename Vec16<T>::type VT;
+  const int64_t b = blockIdx.y;
+  T* xb = x + b * xs;
+  T* mb = m + b * ms;
+  T* vb = v + b * vs;
+  const T* gb = g + b * gs;
+  const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock;
+  int64_t done = 0;
+  if (vec_ok) {
+    const int64_t nv = n / V;
+    for (int64_t i = tid; i < nv; i += nthreads) {
+      VT xv = reinterpret_cast<VT*>(xb)[i], mv = reinterpret_cast<VT*>(mb)[i], vv = reinterpret_cast<VT*>(vb)[i];
+      const VT gv = reinterpret_cast<const VT*>(gb)[i];
+      T* xp = reinterpret_cast<T*>(&xv);
+      T* mp = reinterpret_cast<T*>(&mv);
+      T* vp = reinterpret_cast<T*>(&vv);
+      const T* gp = reinterpret_cast<const T*>(&gv);
+#pragma unroll
+      for (int k = 0; k < V; ++k) adam_update<T>(xp[k], mp[k], vp[k], gp[k], ad, b);
+      reinterpret_cast<VT*>(xb)[i] = xv;
+      reinterpret_cast<VT*>(mb)[i] = mv;
+      reinterpret_cast<VT*>(vb)[i] = vv;
+    }
+    done = nv * V;
+  }
+  for (int64_t i = done + tid; i < n; i += nthreads) adam_update<T>(xb[i], mb[i], vb[i], gb[i], ad, b);
+}
+
+template <typename T>
+static int adam_step_batch(T* x, T* m, T* v, const T* g, int nbatch, int64_t n, int64_t xs, int64_t ms, int64_t vs,
+                           int64_t gs, T omb1, T omb2, T eps, const T* alpha_dev, int64_t alpha_stride, void* stream) {
+  if (!x || !m || !v || !g || !alpha_dev || n < 0 || alpha_stride < 0) {
+    set_error("adam_step_batch: null pointer, n < 0 or a negative step-size stride");
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("adam_step_batch: %d members (1 ... 65535)", nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch > 1 && (xs < n || ms < n || vs < n || gs < n)) {
+    set_error("adam_step_batch: a member stride is below the %lld elements of a member", (long long)n);
+    return ODIL_E_INVAL;
+  }
+  if (n == 0) return 0;
+  constexpr int V = Vec16<T>::N;
+  const int vec_ok = aligned16(x) && aligned16(m) && aligned16(v) && aligned16(g) &&
+                     (nbatch == 1 || (xs % V == 0 && ms % V == 0 && vs % V == 0 && gs % V == 0));
+  AdamArgs<T> ad{nullptr, nullptr, nullptr, T(0), omb1, omb2, eps, alpha_dev, alpha_stride, 0};
+  const dim3 grid(grid_flat(n, kBlock * V), (unsigned)nbatch);
+  hipLaunchKernelGGL(k_adam_batch<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, x, m, v, g, n, xs, ms, vs, gs, ad,
+                     vec_ok);
+  return check_launch("k_adam_batch");
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_axpy(T* __restrict__ y, const T* __restrict__ x, int64_t n, T a) {
   const int64_t nthreads = (int64_t)gridDim.x * kBlock;
@@ -534,6 +597,19 @@ int odil_adam_step_pieces_f32(float* x, float* m, float* v, const float* g, int6
                               float eps, const float* alpha_dev, void* stream) {
   return adam_pieces<float>(x, m, v, g, npieces, stride, offset, count, alpha, one_minus_b1, one_minus_b2, eps, alpha_dev,
                             stream);
+}
+int odil_adam_step_batch_f64(double* x, double* m, double* v, const double* g, int nbatch, int64_t n, int64_t x_stride,
+                             int64_t m_stride, int64_t v_stride, int64_t g_stride, double one_minus_b1,
+                             double one_minus_b2, double eps, const double* alpha_dev, int64_t alpha_stride,
+                             void* stream) {
+  return adam_step_batch<double>(x, m, v, g, nbatch, n, x_stride, m_stride, v_stride, g_stride, one_minus_b1,
+                                 one_minus_b2, eps, alpha_dev, alpha_stride, stream);
+}
+int odil_adam_step_batch_f32(float* x, float* m, float* v, const float* g, int nbatch, int64_t n, int64_t x_stride,
+                             int64_t m_stride, int64_t v_stride, int64_t g_stride, float one_minus_b1,
+                             float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride, void* stream) {
+  return adam_step_batch<float>(x, m, v, g, nbatch, n, x_stride, m_stride, v_stride, g_stride, one_minus_b1,
+                                one_minus_b2, eps, alpha_dev, alpha_stride, stream);
 }
 int odil_narrow_scale(const double* x, float* y, int64_t n, double a, const double* msq, void* stream) {
   if (!x || !y || n < 0) {

@@ -2,7 +2,8 @@
 reference runs a sweep as B processes and has no counterpart; `util` re-exports both names next to `optimize_grad` /
 `optimize_newton`, whose single runs every member reproduces.  Written once for both drivers: `_check_members`; for both
 Newton routes: `_newton_loop`.  `linearize_ensemble` (`EnsembleLinearizer`) is the linearisation of the Newton driver's
-stencil route, all members in one generated launch.  `printlog` and `_pinfo` are `util`'s (one log sink).
+stencil route, all members in one generated launch; the Adam driver's route for members that are not all the Poisson
+stencil is `fused.TracedLaunchEnsemble`.  `printlog` and `_pinfo` are `util`'s (one log sink).
 """
 
 import argparse
@@ -85,8 +86,23 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     fused.launches_refusal: 1-D / 2-D, at least two levels that halve; fused.volumes_refusal: 3-D, at least two levels
     that halve, a finest extent of at least 4); anything else raises ValueError naming the first
     offending member -- structure (shapes, size) is checked for all members before any operator is probed.
-    Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors."""
-    from . import fused
+
+    When not every member is that Poisson operator and form is 'launches', 'volumes' or 'auto' (with operators traced,
+    `runtime.enable_trace`, and members on a device), ALL members run as the traced stencil operators they are
+    (optinfo.route == "traced", fused.TracedLaunchEnsemble): every epoch is the launches of a single traced run -- the
+    synthesis, the generated forward kernels and gathers (`stencil_bind.EpochBatch`: one launch per group of members whose
+    operators generate the same source), the transposed prolongations with the updates of the coarser levels, and
+    `ops.adam_step_batch` for level 0 -- each covering all members.  'auto' then picks by dimension ('volumes' for 3-D).
+    Such members have ONE cell-centred unknown, a plain `Field` (one level: no transfers, exempt from the two-level rule
+    of the forms) or a `MultigridField` with all factors 1, on a 1-D to 3-D grid, with level shapes that
+    `fused.traced_refusal` admits; operators whose kernels have no batched form (networks or `Array` parameters, outputs
+    in parameter space, marching kernels) raise ValueError naming the member.  The callback's pinfo carries the member's own
+    names, terms and norms.  Epochs are replayed as a graph only when no member has host scalars (functions of
+    `problem.tracers`), which travel in the argument blocks and are uploaded again when they change.  With
+    form='workgroup', or without tracing, a member that is not the Poisson operator stays refused.
+    Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route:
+    "poisson" or "traced"; optinfo.form: the form that ran."""
+    from . import fused, runtime
 
     optname = getattr(args, "optimizer", "adam")
     if optname not in ("adam", "adamn"):
@@ -95,9 +111,14 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
         raise ValueError("optimize_ensemble: {} step sizes for {} members".format(len(lrs), len(problems)))
     fused.ensemble_form(form, [(2,)], torch.float64)  # (any other value of `form` raises here)
     predicates = dict(workgroup=fused.small_refusal, launches=fused.launches_refusal, volumes=fused.volumes_refusal)
+    # members that are not all the Poisson stencil run as traced operators (fused.TracedLaunchEnsemble) where the caller
+    # asked for batched launches and operators are traced at all; which route runs is known once the operators are probed
+    # (the generated kernels need a device: members on CPU tensors keep the refusals of the Poisson forms, as before)
+    requested, traceable = form, form != "workgroup" and runtime.enable_trace and torch.cuda.is_available()
+    late = dict(poisson=None, traced=None)  # per route the first (member, reason) it refuses while the other admits
 
     def describe(b, problem, state, refuse):
-        nonlocal form
+        nonlocal form, traceable
         domain = problem.domain
         arrays = domain.arrays_from_state(state)
         shapes = [tuple(int(n) for n in a.shape) for a in arrays]
@@ -105,24 +126,42 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
             refuse(b, "the unknown is not a cell-centred field of the domain")
         if b == 0:
             form = fused.ensemble_form(form, shapes, arrays[0].dtype)
-        reason = predicates[form](shapes, arrays[0].dtype)
-        if reason is not None:
-            refuse(b, reason)
+            traceable = traceable and arrays[0].is_cuda
+        reasons = dict(poisson=predicates[form](shapes, arrays[0].dtype), traced=None)
+        if traceable:
+            reasons["traced"] = _traced_member(domain, state, shapes, arrays[0].dtype, _traced_form(requested, shapes))
+        if reasons["poisson"] is not None and (not traceable or reasons["traced"] is not None):
+            refuse(b, reasons["poisson"])
+        for route, reason in reasons.items():
+            if reason is not None and late[route] is None:
+                late[route] = (b, reason)
         return dict(shapes=shapes, dtype=arrays[0].dtype, device=arrays[0].device,
                     spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
 
-    _, refuse = _check_members("optimize_ensemble", problems, states, describe)
+    kind, refuse = _check_members("optimize_ensemble", problems, states, describe)
     evaluators = []
     for b, (problem, state) in enumerate(zip(problems, states)):
         problem.recognise(state)
         if getattr(problem, "_fused", None) is None:
-            refuse(b, "the operator is not the recognised Poisson stencil")
+            if traceable:
+                break
+            refuse(b, "the operator is not the recognised Poisson stencil ({})".format(
+                "operators are not traced: ODIL_TRACE=0" if not runtime.enable_trace else
+                "form='launches', 'volumes' or 'auto' run other stencil operators as traced kernels" if requested == "workgroup"
+                else "the traced kernels of other stencil operators need members on a device"))
         evaluators.append(problem._fused)
-    kind = dict(workgroup=fused.PoissonEnsemble, launches=fused.PoissonLaunchEnsemble, volumes=fused.PoissonVolumeEnsemble)[form]
-    reason = kind.refusal(evaluators)
-    if reason is not None:
-        refuse(*reason)
-    ensemble = kind(evaluators)
+    route = "poisson" if len(evaluators) == len(problems) else "traced"
+    if late[route] is not None:
+        refuse(*late[route])
+    if route == "poisson":
+        kind = dict(workgroup=fused.PoissonEnsemble, launches=fused.PoissonLaunchEnsemble, volumes=fused.PoissonVolumeEnsemble)[form]
+        reason = kind.refusal(evaluators)
+        if reason is not None:
+            refuse(*reason)
+        ensemble = kind(evaluators)
+    else:  # (ALL members, the Poisson ones as the traced operators they are)
+        form = _traced_form(requested, kind["shapes"])
+        ensemble = _held_traced_ensemble(problems, states, kind, form)
     for b, (problem, state) in enumerate(zip(problems, states)):
         levels = ensemble.levels(ensemble.x, b)
         for dst, src in zip(levels, problem.domain.arrays_from_state(state)):
@@ -136,6 +175,12 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     util.printlog("Running {} optimizer on an ensemble of {} members".format(opt.displayname, len(problems)))
 
     def callback_wrap(epoch, losses, norms):
+        if route == "traced":  # (the member's own names, terms and norms, as its `optimize_grad` run reports them)
+            outs = [out.clone() for out in ensemble.outs]
+            for b, state in enumerate(states):
+                loss, terms, member_norms = ensemble.report(b, outs)
+                callback(b, state, epoch, util._pinfo(loss, terms, ensemble.names[b], member_norms))
+            return
         for b, state in enumerate(states):
             callback(b, state, epoch, util._pinfo(losses[b], [losses[b]], ensemble.names[b], [norms[b]]))
 
@@ -143,8 +188,57 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
         callback_wrap.next_active = getattr(callback, "next_active", None)
         for b, (problem, state) in enumerate(zip(problems, states)):  # (the report of the start, as optimize_grad makes it)
             callback(b, state, args.epoch_start, _evaluate(problem, state))
-    return opt.run_ensemble(ensemble, epochs=args.epochs - args.epoch_start, callback=callback_wrap if callback else None,
-                            lr=args.lr, lrs=lrs, epoch_start=args.epoch_start, **kwargs)
+    arrays, optinfo = opt.run_ensemble(ensemble, epochs=args.epochs - args.epoch_start,
+                                       callback=callback_wrap if callback else None, lr=args.lr, lrs=lrs,
+                                       epoch_start=args.epoch_start, **kwargs)
+    optinfo.route, optinfo.form = route, form
+    return arrays, optinfo
+
+
+def _held_traced_ensemble(problems, states, kind, form):
+    """The `fused.TracedLaunchEnsemble` of these (checked) members: the one kept on problems[0] when it was made for the
+    same problem objects, kind and form and its traced operators still match the states (a sweep run again pays no second
+    tracing of B operators), else a new one."""
+    from . import fused
+
+    held = getattr(problems[0], "_traced_ensemble", None)
+    if not (held is not None and held[0] == (kind, form) and len(held[1]) == len(problems)
+            and all(p is q for p, q in zip(held[1], problems))
+            and all(t.matches(state) for t, state in zip(held[2].traced, states))):
+        held = problems[0]._traced_ensemble = ((kind, form), list(problems), fused.TracedLaunchEnsemble(problems, states, form))
+    return held[2]
+
+
+def _traced_form(requested, shapes):
+    """The form the traced route of `optimize_ensemble` runs members of these level shapes in: what the caller asked for,
+    'auto' by dimension."""
+    if requested == "auto":
+        return "volumes" if len(shapes[0]) == 3 else "launches"
+    return requested
+
+
+def _traced_member(domain, state, shapes, dtype, form):
+    """Why a member is not run by `fused.TracedLaunchEnsemble` in `form`, or None -- structure only: one cell-centred
+    unknown, a plain `Field` or a `MultigridField` with all factors 1 that coarsens every axis, level shapes that
+    `fused.traced_refusal` admits."""
+    from . import fused
+    from .core import MultigridField
+
+    (field,) = state.fields.values()
+    if isinstance(field, MultigridField):
+        factors = field.factors or domain.mg_factors or [1] * len(field.terms)
+        if any(float(f) != 1.0 for f in factors):
+            return "multigrid factors {} (the batched transfers run factors 1)".format([float(f) for f in factors])
+        axes = field.axes or domain.mg_axes
+        if axes is not None and not all(axes):
+            return "multigrid axes {} (the batched transfers coarsen every axis)".format(list(axes))
+        if len(shapes) < 2:  # (only a plain Field is the one-level case)
+            return fused._too_few_levels(shapes)
+    elif type(field) is not Field:
+        return "the unknown is a {} (a cell-centred Field or MultigridField is needed)".format(type(field).__name__)
+    if field.loc != "c" * domain.ndim:
+        return "the unknown is not a cell-centred field of the domain"
+    return fused.traced_refusal(shapes, dtype, form)
 
 
 def optimize_newton_ensemble(args, problems, states, callback=None, linearize="batched", time_linearize=False,

@@ -264,12 +264,15 @@ class PoissonEnsemble(_Members):
 
 
 class BatchedLaunches(_Members):
-    """What the ensembles that run as batched launches share (PoissonLaunchEnsemble, PoissonVolumeEnsemble): level-major
-    [B, *shape] storage, the refusal of members that differ, and epochs one at a time -- the interface
-    `AdamNativeOptimizer.run_ensemble` drives."""
+    """What the ensembles that run as batched launches share (PoissonLaunchEnsemble, PoissonVolumeEnsemble,
+    TracedLaunchEnsemble): level-major [B, *shape] storage and epochs one at a time -- the interface
+    `AdamNativeOptimizer.run_ensemble` drives; for the Poisson forms also the refusal of members that differ, their
+    residuals and right-hand sides."""
+
+    graphable = True  # epochs may be replayed as a captured graph (no launch argument changes between epochs)
 
     def __init__(self, evaluators, pad, levels_refusal):
-        """What both forms hold: x, m, v, g (one [B, *shape] tensor per level), fu, rhs, loss and norm.
+        """What both Poisson forms hold: x, m, v, g (one [B, *shape] tensor per level), fu, rhs, loss and norm.
         levels_refusal(shapes, nbatch, dtype): the library's answer why a transfer level of the batch would not run the
         kernel that level of a single member runs, or None -- asked before the first launch."""
         reason = self.refusal(evaluators)
@@ -279,14 +282,22 @@ class BatchedLaunches(_Members):
         reason = levels_refusal(ev.shapes, len(evaluators), ev.dtype)
         if reason is not None:
             raise ValueError("ensemble of {} members: {}".format(len(evaluators), reason))
-        self.shapes, self.sizes, self.h2, self.dtype, self.device = ev.shapes, ev.sizes, ev.h2, ev.dtype, ev.device
-        self.cshape, self.ndim, self.loc, self.scale = ev.cshape, ev.ndim, "." + ev.loc, float(ev.scale)
-        self.nbatch, self.nlvl, self.total, self.cells = len(evaluators), ev.nlvl, sum(ev.sizes), ev.sizes[0]
-        self.names = [e.names for e in evaluators]
-        level = lambda wide0=0: [self.members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
-        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
+        self.h2, self.scale = ev.h2, float(ev.scale)
+        self._allocate(ev.shapes, ev.dtype, ev.device, [e.names for e in evaluators], pad)
         self.fu, self.rhs = self.members(self.cshape, pad), self.members(self.cshape, pad)
         self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
+
+    def _allocate(self, shapes, dtype, device, names, pad=0):
+        """The level-major state of len(names) members of these level shapes (all axes cell-centred): x, m, v, g, loss and
+        norm.  pad: extra elements between the members of m[0] and v[0]."""
+        self.shapes, self.dtype, self.device = [tuple(s) for s in shapes], dtype, device
+        self.sizes = [math.prod(s) for s in self.shapes]
+        self.cshape, self.ndim = self.shapes[0], len(self.shapes[0])
+        self.loc = "." + "c" * self.ndim
+        self.nbatch, self.nlvl, self.total, self.cells = len(names), len(self.shapes), sum(self.sizes), self.sizes[0]
+        self.names = names
+        level = lambda wide0=0: [self.members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
+        self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
         self.loss, self.norm = (torch.zeros(self.nbatch, dtype=self.dtype, device=self.device) for _ in range(2))
 
     def members(self, shape, wide=0):
@@ -368,6 +379,104 @@ class PoissonVolumeEnsemble(BatchedLaunches):
         ops.poisson_adjoint_adam_volumes(self.fu, self.h2, self.scale, self.g[0], self.x[0], self.m[0], self.v[0], alphas,
                                          omb1, omb2, eps)
         ops.mg_synth_adj_adam_volumes(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+
+
+class TracedLaunchEnsemble(BatchedLaunches):
+    """B traced stencil operators of one cell-centred unknown (a `MultigridField` with factors 1, or a plain `Field`: the
+    one-level case) on one grid side by side, as batched launches: an epoch is the launches of a single traced run
+    (`stencil_jit.TracedOperator.eval_loss_grad` + the optimizer's update), each covering all B members --
+      1. `ops.mg_synth` of all levels into u [B, *cshape] (one level: u is x[0]);
+      2. the generated forward kernels of all members (`stencil_bind.EpochBatch`: k_fwd_batch, k_final_batch, k_loss_batch),
+         ONE launch of each per group of members whose operators generated the same source;
+      3. the generated gathers of all members into g[0];
+      4. the transposed prolongations with the updates of the levels >= 1 (`ops.mg_synth_adj_adam_batch` for 1-D / 2-D
+         members, `ops.mg_synth_adj_adam_volumes` for 3-D members);
+      5. `ops.adam_step_batch` for level 0, after the chain has read g[0] (and after the gathers have re-read their
+         sources: for a plain `Field` the source IS x[0]).
+    Member b computes what its single run computes, bit for bit.  out [B, 1 + 2 nout_b] per group holds loss, terms and
+    norms of its members (`report`); `loss` [B] collects column 0."""
+
+    def __init__(self, problems, states, form="launches"):
+        """The members have passed the structural checks of `ensemble.optimize_ensemble` (one unknown, same level shapes,
+        dtype and device; `traced_refusal` admits the shapes).  A member whose operator has no batched kernels raises
+        ValueError naming it."""
+        from . import stencil_jit
+        from .stencil_bind import EpochBatch
+
+        domain = problems[0].domain
+        arrays = domain.arrays_from_state(states[0])
+        shapes = [tuple(int(n) for n in a.shape) for a in arrays]
+        nb = len(problems)
+        reason = traced_refusal(shapes, arrays[0].dtype, form, nb)
+        if reason is not None:
+            raise ValueError("ensemble of {} members: {}".format(nb, reason))
+        self.form = form
+        self.traced = []
+        for b, (problem, state) in enumerate(zip(problems, states)):
+            try:
+                self.traced.append(stencil_jit.TracedOperator(problem, state, batch=True))
+            except stencil_jit.TraceUnsupported as e:
+                raise ValueError("ensemble member {}: its operator has no batched kernels ({})".format(b, e))
+        self._allocate(shapes, arrays[0].dtype, arrays[0].device, [list(t.names) for t in self.traced])
+        self.u = self.members(self.cshape) if self.nlvl > 1 else self.x[0]
+        self.work = ([None] + [self.members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
+        by_lib = dict()
+        for b, traced in enumerate(self.traced):
+            by_lib.setdefault(traced.lib_path, []).append(b)
+        self.groups = list(by_lib.values())
+        (key,) = states[0].fields.keys()
+        self.outs, self.batches = [], []
+        for group in self.groups:
+            out = torch.zeros((len(group), 1 + 2 * self.traced[group[0]].nout), dtype=self.dtype, device=self.device)
+            self.outs.append(out)
+            self.batches.append(EpochBatch([self.traced[b] for b in group], [[self.u[b]] for b in group],
+                                           [{key: self.g[0][b]} for b in group], out))
+        self.where = dict((b, (k, j)) for k, group in enumerate(self.groups) for j, b in enumerate(group))
+        self.index = [torch.tensor(group, device=self.device) for group in self.groups]
+        if len(self.groups) == 1:  # (column 0 of the packed `out` itself: nothing to collect)
+            self.loss = self.outs[0][:, 0]
+        self.graphable = all(batch.graphable for batch in self.batches)
+
+    def report(self, member, outs=None):
+        """(loss, terms, norms) of `member` as the last epoch evaluated them: 0-d views of the packed `out` (outs: of
+        copies of `self.outs` instead, which later epochs do not overwrite)."""
+        k, j = self.where[member]
+        row, nout = (outs or self.outs)[k][j], self.traced[member].nout
+        return row[0], [row[1 + i] for i in range(nout)], [row[1 + nout + i] for i in range(nout)]
+
+    def epoch(self, alphas, omb1, omb2, eps):
+        """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
+        losses the epoch evaluated (before its update) land in self.loss."""
+        if self.nlvl > 1:
+            ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+        for batch in self.batches:
+            batch.launch()
+        if len(self.groups) > 1:
+            for index, out in zip(self.index, self.outs):
+                self.loss.index_copy_(0, index, out[:, 0])
+        if self.nlvl > 1:
+            chain = ops.mg_synth_adj_adam_volumes if self.ndim == 3 else ops.mg_synth_adj_adam_batch
+            chain(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+        ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], alphas, omb1, omb2, eps)
+
+
+def traced_refusal(shapes, dtype, form, nbatch=1):
+    """Why members of these level shapes are not run by `TracedLaunchEnsemble` in `form` ('launches': 1-D / 2-D, 'volumes':
+    3-D), or None: `launches_refusal` / `volumes_refusal`, the one-level case (a plain `Field`: no transfers) exempt from
+    their two-level rule."""
+    ndim = len(shapes[0])
+    if not 1 <= ndim <= 3:
+        return "{}-D grid: the batched launches of traced operators run 1-D to 3-D grids".format(ndim)
+    if dtype not in (torch.float64, torch.float32):
+        return "dtype {}: the kernels run float64 and float32".format(dtype)
+    if (form == "volumes") != (ndim == 3):
+        return "{}-D grid: form '{}' runs {} grids".format(ndim, form, "3-D" if form == "volumes" else "1-D and 2-D")
+    if len(shapes) == 1:
+        return None
+    reason = (volumes_refusal if ndim == 3 else launches_refusal)(shapes, dtype)
+    if reason is None and nbatch > 1:
+        reason = _volume_levels_refusal(shapes, nbatch, dtype) if ndim == 3 else _levels_refusal(shapes, nbatch)
+    return reason
 
 
 def _library_refusal(entry, shapes, *more):

@@ -1086,6 +1086,18 @@ def adam_step(x, m, v, g, alpha, one_minus_b1, one_minus_b2, eps):
     )
 
 
+def adam_step_batch(x, m, v, g, alphas, one_minus_b1, one_minus_b2, eps):
+    """`adam_step` for the B members of [B, *shape] arrays in ONE launch (the members contiguous, possibly padded: the
+    leading strides are the member strides, as `_members` describes them).  alphas: DEVICE step sizes, [B] (one per
+    member) or one element (shared).  Member b gets the bits of `adam_step` on its own arrays."""
+    nb, shape = int(x.shape[0]), tuple(x.shape[1:])
+    assert x.dtype == m.dtype == v.dtype == g.dtype == alphas.dtype
+    assert alphas.is_cuda and alphas.numel() in (1, nb) and alphas.is_contiguous()
+    (xp, xs), (mp, ms), (vp, vs), (gp, gs) = (_members(t, nb, shape) for t in (x, m, v, g))
+    call("adam_step_batch", x.dtype, xp, mp, vp, gp, c_int(nb), c_int64(x[0].numel()), xs, ms, vs, gs, float(one_minus_b1),
+         float(one_minus_b2), float(eps), ptr(alphas), c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
+
+
 def adam_step_pieces(x, m, v, g, npieces, stride, offset, count, alpha, one_minus_b1, one_minus_b2, eps):
     """adam_step on the elements o * stride + offset + j (o < npieces, j < count) of four flat vectors."""
     assert x.numel() == m.numel() == v.numel() == g.numel() and x.is_contiguous()

@@ -323,7 +323,7 @@ class AdamNativeOptimizer(Optimizer):
 
 
     def _run_ensemble_launches(self, ensemble, epochs, callback, table, epoch_start, omb1, omb2, epsilon):
-        """`run_ensemble` for a `fused.PoissonLaunchEnsemble` or a `fused.PoissonVolumeEnsemble`: every epoch is the launches of a single run, each covering
+        """`run_ensemble` for a `fused.BatchedLaunches` (PoissonLaunchEnsemble, PoissonVolumeEnsemble, TracedLaunchEnsemble): every epoch is the launches of a single run, each covering
         all members.  table: [E] step sizes shared by the members, or [B][E].  The epoch's step sizes are selected, and its
         [B] losses and norms filed into column e of the [B, E] tables, by the device index of `_EpochGraph` -- eagerly or,
         under the `_graph_wanted` policy, replayed as one hipGraph (one stream: the launches are a chain); the same body
@@ -350,7 +350,8 @@ class AdamNativeOptimizer(Optimizer):
         while epoch <= last:
             stop = _whole_epochs_stop(callback, epoch, last)
             while epoch <= stop:
-                if not replay and epoch == first + 2 and last - epoch + 1 > 4 and _graph_wanted(
+                # (an ensemble whose launch arguments change between epochs -- host scalars of traced members -- runs eagerly)
+                if not replay and epoch == first + 2 and last - epoch + 1 > 4 and ensemble.graphable and _graph_wanted(
                         nb * ensemble.total, safe, epochs):
                     at = runner.index.clone()
                     replay = runner.capture()

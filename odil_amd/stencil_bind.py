@@ -7,6 +7,7 @@ The argument blocks (`struct Args`, `struct ParArgs`) are described once, by the
 """
 
 import ctypes
+import time
 
 import numpy as np
 import torch
@@ -21,7 +22,7 @@ _ADAM = [_P] * 3 + [ctypes.c_double] * 4 + [_P]  # x, m, v, alpha, 1 - beta_1, 1
 _ARGTYPES = dict(  # (launchers of stencil_codegen._launchers; all end with the stream)
     jit_fwd=[_P, _P], jit_gather=[ctypes.c_int, _P, _P, _P], jit_gather_adam=[ctypes.c_int, _P, _P] + _ADAM + [_P],
     jit_gather_all=[_P] + [_PP] * 4 + _ADAM[3:] + [_P], jit_jac=[_P, _PP, _P], jit_jac_batch=[_P, _P, ctypes.c_int, _P],
-    jit_par=[_P, _P, _P])
+    jit_par=[_P, _P, _P], jit_fwd_batch=[_P, ctypes.c_int, _P], jit_gather_batch=[ctypes.c_int, _P, _P, ctypes.c_int, _P])
 
 
 def field_ranges(domain, state):
@@ -50,18 +51,22 @@ def _hyper(hyper):
 class StencilBinding:
     """The generated kernels of one traced operator: source, library, buffers, argument block, launches."""
 
-    def __init__(self, problem, state, tr, outs, raw, G, slab, jac, device, par_refused):
-        """tr, outs, raw, G: of `stencil_jit.trace_outputs`; slab, jac: of `_Codegen`.  par_refused(e): called when the
-        outputs in parameter space have no elementwise form (param_expr.Unsupported) -- it raises, or returns and leaves
+    def __init__(self, problem, state, tr, outs, raw, G, slab, jac, device, par_refused, batch=False):
+        """tr, outs, raw, G: of `stencil_jit.trace_outputs`; slab, jac, batch: of `_Codegen`.  par_refused(e): called when
+        the outputs in parameter space have no elementwise form (param_expr.Unsupported) -- it raises, or returns and leaves
         them to the caller (`par_outputs` stays None)."""
         from .core import Array, NeuralNet
+        from .stencil_trace import TraceUnsupported
+
+        if batch and tr.offgrid:
+            raise TraceUnsupported("batched forward kernel: outputs in parameter space")
 
         domain = problem.domain
         self.problem, self.domain, self.tr, self.raw, self.G = problem, domain, tr, raw, G
         # outputs in parameter space (param_tape.py): [(position, expression, slice of the tape it needs)]
         self.offgrid = [(k, e, tr.param_tape.slice_for(e.param_ids())) for k, e in tr.offgrid]
         self.param_tape = tr.param_tape
-        cg = self.cg = _Codegen(tr, outs, raw, G, state, slab=slab, jac=jac)
+        cg = self.cg = _Codegen(tr, outs, raw, G, state, slab=slab, jac=jac, batch=batch)
         # ... as ONE generated kernel when the taped operations have an elementwise form (param_expr.py)
         self.par_outputs = None
         if self.offgrid:
@@ -81,12 +86,7 @@ class StencilBinding:
                 getattr(self.lib, name).argtypes = argtypes
         dt = self.dtype = tr.torch_dtype
         self.total, self.nout = cg.total, len(outs)
-        # Every block ends with one block reduction per output and per network / array parameter: operators
-        # that differentiate through parameters (dozens of reductions) want few, long blocks -- heat with two
-        # space dimensions (46 parameters, 67 M points): 6.6 ms / epoch at 65536 blocks, 5.2 at 4096; plain
-        # stencils prefer many (tracer 4-D: 62.0 ms at 65536, 64.5 at 4096).
-        cap = 4096 if len(cg.pg_decl) > 8 else 65536
-        self.nblocks = min((self.total // cg.vw_fwd + 255) // 256, cap)
+        self.nblocks = cg.fwd_blocks
         nout, npg = self.nout, len(cg.pg_decl)
         self.cot = [torch.empty(cg.GL, dtype=dt, device=device) for _ in range(cg.ncot)]
         self.part = torch.empty(max(1, nout * self.nblocks), dtype=dt, device=device)
@@ -182,6 +182,39 @@ class StencilBinding:
         self._launch("jit_par", ctypes.byref(self.args), ctypes.byref(self.par_args))
 
 
+class _StagingRing:
+    """Blocks of host bytes on their way to launches that read them from DEVICE memory: a ring of `depth` slots, each a
+    pinned block, a device block and an event recorded behind the launch that read it.  A slot is refilled only after its
+    event has completed, so neither the pending copy nor a queued launch ever sees a block the host has since rewritten;
+    with all slots in flight the host waits for the oldest."""
+
+    def __init__(self, nbytes, device, depth):
+        self.slots = [dict(host=torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+                           dev=torch.empty(nbytes, dtype=torch.uint8, device=device), done=None) for _ in range(depth)]
+        self.next = 0
+
+    def take(self):
+        """The next slot, free to be rewritten: fill slot["host"], then `upload(slot)`, launch, `release(slot)`."""
+        slot = self.slots[self.next]
+        self.next = (self.next + 1) % len(self.slots)
+        if slot["done"] is not None:
+            slot["done"].synchronize()  # (the launch that read this slot has run: its blocks may be rewritten)
+        return slot
+
+    @staticmethod
+    def upload(slot):
+        """Queues the copy of the slot's host block on the current stream; returns the device address."""
+        slot["dev"].copy_(slot["host"], non_blocking=True)
+        return slot["dev"].data_ptr()
+
+    @staticmethod
+    def release(slot):
+        """Behind the last launch that reads the slot."""
+        if slot["done"] is None:
+            slot["done"] = torch.cuda.Event()
+        slot["done"].record()
+
+
 class JacobianBatch:
     """ONE launch of `k_jac_batch` for members of an ensemble whose operators generated the same source (so
     `jit_cache._compile` handed them the same library): every member keeps its own trace, argument block and host scalars,
@@ -189,10 +222,7 @@ class JacobianBatch:
     call they are gathered from the members' ctypes structs into pinned host memory and copied on the current stream.
 
     Two linearisations may be queued back to back without a synchronise (the hazard `TracedOperator.graph_upload`
-    describes for host scalars): the staging is a ring of `depth` slots, each a pinned block, a device block and an event
-    recorded behind the launch that read it.  A slot is refilled only after its event has completed, so neither the
-    pending copy nor a queued launch ever sees a block the host has since rewritten; with all slots in flight the host
-    waits for the oldest."""
+    describes for host scalars): the staging is a `_StagingRing` of `depth` slots."""
 
     depth = 4
 
@@ -209,10 +239,7 @@ class JacobianBatch:
         nb = len(members)
         self.abytes = nb * self.asize  # (a multiple of 8: the block holds pointers)
         nbytes = self.abytes + nb * self.nitems * ctypes.sizeof(_P)
-        device = first.out.device
-        self.slots = [dict(host=torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
-                           dev=torch.empty(nbytes, dtype=torch.uint8, device=device), done=None) for _ in range(self.depth)]
-        self.next = 0
+        self.ring = _StagingRing(nbytes, first.out.device, self.depth)
 
     def pointer_table(self, outputs):
         """The members' output pointers as the launch wants them ([B, items] addresses), from outputs[b][j], the contiguous
@@ -230,10 +257,7 @@ class JacobianBatch:
     def launch(self, states, table):
         """k_jac_batch for `states` (one per member) into the arrays of `table` (`pointer_table`; the caller keeps them
         alive)."""
-        slot = self.slots[self.next]
-        self.next = (self.next + 1) % self.depth
-        if slot["done"] is not None:
-            slot["done"].synchronize()  # (the launch that read this slot has run: its blocks may be rewritten)
+        slot = self.ring.take()
         base = slot["host"].data_ptr()
         keep = []
         for b, (member, state) in enumerate(zip(self.members, states)):
@@ -241,12 +265,103 @@ class JacobianBatch:
             ctypes.memmove(base + b * self.asize, ctypes.addressof(member.args), self.asize)
         assert table.shape == (len(self.members), self.nitems) and table.dtype == np.uint64 and table.flags.c_contiguous
         ctypes.memmove(base + self.abytes, table.ctypes.data, table.nbytes)
-        slot["dev"].copy_(slot["host"], non_blocking=True)
-        dev = slot["dev"].data_ptr()
+        dev = self.ring.upload(slot)
         rc = self.lib.jit_jac_batch(dev, dev + self.abytes, len(self.members), ops.stream_ptr())
         if rc != 0:
             raise RuntimeError("generated kernel launch failed (jit_jac_batch): hip error {}".format(rc))
-        if slot["done"] is None:
-            slot["done"] = torch.cuda.Event()
-        slot["done"].record()
+        self.ring.release(slot)
         del keep
+
+
+class EpochBatch:
+    """The forward and gather launches of one Adam epoch for members of an ensemble whose operators generated the same
+    source (generated with batch=True: one library): ONE `jit_fwd_batch` (k_fwd, k_final, k_loss of all members) and ONE
+    `jit_gather_batch` per gather (the merged gather where the generator made one).  As in `JacobianBatch` every member
+    keeps its own trace and argument block and the launches read the blocks from DEVICE memory -- but here no pointer
+    changes between epochs: member b's sources are its slices of packed arrays, its gradients go to its slices of the
+    packed level-0 gradients, its `out` is row b of one packed [B, 1 + 2 nout] tensor.  So the blocks are staged ONCE, and
+    again only when a member's bytes change: host scalars (`cg.hs`, functions of `problem.tracers`), which `launch`
+    evaluates for the members that have any and compares with what the device holds.  Members without host scalars cost
+    no host time per epoch, and their launches can be captured into a graph (`graphable`)."""
+
+    depth = 4
+
+    def __init__(self, members, sources, grads, out):
+        """members: the `TracedOperator`s of one group, in the order of the launch.  sources[b]: the contiguous arrays
+        member b reads, in the order of `cg.src_keys`; grads[b]: {field key: the contiguous array its gradient goes to};
+        out: [B, 1 + 2 nout] contiguous, B the number of members here.  The caller keeps all of them alive."""
+        first = members[0]
+        if any(m.lib_path != first.lib_path for m in members):
+            raise ValueError("EpochBatch: members of one launch share one generated library")
+        if not hasattr(first.lib, "jit_fwd_batch"):
+            raise RuntimeError("these kernels were generated without the batched forward and gather kernels (batch=True)")
+        cg, nb = first.cg, len(members)
+        self.members, self.lib, self.nb = list(members), first.lib, nb
+        assert tuple(out.shape) == (nb, 1 + 2 * first.nout) and out.is_contiguous() and out.dtype == first.dtype
+        real = ctypes.c_double if first.dtype == torch.float64 else ctypes.c_float
+        adam = type("AdamP", (ctypes.Structure,), dict(_fields_=[(n, _P) for n in "xmv"] + [
+            (n, real) for n in ("alpha", "omb1", "omb2", "eps")] + [("alpha_dev", _P)]))
+        gat = type("GatB", (ctypes.Structure,), dict(_fields_=[("g", _P * max(1, len(cg.gathers))), ("ad", adam)]))
+        self.asize, self.gsize = ctypes.sizeof(first.args), ctypes.sizeof(gat)
+        self.abytes = nb * self.asize  # (a multiple of 8: the block holds pointers)
+        # which = -1: the merged gather; the fields it does not cover keep launches of their own
+        self.which = ([-1] if cg.merged else []) + [gi for gi, key in enumerate(cg.gathers) if key not in cg.merged]
+        self.ptrs = []
+        for b, member in enumerate(members):
+            if member.nblocks != cg.fwd_blocks or len(sources[b]) != len(cg.src_keys):
+                raise RuntimeError("EpochBatch: member {} does not match the generated launch".format(b))
+            for t in list(sources[b]) + list(grads[b].values()):
+                if not t.is_contiguous() or t.dtype != member.dtype or not t.is_cuda:
+                    raise RuntimeError("EpochBatch: sources and gradients are contiguous {} arrays on the device".format(member.dtype))
+            for i, t in enumerate(sources[b]):
+                member.args.src[i] = t.data_ptr()
+            member.args.out, member.args.hs = out[b].data_ptr(), None
+            for key, slot in cg.direct.items():  # (the cotangent of the field's only read IS its gradient)
+                if key in grads[b]:
+                    member.args.cot[slot] = grads[b][key].data_ptr()
+            p = gat()  # (ad stays null: the slot of a level-0 update fused into the gather)
+            for gi, key in enumerate(cg.gathers):
+                p.g[gi] = grads[b][key].data_ptr()
+            self.ptrs.append(p)
+        self.hs_members = [b for b, member in enumerate(members) if member.cg.hs]
+        self.graphable = not self.hs_members
+        self.ring = _StagingRing(self.abytes + nb * self.gsize, out.device, self.depth)
+        self.slot, self.dev, self.hs_values = None, None, dict()
+        self.uploads, self.launches, self.host_seconds = 0, 0, 0.0  # blocks staged, calls of `launch`, host time in them
+
+    def _stage(self):
+        """All members' blocks -> a free slot of the ring -> the device (on the current stream)."""
+        if self.slot is not None:
+            self.ring.release(self.slot)  # (behind every launch that read the blocks staged before)
+        slot = self.slot = self.ring.take()
+        base = slot["host"].data_ptr()
+        for b, (member, p) in enumerate(zip(self.members, self.ptrs)):
+            ctypes.memmove(base + b * self.asize, ctypes.addressof(member.args), self.asize)
+            ctypes.memmove(base + self.abytes + b * self.gsize, ctypes.addressof(p), self.gsize)
+        self.dev = self.ring.upload(slot)
+        self.uploads += 1
+
+    def launch(self):
+        """k_fwd, k_final, k_loss and the gathers of all members on the current stream."""
+        t0 = time.perf_counter()
+        stale = self.dev is None
+        for b in self.hs_members:  # (only these cost host time per epoch)
+            values = self.members[b].host_scalars()
+            if self.hs_values.get(b) != values:
+                self.hs_values[b], stale = values, True
+                for i, v in enumerate(values):
+                    self.members[b].args.hsv[i] = v
+        if stale:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("EpochBatch: the argument blocks are staged before a capture, not inside it")
+            self._stage()
+        stream = ops.stream_ptr()
+        rc = self.lib.jit_fwd_batch(self.dev, self.nb, stream)
+        if rc != 0:
+            raise RuntimeError("generated kernel launch failed (jit_fwd_batch): hip error {}".format(rc))
+        for which in self.which:
+            rc = self.lib.jit_gather_batch(which, self.dev, self.dev + self.abytes, self.nb, stream)
+            if rc != 0:
+                raise RuntimeError("generated kernel launch failed (jit_gather_batch {}): hip error {}".format(which, rc))
+        self.launches += 1
+        self.host_seconds += time.perf_counter() - t0

@@ -237,9 +237,12 @@ class _Codegen(_MarchKernels, _GatherKernels):
         property(operator.attrgetter("body.adj." + k)) for k in (
             "cots", "cut_nodes", "jac_store", "pg_decl", "pg_offset", "pgrads", "pg2_used"))
 
-    def __init__(self, tr, outputs, raw, shape, state, slab=None, jac=False):
+    def __init__(self, tr, outputs, raw, shape, state, slab=None, jac=False, batch=False):
         """jac: also emit `k_jac`, the Jacobian coefficient arrays (`_jacobian_kernel`); "batch": and `k_jac_batch`, the
         same body for the members of an ensemble in one launch (a library of its own: what True emits does not change).
+        batch: also emit the forward and gather kernels for the members of an ensemble in one launch each (`k_fwd_batch`,
+        `k_final_batch`, `k_loss_batch`, `k_gat_*_batch`: `_epoch_batch_kernels`) -- again a library of its own; refused
+        (TraceUnsupported) for every kernel form that is no pointwise body under a new head.
         slab = (axis, n): the kernels of ONE RANK of a slab decomposition along grid axis `axis` (n owned
         cells of it per rank; odil_amd/slab_traced.py).  Threads then cover the owned cells only; the index of
         that axis seen by index leaves, constant arrays and windows is the GLOBAL one (i + a.off); sources are
@@ -275,6 +278,9 @@ class _Codegen(_MarchKernels, _GatherKernels):
         self.want_jac, self.jac_batch = bool(jac), jac == "batch"
         if self.jac_batch and slab is not None:
             raise TraceUnsupported("batched Jacobian kernel of a slab rank")
+        self.epoch_batch = bool(batch)
+        if self.epoch_batch and slab is not None:
+            raise TraceUnsupported("batched forward and gather kernels of a slab rank")
         self.par_outputs, self.par_numel, self.par_keys = None, dict(), dict()  # (parameter_outputs)
         # what source() leaves for the host: defined from the start, empty until then
         self.ncot, self.par_arrays, self.edge_numel, self.gathers_done = 0, 0, 0, False
@@ -1513,6 +1519,16 @@ class _Codegen(_MarchKernels, _GatherKernels):
 
     fwd_threads = 256  # threads of a workgroup of k_fwd
 
+    @property
+    def fwd_blocks(self):
+        """After source(): workgroups of `k_fwd` (what the host writes into `Args.nblocks`).
+        Every block ends with one block reduction per output and per network / array parameter: operators
+        that differentiate through parameters (dozens of reductions) want few, long blocks -- heat with two
+        space dimensions (46 parameters, 67 M points): 6.6 ms / epoch at 65536 blocks, 5.2 at 4096; plain
+        stencils prefer many (tracer 4-D: 62.0 ms at 65536, 64.5 at 4096)."""
+        cap = 4096 if len(self.pg_decl) > 8 else 65536
+        return min((self.total // self.vw_fwd + 255) // 256, cap)
+
     def source(self):
         tdt = self.tr.torch_dtype
         vw = self.vw
@@ -1531,6 +1547,8 @@ class _Codegen(_MarchKernels, _GatherKernels):
             has_net = any(n.op == "mlp" for n in self.order)
             interior = None if has_net else self._interior_copy(self.order, vw, reverse=True)
         nout = len(self.outputs)
+        if self.epoch_batch:
+            self._epoch_batch_refusal(march)
         self.npar = sum(len(g) for names in self.pgrads.values() for g in names)
         self.par_arrays = sum(2 * (len(layers) - 1) for _, layers in self.nets) + len(self.arrays)
         T = "double" if tdt == torch.float64 else "float"
@@ -1577,6 +1595,7 @@ class _Codegen(_MarchKernels, _GatherKernels):
         for (s, l), v in bofs.items():
             S.append("#define BOFS_{}_{} {}".format(s, l, v))
         # ---- k_fwd ---------------------------------------------------------------------------------------------
+        first_fwd = len(S)
         S.append('extern "C" __global__ __launch_bounds__({}) void k_fwd(const Args a) {{'.format(self.fwd_threads))
         S.append("  __shared__ T sm[{}];".format(self.fwd_threads // 64))
         for k in range(nout):
@@ -1609,12 +1628,18 @@ class _Codegen(_MarchKernels, _GatherKernels):
         for k, name in enumerate(self.pg_decl):
             S.append("  {{ const T s = block_sum({}, sm); if (threadIdx.x == 0) a.ppart[{} * a.nblocks + blockIdx.x] = s; }}".format(name, k))
         S.append("}")
+        fwd_body = S[first_fwd + 1:]
+        first_final = len(S)
         self._final_kernels(S, nout)
+        final_lines = S[first_final:]
         # ---- gathers -------------------------------------------------------------------------------------------
         if mgather is not None:
             self._march_gather_kernels(S, mgather)
         self.gathers_done = mgather is not None
+        first_gather = len(S)
         self._standard_gathers(S)
+        if self.epoch_batch:
+            self._epoch_batch_kernels(S, fwd_body, final_lines, S[first_gather:])
         if self.want_jac:
             self._jacobian_kernel(S)
         self._launchers(S, nout, HEAD)
@@ -1760,6 +1785,8 @@ class _Codegen(_MarchKernels, _GatherKernels):
                      "(const JacP*)ptrs_dev);".format(self.jac_blocks))
             S.append("  return (int)hipGetLastError();")
             S.append("}")
+        if self.epoch_batch:
+            self._epoch_batch_launchers(S, nout)
         # the argument block: sized last (the gradient expressions add host scalars of their own)
         HEAD.append(struct_text("Args", self.args_layout()))
         HEAD.append("#define HS(i) (a.hs ? a.hs[i] : a.hsv[i])")

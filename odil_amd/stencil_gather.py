@@ -1,7 +1,9 @@
 """The gathers of stencil_codegen.py: from the adjoints `k_fwd` stored to the gradient of every field (`k_gat_*`, one
 launch per field or `k_gat_all` for all of them), with the optimizer's update by the lane that forms the gradient, and the
 Jacobian coefficient arrays `k_jac`, which is a kernel of the same form, with `k_jac_batch`, its body for the members of an
-ensemble in one launch.  (The gathers of a marching kernel: stencil_march.py.)
+ensemble in one launch; and, for Adam ensembles, the forward and gather kernels under heads of that kind (`k_fwd_batch`,
+`k_final_batch`, `k_loss_batch`, `k_gat_*_batch`: `_epoch_batch_kernels`).  (The gathers of a marching kernel:
+stencil_march.py.)
 """
 
 import numpy as np
@@ -108,6 +110,7 @@ class _GatherKernels:
             S.append("    ga.g[k] = (T*)g[k];")
             S.append("    ga.ad[k] = AdamP{(T*)x[k], (T*)m[k], (T*)v[k], (T)alpha, (T)omb1, (T)omb2, (T)eps, (const T*)alpha_dev};")
             S.append("  }")
+            self.gather_all_blocks = nblocks_all
             S.append("  hipLaunchKernelGGL(k_gat_all, dim3({}), dim3(NB), 0, (hipStream_t)stream, *a, ga);".format(nblocks_all))
             S.append("  return (int)hipGetLastError();")
             S.append("}")
@@ -361,3 +364,110 @@ class _GatherKernels:
         S.append("  JacPC& jp = *(JacPC*)(jb + blockIdx.y);")
         S.append("  const AdamP ad = {nullptr, nullptr, nullptr, (T)0, (T)0, (T)0, (T)0, nullptr};")
         S.extend(body)
+
+    # ---- the forward and gather kernels for the members of an ensemble (batch=True) ---------------------------------
+    def _epoch_batch_refusal(self, march):
+        """TraceUnsupported for every kernel form that is not a pointwise body reading `a` alone (called from `source()`
+        once the forward body is known)."""
+        if march is not None:
+            raise TraceUnsupported("batched forward kernel: the marching forward kernel hands sums across workgroups "
+                                   "(`edge`), it is no pointwise body")
+        if self.nets or self.arrays or self.pg_decl:
+            raise TraceUnsupported("batched forward kernel: network or Array parameters (parameter gradients reduced over "
+                                   "the grid)")
+        if self.par_outputs:
+            raise TraceUnsupported("batched forward kernel: outputs in parameter space")
+
+    @staticmethod
+    def _kernel_bodies(lines):
+        """{name: (signature line, the lines after it up to and with the closing brace)} of the kernels in `lines`."""
+        found, k = dict(), 0
+        while k < len(lines):
+            if lines[k].startswith('extern "C" __global__'):
+                end = lines.index("}", k)
+                name = lines[k].split(" void ", 1)[1].split("(", 1)[0]
+                found[name] = (lines[k], lines[k + 1:end + 1])
+                k = end
+            k += 1
+        return found
+
+    def _epoch_batch_kernels(self, S, fwd_body, final_lines, gather_lines):
+        """`k_fwd_batch`, `k_final_batch`, `k_loss_batch`, `k_gat_<i>_batch` and `k_gat_all_batch`: the bodies of the single
+        kernels (their lines as emitted, after the signature) for the B members of an ensemble whose operators gave this
+        same source, on a grid with one more dimension for the member -- the technique of `_jacobian_batch_kernel`: every
+        member has its own argument block in DEVICE memory (`ab[member]`: its own sources, cotangent arrays, partial sums
+        and `out`), read through the constant address space (scalar loads) -- here into a by-value `Args a`, so that the
+        body is compiled on the values of a struct as the single kernel's is on its kernel argument: float kernels are
+        built with -ffp-contract=fast, where WHICH products are fused depends on the code around them, and with `a` a
+        reference into constant memory the forward kernel of a 12 x 18 float member fused two more (its loss differed
+        from the single launch's in the last bit).  The member is the first grid dimension the body does not
+        read: blockIdx.y (k_fwd, the gathers), blockIdx.z (k_final), blockIdx.x (k_loss); the XCD regrouping of
+        `_block_index` reads gridDim.x / blockIdx.x only, so every member keeps the schedule, the partial sums and their
+        order of its single launch.  The gathers take a `GatB` per member: the gradient array of every gather and ONE
+        AdamP (null here: the slot of a fused level-0 update)."""
+        finals, gathers = self._kernel_bodies(final_lines), self._kernel_bodies(gather_lines)
+        ng = max(1, len(self.gathers))
+        S.append("typedef const __attribute__((address_space(4))) Args ArgsC;")
+        S.append("struct GatB {{ T* g[{}]; AdamP ad; }};".format(ng))
+        S.append("typedef const __attribute__((address_space(4))) GatB GatBC;")
+
+        def head(name, bounds, member, gat=False):
+            S.append('extern "C" __global__ __launch_bounds__({}) void {}_batch(const Args* __restrict__ ab{}) {{'.format(
+                bounds, name, ", const GatB* __restrict__ gb" if gat else ""))
+            S.append("  Args a;")
+            S.append("  __builtin_memcpy(&a, (ArgsC*)(ab + {}), sizeof(Args));".format(member))
+            if gat:
+                S.append("  GatB gp;")
+                S.append("  __builtin_memcpy(&gp, (GatBC*)(gb + {}), sizeof(GatB));".format(member))
+                S.append("  const AdamP ad = gp.ad;")
+
+        head("k_fwd", self.fwd_threads, "blockIdx.y")
+        S.extend(fwd_body)
+        head("k_final", "NB", "blockIdx.z")
+        S.extend(finals["k_final"][1])
+        head("k_loss", 64, "blockIdx.x")
+        S.extend(finals["k_loss"][1])
+        for gi in range(len(self.gathers)):
+            name = "k_gat_{}".format(gi)
+            if name not in gathers or "T* __restrict__ g, const AdamP ad" not in gathers[name][0]:
+                raise TraceUnsupported("batched gather kernels: gather {} has no pointwise kernel of its own".format(gi))
+            head(name, "NB", "blockIdx.y", gat=True)
+            S.append("  T* __restrict__ g = gp.g[{}];".format(gi))
+            S.extend(gathers[name][1])
+        if self.merged:
+            if "const GatAll ga" not in gathers["k_gat_all"][0]:
+                raise TraceUnsupported("batched gather kernels: the merged gather is not the pointwise kernel")
+            head("k_gat_all", "NB", "blockIdx.y", gat=True)
+            S.append("  GatAll ga;")
+            for k, key in enumerate(self.merged):
+                S.append("  ga.g[{0}] = gp.g[{1}]; ga.ad[{0}] = ad;".format(k, self.gathers.index(key)))
+            S.extend(gathers["k_gat_all"][1])
+
+    def _epoch_batch_launchers(self, S, nout):
+        """`jit_fwd_batch`, `jit_gather_batch` (which = -1: the merged gather): args_dev / ptrs_dev are `nmembers` argument
+        blocks / `GatB` back to back in DEVICE memory."""
+        S.append('extern "C" int jit_fwd_batch(const void* args_dev, int nmembers, void* stream) {')
+        S.append("  if (nmembers < 1 || nmembers > 65535) return -1;")
+        S.append("  const Args* ab = (const Args*)args_dev;")
+        S.append("  hipLaunchKernelGGL(k_fwd_batch, dim3({}, nmembers), dim3({}), 0, (hipStream_t)stream, ab);".format(
+            self.fwd_blocks, self.fwd_threads))
+        S.append("  hipLaunchKernelGGL(k_final_batch, dim3({}, SEG, nmembers), dim3(NB), 0, (hipStream_t)stream, ab);".format(nout))
+        S.append("  hipLaunchKernelGGL(k_loss_batch, dim3(nmembers), dim3(64), 0, (hipStream_t)stream, ab);")
+        S.append("  return (int)hipGetLastError();")
+        S.append("}")
+        S.append('extern "C" int jit_gather_batch(int which, const void* args_dev, const void* ptrs_dev, int nmembers, void* stream) {')
+        S.append("  if (nmembers < 1 || nmembers > 65535) return -1;")
+        S.append("  const Args* ab = (const Args*)args_dev;")
+        S.append("  const GatB* gb = (const GatB*)ptrs_dev;")
+        S.append("  switch (which) {")
+        for gi, key in enumerate(self.gathers):
+            nblk = self.gather_blocks.get(gi, (int(np.prod(self._field_shape(key))) + 255) // 256)
+            S.append("    case {0}: hipLaunchKernelGGL(k_gat_{0}_batch, dim3({1}, nmembers), dim3(NB), 0, (hipStream_t)stream, ab, gb); "
+                     "break;".format(gi, nblk))
+        if self.merged:
+            S.append("    case -1: hipLaunchKernelGGL(k_gat_all_batch, dim3({}, nmembers), dim3(NB), 0, (hipStream_t)stream, ab, gb); "
+                     "break;".format(self.gather_all_blocks))
+        S.append("    default: return -1;")
+        S.append("  }")
+        S.append("  return (int)hipGetLastError();")
+        S.append("}")

@@ -121,9 +121,11 @@ class TracedOperator(StencilBinding):
     """loss / gradient of one user operator through its generated kernels: the binding of stencil_bind.py, plus where the
     sources come from and where the gradients go on a single GPU."""
 
-    def __init__(self, problem, state, only=None, jac=False):
+    def __init__(self, problem, state, only=None, jac=False, batch=False):
         """jac: also generate `k_jac`, the Jacobian coefficient arrays of `Problem.eval_operator_grad` (a library of its own:
-        the Newton driver asks for it, the gradient optimizers never pay for it); "batch": and `k_jac_batch` (`_Codegen`)."""
+        the Newton driver asks for it, the gradient optimizers never pay for it); "batch": and `k_jac_batch` (`_Codegen`).
+        batch: also generate the forward and gather kernels for the members of an ensemble (`_Codegen`; again a library
+        of its own, for `fused.TracedLaunchEnsemble`)."""
         from .core import Field, MultigridField
         from .util import printlog
 
@@ -131,7 +133,7 @@ class TracedOperator(StencilBinding):
         tr, outs, raw, self.names, G = trace_outputs(problem, state, only)
         # (parameter-space outputs without an elementwise form: the torch replay of _eval_offgrid)
         super().__init__(problem, state, tr, outs, raw, G, None, jac, domain.mod.device, lambda e: printlog(
-            "odil_amd: parameter-space output evaluated by torch ({})".format(e)))
+            "odil_amd: parameter-space output evaluated by torch ({})".format(e)), batch=batch)
         cg, dev, dt = self.cg, domain.mod.device, self.dtype
         self.tracer_keys = [n.attr for n in tr.nodes if n.op == "tracer"]
         self._hs_rows = None  # graph replay: (pinned table, device table, device row, device row index)
