@@ -20,6 +20,12 @@ alternating `--repeat` times, with the host time `stencil_bind.EpochBatch` spend
     python examples/diffusion/ensemble.py --members 256 --ndim 2 --N 64 --linearize members --single 0
     python examples/diffusion/ensemble.py --members 16 --ndim 2 --N 256 --form launches --linsolver multigrid
     python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --optimizer adam --multigrid 1 --epochs 200
+
+`--optimizer lbfgsb` runs it with L-BFGS-B, all members in lock-step: a round is one evaluation of all members, the batched
+vector launches and two host reads.  Printed: the time per round of all members and the host time blocked in the reads,
+beside the time per evaluation of the same members as single `optimize_grad(args, "lbfgsb", ...)` runs one after the other.
+
+    python examples/diffusion/ensemble.py --members 64 --ndim 2 --N 64 --optimizer lbfgsb --multigrid 1 --epochs 100
 """
 
 import argparse
@@ -161,6 +167,71 @@ def main_adam(args, callback):
             print(line)
 
 
+def main_lbfgsb(args, callback):
+    """The sweep with L-BFGS-B: all members in lock-step (`odil.util.optimize_ensemble`, one evaluation of all members per
+    round) against the same members as single `optimize_grad` runs one after the other, the two alternating `--repeat`
+    times after a warm-up."""
+    from odil_amd.optimizer import EarlyStopError
+
+    problems, states = make_members(args)
+    guess = [[a.clone() for a in problem.domain.arrays_from_state(state)] for problem, state in zip(problems, states)]
+
+    def restart():
+        for problem, state, arrays in zip(problems, states, guess):
+            problem.domain.arrays_to_state([a.clone() for a in arrays], state)
+        synchronize()
+
+    def timed(run):
+        restart()
+        start = time.perf_counter()
+        out = run()
+        synchronize()
+        return 1e3 * (time.perf_counter() - start), out
+
+    def together():
+        return odil.util.optimize_ensemble(args, problems, states, form="auto")[1]
+
+    def alone(members=None):
+        evals = 0
+        for problem, state in list(zip(problems, states))[:members]:
+            try:
+                evals += odil.util.optimize_grad(args, "lbfgsb", problem, state)[1].evals
+            except EarlyStopError as stop:  # (a member that converged or gave up before the last epoch)
+                evals += stop.optinfo.evals
+        return evals
+
+    arrays, optinfo = odil.util.optimize_ensemble(args, problems, states, callback, form="auto")  # (the warm-up, with the report)
+    printlog("\nroute '{}', form '{}', {} rounds, {} host reads".format(optinfo.route, optinfo.form, optinfo.rounds, optinfo.host_reads))
+    for b, (problem, state) in enumerate(zip(problems, states)):
+        printlog("member {:3d}: {} iterations, {} evaluations, {}; error u:{:.5g}".format(
+            b, optinfo.nits[b], optinfo.evals[b], optinfo.tasks[b], diffusion.error_rms(problem.domain, problem.extra, state, "u")))
+    if args.single:
+        timed(lambda: alone(1))
+    rounds, reads, total, singles = [], [], [], []
+    for _ in range(max(args.repeat, 1) if args.epochs > args.epoch_start else 0):
+        ms, info = timed(together)
+        total.append(ms)
+        rounds.append(ms / max(info.rounds, 1))
+        reads.append(1e3 * info.read_seconds / max(info.rounds, 1))
+        if args.single:
+            ms, evals = timed(alone)
+            singles.append((ms, ms / max(evals, 1)))
+    span = lambda values: "{:.3f} - {:.3f}".format(min(values), max(values))
+    lines = []
+    if rounds:
+        lines.append("ensemble of {} members: {} ms per round of all members ({} rounds, {} repetitions), of which the host "
+                     "is blocked in the two reads for {} ms".format(args.members, span(rounds), optinfo.rounds, len(rounds), span(reads)))
+    if singles:
+        ratio = min(ms for ms, _ in singles) / min(total)
+        lines.append("single runs: {} ms per evaluation of ONE member; all members one after the other take {:.1f} x the "
+                     "ensemble's time{} (best of each)".format(span([each for _, each in singles]), ratio,
+                                                              "" if ratio >= 1 else ": the ensemble is SLOWER"))
+    for line in lines:
+        printlog(line)
+        if not args.echo:
+            print(line)
+
+
 def main():
     args = parse_args()
     odil.setup_outdir(args)
@@ -175,6 +246,8 @@ def main():
     callback.next_active = lambda epoch: (epoch // every + 1) * every
     if args.optimizer in ("adam", "adamn"):
         return main_adam(args, callback)
+    if args.optimizer == "lbfgsb":
+        return main_lbfgsb(args, callback)
     problems, states = make_members(args)
     guess = [problem.domain.arrays_from_state(state)[0].clone() for problem, state in zip(problems, states)]
 

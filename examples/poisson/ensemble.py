@@ -19,6 +19,11 @@ Members beyond one workgroup (256^2, 64^3) take `--form launches` there too (or 
 Newton driver with the large levels as launches that cover all members (`gmg.EnsembleLaunchGMG`):
 
     python examples/poisson/ensemble.py --ndim 2 --N 256 --members 16 --multigrid 0 --optimizer newton --linsolver multigrid --epochs 1 --form launches
+
+With `--optimizer lbfgsb` all members run L-BFGS-B in lock-step as batched launches (a round: one evaluation of all
+members, the batched vector algebra, two host reads), timed beside the same members as single runs:
+
+    python examples/poisson/ensemble.py --ndim 2 --N 64 --members 64 --optimizer lbfgsb --epochs 100 --form auto
 """
 
 import os
@@ -44,6 +49,8 @@ def parse_args(argv=None):
     own.add_argument("--form", choices=("workgroup", "launches", "volumes", "auto"), default="workgroup",
                      help="One workgroup per member (small members), batched launches (any 1-D / 2-D size), batched launches "
                           "of 3-D members, or whichever fits")
+    own.add_argument("--single", type=int, default=1, help="--optimizer lbfgsb: also time the members as single runs")
+    own.add_argument("--repeat", type=int, default=3, help="--optimizer lbfgsb: timed repetitions of the ensemble and the single runs")
     mine, rest = own.parse_known_args(argv)
     args = poisson.parse_args(["--ndim", "1", "--N", "256"] + rest)
     for key, value in vars(mine).items():
@@ -67,6 +74,68 @@ def make_members(args):
         problems.append(problem)
         states.append(state)
     return problems, states
+
+
+def main_lbfgsb(args, problems, states, callback):
+    """The sweep with L-BFGS-B, all members in lock-step (a round: one evaluation of all members, the batched vector
+    launches, two host reads), timed against the same members as single `optimize_grad` runs one after the other; the two
+    alternate `--repeat` times after a warm-up."""
+    import time
+
+    import torch
+
+    from odil_amd.optimizer import EarlyStopError
+
+    form = "auto" if args.form == "workgroup" else args.form  # (the one-workgroup epochs are Adam's)
+    guess = [[a.clone() for a in problem.domain.arrays_from_state(state)] for problem, state in zip(problems, states)]
+
+    def timed(run):
+        for problem, state, arrays in zip(problems, states, guess):
+            problem.domain.arrays_to_state([a.clone() for a in arrays], state)
+        torch.cuda.synchronize()
+        start = time.perf_counter()
+        out = run()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - start), out
+
+    def alone(members=None):
+        evals = 0
+        for problem, state in list(zip(problems, states))[:members]:
+            try:
+                evals += odil.util.optimize_grad(args, "lbfgsb", problem, state)[1].evals
+            except EarlyStopError as stop:  # (a member that converged or gave up before the last epoch)
+                evals += stop.optinfo.evals
+        return evals
+
+    arrays, optinfo = odil.util.optimize_ensemble(args, problems, states, callback, form=form)  # (warm-up and report)
+    printlog("\nroute '{}', form '{}', {} rounds, {} host reads".format(optinfo.route, optinfo.form, optinfo.rounds, optinfo.host_reads))
+    for b in range(args.members):
+        printlog("member {:3d}: {} iterations, {} evaluations, {}".format(b, optinfo.nits[b], optinfo.evals[b], optinfo.tasks[b]))
+    if args.single:
+        timed(lambda: alone(1))
+    rounds, reads, total, singles = [], [], [], []
+    for _ in range(max(args.repeat, 1) if args.epochs > args.epoch_start else 0):
+        ms, info = timed(lambda: odil.util.optimize_ensemble(args, problems, states, form=form)[1])
+        total.append(ms)
+        rounds.append(ms / max(info.rounds, 1))
+        reads.append(1e3 * info.read_seconds / max(info.rounds, 1))
+        if args.single:
+            ms, evals = timed(alone)
+            singles.append((ms, ms / max(evals, 1)))
+    span = lambda values: "{:.3f} - {:.3f}".format(min(values), max(values))
+    lines = []
+    if rounds:
+        lines.append("ensemble of {} members: {} ms per round of all members ({} rounds, {} repetitions), of which the host "
+                     "is blocked in the two reads for {} ms".format(args.members, span(rounds), optinfo.rounds, len(rounds), span(reads)))
+    if singles:
+        ratio = min(ms for ms, _ in singles) / min(total)
+        lines.append("single runs: {} ms per evaluation of ONE member; all members one after the other take {:.1f} x the "
+                     "ensemble's time{} (best of each)".format(span([each for _, each in singles]), ratio,
+                                                              "" if ratio >= 1 else ": the ensemble is SLOWER"))
+    for line in lines:
+        printlog(line)
+        if not args.echo:
+            print(line)
 
 
 def main():
@@ -98,6 +167,8 @@ def main():
             if not args.echo:  # (the log goes to train.log: the verdict also to the terminal)
                 print(summary)
         return
+    if args.optimizer == "lbfgsb":
+        return main_lbfgsb(args, problems, states, callback)
     arrays, optinfo = odil.util.optimize_ensemble(args, problems, states, callback, lrs=lrs, form=args.form)
     if args.epochs > args.epoch_start:
         printlog("\nloss at the last epoch, per member:")

@@ -408,6 +408,72 @@ int odil_lincomb_f64(double* y, double beta, const double* a, int64_t lda, int n
 int odil_lincomb_f32(float* y, float beta, const float* a, int64_t lda, int nvec, const float* coef, int64_t n,
                      void* stream);
 
+/* The vector algebra of L-BFGS for an ENSEMBLE of nbatch members in lock-step: member-major [nbatch, n] vectors and a
+ * [nbatch, rows, n] history (rows = 2 m: s_k and y_k interleaved), member b of every array at b * <its stride> elements.
+ * Every launch covers a LIST of members: `members` is a DEVICE int32 array of nsel member numbers and the member of a
+ * workgroup is members[blockIdx.y]; members = NULL means all nbatch members (nsel is ignored).  Members that are not in
+ * the list, and the gaps between padded members, are neither read nor written.  Scalars and counts of a member come
+ * from DEVICE arrays with one entry per member (entry b, whatever the list), so that one upload serves a round.
+ * Member b gets the bits of the single entry point on its own arrays -- the same chunks, the same summation order,
+ * both functions of n alone:
+ *   odil_lbfgs_probe_batch    out[b * out_stride + 0 .. 2] = odil_lbfgs_probe of g_b, d_b (a NaN in g_b stays visible)
+ *   odil_lbfgs_dots3_batch    out[b * out_stride + j * ldo + k] = <a_{b,k}, bj_b> for k < counts[b] (counts = NULL:
+ *                             max_count for every member) and j < 3 (b1, b2 may be NULL -> zeros): odil_dots3 with
+ *                             nvec = counts[b]; entries k >= counts[b] are left alone.  a_{b,k} at b * a_stride + k * lda.
+ *   odil_lbfgs_lincomb_batch  y_b = beta * y_b + sum_{k < counts[b]} coef[b * coef_stride + k] * a_{b,k}, summed in
+ *                             the order of odil_lincomb
+ *   odil_lbfgs_axpy_batch     out_b = y_b + alpha[b] * x_b (odil_axpy; out may be y); y = NULL: out_b = alpha[b] * x_b
+ *                             (odil_scale; out may be x); y = alpha = NULL: out_b = x_b
+ *   odil_lbfgs_pair_batch     the correction pair of an accepted step: r_b = g_b - r_b, d_b = stp[b] * d_b and, where
+ *                             slot[b] >= 0, rows 2 slot[b] and 2 slot[b] + 1 of w_b = d_b, r_b -- per element what
+ *                             odil_scale, odil_axpy and two copies leave behind (no reduction: fusing is free)
+ * odil_dots3 picks one of two kernels from n, the alignment of its operands and nvec <= 128.  The batched launcher makes
+ * that choice once for the launch, so it refuses, before anything is launched, what would let it differ between
+ * members or from a member's single call: member strides or pointers that give members different 16-byte alignment,
+ * and max_count > 128 where n and the alignment admit the read-once kernel.  Also refused: null pointers, n < 1, nbatch
+ * or nsel outside 1 ... 65535 (nsel = 0 with a list: nothing to do, 0 is returned), nsel > nbatch, max_count outside
+ * 1 ... rows (0 ... rows for lincomb), member strides below a member's extent, and a partials workspace shorter than
+ * nbatch rows of partials_stride >= odil_lbfgs_batch_partials(n, max_count, elem_size) doubles. */
+int64_t odil_lbfgs_batch_partials(int64_t n, int max_count, int elem_size);
+int odil_lbfgs_probe_batch_f64(const double* g, int64_t g_stride, const double* d, int64_t d_stride, int64_t n,
+                               int nbatch, const int32_t* members, int nsel, double* partials,
+                               int64_t partials_stride, int64_t partials_len, double* out, int64_t out_stride,
+                               void* stream);
+int odil_lbfgs_probe_batch_f32(const float* g, int64_t g_stride, const float* d, int64_t d_stride, int64_t n,
+                               int nbatch, const int32_t* members, int nsel, double* partials,
+                               int64_t partials_stride, int64_t partials_len, float* out, int64_t out_stride,
+                               void* stream);
+int odil_lbfgs_dots3_batch_f64(const double* a, int64_t a_stride, int64_t lda, int rows, const int32_t* counts,
+                               int max_count, const double* b0, int64_t b0_stride, const double* b1, int64_t b1_stride,
+                               const double* b2, int64_t b2_stride, int64_t n, int nbatch, const int32_t* members,
+                               int nsel, double* partials, int64_t partials_stride, int64_t partials_len, double* out,
+                               int64_t out_stride, int64_t ldo, void* stream);
+int odil_lbfgs_dots3_batch_f32(const float* a, int64_t a_stride, int64_t lda, int rows, const int32_t* counts,
+                               int max_count, const float* b0, int64_t b0_stride, const float* b1, int64_t b1_stride,
+                               const float* b2, int64_t b2_stride, int64_t n, int nbatch, const int32_t* members,
+                               int nsel, double* partials, int64_t partials_stride, int64_t partials_len, float* out,
+                               int64_t out_stride, int64_t ldo, void* stream);
+int odil_lbfgs_lincomb_batch_f64(double* y, int64_t y_stride, double beta, const double* a, int64_t a_stride,
+                                 int64_t lda, int rows, const int32_t* counts, int max_count, const double* coef,
+                                 int64_t coef_stride, int64_t n, int nbatch, const int32_t* members, int nsel,
+                                 void* stream);
+int odil_lbfgs_lincomb_batch_f32(float* y, int64_t y_stride, float beta, const float* a, int64_t a_stride, int64_t lda,
+                                 int rows, const int32_t* counts, int max_count, const float* coef, int64_t coef_stride,
+                                 int64_t n, int nbatch, const int32_t* members, int nsel, void* stream);
+int odil_lbfgs_axpy_batch_f64(double* out, int64_t out_stride, const double* y, int64_t y_stride, const double* x,
+                              int64_t x_stride, const double* alpha, int64_t n, int nbatch, const int32_t* members,
+                              int nsel, void* stream);
+int odil_lbfgs_axpy_batch_f32(float* out, int64_t out_stride, const float* y, int64_t y_stride, const float* x,
+                              int64_t x_stride, const float* alpha, int64_t n, int nbatch, const int32_t* members,
+                              int nsel, void* stream);
+int odil_lbfgs_pair_batch_f64(const double* g, int64_t g_stride, double* r, int64_t r_stride, double* d,
+                              int64_t d_stride, double* w, int64_t w_stride, int64_t lda, int rows, const double* stp,
+                              const int32_t* slot, int64_t n, int nbatch, const int32_t* members, int nsel,
+                              void* stream);
+int odil_lbfgs_pair_batch_f32(const float* g, int64_t g_stride, float* r, int64_t r_stride, float* d, int64_t d_stride,
+                              float* w, int64_t w_stride, int64_t lda, int rows, const float* stp, const int32_t* slot,
+                              int64_t n, int nbatch, const int32_t* members, int nsel, void* stream);
+
 /* ---- Newton: matrix-free normal equations (reference core.py:1113-1217,
  *      linsolver.py:17-26) ------------------------------------------------------- */
 /* y = M x  where row r of M has coefficients coeffs[s][r] on columns roll(-shift_s):
@@ -692,6 +758,16 @@ int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, con
                                        int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
                                        float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
                                        void* stream);
+/* The stencil adjoint of all members WITHOUT an update (the gradient of an ensemble whose optimizer is not Adam):
+ * gu[b] = odil_poisson_adjoint of fu[b] for nbatch 1-D, 2-D or 3-D members in one launch, member b = blockIdx.y on the
+ * single kernel's walk, bit for bit.  Strides as above (>= cells of a member, multiples of 16 bytes).  Refused before
+ * anything is launched: null pointers, nbatch outside 1 ... 65535, ndim outside 1 ... 3, such strides.  The transposed
+ * prolongations need no entry point: odil_mg_synth_adj on [nbatch, *shape] arrays with loc '.' + loc runs the levels
+ * that odil_mg_batch_levels_ok / odil_mg_volumes_levels_ok vouch for. */
+int odil_poisson_adjoint_batch_f64(const double* fu, double* gu, int nbatch, int64_t fu_stride, int64_t g_stride,
+                                   const int64_t* shape, int ndim, const double* h2, double scale, void* stream);
+int odil_poisson_adjoint_batch_f32(const float* fu, float* gu, int nbatch, int64_t fu_stride, int64_t g_stride,
+                                   const int64_t* shape, int ndim, const float* h2, float scale, void* stream);
 
 /* TWO sweeps of odil_stencil_var_smooth in mode 0, with the weights omega1 and then omega2, in ONE pass: the coefficient arrays -- 7 of
  * the 10 words a sweep moves in 3-D -- are read once for both, the intermediate iterate stays on the CU.  out != x;

@@ -327,13 +327,14 @@ static int dots(const T* a, int64_t lda, int nvec, const T* b, int64_t n, double
 
 // out[j][k] = <a_k, b_j> for up to three right-hand vectors in ONE pass over the a_k (the L-BFGS
 // history is by far the largest operand: S^T y, S^T s and S^T g cost one read of S instead of three).
+// (the walk of one workgroup over its chunk of ONE a_k: shared by the single kernel and the ensemble form, which differ
+// in where a_k and the three partial sums of the workgroup live)
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_dots3(const T* __restrict__ a, int64_t lda, const T* __restrict__ b0,
-                                                 const T* __restrict__ b1, const T* __restrict__ b2, int64_t n,
-                                                 int nvec, double* __restrict__ partials, int vec_ok) {
+__device__ inline void dots3_unit(const T* __restrict__ ak, const T* __restrict__ b0, const T* __restrict__ b1,
+                                  const T* __restrict__ b2, int64_t n, int vec_ok, double* __restrict__ p0,
+                                  double* __restrict__ p1, double* __restrict__ p2) {
   constexpr int V = Vec16<T>::N;
   typedef typename Vec16<T>::type VT;
-  const T* ak = a + (int64_t)blockIdx.y * lda;
   // chunk boundaries on multiples of V so that every block reads whole 16 B packs
   const int64_t per = (((n + gridDim.x - 1) / gridDim.x) + V - 1) / V * V;
   const int64_t lo = (int64_t)blockIdx.x * per;
@@ -371,11 +372,19 @@ __global__ __launch_bounds__(kBlock) void k_dots3(const T* __restrict__ a, int64
   if (!b2) l2 = 0.0;
   const double t0 = block_sum(l0), t1 = block_sum(l1), t2 = block_sum(l2);
   if (threadIdx.x == 0) {
-    const int64_t base = (int64_t)blockIdx.y * kDotPartials + blockIdx.x;
-    partials[base] = t0;
-    partials[(int64_t)nvec * kDotPartials + base] = t1;
-    partials[(int64_t)2 * nvec * kDotPartials + base] = t2;
+    *p0 = t0;
+    *p1 = t1;
+    *p2 = t2;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_dots3(const T* __restrict__ a, int64_t lda, const T* __restrict__ b0,
+                                                 const T* __restrict__ b1, const T* __restrict__ b2, int64_t n,
+                                                 int nvec, double* __restrict__ partials, int vec_ok) {
+  const int64_t base = (int64_t)blockIdx.y * kDotPartials + blockIdx.x;
+  dots3_unit<T>(a + (int64_t)blockIdx.y * lda, b0, b1, b2, n, vec_ok, partials + base,
+                partials + (int64_t)nvec * kDotPartials + base, partials + (int64_t)2 * nvec * kDotPartials + base);
 }
 
 // The same products with the right-hand vectors read ONCE: a workgroup owns a chunk of elements for
@@ -384,10 +393,12 @@ __global__ __launch_bounds__(kBlock) void k_dots3(const T* __restrict__ a, int64
 // above re-reads b0 / b1 / b2 for every a_k -- four streams per history element, of which three come
 // from the last-level cache: 2.2 TB/s on the history of L-BFGS (m = 50, 1.4 M unknowns).
 constexpr int kDots3MaxVec = 128;  // S and Y of L-BFGS (m = 50) interleaved in one matrix
+// (the unit of the single kernel and of the ensemble form: the partial sum of product j of vector k goes to
+// partials[(j * jstride + k) * qstride + blockIdx.x])
 template <typename T, int E>
-__global__ __launch_bounds__(kBlock) void k_dots3_once(const T* __restrict__ a, int64_t lda, const T* __restrict__ b0,
-                                                      const T* __restrict__ b1, const T* __restrict__ b2, int64_t n,
-                                                      int nvec, double* __restrict__ partials) {
+__device__ inline void dots3_once_unit(const T* __restrict__ a, int64_t lda, const T* __restrict__ b0,
+                                       const T* __restrict__ b1, const T* __restrict__ b2, int64_t n, int nvec,
+                                       double* __restrict__ partials, int jstride, int qstride) {
   constexpr int V = Vec16<T>::N;
   constexpr int NP = E / V;  // 16 B packs per thread and chunk
   typedef typename Vec16<T>::type VT;
@@ -445,8 +456,15 @@ __global__ __launch_bounds__(kBlock) void k_dots3_once(const T* __restrict__ a, 
     double t = 0.0;
     for (int w = 0; w < kBlock / 64; ++w) t += acc[j][w][k];
     if ((j == 1 && !b1) || (j == 2 && !b2)) t = 0.0;
-    partials[(int64_t)q * kDotPartials + blockIdx.x] = t;
+    partials[((int64_t)j * jstride + k) * qstride + blockIdx.x] = t;
   }
+}
+
+template <typename T, int E>
+__global__ __launch_bounds__(kBlock) void k_dots3_once(const T* __restrict__ a, int64_t lda, const T* __restrict__ b0,
+                                                      const T* __restrict__ b1, const T* __restrict__ b2, int64_t n,
+                                                      int nvec, double* __restrict__ partials) {
+  dots3_once_unit<T, E>(a, lda, b0, b1, b2, n, nvec, partials, nvec, kDotPartials);
 }
 
 template <typename T>
@@ -477,14 +495,20 @@ static int dots3(const T* a, int64_t lda, int nvec, const T* b0, const T* b1, co
 }
 
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_lincomb(T* __restrict__ y, T beta, const T* __restrict__ a, int64_t lda,
-                                                   int nvec, const T* __restrict__ coef, int64_t n) {
+__device__ inline void lincomb_unit(T* __restrict__ y, T beta, const T* __restrict__ a, int64_t lda, int nvec,
+                                    const T* __restrict__ coef, int64_t n) {
   const int64_t nthreads = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthreads) {
     T acc = beta == T(0) ? T(0) : beta * y[i];
     for (int k = 0; k < nvec; ++k) acc = acc + coef[k] * a[(int64_t)k * lda + i];
     y[i] = acc;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_lincomb(T* __restrict__ y, T beta, const T* __restrict__ a, int64_t lda,
+                                                   int nvec, const T* __restrict__ coef, int64_t n) {
+  lincomb_unit<T>(y, beta, a, lda, nvec, coef, n);
 }
 
 template <typename T>
@@ -502,9 +526,10 @@ static int lincomb(T* y, T beta, const T* a, int64_t lda, int nvec, const T* coe
 // One pass over the new gradient for everything the L-BFGS line search reads on the host after an
 // evaluation: <g, d> (Wolfe test), <g, g> and max |g| (projected-gradient stopping test); fixed
 // summation order.
+// (units of the single kernels and of the ensemble forms: the partial sums of quantity q at partials[q * qstride + ...])
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_lbfgs_probe(const T* __restrict__ g, const T* __restrict__ d, int64_t n,
-                                                       double* __restrict__ partials) {
+__device__ inline void lbfgs_probe_unit(const T* __restrict__ g, const T* __restrict__ d, int64_t n,
+                                        double* __restrict__ partials, int qstride) {
   const int64_t per = (n + gridDim.x - 1) / gridDim.x;
   const int64_t lo = (int64_t)blockIdx.x * per;
   int64_t hi = lo + per;
@@ -528,19 +553,25 @@ __global__ __launch_bounds__(kBlock) void k_lbfgs_probe(const T* __restrict__ g,
   if (threadIdx.x == 0) {
     for (int w = 1; w < kBlock / 64; ++w) gm = wave_max[w] > gm || wave_max[w] != wave_max[w] ? wave_max[w] : gm;
     partials[blockIdx.x] = t0;
-    partials[kDotPartials + blockIdx.x] = t1;
-    partials[2 * kDotPartials + blockIdx.x] = gm;
+    partials[qstride + blockIdx.x] = t1;
+    partials[2 * qstride + blockIdx.x] = gm;
   }
 }
 
 template <typename T>
-__global__ __launch_bounds__(kBlock) void k_lbfgs_probe_final(const double* __restrict__ partials, int count,
-                                                             T* __restrict__ out) {
+__global__ __launch_bounds__(kBlock) void k_lbfgs_probe(const T* __restrict__ g, const T* __restrict__ d, int64_t n,
+                                                       double* __restrict__ partials) {
+  lbfgs_probe_unit<T>(g, d, n, partials, kDotPartials);
+}
+
+template <typename T>
+__device__ inline void lbfgs_probe_final_unit(const double* __restrict__ partials, int count, int qstride,
+                                              T* __restrict__ out) {
   double gd = 0.0, gg = 0.0, gm = 0.0;
   for (int i = threadIdx.x; i < count; i += kBlock) {
     gd += partials[i];
-    gg += partials[kDotPartials + i];
-    const double pm = partials[2 * kDotPartials + i];
+    gg += partials[qstride + i];
+    const double pm = partials[2 * qstride + i];
     gm = pm > gm || pm != pm ? pm : gm;
   }
   const double t0 = block_sum(gd), t1 = block_sum(gg);
@@ -560,6 +591,12 @@ __global__ __launch_bounds__(kBlock) void k_lbfgs_probe_final(const double* __re
 }
 
 template <typename T>
+__global__ __launch_bounds__(kBlock) void k_lbfgs_probe_final(const double* __restrict__ partials, int count,
+                                                             T* __restrict__ out) {
+  lbfgs_probe_final_unit<T>(partials, count, kDotPartials, out);
+}
+
+template <typename T>
 static int lbfgs_probe(const T* g, const T* d, int64_t n, double* partials, T* out, void* stream) {
   if (!g || !d || !partials || !out || n < 1) {
     set_error("lbfgs_probe: null pointer or n < 1");
@@ -571,6 +608,386 @@ static int lbfgs_probe(const T* g, const T* d, int64_t n, double* partials, T* o
   if (int e = check_launch("k_lbfgs_probe")) return e;
   hipLaunchKernelGGL(k_lbfgs_probe_final<T>, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, partials, grid, out);
   return check_launch("k_lbfgs_probe_final");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same algebra for an ENSEMBLE in lock-step (include/odil_hip.h: odil_lbfgs_*_batch): member-major [B, n] vectors,
+// a [B, rows, n] history.  blockIdx.y walks a list of members (a device array; null: all), every workgroup runs the
+// unit of the single kernel on its member's arrays, the partial sums of member b live in row b of the workspace and
+// are summed in the single launch's order.  Scalars and counts of a member: entry b of device arrays.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ inline int member_of(const int32_t* __restrict__ members, int nbatch) {
+  const int b = members ? members[blockIdx.y] : (int)blockIdx.y;
+  return b >= 0 && b < nbatch ? b : -1;  // (a list entry that names no member: nothing is touched)
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_lbfgs_probe_batch(const T* __restrict__ g, int64_t gs,
+                                                             const T* __restrict__ d, int64_t ds, int64_t n, int nbatch,
+                                                             const int32_t* __restrict__ members,
+                                                             double* __restrict__ partials, int64_t pstride) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  lbfgs_probe_unit<T>(g + b * gs, d + b * ds, n, partials + b * pstride, (int)gridDim.x);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_lbfgs_probe_final_batch(const double* __restrict__ partials, int64_t pstride,
+                                                                   int count, int nbatch,
+                                                                   const int32_t* __restrict__ members,
+                                                                   T* __restrict__ out, int64_t out_stride) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  lbfgs_probe_final_unit<T>(partials + b * pstride, count, count, out + b * out_stride);
+}
+
+// blockIdx.z = k, the history vector; members with fewer vectors leave the launch at once
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_dots3_batch(const T* __restrict__ a, int64_t as, int64_t lda,
+                                                       const int32_t* __restrict__ counts, int max_count,
+                                                       const T* __restrict__ b0, int64_t s0, const T* __restrict__ b1,
+                                                       int64_t s1, const T* __restrict__ b2, int64_t s2, int64_t n,
+                                                       int nbatch, const int32_t* __restrict__ members,
+                                                       double* __restrict__ partials, int64_t pstride, int vec_ok) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  const int count = counts ? min(counts[b], max_count) : max_count;
+  const int k = blockIdx.z;
+  if (k >= count) return;
+  double* p = partials + b * pstride + (int64_t)k * gridDim.x + blockIdx.x;
+  const int64_t jump = (int64_t)max_count * gridDim.x;
+  dots3_unit<T>(a + b * as + (int64_t)k * lda, b0 + b * s0, b1 ? b1 + b * s1 : nullptr, b2 ? b2 + b * s2 : nullptr, n,
+                vec_ok, p, p + jump, p + 2 * jump);
+}
+
+template <typename T, int E>
+__global__ __launch_bounds__(kBlock) void k_dots3_once_batch(const T* __restrict__ a, int64_t as, int64_t lda,
+                                                            const int32_t* __restrict__ counts, int max_count,
+                                                            const T* __restrict__ b0, int64_t s0,
+                                                            const T* __restrict__ b1, int64_t s1,
+                                                            const T* __restrict__ b2, int64_t s2, int64_t n, int nbatch,
+                                                            const int32_t* __restrict__ members,
+                                                            double* __restrict__ partials, int64_t pstride) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  const int count = counts ? min(counts[b], max_count) : max_count;
+  if (count < 1) return;
+  dots3_once_unit<T, E>(a + b * as, lda, b0 + b * s0, b1 ? b1 + b * s1 : nullptr, b2 ? b2 + b * s2 : nullptr, n, count,
+                        partials + b * pstride, max_count, (int)gridDim.x);
+}
+
+// k_final_reduce for member blockIdx.y: blockIdx.x = j * max_count + k, `chunks` partial sums each
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_dots3_final_batch(const double* __restrict__ partials, int64_t pstride,
+                                                             int chunks, const int32_t* __restrict__ counts,
+                                                             int max_count, int nbatch,
+                                                             const int32_t* __restrict__ members, T* __restrict__ out,
+                                                             int64_t out_stride, int64_t ldo) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  const int count = counts ? min(counts[b], max_count) : max_count;
+  const int j = blockIdx.x / max_count, k = blockIdx.x - j * max_count;
+  if (k >= count) return;
+  const double* p = partials + b * pstride + (int64_t)blockIdx.x * chunks;
+  double local = 0.0;
+  for (int i = threadIdx.x; i < chunks; i += kBlock) local += p[i];
+  const double total = block_sum(local);
+  if (threadIdx.x == 0) out[b * out_stride + j * ldo + k] = T(total / 1.0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_lincomb_batch(T* __restrict__ y, int64_t ys, T beta, const T* __restrict__ a,
+                                                         int64_t as, int64_t lda,
+                                                         const int32_t* __restrict__ counts, int max_count,
+                                                         const T* __restrict__ coef, int64_t cs, int64_t n, int nbatch,
+                                                         const int32_t* __restrict__ members) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  const int count = counts ? min(counts[b], max_count) : max_count;
+  lincomb_unit<T>(y + b * ys, beta, a + b * as, lda, count < 0 ? 0 : count, coef + b * cs, n);
+}
+
+// out = y + alpha[b] * x (k_axpy), out = alpha[b] * x (k_scale), out = x; launch-uniform branches
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_axpy_batch(T* out, int64_t os, const T* y, int64_t ys, const T* x,
+                                                      int64_t xs, const T* __restrict__ alpha, int64_t n, int nbatch,
+                                                      const int32_t* __restrict__ members) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  T* ob = out + b * os;
+  const T* xb = x + b * xs;
+  const T* yb = y ? y + b * ys : nullptr;
+  const T a = alpha ? alpha[b] : T(1);
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthreads) {
+    if (yb)
+      ob[i] = yb[i] + a * xb[i];
+    else if (alpha)
+      ob[i] = a * xb[i];
+    else
+      ob[i] = xb[i];
+  }
+}
+
+// y = g - r as the single run forms it (r = -1 * r, then r = r + 1 * g), s = stp * d, and both into their history rows
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_lbfgs_pair_batch(const T* __restrict__ g, int64_t gs, T* __restrict__ r,
+                                                            int64_t rs, T* __restrict__ d, int64_t ds,
+                                                            T* __restrict__ w, int64_t ws, int64_t lda, int rows,
+                                                            const T* __restrict__ stp, const int32_t* __restrict__ slot,
+                                                            int64_t n, int nbatch,
+                                                            const int32_t* __restrict__ members) {
+  const int b = member_of(members, nbatch);
+  if (b < 0) return;
+  const T* gb = g + b * gs;
+  T* rb = r + b * rs;
+  T* db = d + b * ds;
+  const T f = stp[b];
+  const int sl = slot[b];
+  const bool store = sl >= 0 && 2 * sl + 1 < rows;
+  T* wsb = w + b * ws + (int64_t)(store ? 2 * sl : 0) * lda;
+  T* wyb = wsb + lda;
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthreads) {
+    const T neg = T(-1) * rb[i];
+    const T yi = neg + T(1) * gb[i];
+    const T si = f * db[i];
+    rb[i] = yi;
+    db[i] = si;
+    if (store) {
+      wsb[i] = si;
+      wyb[i] = yi;
+    }
+  }
+}
+
+// What every batched launcher refuses first.  -> 0, with *rows_y = the grid's member extent (0: an empty list).
+static int batch_list(const char* what, int64_t n, int nbatch, const int32_t* members, int nsel, int* rows_y) {
+  if (n < 1) {
+    set_error("%s: n=%lld < 1", what, (long long)n);
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1 ... 65535, one grid row each)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (members && (nsel < 0 || nsel > nbatch)) {
+    set_error("%s: a list of %d members for %d members", what, nsel, nbatch);
+    return ODIL_E_INVAL;
+  }
+  *rows_y = members ? nsel : nbatch;
+  return 0;
+}
+
+static int batch_stride(const char* what, const char* name, int64_t stride, int64_t extent, int nbatch) {
+  if (nbatch > 1 && stride < extent) {
+    set_error("%s: member stride %lld of %s is below the %lld elements of a member", what, (long long)stride, name,
+              (long long)extent);
+    return ODIL_E_INVAL;
+  }
+  return 0;
+}
+
+// rows: history vectors a member HAS; max_count: how many of them a launch may use
+static int batch_history(const char* what, int64_t a_stride, int64_t lda, int rows, int max_count, int least, int64_t n,
+                         int nbatch) {
+  if (rows < 1 || max_count < least || max_count > rows) {
+    set_error("%s: count %d outside %d ... %d, the history vectors of a member", what, max_count, least, rows);
+    return ODIL_E_INVAL;
+  }
+  if (lda < n) {
+    set_error("%s: lda=%lld is below n=%lld", what, (long long)lda, (long long)n);
+    return ODIL_E_INVAL;
+  }
+  return batch_stride(what, "the history", a_stride, (int64_t)(rows - 1) * lda + n, nbatch);
+}
+
+static int dots3_chunks(int64_t n, int elem_size, bool once) {
+  const int grid = once ? grid_for(n, kBlock * 4 * (16 / elem_size)) : grid_for(n, kBlock * 64);
+  return grid > kDotPartials ? kDotPartials : grid;
+}
+
+static int probe_chunks(int64_t n) {
+  const int grid = grid_for(n, kBlock * 8);
+  return grid > kDotPartials ? kDotPartials : grid;
+}
+
+static int64_t batch_partials(int64_t n, int max_count, int elem_size) {
+  int chunks = dots3_chunks(n, elem_size, true);
+  if (dots3_chunks(n, elem_size, false) > chunks) chunks = dots3_chunks(n, elem_size, false);
+  if (probe_chunks(n) > chunks) chunks = probe_chunks(n);
+  return (int64_t)3 * (max_count < 1 ? 1 : max_count) * chunks;
+}
+
+static int batch_workspace(const char* what, const double* partials, int64_t partials_stride, int64_t partials_len,
+                           int64_t need, int nbatch) {
+  if (!partials || partials_stride < need || partials_len < (int64_t)(nbatch - 1) * partials_stride + need) {
+    set_error("%s: partials workspace too short: %lld doubles in rows of %lld, %d members need %lld each", what,
+              (long long)partials_len, (long long)partials_stride, nbatch, (long long)need);
+    return ODIL_E_INVAL;
+  }
+  return 0;
+}
+
+template <typename T>
+static int lbfgs_probe_batch(const T* g, int64_t g_stride, const T* d, int64_t d_stride, int64_t n, int nbatch,
+                             const int32_t* members, int nsel, double* partials, int64_t partials_stride,
+                             int64_t partials_len, T* out, int64_t out_stride, void* stream) {
+  static const char* what = "lbfgs_probe_batch";
+  if (!g || !d || !partials || !out) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  int ny;
+  if (int e = batch_list(what, n, nbatch, members, nsel, &ny)) return e;
+  if (int e = batch_stride(what, "g", g_stride, n, nbatch)) return e;
+  if (int e = batch_stride(what, "d", d_stride, n, nbatch)) return e;
+  if (int e = batch_stride(what, "out", out_stride, 3, nbatch)) return e;
+  const int grid = probe_chunks(n);
+  if (int e = batch_workspace(what, partials, partials_stride, partials_len, (int64_t)3 * grid, nbatch)) return e;
+  if (ny == 0) return 0;
+  hipLaunchKernelGGL(k_lbfgs_probe_batch<T>, dim3(grid, ny), dim3(kBlock), 0, (hipStream_t)stream, g, g_stride, d,
+                     d_stride, n, nbatch, members, partials, partials_stride);
+  if (int e = check_launch("k_lbfgs_probe_batch")) return e;
+  hipLaunchKernelGGL(k_lbfgs_probe_final_batch<T>, dim3(1, ny), dim3(kBlock), 0, (hipStream_t)stream, partials,
+                     partials_stride, grid, nbatch, members, out, out_stride);
+  return check_launch("k_lbfgs_probe_final_batch");
+}
+
+// vec_ok of `dots3` for member b's own arrays
+template <typename T>
+static int dots3_member_vec_ok(const T* a, int64_t as, int64_t lda, const T* b0, int64_t s0, const T* b1, int64_t s1,
+                               const T* b2, int64_t s2, int64_t b) {
+  return aligned16(a + b * as) && aligned16(b0 + b * s0) && (!b1 || aligned16(b1 + b * s1)) &&
+         (!b2 || aligned16(b2 + b * s2)) && (lda * (int64_t)sizeof(T)) % 16 == 0;
+}
+
+template <typename T>
+static int lbfgs_dots3_batch(const T* a, int64_t a_stride, int64_t lda, int rows, const int32_t* counts, int max_count,
+                             const T* b0, int64_t b0_stride, const T* b1, int64_t b1_stride, const T* b2,
+                             int64_t b2_stride, int64_t n, int nbatch, const int32_t* members, int nsel,
+                             double* partials, int64_t partials_stride, int64_t partials_len, T* out,
+                             int64_t out_stride, int64_t ldo, void* stream) {
+  static const char* what = "lbfgs_dots3_batch";
+  if (!a || !b0 || !partials || !out) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  int ny;
+  if (int e = batch_list(what, n, nbatch, members, nsel, &ny)) return e;
+  if (int e = batch_history(what, a_stride, lda, rows, max_count, 1, n, nbatch)) return e;
+  if (int e = batch_stride(what, "b0", b0_stride, n, nbatch)) return e;
+  if (b1)
+    if (int e = batch_stride(what, "b1", b1_stride, n, nbatch)) return e;
+  if (b2)
+    if (int e = batch_stride(what, "b2", b2_stride, n, nbatch)) return e;
+  if (ldo < max_count) {
+    set_error("%s: ldo=%lld is below the count %d", what, (long long)ldo, max_count);
+    return ODIL_E_INVAL;
+  }
+  if (int e = batch_stride(what, "out", out_stride, 2 * ldo + max_count, nbatch)) return e;
+  // the choice of kernel a member's single call makes: one answer for the launch, or none
+  const int vec_ok = dots3_member_vec_ok<T>(a, a_stride, lda, b0, b0_stride, b1, b1_stride, b2, b2_stride, 0);
+  for (int b = 1; b < nbatch; ++b)
+    if (dots3_member_vec_ok<T>(a, a_stride, lda, b0, b0_stride, b1, b1_stride, b2, b2_stride, b) != vec_ok) {
+      set_error("%s: member %d is%s aligned to 16 bytes where member 0 is%s (member strides off the 16-byte grid): the "
+                "members' single calls would not run the same kernel", what, b, vec_ok ? " not" : "", vec_ok ? "" : " not");
+      return ODIL_E_INVAL;
+    }
+  const bool once_sized = vec_ok && n % Vec16<T>::N == 0 && n >= (int64_t)kBlock * 64;
+  if (once_sized && max_count > kDots3MaxVec) {
+    set_error("%s: count %d above %d at n=%lld: the kernel a member's single call runs would depend on its own count", what,
+              max_count, kDots3MaxVec, (long long)n);
+    return ODIL_E_INVAL;
+  }
+  const int chunks = dots3_chunks(n, (int)sizeof(T), once_sized);
+  if (int e = batch_workspace(what, partials, partials_stride, partials_len, (int64_t)3 * max_count * chunks, nbatch))
+    return e;
+  if (ny == 0) return 0;
+  if (once_sized) {
+    constexpr int E = 4 * Vec16<T>::N;
+    hipLaunchKernelGGL((k_dots3_once_batch<T, E>), dim3(chunks, ny), dim3(kBlock), 0, (hipStream_t)stream, a, a_stride,
+                       lda, counts, max_count, b0, b0_stride, b1, b1_stride, b2, b2_stride, n, nbatch, members, partials,
+                       partials_stride);
+    if (int e = check_launch("k_dots3_once_batch")) return e;
+  } else {
+    hipLaunchKernelGGL(k_dots3_batch<T>, dim3(chunks, ny, max_count), dim3(kBlock), 0, (hipStream_t)stream, a, a_stride,
+                       lda, counts, max_count, b0, b0_stride, b1, b1_stride, b2, b2_stride, n, nbatch, members, partials,
+                       partials_stride, vec_ok);
+    if (int e = check_launch("k_dots3_batch")) return e;
+  }
+  hipLaunchKernelGGL(k_dots3_final_batch<T>, dim3(3 * max_count, ny), dim3(kBlock), 0, (hipStream_t)stream, partials,
+                     partials_stride, chunks, counts, max_count, nbatch, members, out, out_stride, ldo);
+  return check_launch("k_dots3_final_batch");
+}
+
+template <typename T>
+static int lbfgs_lincomb_batch(T* y, int64_t y_stride, T beta, const T* a, int64_t a_stride, int64_t lda, int rows,
+                               const int32_t* counts, int max_count, const T* coef, int64_t coef_stride, int64_t n,
+                               int nbatch, const int32_t* members, int nsel, void* stream) {
+  static const char* what = "lbfgs_lincomb_batch";
+  if (!y || !a || !coef) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  int ny;
+  if (int e = batch_list(what, n, nbatch, members, nsel, &ny)) return e;
+  if (int e = batch_history(what, a_stride, lda, rows, max_count, 0, n, nbatch)) return e;
+  if (int e = batch_stride(what, "y", y_stride, n, nbatch)) return e;
+  if (int e = batch_stride(what, "coef", coef_stride, max_count, nbatch)) return e;
+  if (ny == 0) return 0;
+  hipLaunchKernelGGL(k_lincomb_batch<T>, dim3(grid_for(n, kBlock), ny), dim3(kBlock), 0, (hipStream_t)stream, y,
+                     y_stride, beta, a, a_stride, lda, counts, max_count, coef, coef_stride, n, nbatch, members);
+  return check_launch("k_lincomb_batch");
+}
+
+template <typename T>
+static int lbfgs_axpy_batch(T* out, int64_t out_stride, const T* y, int64_t y_stride, const T* x, int64_t x_stride,
+                            const T* alpha, int64_t n, int nbatch, const int32_t* members, int nsel, void* stream) {
+  static const char* what = "lbfgs_axpy_batch";
+  if (!out || !x || (y && !alpha)) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  int ny;
+  if (int e = batch_list(what, n, nbatch, members, nsel, &ny)) return e;
+  if (int e = batch_stride(what, "out", out_stride, n, nbatch)) return e;
+  if (int e = batch_stride(what, "x", x_stride, n, nbatch)) return e;
+  if (y)
+    if (int e = batch_stride(what, "y", y_stride, n, nbatch)) return e;
+  if (ny == 0) return 0;
+  int grid = grid_flat(n, kBlock * 2);
+  if (grid > 65535 * 16) grid = 65535 * 16;
+  hipLaunchKernelGGL(k_axpy_batch<T>, dim3(grid, ny), dim3(kBlock), 0, (hipStream_t)stream, out, out_stride, y,
+                     y_stride, x, x_stride, alpha, n, nbatch, members);
+  return check_launch("k_axpy_batch");
+}
+
+template <typename T>
+static int lbfgs_pair_batch(const T* g, int64_t g_stride, T* r, int64_t r_stride, T* d, int64_t d_stride, T* w,
+                            int64_t w_stride, int64_t lda, int rows, const T* stp, const int32_t* slot, int64_t n,
+                            int nbatch, const int32_t* members, int nsel, void* stream) {
+  static const char* what = "lbfgs_pair_batch";
+  if (!g || !r || !d || !w || !stp || !slot) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  int ny;
+  if (int e = batch_list(what, n, nbatch, members, nsel, &ny)) return e;
+  if (rows < 2 || rows % 2) {
+    set_error("%s: %d history vectors (an even number: s and y interleaved)", what, rows);
+    return ODIL_E_INVAL;
+  }
+  if (int e = batch_history(what, w_stride, lda, rows, rows, 1, n, nbatch)) return e;
+  if (int e = batch_stride(what, "g", g_stride, n, nbatch)) return e;
+  if (int e = batch_stride(what, "r", r_stride, n, nbatch)) return e;
+  if (int e = batch_stride(what, "d", d_stride, n, nbatch)) return e;
+  if (ny == 0) return 0;
+  int grid = grid_flat(n, kBlock * 2);
+  if (grid > 65535 * 16) grid = 65535 * 16;
+  hipLaunchKernelGGL(k_lbfgs_pair_batch<T>, dim3(grid, ny), dim3(kBlock), 0, (hipStream_t)stream, g, g_stride, r,
+                     r_stride, d, d_stride, w, w_stride, lda, rows, stp, slot, n, nbatch, members);
+  return check_launch("k_lbfgs_pair_batch");
 }
 
 }  // namespace odil
@@ -668,6 +1085,78 @@ int odil_dots3_f64(const double* a, int64_t lda, int nvec, const double* b0, con
 int odil_dots3_f32(const float* a, int64_t lda, int nvec, const float* b0, const float* b1, const float* b2, int64_t n,
                    double* partials, float* out, void* stream) {
   return dots3<float>(a, lda, nvec, b0, b1, b2, n, partials, out, stream);
+}
+int64_t odil_lbfgs_batch_partials(int64_t n, int max_count, int elem_size) {
+  if (n < 1 || (elem_size != 4 && elem_size != 8)) return 0;
+  return batch_partials(n, max_count, elem_size);
+}
+int odil_lbfgs_probe_batch_f64(const double* g, int64_t g_stride, const double* d, int64_t d_stride, int64_t n,
+                               int nbatch, const int32_t* members, int nsel, double* partials,
+                               int64_t partials_stride, int64_t partials_len, double* out, int64_t out_stride,
+                               void* stream) {
+  return lbfgs_probe_batch<double>(g, g_stride, d, d_stride, n, nbatch, members, nsel, partials, partials_stride,
+                                   partials_len, out, out_stride, stream);
+}
+int odil_lbfgs_probe_batch_f32(const float* g, int64_t g_stride, const float* d, int64_t d_stride, int64_t n,
+                               int nbatch, const int32_t* members, int nsel, double* partials,
+                               int64_t partials_stride, int64_t partials_len, float* out, int64_t out_stride,
+                               void* stream) {
+  return lbfgs_probe_batch<float>(g, g_stride, d, d_stride, n, nbatch, members, nsel, partials, partials_stride,
+                                  partials_len, out, out_stride, stream);
+}
+int odil_lbfgs_dots3_batch_f64(const double* a, int64_t a_stride, int64_t lda, int rows, const int32_t* counts,
+                               int max_count, const double* b0, int64_t b0_stride, const double* b1, int64_t b1_stride,
+                               const double* b2, int64_t b2_stride, int64_t n, int nbatch, const int32_t* members,
+                               int nsel, double* partials, int64_t partials_stride, int64_t partials_len, double* out,
+                               int64_t out_stride, int64_t ldo, void* stream) {
+  return lbfgs_dots3_batch<double>(a, a_stride, lda, rows, counts, max_count, b0, b0_stride, b1, b1_stride, b2,
+                                   b2_stride, n, nbatch, members, nsel, partials, partials_stride, partials_len, out,
+                                   out_stride, ldo, stream);
+}
+int odil_lbfgs_dots3_batch_f32(const float* a, int64_t a_stride, int64_t lda, int rows, const int32_t* counts,
+                               int max_count, const float* b0, int64_t b0_stride, const float* b1, int64_t b1_stride,
+                               const float* b2, int64_t b2_stride, int64_t n, int nbatch, const int32_t* members,
+                               int nsel, double* partials, int64_t partials_stride, int64_t partials_len, float* out,
+                               int64_t out_stride, int64_t ldo, void* stream) {
+  return lbfgs_dots3_batch<float>(a, a_stride, lda, rows, counts, max_count, b0, b0_stride, b1, b1_stride, b2, b2_stride,
+                                  n, nbatch, members, nsel, partials, partials_stride, partials_len, out, out_stride, ldo,
+                                  stream);
+}
+int odil_lbfgs_lincomb_batch_f64(double* y, int64_t y_stride, double beta, const double* a, int64_t a_stride,
+                                 int64_t lda, int rows, const int32_t* counts, int max_count, const double* coef,
+                                 int64_t coef_stride, int64_t n, int nbatch, const int32_t* members, int nsel,
+                                 void* stream) {
+  return lbfgs_lincomb_batch<double>(y, y_stride, beta, a, a_stride, lda, rows, counts, max_count, coef, coef_stride, n,
+                                     nbatch, members, nsel, stream);
+}
+int odil_lbfgs_lincomb_batch_f32(float* y, int64_t y_stride, float beta, const float* a, int64_t a_stride, int64_t lda,
+                                 int rows, const int32_t* counts, int max_count, const float* coef, int64_t coef_stride,
+                                 int64_t n, int nbatch, const int32_t* members, int nsel, void* stream) {
+  return lbfgs_lincomb_batch<float>(y, y_stride, beta, a, a_stride, lda, rows, counts, max_count, coef, coef_stride, n,
+                                    nbatch, members, nsel, stream);
+}
+int odil_lbfgs_axpy_batch_f64(double* out, int64_t out_stride, const double* y, int64_t y_stride, const double* x,
+                              int64_t x_stride, const double* alpha, int64_t n, int nbatch, const int32_t* members,
+                              int nsel, void* stream) {
+  return lbfgs_axpy_batch<double>(out, out_stride, y, y_stride, x, x_stride, alpha, n, nbatch, members, nsel, stream);
+}
+int odil_lbfgs_axpy_batch_f32(float* out, int64_t out_stride, const float* y, int64_t y_stride, const float* x,
+                              int64_t x_stride, const float* alpha, int64_t n, int nbatch, const int32_t* members,
+                              int nsel, void* stream) {
+  return lbfgs_axpy_batch<float>(out, out_stride, y, y_stride, x, x_stride, alpha, n, nbatch, members, nsel, stream);
+}
+int odil_lbfgs_pair_batch_f64(const double* g, int64_t g_stride, double* r, int64_t r_stride, double* d,
+                              int64_t d_stride, double* w, int64_t w_stride, int64_t lda, int rows, const double* stp,
+                              const int32_t* slot, int64_t n, int nbatch, const int32_t* members, int nsel,
+                              void* stream) {
+  return lbfgs_pair_batch<double>(g, g_stride, r, r_stride, d, d_stride, w, w_stride, lda, rows, stp, slot, n, nbatch,
+                                  members, nsel, stream);
+}
+int odil_lbfgs_pair_batch_f32(const float* g, int64_t g_stride, float* r, int64_t r_stride, float* d, int64_t d_stride,
+                              float* w, int64_t w_stride, int64_t lda, int rows, const float* stp, const int32_t* slot,
+                              int64_t n, int nbatch, const int32_t* members, int nsel, void* stream) {
+  return lbfgs_pair_batch<float>(g, g_stride, r, r_stride, d, d_stride, w, w_stride, lda, rows, stp, slot, n, nbatch,
+                                 members, nsel, stream);
 }
 int odil_lincomb_f64(double* y, double beta, const double* a, int64_t lda, int nvec, const double* coef, int64_t n,
                      void* stream) {

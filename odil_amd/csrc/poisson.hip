@@ -413,6 +413,15 @@ __global__ __launch_bounds__(kBlock) void k_poisson_adjoint_batch(const T* __res
   poisson_adjoint_unit<T, FULL>(fu + b * st.s[0], gu ? gu + b * st.s[1] : nullptr, a, h, scale, ad, b);
 }
 
+// The ensemble form without an update: member blockIdx.y, the gradient alone (no x / m / v to offset).
+template <typename T, bool FULL>
+__global__ __launch_bounds__(kBlock) void k_poisson_adjoint_grad_batch(const T* __restrict__ fu, T* __restrict__ gu,
+                                                                      BatchStrides st, StencilArgs a, H2<T> h, T scale) {
+  const int64_t b = blockIdx.y;
+  const AdamArgs<T> none{nullptr, nullptr, nullptr, T(0), T(0), T(0), T(0), nullptr, 0, 0};
+  poisson_adjoint_unit<T, FULL>(fu + b * st.s[0], gu + b * st.s[1], a, h, scale, none, b);
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_poisson_jac(T* __restrict__ coeffs, StencilArgs a, int ndim, T h2z, T h2y,
                                                        T h2x) {
@@ -714,6 +723,33 @@ static int poisson_adjoint_adam_batch(const T* fu, T* gu, T* x, T* m, T* v, int 
 }
 
 template <typename T>
+static int poisson_adjoint_batch(const T* fu, T* gu, int nbatch, int64_t fu_stride, int64_t g_stride,
+                                 const int64_t* shape, int ndim, const T* h2, T scale, void* stream) {
+  static const char* what = "poisson_adjoint_batch";
+  if (!fu || !gu) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (ndim < 1 || ndim > 3) {
+    set_error("%s: ndim %d (the ensemble runs 1-D to 3-D members)", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  StencilArgs a;
+  T h[3];
+  BatchStrides st = {{fu_stride, g_stride, 0, 0, 0}};
+  if (int e = batch_args<T>(what, a, h, shape, ndim, h2, nbatch, st.s, 2, ndim == 3)) return e;
+  a.loss_z0 = a.loss_z1 = 0;
+  const dim3 grid(unit_grid(a.usched), nbatch);
+  if (a.n[2] % VecOf<T>::N == 0)
+    hipLaunchKernelGGL((k_poisson_adjoint_grad_batch<T, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, fu, gu, st, a,
+                       make_h2<T>(h), scale);
+  else
+    hipLaunchKernelGGL((k_poisson_adjoint_grad_batch<T, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, fu, gu, st,
+                       a, make_h2<T>(h), scale);
+  return check_launch("k_poisson_adjoint_grad_batch");
+}
+
+template <typename T>
 static int poisson_jacobi(const T* u, const T* rhs, T* uout, const int64_t* shape, int ndim, const T* h2, T omega,
                           void* stream) {
   StencilArgs a;
@@ -922,6 +958,14 @@ int odil_poisson_adjoint_adam_batch_f64(const double* fu, double* gu, double* x,
   return poisson_adjoint_adam_batch<double>(fu, gu, x, m, v, nbatch, fu_stride, g_stride, x_stride, m_stride, v_stride,
                                             shape, ndim, h2, scale, one_minus_b1, one_minus_b2, eps, alpha_dev,
                                             alpha_stride, stream);
+}
+int odil_poisson_adjoint_batch_f64(const double* fu, double* gu, int nbatch, int64_t fu_stride, int64_t g_stride,
+                                   const int64_t* shape, int ndim, const double* h2, double scale, void* stream) {
+  return poisson_adjoint_batch<double>(fu, gu, nbatch, fu_stride, g_stride, shape, ndim, h2, scale, stream);
+}
+int odil_poisson_adjoint_batch_f32(const float* fu, float* gu, int nbatch, int64_t fu_stride, int64_t g_stride,
+                                   const int64_t* shape, int ndim, const float* h2, float scale, void* stream) {
+  return poisson_adjoint_batch<float>(fu, gu, nbatch, fu_stride, g_stride, shape, ndim, h2, scale, stream);
 }
 int odil_poisson_adjoint_adam_volumes_f64(const double* fu, double* gu, double* x, double* m, double* v, int nbatch,
                                           int64_t fu_stride, int64_t g_stride, int64_t x_stride, int64_t m_stride,

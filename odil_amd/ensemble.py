@@ -1,4 +1,4 @@
-"""Drivers that run B problems side by side: `optimize_ensemble` (Adam) and `optimize_newton_ensemble` (Newton).  The
+"""Drivers that run B problems side by side: `optimize_ensemble` (Adam, L-BFGS-B) and `optimize_newton_ensemble` (Newton).  The
 reference runs a sweep as B processes and has no counterpart; `util` re-exports both names next to `optimize_grad` /
 `optimize_newton`, whose single runs every member reproduces.  Written once for both drivers: `_check_members`; for both
 Newton routes: `_newton_loop`.  `linearize_ensemble` (`EnsembleLinearizer`) is the linearisation of the Newton driver's
@@ -76,7 +76,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     fused.volumes_refusal).  'auto': 'volumes' for 3-D members; else 'workgroup' where `fused.small_refusal` admits the
     members, 'launches' otherwise.
 
-    args.optimizer must be 'adam' / 'adamn'; lrs: one step size per member (default args.lr for all).
+    args.optimizer must be 'adam' / 'adamn' (or 'lbfgsb': the last paragraph); lrs: one step size per member (default
+    args.lr for all).
     callback(member, state, epoch, pinfo): called for every member at args.epoch_start (the initial evaluation) and at
     the epochs its `next_active(epoch)` attribute names (the cadence of `make_callback`; without the attribute: every
     epoch), pinfo as `optimize_grad` reports it, device scalars read lazily.  The callback reads the state; arrays it
@@ -101,12 +102,41 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     `problem.tracers`), which travel in the argument blocks and are uploaded again when they change.  With
     form='workgroup', or without tracing, a member that is not the Poisson operator stays refused.
     Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route:
-    "poisson" or "traced"; optinfo.form: the form that ran."""
+    "poisson" or "traced"; optinfo.form: the form that ran.
+
+    args.optimizer == 'lbfgsb' runs L-BFGS-B on all members in LOCK-STEP (`LbfgsbOptimizer.run_ensemble`), on both routes,
+    with form 'launches', 'volumes' or 'auto' ('auto' by dimension; 'workgroup', the default, raises ValueError: the
+    whole-epoch kernels are Adam; so does `lrs`).  Route selection and structural checks are those above.  A round is ONE
+    evaluation of all members (the launches of an epoch without any update: `BatchedLaunches.loss_grad`), the batched
+    vector algebra (`ops.lbfgs_*_batch`, each launch over the list of members that need it) and two host reads -- the cost
+    of one iteration of a single run, whatever B is.  Members progress independently: one in the middle of a line search
+    evaluates again while others accept their step; a member retires when it has made args.epochs iterations, converges
+    (args.bfgs_pgtol) or its line search fails with an empty memory, and is evaluated along but never touched.  Every
+    member ends where its own `optimize_grad(args, "lbfgsb", problem, state)` run ends, bit for bit.  args.bfgs_m (at most
+    64: ValueError beyond), bfgs_maxls and bfgs_pgtol as in `optimize_grad`; the history of all members takes
+    B 2 m n 8 bytes, refused (ValueError naming the bytes) before any state changes when the device has less free.
+    No EarlyStopError: optinfo.tasks / .warnflags / .nits / .evals ([B]) say how each member ended; optinfo.rounds,
+    .host_reads, .read_seconds (host time blocked in the reads), .ensemble.  The callback is called for member b at the
+    start and after those of ITS OWN iterations that `next_active` names, when its state shows the iterate it has just
+    accepted; at return every state holds its member's last accepted iterate.  Eager: no graph replay."""
     from . import fused, runtime
 
     optname = getattr(args, "optimizer", "adam")
-    if optname not in ("adam", "adamn"):
-        raise ValueError("optimize_ensemble runs Adam ('adam' / 'adamn'), not optimizer '{}'".format(optname))
+    if optname not in ("adam", "adamn", "lbfgsb"):
+        raise ValueError("optimize_ensemble runs Adam ('adam' / 'adamn') and L-BFGS-B ('lbfgsb'), not optimizer '{}'".format(optname))
+    lbfgsb = optname == "lbfgsb"
+    if lbfgsb:
+        if form == "workgroup":
+            raise ValueError("optimize_ensemble: form 'workgroup' runs whole Adam epochs in one launch; optimizer 'lbfgsb' runs "
+                             "as batched launches: form='launches', 'volumes' or 'auto'")
+        if lrs is not None:
+            raise ValueError("optimize_ensemble: step sizes `lrs` are Adam's; the line search of L-BFGS-B finds its own")
+        for src, dst in [("bfgs_m", "m"), ("bfgs_pgtol", "pgtol"), ("bfgs_maxls", "maxls")]:  # (as optimize_grad)
+            if getattr(args, src, None) is not None:
+                kwargs[dst] = getattr(args, src)
+        opt = make_optimizer(optname, dtype=problems[0].domain.dtype if problems else None, **kwargs)
+        if opt.m > opt.max_ensemble_m:
+            raise ValueError("optimize_ensemble: " + opt.ensemble_refusal(len(problems), 0, "cpu"))
     if lrs is not None and len(lrs) != len(problems):
         raise ValueError("optimize_ensemble: {} step sizes for {} members".format(len(lrs), len(problems)))
     fused.ensemble_form(form, [(2,)], torch.float64)  # (any other value of `form` raises here)
@@ -125,7 +155,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
         if shapes[0] != tuple(domain.cshape):
             refuse(b, "the unknown is not a cell-centred field of the domain")
         if b == 0:
-            form = fused.ensemble_form(form, shapes, arrays[0].dtype)
+            # (L-BFGS-B has no one-workgroup form: 'auto' picks among the batched launches, by dimension)
+            form = _traced_form(form, shapes) if lbfgsb else fused.ensemble_form(form, shapes, arrays[0].dtype)
             traceable = traceable and arrays[0].is_cuda
         reasons = dict(poisson=predicates[form](shapes, arrays[0].dtype), traced=None)
         if traceable:
@@ -162,12 +193,18 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     else:  # (ALL members, the Poisson ones as the traced operators they are)
         form = _traced_form(requested, kind["shapes"])
         ensemble = _held_traced_ensemble(problems, states, kind, form)
+    if lbfgsb:  # (before any state changes: the history of all members must fit the device)
+        reason = opt.ensemble_refusal(ensemble.nbatch, ensemble.total, ensemble.device)
+        if reason is not None:
+            raise ValueError("optimize_ensemble: " + reason)
     for b, (problem, state) in enumerate(zip(problems, states)):
         levels = ensemble.levels(ensemble.x, b)
         for dst, src in zip(levels, problem.domain.arrays_from_state(state)):
             dst.copy_(src)
         problem.domain.arrays_to_state(levels, state)  # (views of the packed state: always the current iterate)
 
+    if lbfgsb:
+        return _lbfgsb_run(args, opt, problems, states, callback, ensemble, route, form)
     for src, dst in [("adam_epsilon", "epsilon"), ("adam_beta_1", "beta_1"), ("adam_beta_2", "beta_2")]:
         if getattr(args, src, None) is not None:
             kwargs[dst] = getattr(args, src)
@@ -191,6 +228,31 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     arrays, optinfo = opt.run_ensemble(ensemble, epochs=args.epochs - args.epoch_start,
                                        callback=callback_wrap if callback else None, lr=args.lr, lrs=lrs,
                                        epoch_start=args.epoch_start, **kwargs)
+    optinfo.route, optinfo.form = route, form
+    return arrays, optinfo
+
+
+def _lbfgsb_run(args, opt, problems, states, callback, ensemble, route, form):
+    """The L-BFGS-B end of `optimize_ensemble`: the members are checked, `ensemble` holds their state (the states' arrays
+    are views of it).  All members advance in lock-step (`LbfgsbOptimizer.run_ensemble`); the callback's pinfo is the
+    member's last evaluation -- the one at the iterate it has just accepted -- copied before a later round overwrites it."""
+    util.printlog("Running {} optimizer on an ensemble of {} members".format(opt.displayname, len(problems)))
+
+    def report(b, epoch):
+        if route == "traced":  # (the member's own names, terms and norms)
+            k, j = ensemble.where[b]
+            loss, terms, norms = ensemble.report(b, {k: {j: ensemble.outs[k][j].clone()}})
+            callback(b, states[b], epoch, util._pinfo(loss, terms, ensemble.names[b], norms))
+        else:
+            loss = ensemble.loss[b].clone()
+            callback(b, states[b], epoch, util._pinfo(loss, [loss], ensemble.names[b], [torch.sqrt(loss)]))
+
+    if callback:
+        report.next_active = getattr(callback, "next_active", None)
+        for b, (problem, state) in enumerate(zip(problems, states)):  # (the report of the start, as optimize_grad makes it)
+            callback(b, state, args.epoch_start, _evaluate(problem, state))
+    arrays, optinfo = opt.run_ensemble(ensemble, epochs=args.epochs - args.epoch_start, callback=report if callback else None,
+                                       epoch_start=args.epoch_start)
     optinfo.route, optinfo.form = route, form
     return arrays, optinfo
 

@@ -311,6 +311,18 @@ class BatchedLaunches(_Members):
         """The level arrays of one member: views of the [B, *shape] level tensors."""
         return [t[member] for t in packed]
 
+    def loss_grad(self):
+        """The launches of `epoch` WITHOUT any update (what an optimizer that is not Adam drives: L-BFGS-B in lock-step):
+        the [B] losses at self.x land in self.loss, the gradient of every level in self.g; x, m and v stay as they are.
+        Member b gets the bits of its single gradient evaluation."""
+        raise NotImplementedError
+
+    def _transposes(self):
+        """The gradients of the levels >= 1 from g[0]: `ops.mg_synth_adj` on the [B, *shape] level arrays, the members as a
+        leading axis that is not coarsened -- the levels the ensemble's constructor has asked the library about."""
+        if self.nlvl > 1:
+            ops.mg_synth_adj(self.g[0], [(self.nbatch,) + s for s in self.shapes], self.loc, grads=self.g)
+
     def epochs(self, alphas, losses, norms, omb1, omb2, eps):
         """losses.shape[1] epochs (the interface of PoissonEnsemble.epochs).  alphas: [B, E], or [E] shared by all members."""
         for e in range(losses.shape[1]):
@@ -347,6 +359,12 @@ class PoissonLaunchEnsemble(BatchedLaunches):
                                        omb2, eps)
         ops.mg_synth_adj_adam_batch(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
 
+    def loss_grad(self):
+        ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+        ops.poisson_residual_batch(self.u, self.rhs, self.h2, self.fu, self.loss, self.partials)
+        ops.poisson_adjoint_batch(self.fu, self.h2, self.scale, self.g[0])
+        self._transposes()
+
 
 class PoissonVolumeEnsemble(BatchedLaunches):
     """B recognised 3-D Poisson problems of one shape side by side, as batched launches: an epoch is the launches of
@@ -379,6 +397,15 @@ class PoissonVolumeEnsemble(BatchedLaunches):
         ops.poisson_adjoint_adam_volumes(self.fu, self.h2, self.scale, self.g[0], self.x[0], self.m[0], self.v[0], alphas,
                                          omb1, omb2, eps)
         ops.mg_synth_adj_adam_volumes(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+
+    def loss_grad(self):
+        if self.nlvl > 2:
+            coarse = ops.mg_synth(self.x[1:], self.loc, work=[None] + self.work[2:], out=self.work[1])
+        else:
+            coarse = self.x[1]
+        ops.poisson_residual_synth_batch(coarse, self.x[0], self.rhs, self.h2, self.fu, self.loss, self.partials, self.sums)
+        ops.poisson_adjoint_batch(self.fu, self.h2, self.scale, self.g[0])
+        self._transposes()
 
 
 class TracedLaunchEnsemble(BatchedLaunches):
@@ -458,6 +485,16 @@ class TracedLaunchEnsemble(BatchedLaunches):
             chain = ops.mg_synth_adj_adam_volumes if self.ndim == 3 else ops.mg_synth_adj_adam_batch
             chain(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
         ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], alphas, omb1, omb2, eps)
+
+    def loss_grad(self):
+        if self.nlvl > 1:
+            ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+        for batch in self.batches:
+            batch.launch()
+        if len(self.groups) > 1:
+            for index, out in zip(self.index, self.outs):
+                self.loss.index_copy_(0, index, out[:, 0])
+        self._transposes()
 
 
 def traced_refusal(shapes, dtype, form, nbatch=1):

@@ -1205,6 +1205,136 @@ def lincomb(y, beta, a, coef):
     return y
 
 
+# ---- the L-BFGS algebra of an ensemble in lock-step (odil_lbfgs_*_batch): member-major [B, n] vectors whose rows are
+# contiguous (the leading stride is the member stride: members may be padded), a [B, rows, n] history, a list of members
+# per launch (`members`: DEVICE int32 tensor, None = all), scalars and counts of a member in entry b of DEVICE arrays.
+def _rows(t, nb, n):
+    """(device pointer, member stride in elements) of a [B, n] tensor with contiguous rows."""
+    assert t.dim() == 2 and tuple(t.shape) == (nb, n) and (t.stride(1) == 1 or n == 1), (tuple(t.shape), t.stride())
+    if not t.is_cuda:
+        raise _lib.OdilHipError("tensor is on '{}': the HIP kernels need device memory (no CPU fallback)".format(t.device))
+    return c_void_p(t.data_ptr()), c_int64(t.stride(0) if nb > 1 else max(t.stride(0), n))
+
+
+def _history(w, nb, n):
+    """(device pointer, member stride, lda, rows) of a [B, rows, n] history."""
+    assert w.dim() == 3 and w.shape[0] == nb and w.shape[2] == n and (w.stride(2) == 1 or n == 1), (tuple(w.shape), w.stride())
+    if not w.is_cuda:
+        raise _lib.OdilHipError("tensor is on '{}': the HIP kernels need device memory (no CPU fallback)".format(w.device))
+    rows = int(w.shape[1])
+    lda = w.stride(1) if rows > 1 else max(w.stride(1), n)
+    return c_void_p(w.data_ptr()), c_int64(w.stride(0) if nb > 1 else max(w.stride(0), (rows - 1) * lda + n)), c_int64(lda), rows
+
+
+def _member_list(members, nb):
+    if members is None:
+        return None, c_int(nb)
+    assert members.dtype == torch.int32 and members.is_cuda and members.is_contiguous() and members.dim() == 1
+    return c_void_p(members.data_ptr()), c_int(members.numel())
+
+
+def _per_member(t, nb, dtype):
+    if t is None:
+        return None
+    assert t.dtype == dtype and t.is_cuda and t.is_contiguous() and t.numel() == nb, (t.dtype, tuple(t.shape))
+    return c_void_p(t.data_ptr())
+
+
+def lbfgs_batch_partials(n, max_count, dtype):
+    """Doubles of reduction workspace ONE member of `lbfgs_probe_batch` / `lbfgs_dots3_batch` needs."""
+    return int(_lib.load().odil_lbfgs_batch_partials(c_int64(n), c_int(max_count), 8 if dtype == torch.float64 else 4))
+
+
+def _partials_args(partials, nb):
+    assert partials.dtype == torch.float64 and partials.dim() == 2 and partials.shape[0] == nb and partials.stride(1) == 1
+    if not partials.is_cuda:
+        raise _lib.OdilHipError("the partials workspace is on '{}': the HIP kernels need device memory".format(partials.device))
+    stride = max(partials.stride(0), partials.shape[1])
+    return c_void_p(partials.data_ptr()), c_int64(stride), c_int64((nb - 1) * stride + partials.shape[1])
+
+
+def lbfgs_probe_batch(g, d, out, partials, members=None):
+    """out[b, :3] = `lbfgs_probe(g[b], d[b])` for the listed members of [B, n] vectors, bit for bit: one launch + one
+    reduction launch.  out: [B, >= 3] with contiguous rows; partials: [B, >= lbfgs_batch_partials(n, 1)] float64."""
+    nb, n = int(g.shape[0]), int(g.shape[1])
+    assert g.dtype == d.dtype == out.dtype and out.dim() == 2 and out.shape[0] == nb and out.shape[1] >= 3 and out.stride(1) == 1
+    (gp, gs), (dp, ds) = _rows(g, nb, n), _rows(d, nb, n)
+    mp, nsel = _member_list(members, nb)
+    call("lbfgs_probe_batch", g.dtype, gp, gs, dp, ds, c_int64(n), c_int(nb), mp, nsel, *_partials_args(partials, nb),
+         c_void_p(out.data_ptr()), c_int64(out.stride(0) if nb > 1 else max(out.stride(0), 3)), stream_ptr())
+    return out
+
+
+def lbfgs_dots3_batch(w, counts, max_count, bs, out, partials, members=None):
+    """out[b, j, k] = <w[b, k], bs[j][b]> for k < counts[b] (counts: DEVICE int32 [B], None: max_count for all) and up to
+    three [B, n] vectors bs: `dots3(w[b, :counts[b]], [bs[j][b]])` for the listed members, bit for bit.  out: [B, 3, ldo]
+    with ldo >= max_count; entries k >= counts[b] are left alone.  w: [B, rows, n], or [B, n] (one vector per member)."""
+    if w.dim() == 2:
+        w = w[:, None, :]
+    nb, n = int(w.shape[0]), int(w.shape[2])
+    wp, ws, lda, rows = _history(w, nb, n)
+    if rows == 1:
+        lda = c_int64(n)  # (what `dots3(d[None], ...)` of one member passes)
+    bs = list(bs) + [None] * (3 - len(bs))
+    b = [_rows(t, nb, n) if t is not None else (None, c_int64(0)) for t in bs]
+    assert out.dtype == w.dtype and out.dim() == 3 and out.shape[0] == nb and out.shape[1] == 3 and out.stride(2) == 1
+    assert out.shape[2] >= max_count and (out.stride(1) >= out.shape[2] or out.shape[2] == 1)
+    mp, nsel = _member_list(members, nb)
+    ldo = out.stride(1)
+    call("lbfgs_dots3_batch", w.dtype, wp, ws, lda, c_int(rows), _per_member(counts, nb, torch.int32), c_int(max_count),
+         b[0][0], b[0][1], b[1][0], b[1][1], b[2][0], b[2][1], c_int64(n), c_int(nb), mp, nsel,
+         *_partials_args(partials, nb), c_void_p(out.data_ptr()),
+         c_int64(out.stride(0) if nb > 1 else max(out.stride(0), 2 * ldo + max_count)), c_int64(ldo), stream_ptr())
+    return out
+
+
+def lbfgs_lincomb_batch(y, beta, w, counts, max_count, coef, members=None):
+    """y[b] = beta y[b] + sum_{k < counts[b]} coef[b, k] w[b, k] for the listed members: `lincomb` per member, bit for bit."""
+    nb, n = int(y.shape[0]), int(y.shape[1])
+    wp, ws, lda, rows = _history(w, nb, n)
+    (yp, ys), (cp, cs) = _rows(y, nb, n), _rows(coef, nb, int(coef.shape[1]))
+    assert coef.dtype == y.dtype == w.dtype and coef.shape[1] >= max_count
+    mp, nsel = _member_list(members, nb)
+    call("lbfgs_lincomb_batch", y.dtype, yp, ys, float(beta), wp, ws, lda, c_int(rows), _per_member(counts, nb, torch.int32),
+         c_int(max_count), cp, cs, c_int64(n), c_int(nb), mp, nsel, stream_ptr())
+    return y
+
+
+def lbfgs_axpy_batch(out, y, x, alpha, members=None):
+    """out[b] = y[b] + alpha[b] x[b] (`axpy`; out may be y) for the listed members; y = None: out[b] = alpha[b] x[b]
+    (`scale`); y = alpha = None: out[b] = x[b].  alpha: DEVICE [B]."""
+    nb, n = int(x.shape[0]), int(x.shape[1])
+    assert out.dtype == x.dtype and (y is None or y.dtype == x.dtype)
+    (op, os_), (xp, xs) = _rows(out, nb, n), _rows(x, nb, n)
+    yp, ys = _rows(y, nb, n) if y is not None else (None, c_int64(0))
+    mp, nsel = _member_list(members, nb)
+    call("lbfgs_axpy_batch", x.dtype, op, os_, yp, ys, xp, xs, _per_member(alpha, nb, x.dtype), c_int64(n), c_int(nb), mp,
+         nsel, stream_ptr())
+    return out
+
+
+def lbfgs_pair_batch(g, r, d, w, stp, slot, members=None):
+    """The correction pair of the listed members in one launch: r[b] = g[b] - r[b], d[b] = stp[b] d[b] and, where
+    slot[b] >= 0, w[b, 2 slot[b]] = d[b], w[b, 2 slot[b] + 1] = r[b].  stp: DEVICE [B]; slot: DEVICE int32 [B]."""
+    nb, n = int(g.shape[0]), int(g.shape[1])
+    assert g.dtype == r.dtype == d.dtype == w.dtype
+    wp, ws, lda, rows = _history(w, nb, n)
+    (gp, gs), (rp, rs), (dp, ds) = _rows(g, nb, n), _rows(r, nb, n), _rows(d, nb, n)
+    mp, nsel = _member_list(members, nb)
+    call("lbfgs_pair_batch", g.dtype, gp, gs, rp, rs, dp, ds, wp, ws, lda, c_int(rows), _per_member(stp, nb, g.dtype),
+         _per_member(slot, nb, torch.int32), c_int64(n), c_int(nb), mp, nsel, stream_ptr())
+
+
+def poisson_adjoint_batch(fu, h2, scale, out):
+    """out[b] = `poisson_adjoint(fu[b])` for the B members of [B, *shape] arrays (1-D to 3-D) in ONE launch, no update."""
+    nb, shape = int(fu.shape[0]), tuple(fu.shape[1:])
+    (fp, fs), (gp, gs) = _members(fu, nb, shape), _members(out, nb, shape)
+    h2a, h2p = host_reals(h2, fu.dtype)
+    call("poisson_adjoint_batch", fu.dtype, fp, gp, c_int(nb), fs, gs, i64(shape), c_int(len(shape)), h2p, float(scale),
+         stream_ptr())
+    return out
+
+
 def stencil_apply(coeffs, shifts, x, transpose=False, out=None):
     """y = M x or M^T x for the stencil matrix with per-shift coefficient arrays
     (reference core.py:1144-1171)."""

@@ -16,6 +16,7 @@
 
 import math
 import os
+import time
 from argparse import Namespace
 
 import numpy as np
@@ -663,7 +664,29 @@ class LbfgsVectors:
 
 def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0, maxfun=math.inf, callback=None,
                     history=None):
-    """L-BFGS-B 3.0 without bounds.  `x`: flat vector (updated in place); `fg(x) -> (f, g)`
+    """`lbfgsb_member` run to its end for ONE problem: every read it asks for is answered at once by `vec` (the
+    documentation of the algorithm and of the arguments is there).  Returns dict(task, warnflag, nit, funcalls, f)."""
+    member = lbfgsb_member(x, fg, vec, maxiter, m=m, maxls=maxls, pgtol=pgtol, factr=factr, maxfun=maxfun,
+                           callback=callback, history=history)
+    try:
+        ask = next(member)
+        while True:
+            ask = member.send(vec.read_probes() if ask[0] == "probes" else vec.history_products(*ask[1:]))
+    except StopIteration as stop:
+        return stop.value
+
+
+def lbfgsb_member(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0, maxfun=math.inf, callback=None,
+                  history=None):
+    """The scalar logic of L-BFGS-B as a coroutine of ONE problem (a generator): it enqueues vector work on `vec` and
+    yields where it needs device results on the host -- ("probes",), answered with what `vec.read_probes()` returns, and
+    ("products", nphys, bs), answered with `vec.history_products(nphys, bs)`; its return value is the result dict.
+    `lbfgsb_minimize` answers at once (one problem); `LbfgsbOptimizer.run_ensemble` advances one coroutine per member in
+    lock-step and answers all members from one device-to-host copy per kind of read (their `vec` queues the work, which
+    then runs as batched launches).  One text of dcsrch / dcstep, matupd, the two triangular solves and the skip and
+    restart rules for both.
+
+    L-BFGS-B 3.0 without bounds.  `x`: flat vector (updated in place); `fg(x) -> (f, g)`
     with g written/returned as a flat vector (f may stay on the device: it reaches the host through
     `vec.read_probes`); `vec`: vector backend.  Returns dict(task, warnflag, nit, funcalls, f).
 
@@ -720,7 +743,7 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
             ss[:-1, :-1] = ss[1:, 1:]
             yy[:-1, :-1] = yy[1:, 1:]
         vec.store_pair(slot, s, y)
-        (s_y, s_s, s_g), (y_y, y_s, y_g) = vec.history_products(len(slots), [y, s, g])
+        (s_y, s_s, s_g), (y_y, y_s, y_g) = yield ("products", len(slots), [y, s, g])
         pending = (y_g, s_g)
         rr = float(y_y[slot])  # y_new . y_new is one of the products of that pass: no separate reduction
         theta = rr / dr
@@ -739,7 +762,7 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
     vec.copy(g, gnew)
     nfev += 1
     vec.probe_eval(fobj, g, g)
-    _, _, _, sbgnrm, f = vec.read_probes()
+    _, _, _, sbgnrm, f = yield ("probes",)
     if sbgnrm <= pgtol:
         return dict(task="CONVERGENCE: NORM_OF_PROJECTED_GRADIENT_<=_PGTOL", warnflag=0, nit=0, funcalls=nfev, f=f)
     first = True  # the very first line search of a cold start scales its trial step by 1 / |d|
@@ -749,7 +772,7 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
         if s_y <= epsmch * (-float(gs_old)):
             nskip += 1
             continue
-        push_pair(s_old, y_old, s_y, None)
+        yield from push_pair(s_old, y_old, s_y, None)
 
     while True:
         # ---- search direction d = -B^{-1} g (compact representation) --------------------
@@ -759,7 +782,7 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
             if pending is not None:
                 p1, p2 = pending  # Y^T g, S^T g came out of the pass that formed the update rows
             else:
-                sg_, yg_ = vec.history_products(len(slots), [g])
+                sg_, yg_ = yield ("products", len(slots), [g])
                 p1, p2 = yg_[0], sg_[0]
             pending = None
             yg = np.asarray(p1)[order]
@@ -786,13 +809,13 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
         launched = False
         if first:
             first = False
-            dtd, gd = vec.read_probes()[:2]
+            dtd, gd = (yield ("probes",))[:2]
             stp = min(1.0 / math.sqrt(dtd), stpmx)
         else:
             stp = 1.0
             evaluate(stp)  # before <g_old, d> is on the host
             launched = True
-            dtd, gd, gd_new, gmax_new, f_new = vec.read_probes()
+            dtd, gd, gd_new, gmax_new, f_new = yield ("probes",)
         gdold = gd
         ls_failed = False
         if gd >= 0.0:
@@ -810,7 +833,7 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
                     break
                 if not launched:
                     evaluate(stp)
-                    _, _, gd_new, gmax_new, f_new = vec.read_probes()
+                    _, _, gd_new, gmax_new, f_new = yield ("probes",)
                 launched = False
                 f, gd, sbgnrm = f_new, gd_new, gmax_new
                 stp, task = search.step(stp, f, gd)
@@ -857,7 +880,250 @@ def lbfgsb_minimize(x, fg, vec, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0,
             nskip += 1
             pending = None
             continue
-        push_pair(d, r, dr, stp * stp * dtd if stp != 1.0 else dtd)
+        yield from push_pair(d, r, dr, stp * stp * dtd if stp != 1.0 else dtd)
+
+
+# --------------------------------------------------------------------------------------
+# L-BFGS-B on B problems in lock-step: one `lbfgsb_member` coroutine per member, whose vector work is queued and run
+# as launches that cover all members that ask for the same thing.
+# --------------------------------------------------------------------------------------
+# The kinds of queued work in the order ONE member can ask for them between two reads: a member's queue is always
+# ascending in this order, so running the kinds in this order, each for all members that queued it, keeps every
+# member's own order.  Vectors are named: x, t (x at the start of the line search), r (g there, later y), d, g, and e
+# (the gradient the last evaluation left).
+_QUEUE_ORDER = [("copy", "x", "t"), ("copy", "g", "r"), ("pair",), ("scale",), ("lincomb",), ("probe_direction",),
+                ("copy", "t", "x"), ("copy", "r", "g"), ("set_x",), ("eval",), ("copy", "g", "e"), ("probe_eval",)]
+
+
+class _MemberQueue:
+    """The `vec` (and `fg`) of one member's coroutine in an ensemble: the interface of `LbfgsVectors` on NAMED vectors,
+    every call filed as [kind, scalars...] for `lbfgsb_minimize_ensemble` to run for many members at once.  The calls that
+    form a correction pair -- y = g - r, s = stp d, the store into the history -- are filed as ONE piece of work."""
+
+    def __init__(self):
+        self.ops, self.names = [], iter("trdg")
+
+    def new(self):
+        return next(self.names)
+
+    def fg(self, x):
+        self.ops.append([("eval",)])
+        return None, "e"
+
+    def copy(self, dst, src):
+        self.ops.append([("copy", dst, src)])
+
+    def set_axpy(self, out, t, d, a):
+        assert (out, t, d) == ("x", "t", "d")
+        self.ops.append([("set_x",), float(a)])
+
+    def scale_into(self, dst, src, a):
+        if (dst, src) == ("d", "d"):  # s = stp d of the pair whose y was just formed
+            assert self.ops[-1][0] == ("pair",)
+            self.ops[-1][1] = float(a)
+        else:
+            assert (dst, src) == ("d", "g")
+            self.ops.append([("scale",), float(a)])
+
+    def sub_into(self, dst, a, b):
+        assert (dst, a, b) == ("r", "g", "r")
+        self.ops.append([("pair",), 1.0, -1])  # (step 1, not stored: until scale_into / store_pair say otherwise)
+
+    def store_pair(self, slot, s, y):
+        assert (s, y) == ("d", "r") and self.ops[-1][0] == ("pair",)
+        self.ops[-1][2] = int(slot)
+
+    def probe_direction(self, d, g):
+        self.ops.append([("probe_direction",)])
+
+    def probe_eval(self, f, g, d):
+        assert g == "g" and d in ("d", "g")
+        self.ops.append([("probe_eval", d)])
+
+    def history_lincomb(self, y, nphys, cs, cy):
+        if nphys:
+            c = np.zeros(2 * nphys)
+            c[0::2], c[1::2] = cs, cy
+            self.ops.append([("lincomb",), int(nphys), c])
+
+    def dot(self, a, b):
+        raise NotImplementedError("an ensemble has no warm start of the memory")
+
+    def take(self):
+        ops, self.ops = self.ops, []
+        ranks = [_QUEUE_ORDER.index(op[0] if op[0][0] == "copy" else op[0][:1]) for op in ops]
+        assert ranks == sorted(ranks), [op[0] for op in ops]
+        return list(zip(ranks, ops))
+
+
+def lbfgsb_minimize_ensemble(backend, nbatch, maxiter, m=50, maxls=50, pgtol=1e-16, factr=0.0, maxfun=math.inf,
+                             callback=None):
+    """`lbfgsb_minimize` for `nbatch` problems in lock-step, every member through its own `lbfgsb_member`: all members
+    advance to their next read, the vector work they queued runs as `backend.run(plan)` -- plan: [(kind, members, the
+    members' scalars)] in `_QUEUE_ORDER` -- and ONE `backend.read_probes()` ([B, 8] host table, the layout of
+    `LbfgsVectors.scal`) or `backend.read_products()` ([B, 3, 2 m]) answers all of them.  A round is one evaluation of the
+    ensemble; it costs a read of the probes and, when a member accepted a step, a read of its history products.  Members
+    in the middle of a line search evaluate again while others form their pair and direction; a member that has returned
+    is evaluated along but never touched.  callback(member): at every new iterate of that member, when the member's x is
+    its accepted iterate and the last evaluation is the evaluation there.
+    Returns ([result dict per member], Namespace(rounds, host_reads))."""
+    queues = [_MemberQueue() for _ in range(nbatch)]
+    hook = (lambda b: (lambda x: callback(b))) if callback is not None else (lambda b: None)
+    members = [lbfgsb_member("x", q.fg, q, maxiter, m=m, maxls=maxls, pgtol=pgtol, factr=factr, maxfun=maxfun,
+                             callback=hook(b)) for b, q in enumerate(queues)]
+    asks, results = [None] * nbatch, [None] * nbatch
+
+    def advance(b, answer):
+        try:
+            asks[b] = members[b].send(answer)
+        except StopIteration as stop:
+            asks[b], results[b] = None, stop.value
+
+    def plan(who, products=False):
+        """The queued work of the members `who` (and what members that have returned left behind), kind by kind."""
+        groups = dict()
+        for b in range(nbatch):
+            if b in who or asks[b] is None:
+                for rank, op in queues[b].take():
+                    groups.setdefault((rank, op[0]), []).append((b, op[1:]))
+        if products:
+            for b in sorted(who):
+                groups.setdefault((len(_QUEUE_ORDER), ("products",) + tuple(asks[b][2])), []).append((b, [asks[b][1]]))
+        return [(key, [b for b, _ in group], [scalars for _, scalars in group]) for (rank, key), group in sorted(groups.items())]
+
+    for b in range(nbatch):
+        advance(b, None)
+    info = Namespace(rounds=0, host_reads=0)
+    while any(ask is not None for ask in asks):
+        waiting = {b for b, ask in enumerate(asks) if ask is not None and ask[0] == "products"}
+        if waiting:
+            backend.run(plan(waiting, products=True))
+            out = backend.read_products()
+            info.host_reads += 1
+            for b in sorted(waiting):
+                nphys, bs = asks[b][1:]
+                o = np.array(out[b, :len(bs), :2 * nphys])
+                advance(b, (o[:, 0::2], o[:, 1::2]))
+            continue
+        live = {b for b, ask in enumerate(asks) if ask is not None}  # (all of them wait for the probes)
+        work = plan(live)
+        backend.run(work)
+        h = backend.read_probes()
+        info.host_reads += 1
+        info.rounds += any(key == ("eval",) for key, _, _ in work)
+        for b in sorted(live):
+            advance(b, (float(h[b, 0]), float(h[b, 1]), float(h[b, 3]), float(h[b, 5]), float(h[b, 6])))
+    backend.run(plan(set()))  # (a member that gave up put its last accepted iterate back: x = t)
+    return results, info
+
+
+class EnsembleLbfgsVectors:
+    """The backend of `lbfgsb_minimize_ensemble` on HIP kernels: member-major float64 vectors x, t, r, d, g, e [B, n], the
+    history w [B, 2 m, n] (row 2 k = s_k, row 2 k + 1 = y_k), the table of probes scal [B, 8] in the layout of
+    `LbfgsVectors.scal` and the history products prod [B, 3, 2 m].  Every kind of queued work is one launch (two for a
+    reduction) over the list of members that queued it (`ops.lbfgs_*_batch`); member b gets the bits `LbfgsVectors` gives
+    it alone.  The members' scalars, counts and lists of one `run` travel in ONE pinned staging buffer per type, uploaded
+    before its first launch (the buffers are rewritten only after the read that follows every `run`, which waits for the
+    upload).  evaluate(x, e): the evaluation of ALL members at x [B, n], gradients into e, returns the [B] losses."""
+
+    def __init__(self, nbatch, n, m, device, evaluate):
+        self.nb, self.n, self.m, self.device, self.evaluate = nbatch, n, m, device, evaluate
+        f64 = dict(dtype=torch.float64, device=device)
+        self.v = {name: torch.zeros((nbatch, n), **f64) for name in "xtrdge"}
+        self.w = torch.zeros((nbatch, 2 * m, n), **f64)
+        self.scal = torch.zeros((nbatch, 8), **f64)
+        self.prod = torch.zeros((nbatch, 3, 2 * m), **f64)
+        self.coef = torch.zeros((nbatch, 2 * m), **f64)
+        self.partials = torch.empty((nbatch, ops.lbfgs_batch_partials(n, 2 * m, torch.float64)), **f64)
+        self.reals = torch.zeros((4, nbatch), **f64)  # rows of per-member scalars: one per kind of work that has one
+        self.ints = torch.zeros((32, nbatch), dtype=torch.int32, device=device)  # counts, slots and member lists
+        self.reals_host, self.ints_host, self.coef_host = (torch.zeros(t.shape, dtype=t.dtype).pin_memory()
+                                                           for t in (self.reals, self.ints, self.coef))
+        self.scal_host, self.prod_host = torch.zeros(self.scal.shape, dtype=torch.float64).pin_memory(), torch.zeros(
+            self.prod.shape, dtype=torch.float64).pin_memory()
+        self.read_seconds = 0.0  # host time spent in the two reads
+
+    def run(self, plan):
+        nb, v = self.nb, self.v
+        reals, ints, coef = self.reals_host.numpy(), self.ints_host.numpy(), self.coef_host.numpy()
+        nreal, nint, launches = 0, 0, []
+        used = dict(coef=False)
+
+        def real_row(who, values):
+            nonlocal nreal
+            reals[nreal, who] = values
+            nreal += 1
+            return self.reals[nreal - 1]
+
+        def int_row(who, values):
+            nonlocal nint
+            ints[nint, who] = values
+            nint += 1
+            return self.ints[nint - 1]
+
+        def listed(who):
+            nonlocal nint
+            if len(who) == nb:
+                return None
+            ints[nint, :len(who)] = who
+            nint += 1
+            return self.ints[nint - 1, :len(who)]
+
+        for key, who, scalars in plan:
+            kind, sel = key[0], listed(who)
+            if kind == "copy":
+                launches.append((ops.lbfgs_axpy_batch, (v[key[1]], None, v[key[2]], None, sel)))
+            elif kind == "pair":
+                launches.append((ops.lbfgs_pair_batch, (v["g"], v["r"], v["d"], self.w, real_row(who, [s[0] for s in scalars]),
+                                                        int_row(who, [s[1] for s in scalars]), sel)))
+            elif kind == "scale":
+                launches.append((ops.lbfgs_axpy_batch, (v["d"], None, v["g"], real_row(who, [s[0] for s in scalars]), sel)))
+            elif kind == "lincomb":
+                for b, (nphys, c) in zip(who, scalars):
+                    coef[b, :2 * nphys] = c
+                used["coef"] = True
+                counts = int_row(who, [2 * s[0] for s in scalars])
+                launches.append((ops.lbfgs_lincomb_batch, (v["d"], 1.0, self.w, counts, 2 * max(s[0] for s in scalars), self.coef, sel)))
+            elif kind == "probe_direction":  # <d, d>, <g, d> into columns 0, 1 (column 2: the zero of a missing third vector)
+                launches.append((ops.lbfgs_dots3_batch, (v["d"], None, 1, [v["d"], v["g"]], self.scal[:, :3].unsqueeze(2),
+                                                         self.partials, sel)))
+            elif kind == "set_x":
+                launches.append((ops.lbfgs_axpy_batch, (v["x"], v["t"], v["d"], real_row(who, [s[0] for s in scalars]), sel)))
+            elif kind == "eval":
+                launches.append((self._evaluate, ()))
+            elif kind == "probe_eval":
+                launches.append((ops.lbfgs_probe_batch, (v["g"], v[key[1]], self.scal[:, 3:], self.partials, sel)))
+            elif kind == "products":
+                counts = int_row(who, [2 * s[0] for s in scalars])
+                launches.append((ops.lbfgs_dots3_batch, (self.w, counts, 2 * max(s[0] for s in scalars), [v[name] for name in key[1:]],
+                                                         self.prod, self.partials, sel)))
+            else:
+                raise AssertionError(key)
+        if nreal:
+            self.reals[:nreal].copy_(self.reals_host[:nreal], non_blocking=True)
+        if nint:
+            self.ints[:nint].copy_(self.ints_host[:nint], non_blocking=True)
+        if used["coef"]:
+            self.coef.copy_(self.coef_host, non_blocking=True)
+        for launch, args in launches:
+            launch(*args)
+
+    def _evaluate(self):
+        loss = self.evaluate(self.v["x"], self.v["e"])
+        self.scal[:, 6].copy_(loss)
+
+    def _read(self, host, device):
+        start = time.perf_counter()
+        host.copy_(device, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        self.read_seconds += time.perf_counter() - start  # (the host blocked: what is left of the round's device time)
+        return host.numpy()
+
+    def read_probes(self):
+        return self._read(self.scal_host, self.scal)
+
+    def read_products(self):
+        return self._read(self.prod_host, self.prod)
 
 
 class LbfgsbOptimizer(Optimizer):
@@ -973,6 +1239,76 @@ class LbfgsbOptimizer(Optimizer):
                 optinfo,
             )
         return xviews, optinfo
+
+    max_ensemble_m = 64  # 2 m history vectors <= 128: the products of every member's history take one kernel whatever its count
+
+    def ensemble_refusal(self, nbatch, n, device):
+        """Why `run_ensemble` does not run `nbatch` members of `n` unknowns on `device`, or None: a memory beyond
+        `max_ensemble_m` pairs (`ops.dots3` picks its kernel from the number of stored vectors above 128: the members'
+        single runs would each follow their own count), or a history that does not fit the free device memory."""
+        if self.m > self.max_ensemble_m:
+            return "bfgs_m = {} (an ensemble runs at most {}: beyond, the kernel that forms a member's history products " \
+                   "would depend on that member's own count)".format(self.m, self.max_ensemble_m)
+        need = nbatch * 2 * self.m * n * 8
+        if torch.device(device).type == "cuda":
+            free = torch.cuda.mem_get_info(device)[0]
+            if need > free:
+                return "the history of {} members x 2 x {} vectors x {} unknowns takes {} bytes, {} bytes of device memory " \
+                       "are free".format(nbatch, self.m, n, need, free)
+        return None
+
+    def run_ensemble(self, ensemble, epochs, callback=None, epoch_start=0, **kwargs):
+        """`run` for every member of a `fused.BatchedLaunches` at once, in lock-step (`lbfgsb_minimize_ensemble` on
+        `EnsembleLbfgsVectors`): a round is ONE evaluation of all members (`ensemble.loss_grad()`, between a copy per level
+        from the packed float64 x into the ensemble's level arrays and one per level back from its gradients), the batched
+        vector launches and at most two host reads -- what one iteration of a single run costs, whatever B is.  The
+        L-BFGS vectors are float64, the evaluation buffers have the ensemble's dtype, as in `run`.  Eager: no graph.
+        No exception for a member that stops early: optinfo.tasks / .warnflags / .nits / .evals say how each member ended
+        (what `run` reports in optinfo, or in the optinfo of its EarlyStopError).
+        callback(member, epoch): after the member's own iteration epoch - epoch_start, at the epochs the callback's
+        `next_active` names (without the attribute: every iteration); the level arrays of `ensemble.x` and the last
+        evaluation (`ensemble.loss`, the traced `report`) then show that member's accepted iterate."""
+        nb, n = ensemble.nbatch, ensemble.total
+        reason = self.ensemble_refusal(nb, n, ensemble.device)
+        if reason is not None:
+            raise ValueError("L-BFGS-B ensemble: " + reason)
+        offsets = np.cumsum([0] + list(ensemble.sizes))
+        pieces = lambda packed: [packed[:, a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+
+        def evaluate(x, e):
+            for level, piece in zip(ensemble.x, pieces(x)):
+                level.view(nb, -1).copy_(piece)  # (cast to the evaluation dtype)
+            ensemble.loss_grad()
+            for level, piece in zip(ensemble.g, pieces(e)):
+                piece.copy_(level.view(nb, -1))
+            self.evals += 1
+            return ensemble.loss
+
+        vec = EnsembleLbfgsVectors(nb, n, self.m, ensemble.device, evaluate)
+        for level, piece in zip(ensemble.x, pieces(vec.v["x"])):
+            piece.copy_(level.view(nb, -1))
+        next_active = getattr(callback, "next_active", None) if callback is not None else None
+        nits = [0] * nb
+        due = [next_active(epoch_start) if next_active is not None else epoch_start + 1 for _ in range(nb)]
+
+        def iterate(b):
+            nits[b] += 1
+            epoch = epoch_start + nits[b]
+            if callback is not None and epoch >= due[b]:
+                callback(b, epoch)
+                due[b] = next_active(epoch) if next_active is not None else epoch + 1
+
+        results, info = lbfgsb_minimize_ensemble(vec, nb, epochs, m=self.m, maxls=self.maxls, pgtol=self.pgtol,
+                                                 factr=self.factr, callback=iterate)
+        for level, piece in zip(ensemble.x, pieces(vec.v["x"])):  # (every member's last accepted iterate)
+            level.view(nb, -1).copy_(piece)
+        optinfo = Namespace(epochs=epochs, rounds=info.rounds, host_reads=info.host_reads, ensemble=ensemble,
+                            read_seconds=vec.read_seconds)
+        optinfo.tasks = [res["task"] for res in results]
+        optinfo.warnflags = np.array([res["warnflag"] for res in results])
+        optinfo.nits = np.array([res["nit"] for res in results])
+        optinfo.evals = np.array([res["funcalls"] for res in results])
+        return [ensemble.levels(ensemble.x, k) for k in range(nb)], optinfo
 
 
 def make_optimizer(name, dtype=None, mod=None, **kwargs):
