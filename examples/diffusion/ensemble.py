@@ -9,6 +9,8 @@ is printed from device events around it.  The time per step is printed beside th
 `optimize_newton` runs, one after the other (`--single 0` skips those).  `--form launches` runs members that are too large
 for one workgroup (256^2, 64^3, 128^3): the levels above 32768 cells as launches that cover all members, the convergence
 decision on the device (`gmg.EnsembleLaunchGMG`); `--form auto` takes it only where `--form workgroup` refuses.
+`--pair_min_cells N` sets from how many cells of all members together a launch level smooths twice per pass
+(`odil_stencil_var_smooth2_batch`; 0: always, -1: never).
 
 `--optimizer adam` runs the same sweep with Adam (`odil.util.optimize_ensemble(form="auto")`, its route for traced stencil
 operators: every launch of an epoch covers all members; `--multigrid 1` for a multigrid-decomposed unknown) and prints the
@@ -65,6 +67,9 @@ def parse_args(argv=None):
                      help="Linearise all members in one generated launch, or member by member")
     own.add_argument("--form", type=str, default="workgroup", choices=("workgroup", "launches", "auto"),
                      help="One workgroup per member, batched launches for members beyond one workgroup, or whichever serves")
+    own.add_argument("--pair_min_cells", type=int, default=None,
+                     help="--form launches: levels on which all members together have at least N cells smooth twice per pass "
+                          "(gmg.EnsembleLaunchGMG.pair_min_cells; 0: always, -1: never; default: the class's)")
     own.add_argument("--repeat", type=int, default=3, help="--optimizer adam: timed repetitions of the ensemble and the single runs")
     mine, rest = own.parse_known_args(argv)
     args = diffusion.parse_args(["--ndim", "2", "--N", "16", "--epochs", "2"] + rest)
@@ -248,6 +253,10 @@ def main():
         return main_adam(args, callback)
     if args.optimizer == "lbfgsb":
         return main_lbfgsb(args, callback)
+    if args.pair_min_cells is not None:  # (for this run: the driver builds its solver from the class)
+        from odil_amd import gmg
+
+        gmg.EnsembleLaunchGMG.pair_min_cells = float("inf") if args.pair_min_cells < 0 else args.pair_min_cells
     problems, states = make_members(args)
     guess = [problem.domain.arrays_from_state(state)[0].clone() for problem, state in zip(problems, states)]
 

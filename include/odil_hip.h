@@ -777,6 +777,23 @@ int odil_stencil_var_smooth2_f64(const double* coeffs, const double* x, const do
                                  int ndim, double omega1, double omega2, int zc_hint, void* stream);
 int odil_stencil_var_smooth2_f32(const float* coeffs, const float* x, const float* b, float* out, const int64_t* shape,
                                  int ndim, float omega1, float omega2, int zc_hint, void* stream);
+/* odil_stencil_var_smooth2 for every member of an ensemble in ONE launch (the member on blockIdx.y, the device code and
+ * the bits of the single entry point per member).  Arrays and strides (in elements) as in odil_stencil_var_smooth_batch:
+ * member m's coefficient arrays at coeffs + m coeff_stride, its vectors at x + m x_stride, b + m b_stride, out +
+ * m out_stride.  x == NULL: every member starts from the zero vector (x is not read, x_stride is ignored).  active: NULL,
+ * or int[nbatch]: a member with active[m] == 0 is skipped whole (no load, no store).  The unit schedule is that of one
+ * member; with zc_hint <= 0 the chunk length counts the workgroups of all members (where a chunk is cut does not enter
+ * the arithmetic).  Refused before anything is launched: what odil_stencil_var_smooth2 refuses, nbatch outside
+ * 1 ... 65535, more than 2^24 cells per member, null coeffs / b / out, x == out, a stride smaller than a member, an odd
+ * stride (a lane loads packs of two cells: every member begins on a pack boundary). */
+int odil_stencil_var_smooth2_batch_f64(const double* coeffs, int64_t coeff_stride, const double* x, int64_t x_stride,
+                                       const double* b, int64_t b_stride, double* out, int64_t out_stride,
+                                       const int64_t* shape, int ndim, int nbatch, double omega1, double omega2, int zc_hint,
+                                       const int* active, void* stream);
+int odil_stencil_var_smooth2_batch_f32(const float* coeffs, int64_t coeff_stride, const float* x, int64_t x_stride,
+                                       const float* b, int64_t b_stride, float* out, int64_t out_stride,
+                                       const int64_t* shape, int ndim, int nbatch, float omega1, float omega2, int zc_hint,
+                                       const int* active, void* stream);
 
 /* The COARSE TAIL of a multigrid V-cycle in one launch: one workgroup walks `nlev` <= 8 small levels (pre-smoothing,
  * residual + restriction, dense solve on the coarsest, prolongation + post-smoothing) with a workgroup barrier where a

@@ -396,12 +396,11 @@ __global__ __launch_bounds__(HASY ? 64 * kS2Waves : 64) void k_poisson_jacobi2(c
 // along x, LDS along y, registers along z); every window carries a halo pack per side, whose addresses wrap
 // periodically like every index of this operator (wall rows carry zero coefficients instead).
 // ZERO: the sweeps start from the zero vector -- x is not read (the ring holds zeros: the same products, the same bits).
-template <typename T, int V, bool HASY, int DC, bool ZERO = false>
-__global__ __launch_bounds__(HASY ? 64 * kS2Waves : 64) void k_svar_smooth2(const T* __restrict__ c,
-                                                                            const T* __restrict__ x,
-                                                                            const T* __restrict__ rhs,
-                                                                            T* __restrict__ xout, Smooth2Args a,
-                                                                            T omega1, T omega2) {
+// The whole march of one workgroup on ONE operator: the body of the single kernel and, per member, of the batched one.
+template <typename T, int V, bool HASY, int DC, bool ZERO>
+__device__ __forceinline__ void svar_smooth2_unit(const T* __restrict__ c, const T* __restrict__ x,
+                                                  const T* __restrict__ rhs, T* __restrict__ xout, const Smooth2Args& a,
+                                                  T omega1, T omega2) {
   constexpr int NW = HASY ? kS2Waves : 1;
   constexpr int HY = HASY ? 2 : 0;
   constexpr int R = kS2Ring, D = 1;  // x runs one step ahead of its use, the coefficient set DC steps
@@ -567,10 +566,36 @@ __global__ __launch_bounds__(HASY ? 64 * kS2Waves : 64) void k_svar_smooth2(cons
   }
 }
 
+template <typename T, int V, bool HASY, int DC, bool ZERO = false>
+__global__ __launch_bounds__(HASY ? 64 * kS2Waves : 64) void k_svar_smooth2(const T* __restrict__ c,
+                                                                            const T* __restrict__ x,
+                                                                            const T* __restrict__ rhs,
+                                                                            T* __restrict__ xout, Smooth2Args a,
+                                                                            T omega1, T omega2) {
+  svar_smooth2_unit<T, V, HASY, DC, ZERO>(c, x, rhs, xout, a, omega1, omega2);
+}
+
+// The pair for every member of an ensemble (gmg.EnsembleLaunchGMG): member m = blockIdx.y runs the march above on its own
+// arrays -- the unit schedule and `a` are those of one member, shared by all.  `active` (NULL: all): the workgroups of a
+// member with active[m] == 0 leave before their first load, store or barrier (one uniform scalar read per workgroup), as
+// in k_svar_smooth_batch (stencil_mg.hip).  No workgroup reads what another one writes.
+template <typename T, int V, bool HASY, int DC, bool ZERO = false>
+__global__ __launch_bounds__(HASY ? 64 * kS2Waves : 64) void k_svar_smooth2_batch(const T* __restrict__ c, int64_t cstride,
+                                                                                  const T* __restrict__ x, int64_t xstride,
+                                                                                  const T* __restrict__ rhs, int64_t bstride,
+                                                                                  T* __restrict__ xout, int64_t ostride,
+                                                                                  Smooth2Args a, T omega1, T omega2,
+                                                                                  const int* __restrict__ active) {
+  const int64_t m = blockIdx.y;
+  if (active != nullptr && active[m] == 0) return;
+  svar_smooth2_unit<T, V, HASY, DC, ZERO>(c + m * cstride, ZERO ? nullptr : x + m * xstride, rhs + m * bstride,
+                                          xout + m * ostride, a, omega1, omega2);
+}
+
 // V: cells per lane; halo: packs of x-halo per side of a window that is not the whole row
 template <typename T>
 static int smooth2_args(Smooth2Args& a, const int64_t* shape, int ndim, const T* h2, T h[3], int zc_hint, int V,
-                        int halo, const char* what) {
+                        int halo, const char* what, int64_t members = 1) {
   if (ndim < 1 || ndim > 3 || !shape || !h2) {
     set_error("%s: ndim=%d out of range [1,3] or null shape/h2", what, ndim);
     return ODIL_E_INVAL;
@@ -612,8 +637,8 @@ static int smooth2_args(Smooth2Args& a, const int64_t* shape, int ndim, const T*
   }
   a.stream = a.n[0] * a.n[1] * a.n[2] * (int64_t)sizeof(T) > kStreamBytes;
   // chunks of planes: every chunk primes its window with two extra planes of the first sweep, so they are long --
-  // as long as the launch still has a few workgroups per CU
-  const int64_t per_plane = nyt * nxt;
+  // as long as the launch still has a few workgroups per CU (members: operators of this shape that share the launch)
+  const int64_t per_plane = nyt * nxt * members;
   int64_t zc = zc_hint > 0 ? zc_hint : 64;
   while (zc_hint <= 0 && zc > 8 && ((a.n[0] + zc - 1) / zc) * per_plane < 1024) zc /= 2;
   if (zc > a.n[0]) zc = a.n[0];
@@ -709,18 +734,14 @@ static int poisson_jacobi2_synth(const T* coarse, const T* x, const T* rhs, T* x
   return check_launch("k_poisson_jacobi2<synth>");
 }
 
+// What the single and the batched pair share: the window, the unit schedule and the coefficient slots of ONE operator
+// of `shape`.  members: operators that share the launch (the chunk-length rule counts the workgroups of all of them).
 template <typename T>
-static int svar_smooth2(const T* coeffs, const T* x, const T* b, T* out, const int64_t* shape, int ndim, T omega1, T omega2,
-                        int zc_hint, void* stream) {
+static int svar_smooth2_fill(Smooth2Args& a, const int64_t* shape, int ndim, int zc_hint, int64_t members, const char* what) {
   constexpr int V = 2;  // (two cells per lane in either precision: with four floats the coefficient set spills)
-  Smooth2Args a;
   T h[3];
   const T ones[3] = {T(1), T(1), T(1)};
-  if (int e = smooth2_args<T>(a, shape, ndim, ones, h, zc_hint, V, 1, "stencil_var_smooth2")) return e;
-  if (!coeffs || !b || !out || x == out) {  // (x == NULL: the sweeps start from the zero vector)
-    set_error("stencil_var_smooth2: null pointer or in-place sweeps");
-    return ODIL_E_INVAL;
-  }
+  if (int e = smooth2_args<T>(a, shape, ndim, ones, h, zc_hint, V, 1, what, members)) return e;
   // every window carries its halo pack (the indices of this operator wrap periodically: also a window that is the whole row)
   a.halo_x = 1;
   a.nxt = (a.packs + 61) / 62;
@@ -749,6 +770,19 @@ static int svar_smooth2(const T* coeffs, const T* x, const T* b, T* out, const i
     for (int d = 0; d < 3; ++d) a.slot[d] = 0;
     for (int i = 0; i < ndim; ++i) a.slot[map3[ndim - 1][i]] = 1 + 2 * i;
   }
+  return 0;
+}
+
+template <typename T>
+static int svar_smooth2(const T* coeffs, const T* x, const T* b, T* out, const int64_t* shape, int ndim, T omega1, T omega2,
+                        int zc_hint, void* stream) {
+  constexpr int V = 2;
+  Smooth2Args a;
+  if (int e = svar_smooth2_fill<T>(a, shape, ndim, zc_hint, 1, "stencil_var_smooth2")) return e;
+  if (!coeffs || !b || !out || x == out) {  // (x == NULL: the sweeps start from the zero vector)
+    set_error("stencil_var_smooth2: null pointer or in-place sweeps");
+    return ODIL_E_INVAL;
+  }
   const int grid = unit_grid(a.usched);
   if (a.active[1] && x)
     hipLaunchKernelGGL((k_svar_smooth2<T, V, true, S2_SVAR_DC>), dim3(grid), dim3(64 * kS2Waves), 0, (hipStream_t)stream,
@@ -763,6 +797,60 @@ static int svar_smooth2(const T* coeffs, const T* x, const T* b, T* out, const i
     hipLaunchKernelGGL((k_svar_smooth2<T, V, false, S2_SVAR_DC, true>), dim3(grid), dim3(64), 0, (hipStream_t)stream, coeffs,
                        x, b, out, a, omega1, omega2);
   return check_launch("k_svar_smooth2");
+}
+
+// a member's arrays must hold a member and begin on a pack boundary (a lane loads packs of two cells)
+static int svar_smooth2_stride(const char* what, const char* name, int64_t stride, int64_t need) {
+  if (stride < need) {
+    set_error("%s: %s_stride %lld is smaller than a member (%lld)", what, name, (long long)stride, (long long)need);
+    return ODIL_E_INVAL;
+  }
+  if (stride % 2) {
+    set_error("%s: %s_stride %lld is odd (every member begins on a pack of two cells)", what, name, (long long)stride);
+    return ODIL_E_INVAL;
+  }
+  return 0;
+}
+
+template <typename T>
+static int svar_smooth2_batch(const T* coeffs, int64_t coeff_stride, const T* x, int64_t x_stride, const T* b,
+                              int64_t b_stride, T* out, int64_t out_stride, const int64_t* shape, int ndim, int nbatch,
+                              T omega1, T omega2, int zc_hint, const int* active, void* stream) {
+  constexpr int V = 2;
+  const char* what = "stencil_var_smooth2_batch";
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("%s: %d members (1..65535: the member is a grid dimension)", what, nbatch);
+    return ODIL_E_INVAL;
+  }
+  Smooth2Args a;
+  if (int e = svar_smooth2_fill<T>(a, shape, ndim, zc_hint, nbatch, what)) return e;
+  if (a.size > (int64_t)1 << 24) {  // (the limit of the other batched launches: stencil_mg.hip, svar_batch_fill)
+    set_error("%s: too many cells per member", what);
+    return ODIL_E_INVAL;
+  }
+  if (!coeffs || !b || !out || x == out) {  // (x == NULL: the sweeps start from the zero vector)
+    set_error("%s: null pointer or in-place sweeps", what);
+    return ODIL_E_INVAL;
+  }
+  if (int e = svar_smooth2_stride(what, "coeff", coeff_stride, (2 * ndim + 1) * a.size)) return e;
+  if (x)
+    if (int e = svar_smooth2_stride(what, "x", x_stride, a.size)) return e;
+  if (int e = svar_smooth2_stride(what, "b", b_stride, a.size)) return e;
+  if (int e = svar_smooth2_stride(what, "out", out_stride, a.size)) return e;
+  const dim3 grid((unsigned)unit_grid(a.usched), (unsigned)nbatch);
+#define ODIL_SMOOTH2_BATCH(HASY, ZERO, THREADS)                                                                       \
+  hipLaunchKernelGGL((k_svar_smooth2_batch<T, V, HASY, S2_SVAR_DC, ZERO>), grid, dim3(THREADS), 0, (hipStream_t)stream, \
+                     coeffs, coeff_stride, x, x_stride, b, b_stride, out, out_stride, a, omega1, omega2, active)
+  if (a.active[1] && x)
+    ODIL_SMOOTH2_BATCH(true, false, 64 * kS2Waves);
+  else if (a.active[1])
+    ODIL_SMOOTH2_BATCH(true, true, 64 * kS2Waves);
+  else if (x)
+    ODIL_SMOOTH2_BATCH(false, false, 64);
+  else
+    ODIL_SMOOTH2_BATCH(false, true, 64);
+#undef ODIL_SMOOTH2_BATCH
+  return check_launch("k_svar_smooth2_batch");
 }
 
 }  // namespace odil
@@ -795,5 +883,19 @@ int odil_stencil_var_smooth2_f64(const double* coeffs, const double* x, const do
 int odil_stencil_var_smooth2_f32(const float* coeffs, const float* x, const float* b, float* out, const int64_t* shape,
                                  int ndim, float omega1, float omega2, int zc_hint, void* stream) {
   return svar_smooth2<float>(coeffs, x, b, out, shape, ndim, omega1, omega2, zc_hint, stream);
+}
+int odil_stencil_var_smooth2_batch_f64(const double* coeffs, int64_t coeff_stride, const double* x, int64_t x_stride,
+                                       const double* b, int64_t b_stride, double* out, int64_t out_stride,
+                                       const int64_t* shape, int ndim, int nbatch, double omega1, double omega2, int zc_hint,
+                                       const int* active, void* stream) {
+  return svar_smooth2_batch<double>(coeffs, coeff_stride, x, x_stride, b, b_stride, out, out_stride, shape, ndim, nbatch,
+                                    omega1, omega2, zc_hint, active, stream);
+}
+int odil_stencil_var_smooth2_batch_f32(const float* coeffs, int64_t coeff_stride, const float* x, int64_t x_stride,
+                                       const float* b, int64_t b_stride, float* out, int64_t out_stride,
+                                       const int64_t* shape, int ndim, int nbatch, float omega1, float omega2, int zc_hint,
+                                       const int* active, void* stream) {
+  return svar_smooth2_batch<float>(coeffs, coeff_stride, x, x_stride, b, b_stride, out, out_stride, shape, ndim, nbatch,
+                                   omega1, omega2, zc_hint, active, stream);
 }
 }  // extern "C"

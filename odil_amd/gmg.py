@@ -923,6 +923,19 @@ def mean_children(r, loc, out=None):
     return torch.mul(r, 1.0 / 2 ** loc.count("c"), out=out)
 
 
+def sweep_plan(weights, first_single=False):
+    """The launches of the sweeps with `weights`, in order: tuples of one weight (a single sweep) or two (the one-pass
+    pair) -- pairs from the front, a single sweep left over when the count is odd, e.g. [(w0, w1), (w2,)].
+    first_single: the first sweep stays a launch of its own (it carries the norm's partial sums), the rest is paired:
+    [(w0,), (w1, w2), (w3,)].  Host arithmetic only."""
+    weights = list(weights)
+    plan = [(weights.pop(0),)] if first_single and weights else []
+    while weights:
+        plan.append(tuple(weights[:2]))
+        weights = weights[2:]
+    return plan
+
+
 class EnsembleLaunchGMG(EnsembleGMG):
     """B systems of ONE shape that are too large for one workgroup each, solved side by side: the hierarchy of
     `EnsembleGMG.from_coeffs` (the same batched set-up, member 0's coarsening decisions, ValueError for a member that
@@ -936,7 +949,8 @@ class EnsembleLaunchGMG(EnsembleGMG):
     that merges some axes only: the residual, then `mean_children`), `interp_add` up, in 3-D two cycles on level 1.  A
     coarse correction on the tail's top level is odil_stencil_solve_batch with start 0, tol 0 and maxcycles 1 (2 where
     level 1 is the tail's top in 3-D).  A cycle of member b reads its iterate from x and only its LAST post-smoothing
-    sweep writes x; everything in between is scratch.
+    sweep writes x; everything in between is scratch.  On a launch level that `pair_eligible` admits the sweeps run two per
+    pass over the coefficient arrays (odil_stencil_var_smooth2_batch, `sweep_plan`), bit-identical to single sweeps.
 
     `solve` keeps the contract of `EnsembleGMG.solve` -- start codes, stop rules, `status`, `history`, `outcome` -- with
     the decision on the device: the first pre-smoothing sweep of cycle k leaves partial sums of (A x_k - b)^2, and
@@ -953,6 +967,7 @@ class EnsembleLaunchGMG(EnsembleGMG):
     tail_max_cells = EnsembleGMG.max_cells  # levels of at most this many cells go to the one-workgroup tail (never the finest)
     method_name = "gmg-vcycle (variable coefficients), batched launches"
     max_member_cells = 1 << 24  # (the member is a grid dimension of the batched launches: their limit per member)
+    pair_min_cells = 1 << 20  # launch levels on which ALL members together have at least this many cells smooth in pairs (odil_stencil_var_smooth2_batch); math.inf: single sweeps only.  Measured: the largest of 2^18 ... 2^23 that loses on no row of the table
 
     def __init__(self, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None):
         self._strength = None
@@ -1071,20 +1086,39 @@ class EnsembleLaunchGMG(EnsembleGMG):
         self._launch(self._x[top], self._b[top], self._tail_out[0], self._tail_out[1], start, 0, maxcycles, 0.0)
         return self._x[top]
 
+    def pair_eligible(self, lvl):
+        """Launch level lvl smooths in pairs (odil_stencil_var_smooth2_batch): a shape the pair admits, and at least
+        `pair_min_cells` cells of ALL members together on that level (together they fill the chip).  Host arithmetic."""
+        return (ops.smooth2_supported(self.shapes[lvl])
+                and self.nbatch * math.prod(self.shapes[lvl]) >= self.pair_min_cells)
+
+    def _launches(self, lvl, weights, first_single=False):
+        """`sweep_plan` on a level that pairs, else one launch per sweep (the cycle without the pair kernel)."""
+        return sweep_plan(weights, first_single) if self.pair_eligible(lvl) else [(w,) for w in weights]
+
+    def _smooth(self, c, src, b, ws, dst, partials=None):
+        """One launch of the plan: a single sweep (with the partial sums, where asked for) or the one-pass pair."""
+        if len(ws) == 2:
+            ops.stencil_var_smooth2_batch(c, src, b, ws[0], ws[1], dst, active=self._active)
+        else:
+            ops.stencil_var_smooth_batch(c, src, b, ws[0], dst, active=self._active, partials=partials)
+
     def _cycle(self, lvl, x, b, zero=False, decide=None):
         """One cycle of every active member on launch level lvl, from x (zero: from the zero vector) into x.
-        decide: called after the first pre-smoothing sweep, which then leaves its partial sums; True ends the cycle there."""
+        decide: called after the first pre-smoothing sweep, which then leaves its partial sums; True ends the cycle there.
+        Sweeps run in the launches of `sweep_plan` where the level pairs (bit-identical to single sweeps); every launch
+        but the last one of the post-smoothing writes one of the two scratch arrays, never the one it reads."""
         c, active = self.level(lvl), self._active
         scratch = self._s[lvl]
         cur = None if zero else x
-        for j, w in enumerate(self.wpre):
+        pre = self._launches(lvl, self.wpre, first_single=decide is not None)
+        for j, ws in enumerate(pre):
             dst = scratch[j % 2]
-            ops.stencil_var_smooth_batch(c, cur, b, w, dst, active=active,
-                                         partials=self._partials if decide is not None and j == 0 else None)
+            self._smooth(c, cur, b, ws, dst, partials=self._partials if decide is not None and j == 0 else None)
             cur = dst
             if decide is not None and j == 0 and decide():
                 return
-        other = scratch[len(self.wpre) % 2]
+        other = scratch[len(pre) % 2]
         bc = self._b[lvl + 1]
         if all(self.halve[lvl]):
             ops.stencil_var_residual_restrict_batch(c, cur, b, 1.0 / 2 ** self.ndim, bc, active=active)
@@ -1101,9 +1135,10 @@ class EnsembleLaunchGMG(EnsembleGMG):
                 self._cycle(lvl + 1, xc, bc)
         ops.interp_add(xc, "." + self.locs[lvl], add=cur, out=other)  # x + P x_c
         cur, other = other, cur
-        for j, w in enumerate(self.wpost):
-            dst = x if j == len(self.wpost) - 1 else other
-            ops.stencil_var_smooth_batch(c, cur, b, w, dst, active=active)
+        post = self._launches(lvl, self.wpost)
+        for j, ws in enumerate(post):
+            dst = x if j == len(post) - 1 else other
+            self._smooth(c, cur, b, ws, dst)
             cur, other = dst, cur
 
     def _nested(self, b, x):

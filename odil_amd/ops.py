@@ -353,6 +353,27 @@ def stencil_var_smooth_batch(coeffs, x, b, omega, out, mode=0, active=None, part
     return out
 
 
+def stencil_var_smooth2_batch(coeffs, x, b, omega1, omega2, out, active=None, zc_hint=0):
+    """`stencil_var_smooth2` (two sweeps, weights omega1 then omega2, in ONE pass over the coefficient arrays; x = None:
+    from the zero vector) for every member of an ensemble in ONE launch (include/odil_hip.h:
+    odil_stencil_var_smooth2_batch): per member the bits of two `stencil_var_smooth` calls.  Arrays, strides and `active`
+    as in `stencil_var_smooth_batch`, members of a shape `smooth2_supported` admits, every member on a pack boundary
+    (even strides); out is not x."""
+    nb, shape = b.shape[0], tuple(int(n) for n in b.shape[1:])
+    ndim, cells = len(shape), math.prod(shape)
+    assert smooth2_supported(shape), shape
+    assert tuple(out.shape) == tuple(b.shape) and out.dtype == b.dtype == coeffs.dtype and coeffs.shape[0] == nb
+    assert x is None or (tuple(x.shape) == tuple(b.shape) and x.dtype == b.dtype)
+    pack = 2 * b.element_size()
+    assert all(t is None or t.data_ptr() % pack == 0 for t in (coeffs, x, b, out)), "arrays must begin on a pack boundary"
+    cp, cs = _packed_members(coeffs, (2 * ndim + 1) * cells)
+    call("stencil_var_smooth2_batch", b.dtype, cp, cs, None if x is None else _base_ptr(x),
+         c_int64(0 if x is None else _member_stride(x, cells)), _base_ptr(b), c_int64(_member_stride(b, cells)), _base_ptr(out),
+         c_int64(_member_stride(out, cells)), i64(shape), c_int(ndim), c_int(nb), float(omega1), float(omega2), c_int(zc_hint),
+         _active_ptr(active, nb), stream_ptr())
+    return out
+
+
 def stencil_var_residual_restrict_batch(coeffs, x, b, scale, out, active=None):
     """out = scale * (sum over the 2^d children of b - A x) for every member in ONE launch (odil_stencil_var_residual_
     restrict_batch): every axis merged, even extents, no norm.  Arrays as in `stencil_var_smooth_batch`; out: [B, *shape / 2]."""
