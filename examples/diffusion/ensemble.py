@@ -11,6 +11,12 @@ for one workgroup (256^2, 64^3, 128^3): the levels above 32768 cells as launches
 decision on the device (`gmg.EnsembleLaunchGMG`); `--form auto` takes it only where `--form workgroup` refuses.
 `--pair_min_cells N` sets from how many cells of all members together a launch level smooths twice per pass
 (`odil_stencil_var_smooth2_batch`; 0: always, -1: never).
+`--velocity V` adds first-order upwind convection,  div(k grad u) - v du/dx_0 - beta u^3 = f  with v_b = V (b + 1) / B
+(`--velocity_from V0`: v_b = V0 + (V - V0) (b + 1) / B) swept over the members like the conductivity amplitude (the Jacobian stays a (2 d + 1)-point stencil); the members of an
+ensemble walk one set of levels, so V is chosen where they coarsen alike (e.g. `--N 8 --ndim 3 --velocity 800 --members 4`:
+v = 200 ... 800), and a refusal is printed as it is.  `--krylov auto` hands a member whose cycles stop contracting to GCR(6)
+inside the solve launch (`optimize_newton_ensemble(krylov="auto")`); `--krylov never` reports it as not converged.
+`--alternate R` times the ensemble and the single runs R more times, alternating in one process, and prints min - max.
 
 `--optimizer adam` runs the same sweep with Adam (`odil.util.optimize_ensemble(form="auto")`, its route for traced stencil
 operators: every launch of an epoch covers all members; `--multigrid 1` for a multigrid-decomposed unknown) and prints the
@@ -53,9 +59,18 @@ def operator(ctx):
         st.append(ctx.field("u", *[-1 if j == i else 0 for j in dirs]))
         st.append(ctx.field("u", *[1 if j == i else 0 for j in dirs]))
     fu = diffusion.flux_divergence(st, extra.kfaces, dirs, ctx.indices(), ctx.size(), ctx.step(), mod, extra.args.sigma)
+    if getattr(extra, "velocity", 0.0):
+        fu = fu - upwind_convection(st[0], st[1], extra.velocity, ctx.indices(), ctx.size(), ctx.step(), mod)
     if extra.beta:
         fu = fu - extra.beta * (st[0] * st[0] * st[0])
     return [fu - extra.rhs]
+
+
+def upwind_convection(q, qm, velocity, iw, nw, dw, mod):
+    """v du/dx_0 by first-order upwinding (v > 0: the difference towards -e_0) on the rows away from the walls of axis 0."""
+    zero = mod.cast(0, q.dtype)
+    inner = velocity * (q - qm) / dw[0]
+    return mod.where(iw[0] == 0, zero, mod.where(iw[0] == nw[0] - 1, zero, inner))
 
 
 def parse_args(argv=None):
@@ -70,6 +85,14 @@ def parse_args(argv=None):
     own.add_argument("--pair_min_cells", type=int, default=None,
                      help="--form launches: levels on which all members together have at least N cells smooth twice per pass "
                           "(gmg.EnsembleLaunchGMG.pair_min_cells; 0: always, -1: never; default: the class's)")
+    own.add_argument("--velocity", type=float, default=0.0,
+                     help="Upwind convection - v du/dx_0, v swept over the members up to this value (0: none)")
+    own.add_argument("--velocity_from", type=float, default=0.0,
+                     help="The sweep of v starts above this value: v_b = from + (V - from) (b + 1) / B")
+    own.add_argument("--krylov", type=str, default="never", choices=("never", "auto"),
+                     help="Newton: hand a member whose cycles stop contracting to GCR inside the solve launch")
+    own.add_argument("--alternate", type=int, default=0,
+                     help="Newton: after the report, time the ensemble and the single runs alternating this many times")
     own.add_argument("--repeat", type=int, default=3, help="--optimizer adam: timed repetitions of the ensemble and the single runs")
     mine, rest = own.parse_known_args(argv)
     args = diffusion.parse_args(["--ndim", "2", "--N", "16", "--epochs", "2"] + rest)
@@ -87,12 +110,16 @@ def make_member(args, b):
     amp = (b + 1) / args.members
     extra.kfaces = [tuple(1 + amp * (k - 1) for k in pair) for pair in extra.kfaces]
     extra.beta = float(args.beta)
+    lowest = float(getattr(args, "velocity_from", 0.0))
+    extra.velocity = lowest + (float(getattr(args, "velocity", 0.0)) - lowest) * amp if getattr(args, "velocity", 0.0) else 0.0
     ndim = domain.ndim
     st = [extra.ref_u]
     for i in range(ndim):
         st += [mod.roll(extra.ref_u, 1, i), mod.roll(extra.ref_u, -1, i)]
     extra.rhs = diffusion.flux_divergence(st, extra.kfaces, range(ndim), domain.indices(), domain.size(), domain.step(), mod,
                                           args.sigma)
+    if extra.velocity:
+        extra.rhs = extra.rhs - upwind_convection(st[0], st[1], extra.velocity, domain.indices(), domain.size(), domain.step(), mod)
     if args.beta:
         extra.rhs = extra.rhs - extra.beta * (extra.ref_u * extra.ref_u * extra.ref_u)
     return odil.Problem(operator, domain, extra), state
@@ -265,7 +292,14 @@ def main():
             problem.domain.arrays_to_state([u.clone()], state)
         synchronize()
 
-    arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback, linearize=args.linearize, form=args.form)
+    try:
+        arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, callback, linearize=args.linearize,
+                                                               form=args.form, krylov=args.krylov)
+    except ValueError as refusal:
+        if not (args.velocity or args.krylov != "never"):
+            raise  # (command lines without the two options: as before)
+        print(refusal)  # (members that coarsen differently, a form that has no hand-over, ...: as it is)
+        raise SystemExit(1)
     import torch
 
     together, timed = None, optinfo.route == "stencil" and torch.cuda.is_available()
@@ -273,16 +307,23 @@ def main():
         restart()
         start = time.perf_counter()
         arrays, optinfo = odil.util.optimize_newton_ensemble(args, problems, states, linearize=args.linearize, time_linearize=timed,
-                                                               form=args.form)
+                                                               form=args.form, krylov=args.krylov)
         synchronize()
         together = (time.perf_counter() - start) / nsteps
     status = [optinfo.solver.status(b) for b in range(args.members)] if optinfo.solver is not None else []
     printlog("\nroute '{}', form '{}', last Newton step, per member:".format(optinfo.route, optinfo.form))
     for b, (problem, state, st) in enumerate(zip(problems, states, status)):
-        printlog("member {:3d}: {} cycles, relative residual {:.2e}{}, error u:{:.5g}".format(
-            b, st["niter"], st["residual"] / max(st["bnorm"], 1e-300), "" if st["converged"] else " (not converged)",
+        handed = "" if st.get("handover") is None else ", handed to GCR before cycle {}".format(st["handover"])
+        printlog("member {:3d}: {} cycles{}, relative residual {:.2e}{}, error u:{:.5g}".format(
+            b, st["niter"], handed, st["residual"] / max(st["bnorm"], 1e-300), "" if st["converged"] else " (not converged)",
             diffusion.error_rms(problem.domain, problem.extra, state, "u")))
     lines = ["{} converged members of {}".format(sum(bool(st["converged"]) for st in status), args.members)]
+    if args.krylov != "never":
+        handed = [int(st["handover"]) for st in status if st.get("handover") is not None]
+        lines.append("{} members handed to GCR inside the launch{}".format(
+            len(handed), " (before cycles {} ... {})".format(min(handed), max(handed)) if handed else ""))
+    if status and (args.velocity or args.krylov != "never"):
+        lines.append("passes per member: {} ... {}".format(min(st["niter"] for st in status), max(st["niter"] for st in status)))
     if together is not None:
         lines.append("ensemble: {:.3f} ms per Newton step of all members".format(1e3 * together))
     if together is not None and optinfo.linearize_ms is not None:
@@ -300,6 +341,31 @@ def main():
         alone = (time.perf_counter() - start) / nsteps
         lines.append("single runs: {:.3f} ms per Newton step of all members, {:.1f} x the ensemble".format(
             1e3 * alone, alone / together))
+    if args.alternate > 0 and together is not None:
+        # every kernel of both routes is loaded by now (a single run that hands over to GCR loads its own on the way)
+        def ensemble_steps():
+            odil.util.optimize_newton_ensemble(args, problems, states, linearize=args.linearize, form=args.form, krylov=args.krylov)
+
+        def single_steps():
+            for problem, state in zip(problems, states):
+                odil.util.optimize_newton(args, problem, state)
+
+        times = dict(ensemble=[], single=[])
+        for _ in range(args.alternate):
+            for name, run in (("ensemble", ensemble_steps), ("single", single_steps)):
+                if name == "single" and not args.single:
+                    continue
+                restart()
+                start = time.perf_counter()
+                run()
+                synchronize()
+                times[name].append(1e3 * (time.perf_counter() - start) / nsteps)
+        span = lambda values: "{:.3f} - {:.3f}".format(min(values), max(values))
+        lines.append("alternating, {} repetitions: ensemble {} ms per Newton step of all members".format(
+            args.alternate, span(times["ensemble"])))
+        if times["single"]:
+            lines.append("alternating: single runs {} ms per Newton step of all members, {:.1f} x the ensemble (best of "
+                         "each)".format(span(times["single"]), min(times["single"]) / min(times["ensemble"])))
     for line in lines:
         printlog(line)
         if not args.echo:  # (the log goes to train.log: the verdict also to the terminal)

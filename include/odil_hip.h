@@ -849,6 +849,42 @@ int odil_stencil_solve_batch_f32(const float* coeffs, int64_t coeff_stride, cons
                                  void* stream);
 /* work elements per member of odil_stencil_solve_batch; 0 if the shapes are malformed */
 int64_t odil_stencil_solve_batch_work(const int64_t* shapes, int nlev, int ndim);
+/* odil_stencil_solve_batch with a KRYLOV HAND-OVER inside the launch: a member whose cycles stop contracting goes on with
+ * GCR(krylov_m) around the same cycle, in its own workgroup -- still one launch and one read-back for the whole ensemble.
+ * Arguments as odil_stencil_solve_batch, and
+ *   krylov_m   1..8 directions kept between restarts (gmg.EnsembleGMG passes 6)
+ *   work       per member odil_stencil_solve_krylov_batch_work(shapes, nlev, ndim, krylov_m) = that of
+ *              odil_stencil_solve_batch plus (2 krylov_m + 2) finest-level vectors: the iterate xk, the residual rho, the
+ *              directions Z[m] and their images Q[m]
+ *   outcome    [nbatch, 3]: passes run (cycles + GCR passes), stop reason, the cycle before which the member was handed
+ *              over (-1: never)
+ * The decision before cycle k, in this order: 3 a non-finite norm; 0 converged; 1 k == maxcycles; HAND-OVER when k >= 2 and
+ * history[1 + k] >= 0.25 history[k] and history[1 + k] > 1e6 tol^2 history[0] (the rule of gmg.PoissonGMG.solve on mean
+ * squares); 2 stagnated; else one cycle.  A member that never meets the hand-over rule runs the instruction sequence of
+ * odil_stencil_solve_batch on the same buffers: iterate, history and (cycles, reason) are its bits, outcome[b, 2] = -1.
+ * After the hand-over every pass is that of gmg.PoissonGMG.solve_krylov: e = one cycle from the ZERO start on rho, z = e,
+ * q = A z, classical Gram-Schmidt of (q, z) against the stored (Q_j, Z_j), both scaled by 1 / |q|, a = <q, rho>,
+ * xk += a z, rho -= a q, history[1 + k] = mean(rho^2); after krylov_m passes the directions are dropped.  Vectors in the
+ * working precision, every product and norm accumulated in double in the fixed order of odil_stencil_solve_batch.  Stop
+ * reasons inside GCR: 3 non-finite rho; 4 BREAKDOWN, |q|^2 zero or non-finite (not converged); 1 k == maxcycles; 0 only
+ * when the TRUE residual rhs - A xk, formed anew once the recurrence passes the tolerance and written over history[1 + k],
+ * passes it too (else GCR restarts from that residual).  The loop is bounded by maxcycles whatever the numbers do.
+ * Malformed arguments, krylov_m outside 1..8 and a work array too small for the larger work size are refused before any
+ * launch.  (No reference counterpart.) */
+int odil_stencil_solve_krylov_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve,
+                                        int nlev, int ndim, int nbatch, double* x, int64_t x_stride, const double* b,
+                                        int64_t b_stride, double* work, int64_t work_stride, int64_t work_len,
+                                        const double* inv, int64_t inv_stride, int ninv, const double* wpre, int npre,
+                                        const double* wpost, int npost, int start, int mode, int maxcycles, double tol,
+                                        double* history, int64_t history_stride, int* outcome, int krylov_m, void* stream);
+int odil_stencil_solve_krylov_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve,
+                                        int nlev, int ndim, int nbatch, float* x, int64_t x_stride, const float* b,
+                                        int64_t b_stride, float* work, int64_t work_stride, int64_t work_len,
+                                        const float* inv, int64_t inv_stride, int ninv, const float* wpre, int npre,
+                                        const float* wpost, int npost, int start, int mode, int maxcycles, float tol,
+                                        double* history, int64_t history_stride, int* outcome, int krylov_m, void* stream);
+/* work elements per member of odil_stencil_solve_krylov_batch; 0 if the shapes are malformed or krylov_m is not 1..8 */
+int64_t odil_stencil_solve_krylov_batch_work(const int64_t* shapes, int nlev, int ndim, int krylov_m);
 /* Mixed-precision iterative refinement of the multigrid Newton solve (gmg.py; no reference counterpart -- the reference's
  * direct solver is double throughout): float32 V-cycles inside a float64 residual loop.  narrow_scale: y32 = s x64 with
  * s = a / sqrt(*msq) (msq: device scalar, the mean square the residual kernel just wrote; NULL: s = a); widen_axpy:

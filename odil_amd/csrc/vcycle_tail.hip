@@ -342,6 +342,8 @@ static int vcycle_tail(const T* coeffs, const int64_t* shapes, const int* halve,
 constexpr int kSolveMaxCycles = 1000;
 // (k_vcycle_tail takes extents up to 4096; a 1-D member of 32768 cells is one row: tail_div is exact for i < 2^22)
 constexpr int kSolveMaxExtent = 32768;
+// (directions GCR keeps between restarts: their products with the new image are one register pair each)
+constexpr int kKrylovMax = 8;
 
 template <typename T>
 struct SolveArgs {
@@ -370,11 +372,42 @@ __device__ __forceinline__ double solve_block_sum(double s, double* red) {
   return v[0];
 }
 
+// GCR of k_stencil_solve_batch: rho = rhs - A xk on the finest level, its mean square to every thread (xk complete and
+// visible before the call)
 template <typename T>
+__device__ __forceinline__ double solve_true_residual(const T* __restrict__ c, const T* __restrict__ xk,
+                                                      const T* __restrict__ rhs, T* __restrict__ rho, const TailLevel& L,
+                                                      const TailArgs<T>& a, double* red, double rcells) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < L.size; i += kTailThreads) {
+    int id[3];
+    tail_decode(i, L, id);
+    const T v = rhs[i] - tail_apply<T>(c, xk, false, L, a, i, id);
+    rho[i] = v;
+    acc += (double)v * (double)v;
+  }
+  return solve_block_sum(acc, red) * rcells;
+}
+
+// one decision of thread 0 (`why` of the others is ignored) to every thread
+__device__ __forceinline__ int solve_publish(int why, int* shared) {
+  if (threadIdx.x == 0) *shared = why;
+  __syncthreads();
+  const int all = *shared;
+  __syncthreads();  // (read by all before thread 0 writes the next decision)
+  return all;
+}
+
+// KRYLOV (odil_stencil_solve_krylov_batch): one more rule in the decision before cycle k -- a member whose cycles contract
+// by less than 0.5 well above the tolerance (the hand-over rule of gmg.PoissonGMG.solve, on mean squares) goes on with
+// GCR(krylov_m) around the same cycle (the algebra of PoissonGMG.solve_krylov), inside this launch.  A member that never
+// meets the rule runs the instruction sequence of the plain kernel on the same buffers.  The (2 m + 2) vectors of GCR --
+// the iterate xk, the residual rho, Z[m], Q[m] -- follow the levels' 3 x cells in `work`.  outcome: [B, 3].
+template <typename T, bool KRYLOV>
 __global__ __launch_bounds__(kTailThreads) void k_stencil_solve_batch(const T* __restrict__ coeffs_all, T* x_all,
                                                                       const T* __restrict__ b_all, T* work_all,
                                                                       const T* __restrict__ inv_all, double* history_all,
-                                                                      int* outcome, SolveArgs<T> s) {
+                                                                      int* outcome, SolveArgs<T> s, int krylov_m) {
   const TailArgs<T>& a = s.t;
   const int64_t member = blockIdx.x;
   const T* coeffs = coeffs_all + member * s.coeff_stride;
@@ -400,7 +433,9 @@ __global__ __launch_bounds__(kTailThreads) void k_stencil_solve_batch(const T* _
   // the right-hand side of the system solved: b, or in a Newton step r = A u - b (the finest level's third slot of `work`)
   T* rwork = work + L0.b;
   const T* rhs0 = s.mode ? rwork : bm;
-  auto rhs = [&](int l) -> const T* { return l == 0 ? rhs0 : work + a.lv[l].b; };
+  // (KRYLOV: the cycle that preconditions GCR takes the residual rho as its finest right-hand side; workgroup-uniform)
+  const T* rhs_top = rhs0;
+  auto rhs = [&](int l) -> const T* { return l == 0 ? (KRYLOV ? rhs_top : rhs0) : work + a.lv[l].b; };
 
   auto coarsest = [&]() {
     const TailLevel& L = a.lv[last];
@@ -496,48 +531,216 @@ __global__ __launch_bounds__(kTailThreads) void k_stencil_solve_batch(const T* _
   // 4. cycles until a stop rule fires (k <= maxcycles <= kSolveMaxCycles: the loop is bounded whatever the numbers do)
   int k = 0, reason = 1;
   double prev = bsq;
-  for (; k <= s.maxcycles; ++k) {
-    sum = 0.0;
-    {
-      const T* xc = cur(0);
-      const bool zero = get(0) == 0;
-      for (int i = threadIdx.x; i < L0.size; i += kTailThreads) {
-        int id[3];
-        tail_decode(i, L0, id);
-        const double v = (double)(tail_apply<T>(coeffs + L0.c, xc, zero, L0, a, i, id) - rhs0[i]);
-        sum += v * v;
+  int handover = -1;
+  T* xk = nullptr;
+  if constexpr (!KRYLOV) {
+    // (this loop has a COPY in the branch below, which adds the hand-over rule and the GCR pass: a change to the residual
+    // or to the stop rules here is made there too -- tests/test_newton_ensemble_krylov_gpu.py holds members that never
+    // hand over to the same bits from both)
+    for (; k <= s.maxcycles; ++k) {
+      sum = 0.0;
+      {
+        const T* xc = cur(0);
+        const bool zero = get(0) == 0;
+        for (int i = threadIdx.x; i < L0.size; i += kTailThreads) {
+          int id[3];
+          tail_decode(i, L0, id);
+          const double v = (double)(tail_apply<T>(coeffs + L0.c, xc, zero, L0, a, i, id) - rhs0[i]);
+          sum += v * v;
+        }
+      }
+      const double rsq = solve_block_sum(sum, red) * rcells;
+      // the decision is taken ONCE and read by every thread after a barrier: every exit of this loop is workgroup-uniform
+      if (threadIdx.x == 0) {
+        history[1 + k] = rsq;
+        int why = -1;
+        if (!__builtin_isfinite(rsq) || !__builtin_isfinite(bsq)) why = 3;
+        else if (rsq <= s.tol2 * bsq) why = 0;
+        else if (k == s.maxcycles) why = 1;
+        else if (k >= 3 && rsq >= (0.98 * 0.98) * prev) why = 2;
+        stop_shared = why;
+      }
+      __syncthreads();
+      const int why = stop_shared;
+      __syncthreads();  // (read by all before thread 0 writes the next decision)
+      if (why >= 0) {
+        reason = why;
+        break;
+      }
+      prev = rsq;
+      if (last == 0)
+        coarsest();
+      else
+        vcycle(0);
+    }
+  } else {
+    // The same loop with the hand-over rule (the plain loop above stays as it was, and with it the registers of its
+    // instantiation).  GCR(m) with one cycle from the zero start as the preconditioner takes over from the iterate of cycle
+    // `handover` (PoissonGMG.solve_krylov); it shares this loop, so the cycle stands once in it.  Every branch below that
+    // holds a barrier depends on `handover`, `have`, `k` and on decisions read from stop_shared alone: workgroup-uniform.
+    // The sums of solve_block_sum are the same bits in every thread.
+    int have = 0;
+    const int cells = L0.size;
+    xk = work + a.lv[last].b + a.lv[last].size;  // (behind the three arrays of every level)
+    T* rho = xk + cells;
+    T* zall = rho + cells;
+    T* qall = zall + (int64_t)krylov_m * cells;
+    for (; k <= s.maxcycles; ++k) {
+      if (handover < 0) {
+        sum = 0.0;
+        {
+          const T* xc = cur(0);
+          const bool zero = get(0) == 0;
+          for (int i = threadIdx.x; i < L0.size; i += kTailThreads) {
+            int id[3];
+            tail_decode(i, L0, id);
+            const double v = (double)(tail_apply<T>(coeffs + L0.c, xc, zero, L0, a, i, id) - rhs0[i]);
+            sum += v * v;
+          }
+        }
+        const double rsq = solve_block_sum(sum, red) * rcells;
+        // the decision is taken ONCE and read by every thread after a barrier: every exit of this loop is workgroup-uniform
+        if (threadIdx.x == 0) {
+          history[1 + k] = rsq;
+          int why = -1;
+          if (!__builtin_isfinite(rsq) || !__builtin_isfinite(bsq)) why = 3;
+          else if (rsq <= s.tol2 * bsq) why = 0;
+          else if (k == s.maxcycles) why = 1;
+          else if (k >= 2 && rsq >= 0.25 * prev && rsq > 1e6 * s.tol2 * bsq) why = -2;  // (hand over to GCR)
+          else if (k >= 3 && rsq >= (0.98 * 0.98) * prev) why = 2;
+          stop_shared = why;
+        }
+        __syncthreads();
+        const int why = stop_shared;
+        __syncthreads();  // (read by all before thread 0 writes the next decision)
+        if (why >= 0) {
+          reason = why;
+          break;
+        }
+        prev = rsq;
+        if (why == -2) {
+          // (the cycle rotates its own buffers underneath: the iterate gets a home of its own)
+          handover = k;
+          const T* x0 = cur(0);
+          for (int i = threadIdx.x; i < cells; i += kTailThreads) xk[i] = x0 != nullptr ? x0[i] : T(0);
+          __syncthreads();
+          solve_true_residual<T>(coeffs + L0.c, xk, rhs0, rho, L0, a, red, rcells);
+        }
+      }
+      if (handover >= 0) {  // e = M^-1 rho: the cycle from the zero start, rho its right-hand side
+        rhs_top = rho;
+        set(0, 0);
+      }
+      if (last == 0)
+        coarsest();
+      else
+        vcycle(0);
+      {
+        if (handover >= 0) {
+          // the rest of pass k of GCR; k < maxcycles here, and a pass that goes on raises k
+          rhs_top = rhs0;
+          const T* e = cur(0);
+          T* z = zall + (int64_t)have * cells;
+          T* q = qall + (int64_t)have * cells;
+          // z = e, q = A z, and the products of q with the stored images in the same pass
+          double dot[kKrylovMax];
+#pragma unroll
+          for (int j = 0; j < kKrylovMax; ++j) dot[j] = 0.0;
+          for (int i = threadIdx.x; i < cells; i += kTailThreads) {
+            int id[3];
+            tail_decode(i, L0, id);
+            const T qi = tail_apply<T>(coeffs + L0.c, e, false, L0, a, i, id);
+            z[i] = e[i];
+            q[i] = qi;
+#pragma unroll
+            for (int j = 0; j < kKrylovMax; ++j)
+              if (j < have) dot[j] += (double)qall[(int64_t)j * cells + i] * (double)qi;
+          }
+#pragma unroll
+          for (int j = 0; j < kKrylovMax; ++j)
+            if (j < have) dot[j] = solve_block_sum(dot[j], red);
+          // classical Gram-Schmidt: q -= sum beta_j Q_j, z -= sum beta_j Z_j; |q|^2
+          double qq = 0.0;
+          for (int i = threadIdx.x; i < cells; i += kTailThreads) {
+            T qi = q[i], zi = z[i];
+#pragma unroll
+            for (int j = 0; j < kKrylovMax; ++j)
+              if (j < have) {
+                const T beta = (T)dot[j];
+                qi = qi - beta * qall[(int64_t)j * cells + i];
+                zi = zi - beta * zall[(int64_t)j * cells + i];
+              }
+            q[i] = qi;
+            z[i] = zi;
+            qq += (double)qi * (double)qi;
+          }
+          qq = solve_block_sum(qq, red);
+          // breakdown: the preconditioner returned nothing useful
+          if (solve_publish(!(qq > 0.0) || !__builtin_isfinite(qq) ? 4 : -1, &stop_shared) >= 0) {
+            reason = 4;
+            break;
+          }
+          const T scale = (T)(1.0 / sqrt(qq));
+          double aq = 0.0;
+          for (int i = threadIdx.x; i < cells; i += kTailThreads) {
+            const T qi = q[i] * scale;
+            q[i] = qi;
+            z[i] = z[i] * scale;
+            aq += (double)qi * (double)rho[i];
+          }
+          const T alpha = (T)solve_block_sum(aq, red);
+          double rr = 0.0;
+          for (int i = threadIdx.x; i < cells; i += kTailThreads) {
+            xk[i] = xk[i] + alpha * z[i];
+            const T v = rho[i] - alpha * q[i];
+            rho[i] = v;
+            rr += (double)v * (double)v;
+          }
+          double rsq = solve_block_sum(rr, red) * rcells;
+          const int k1 = k + 1;
+          int why = -1;
+          if (threadIdx.x == 0) {
+            history[1 + k1] = rsq;
+            if (!__builtin_isfinite(rsq)) why = 3;
+            else if (rsq <= s.tol2 * bsq) why = -3;  // (the recurrence says converged: the true residual decides)
+            else if (k1 == s.maxcycles) why = 1;
+          }
+          why = solve_publish(why, &stop_shared);
+          ++have;
+          if (why == -3) {
+            rsq = solve_true_residual<T>(coeffs + L0.c, xk, rhs0, rho, L0, a, red, rcells);
+            why = -1;
+            if (threadIdx.x == 0) {
+              history[1 + k1] = rsq;
+              if (!__builtin_isfinite(rsq)) why = 3;
+              else if (rsq <= s.tol2 * bsq) why = 0;
+              else if (k1 == s.maxcycles) why = 1;
+            }
+            why = solve_publish(why, &stop_shared);
+            have = 0;  // (the recurrence had drifted: the directions go with it)
+          }
+          if (why >= 0) {
+            reason = why;
+            k = k1;
+            break;
+          }
+          if (have == krylov_m) have = 0;  // restart: the stored directions are dropped
+        }
       }
     }
-    const double rsq = solve_block_sum(sum, red) * rcells;
-    // the decision is taken ONCE and read by every thread after a barrier: every exit of this loop is workgroup-uniform
-    if (threadIdx.x == 0) {
-      history[1 + k] = rsq;
-      int why = -1;
-      if (!__builtin_isfinite(rsq) || !__builtin_isfinite(bsq)) why = 3;
-      else if (rsq <= s.tol2 * bsq) why = 0;
-      else if (k == s.maxcycles) why = 1;
-      else if (k >= 3 && rsq >= (0.98 * 0.98) * prev) why = 2;
-      stop_shared = why;
-    }
-    __syncthreads();
-    const int why = stop_shared;
-    __syncthreads();  // (read by all before thread 0 writes the next decision)
-    if (why >= 0) {
-      reason = why;
-      break;
-    }
-    prev = rsq;
-    if (last == 0)
-      coarsest();
-    else
-      vcycle(0);
   }
   if (threadIdx.x == 0) {
-    outcome[2 * member] = k;
-    outcome[2 * member + 1] = reason;
+    if constexpr (KRYLOV) {
+      outcome[3 * member] = k;
+      outcome[3 * member + 1] = reason;
+      outcome[3 * member + 2] = handover;
+    } else {
+      outcome[2 * member] = k;
+      outcome[2 * member + 1] = reason;
+    }
   }
   // 5. the result: x, or u - d
-  const T* res = cur(0);
+  const T* res = KRYLOV && handover >= 0 ? xk : cur(0);
   if (s.mode) {
     if (res != nullptr)
       for (int i = threadIdx.x; i < L0.size; i += kTailThreads) xm[i] = xm[i] - res[i];
@@ -548,8 +751,8 @@ __global__ __launch_bounds__(kTailThreads) void k_stencil_solve_batch(const T* _
 
 // the level table of `shapes` / `halve` (what vcycle_tail builds); false with the error set
 template <typename T>
-static bool solve_levels(TailArgs<T>& a, const int64_t* shapes, const int* halve, int nlev, int ndim, int64_t* ncoeff,
-                         int64_t* nwork) {
+static bool solve_levels(const char* who, TailArgs<T>& a, const int64_t* shapes, const int* halve, int nlev, int ndim,
+                         int64_t* ncoeff, int64_t* nwork) {
   a.nlev = nlev, a.ndim = ndim;
   for (int d = 0; d < 3; ++d) {
     const int i = d - (3 - ndim);
@@ -568,7 +771,7 @@ static bool solve_levels(TailArgs<T>& a, const int64_t* shapes, const int* halve
       if (i < 0) continue;
       const int64_t n = shapes[l * ndim + i];
       if (n < 1 || n > kSolveMaxExtent) {
-        set_error("stencil_solve_batch: extent %lld of level %d", (long long)n, l);
+        set_error("%s: extent %lld of level %d", who, (long long)n, l);
         return false;
       }
       L.n[d] = (int)n;
@@ -578,13 +781,13 @@ static bool solve_levels(TailArgs<T>& a, const int64_t* shapes, const int* halve
         L.halve[d] = halve[l * ndim + i] != 0;
         const int64_t nc = shapes[(l + 1) * ndim + i];
         if ((L.halve[d] && (n % 2 || nc != n / 2)) || (!L.halve[d] && nc != n)) {
-          set_error("stencil_solve_batch: level %d does not follow from level %d along axis %d", l + 1, l, i);
+          set_error("%s: level %d does not follow from level %d along axis %d", who, l + 1, l, i);
           return false;
         }
       }
     }
     if (size > (1 << 20)) {
-      set_error("stencil_solve_batch: level %d has %lld cells (one workgroup walks the hierarchy)", l, (long long)size);
+      set_error("%s: level %d has %lld cells (one workgroup walks the hierarchy)", who, l, (long long)size);
       return false;
     }
     L.size = (int)size;
@@ -597,71 +800,79 @@ static bool solve_levels(TailArgs<T>& a, const int64_t* shapes, const int* halve
   return true;
 }
 
-template <typename T>
+// KRYLOV: odil_stencil_solve_krylov_batch (krylov_m directions, the work of the (2 m + 2) vectors of GCR, outcome [B, 3])
+template <typename T, bool KRYLOV = false>
 static int stencil_solve_batch(const T* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve, int nlev,
                                int ndim, int nbatch, T* x, int64_t x_stride, const T* b, int64_t b_stride, T* work,
                                int64_t work_stride, int64_t work_len, const T* inv, int64_t inv_stride, int ninv,
                                const T* wpre, int npre, const T* wpost, int npost, int start, int mode, int maxcycles,
-                               double tol, double* history, int64_t history_stride, int* outcome, void* stream) {
+                               double tol, double* history, int64_t history_stride, int* outcome, void* stream,
+                               int krylov_m = 0) {
+  const char* who = KRYLOV ? "stencil_solve_krylov_batch" : "stencil_solve_batch";
+  if (KRYLOV && (krylov_m < 1 || krylov_m > kKrylovMax)) {
+    set_error("%s: krylov_m %d (1..%d directions)", who, krylov_m, kKrylovMax);
+    return ODIL_E_INVAL;
+  }
   if (nlev < 1 || nlev > kTailMaxLev || ndim < 1 || ndim > 3 || npre < 0 || npre > 4 || npost < 0 || npost > 4) {
-    set_error("stencil_solve_batch: bad arguments (1..%d levels, ndim 1..3, at most 4 sweeps per side)", kTailMaxLev);
+    set_error("%s: bad arguments (1..%d levels, ndim 1..3, at most 4 sweeps per side)", who, kTailMaxLev);
     return ODIL_E_INVAL;
   }
   if (!shapes || (nlev > 1 && !halve) || !coeffs || !x || !b || !work || !inv || !history || !outcome ||
       (npre && !wpre) || (npost && !wpost)) {
-    set_error("stencil_solve_batch: null pointer");
+    set_error("%s: null pointer", who);
     return ODIL_E_INVAL;
   }
   if (nbatch < 1 || nbatch > 65535) {
-    set_error("stencil_solve_batch: %d members (1..65535: one workgroup each)", nbatch);
+    set_error("%s: %d members (1..65535: one workgroup each)", who, nbatch);
     return ODIL_E_INVAL;
   }
   if (start < 0 || start > 2 || mode < 0 || mode > 1 || (mode == 1 && start == 1)) {
-    set_error("stencil_solve_batch: start %d, mode %d (start 0..2, mode 0..1; a Newton step starts from 0 or 2)", start, mode);
+    set_error("%s: start %d, mode %d (start 0..2, mode 0..1; a Newton step starts from 0 or 2)", who, start, mode);
     return ODIL_E_INVAL;
   }
   if (maxcycles < 0 || maxcycles > kSolveMaxCycles) {
-    set_error("stencil_solve_batch: maxcycles %d (0..%d)", maxcycles, kSolveMaxCycles);
+    set_error("%s: maxcycles %d (0..%d)", who, maxcycles, kSolveMaxCycles);
     return ODIL_E_INVAL;
   }
   if (!(tol >= 0.0)) {
-    set_error("stencil_solve_batch: negative tol");
+    set_error("%s: negative tol", who);
     return ODIL_E_INVAL;
   }
   if (x == b) {
-    set_error("stencil_solve_batch: x must not alias b");
+    set_error("%s: x must not alias b", who);
     return ODIL_E_INVAL;
   }
   if (coeff_stride < 0 || x_stride < 0 || b_stride < 0 || work_stride < 0 || inv_stride < 0 || history_stride < 0) {
-    set_error("stencil_solve_batch: negative stride");
+    set_error("%s: negative stride", who);
     return ODIL_E_INVAL;
   }
   SolveArgs<T> s;
   TailArgs<T>& a = s.t;
   int64_t ncoeff = 0, nwork = 0;
-  if (!solve_levels<T>(a, shapes, halve, nlev, ndim, &ncoeff, &nwork)) return ODIL_E_INVAL;
+  if (!solve_levels<T>(who, a, shapes, halve, nlev, ndim, &ncoeff, &nwork)) return ODIL_E_INVAL;
   const int64_t cells = a.lv[0].size;
+  if (KRYLOV) nwork += (int64_t)(2 * krylov_m + 2) * cells;  // (xk, rho, Z[m], Q[m] behind the levels' arrays)
   if (ninv != a.lv[nlev - 1].size) {
-    set_error("stencil_solve_batch: the coarsest level has %d unknowns, the inverse %d", a.lv[nlev - 1].size, ninv);
+    set_error("%s: the coarsest level has %d unknowns, the inverse %d", who, a.lv[nlev - 1].size, ninv);
     return ODIL_E_INVAL;
   }
   if (x_stride < cells || b_stride < cells || work_stride < nwork) {
-    set_error("stencil_solve_batch: stride smaller than a member (x %lld, b %lld of %lld cells; work %lld of %lld values)",
+    set_error("%s: stride smaller than a member (x %lld, b %lld of %lld cells; work %lld of %lld values)", who,
               (long long)x_stride, (long long)b_stride, (long long)cells, (long long)work_stride, (long long)nwork);
     return ODIL_E_INVAL;
   }
   if (work_len < (int64_t)(nbatch - 1) * work_stride + nwork) {
-    set_error("stencil_solve_batch: work array of %lld values, %lld needed", (long long)work_len,
+    set_error("%s: work array of %lld values, %lld needed", who, (long long)work_len,
               (long long)((int64_t)(nbatch - 1) * work_stride + nwork));
     return ODIL_E_INVAL;
   }
   if ((coeff_stride != 0 && coeff_stride < ncoeff) || (inv_stride != 0 && inv_stride < (int64_t)ninv * ninv)) {
-    set_error("stencil_solve_batch: coeff_stride %lld / inv_stride %lld neither 0 (shared) nor a member's %lld / %lld values",
+    set_error("%s: coeff_stride %lld / inv_stride %lld neither 0 (shared) nor a member's %lld / %lld values", who,
               (long long)coeff_stride, (long long)inv_stride, (long long)ncoeff, (long long)ninv * ninv);
     return ODIL_E_INVAL;
   }
   if (history_stride < (int64_t)maxcycles + 2) {
-    set_error("stencil_solve_batch: history_stride %lld smaller than maxcycles + 2 = %d", (long long)history_stride,
+    set_error("%s: history_stride %lld smaller than maxcycles + 2 = %d", who, (long long)history_stride,
               maxcycles + 2);
     return ODIL_E_INVAL;
   }
@@ -674,9 +885,9 @@ static int stencil_solve_batch(const T* coeffs, int64_t coeff_stride, const int6
   s.coeff_stride = coeff_stride, s.x_stride = x_stride, s.b_stride = b_stride, s.work_stride = work_stride;
   s.inv_stride = inv_stride, s.history_stride = history_stride;
   s.start = start, s.mode = mode, s.maxcycles = maxcycles, s.tol2 = tol * tol;
-  hipLaunchKernelGGL((k_stencil_solve_batch<T>), dim3(nbatch), dim3(kTailThreads), 0, (hipStream_t)stream, coeffs, x, b,
-                     work, inv, history, outcome, s);
-  return check_launch("k_stencil_solve_batch");
+  hipLaunchKernelGGL((k_stencil_solve_batch<T, KRYLOV>), dim3(nbatch), dim3(kTailThreads), 0, (hipStream_t)stream, coeffs,
+                     x, b, work, inv, history, outcome, s, krylov_m);
+  return check_launch(KRYLOV ? "k_stencil_solve_krylov_batch" : "k_stencil_solve_batch");
 }
 
 }  // namespace odil
@@ -732,5 +943,32 @@ int64_t odil_stencil_solve_batch_work(const int64_t* shapes, int nlev, int ndim)
     total += 3 * size;
   }
   return total;
+}
+int odil_stencil_solve_krylov_batch_f64(const double* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve,
+                                        int nlev, int ndim, int nbatch, double* x, int64_t x_stride, const double* b,
+                                        int64_t b_stride, double* work, int64_t work_stride, int64_t work_len,
+                                        const double* inv, int64_t inv_stride, int ninv, const double* wpre, int npre,
+                                        const double* wpost, int npost, int start, int mode, int maxcycles, double tol,
+                                        double* history, int64_t history_stride, int* outcome, int krylov_m, void* stream) {
+  return stencil_solve_batch<double, true>(coeffs, coeff_stride, shapes, halve, nlev, ndim, nbatch, x, x_stride, b, b_stride,
+                                           work, work_stride, work_len, inv, inv_stride, ninv, wpre, npre, wpost, npost, start,
+                                           mode, maxcycles, tol, history, history_stride, outcome, stream, krylov_m);
+}
+int odil_stencil_solve_krylov_batch_f32(const float* coeffs, int64_t coeff_stride, const int64_t* shapes, const int* halve,
+                                        int nlev, int ndim, int nbatch, float* x, int64_t x_stride, const float* b,
+                                        int64_t b_stride, float* work, int64_t work_stride, int64_t work_len,
+                                        const float* inv, int64_t inv_stride, int ninv, const float* wpre, int npre,
+                                        const float* wpost, int npost, int start, int mode, int maxcycles, float tol,
+                                        double* history, int64_t history_stride, int* outcome, int krylov_m, void* stream) {
+  return stencil_solve_batch<float, true>(coeffs, coeff_stride, shapes, halve, nlev, ndim, nbatch, x, x_stride, b, b_stride,
+                                          work, work_stride, work_len, inv, inv_stride, ninv, wpre, npre, wpost, npost, start,
+                                          mode, maxcycles, (double)tol, history, history_stride, outcome, stream, krylov_m);
+}
+int64_t odil_stencil_solve_krylov_batch_work(const int64_t* shapes, int nlev, int ndim, int krylov_m) {
+  const int64_t levels = odil_stencil_solve_batch_work(shapes, nlev, ndim);
+  if (!levels || krylov_m < 1 || krylov_m > kKrylovMax) return 0;
+  int64_t cells = 1;
+  for (int i = 0; i < ndim; ++i) cells *= shapes[i];
+  return levels + (int64_t)(2 * krylov_m + 2) * cells;
 }
 }  // extern "C"

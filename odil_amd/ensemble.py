@@ -7,6 +7,7 @@ stencil is `fused.TracedLaunchEnsemble`.  `printlog` and `_pinfo` are `util`'s (
 """
 
 import argparse
+import math
 import os
 
 import numpy as np
@@ -304,7 +305,7 @@ def _traced_member(domain, state, shapes, dtype, form):
 
 
 def optimize_newton_ensemble(args, problems, states, callback=None, linearize="batched", time_linearize=False,
-                             form="workgroup"):
+                             form="workgroup", krylov="never"):
     """Newton on B small Poisson problems AT ONCE: every epoch is ONE launch that runs the whole Newton step of all
     members, one workgroup per member (gmg.EnsembleGMG.newton_step: residual, nested-iteration start, V-cycles down to the
     tolerance, the convergence decision and the update, no host read-back in between).  Every member ends at the Newton
@@ -329,9 +330,20 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
     of all members are set up again in launches that do not grow with B (`gmg.EnsembleGMG.rebuild`: two per level, one for
     the dense coarsest matrices; the pseudo-inverses on the host), ONE launch solves M_b d_b = f_b(u_b) for all members and
     one forms u -= d.  A member whose Jacobian is no such stencil raises ValueError naming it at the first epoch, before any
-    member is updated; so do members whose hierarchies do not coarsen along the same axes.  There is NO fallback to the
-    normal-equation routes when a member's cycles do not contract (`optimize_newton` has one): the member's status
-    reports converged=False or stagnated, and the caller decides.
+    member is updated; so do members whose hierarchies do not coarsen along the same axes.  There is no fallback to the
+    NORMAL EQUATIONS when a member's cycles do not contract (`optimize_newton` has one); with krylov='auto' a slow member is
+    handed to GCR inside the launch (below), with krylov='never' its status reports converged=False or stagnated, and the
+    caller decides.
+
+    krylov: 'never' (the default) or 'auto', on both routes: a member whose cycles contract by less than 0.5 well above
+    the tolerance (the rule of `gmg.PoissonGMG.solve`) goes on with GCR(6) around the same cycle inside the solve launch
+    (`gmg.EnsembleGMG(krylov="auto")`, odil_stencil_solve_krylov_batch) -- still one launch and one read-back per step;
+    members that never meet the rule get the bits of 'never'.  Its work memory, B (2 m + 2) cells values more, must fit the
+    free device memory: else ValueError naming the bytes, before any state changes.  optinfo.handover: [B, epochs], the
+    cycle before which the member was handed over in that step, -1 where it was not; the member's status names it and
+    reports method "... + GCR(6)".  Only form 'workgroup' serves it: with form='launches', and with form='auto' when the
+    members need the batched launches, ValueError (naming the member and the reason).  Any other value raises ValueError
+    before any member is looked at.
 
     linearize (stencil route): "batched" is the above; "members" linearises member by member (`linearize_device`,
     `gmg.recognise_stencil`, copies into the packed buffers: B launches of `k_jac`) -- the same iterates, cycle counts and
@@ -356,6 +368,11 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
 
     if form not in ("workgroup", "launches", "auto"):
         raise ValueError("optimize_newton_ensemble: form '{}' is none of 'workgroup', 'launches', 'auto'".format(form))
+    if krylov not in ("never", "auto"):
+        raise ValueError("optimize_newton_ensemble: krylov '{}' is neither 'never' nor 'auto'".format(krylov))
+    if krylov != "never" and form == "launches":
+        raise ValueError("optimize_newton_ensemble: krylov '{}' with form 'launches' (the hand-over to GCR runs inside the "
+                         "one-workgroup solve launch: form 'workgroup')".format(krylov))
     linsolver = getattr(args, "linsolver", "direct")
     if linsolver not in ("direct", "multigrid"):
         raise ValueError("optimize_newton_ensemble: linsolver '{}' (the one-workgroup Newton solves serve 'direct' and "
@@ -367,6 +384,7 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
                          "solve M d = r, which has the solution of the normal equations only without it")
     refused = dict(poisson=None, stencil=None)  # per route the first (member, reason) it refuses while the other admits
     launches = dict(refused=None, needed=form == "launches")  # (form 'launches' / 'auto': what the batched launches say)
+    launches["why"] = None  # (form 'auto': the first (member, reason) for which the one-workgroup form does not serve)
 
     def describe(b, problem, state, refuse):
         kind = _plain_field(b, problem, state, refuse)
@@ -387,6 +405,7 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         if None not in reasons.values():
             if form == "auto" and launches["refused"] is None:  # (no one-workgroup route: the batched launches serve it)
                 launches["needed"] = True
+                launches["why"] = launches["why"] or (b, reasons["poisson"])
                 return kind
             refuse(b, reasons["poisson"] if form == "workgroup" else "{}; as batched launches: {}".format(
                 reasons["poisson"], launches["refused"][1]))
@@ -396,6 +415,15 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         return kind
 
     kind, refuse = _check_members("optimize_newton_ensemble", problems, states, describe)
+
+    def keep_krylov():
+        """form 'auto' that needs the batched launches does not drop the option silently (known from the shapes alone
+        before the operators are probed, from the route's refusal after)."""
+        if launches["needed"] and krylov != "never":
+            refuse(launches["why"][0], "{}; the batched launches that serve such members have no hand-over to GCR (krylov "
+                   "'{}')".format(launches["why"][1], krylov))
+
+    keep_krylov()
     evaluators = []
     for problem, state in zip(problems, states):
         problem.recognise(state)
@@ -404,29 +432,50 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
     route = "stencil" if any(ev is None for ev in evaluators) else "poisson"
     if form == "auto" and refused[route] is not None and launches["refused"] is None:
         launches["needed"] = True  # (the one-workgroup route these operators take refuses a member)
+        launches["why"] = launches["why"] or refused[route]
+    keep_krylov()
     if launches["needed"]:
         route = "stencil"
     elif refused[route] is not None:
         refuse(*refused[route])
     ran = "launches" if launches["needed"] else "workgroup"
+    options = dict()  # (of the solver's constructor)
+    if krylov != "never":
+        options["krylov"] = krylov
+        reason = _krylov_memory_refusal(len(problems), kind["cshape"], kind["dtype"], kind["device"], gmg.EnsembleGMG.krylov_m)
+        if reason is not None:
+            raise ValueError("optimize_newton_ensemble: " + reason)
     if route == "poisson":  # (one launch per epoch: the whole Newton step on the packed iterate and right-hand sides)
         ev = evaluators[0]
-        solver = gmg.EnsembleGMG(ev.cshape, ev.h2, ev.dtype, ev.device, len(evaluators))
+        solver = gmg.EnsembleGMG(ev.cshape, ev.h2, ev.dtype, ev.device, len(evaluators), **options)
         rhs = torch.stack([e.rhs.reshape(ev.cshape) for e in evaluators])
 
         def step(u, first, tol, maxcycles):  # (no linearisation: nothing to report)
             solver.newton_step(u, rhs, tol=tol, maxcycles=maxcycles)
     else:
         solver, step = _stencil_route(args, problems, states, kind, linearize, time_linearize,
-                                      gmg.EnsembleLaunchGMG if ran == "launches" else gmg.EnsembleGMG)
+                                      gmg.EnsembleLaunchGMG if ran == "launches" else gmg.EnsembleGMG, options)
     return _newton_loop(args, problems, states, callback, linsolver, kind["dtype"], route, solver, step, ran)
 
 
-def _stencil_route(args, problems, states, kind, linearize="batched", timed=False, hierarchy=gmg.EnsembleGMG):
+def _krylov_memory_refusal(nbatch, cshape, dtype, device, m):
+    """Why the work memory that krylov='auto' adds -- B (2 m + 2) finest-level vectors: iterate, residual, m directions and
+    their images per member -- does not fit the free memory of `device`, or None."""
+    need = nbatch * (2 * m + 2) * math.prod(cshape) * torch.empty((), dtype=dtype).element_size()
+    if device is not None and torch.device(device).type == "cuda":
+        free = torch.cuda.mem_get_info(device)[0]
+        if need > free:
+            return "krylov 'auto' adds {} members x {} vectors x {} cells = {} bytes of work memory, {} bytes of device " \
+                   "memory are free".format(nbatch, 2 * m + 2, math.prod(cshape), need, free)
+    return None
+
+
+def _stencil_route(args, problems, states, kind, linearize="batched", timed=False, hierarchy=gmg.EnsembleGMG, options=None):
     """(solver, step) of the route for members that are not all the Poisson operator (the docstring of
     `optimize_newton_ensemble`); the members have passed its checks, `kind` is what they share.  Linearises once here,
     before any state changes: a member that has no stencil Jacobian is named first.  Without an epoch to run, no solver.
-    hierarchy: the class whose `from_coeffs` makes the solver (gmg.EnsembleGMG, or gmg.EnsembleLaunchGMG for form 'launches').
+    hierarchy: the class whose `from_coeffs` makes the solver (gmg.EnsembleGMG, or gmg.EnsembleLaunchGMG for form 'launches');
+    options: further keywords of it (krylov).
     step returns (Jacobian launches made, the pair of events around the linearisation or None)."""
     nb, cshape, dtype, device = len(problems), kind["cshape"], kind["dtype"], kind["device"]
     ndim = len(cshape)
@@ -467,7 +516,7 @@ def _stencil_route(args, problems, states, kind, linearize="batched", timed=Fals
     solver, first = None, None
     if args.epochs > args.epoch_start:
         first = linearise(stage)
-        solver = hierarchy.from_coeffs(stage)
+        solver = hierarchy.from_coeffs(stage, **(options or dict()))
     del stage
 
     def step(u, is_first, tol, maxcycles):
@@ -653,6 +702,7 @@ def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solv
 
     nepochs = max(args.epochs - args.epoch_start, 0)
     cycles = np.zeros((nb, nepochs), dtype=np.int64)
+    handover = np.full((nb, nepochs), -1, dtype=np.int64)
     residuals = np.zeros((nb, nepochs))
     launches, events = np.zeros(nepochs, dtype=np.int64), []
     next_active = getattr(callback, "next_active", None) if callback else None
@@ -667,6 +717,8 @@ def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solv
             launches[k] = made[0]
             events.append(made[1])
         cycles[:, k] = solver.outcome[:, 0]
+        if solver.outcome.shape[1] > 2:  # (a solver with the hand-over to GCR: the cycle it happened before, or -1)
+            handover[:, k] = solver.outcome[:, 2]
         residuals[:, k] = [solver.status(b)["residual"] for b in range(nb)]
         if getattr(args, "linsolver_verbose", 0):
             util.printlog([solver.status(b) for b in range(nb)])
@@ -679,4 +731,5 @@ def _newton_loop(args, problems, states, callback, linsolver, dtype, route, solv
         torch.cuda.synchronize()
         linearize_ms = np.array([pair[0].elapsed_time(pair[1]) for pair in events])
     return arrays, argparse.Namespace(epochs=args.epochs, evals=nepochs, cycles=cycles, residuals=residuals, solver=solver,
-                                      route=route, form=form, linearize_launches=launches, linearize_ms=linearize_ms)
+                                      route=route, form=form, linearize_launches=launches, linearize_ms=linearize_ms,
+                                      handover=handover)

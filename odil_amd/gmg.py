@@ -673,18 +673,25 @@ class EnsembleGMG:
 
     However it was made, an object has these attributes (`core`; `solve`, `newton_step`, `status` and the drivers of
     ensemble.py rely on nothing else):
-        nbatch, dtype, device, ndim, shapes, locs, halve, coeffs, inv, wpre, wpost, nu1, nu2, cells, work, method
+        nbatch, dtype, device, ndim, shapes, locs, halve, coeffs, inv, wpre, wpost, nu1, nu2, cells, work, method, krylov
     shapes: the levels, fine to coarse; halve / locs: per transition the axes that are halved, as booleans / as 'c' and
     '.'; coeffs: the operators of all levels, flat [ncoeff] when the members share them, else [B, ncoeff]; inv: the
     coarsest inverse [n, n] or [B, n, n]; wpre / wpost: the weights of the nu1 / nu2 sweeps before / after the coarse
     correction; cells: of the finest level; work: [B, need] scratch of the launch; method: what `status` reports.
-    Only an object made by `from_coeffs` has `fine`, `level` and `rebuild` (ValueError on the others)."""
+    Only an object made by `from_coeffs` has `fine`, `level` and `rebuild` (ValueError on the others).
+
+    krylov: "never" (the default) -- a member whose cycles stop contracting ends with converged=False or stagnated; "auto"
+    -- such a member is handed to GCR(krylov_m) around the same cycle INSIDE the launch (odil_stencil_solve_krylov_batch,
+    the hand-over rule of `PoissonGMG.solve`), still one launch and one read-back per solve; `work` grows by
+    (2 krylov_m + 2) finest-level vectors per member.  A member that never meets the rule gets the bits of "never".
+    `status` reports the cycle of the hand-over; `outcome` is [B, 3] then (passes, stop reason, hand-over cycle or -1)."""
 
     max_cells = 32768    # cells of a member's finest level (32^3, 128^2, 1-D up to 32768)
     max_levels = 8       # kTailMaxLev of csrc/vcycle_tail.hip
     max_coarsest = 512   # unknowns of the coarsest level (its dense inverse is applied by one workgroup)
     core = ("nbatch", "dtype", "device", "ndim", "shapes", "locs", "halve", "coeffs", "inv", "wpre", "wpost", "nu1", "nu2",
-            "cells", "work", "method")
+            "cells", "work", "method", "krylov")
+    krylov, krylov_m = "never", 6  # (what an object has that was made without the keywords)
 
     @classmethod
     def plan(cls, shape, h2, npdt, min_size=None):
@@ -699,8 +706,10 @@ class EnsembleGMG:
                 shapes, h2s, locs = poisson_hierarchy(shape, h2, npdt, min_size)
         return shapes, h2s, locs, min_size
 
-    def __init__(self, shape, h2=None, dtype=None, device=None, nbatch=None, min_size=None, nu1=None, nu2=None):
+    def __init__(self, shape, h2=None, dtype=None, device=None, nbatch=None, min_size=None, nu1=None, nu2=None,
+                 krylov="never", krylov_m=6):
         self._strength = None  # (the scratch of the set-up launches: only `from_coeffs` objects have one)
+        self._set_krylov(krylov, krylov_m)
         if torch.is_tensor(shape):
             self.method = "gmg-vcycle (variable coefficients), one workgroup per member"
             self._init_coeffs(shape, nu1, nu2, 2 if min_size is None else min_size)
@@ -728,8 +737,15 @@ class EnsembleGMG:
         self.nu1, self.nu2, self.wpre, self.wpost = first.nu1, first.nu2, first.weights(first.nu1), first.weights(first.nu2)
         self._finish([tuple(s) for s in first.shapes], [[c == "c" for c in loc] for loc in first.locs], coeffs, inv)
 
+    def _set_krylov(self, krylov, krylov_m):
+        if krylov not in ("never", "auto"):
+            raise ValueError("EnsembleGMG: krylov '{}' is neither 'never' nor 'auto'".format(krylov))
+        if not 1 <= int(krylov_m) <= 8:
+            raise ValueError("EnsembleGMG: krylov_m = {} (1..8 directions)".format(krylov_m))
+        self.krylov, self.krylov_m = krylov, int(krylov_m)
+
     @classmethod
-    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2):
+    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2, krylov="never", krylov_m=6):
         """One variable-coefficient operator per member, coeffs [B, 2 d + 1, *shape]: level by level what
         `StencilGMG(coeffs[b])` builds for every member -- coefficient arrays and coarsest pseudo-inverse bit for bit -- in
         launches whose number does not depend on B: per level ONE strength launch and one read-back of [B, 2 d] (the
@@ -737,7 +753,7 @@ class EnsembleGMG:
         for the dense coarsest matrices and one read-back; the pseudo-inverses are `StencilGMG.invert` per member on the
         host in float64.  The kernel walks one set of shapes: every member must take member 0's decision on every level,
         else ValueError (no object is made).  Coarsening stops under StencilGMG's rule or at `max_levels` levels."""
-        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size)
+        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size, krylov=krylov, krylov_m=krylov_m)
 
     def _init_coeffs(self, coeffs, nu1, nu2, min_size):
         nb, ndim = int(coeffs.shape[0]), coeffs.dim() - 2
@@ -770,7 +786,10 @@ class EnsembleGMG:
 
     def _work_elements(self, shapes):
         """Work elements per member of the launch that walks these levels; ValueError when one workgroup does not."""
-        need = ops.stencil_solve_batch_work(shapes)
+        if self.krylov == "auto":
+            need = ops.stencil_solve_krylov_batch_work(shapes, self.krylov_m)
+        else:
+            need = ops.stencil_solve_batch_work(shapes)
         if not need or len(shapes) > self.max_levels or math.prod(shapes[-1]) > self.max_coarsest:
             raise ValueError("EnsembleGMG: levels {} are not walked by one workgroup (at most {} levels, a coarsest level "
                              "of at most {} unknowns)".format(shapes, self.max_levels, self.max_coarsest))
@@ -785,10 +804,14 @@ class EnsembleGMG:
         self.locs = ["".join("c" if on else "." for on in halve) for halve in halves]
         self.coeffs, self.inv, self.cells = coeffs, inv, math.prod(shapes[0])
         self.work = torch.empty((self.nbatch, need), dtype=self.dtype, device=self.device)
-        self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
-                                                    self.wpre, self.wpost)
+        if self.krylov == "auto":
+            self._launch = ops.stencil_solve_krylov_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work,
+                                                               self.inv, self.wpre, self.wpost, self.krylov_m)
+        else:
+            self._launch = ops.stencil_solve_batch_plan(self.coeffs, self.shapes, self.halve, self.nbatch, self.work, self.inv,
+                                                        self.wpre, self.wpost)
         self._out = dict()      # maxcycles -> (history, outcome) device tensors
-        self.history = None     # [B, maxcycles + 2], [B, 2] of the last launch on the host
+        self.history = None     # [B, maxcycles + 2], [B, 2] ("auto": [B, 3]) of the last launch on the host
         self.outcome = None
         missing = [name for name in self.core if not hasattr(self, name)]
         assert not missing, "EnsembleGMG lacks {}".format(missing)
@@ -885,7 +908,7 @@ class EnsembleGMG:
         if out is None:
             out = self._out[maxcycles] = (
                 torch.zeros((self.nbatch, maxcycles + 2), dtype=torch.float64, device=self.device),
-                torch.zeros((self.nbatch, 2), dtype=torch.int32, device=self.device))
+                torch.zeros((self.nbatch, 3 if self.krylov == "auto" else 2), dtype=torch.int32, device=self.device))
         self._launch(x, b, out[0], out[1], start, mode, maxcycles, tol)
         # ONE read-back per solve of the whole ensemble, after the launch
         self.history, self.outcome = out[0].cpu().numpy(), out[1].cpu().numpy()
@@ -901,13 +924,16 @@ class EnsembleGMG:
         return self._run(u, rhs, tol, maxcycles, start, 1)
 
     def status(self, member):
-        """What `PoissonGMG.solve` reports, for one member of the last launch."""
-        k, why = (int(v) for v in self.outcome[member])
+        """What `PoissonGMG.solve` reports, for one member of the last launch; handover: the cycle before which the member
+        went on with GCR (None: it never did).  Stop reason 4, a breakdown of GCR: converged=False, stagnated=False."""
+        k, why = (int(v) for v in self.outcome[member][:2])
+        handover = int(self.outcome[member][2]) if self.outcome.shape[1] > 2 and self.outcome[member][2] >= 0 else None
         hist = self.history[member]
         res = math.sqrt(max(float(hist[1 + k]), 0.0) * self.cells) if hist[1 + k] == hist[1 + k] else float("nan")
         bn = math.sqrt(max(float(hist[0]), 0.0) * self.cells) if hist[0] == hist[0] else float("nan")
         return dict(residual=res, bnorm=bn, niter=k, converged=why == 0, stagnated=bool(why == 2 and res < bn),
-                    method=self.method)
+                    method=self.method if handover is None else "{} + GCR({})".format(self.method, self.krylov_m),
+                    handover=handover)
 
 
 def mean_children(r, loc, out=None):
@@ -962,15 +988,21 @@ class EnsembleLaunchGMG(EnsembleGMG):
     not depend on nbatch, on its position, or on when other members stop.
 
     Attributes as `EnsembleGMG.core`; besides: nlaunch (number of launch levels), tail_shapes.  `newton_step` is not
-    served (the Newton driver solves M d = f and updates on its own)."""
+    served (the Newton driver solves M d = f and updates on its own).  The hand-over to GCR of `EnsembleGMG(krylov="auto")`
+    is out of scope in this form: the iterate of a member lives across launches here, and a Krylov wrapper around them is
+    not built -- krylov other than "never" raises ValueError."""
 
     tail_max_cells = EnsembleGMG.max_cells  # levels of at most this many cells go to the one-workgroup tail (never the finest)
     method_name = "gmg-vcycle (variable coefficients), batched launches"
     max_member_cells = 1 << 24  # (the member is a grid dimension of the batched launches: their limit per member)
     pair_min_cells = 1 << 20  # launch levels on which ALL members together have at least this many cells smooth in pairs (odil_stencil_var_smooth2_batch); math.inf: single sweeps only.  Measured (DESIGN section 5): the largest of 2^18 ... 2^23 that loses on no row of the table
 
-    def __init__(self, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None):
+    def __init__(self, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None, krylov="never"):
+        if krylov != "never":
+            raise ValueError("EnsembleLaunchGMG: krylov '{}' (the batched launches have no hand-over to GCR: 'never' "
+                             "only)".format(krylov))
         self._strength = None
+        self._set_krylov("never", 6)
         self.method = self.method_name
         if tail_max_cells is not None:
             self.tail_max_cells = int(tail_max_cells)
@@ -981,9 +1013,9 @@ class EnsembleLaunchGMG(EnsembleGMG):
         self._init_coeffs(coeffs, nu1, nu2, min_size)
 
     @classmethod
-    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None):
-        """coeffs [B, 2 d + 1, *shape]; tail_max_cells: None for the class's."""
-        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size, tail_max_cells=tail_max_cells)
+    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None, krylov="never"):
+        """coeffs [B, 2 d + 1, *shape]; tail_max_cells: None for the class's; krylov: 'never' (else ValueError)."""
+        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size, tail_max_cells=tail_max_cells, krylov=krylov)
 
     @classmethod
     def split(cls, shapes, tail_max_cells=None):

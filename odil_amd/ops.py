@@ -458,6 +458,14 @@ def stencil_solve_batch_work(shapes):
     return int(_lib.load().odil_stencil_solve_batch_work(i64(flat), c_int(len(shapes)), c_int(len(shapes[0]))))
 
 
+def stencil_solve_krylov_batch_work(shapes, m):
+    """Work elements per member of `stencil_solve_krylov_batch_plan` with m directions: `stencil_solve_batch_work` plus
+    (2 m + 2) finest-level vectors (0: malformed shapes, or m outside 1..8)."""
+    flat = [int(n) for shape in shapes for n in shape]
+    return int(_lib.load().odil_stencil_solve_krylov_batch_work(i64(flat), c_int(len(shapes)), c_int(len(shapes[0])),
+                                                                 c_int(int(m))))
+
+
 def _member_stride(t, need, shared_ok=False):
     """Elements between the members of a packed tensor [B, ...] whose members are contiguous (0: one member shared by all)."""
     if shared_ok and t.dim() == 1:
@@ -473,12 +481,12 @@ def _base_ptr(t):
     return c_void_p(t.data_ptr())
 
 
-def stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpost):
+def stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpost, krylov_m=None):
     """`stencil_solve_batch` with everything that does not change between calls prepared once (as
     `stencil_vcycle_tail_plan`): -> launch(x, b, history, outcome, start, mode, maxcycles, tol).
     coeffs: flat [ncoeff] (one operator for all members) or [B, ncoeff]; inv: [n, n] or [B, n, n]; work: [B, >= need];
     x, b: [B, *shape] with contiguous members (any leading stride); history: [B, >= maxcycles + 2] float64; outcome:
-    [B, 2] int32."""
+    [B, 2] int32.  krylov_m: `stencil_solve_krylov_batch_plan`."""
     import ctypes
 
     nlev, ndim = len(shapes), len(shapes[0])
@@ -488,7 +496,7 @@ def stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpo
     maskp = ctypes.cast(mask, ctypes.c_void_p)
     wa, wap = host_reals(list(wpre) or [0.0], coeffs.dtype)
     wb, wbp = host_reals(list(wpost) or [0.0], coeffs.dtype)
-    need = stencil_solve_batch_work(shapes)
+    need = stencil_solve_batch_work(shapes) if krylov_m is None else stencil_solve_krylov_batch_work(shapes, krylov_m)
     ncoeff = (2 * ndim + 1) * sum(math.prod(s) for s in shapes)
     cstride = _member_stride(coeffs, ncoeff, shared_ok=True)
     istride = 0 if inv.dim() == 2 else _member_stride(inv, ninv * ninv)
@@ -503,18 +511,29 @@ def stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpo
            c_int(len(wpre)), wbp, c_int(len(wpost)))
     keep = (coeffs, work, inv, mask, wa, wb, shapes64)  # (the arrays the pointers point into)
     dtype = coeffs.dtype
+    entry, columns = ("stencil_solve_batch", 2) if krylov_m is None else ("stencil_solve_krylov_batch", 3)
+    tail = () if krylov_m is None else (c_int(int(krylov_m)),)
 
     def launch(x, b, history, outcome, start=2, mode=0, maxcycles=60, tol=0.0):
         assert x.dtype == b.dtype == dtype and x.shape[0] == b.shape[0] == nbatch
         assert history.dtype == torch.float64 and history.shape[0] == nbatch and history.is_contiguous()
-        assert outcome.dtype == torch.int32 and tuple(outcome.shape) == (nbatch, 2) and outcome.is_contiguous()
-        call("stencil_solve_batch", dtype, *head, _base_ptr(x), c_int64(_member_stride(x, cells)),
+        assert outcome.dtype == torch.int32 and tuple(outcome.shape) == (nbatch, columns) and outcome.is_contiguous()
+        call(entry, dtype, *head, _base_ptr(x), c_int64(_member_stride(x, cells)),
              _base_ptr(b), c_int64(_member_stride(b, cells)), *mid, c_int(start), c_int(mode), c_int(maxcycles),
-             float(tol), ptr(history), c_int64(history.shape[1]), ptr(outcome), stream_ptr())
+             float(tol), ptr(history), c_int64(history.shape[1]), ptr(outcome), *tail, stream_ptr())
         return x
 
     launch.keep = keep
     return launch
+
+
+def stencil_solve_krylov_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpost, m=6):
+    """`stencil_solve_batch_plan` for odil_stencil_solve_krylov_batch: a member whose cycles stop contracting goes on with
+    GCR(m) around the same cycle inside the launch.  work: [B, >= stencil_solve_krylov_batch_work(shapes, m)]; outcome:
+    [B, 3] int32 (passes, stop reason -- 4: breakdown of GCR --, the cycle of the hand-over or -1)."""
+    if not 1 <= int(m) <= 8:
+        raise ValueError("stencil_solve_krylov_batch_plan: m = {} (1..8 directions)".format(m))
+    return stencil_solve_batch_plan(coeffs, shapes, halve, nbatch, work, inv, wpre, wpost, krylov_m=int(m))
 
 
 def stencil_solve_batch(coeffs, shapes, halve, x, b, work, inv, wpre, wpost, history, outcome, start=2, mode=0, maxcycles=60,
