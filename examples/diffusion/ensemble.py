@@ -15,7 +15,9 @@ decision on the device (`gmg.EnsembleLaunchGMG`); `--form auto` takes it only wh
 (`--velocity_from V0`: v_b = V0 + (V - V0) (b + 1) / B) swept over the members like the conductivity amplitude (the Jacobian stays a (2 d + 1)-point stencil); the members of an
 ensemble walk one set of levels, so V is chosen where they coarsen alike (e.g. `--N 8 --ndim 3 --velocity 800 --members 4`:
 v = 200 ... 800), and a refusal is printed as it is.  `--krylov auto` hands a member whose cycles stop contracting to GCR(6)
-inside the solve launch (`optimize_newton_ensemble(krylov="auto")`); `--krylov never` reports it as not converged.
+inside the solve launch (`optimize_newton_ensemble(krylov="auto")`); `--krylov any` does so in whichever form runs the
+members, with `--form launches` across the batched launches (`gmg.EnsembleLaunchKrylovGMG`); `--krylov never` reports it as
+not converged.
 `--alternate R` times the ensemble and the single runs R more times, alternating in one process, and prints min - max.
 
 `--optimizer adam` runs the same sweep with Adam (`odil.util.optimize_ensemble(form="auto")`, its route for traced stencil
@@ -89,8 +91,9 @@ def parse_args(argv=None):
                      help="Upwind convection - v du/dx_0, v swept over the members up to this value (0: none)")
     own.add_argument("--velocity_from", type=float, default=0.0,
                      help="The sweep of v starts above this value: v_b = from + (V - from) (b + 1) / B")
-    own.add_argument("--krylov", type=str, default="never", choices=("never", "auto"),
-                     help="Newton: hand a member whose cycles stop contracting to GCR inside the solve launch")
+    own.add_argument("--krylov", type=str, default="never", choices=("never", "auto", "any"),
+                     help="Newton: hand a member whose cycles stop contracting to GCR inside the solve launch (auto: --form "
+                          "workgroup only) or in whichever form runs the members (any: also across the batched launches)")
     own.add_argument("--alternate", type=int, default=0,
                      help="Newton: after the report, time the ensemble and the single runs alternating this many times")
     own.add_argument("--repeat", type=int, default=3, help="--optimizer adam: timed repetitions of the ensemble and the single runs")
@@ -320,8 +323,8 @@ def main():
     lines = ["{} converged members of {}".format(sum(bool(st["converged"]) for st in status), args.members)]
     if args.krylov != "never":
         handed = [int(st["handover"]) for st in status if st.get("handover") is not None]
-        lines.append("{} members handed to GCR inside the launch{}".format(
-            len(handed), " (before cycles {} ... {})".format(min(handed), max(handed)) if handed else ""))
+        lines.append("{} members handed to GCR {}{}".format(
+            len(handed), "inside the launch" if optinfo.form == "workgroup" else "across the launches", " (before cycles {} ... {})".format(min(handed), max(handed)) if handed else ""))
     if status and (args.velocity or args.krylov != "never"):
         lines.append("passes per member: {} ... {}".format(min(st["niter"] for st in status), max(st["niter"] for st in status)))
     if together is not None:

@@ -885,6 +885,73 @@ int odil_stencil_solve_krylov_batch_f32(const float* coeffs, int64_t coeff_strid
                                         double* history, int64_t history_stride, int* outcome, int krylov_m, void* stream);
 /* work elements per member of odil_stencil_solve_krylov_batch; 0 if the shapes are malformed or krylov_m is not 1..8 */
 int64_t odil_stencil_solve_krylov_batch_work(const int64_t* shapes, int nlev, int ndim, int krylov_m);
+/* The KRYLOV HAND-OVER for members too large for one workgroup (gmg.EnsembleLaunchKrylovGMG): GCR(krylov_m) around the
+ * batched cycle of odil_stencil_var_smooth_batch and its companions, run ACROSS launches in lock-step -- pass k is the same
+ * pass for every member -- with every decision on the device.  Decision order, pass algebra and stop reasons are those of
+ * odil_stencil_solve_krylov_batch above; conventions those of the batched cycle: the member on blockIdx.y, strides in
+ * ELEMENTS and >= one member, nbatch 1..65535, malformed arguments refused before any launch, mask[b] == 0: the workgroups
+ * of member b return before any load or store; no workgroup waits for, signals or reads what another one of the same
+ * launch writes (no grid barrier, no counter, no atomic).  Products and norms: accumulated in double per workgroup of
+ * 1024 consecutive cells, workgroup p of member b leaving quantity j in gpart[b gpart_stride + j P + p] with P =
+ * odil_stencil_gcr_batch_parts(cells) (a function of the cells alone; 0: cells outside 1..2^24); the decision adds the P
+ * sums in a fixed order (thread t the sums t, t + 256, ..., then lanes, then waves).  gpart_stride >= (krylov_m + 2) P.
+ *   store     [nbatch, 2 krylov_m, cells]: per member the directions Z (rows 0 .. m - 1) and their images Q (rows m ..).
+ *             The pass k works in the rows slot = k mod krylov_m: before it the cycle has written e into row slot and
+ *             odil_stencil_var_smooth_batch in mode 1 with b = 0 t = -A e into row m + slot; the sign is taken on reading.
+ *             The j-th oldest of the have[b] kept directions is in the rows (slot - have[b] + j) mod krylov_m.
+ *   have      DEVICE int[nbatch]; max_have: the host's bound 0..krylov_m on it (a larger entry is cut; the row of the pass
+ *             itself is never read as a kept one).  scal: DEVICE double[nbatch, >= krylov_m + 2]: beta_j, 1 / |q'|, a.
+ *   dots      quantity j = <Q_j, q> for j < have[b], q = -t: one pass over q (max_have == 0: nothing to do)
+ *   project   q' = q - sum_j beta_j Q_j, z' = e - sum_j beta_j Z_j, in place in the rows of the pass (classical
+ *             Gram-Schmidt: every beta from the un-projected q); quantities m, m + 1 = <q', q'>, <q', rho>
+ *   update    q = q' scal[m], z = z' scal[m] in place, x += scal[m + 1] z, rho -= scal[m + 1] q; quantity 0 = <rho, rho>
+ *   sumsq     quantity 0 = <v, v> (the true residual of a member to verify)
+ *   decide    one workgroup per member, double / int only; state: active (the stationary members: the mask of the base
+ *             cycle), gcr, fresh (rho = b - A x is to be formed, have = 0), verify, have -- DEVICE int[nbatch] each.
+ *             mode 0, before pass k.  Stationary member: odil_stencil_cycle_decide_batch on `partials` with the HAND-OVER
+ *               in the order of odil_stencil_solve_krylov_batch: active = 0, gcr = fresh = 1, have = 0, outcome[b, 2] = k.
+ *               GCR member: history[b, 1 + k] = quantity 0 / cells, then 3 non-finite; recurrence <= tol^2 history[b, 0]:
+ *               verify = fresh = 1, gcr = 0, have = 0; 1 k == maxcycles; have == krylov_m: have = 0.
+ *             mode 1: scal[b, j] = the products of `dots`; fresh = 0.
+ *             mode 2: |q'|^2 = quantity m zero or non-finite: 4 BREAKDOWN, outcome (k, 4), gcr = 0 -- before `update`
+ *               touches the iterate; else scal[b, m] = 1 / |q'|, scal[b, m + 1] = quantity (m + 1) / |q'|, have += 1.
+ *             mode 3, a member to verify: history[b, 1 + k] = quantity 0 / cells of the true residual; 3 non-finite,
+ *               0 converged, 1 k == maxcycles, else gcr = 1 with no directions; verify = fresh = 0.
+ *             outcome: [nbatch, 3] (passes, reason, hand-over cycle or -1).  After modes 0 and 3 a one-workgroup launch
+ *             writes counts[0 .. 3] = members with active, gcr, verify, fresh set.
+ * (No reference counterpart: the reference solves one system at a time, linsolver.py:17-26, 61-72.) */
+int64_t odil_stencil_gcr_batch_parts(int64_t cells);
+int odil_stencil_gcr_dots_batch_f64(const double* store, int64_t store_stride, int64_t cells, int krylov_m, int slot,
+                                    const int* have, int max_have, const int* mask, int nbatch, double* gpart,
+                                    int64_t gpart_stride, void* stream);
+int odil_stencil_gcr_dots_batch_f32(const float* store, int64_t store_stride, int64_t cells, int krylov_m, int slot,
+                                    const int* have, int max_have, const int* mask, int nbatch, double* gpart,
+                                    int64_t gpart_stride, void* stream);
+int odil_stencil_gcr_project_batch_f64(double* store, int64_t store_stride, const double* rho, int64_t rho_stride,
+                                       int64_t cells, int krylov_m, int slot, const int* have, int max_have,
+                                       const double* scal, int64_t scal_stride, const int* mask, int nbatch, double* gpart,
+                                       int64_t gpart_stride, void* stream);
+int odil_stencil_gcr_project_batch_f32(float* store, int64_t store_stride, const float* rho, int64_t rho_stride, int64_t cells,
+                                       int krylov_m, int slot, const int* have, int max_have, const double* scal,
+                                       int64_t scal_stride, const int* mask, int nbatch, double* gpart, int64_t gpart_stride,
+                                       void* stream);
+int odil_stencil_gcr_update_batch_f64(double* store, int64_t store_stride, double* x, int64_t x_stride, double* rho,
+                                      int64_t rho_stride, int64_t cells, int krylov_m, int slot, const double* scal,
+                                      int64_t scal_stride, const int* mask, int nbatch, double* gpart, int64_t gpart_stride,
+                                      void* stream);
+int odil_stencil_gcr_update_batch_f32(float* store, int64_t store_stride, float* x, int64_t x_stride, float* rho,
+                                      int64_t rho_stride, int64_t cells, int krylov_m, int slot, const double* scal,
+                                      int64_t scal_stride, const int* mask, int nbatch, double* gpart, int64_t gpart_stride,
+                                      void* stream);
+int odil_stencil_gcr_sumsq_batch_f64(const double* v, int64_t v_stride, int64_t cells, const int* mask, int nbatch,
+                                     double* gpart, int64_t gpart_stride, void* stream);
+int odil_stencil_gcr_sumsq_batch_f32(const float* v, int64_t v_stride, int64_t cells, const int* mask, int nbatch,
+                                     double* gpart, int64_t gpart_stride, void* stream);
+int odil_stencil_gcr_decide_batch(int mode, const double* partials, int64_t partials_stride, const double* partials0,
+                                  int64_t partials0_stride, int nparts, const double* gpart, int64_t gpart_stride, int gparts,
+                                  int nbatch, int64_t cells, int k, int maxcycles, double tol, int krylov_m, double* history,
+                                  int64_t history_stride, int* outcome, int* active, int* gcr, int* fresh, int* verify,
+                                  int* have, double* scal, int64_t scal_stride, int* counts, void* stream);
 /* Mixed-precision iterative refinement of the multigrid Newton solve (gmg.py; no reference counterpart -- the reference's
  * direct solver is double throughout): float32 V-cycles inside a float64 residual loop.  narrow_scale: y32 = s x64 with
  * s = a / sqrt(*msq) (msq: device scalar, the mean square the residual kernel just wrote; NULL: s = a); widen_axpy:

@@ -335,15 +335,21 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
     handed to GCR inside the launch (below), with krylov='never' its status reports converged=False or stagnated, and the
     caller decides.
 
-    krylov: 'never' (the default) or 'auto', on both routes: a member whose cycles contract by less than 0.5 well above
-    the tolerance (the rule of `gmg.PoissonGMG.solve`) goes on with GCR(6) around the same cycle inside the solve launch
+    krylov: 'never' (the default), 'auto' or 'any'.  'auto', on both routes: a member whose cycles contract by less than
+    0.5 well above the tolerance (the rule of `gmg.PoissonGMG.solve`) goes on with GCR(6) around the same cycle inside the solve launch
     (`gmg.EnsembleGMG(krylov="auto")`, odil_stencil_solve_krylov_batch) -- still one launch and one read-back per step;
     members that never meet the rule get the bits of 'never'.  Its work memory, B (2 m + 2) cells values more, must fit the
     free device memory: else ValueError naming the bytes, before any state changes.  optinfo.handover: [B, epochs], the
     cycle before which the member was handed over in that step, -1 where it was not; the member's status names it and
-    reports method "... + GCR(6)".  Only form 'workgroup' serves it: with form='launches', and with form='auto' when the
-    members need the batched launches, ValueError (naming the member and the reason).  Any other value raises ValueError
-    before any member is looked at.
+    reports method "... + GCR(6)".  Only form 'workgroup' serves 'auto': with form='launches', and with form='auto' when
+    the members need the batched launches, ValueError (naming the member and the reason).
+    krylov 'any': hand slow members over in whichever form runs them.  Where the one-workgroup form runs them it is 'auto'
+    in everything (the same launch, bits and status).  Where the batched launches run them (form='launches', or
+    form='auto' with members that need them) the solver is `gmg.EnsembleLaunchKrylovGMG`: the same decision order, pass
+    algebra and stop reasons in one lock-step loop of passes across the launches, every decision on the device, four ints
+    read back per pass; a handed-over member reports method "gmg-vcycle (variable coefficients), batched launches +
+    GCR(6)", members that never meet the rule keep the bits of 'never'.  The same work memory is checked the same way.
+    Any other value raises ValueError before any member is looked at.
 
     linearize (stencil route): "batched" is the above; "members" linearises member by member (`linearize_device`,
     `gmg.recognise_stencil`, copies into the packed buffers: B launches of `k_jac`) -- the same iterates, cycle counts and
@@ -368,9 +374,9 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
 
     if form not in ("workgroup", "launches", "auto"):
         raise ValueError("optimize_newton_ensemble: form '{}' is none of 'workgroup', 'launches', 'auto'".format(form))
-    if krylov not in ("never", "auto"):
-        raise ValueError("optimize_newton_ensemble: krylov '{}' is neither 'never' nor 'auto'".format(krylov))
-    if krylov != "never" and form == "launches":
+    if krylov not in ("never", "auto", "any"):
+        raise ValueError("optimize_newton_ensemble: krylov '{}' is neither 'never' nor 'auto' nor 'any'".format(krylov))
+    if krylov == "auto" and form == "launches":
         raise ValueError("optimize_newton_ensemble: krylov '{}' with form 'launches' (the hand-over to GCR runs inside the "
                          "one-workgroup solve launch: form 'workgroup')".format(krylov))
     linsolver = getattr(args, "linsolver", "direct")
@@ -419,7 +425,7 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
     def keep_krylov():
         """form 'auto' that needs the batched launches does not drop the option silently (known from the shapes alone
         before the operators are probed, from the route's refusal after)."""
-        if launches["needed"] and krylov != "never":
+        if launches["needed"] and krylov == "auto":
             refuse(launches["why"][0], "{}; the batched launches that serve such members have no hand-over to GCR (krylov "
                    "'{}')".format(launches["why"][1], krylov))
 
@@ -440,8 +446,12 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         refuse(*refused[route])
     ran = "launches" if launches["needed"] else "workgroup"
     options = dict()  # (of the solver's constructor)
+    hierarchy = gmg.EnsembleLaunchGMG if ran == "launches" else gmg.EnsembleGMG
     if krylov != "never":
-        options["krylov"] = krylov
+        if ran == "launches":  # (krylov 'any': the hand-over across the batched launches; 'auto' was refused above)
+            hierarchy = gmg.EnsembleLaunchKrylovGMG
+        else:
+            options["krylov"] = "auto"
         reason = _krylov_memory_refusal(len(problems), kind["cshape"], kind["dtype"], kind["device"], gmg.EnsembleGMG.krylov_m)
         if reason is not None:
             raise ValueError("optimize_newton_ensemble: " + reason)
@@ -453,8 +463,7 @@ def optimize_newton_ensemble(args, problems, states, callback=None, linearize="b
         def step(u, first, tol, maxcycles):  # (no linearisation: nothing to report)
             solver.newton_step(u, rhs, tol=tol, maxcycles=maxcycles)
     else:
-        solver, step = _stencil_route(args, problems, states, kind, linearize, time_linearize,
-                                      gmg.EnsembleLaunchGMG if ran == "launches" else gmg.EnsembleGMG, options)
+        solver, step = _stencil_route(args, problems, states, kind, linearize, time_linearize, hierarchy, options)
     return _newton_loop(args, problems, states, callback, linsolver, kind["dtype"], route, solver, step, ran)
 
 
@@ -474,7 +483,8 @@ def _stencil_route(args, problems, states, kind, linearize="batched", timed=Fals
     """(solver, step) of the route for members that are not all the Poisson operator (the docstring of
     `optimize_newton_ensemble`); the members have passed its checks, `kind` is what they share.  Linearises once here,
     before any state changes: a member that has no stencil Jacobian is named first.  Without an epoch to run, no solver.
-    hierarchy: the class whose `from_coeffs` makes the solver (gmg.EnsembleGMG, or gmg.EnsembleLaunchGMG for form 'launches');
+    hierarchy: the class whose `from_coeffs` makes the solver (gmg.EnsembleGMG; for form 'launches' gmg.EnsembleLaunchGMG or
+    gmg.EnsembleLaunchKrylovGMG);
     options: further keywords of it (krylov).
     step returns (Jacobian launches made, the pair of events around the linearisation or None)."""
     nb, cshape, dtype, device = len(problems), kind["cshape"], kind["dtype"], kind["device"]

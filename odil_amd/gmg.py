@@ -989,8 +989,8 @@ class EnsembleLaunchGMG(EnsembleGMG):
 
     Attributes as `EnsembleGMG.core`; besides: nlaunch (number of launch levels), tail_shapes.  `newton_step` is not
     served (the Newton driver solves M d = f and updates on its own).  The hand-over to GCR of `EnsembleGMG(krylov="auto")`
-    is out of scope in this form: the iterate of a member lives across launches here, and a Krylov wrapper around them is
-    not built -- krylov other than "never" raises ValueError."""
+    -- inside ONE launch -- is not served in this form: krylov other than "never" raises ValueError.  The subclass
+    `EnsembleLaunchKrylovGMG` hands slow members to GCR across the launches (`optimize_newton_ensemble(krylov="any")`)."""
 
     tail_max_cells = EnsembleGMG.max_cells  # levels of at most this many cells go to the one-workgroup tail (never the finest)
     method_name = "gmg-vcycle (variable coefficients), batched launches"
@@ -1083,10 +1083,7 @@ class EnsembleLaunchGMG(EnsembleGMG):
         self.nlaunch = first = self.split(shapes, self.tail_max_cells)
         self.tail_shapes = shapes[first:]
         self.work = torch.empty((nb, need), dtype=dtype, device=device)
-        sizes = [(2 * self.ndim + 1) * math.prod(s) for s in shapes]
-        tail_coeffs = coeffs[:, sum(sizes[:first]):sum(sizes)]
-        self._launch = ops.stencil_solve_batch_plan(tail_coeffs, self.tail_shapes, halves[first:], nb, self.work, inv,
-                                                    self.wpre, self.wpost)
+        self._plan_tail()
 
         def arrays(lvl):
             return torch.zeros((nb,) + shapes[lvl], dtype=dtype, device=device)
@@ -1111,6 +1108,14 @@ class EnsembleLaunchGMG(EnsembleGMG):
         missing = [name for name in self.core if not hasattr(self, name)]
         assert not missing, "EnsembleLaunchGMG lacks {}".format(missing)
 
+    def _plan_tail(self):
+        """The launch plan of the tail (odil_stencil_solve_batch) from the object's levels, weights and coarsest inverses."""
+        first = self.nlaunch
+        sizes = [(2 * self.ndim + 1) * math.prod(s) for s in self.shapes]
+        tail_coeffs = self.coeffs[:, sum(sizes[:first]):sum(sizes)]
+        self._launch = ops.stencil_solve_batch_plan(tail_coeffs, self.tail_shapes, self.halve[first:], self.nbatch, self.work,
+                                                    self.inv, self.wpre, self.wpost)
+
     def _tail_solve(self, start, maxcycles):
         """The tail's top level: x <- its nested-iteration start (start 2, maxcycles 0) or `maxcycles` cycles from zero
         (start 0), for every member, frozen ones included (their result is discarded)."""
@@ -1128,25 +1133,27 @@ class EnsembleLaunchGMG(EnsembleGMG):
         """`sweep_plan` on a level that pairs, else one launch per sweep (the cycle without the pair kernel)."""
         return sweep_plan(weights, first_single) if self.pair_eligible(lvl) else [(w,) for w in weights]
 
-    def _smooth(self, c, src, b, ws, dst, partials=None):
+    def _smooth(self, c, src, b, ws, dst, partials=None, mask=None):
         """One launch of the plan: a single sweep (with the partial sums, where asked for) or the one-pass pair."""
+        mask = self._active if mask is None else mask
         if len(ws) == 2:
-            ops.stencil_var_smooth2_batch(c, src, b, ws[0], ws[1], dst, active=self._active)
+            ops.stencil_var_smooth2_batch(c, src, b, ws[0], ws[1], dst, active=mask)
         else:
-            ops.stencil_var_smooth_batch(c, src, b, ws[0], dst, active=self._active, partials=partials)
+            ops.stencil_var_smooth_batch(c, src, b, ws[0], dst, active=mask, partials=partials)
 
-    def _cycle(self, lvl, x, b, zero=False, decide=None):
+    def _cycle(self, lvl, x, b, zero=False, decide=None, mask=None):
         """One cycle of every active member on launch level lvl, from x (zero: from the zero vector) into x.
         decide: called after the first pre-smoothing sweep, which then leaves its partial sums; True ends the cycle there.
+        mask: int32 [B], the members the launches serve (None: the active ones).
         Sweeps run in the launches of `sweep_plan` where the level pairs (bit-identical to single sweeps); every launch
         but the last one of the post-smoothing writes one of the two scratch arrays, never the one it reads."""
-        c, active = self.level(lvl), self._active
+        c, active = self.level(lvl), self._active if mask is None else mask
         scratch = self._s[lvl]
         cur = None if zero else x
         pre = self._launches(lvl, self.wpre, first_single=decide is not None)
         for j, ws in enumerate(pre):
             dst = scratch[j % 2]
-            self._smooth(c, cur, b, ws, dst, partials=self._partials if decide is not None and j == 0 else None)
+            self._smooth(c, cur, b, ws, dst, partials=self._partials if decide is not None and j == 0 else None, mask=active)
             cur = dst
             if decide is not None and j == 0 and decide():
                 return
@@ -1162,15 +1169,15 @@ class EnsembleLaunchGMG(EnsembleGMG):
             xc = self._tail_solve(0, 2 if twice else 1)
         else:
             xc = self._x[lvl + 1]
-            self._cycle(lvl + 1, xc, bc, zero=True)
+            self._cycle(lvl + 1, xc, bc, zero=True, mask=active)
             if twice:
-                self._cycle(lvl + 1, xc, bc)
+                self._cycle(lvl + 1, xc, bc, mask=active)
         ops.interp_add(xc, "." + self.locs[lvl], add=cur, out=other)  # x + P x_c
         cur, other = other, cur
         post = self._launches(lvl, self.wpost)
         for j, ws in enumerate(post):
             dst = x if j == len(post) - 1 else other
-            self._smooth(c, cur, b, ws, dst)
+            self._smooth(c, cur, b, ws, dst, mask=active)
             cur, other = dst, cur
 
     def _nested(self, b, x):
@@ -1222,6 +1229,131 @@ class EnsembleLaunchGMG(EnsembleGMG):
 
     def newton_step(self, u, rhs, tol=1e-10, maxcycles=60, start=2):
         raise ValueError("EnsembleLaunchGMG: newton_step is not served (solve M d = f with `solve`, then update)")
+
+
+class EnsembleLaunchKrylovGMG(EnsembleLaunchGMG):
+    """`EnsembleLaunchGMG` with the hand-over of `EnsembleGMG(krylov="auto")`: a member whose cycles stop contracting goes
+    on with GCR(krylov_m) around the same batched cycle, ACROSS the launches, every decision on the device
+    (odil_stencil_gcr_*_batch; decision order, pass algebra and stop reasons: odil_stencil_solve_krylov_batch).
+
+    One lock-step loop of passes; pass k is the same pass for all members.  A member is STATIONARY (the base class's cycle,
+    launch for launch, under the mask `active`), in GCR (after its hand-over) or stopped.  Per pass:
+      the first pre-smoothing sweep of the stationary members, then the decision (mode 0): a stationary member under the
+        base class's rules plus the HAND-OVER -- it keeps x_k, since only the masked last post-smoothing sweep writes x --
+        and a GCR member on the mean(rho^2) its last pass left as history[1 + k];
+      the rest of the stationary cycle;
+      the host reads FOUR ints (stationary, GCR, to verify, rho to form; copied while the cycle runs) and enqueues only
+        the sequences that have members: rho = b - A x for the members handed over or to verify; the true residual's norm
+        and the decision of the members to verify (mode 3: converged only on the TRUE residual, else GCR restarts from it);
+        the GCR sequence: e = one cycle from the zero start on rho under the mask `gcr` (the base class's launches on the
+        same scratch), t = 0 - A e, the products with the kept Q_j, the betas (mode 1), the projection of (q, z), the
+        scaling 1 / |q| and a = <q, rho> or the BREAKDOWN (mode 2), then x += a z, rho -= a q.
+    Pass k works in the rows k mod krylov_m of the store [B, 2 krylov_m, cells]: the cycle writes e and the residual
+    launch t straight into them, the projection and the scaling run in place.  After krylov_m passes the directions are
+    dropped.  The tail launch and `interp_add` cannot skip members: what they compute for masked-out members lands in
+    scratch and is discarded.  The loop runs at most maxcycles + 1 passes.  An ensemble in which no member hands over makes
+    the launches of `EnsembleLaunchGMG` (with the wider decision kernel) and nothing more: x, history and (passes, reason)
+    are its bits.  A member's bits do not depend on nbatch, its position, or what other members do.
+
+    krylov == "auto" as an attribute: `status` and the [B, 3] `outcome` (passes, reason, hand-over cycle or -1) of
+    `EnsembleGMG` apply unchanged.  Work memory: (2 krylov_m + 2) finest-level vectors per member (store, rho, and a zero
+    vector).  (`_set_cycle` is a hook of the tests.)"""
+
+    def __init__(self, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None, krylov_m=6):
+        if not 1 <= int(krylov_m) <= 8:
+            raise ValueError("EnsembleLaunchKrylovGMG: krylov_m = {} (1..8 directions)".format(krylov_m))
+        self._m = int(krylov_m)
+        super().__init__(coeffs, nu1=nu1, nu2=nu2, min_size=min_size, tail_max_cells=tail_max_cells)
+        self.krylov, self.krylov_m = "auto", self._m
+
+    @classmethod
+    def from_coeffs(cls, coeffs, nu1=None, nu2=None, min_size=2, tail_max_cells=None, krylov_m=6):
+        """coeffs [B, 2 d + 1, *shape]; tail_max_cells: None for the class's; krylov_m: 1..8 directions (else ValueError)."""
+        return cls(coeffs, nu1=nu1, nu2=nu2, min_size=min_size, tail_max_cells=tail_max_cells, krylov_m=krylov_m)
+
+    def _finish(self, shapes, halves, coeffs, inv):
+        super()._finish(shapes, halves, coeffs, inv)
+        self._gcr = ops.GcrBatch(self.nbatch, shapes[0], self._m, self.dtype, self.device, self._active)
+
+    def _set_cycle(self, wpre=None, wpost=None, inv=None):
+        """A TEST HOOK, not part of the supported surface: other sweep weights (as many as before) and / or coarsest
+        inverses [B, n, n] for every later cycle -- how a test makes the cycle return nothing (weights 0, inverse 0) to
+        reach the breakdown of GCR with a numerical input.  ValueError for another number of weights or another shape."""
+        for name, new, old in (("wpre", wpre, self.wpre), ("wpost", wpost, self.wpost)):
+            if new is not None and len(new) != len(old):
+                raise ValueError("EnsembleLaunchKrylovGMG._set_cycle: {} weights for {} ({} sweeps)".format(
+                    len(new), name, len(old)))
+        if inv is not None and tuple(inv.shape) != tuple(self.inv.shape):
+            raise ValueError("EnsembleLaunchKrylovGMG._set_cycle: inverses {} (the object's: {})".format(
+                tuple(inv.shape), tuple(self.inv.shape)))
+        if wpre is not None:
+            self.wpre = [float(w) for w in wpre]
+        if wpost is not None:
+            self.wpost = [float(w) for w in wpost]
+        if inv is not None:
+            self.inv.copy_(inv)
+        self._plan_tail()
+        return self
+
+    def solve(self, b, x, tol=1e-10, maxcycles=60, start=2):
+        """`EnsembleGMG.solve`: A_b x_b = b_b for every member, in place in x [B, *shape] (contiguous, as b)."""
+        assert tuple(x.shape) == tuple(b.shape) == (self.nbatch,) + self.shapes[0], (x.shape, b.shape)
+        assert x.is_contiguous() and b.is_contiguous() and x.dtype == b.dtype == self.dtype and start in (0, 1, 2)
+        out = self._out.get(maxcycles)
+        if out is None:
+            out = self._out[maxcycles] = (
+                torch.zeros((self.nbatch, maxcycles + 2), dtype=torch.float64, device=self.device),
+                torch.zeros((self.nbatch, 3), dtype=torch.int32, device=self.device))
+        history, outcome = out
+        g, m, fine = self._gcr, self._m, self.level(0)
+        self._active.fill_(1)
+        g.reset()
+        outcome[:, 2].fill_(-1)
+        if start == 0:
+            x.zero_()
+            bsq = self._partials
+        else:
+            if start == 2:
+                self._nested(b, x)
+            bsq = self._partials0
+            ops.stencil_var_smooth_batch(fine, None, b, 1.0, self._s[0][0], partials=bsq)
+        nstat = self.nbatch
+        for k in range(maxcycles + 1):
+            def decide():
+                g.decide(0, k, maxcycles, tol, history, outcome, self._partials, partials0=bsq if k == 0 else None)
+                g.counts_host.copy_(g.counts, non_blocking=True)
+                self._decided.record()
+                return k == maxcycles
+
+            if nstat:
+                self._cycle(0, x, b, zero=start == 0 and k == 0, decide=decide)
+            else:
+                decide()
+            self._decided.synchronize()  # (FOUR ints per pass; the stationary cycle is in flight meanwhile)
+            nstat, ngcr, nverify, nfresh = (int(v) for v in g.counts_host)
+            if nstat + ngcr + nverify == 0:
+                break
+            if nfresh:  # (handed over before this pass, or to verify)
+                ops.stencil_var_smooth_batch(fine, x, b, 0.0, g.rho, mode=1, active=g.fresh)
+            if nverify:
+                g.sumsq(g.rho, g.verify)
+                g.decide(3, k, maxcycles, tol, history, outcome, self._partials)
+            if (ngcr or nverify) and k < maxcycles:
+                slot = k % m
+                e, t = g.row(slot), g.row(m + slot)
+                self._cycle(0, e, g.rho, zero=True, mask=g.gcr)
+                ops.stencil_var_smooth_batch(fine, e, g.zero, 0.0, t, mode=1, active=g.gcr)
+                g.dots(slot)
+                g.decide(1, k, maxcycles, tol, history, outcome, self._partials)
+                g.project(slot)
+                g.decide(2, k, maxcycles, tol, history, outcome, self._partials)
+                g.update(slot, x)
+        # ONE read-back of history and outcome per solve of the whole ensemble
+        self.history, self.outcome = history.cpu().numpy(), outcome.cpu().numpy()
+        return x
+
+    def newton_step(self, u, rhs, tol=1e-10, maxcycles=60, start=2):
+        raise ValueError("EnsembleLaunchKrylovGMG: newton_step is not served (solve M d = f with `solve`, then update)")
 
 
 def stencil_coefficients(items, shape, period=None, dtype=None, device=None):

@@ -410,6 +410,80 @@ def stencil_cycle_decide_batch(partials, cells, k, maxcycles, tol, history, outc
     return nactive
 
 
+def stencil_gcr_batch_parts(cells):
+    """Partial sums per member and quantity that the `stencil_gcr_*_batch` passes leave (0: cells outside 1..2^24)."""
+    return int(_lib.load().odil_stencil_gcr_batch_parts(c_int64(int(cells))))
+
+
+class GcrBatch:
+    """The device state and the launches of GCR(m) for an ensemble in lock-step (include/odil_hip.h:
+    odil_stencil_gcr_*_batch), allocated once: store [B, 2 m, cells] (Z, then Q), rho [B, *shape], zero [B, *shape]
+    (never written: the right-hand side of t = 0 - A e), the masks active / gcr / fresh / verify and have (int32 [B]),
+    scal [B, m + 2], gpart [B, m + 2, P], counts (int32 [4]) with a pinned host copy.  Everything a pass reads about a
+    member comes from these device arrays."""
+
+    def __init__(self, nbatch, shape, m, dtype, device, active):
+        self.nb, self.shape, self.m, self.dtype = int(nbatch), tuple(int(n) for n in shape), int(m), dtype
+        self.cells = math.prod(self.shape)
+        self.parts = stencil_gcr_batch_parts(self.cells)
+        if not self.parts or not 1 <= self.m <= 8:
+            raise ValueError("GcrBatch: {} cells per member, {} directions (1..2^24 cells, 1..8 directions)".format(self.cells, m))
+        self.store = torch.zeros((self.nb, 2 * self.m, self.cells), dtype=dtype, device=device)
+        self.rho = torch.zeros((self.nb,) + self.shape, dtype=dtype, device=device)
+        self.zero = torch.zeros((self.nb,) + self.shape, dtype=dtype, device=device)
+        self.active = active
+        self.flags = torch.zeros((4, self.nb), dtype=torch.int32, device=device)
+        self.gcr, self.fresh, self.verify, self.have = self.flags[0], self.flags[1], self.flags[2], self.flags[3]
+        self.scal = torch.zeros((self.nb, self.m + 2), dtype=torch.float64, device=device)
+        self.gpart = torch.zeros((self.nb, self.m + 2, self.parts), dtype=torch.float64, device=device)
+        self.counts = torch.zeros(4, dtype=torch.int32, device=device)
+        self.counts_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self._common = (c_int64(self.cells), c_int(self.m))
+        self._gp = (ptr(self.gpart), c_int64((self.m + 2) * self.parts))
+        self._sc = (ptr(self.scal), c_int64(self.m + 2))
+        self._st = (ptr(self.store), c_int64(2 * self.m * self.cells))
+
+    def row(self, r):
+        """[B, *shape]: row r of every member's store (a strided view: contiguous members)."""
+        return self.store[:, r].unflatten(1, self.shape)
+
+    def reset(self):
+        self.flags.zero_()
+
+    def dots(self, slot):
+        call("stencil_gcr_dots_batch", self.dtype, *self._st, *self._common, c_int(slot), ptr(self.have), c_int(self.m),
+             ptr(self.gcr), c_int(self.nb), *self._gp, stream_ptr())
+
+    def project(self, slot):
+        call("stencil_gcr_project_batch", self.dtype, *self._st, ptr(self.rho), c_int64(self.cells), *self._common, c_int(slot),
+             ptr(self.have), c_int(self.m), *self._sc, ptr(self.gcr), c_int(self.nb), *self._gp, stream_ptr())
+
+    def update(self, slot, x):
+        call("stencil_gcr_update_batch", self.dtype, *self._st, _base_ptr(x), c_int64(_member_stride(x, self.cells)),
+             ptr(self.rho), c_int64(self.cells), *self._common, c_int(slot), *self._sc, ptr(self.gcr), c_int(self.nb),
+             *self._gp, stream_ptr())
+
+    def sumsq(self, v, mask):
+        call("stencil_gcr_sumsq_batch", self.dtype, _base_ptr(v), c_int64(_member_stride(v, self.cells)), c_int64(self.cells),
+             ptr(mask), c_int(self.nb), *self._gp, stream_ptr())
+
+    def decide(self, mode, k, maxcycles, tol, history, outcome, partials, partials0=None):
+        """odil_stencil_gcr_decide_batch; after the modes 0 and 3 `counts` holds the members of every kind."""
+        assert history.dtype == torch.float64 and history.shape[0] == self.nb and history.is_contiguous()
+        assert outcome.dtype == torch.int32 and tuple(outcome.shape) == (self.nb, 3) and outcome.is_contiguous()
+        assert partials.dtype == torch.float64 and partials.dim() == 2 and partials.is_contiguous()
+        assert partials0 is None or (partials0.shape == partials.shape and partials0.is_contiguous())
+        lib = _lib.load()
+        status = lib.odil_stencil_gcr_decide_batch(
+            c_int(mode), ptr(partials), c_int64(partials.shape[1]), ptr(partials0), c_int64(partials.shape[1]),
+            c_int(partials.shape[1]), self._gp[0], self._gp[1], c_int(self.parts), c_int(self.nb), c_int64(self.cells), c_int(k),
+            c_int(maxcycles), c_double(float(tol)), c_int(self.m), ptr(history), c_int64(history.shape[1]), ptr(outcome),
+            ptr(self.active), ptr(self.gcr), ptr(self.fresh), ptr(self.verify), ptr(self.have), self._sc[0], self._sc[1],
+            ptr(self.counts), stream_ptr())
+        if status != 0:
+            raise _lib.OdilHipError("odil_stencil_gcr_decide_batch: {}".format(lib.odil_last_error().decode()))
+
+
 def stencil_vcycle_tail(coeffs, shapes, halve, xin, b, xout, work, inv, wpre, wpost, fmg=False):
     """The coarse tail of a multigrid cycle in one launch (include/odil_hip.h: odil_stencil_vcycle_tail).  coeffs: one
     flat tensor holding the coefficient arrays of every tail level; shapes: their extents, finest first; halve: per
