@@ -363,6 +363,22 @@ int odil_adam_step_batch_f64(double* x, double* m, double* v, const double* g, i
 int odil_adam_step_batch_f32(float* x, float* m, float* v, const float* g, int nbatch, int64_t n, int64_t x_stride,
                              int64_t m_stride, int64_t v_stride, int64_t g_stride, float one_minus_b1,
                              float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride, void* stream);
+/* The Array unknowns of the `nbatch` (1 ... 65535) members of an ensemble of traced operators, `np` packed parameters
+ * per member, in ONE launch.  pgrad[b * pgrad_stride + r], r < npg: the gradient the generated k_loss_batch left for
+ * row r of member b's parameter partial sums; map (DEVICE ints): map[b * map_stride + p] is the row of packed parameter
+ * p (map_stride 0: one map [np] for all members), any value outside 0 ... npg - 1 (-1 by convention) means that no grid
+ * kernel forms a gradient for it.  Writes g[b * np + p] = that gradient (0 where there is none) and applies the update
+ * of odil_adam_step -- the same device function -- to x, m, v [nbatch, np] with member b's step size alpha_dev[b *
+ * alpha_stride] (alpha_stride 0: one for all).  x, m, v all NULL: only g is formed (the evaluation of an optimizer that
+ * is not Adam; alpha_dev may then be NULL). */
+int odil_adam_step_params_batch_f64(double* x, double* m, double* v, double* g, const double* pgrad, const int* map,
+                                    int nbatch, int64_t np, int npg, int64_t pgrad_stride, int64_t map_stride,
+                                    double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                    int64_t alpha_stride, void* stream);
+int odil_adam_step_params_batch_f32(float* x, float* m, float* v, float* g, const float* pgrad, const int* map, int nbatch,
+                                    int64_t np, int npg, int64_t pgrad_stride, int64_t map_stride, float one_minus_b1,
+                                    float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
+                                    void* stream);
 /* Planes of ghost-extended arrays <-> contiguous message buffers of the slab exchanges (odil_amd/slab.py,
  * slab_traced.py; no reference counterpart).  `descs`: DEVICE array of ndesc (<= 65535) records
  * of five int64 {base, outer, ostride, inner, boff}: plane k of the message is `outer` runs of `inner` contiguous

@@ -14,18 +14,20 @@ import numpy as np
 import torch
 
 from . import gmg, ops, util
-from .core import Field, Problem
+from .core import Array, Field, Problem
 from .optimizer import make_optimizer
 
 # what members are compared by -> how a refusal calls it
-_LABELS = dict(shapes="level shapes", cshape="cells", dtype="dtype", device="device", spacing="grid spacing")
+_LABELS = dict(shapes="level shapes", cshape="cells", dtype="dtype", device="device", spacing="grid spacing",
+               params="Array unknowns (key, position in the state, shape)")
 
 
-def _check_members(who, problems, states, describe):
+def _check_members(who, problems, states, describe, arrays_ok=False):
     """The checks both drivers open with, structure only (no operator is probed, no state changes): as many states as
-    problems, every state initialised with one unknown field, and `describe(b, problem, state, refuse) -> kind`, a dict
-    of what the members must share (keys of `_LABELS`, compared in its order with member 0's) -- which also makes the
-    driver's own refusals.  `refuse(member, reason)` raises ValueError("<who>: member <b>: <reason>").
+    problems, every state initialised with one unknown field (arrays_ok: `Array` unknowns beside it do not count), and
+    `describe(b, problem, state, refuse) -> kind`, a dict of what the members must share (keys of `_LABELS`, compared in
+    its order with member 0's) -- which also makes the driver's own refusals.  `refuse(member, reason)` raises
+    ValueError("<who>: member <b>: <reason>").
     Returns (the kind all members share, refuse)."""
     if not problems or len(problems) != len(states):
         raise ValueError("{}: {} problems with {} states".format(who, len(problems), len(states)))
@@ -37,8 +39,9 @@ def _check_members(who, problems, states, describe):
     for b, (problem, state) in enumerate(zip(problems, states)):
         if not state.initialized:
             refuse(b, "uninitialized state, use `state = domain.init_state(state)`")
-        if len(state.fields) != 1:
-            refuse(b, "{} unknown fields (the Poisson problem has one)".format(len(state.fields)))
+        nfields = sum(1 for f in state.fields.values() if not (arrays_ok and isinstance(f, Array)))
+        if nfields != 1:
+            refuse(b, "{} unknown fields (the Poisson problem has one)".format(nfields))
         kind = describe(b, problem, state, refuse)
         first = first or kind
         for what, value in kind.items():
@@ -95,15 +98,30 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     synthesis, the generated forward kernels and gathers (`stencil_bind.EpochBatch`: one launch per group of members whose
     operators generate the same source), the transposed prolongations with the updates of the coarser levels, and
     `ops.adam_step_batch` for level 0 -- each covering all members.  'auto' then picks by dimension ('volumes' for 3-D).
-    Such members have ONE cell-centred unknown, a plain `Field` (one level: no transfers, exempt from the two-level rule
-    of the forms) or a `MultigridField` with all factors 1, on a 1-D to 3-D grid, with level shapes that
-    `fused.traced_refusal` admits; operators whose kernels have no batched form (networks or `Array` parameters, outputs
+    Such members have ONE cell-centred grid unknown (and possibly `Array` unknowns: next paragraph), a plain `Field` (one
+    level: no transfers, exempt from the two-level rule of the forms) or a `MultigridField` with all factors 1, on a 1-D to 3-D grid, with level shapes that
+    `fused.traced_refusal` admits; operators whose kernels have no batched form (network parameters, outputs
     in parameter space, marching kernels) raise ValueError naming the member.  The callback's pinfo carries the member's own
     names, terms and norms.  Epochs are replayed as a graph only when no member has host scalars (functions of
     `problem.tracers`), which travel in the argument blocks and are uploaded again when they change.  With
     form='workgroup', or without tracing, a member that is not the Poisson operator stays refused.
-    Returns ([level arrays of member b], optinfo); optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route:
-    "poisson" or "traced"; optinfo.form: the form that ran.
+
+    INVERSE PROBLEMS run on that traced route: beside its one grid unknown a member may have any number of `Array`
+    unknowns (constants that the grid residuals multiply stencil terms by: `ctx.field(key)[k]`), of any shape, anywhere in
+    the state -- the same keys, shapes and positions for all members (else ValueError naming the member, before any state
+    changes).  The members' constants live in packed [B, P] tensors beside the level arrays; every member's kernels read
+    its own row and reduce the gradient of its constants over the grid as its single run does, and ONE launch per epoch
+    (`ops.adam_step_params_batch`) updates the constants of all members.  The arrays returned for member b, and those its
+    state holds afterwards, are all its arrays in `arrays_from_state` order, the `Array`s included, and every one ends where
+    the member's own `optimize_grad` run ends, bit for bit, with Adam and with L-BFGS-B (whose member-major vectors hold the
+    constants where the single run's packed vector has them).  Not served: `NeuralNet` unknowns, outputs in parameter space
+    (a prior on the constants), marching kernels -- ValueError naming the member -- and, because a single run packs its
+    arrays back to back and its 3-D transfer kernels choose by alignment, a number of `Array` elements before a 3-D
+    multigrid field that is no multiple of 4 (put the `Array` after the field).  `optimize_newton_ensemble` keeps refusing
+    members with `Array` unknowns.
+    Returns ([arrays of member b: its level arrays; with `Array` unknowns all its arrays in state order], optinfo);
+    optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route: "poisson" or "traced"; optinfo.form: the form that
+    ran.
 
     args.optimizer == 'lbfgsb' runs L-BFGS-B on all members in LOCK-STEP (`LbfgsbOptimizer.run_ensemble`), on both routes,
     with form 'launches', 'volumes' or 'auto' ('auto' by dimension; 'workgroup', the default, raises ValueError: the
@@ -147,11 +165,18 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     # (the generated kernels need a device: members on CPU tensors keep the refusals of the Poisson forms, as before)
     requested, traceable = form, form != "workgroup" and runtime.enable_trace and torch.cuda.is_available()
     late = dict(poisson=None, traced=None)  # per route the first (member, reason) it refuses while the other admits
+    unserved = []  # (member, reason) of members with `Array` unknowns when no traced route runs at all
 
     def describe(b, problem, state, refuse):
         nonlocal form, traceable
         domain = problem.domain
-        arrays = domain.arrays_from_state(state)
+        # the one grid unknown (its level arrays) and the `Array` unknowns beside it, by position in `arrays_from_state`
+        params, arrays = [], None
+        for pos, (key, field) in enumerate(state.fields.items()):
+            if isinstance(field, Array):
+                params.append((key, pos, tuple(int(n) for n in field.array.shape)))
+            else:
+                unknown, arrays, upos = field, domain.arrays_from_field(field), pos
         shapes = [tuple(int(n) for n in a.shape) for a in arrays]
         if shapes[0] != tuple(domain.cshape):
             refuse(b, "the unknown is not a cell-centred field of the domain")
@@ -160,17 +185,40 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
             form = _traced_form(form, shapes) if lbfgsb else fused.ensemble_form(form, shapes, arrays[0].dtype)
             traceable = traceable and arrays[0].is_cuda
         reasons = dict(poisson=predicates[form](shapes, arrays[0].dtype), traced=None)
+        if params:  # (inverse problems: the traced route alone serves them)
+            reasons["poisson"] = ("{} Array unknown{} beside the field: such members run as traced operators -- form='launches', "
+                                  "'volumes' or 'auto', with operators traced and the members on a device".format(
+                                      len(params), "" if len(params) == 1 else "s"))
         if traceable:
-            reasons["traced"] = _traced_member(domain, state, shapes, arrays[0].dtype, _traced_form(requested, shapes))
-        if reasons["poisson"] is not None and (not traceable or reasons["traced"] is not None):
+            reasons["traced"] = _traced_member(domain, unknown, shapes, arrays[0].dtype, _traced_form(requested, shapes))
+            ahead = sum(math.prod(shape) for _, pos, shape in params if pos < upos)
+            if reasons["traced"] is None and len(shapes[0]) == 3 and len(shapes) > 1 and ahead % 4:
+                # a single run packs its arrays back to back: with `ahead` elements in front, the levels of its field are
+                # not aligned to four elements, and its 3-D transfers take other kernels (other rounding) than those of
+                # the members' aligned level arrays here
+                reasons["traced"] = ("{} Array elements stand before the 3-D multigrid field: a single run's level arrays are "
+                                     "then not aligned to 4 elements and its transfer kernels round differently (put the "
+                                     "Array after the field, or a multiple of 4 elements before it)".format(ahead))
+            for key, _, _ in params:
+                array = state.fields[key].array
+                if reasons["traced"] is None and (array.dtype != arrays[0].dtype or array.device != arrays[0].device):
+                    reasons["traced"] = "Array unknown '{}' is a {} tensor on {} (the field: {} on {})".format(
+                        key, array.dtype, array.device, arrays[0].dtype, arrays[0].device)
+        if params and not traceable:  # (said once the members have been compared with each other: `unserved`)
+            unserved.append((b, reasons["poisson"]))
+        elif params and reasons["traced"] is not None:  # (the only route that serves them says why it does not)
+            refuse(b, reasons["traced"])
+        elif reasons["poisson"] is not None and (not traceable or reasons["traced"] is not None):
             refuse(b, reasons["poisson"])
         for route, reason in reasons.items():
             if reason is not None and late[route] is None:
                 late[route] = (b, reason)
-        return dict(shapes=shapes, dtype=arrays[0].dtype, device=arrays[0].device,
+        return dict(shapes=shapes, params=params, dtype=arrays[0].dtype, device=arrays[0].device,
                     spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
 
-    kind, refuse = _check_members("optimize_ensemble", problems, states, describe)
+    kind, refuse = _check_members("optimize_ensemble", problems, states, describe, arrays_ok=True)
+    if unserved:
+        refuse(*unserved[0])
     evaluators = []
     for b, (problem, state) in enumerate(zip(problems, states)):
         problem.recognise(state)
@@ -280,14 +328,13 @@ def _traced_form(requested, shapes):
     return requested
 
 
-def _traced_member(domain, state, shapes, dtype, form):
-    """Why a member is not run by `fused.TracedLaunchEnsemble` in `form`, or None -- structure only: one cell-centred
-    unknown, a plain `Field` or a `MultigridField` with all factors 1 that coarsens every axis, level shapes that
-    `fused.traced_refusal` admits."""
+def _traced_member(domain, field, shapes, dtype, form):
+    """Why a member whose grid unknown is `field` is not run by `fused.TracedLaunchEnsemble` in `form`, or None --
+    structure only: one cell-centred unknown, a plain `Field` or a `MultigridField` with all factors 1 that coarsens every
+    axis, level shapes that `fused.traced_refusal` admits.  (`Array` unknowns beside it: the caller's.)"""
     from . import fused
     from .core import MultigridField
 
-    (field,) = state.fields.values()
     if isinstance(field, MultigridField):
         factors = field.factors or domain.mg_factors or [1] * len(field.terms)
         if any(float(f) != 1.0 for f in factors):

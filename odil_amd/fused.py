@@ -311,6 +311,11 @@ class BatchedLaunches(_Members):
         """The level arrays of one member: views of the [B, *shape] level tensors."""
         return [t[member] for t in packed]
 
+    def blocks(self, packed):
+        """`packed` (x, m, v or g) as [B, size] views in the order of the members' `arrays_from_state`: what an optimizer
+        on member-major [B, n] vectors copies from and to, block by block."""
+        return [t.view(self.nbatch, -1) for t in packed]
+
     def loss_grad(self):
         """The launches of `epoch` WITHOUT any update (what an optimizer that is not Adam drives: L-BFGS-B in lock-step):
         the [B] losses at self.x land in self.loss, the gradient of every level in self.g; x, m and v stay as they are.
@@ -408,6 +413,13 @@ class PoissonVolumeEnsemble(BatchedLaunches):
         self._transposes()
 
 
+class _Levels(list):
+    """The level tensors of one packed quantity of an ensemble (x, m, v or g) with `.params`: the [B, P] tensor of the
+    members' `Array` unknowns beside them."""
+
+    params = None
+
+
 class TracedLaunchEnsemble(BatchedLaunches):
     """B traced stencil operators of one cell-centred unknown (a `MultigridField` with factors 1, or a plain `Field`: the
     one-level case) on one grid side by side, as batched launches: an epoch is the launches of a single traced run
@@ -421,20 +433,47 @@ class TracedLaunchEnsemble(BatchedLaunches):
       5. `ops.adam_step_batch` for level 0, after the chain has read g[0] (and after the gathers have re-read their
          sources: for a plain `Field` the source IS x[0]).
     Member b computes what its single run computes, bit for bit.  out [B, 1 + 2 nout_b] per group holds loss, terms and
-    norms of its members (`report`); `loss` [B] collects column 0."""
+    norms of its members (`report`); `loss` [B] collects column 0.
+
+    Inverse problems: beside the grid unknown the members may have `Array` unknowns (constants the residuals multiply
+    stencil terms by; any number, shape and position in the state, the same for all members).  Their state is packed
+    beside the level-major grid state: x, m, v and g are then `_Levels` whose `.params` is a [B, P] tensor (P: the elements
+    of all Arrays in state order); member b's kernels read its constants from its row (`a.par`), reduce their gradients
+    over the grid into its rows of packed partial sums and of `pgrad` [B, npg] (the bodies of k_fwd / k_final / k_loss of
+    the single run), and
+      6. `ops.adam_step_params_batch`: ONE launch that forms g.params from `pgrad` through `param_rows` and updates
+         x.params, m.params, v.params of all members -- behind the gathers, which re-read the constants.
+    `levels(packed, b)` gives member b's arrays in `arrays_from_state` order, `blocks(packed)` the [B, size] views an
+    optimizer on member-major vectors works with, `total` counts the parameters.  Members without `Array` unknowns make
+    exactly the launches 1 - 5.  Not served: network unknowns, outputs in parameter space (priors on the constants)."""
 
     def __init__(self, problems, states, form="launches"):
-        """The members have passed the structural checks of `ensemble.optimize_ensemble` (one unknown, same level shapes,
-        dtype and device; `traced_refusal` admits the shapes).  A member whose operator has no batched kernels raises
-        ValueError naming it."""
+        """The members have passed the structural checks of `ensemble.optimize_ensemble` (one grid unknown, the same
+        `Array` unknowns, same level shapes, dtype and device; `traced_refusal` admits the shapes).  A member whose
+        operator has no batched kernels raises ValueError naming it."""
         from . import stencil_jit
-        from .stencil_bind import EpochBatch
+        from .core import Array
+        from .stencil_bind import EpochBatch, field_ranges
 
         domain = problems[0].domain
         arrays = domain.arrays_from_state(states[0])
-        shapes = [tuple(int(n) for n in a.shape) for a in arrays]
+        # the state's arrays in `arrays_from_state` order: ("level", l) of the grid unknown, ("param", offset, shape) of
+        # an `Array` in the members' packed parameters
+        self.order, self.param_keys, self.nparams = [], [], 0
+        for key, field, pos, n in field_ranges(domain, states[0]):
+            if isinstance(field, Array):
+                shape = tuple(int(k) for k in arrays[pos].shape)
+                self.order.append(("param", self.nparams, shape))
+                self.param_keys.append((key, self.nparams, math.prod(shape)))
+                self.nparams += math.prod(shape)
+            else:
+                grid_key, first = key, pos
+                self.order.extend(("level", l) for l in range(n))
+        nlvl = sum(1 for item in self.order if item[0] == "level")
+        shapes = [tuple(int(n) for n in a.shape) for a in arrays[first:first + nlvl]]
+        dtype, device = arrays[first].dtype, arrays[first].device
         nb = len(problems)
-        reason = traced_refusal(shapes, arrays[0].dtype, form, nb)
+        reason = traced_refusal(shapes, dtype, form, nb)
         if reason is not None:
             raise ValueError("ensemble of {} members: {}".format(nb, reason))
         self.form = form
@@ -444,25 +483,77 @@ class TracedLaunchEnsemble(BatchedLaunches):
                 self.traced.append(stencil_jit.TracedOperator(problem, state, batch=True))
             except stencil_jit.TraceUnsupported as e:
                 raise ValueError("ensemble member {}: its operator has no batched kernels ({})".format(b, e))
-        self._allocate(shapes, arrays[0].dtype, arrays[0].device, [list(t.names) for t in self.traced])
+        self._allocate(shapes, dtype, device, [list(t.names) for t in self.traced])
         self.u = self.members(self.cshape) if self.nlvl > 1 else self.x[0]
         self.work = ([None] + [self.members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
         by_lib = dict()
         for b, traced in enumerate(self.traced):
             by_lib.setdefault(traced.lib_path, []).append(b)
         self.groups = list(by_lib.values())
-        (key,) = states[0].fields.keys()
+        if self.param_keys:
+            self._allocate_params()
         self.outs, self.batches = [], []
         for group in self.groups:
             out = torch.zeros((len(group), 1 + 2 * self.traced[group[0]].nout), dtype=self.dtype, device=self.device)
             self.outs.append(out)
+            more = dict()
+            if self.traced[group[0]].cg.arrays:
+                more = dict(params=[{key: self.x.params[b, off:off + n] for key, off, n in self.param_keys} for b in group],
+                            pgrad=[self.pgrad[b] for b in group])
             self.batches.append(EpochBatch([self.traced[b] for b in group], [[self.u[b]] for b in group],
-                                           [{key: self.g[0][b]} for b in group], out))
+                                           [{grid_key: self.g[0][b]} for b in group], out, **more))
         self.where = dict((b, (k, j)) for k, group in enumerate(self.groups) for j, b in enumerate(group))
         self.index = [torch.tensor(group, device=self.device) for group in self.groups]
         if len(self.groups) == 1:  # (column 0 of the packed `out` itself: nothing to collect)
             self.loss = self.outs[0][:, 0]
         self.graphable = all(batch.graphable for batch in self.batches)
+
+    def _allocate_params(self):
+        """The packed state of the members' `Array` unknowns beside the level-major grid state: x, m, v, g get `.params`,
+        a [B, P] tensor each (P: the elements of all Arrays, in state order); `pgrad` [B, npg]: where member b's k_loss
+        leaves the gradients of the rows of its `pg_decl`; `param_rows`: packed parameter -> its row there (-1: no grid
+        kernel reads that Array with a gradient), one map [P] when all members' kernels agree, else a map per member."""
+        self.total += self.nparams
+        for name in "xmvg":
+            levels = _Levels(getattr(self, name))
+            levels.params = torch.zeros((self.nbatch, self.nparams), dtype=self.dtype, device=self.device)
+            setattr(self, name, levels)
+        rows = []
+        for traced in self.traced:
+            cg, row = traced.cg, []
+            for key, _, n in self.param_keys:
+                row.extend(range(cg.pg_offset[key], cg.pg_offset[key] + n) if key in cg.pgrads else [-1] * n)
+            rows.append(row)
+        npg = max(1, max(len(traced.cg.pg_decl) for traced in self.traced))
+        self.pgrad = torch.zeros((self.nbatch, npg), dtype=self.dtype, device=self.device)
+        self.param_rows = ops.param_rows(rows[0] if all(row == rows[0] for row in rows) else rows, npg, self.device)
+
+    def levels(self, packed, member):
+        """The arrays of one member in its `arrays_from_state` order: views of the [B, *shape] level tensors and, for
+        `Array` unknowns, of its row of the packed parameters."""
+        params = getattr(packed, "params", None)
+        if params is None:
+            return [t[member] for t in packed]
+        return [packed[item[1]][member] if item[0] == "level" else params[member, item[1]:item[1] + math.prod(item[2])].view(item[2])
+                for item in self.order]
+
+    def blocks(self, packed):
+        params = getattr(packed, "params", None)
+        if params is None:
+            return [t.view(self.nbatch, -1) for t in packed]
+        return [packed[item[1]].view(self.nbatch, -1) if item[0] == "level" else params[:, item[1]:item[1] + math.prod(item[2])]
+                for item in self.order]
+
+    def _param_step(self, alphas=None, omb1=0.0, omb2=0.0, eps=0.0):
+        """ONE launch for the `Array` unknowns of all members, behind the gathers (which re-read the constants): the packed
+        parameter gradient from the rows k_loss_batch wrote and, with step sizes, the Adam update."""
+        if not self.nparams:
+            return
+        if alphas is None:
+            ops.adam_step_params_batch(None, None, None, self.g.params, self.pgrad, self.param_rows)
+        else:
+            ops.adam_step_params_batch(self.x.params, self.m.params, self.v.params, self.g.params, self.pgrad, self.param_rows,
+                                       alphas, omb1, omb2, eps)
 
     def report(self, member, outs=None):
         """(loss, terms, norms) of `member` as the last epoch evaluated them: 0-d views of the packed `out` (outs: of
@@ -485,6 +576,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
             chain = ops.mg_synth_adj_adam_volumes if self.ndim == 3 else ops.mg_synth_adj_adam_batch
             chain(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
         ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], alphas, omb1, omb2, eps)
+        self._param_step(alphas, omb1, omb2, eps)
 
     def loss_grad(self):
         if self.nlvl > 1:
@@ -495,6 +587,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
             for index, out in zip(self.index, self.outs):
                 self.loss.index_copy_(0, index, out[:, 0])
         self._transposes()
+        self._param_step()
 
 
 def traced_refusal(shapes, dtype, form, nbatch=1):

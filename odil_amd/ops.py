@@ -1212,6 +1212,36 @@ def adam_step_batch(x, m, v, g, alphas, one_minus_b1, one_minus_b2, eps):
          float(one_minus_b2), float(eps), ptr(alphas), c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
 
 
+def param_rows(rows, npg, device):
+    """The index map of `adam_step_params_batch` as a DEVICE int32 tensor, checked on the host: rows [P], or [B, P] (a map
+    per member), every entry -1 (no grid gradient for that packed parameter) or a row 0 ... npg - 1 of `pgrad`."""
+    rows = torch.tensor(rows, dtype=torch.int64)
+    if rows.dim() not in (1, 2) or (rows.numel() and (int(rows.min()) < -1 or int(rows.max()) >= int(npg))):
+        raise ValueError("param_rows: entries are -1 or rows 0 ... {} of the parameter gradients".format(int(npg) - 1))
+    return rows.to(torch.int32).contiguous().to(device)
+
+
+def adam_step_params_batch(x, m, v, g, pgrad, rows, alphas=None, one_minus_b1=0.0, one_minus_b2=0.0, eps=0.0):
+    """The Array unknowns of the B members of an ensemble in ONE launch: g[b, p] = pgrad[b, rows[p]] (0 where rows[p] is
+    -1) and `adam_step` of x, m, v [B, P] with that gradient.  pgrad: [B, npg] (rows contiguous, any row stride >= npg);
+    rows: `param_rows` ([P], or [B, P]); alphas: DEVICE step sizes, [B] or one element (shared).  x, m, v all None: only
+    g is formed.  Member b gets the bits of `adam_step` on its own arrays."""
+    nb, npar = int(g.shape[0]), int(g.shape[1])
+    assert g.dim() == 2 and g.is_contiguous() and g.dtype == pgrad.dtype
+    assert pgrad.dim() == 2 and pgrad.shape[0] == nb and (pgrad.shape[1] == 0 or pgrad.stride(1) == 1) and pgrad.is_cuda
+    assert rows.dtype == torch.int32 and rows.is_cuda and rows.is_contiguous()
+    assert tuple(rows.shape) in ((npar,), (nb, npar)), (tuple(rows.shape), (nb, npar))
+    update = x is not None or m is not None or v is not None
+    if update:
+        assert all(t is not None and t.shape == g.shape and t.dtype == g.dtype and t.is_contiguous() for t in (x, m, v))
+        assert alphas.dtype == g.dtype and alphas.is_cuda and alphas.numel() in (1, nb) and alphas.is_contiguous()
+    pstride = max(int(pgrad.stride(0)), int(pgrad.shape[1])) if nb > 1 else int(pgrad.shape[1])
+    call("adam_step_params_batch", g.dtype, ptr(x), ptr(m), ptr(v), ptr(g), c_void_p(pgrad.data_ptr()), ptr(rows), c_int(nb),
+         c_int64(npar), c_int(int(pgrad.shape[1])), c_int64(pstride), c_int64(npar if rows.dim() == 2 else 0),
+         float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas) if update else None,
+         c_int64(1 if update and alphas.numel() == nb and nb > 1 else 0), stream_ptr())
+
+
 def adam_step_pieces(x, m, v, g, npieces, stride, offset, count, alpha, one_minus_b1, one_minus_b2, eps):
     """adam_step on the elements o * stride + offset + j (o < npieces, j < count) of four flat vectors."""
     assert x.numel() == m.numel() == v.numel() == g.numel() and x.is_contiguous()

@@ -333,8 +333,9 @@ class AdamNativeOptimizer(Optimizer):
         first, last = epoch_start + 1, epoch_start + epochs
         losses = torch.empty((nb, max(epochs, 0)), dtype=tdtype, device=device)
         norms = torch.empty_like(losses)
-        for t in ensemble.m + ensemble.v:
-            t.zero_()
+        for packed in (ensemble.m, ensemble.v):  # (with the moments of `Array` unknowns, where the members have any)
+            for t in list(packed) + [t for t in [getattr(packed, "params", None)] if t is not None]:
+                t.zero_()
         rows = np.array(table, dtype=np.float64)
         rows = rows.T if rows.ndim == 2 else rows  # a row per epoch
 
@@ -1272,21 +1273,25 @@ class LbfgsbOptimizer(Optimizer):
         reason = self.ensemble_refusal(nb, n, ensemble.device)
         if reason is not None:
             raise ValueError("L-BFGS-B ensemble: " + reason)
-        offsets = np.cumsum([0] + list(ensemble.sizes))
+        # the member-major [B, n] vectors hold a member's arrays in `arrays_from_state` order -- the packed vector of its
+        # single run, `Array` unknowns at their position: the bits of the dot products depend on it
+        xblocks, gblocks = ensemble.blocks(ensemble.x), ensemble.blocks(ensemble.g)
+        offsets = np.cumsum([0] + [int(block.shape[1]) for block in xblocks])
+        assert offsets[-1] == n
         pieces = lambda packed: [packed[:, a:b] for a, b in zip(offsets[:-1], offsets[1:])]
 
         def evaluate(x, e):
-            for level, piece in zip(ensemble.x, pieces(x)):
-                level.view(nb, -1).copy_(piece)  # (cast to the evaluation dtype)
+            for block, piece in zip(xblocks, pieces(x)):
+                block.copy_(piece)  # (cast to the evaluation dtype)
             ensemble.loss_grad()
-            for level, piece in zip(ensemble.g, pieces(e)):
-                piece.copy_(level.view(nb, -1))
+            for block, piece in zip(gblocks, pieces(e)):
+                piece.copy_(block)
             self.evals += 1
             return ensemble.loss
 
         vec = EnsembleLbfgsVectors(nb, n, self.m, ensemble.device, evaluate)
-        for level, piece in zip(ensemble.x, pieces(vec.v["x"])):
-            piece.copy_(level.view(nb, -1))
+        for block, piece in zip(xblocks, pieces(vec.v["x"])):
+            piece.copy_(block)
         next_active = getattr(callback, "next_active", None) if callback is not None else None
         nits = [0] * nb
         due = [next_active(epoch_start) if next_active is not None else epoch_start + 1 for _ in range(nb)]
@@ -1300,8 +1305,8 @@ class LbfgsbOptimizer(Optimizer):
 
         results, info = lbfgsb_minimize_ensemble(vec, nb, epochs, m=self.m, maxls=self.maxls, pgtol=self.pgtol,
                                                  factr=self.factr, callback=iterate)
-        for level, piece in zip(ensemble.x, pieces(vec.v["x"])):  # (every member's last accepted iterate)
-            level.view(nb, -1).copy_(piece)
+        for block, piece in zip(xblocks, pieces(vec.v["x"])):  # (every member's last accepted iterate)
+            block.copy_(piece)
         optinfo = Namespace(epochs=epochs, rounds=info.rounds, host_reads=info.host_reads, ensemble=ensemble,
                             read_seconds=vec.read_seconds)
         optinfo.tasks = [res["task"] for res in results]

@@ -282,14 +282,20 @@ class EpochBatch:
     packed level-0 gradients, its `out` is row b of one packed [B, 1 + 2 nout] tensor.  So the blocks are staged ONCE, and
     again only when a member's bytes change: host scalars (`cg.hs`, functions of `problem.tracers`), which `launch`
     evaluates for the members that have any and compares with what the device holds.  Members without host scalars cost
-    no host time per epoch, and their launches can be captured into a graph (`graphable`)."""
+    no host time per epoch, and their launches can be captured into a graph (`graphable`).  `Array` unknowns that the
+    kernels read change nothing in that: member b's `args.par` points at its rows of packed parameter tensors, `args.ppart`
+    and `args.pgrad` at its rows of packed partial sums and parameter gradients."""
 
     depth = 4
 
-    def __init__(self, members, sources, grads, out):
+    def __init__(self, members, sources, grads, out, params=None, pgrad=None):
         """members: the `TracedOperator`s of one group, in the order of the launch.  sources[b]: the contiguous arrays
         member b reads, in the order of `cg.src_keys`; grads[b]: {field key: the contiguous array its gradient goes to};
-        out: [B, 1 + 2 nout] contiguous, B the number of members here.  The caller keeps all of them alive."""
+        out: [B, 1 + 2 nout] contiguous, B the number of members here.  The caller keeps all of them alive.
+        Members whose kernels read `Array` unknowns (`cg.arrays`): params[b]: {Array key: the contiguous array member b
+        reads it from -- its row of a packed tensor}; pgrad[b]: the contiguous row of at least len(cg.pg_decl) elements its
+        k_loss writes the parameter gradients to, in the order of `cg.pg_decl`.  The partial sums of those rows (`ppart`)
+        are one packed [B, npg * nblocks] buffer held here."""
         first = members[0]
         if any(m.lib_path != first.lib_path for m in members):
             raise ValueError("EpochBatch: members of one launch share one generated library")
@@ -307,12 +313,29 @@ class EpochBatch:
         # which = -1: the merged gather; the fields it does not cover keep launches of their own
         self.which = ([-1] if cg.merged else []) + [gi for gi, key in enumerate(cg.gathers) if key not in cg.merged]
         self.ptrs = []
+        npg = len(cg.pg_decl)
+        if cg.nets or (cg.arrays and (params is None or pgrad is None)):
+            raise RuntimeError("EpochBatch: kernels that read parameter arrays need `params` and `pgrad` (Array unknowns only)")
+        self.ppart = torch.empty((nb, max(1, npg * cg.fwd_blocks)), dtype=first.dtype, device=out.device) if cg.arrays else None
         for b, member in enumerate(members):
             if member.nblocks != cg.fwd_blocks or len(sources[b]) != len(cg.src_keys):
                 raise RuntimeError("EpochBatch: member {} does not match the generated launch".format(b))
             for t in list(sources[b]) + list(grads[b].values()):
                 if not t.is_contiguous() or t.dtype != member.dtype or not t.is_cuda:
                     raise RuntimeError("EpochBatch: sources and gradients are contiguous {} arrays on the device".format(member.dtype))
+            if cg.arrays:
+                if len(member.cg.pg_decl) != npg or [n for _, n in member.cg.arrays] != [n for _, n in cg.arrays]:
+                    raise RuntimeError("EpochBatch: member {} does not match the generated launch".format(b))
+                row = pgrad[b]
+                for t, least in [(params[b][key], numel) for key, numel in cg.arrays] + [(row, npg)]:
+                    if not t.is_contiguous() or t.dtype != member.dtype or not t.is_cuda or t.numel() < least:
+                        raise RuntimeError("EpochBatch: Array unknowns and their gradient rows are contiguous {} arrays on the "
+                                           "device, no shorter than the kernels index them".format(member.dtype))
+                for i, (key, _) in enumerate(cg.arrays):  # (no network arrays before them: `cg.nets` is empty)
+                    member.args.par[i] = params[b][key].data_ptr()
+                member.args.ppart, member.args.pgrad = self.ppart[b].data_ptr(), row.data_ptr()
+                if member.part2.numel() < 16 * (member.nout + npg):  # (SEG partial sums per row of k_final)
+                    raise RuntimeError("EpochBatch: member {}: `part2` is shorter than the rows of k_final".format(b))
             for i, t in enumerate(sources[b]):
                 member.args.src[i] = t.data_ptr()
             member.args.out, member.args.hs = out[b].data_ptr(), None

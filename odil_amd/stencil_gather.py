@@ -372,7 +372,10 @@ class _GatherKernels:
         if march is not None:
             raise TraceUnsupported("batched forward kernel: the marching forward kernel hands sums across workgroups "
                                    "(`edge`), it is no pointwise body")
-        if self.nets or self.arrays or self.pg_decl:
+        # (`Array` unknowns pass: member b's `a.par`, `a.ppart` and `a.pgrad` are its own, and the rows of `pg_decl` are
+        # reduced by the bodies of k_final / k_loss like the outputs' -- stencil_bind.EpochBatch; a network's parameter
+        # arrays and their hundreds of rows have no packed home there)
+        if self.nets:
             raise TraceUnsupported("batched forward kernel: network or Array parameters (parameter gradients reduced over "
                                    "the grid)")
         if self.par_outputs:
@@ -451,7 +454,8 @@ class _GatherKernels:
         S.append("  const Args* ab = (const Args*)args_dev;")
         S.append("  hipLaunchKernelGGL(k_fwd_batch, dim3({}, nmembers), dim3({}), 0, (hipStream_t)stream, ab);".format(
             self.fwd_blocks, self.fwd_threads))
-        S.append("  hipLaunchKernelGGL(k_final_batch, dim3({}, SEG, nmembers), dim3(NB), 0, (hipStream_t)stream, ab);".format(nout))
+        S.append("  hipLaunchKernelGGL(k_final_batch, dim3({}, SEG, nmembers), dim3(NB), 0, (hipStream_t)stream, ab);".format(
+            nout + len(self.pg_decl)))  # (the rows of k_final: the outputs, then the parameter gradients of `Array` unknowns)
         S.append("  hipLaunchKernelGGL(k_loss_batch, dim3(nmembers), dim3(64), 0, (hipStream_t)stream, ab);")
         S.append("  return (int)hipGetLastError();")
         S.append("}")

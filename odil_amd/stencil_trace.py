@@ -624,6 +624,16 @@ class ParamArray:
     def __getitem__(self, item):
         if isinstance(item, tuple) and len(item) == 1:
             item = item[0]
+        if len(self.shape) > 1:  # one element of an Array of several axes, a[i, j]: its position in the contiguous array
+            if not (isinstance(item, tuple) and len(item) == len(self.shape) and all(isinstance(i, (int, np.integer)) for i in item)):
+                raise TraceUnsupported("Array unknowns support a[k] (one axis) and a[i, j, ...] (one element) only")
+            k = 0
+            for i, n in zip(item, self.shape):
+                i = int(i) + (n if i < 0 else 0)
+                if not 0 <= i < n:
+                    raise IndexError("index {} out of range".format(tuple(int(i) for i in item)))
+                k = k * n + i
+            return self.tr.node("aparam", attr=(self.key, k, self.frozen), kind=_R)
         if len(self.shape) != 1 or not isinstance(item, (int, np.integer)):
             raise TraceUnsupported("Array unknowns support a[k] only")
         k = int(item) + (self.shape[0] if item < 0 else 0)
