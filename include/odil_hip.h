@@ -379,6 +379,20 @@ int odil_adam_step_params_batch_f32(float* x, float* m, float* v, float* g, cons
                                     int64_t np, int npg, int64_t pgrad_stride, int64_t map_stride, float one_minus_b1,
                                     float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
                                     void* stream);
+/* odil_adam_step_params_batch for members whose operators also have outputs in PARAMETER space (a weight decay, a prior
+ * on an Array).  extra [nbatch, np]: what the generated k_par_batch left of member b's gradient -- added to what stood
+ * there where a grid kernel forms a gradient too, set where none does.  Forms g[b * np + p] = (the gradient of row
+ * map[p], 0 without one) + extra[b * np + p], the sum a single run forms when its k_par adds to its packed gradient,
+ * applies the same update (x, m, v all NULL: none), and CLEARS extra, which the next k_par_batch adds to again.  One
+ * launch. */
+int odil_adam_step_params_extra_batch_f64(double* x, double* m, double* v, double* g, const double* pgrad, double* extra,
+                                          const int* map, int nbatch, int64_t np, int npg, int64_t pgrad_stride,
+                                          int64_t map_stride, double one_minus_b1, double one_minus_b2, double eps,
+                                          const double* alpha_dev, int64_t alpha_stride, void* stream);
+int odil_adam_step_params_extra_batch_f32(float* x, float* m, float* v, float* g, const float* pgrad, float* extra,
+                                          const int* map, int nbatch, int64_t np, int npg, int64_t pgrad_stride,
+                                          int64_t map_stride, float one_minus_b1, float one_minus_b2, float eps,
+                                          const float* alpha_dev, int64_t alpha_stride, void* stream);
 /* Planes of ghost-extended arrays <-> contiguous message buffers of the slab exchanges (odil_amd/slab.py,
  * slab_traced.py; no reference counterpart).  `descs`: DEVICE array of ndesc (<= 65535) records
  * of five int64 {base, outer, ostride, inner, boff}: plane k of the message is `outer` runs of `inner` contiguous

@@ -269,6 +269,55 @@ static int adam_step_params_batch(T* x, T* m, T* v, T* g, const T* pgrad, const 
   return check_launch("k_adam_params_batch");
 }
 
+// The same launch for members whose operators also have outputs in PARAMETER space (a weight decay, a prior on an Array):
+// the generated k_par_batch has left member b's part of the gradient in extra[b, p] -- ADDED to what stood there where a
+// grid kernel forms a gradient too, SET where none does, as k_par adds to or sets the packed gradient of a single run.
+// g = pgrad[row] + extra is the sum that single run forms (0 + extra where there is no row: exact), and extra is cleared
+// behind the read, so that the next k_par_batch adds to zero again: no launch of its own for that.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_adam_params_extra_batch(T* __restrict__ x, T* __restrict__ m, T* __restrict__ v,
+                                                                   T* __restrict__ g, const T* __restrict__ pgrad,
+                                                                   T* __restrict__ extra, const int* __restrict__ map,
+                                                                   int64_t np, int npg, int64_t pgrad_stride,
+                                                                   int64_t map_stride, T omb1, T omb2, T eps,
+                                                                   const T* __restrict__ alpha_dev, int64_t alpha_stride) {
+  const int64_t b = blockIdx.y;
+  const int64_t nthreads = (int64_t)gridDim.x * kBlock;
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < np; p += nthreads) {
+    const int row = map[b * map_stride + p];
+    const int64_t at = b * np + p;
+    const T gp = ((row >= 0 && row < npg) ? pgrad[b * pgrad_stride + row] : T(0)) + extra[at];
+    extra[at] = T(0);
+    g[at] = gp;
+    if (x) adam_one<T>(x[at], m[at], v[at], gp, alpha_dev[b * alpha_stride], omb1, omb2, eps);
+  }
+}
+
+template <typename T>
+static int adam_step_params_extra_batch(T* x, T* m, T* v, T* g, const T* pgrad, T* extra, const int* map, int nbatch,
+                                        int64_t np, int npg, int64_t pgrad_stride, int64_t map_stride, T omb1, T omb2,
+                                        T eps, const T* alpha_dev, int64_t alpha_stride, void* stream) {
+  const bool update = x || m || v;
+  if (!g || !pgrad || !extra || !map || np < 0 || npg < 0 || (update && (!x || !m || !v || !alpha_dev)) ||
+      alpha_stride < 0) {
+    set_error("adam_step_params_extra_batch: null pointer, negative size or a negative step-size stride");
+    return ODIL_E_INVAL;
+  }
+  if (nbatch < 1 || nbatch > 65535) {
+    set_error("adam_step_params_extra_batch: %d members (1 ... 65535)", nbatch);
+    return ODIL_E_INVAL;
+  }
+  if (pgrad_stride < npg || (map_stride != 0 && map_stride < np)) {
+    set_error("adam_step_params_extra_batch: a row stride is below the length of its rows");
+    return ODIL_E_INVAL;
+  }
+  if (np == 0) return 0;
+  const dim3 grid(grid_flat(np, kBlock), (unsigned)nbatch);
+  hipLaunchKernelGGL(k_adam_params_extra_batch<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, x, m, v, g, pgrad, extra,
+                     map, np, npg, pgrad_stride, map_stride, omb1, omb2, eps, alpha_dev, alpha_stride);
+  return check_launch("k_adam_params_extra_batch");
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_axpy(T* __restrict__ y, const T* __restrict__ x, int64_t n, T a) {
   const int64_t nthreads = (int64_t)gridDim.x * kBlock;
@@ -1089,6 +1138,20 @@ int odil_adam_step_params_batch_f32(float* x, float* m, float* v, float* g, cons
                                     void* stream) {
   return adam_step_params_batch<float>(x, m, v, g, pgrad, map, nbatch, np, npg, pgrad_stride, map_stride, one_minus_b1,
                                        one_minus_b2, eps, alpha_dev, alpha_stride, stream);
+}
+int odil_adam_step_params_extra_batch_f64(double* x, double* m, double* v, double* g, const double* pgrad, double* extra,
+                                          const int* map, int nbatch, int64_t np, int npg, int64_t pgrad_stride,
+                                          int64_t map_stride, double one_minus_b1, double one_minus_b2, double eps,
+                                          const double* alpha_dev, int64_t alpha_stride, void* stream) {
+  return adam_step_params_extra_batch<double>(x, m, v, g, pgrad, extra, map, nbatch, np, npg, pgrad_stride, map_stride,
+                                              one_minus_b1, one_minus_b2, eps, alpha_dev, alpha_stride, stream);
+}
+int odil_adam_step_params_extra_batch_f32(float* x, float* m, float* v, float* g, const float* pgrad, float* extra,
+                                          const int* map, int nbatch, int64_t np, int npg, int64_t pgrad_stride,
+                                          int64_t map_stride, float one_minus_b1, float one_minus_b2, float eps,
+                                          const float* alpha_dev, int64_t alpha_stride, void* stream) {
+  return adam_step_params_extra_batch<float>(x, m, v, g, pgrad, extra, map, nbatch, np, npg, pgrad_stride, map_stride,
+                                             one_minus_b1, one_minus_b2, eps, alpha_dev, alpha_stride, stream);
 }
 int odil_narrow_scale(const double* x, float* y, int64_t n, double a, const double* msq, void* stream) {
   if (!x || !y || n < 0) {

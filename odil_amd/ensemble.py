@@ -14,17 +14,19 @@ import numpy as np
 import torch
 
 from . import gmg, ops, util
-from .core import Array, Field, Problem
+from .core import Array, Field, NeuralNet, Problem
 from .optimizer import make_optimizer
 
 # what members are compared by -> how a refusal calls it
 _LABELS = dict(shapes="level shapes", cshape="cells", dtype="dtype", device="device", spacing="grid spacing",
-               params="Array unknowns (key, position in the state, shape)")
+               params="Array unknowns (key, position in the state, shape)",
+               nets="NeuralNet unknowns (key, position in the state, layer shapes)")
 
 
 def _check_members(who, problems, states, describe, arrays_ok=False):
     """The checks both drivers open with, structure only (no operator is probed, no state changes): as many states as
-    problems, every state initialised with one unknown field (arrays_ok: `Array` unknowns beside it do not count), and
+    problems, every state initialised with one unknown field (arrays_ok: `Array` unknowns beside it do not count, nor do
+    `NeuralNet` unknowns beside a grid field under a key where member 0 has a network beside its grid field), and
     `describe(b, problem, state, refuse) -> kind`, a dict of what the members must share (keys of `_LABELS`, compared in
     its order with member 0's) -- which also makes the driver's own refusals.  `refuse(member, reason)` raises
     ValueError("<who>: member <b>: <reason>").
@@ -35,11 +37,17 @@ def _check_members(who, problems, states, describe, arrays_ok=False):
     def refuse(member, reason):
         raise ValueError("{}: member {}: {}".format(who, member, reason))
 
-    first = None
+    first, net_keys = None, set()
     for b, (problem, state) in enumerate(zip(problems, states)):
         if not state.initialized:
             refuse(b, "uninitialized state, use `state = domain.init_state(state)`")
         nfields = sum(1 for f in state.fields.values() if not (arrays_ok and isinstance(f, Array)))
+        if arrays_ok:
+            nets = [key for key, f in state.fields.items() if isinstance(f, NeuralNet)]
+            if len(nets) < nfields:  # (the state also holds a grid field)
+                if b == 0:
+                    net_keys = set(nets)
+                nfields -= sum(1 for key in nets if key in net_keys)
         if nfields != 1:
             refuse(b, "{} unknown fields (the Poisson problem has one)".format(nfields))
         kind = describe(b, problem, state, refuse)
@@ -100,8 +108,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     `ops.adam_step_batch` for level 0 -- each covering all members.  'auto' then picks by dimension ('volumes' for 3-D).
     Such members have ONE cell-centred grid unknown (and possibly `Array` unknowns: next paragraph), a plain `Field` (one
     level: no transfers, exempt from the two-level rule of the forms) or a `MultigridField` with all factors 1, on a 1-D to 3-D grid, with level shapes that
-    `fused.traced_refusal` admits; operators whose kernels have no batched form (network parameters, outputs
-    in parameter space, marching kernels) raise ValueError naming the member.  The callback's pinfo carries the member's own
+    `fused.traced_refusal` admits; operators whose kernels have no batched form (marching kernels, outputs in parameter
+    space that only the torch replay evaluates) raise ValueError naming the member.  The callback's pinfo carries the member's own
     names, terms and norms.  Epochs are replayed as a graph only when no member has host scalars (functions of
     `problem.tracers`), which travel in the argument blocks and are uploaded again when they change.  With
     form='workgroup', or without tracing, a member that is not the Poisson operator stays refused.
@@ -114,12 +122,24 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     (`ops.adam_step_params_batch`) updates the constants of all members.  The arrays returned for member b, and those its
     state holds afterwards, are all its arrays in `arrays_from_state` order, the `Array`s included, and every one ends where
     the member's own `optimize_grad` run ends, bit for bit, with Adam and with L-BFGS-B (whose member-major vectors hold the
-    constants where the single run's packed vector has them).  Not served: `NeuralNet` unknowns, outputs in parameter space
-    (a prior on the constants), marching kernels -- ValueError naming the member -- and, because a single run packs its
-    arrays back to back and its 3-D transfer kernels choose by alignment, a number of `Array` elements before a 3-D
-    multigrid field that is no multiple of 4 (put the `Array` after the field).  `optimize_newton_ensemble` keeps refusing
-    members with `Array` unknowns.
-    Returns ([arrays of member b: its level arrays; with `Array` unknowns all its arrays in state order], optinfo);
+    constants where the single run's packed vector has them).
+    `NeuralNet` unknowns (pointwise networks the residuals evaluate: the conductivity `sigmoid(MLP(u)) kmax` of
+    examples/heat) stand beside the field like the `Array`s: the same keys, positions and layer shapes for all members,
+    the same dtype and device as the field (else ValueError naming the member, before any state changes and before any
+    operator is traced); their weights and biases live in the same packed [B, P] tensors, weights then biases as
+    `arrays_from_state` has them.  Outputs in PARAMETER space -- heat's `wreg`, a weight decay, a prior on an `Array` -- are
+    evaluated by one generated launch per epoch (`k_par_batch`), their terms and norms reported at their outputs'
+    positions under the member's names.
+    Host scalars: regularisers annealed with the epoch read `ctx.tracers["epoch"]`.  The callback is where to advance
+    `problems[member].tracers["epoch"]`, exactly as the callback of a single run does (`make_callback`); such members are
+    not replayed as a graph, and their argument blocks are uploaded again when a value has changed.
+    Not served: marching kernels (float32 members of three or more dimensions with a last axis of at least 128 cells),
+    parameter-space outputs that only the torch replay evaluates (reductions, broadcasts: `param_expr.Unsupported`), Newton
+    -- ValueError naming the member -- and, because a single run packs its arrays back to back and its 3-D transfer
+    kernels choose by alignment, a number of `Array` / `NeuralNet` elements before a 3-D multigrid field that is no
+    multiple of 4 (put them after the field).  `optimize_newton_ensemble` keeps refusing members with `Array` or
+    `NeuralNet` unknowns.
+    Returns ([arrays of member b: its level arrays; with `Array` / `NeuralNet` unknowns all its arrays in state order], optinfo);
     optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route: "poisson" or "traced"; optinfo.form: the form that
     ran.
 
@@ -171,10 +191,14 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
         nonlocal form, traceable
         domain = problem.domain
         # the one grid unknown (its level arrays) and the `Array` unknowns beside it, by position in `arrays_from_state`
-        params, arrays = [], None
+        # (and the `NeuralNet` unknowns, when the state holds a grid field at all: a network alone is "the unknown")
+        params, nets, arrays = [], [], None
+        beside = any(not isinstance(field, (Array, NeuralNet)) for field in state.fields.values())
         for pos, (key, field) in enumerate(state.fields.items()):
             if isinstance(field, Array):
                 params.append((key, pos, tuple(int(n) for n in field.array.shape)))
+            elif beside and isinstance(field, NeuralNet):
+                nets.append((key, pos, [tuple(int(n) for n in a.shape) for a in domain.arrays_from_field(field)]))
             else:
                 unknown, arrays, upos = field, domain.arrays_from_field(field), pos
         shapes = [tuple(int(n) for n in a.shape) for a in arrays]
@@ -185,35 +209,41 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
             form = _traced_form(form, shapes) if lbfgsb else fused.ensemble_form(form, shapes, arrays[0].dtype)
             traceable = traceable and arrays[0].is_cuda
         reasons = dict(poisson=predicates[form](shapes, arrays[0].dtype), traced=None)
-        if params:  # (inverse problems: the traced route alone serves them)
-            reasons["poisson"] = ("{} Array unknown{} beside the field: such members run as traced operators -- form='launches', "
-                                  "'volumes' or 'auto', with operators traced and the members on a device".format(
-                                      len(params), "" if len(params) == 1 else "s"))
+        if params or nets:  # (inverse problems: the traced route alone serves them)
+            count = " and ".join("{} {} unknown{}".format(len(lst), name, "" if len(lst) == 1 else "s")
+                                 for lst, name in ((params, "Array"), (nets, "NeuralNet")) if lst)
+            reasons["poisson"] = ("{} beside the field: such members run as traced operators -- form='launches', "
+                                  "'volumes' or 'auto', with operators traced and the members on a device".format(count))
         if traceable:
             reasons["traced"] = _traced_member(domain, unknown, shapes, arrays[0].dtype, _traced_form(requested, shapes))
             ahead = sum(math.prod(shape) for _, pos, shape in params if pos < upos)
+            nets_ahead = sum(math.prod(shape) for _, pos, shapes_ in nets if pos < upos for shape in shapes_)
+            ahead += nets_ahead
             if reasons["traced"] is None and len(shapes[0]) == 3 and len(shapes) > 1 and ahead % 4:
                 # a single run packs its arrays back to back: with `ahead` elements in front, the levels of its field are
                 # not aligned to four elements, and its 3-D transfers take other kernels (other rounding) than those of
                 # the members' aligned level arrays here
-                reasons["traced"] = ("{} Array elements stand before the 3-D multigrid field: a single run's level arrays are "
+                reasons["traced"] = ("{} {} elements stand before the 3-D multigrid field: a single run's level arrays are "
                                      "then not aligned to 4 elements and its transfer kernels round differently (put the "
-                                     "Array after the field, or a multiple of 4 elements before it)".format(ahead))
-            for key, _, _ in params:
-                array = state.fields[key].array
+                                     "{} after the field, or a multiple of 4 elements before it)".format(
+                                         ahead, "Array and NeuralNet" if nets_ahead else "Array",
+                                         "NeuralNet" if nets_ahead else "Array"))
+            held = [("Array", key, state.fields[key].array) for key, _, _ in params]
+            held += [("NeuralNet", key, a) for key, _, _ in nets for a in domain.arrays_from_field(state.fields[key])]
+            for what, key, array in held:
                 if reasons["traced"] is None and (array.dtype != arrays[0].dtype or array.device != arrays[0].device):
-                    reasons["traced"] = "Array unknown '{}' is a {} tensor on {} (the field: {} on {})".format(
-                        key, array.dtype, array.device, arrays[0].dtype, arrays[0].device)
-        if params and not traceable:  # (said once the members have been compared with each other: `unserved`)
+                    reasons["traced"] = "{} unknown '{}' is a {} tensor on {} (the field: {} on {})".format(
+                        what, key, array.dtype, array.device, arrays[0].dtype, arrays[0].device)
+        if (params or nets) and not traceable:  # (said once the members have been compared with each other: `unserved`)
             unserved.append((b, reasons["poisson"]))
-        elif params and reasons["traced"] is not None:  # (the only route that serves them says why it does not)
+        elif (params or nets) and reasons["traced"] is not None:  # (the only route that serves them says why it does not)
             refuse(b, reasons["traced"])
         elif reasons["poisson"] is not None and (not traceable or reasons["traced"] is not None):
             refuse(b, reasons["poisson"])
         for route, reason in reasons.items():
             if reason is not None and late[route] is None:
                 late[route] = (b, reason)
-        return dict(shapes=shapes, params=params, dtype=arrays[0].dtype, device=arrays[0].device,
+        return dict(shapes=shapes, params=params, nets=nets, dtype=arrays[0].dtype, device=arrays[0].device,
                     spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
 
     kind, refuse = _check_members("optimize_ensemble", problems, states, describe, arrays_ok=True)
@@ -263,8 +293,9 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     def callback_wrap(epoch, losses, norms):
         if route == "traced":  # (the member's own names, terms and norms, as its `optimize_grad` run reports them)
             outs = [out.clone() for out in ensemble.outs]
+            pouts = [None if pout is None else pout.clone() for pout in ensemble.pouts]
             for b, state in enumerate(states):
-                loss, terms, member_norms = ensemble.report(b, outs)
+                loss, terms, member_norms = ensemble.report(b, outs, pouts)
                 callback(b, state, epoch, util._pinfo(loss, terms, ensemble.names[b], member_norms))
             return
         for b, state in enumerate(states):
@@ -290,7 +321,9 @@ def _lbfgsb_run(args, opt, problems, states, callback, ensemble, route, form):
     def report(b, epoch):
         if route == "traced":  # (the member's own names, terms and norms)
             k, j = ensemble.where[b]
-            loss, terms, norms = ensemble.report(b, {k: {j: ensemble.outs[k][j].clone()}})
+            pout = ensemble.pouts[k]
+            loss, terms, norms = ensemble.report(b, {k: {j: ensemble.outs[k][j].clone()}},
+                                                 None if pout is None else {k: {j: pout[j].clone()}})
             callback(b, states[b], epoch, util._pinfo(loss, terms, ensemble.names[b], norms))
         else:
             loss = ensemble.loss[b].clone()

@@ -415,7 +415,7 @@ class PoissonVolumeEnsemble(BatchedLaunches):
 
 class _Levels(list):
     """The level tensors of one packed quantity of an ensemble (x, m, v or g) with `.params`: the [B, P] tensor of the
-    members' `Array` unknowns beside them."""
+    members' `Array` and `NeuralNet` unknowns beside them."""
 
     params = None
 
@@ -445,27 +445,48 @@ class TracedLaunchEnsemble(BatchedLaunches):
          x.params, m.params, v.params of all members -- behind the gathers, which re-read the constants.
     `levels(packed, b)` gives member b's arrays in `arrays_from_state` order, `blocks(packed)` the [B, size] views an
     optimizer on member-major vectors works with, `total` counts the parameters.  Members without `Array` unknowns make
-    exactly the launches 1 - 5.  Not served: network unknowns, outputs in parameter space (priors on the constants)."""
+    exactly the launches 1 - 5.
+
+    `NeuralNet` unknowns (pointwise networks the residuals evaluate, `ctx.neural_net(key)`) are packed the same way: every
+    array of a network is a ("param", offset, shape) item of `order`, weights then biases as `arrays_from_state` has them,
+    its gradient rows are those of `pg_decl` (all `pw` groups layer by layer, then all `pb` groups; a weight matrix is
+    stored (no, ni), row j * ni + i its contiguous element), -1 in `param_rows` where no grid kernel writes one (a network
+    read only with frozen=True, an Array that appears only in a prior).  The operators are generated with batch="params".
+
+    Outputs in parameter space (a weight decay, heat's `wreg`, a prior on an Array: `TracedOperator.par_outputs`) run as
+      6a. `k_par_batch` (`EpochBatch.launch_par`), one launch per group, behind k_loss_batch: member b's terms and norms
+          into its row of the group's `pout`, the term added to its loss, its gradients added to its row of `gextra`
+          [B, P], which is zero before -- SET where no grid kernel writes (the `fresh` rule of `param_expr.emit`);
+      6b. launch 6 with `extra=gextra` (odil_adam_step_params_extra_batch): g.params = pgrad[row] + gextra, the update,
+          and gextra cleared for the next epoch
+    -- the sums of a single run (pgrad -> gviews, k_par adds, one Adam step over the packed vector), whose bits every
+    member keeps, in ONE parameter launch beside `k_par_batch`; members without such outputs keep launch 6 as it was.
+    `report` inserts the parameter-space terms and norms at their outputs' positions.
+    Not served: marching kernels, parameter-space outputs that only the torch replay evaluates."""
 
     def __init__(self, problems, states, form="launches"):
         """The members have passed the structural checks of `ensemble.optimize_ensemble` (one grid unknown, the same
-        `Array` unknowns, same level shapes, dtype and device; `traced_refusal` admits the shapes).  A member whose
+        `Array` and `NeuralNet` unknowns, same level shapes, dtype and device; `traced_refusal` admits the shapes).  A member whose
         operator has no batched kernels raises ValueError naming it."""
         from . import stencil_jit
-        from .core import Array
+        from .core import Array, NeuralNet
         from .stencil_bind import EpochBatch, field_ranges
 
         domain = problems[0].domain
         arrays = domain.arrays_from_state(states[0])
         # the state's arrays in `arrays_from_state` order: ("level", l) of the grid unknown, ("param", offset, shape) of
-        # an `Array` in the members' packed parameters
-        self.order, self.param_keys, self.nparams = [], [], 0
+        # an `Array`, or of one array of a `NeuralNet` (weights, then biases), in the members' packed parameters
+        self.order, self.param_keys, self.nparams, self.ranges = [], [], 0, []
         for key, field, pos, n in field_ranges(domain, states[0]):
-            if isinstance(field, Array):
-                shape = tuple(int(k) for k in arrays[pos].shape)
-                self.order.append(("param", self.nparams, shape))
-                self.param_keys.append((key, self.nparams, math.prod(shape)))
-                self.nparams += math.prod(shape)
+            kind = "net" if isinstance(field, NeuralNet) else "array" if isinstance(field, Array) else "grid"
+            self.ranges.append((key, kind, pos, n))
+            if isinstance(field, (Array, NeuralNet)):
+                start = self.nparams
+                for a in arrays[pos:pos + n]:
+                    shape = tuple(int(k) for k in a.shape)
+                    self.order.append(("param", self.nparams, shape))
+                    self.nparams += math.prod(shape)
+                self.param_keys.append((key, start, self.nparams - start))
             else:
                 grid_key, first = key, pos
                 self.order.extend(("level", l) for l in range(n))
@@ -480,7 +501,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
         self.traced = []
         for b, (problem, state) in enumerate(zip(problems, states)):
             try:
-                self.traced.append(stencil_jit.TracedOperator(problem, state, batch=True))
+                self.traced.append(stencil_jit.TracedOperator(problem, state, batch="params"))
             except stencil_jit.TraceUnsupported as e:
                 raise ValueError("ensemble member {}: its operator has no batched kernels ({})".format(b, e))
         self._allocate(shapes, dtype, device, [list(t.names) for t in self.traced])
@@ -492,14 +513,22 @@ class TracedLaunchEnsemble(BatchedLaunches):
         self.groups = list(by_lib.values())
         if self.param_keys:
             self._allocate_params()
-        self.outs, self.batches = [], []
+        self.outs, self.batches, self.gextra = [], [], None
         for group in self.groups:
             out = torch.zeros((len(group), 1 + 2 * self.traced[group[0]].nout), dtype=self.dtype, device=self.device)
             self.outs.append(out)
-            more = dict()
-            if self.traced[group[0]].cg.arrays:
-                more = dict(params=[{key: self.x.params[b, off:off + n] for key, off, n in self.param_keys} for b in group],
-                            pgrad=[self.pgrad[b] for b in group])
+            more, lead = dict(), self.traced[group[0]]
+            if lead.cg.arrays or lead.cg.nets:
+                more = dict(params=[self._member_params(b) for b in group], pgrad=[self.pgrad[b] for b in group])
+            if lead.par_outputs:
+                for i in lead.cg.par_index:
+                    if self.order[i][0] != "param":
+                        raise ValueError("ensemble member {}: an output in parameter space reads the grid unknown".format(group[0]))
+                if self.gextra is None:  # (what k_par_batch leaves of the parameter gradients: `_param_step` adds it)
+                    self.gextra = _Levels(self.g)
+                    self.gextra.params = torch.zeros_like(self.g.params)
+                more.update(par_vals=[[self.levels(self.x, b)[i] for i in lead.cg.par_index] for b in group],
+                            par_grads=[[self.levels(self.gextra, b)[i] for i in lead.cg.par_index] for b in group])
             self.batches.append(EpochBatch([self.traced[b] for b in group], [[self.u[b]] for b in group],
                                            [{grid_key: self.g[0][b]} for b in group], out, **more))
         self.where = dict((b, (k, j)) for k, group in enumerate(self.groups) for j, b in enumerate(group))
@@ -507,9 +536,21 @@ class TracedLaunchEnsemble(BatchedLaunches):
         if len(self.groups) == 1:  # (column 0 of the packed `out` itself: nothing to collect)
             self.loss = self.outs[0][:, 0]
         self.graphable = all(batch.graphable for batch in self.batches)
+        self.par_batches = [batch for batch in self.batches if batch.npar_out]
+
+    def _member_params(self, member):
+        """{key: member b's view(s) of its row of x.params} as `EpochBatch` takes them: one array per `Array`, the list of
+        its arrays (weights, then biases) per network."""
+        levels, res = self.levels(self.x, member), dict()
+        for key, kind, pos, n in self.ranges:
+            if kind == "net":
+                res[key] = levels[pos:pos + n]
+            elif kind == "array":
+                res[key] = levels[pos]
+        return res
 
     def _allocate_params(self):
-        """The packed state of the members' `Array` unknowns beside the level-major grid state: x, m, v, g get `.params`,
+        """The packed state of the members' `Array` and `NeuralNet` unknowns beside the level-major grid state: x, m, v, g get `.params`,
         a [B, P] tensor each (P: the elements of all Arrays, in state order); `pgrad` [B, npg]: where member b's k_loss
         leaves the gradients of the rows of its `pg_decl`; `param_rows`: packed parameter -> its row there (-1: no grid
         kernel reads that Array with a gradient), one map [P] when all members' kernels agree, else a map per member."""
@@ -545,22 +586,50 @@ class TracedLaunchEnsemble(BatchedLaunches):
                 for item in self.order]
 
     def _param_step(self, alphas=None, omb1=0.0, omb2=0.0, eps=0.0):
-        """ONE launch for the `Array` unknowns of all members, behind the gathers (which re-read the constants): the packed
-        parameter gradient from the rows k_loss_batch wrote and, with step sizes, the Adam update."""
+        """ONE launch for the `Array` and `NeuralNet` unknowns of all members, behind the gathers (which re-read them): the
+        packed parameter gradient from the rows k_loss_batch wrote -- plus what k_par_batch left in `gextra` -- and, with
+        step sizes, the Adam update."""
         if not self.nparams:
             return
+        extra = None if self.gextra is None else self.gextra.params
         if alphas is None:
-            ops.adam_step_params_batch(None, None, None, self.g.params, self.pgrad, self.param_rows)
+            ops.adam_step_params_batch(None, None, None, self.g.params, self.pgrad, self.param_rows, extra=extra)
         else:
             ops.adam_step_params_batch(self.x.params, self.m.params, self.v.params, self.g.params, self.pgrad, self.param_rows,
-                                       alphas, omb1, omb2, eps)
+                                       alphas, omb1, omb2, eps, extra=extra)
 
-    def report(self, member, outs=None):
-        """(loss, terms, norms) of `member` as the last epoch evaluated them: 0-d views of the packed `out` (outs: of
-        copies of `self.outs` instead, which later epochs do not overwrite)."""
+    def report(self, member, outs=None, pouts=None):
+        """(loss, terms, norms) of `member` as the last epoch evaluated them: 0-d views of the packed `out` (outs, pouts: of
+        copies of `self.outs` / `self.pouts` instead, which later epochs do not overwrite)."""
         k, j = self.where[member]
         row, nout = (outs or self.outs)[k][j], self.traced[member].nout
-        return row[0], [row[1 + i] for i in range(nout)], [row[1 + nout + i] for i in range(nout)]
+        terms, norms = [row[1 + i] for i in range(nout)], [row[1 + nout + i] for i in range(nout)]
+        if self.traced[member].par_outputs:  # (at their outputs' positions, as `TracedOperator.eval_loss_grad` inserts them)
+            pout = (pouts or self.pouts)[k][j]
+            for q, (at, _) in enumerate(self.traced[member].par_outputs):
+                terms.insert(at, pout[2 * q])
+                norms.insert(at, pout[2 * q + 1])
+        return row[0], terms, norms
+
+    @property
+    def pouts(self):
+        """Per group the packed [B_k, 2 npar_out] terms and norms of its outputs in parameter space, None without any."""
+        return [batch.pout for batch in self.batches]
+
+    def _evaluate(self, alphas=None, omb1=0.0, omb2=0.0, eps=0.0):
+        """Behind the gathers: the outputs in parameter space (k_par_batch adds their terms to the members' losses, which
+        are collected after it), then the parameter gradients and, with step sizes, the update of the parameters."""
+        if self.par_batches:
+            for batch in self.par_batches:
+                batch.launch_par()
+            self._collect_loss()
+        self._param_step(alphas, omb1, omb2, eps)
+
+    def _collect_loss(self):
+        """Column 0 of every group's `out` into `loss` [B] (one group: `loss` IS that column)."""
+        if len(self.groups) > 1:
+            for index, out in zip(self.index, self.outs):
+                self.loss.index_copy_(0, index, out[:, 0])
 
     def epoch(self, alphas, omb1, omb2, eps):
         """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
@@ -569,25 +638,23 @@ class TracedLaunchEnsemble(BatchedLaunches):
             ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
         for batch in self.batches:
             batch.launch()
-        if len(self.groups) > 1:
-            for index, out in zip(self.index, self.outs):
-                self.loss.index_copy_(0, index, out[:, 0])
+        if not self.par_batches:
+            self._collect_loss()
         if self.nlvl > 1:
             chain = ops.mg_synth_adj_adam_volumes if self.ndim == 3 else ops.mg_synth_adj_adam_batch
             chain(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
         ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], alphas, omb1, omb2, eps)
-        self._param_step(alphas, omb1, omb2, eps)
+        self._evaluate(alphas, omb1, omb2, eps)
 
     def loss_grad(self):
         if self.nlvl > 1:
             ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
         for batch in self.batches:
             batch.launch()
-        if len(self.groups) > 1:
-            for index, out in zip(self.index, self.outs):
-                self.loss.index_copy_(0, index, out[:, 0])
+        if not self.par_batches:
+            self._collect_loss()
         self._transposes()
-        self._param_step()
+        self._evaluate()
 
 
 def traced_refusal(shapes, dtype, form, nbatch=1):

@@ -1221,11 +1221,13 @@ def param_rows(rows, npg, device):
     return rows.to(torch.int32).contiguous().to(device)
 
 
-def adam_step_params_batch(x, m, v, g, pgrad, rows, alphas=None, one_minus_b1=0.0, one_minus_b2=0.0, eps=0.0):
+def adam_step_params_batch(x, m, v, g, pgrad, rows, alphas=None, one_minus_b1=0.0, one_minus_b2=0.0, eps=0.0, extra=None):
     """The Array unknowns of the B members of an ensemble in ONE launch: g[b, p] = pgrad[b, rows[p]] (0 where rows[p] is
     -1) and `adam_step` of x, m, v [B, P] with that gradient.  pgrad: [B, npg] (rows contiguous, any row stride >= npg);
     rows: `param_rows` ([P], or [B, P]); alphas: DEVICE step sizes, [B] or one element (shared).  x, m, v all None: only
-    g is formed.  Member b gets the bits of `adam_step` on its own arrays."""
+    g is formed.  Member b gets the bits of `adam_step` on its own arrays.
+    extra [B, P] (odil_adam_step_params_extra_batch): the part of the gradient a generated `k_par_batch` left, added to
+    the rows' before the update and cleared by the launch."""
     nb, npar = int(g.shape[0]), int(g.shape[1])
     assert g.dim() == 2 and g.is_contiguous() and g.dtype == pgrad.dtype
     assert pgrad.dim() == 2 and pgrad.shape[0] == nb and (pgrad.shape[1] == 0 or pgrad.stride(1) == 1) and pgrad.is_cuda
@@ -1236,8 +1238,12 @@ def adam_step_params_batch(x, m, v, g, pgrad, rows, alphas=None, one_minus_b1=0.
         assert all(t is not None and t.shape == g.shape and t.dtype == g.dtype and t.is_contiguous() for t in (x, m, v))
         assert alphas.dtype == g.dtype and alphas.is_cuda and alphas.numel() in (1, nb) and alphas.is_contiguous()
     pstride = max(int(pgrad.stride(0)), int(pgrad.shape[1])) if nb > 1 else int(pgrad.shape[1])
-    call("adam_step_params_batch", g.dtype, ptr(x), ptr(m), ptr(v), ptr(g), c_void_p(pgrad.data_ptr()), ptr(rows), c_int(nb),
-         c_int64(npar), c_int(int(pgrad.shape[1])), c_int64(pstride), c_int64(npar if rows.dim() == 2 else 0),
+    more = ()
+    if extra is not None:
+        assert extra.shape == g.shape and extra.dtype == g.dtype and extra.is_contiguous() and extra.is_cuda
+        more = (ptr(extra),)
+    call("adam_step_params_extra_batch" if more else "adam_step_params_batch", g.dtype, ptr(x), ptr(m), ptr(v), ptr(g),
+         c_void_p(pgrad.data_ptr()), *more, ptr(rows), c_int(nb), c_int64(npar), c_int(int(pgrad.shape[1])), c_int64(pstride), c_int64(npar if rows.dim() == 2 else 0),
          float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas) if update else None,
          c_int64(1 if update and alphas.numel() == nb and nb > 1 else 0), stream_ptr())
 

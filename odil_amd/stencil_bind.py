@@ -22,7 +22,8 @@ _ADAM = [_P] * 3 + [ctypes.c_double] * 4 + [_P]  # x, m, v, alpha, 1 - beta_1, 1
 _ARGTYPES = dict(  # (launchers of stencil_codegen._launchers; all end with the stream)
     jit_fwd=[_P, _P], jit_gather=[ctypes.c_int, _P, _P, _P], jit_gather_adam=[ctypes.c_int, _P, _P] + _ADAM + [_P],
     jit_gather_all=[_P] + [_PP] * 4 + _ADAM[3:] + [_P], jit_jac=[_P, _PP, _P], jit_jac_batch=[_P, _P, ctypes.c_int, _P],
-    jit_par=[_P, _P, _P], jit_fwd_batch=[_P, ctypes.c_int, _P], jit_gather_batch=[ctypes.c_int, _P, _P, ctypes.c_int, _P])
+    jit_par=[_P, _P, _P], jit_par_batch=[_P, _P, ctypes.c_int, _P], jit_fwd_batch=[_P, ctypes.c_int, _P],
+    jit_gather_batch=[ctypes.c_int, _P, _P, ctypes.c_int, _P])
 
 
 def field_ranges(domain, state):
@@ -58,7 +59,7 @@ class StencilBinding:
         from .core import Array, NeuralNet
         from .stencil_trace import TraceUnsupported
 
-        if batch and tr.offgrid:
+        if batch and batch != "params" and tr.offgrid:
             raise TraceUnsupported("batched forward kernel: outputs in parameter space")
 
         domain = problem.domain
@@ -74,6 +75,8 @@ class StencilBinding:
             try:
                 self.par_outputs = param_expr.convert(tr.param_tape, self.offgrid, numel)
             except param_expr.Unsupported as e:
+                if batch:  # (the torch replay of a single run has no batched form)
+                    raise TraceUnsupported("batched parameter kernel: parameter-space output evaluated by torch ({})".format(e))
                 par_refused(e)
         if self.par_outputs is not None:
             cg.parameter_outputs(self.par_outputs, numel, {
@@ -284,18 +287,24 @@ class EpochBatch:
     evaluates for the members that have any and compares with what the device holds.  Members without host scalars cost
     no host time per epoch, and their launches can be captured into a graph (`graphable`).  `Array` unknowns that the
     kernels read change nothing in that: member b's `args.par` points at its rows of packed parameter tensors, `args.ppart`
-    and `args.pgrad` at its rows of packed partial sums and parameter gradients."""
+    and `args.pgrad` at its rows of packed partial sums and parameter gradients.  `NeuralNet` unknowns are such parameter
+    arrays too (generated with batch="params"): per network its weights, then its biases, then the Arrays, the order of
+    `a.par` in a single run.  Outputs in parameter space (`cg.par_outputs`): every member also has a `ParArgs` block -- val
+    / grad: its slices of the packed parameters and of their gradients, pout: its row of a packed [B, 2 npar_out] tensor
+    held here -- staged with the argument blocks, and `launch_par` runs `k_par_batch` of all members."""
 
     depth = 4
 
-    def __init__(self, members, sources, grads, out, params=None, pgrad=None):
+    def __init__(self, members, sources, grads, out, params=None, pgrad=None, par_vals=None, par_grads=None):
         """members: the `TracedOperator`s of one group, in the order of the launch.  sources[b]: the contiguous arrays
         member b reads, in the order of `cg.src_keys`; grads[b]: {field key: the contiguous array its gradient goes to};
         out: [B, 1 + 2 nout] contiguous, B the number of members here.  The caller keeps all of them alive.
         Members whose kernels read `Array` unknowns (`cg.arrays`): params[b]: {Array key: the contiguous array member b
         reads it from -- its row of a packed tensor}; pgrad[b]: the contiguous row of at least len(cg.pg_decl) elements its
         k_loss writes the parameter gradients to, in the order of `cg.pg_decl`.  The partial sums of those rows (`ppart`)
-        are one packed [B, npg * nblocks] buffer held here."""
+        are one packed [B, npg * nblocks] buffer held here.  For a network, params[b][key] is the list of its arrays
+        (weights, then biases).  par_vals[b] / par_grads[b] (outputs in parameter space): the contiguous arrays of
+        `cg.par_index`, in that order, and where their gradients go."""
         first = members[0]
         if any(m.lib_path != first.lib_path for m in members):
             raise ValueError("EpochBatch: members of one launch share one generated library")
@@ -314,28 +323,65 @@ class EpochBatch:
         self.which = ([-1] if cg.merged else []) + [gi for gi, key in enumerate(cg.gathers) if key not in cg.merged]
         self.ptrs = []
         npg = len(cg.pg_decl)
-        if cg.nets or (cg.arrays and (params is None or pgrad is None)):
-            raise RuntimeError("EpochBatch: kernels that read parameter arrays need `params` and `pgrad` (Array unknowns only)")
-        self.ppart = torch.empty((nb, max(1, npg * cg.fwd_blocks)), dtype=first.dtype, device=out.device) if cg.arrays else None
+        reads_params = bool(cg.nets or cg.arrays)
+        if reads_params and (params is None or pgrad is None):
+            raise RuntimeError("EpochBatch: kernels that read parameter arrays need `params` and `pgrad`")
+        self.ppart = torch.empty((nb, max(1, npg * cg.fwd_blocks)), dtype=first.dtype, device=out.device) if npg else None
+        self.npar_out = len(first.par_outputs or ())
+        self.pargs, self.pout, self.psize = [], None, 0
+        if self.npar_out:
+            if not hasattr(first.lib, "jit_par_batch"):
+                raise RuntimeError("these kernels were generated without the batched parameter kernel (batch=\"params\")")
+            if par_vals is None or par_grads is None:
+                raise RuntimeError("EpochBatch: outputs in parameter space need `par_vals` and `par_grads`")
+            self.pout = torch.zeros((nb, 2 * self.npar_out), dtype=first.dtype, device=out.device)
+            self.psize = ctypes.sizeof(first.par_args)
+        # the parameter arrays in the order of `a.par`: per network its weights then its biases, then the Arrays
+        layout = [(key, [ni * no for ni, no in zip(layers[:-1], layers[1:])] + list(layers[1:])) for key, layers in cg.nets]
+        layout += [(key, [numel]) for key, numel in cg.arrays]
         for b, member in enumerate(members):
             if member.nblocks != cg.fwd_blocks or len(sources[b]) != len(cg.src_keys):
                 raise RuntimeError("EpochBatch: member {} does not match the generated launch".format(b))
             for t in list(sources[b]) + list(grads[b].values()):
                 if not t.is_contiguous() or t.dtype != member.dtype or not t.is_cuda:
                     raise RuntimeError("EpochBatch: sources and gradients are contiguous {} arrays on the device".format(member.dtype))
-            if cg.arrays:
-                if len(member.cg.pg_decl) != npg or [n for _, n in member.cg.arrays] != [n for _, n in cg.arrays]:
+            if reads_params:
+                if (len(member.cg.pg_decl) != npg or [n for _, n in member.cg.arrays] != [n for _, n in cg.arrays]
+                        or [tuple(l) for _, l in member.cg.nets] != [tuple(l) for _, l in cg.nets]):
                     raise RuntimeError("EpochBatch: member {} does not match the generated launch".format(b))
                 row = pgrad[b]
-                for t, least in [(params[b][key], numel) for key, numel in cg.arrays] + [(row, npg)]:
+                held = []
+                for key, numels in layout:
+                    given = params[b][key]
+                    given = list(given) if isinstance(given, (list, tuple)) else [given]
+                    if len(given) != len(numels):
+                        raise RuntimeError("EpochBatch: member {}: '{}' has {} parameter arrays, the kernels read {}".format(
+                            b, key, len(given), len(numels)))
+                    held += list(zip(given, numels))
+                for t, least in held + [(row, npg)]:
                     if not t.is_contiguous() or t.dtype != member.dtype or not t.is_cuda or t.numel() < least:
-                        raise RuntimeError("EpochBatch: Array unknowns and their gradient rows are contiguous {} arrays on the "
+                        raise RuntimeError("EpochBatch: parameter arrays and their gradient rows are contiguous {} arrays on the "
                                            "device, no shorter than the kernels index them".format(member.dtype))
-                for i, (key, _) in enumerate(cg.arrays):  # (no network arrays before them: `cg.nets` is empty)
-                    member.args.par[i] = params[b][key].data_ptr()
-                member.args.ppart, member.args.pgrad = self.ppart[b].data_ptr(), row.data_ptr()
+                assert len(held) == cg.par_arrays
+                for i, (t, _) in enumerate(held):
+                    member.args.par[i] = t.data_ptr()
+                member.args.pgrad = row.data_ptr()
+                if npg:
+                    member.args.ppart = self.ppart[b].data_ptr()
                 if member.part2.numel() < 16 * (member.nout + npg):  # (SEG partial sums per row of k_final)
                     raise RuntimeError("EpochBatch: member {}: `part2` is shorter than the rows of k_final".format(b))
+            if self.npar_out:
+                index = cg.par_index
+                if member.cg.par_index != index or len(par_vals[b]) != len(index) or len(par_grads[b]) != len(index):
+                    raise RuntimeError("EpochBatch: member {} does not match the generated parameter kernel".format(b))
+                for s_, (i, val, grad) in enumerate(zip(index, par_vals[b], par_grads[b])):
+                    for t in (val, grad):
+                        if not t.is_contiguous() or t.dtype != member.dtype or not t.is_cuda or t.numel() < cg.par_numel[i]:
+                            raise RuntimeError("EpochBatch: the arrays of the parameter kernel and their gradients are contiguous "
+                                               "{} arrays on the device, no shorter than it indexes them".format(member.dtype))
+                    member.par_args.val[s_], member.par_args.grad[s_] = val.data_ptr(), grad.data_ptr()
+                member.par_args.pout = self.pout[b].data_ptr()
+                self.pargs.append(member.par_args)
             for i, t in enumerate(sources[b]):
                 member.args.src[i] = t.data_ptr()
             member.args.out, member.args.hs = out[b].data_ptr(), None
@@ -348,7 +394,8 @@ class EpochBatch:
             self.ptrs.append(p)
         self.hs_members = [b for b, member in enumerate(members) if member.cg.hs]
         self.graphable = not self.hs_members
-        self.ring = _StagingRing(self.abytes + nb * self.gsize, out.device, self.depth)
+        self.gbytes = nb * self.gsize  # (a multiple of 8 too; the ParArgs blocks follow)
+        self.ring = _StagingRing(self.abytes + self.gbytes + nb * self.psize, out.device, self.depth)
         self.slot, self.dev, self.hs_values = None, None, dict()
         self.uploads, self.launches, self.host_seconds = 0, 0, 0.0  # blocks staged, calls of `launch`, host time in them
 
@@ -361,6 +408,8 @@ class EpochBatch:
         for b, (member, p) in enumerate(zip(self.members, self.ptrs)):
             ctypes.memmove(base + b * self.asize, ctypes.addressof(member.args), self.asize)
             ctypes.memmove(base + self.abytes + b * self.gsize, ctypes.addressof(p), self.gsize)
+        for b, pa in enumerate(self.pargs):
+            ctypes.memmove(base + self.abytes + self.gbytes + b * self.psize, ctypes.addressof(pa), self.psize)
         self.dev = self.ring.upload(slot)
         self.uploads += 1
 
@@ -387,4 +436,17 @@ class EpochBatch:
             if rc != 0:
                 raise RuntimeError("generated kernel launch failed (jit_gather_batch {}): hip error {}".format(which, rc))
         self.launches += 1
+        self.host_seconds += time.perf_counter() - t0
+
+    def launch_par(self):
+        """k_par_batch of all members on the current stream, behind `launch` (which staged the blocks and the host scalars
+        of this epoch) and behind whatever forms the gradients it adds to."""
+        if not self.npar_out:
+            return
+        if self.dev is None:
+            raise RuntimeError("EpochBatch: `launch_par` runs behind `launch`, which stages the argument blocks")
+        t0 = time.perf_counter()
+        rc = self.lib.jit_par_batch(self.dev, self.dev + self.abytes + self.gbytes, self.nb, ops.stream_ptr())
+        if rc != 0:
+            raise RuntimeError("generated kernel launch failed (jit_par_batch): hip error {}".format(rc))
         self.host_seconds += time.perf_counter() - t0

@@ -242,7 +242,9 @@ class _Codegen(_MarchKernels, _GatherKernels):
         same body for the members of an ensemble in one launch (a library of its own: what True emits does not change).
         batch: also emit the forward and gather kernels for the members of an ensemble in one launch each (`k_fwd_batch`,
         `k_final_batch`, `k_loss_batch`, `k_gat_*_batch`: `_epoch_batch_kernels`) -- again a library of its own; refused
-        (TraceUnsupported) for every kernel form that is no pointwise body under a new head.
+        (TraceUnsupported) for every kernel form that is no pointwise body under a new head.  batch="params": what True
+        emits, and pointwise network bodies and outputs in parameter space (`k_par_batch`) admitted as well -- for an
+        operator with neither, the same bytes as True.
         slab = (axis, n): the kernels of ONE RANK of a slab decomposition along grid axis `axis` (n owned
         cells of it per rank; odil_amd/slab_traced.py).  Threads then cover the owned cells only; the index of
         that axis seen by index leaves, constant arrays and windows is the GLOBAL one (i + a.off); sources are
@@ -278,7 +280,7 @@ class _Codegen(_MarchKernels, _GatherKernels):
         self.want_jac, self.jac_batch = bool(jac), jac == "batch"
         if self.jac_batch and slab is not None:
             raise TraceUnsupported("batched Jacobian kernel of a slab rank")
-        self.epoch_batch = bool(batch)
+        self.epoch_batch, self.batch_params = bool(batch), batch == "params"
         if self.epoch_batch and slab is not None:
             raise TraceUnsupported("batched forward and gather kernels of a slab rank")
         self.par_outputs, self.par_numel, self.par_keys = None, dict(), dict()  # (parameter_outputs)
@@ -1740,7 +1742,10 @@ class _Codegen(_MarchKernels, _GatherKernels):
             from . import param_expr
 
             fresh = {i for i, key in self.par_keys.items() if key not in self.pgrads}
+            first_par = len(S)
             param_expr.emit(self, S, self.par_outputs, fresh)
+            if self.epoch_batch:
+                self._par_batch_kernel(S, S[first_par:])
         # launchers
         S.append('extern "C" int jit_fwd(const Args* a, void* stream) {')
         S.append("  hipLaunchKernelGGL(k_fwd, dim3(a->nblocks), dim3({}), 0, (hipStream_t)stream, *a);".format(self.fwd_threads))

@@ -375,6 +375,11 @@ class _GatherKernels:
         # (`Array` unknowns pass: member b's `a.par`, `a.ppart` and `a.pgrad` are its own, and the rows of `pg_decl` are
         # reduced by the bodies of k_final / k_loss like the outputs' -- stencil_bind.EpochBatch; a network's parameter
         # arrays and their hundreds of rows have no packed home there)
+        # batch="params": they have one -- a network's arrays are slices of the member's row of the packed parameters like
+        # the Arrays (`W` / `Bv` read `a.par` of the member's block: no marching kernel here, so `wregs` is "mem"), and the
+        # outputs in parameter space run as `k_par_batch`
+        if self.batch_params:
+            return
         if self.nets:
             raise TraceUnsupported("batched forward kernel: network or Array parameters (parameter gradients reduced over "
                                    "the grid)")
@@ -446,6 +451,28 @@ class _GatherKernels:
                 S.append("  ga.g[{0}] = gp.g[{1}]; ga.ad[{0}] = ad;".format(k, self.gathers.index(key)))
             S.extend(gathers["k_gat_all"][1])
 
+    def _par_batch_kernel(self, S, par_lines):
+        """`k_par_batch` and `jit_par_batch`: the body of `k_par` (param_expr.emit: its lines as emitted, after the
+        signature) for the B members of an ensemble.  `k_par` is ONE workgroup, so the member is blockIdx.x; its `Args`
+        and its `ParArgs` (val / grad: its slices of the packed parameters and their gradients, pout: its row of the packed
+        terms and norms) are read from DEVICE memory through the constant address space into by-value copies, as the other
+        batched kernels read theirs; the host scalars travel in the member's `Args`."""
+        body = self._kernel_bodies(par_lines)["k_par"][1]
+        S.append("typedef const __attribute__((address_space(4))) ParArgs ParArgsC;")
+        S.append('extern "C" __global__ __launch_bounds__(NB) void k_par_batch(const Args* __restrict__ ab, '
+                 'const ParArgs* __restrict__ pb) {')
+        S.append("  Args a;")
+        S.append("  __builtin_memcpy(&a, (ArgsC*)(ab + blockIdx.x), sizeof(Args));")
+        S.append("  ParArgs pa;")
+        S.append("  __builtin_memcpy(&pa, (ParArgsC*)(pb + blockIdx.x), sizeof(ParArgs));")
+        S.extend(body)
+        S.append('extern "C" int jit_par_batch(const void* args_dev, const void* pargs_dev, int nmembers, void* stream) {')
+        S.append("  if (nmembers < 1 || nmembers > 65535) return -1;")
+        S.append("  hipLaunchKernelGGL(k_par_batch, dim3(nmembers), dim3(NB), 0, (hipStream_t)stream, (const Args*)args_dev, "
+                 "(const ParArgs*)pargs_dev);")
+        S.append("  return (int)hipGetLastError();")
+        S.append("}")
+
     def _epoch_batch_launchers(self, S, nout):
         """`jit_fwd_batch`, `jit_gather_batch` (which = -1: the merged gather): args_dev / ptrs_dev are `nmembers` argument
         blocks / `GatB` back to back in DEVICE memory."""
@@ -455,7 +482,7 @@ class _GatherKernels:
         S.append("  hipLaunchKernelGGL(k_fwd_batch, dim3({}, nmembers), dim3({}), 0, (hipStream_t)stream, ab);".format(
             self.fwd_blocks, self.fwd_threads))
         S.append("  hipLaunchKernelGGL(k_final_batch, dim3({}, SEG, nmembers), dim3(NB), 0, (hipStream_t)stream, ab);".format(
-            nout + len(self.pg_decl)))  # (the rows of k_final: the outputs, then the parameter gradients of `Array` unknowns)
+            nout + len(self.pg_decl)))  # (the rows of k_final: the outputs, then the parameter gradients of networks and `Array` unknowns)
         S.append("  hipLaunchKernelGGL(k_loss_batch, dim3(nmembers), dim3(64), 0, (hipStream_t)stream, ab);")
         S.append("  return (int)hipGetLastError();")
         S.append("}")
