@@ -788,6 +788,32 @@ int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, con
                                        int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
                                        float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
                                        void* stream);
+/* The transposed prolongation chain for the STACKED rows of an ensemble: [nrows, *shape] level arrays (contiguous, layout
+ * '.' + loc) of 1-D to 3-D rows with ANY loc of 'c' / 'n' -- the F grid unknowns of B members as nrows = F B rows, row
+ * f B + b.  `shapes` are the nlvl x ndim extents of ONE row.  One launch per level for all rows; the Adam update of the
+ * levels >= 1 runs in the launch that forms their gradient, row r with the step size alpha_dev[(r % period) *
+ * alpha_stride] (period 0: r itself; alpha_stride 0: one step size for all rows).  x = m = v = NULL: the gradients alone
+ * (entry 0 of grads, x, m, v is never touched: the chain reads gu).  A level whose single transpose is the fast or a
+ * cell-centred marching kernel runs that kernel on all rows; one whose single transpose is the node-centred marching
+ * kernel ('ncc' with four coarse planes or more) runs that kernel row by row, the row on a grid dimension; a level whose
+ * single transpose is the generic kernel (a node-centred y or x axis: 'nc', 'cn', 'nn', 'n') runs k_interp_adj_members,
+ * the generic kernel's sum per coarse value with the row on a grid dimension and the update in the same thread.  Per row
+ * the gradients are the bits of odil_mg_synth_adj on that row alone, x, m, v those of odil_adam_step.
+ * Refused before anything is launched: null pointers, nrows outside 1 ... 65535, ndim outside 1 ... 3, a loc with '.',
+ * fewer than two levels, gradient arrays off the 16-byte grid, a negative stride or period, and rows one of whose levels
+ * would not compute what that level of a single row computes.
+ * odil_mg_members_levels_ok answers the last question -- for this chain and for the prolongation odil_mg_synth runs on
+ * the same arrays, whose kernels all sum in the reference's order -- from shapes, loc, nrows and the element size alone
+ * (0: they do; else the reason is the error text). */
+int odil_mg_members_levels_ok(const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows, int elem_size);
+int odil_mg_synth_adj_adam_members_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       const char* loc, int nrows, double* const* x, double* const* m, double* const* v,
+                                       double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                       int64_t alpha_stride, int64_t period, void* stream);
+int odil_mg_synth_adj_adam_members_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       const char* loc, int nrows, float* const* x, float* const* m, float* const* v,
+                                       float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
+                                       int64_t alpha_stride, int64_t period, void* stream);
 /* The stencil adjoint of all members WITHOUT an update (the gradient of an ensemble whose optimizer is not Adam):
  * gu[b] = odil_poisson_adjoint of fu[b] for nbatch 1-D, 2-D or 3-D members in one launch, member b = blockIdx.y on the
  * single kernel's walk, bit for bit.  Strides as above (>= cells of a member, multiples of 16 bytes).  Refused before

@@ -338,7 +338,16 @@ struct AdamArgs {
   // canonical axis of the transfer kernels that counts the members when alpha_stride != 0: 1 ('.cc'), 2 ('.c'), or
   // 0 ('.ccc': the leading volumes of the marching kernels)
   int member_axis;
+  // stacked ensembles (the rows of several fields of B members, row f * B + b): row r reads the step size of row
+  // r % alpha_period; 0: every row its own
+  int64_t alpha_period;
 };
+
+// The entry of the step-size table that row `member` of an ensemble reads.
+template <typename T>
+ODIL_HD inline int64_t adam_alpha_row(const AdamArgs<T>& a, int64_t member) {
+  return a.alpha_period ? member % a.alpha_period : member;
+}
 
 #ifdef __HIPCC__
 template <typename T>
@@ -346,7 +355,7 @@ __device__ inline void adam_update(T& x, T& m, T& v, T g, const AdamArgs<T>& a, 
   // reference optimizer.py:316-318
   m = m + (g - m) * a.omb1;
   v = v + (g * g - v) * a.omb2;
-  const T alpha = a.alpha_dev ? a.alpha_dev[member * a.alpha_stride] : a.alpha;
+  const T alpha = a.alpha_dev ? a.alpha_dev[adam_alpha_row(a, member) * a.alpha_stride] : a.alpha;
   x = x - (m * alpha) / (sqrt(v) + a.eps);
 }
 #endif

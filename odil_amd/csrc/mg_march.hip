@@ -1044,7 +1044,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_tile(const T* __restrict_
   gfine += fvol;
   c.gfine = gfine, c.gcoarse = gcoarse + cvol, c.gscaled = gscaled ? gscaled + cvol : nullptr;
   if (ad.x) ad.x += cvol, ad.m += cvol, ad.v += cvol;
-  if (ad.alpha_dev) ad.alpha_dev += (int64_t)blockIdx.y * ad.alpha_stride;  // (an ensemble: the volume's own step size)
+  if (ad.alpha_dev) ad.alpha_dev += adam_alpha_row(ad, blockIdx.y) * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   c.scale = scale;
   c.z0 = z0;
   tile_column(c.lx, c.ly);
@@ -1350,9 +1350,9 @@ __global__ __launch_bounds__(kBlock) void k_poisson_adjoint_tile(const T* __rest
 // P^T with a node-centred marching axis: coarse plane J collects fine plane 2J and half of the
 // fine planes 2J-1 and 2J+1, each reduced over its (y, x) window with the two-cell-axis ghost rule.
 template <typename T, int CX>
-__global__ __launch_bounds__(kBlock) void k_interp_adj_march_n(const T* __restrict__ gfine, T* __restrict__ gcoarse,
-                                                               T* __restrict__ gscaled, MarchArgs a, T scale,
-                                                               AdamArgs<T> ad) {
+__device__ __forceinline__ void march_n_column(const T* __restrict__ gfine, T* __restrict__ gcoarse,
+                                               T* __restrict__ gscaled, const MarchArgs& a, T scale,
+                                               const AdamArgs<T>& ad) {
   const int cny = a.cn[1], cnx = a.cn[2];
   const int fnz = a.fn[0], fny = a.fn[1], fnx = a.fn[2];
   const int64_t cplane = (int64_t)cny * cnx, fplane = (int64_t)fny * fnx;
@@ -1388,6 +1388,25 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_march_n(const T* __restri
   }
 }
 
+template <typename T, int CX>
+__global__ __launch_bounds__(kBlock) void k_interp_adj_march_n(const T* __restrict__ gfine, T* __restrict__ gcoarse,
+                                                               T* __restrict__ gscaled, MarchArgs a, T scale,
+                                                               AdamArgs<T> ad) {
+  march_n_column<T, CX>(gfine, gcoarse, gscaled, a, scale, ad);
+}
+
+// The same for the rows of a stacked ensemble ([R, *shape] arrays of 'ncc' volumes): row blockIdx.y walks the columns of
+// k_interp_adj_march_n on its own volume, with its own step size.  The z chunks are those of ONE volume.
+template <typename T, int CX>
+__global__ __launch_bounds__(kBlock) void k_interp_adj_march_n_rows(const T* __restrict__ gfine, T* __restrict__ gcoarse,
+                                                                    MarchArgs a, AdamArgs<T> ad) {
+  const int64_t row = blockIdx.y;
+  const int64_t cvol = (int64_t)a.cn[0] * a.cn[1] * a.cn[2], fvol = (int64_t)a.fn[0] * a.fn[1] * a.fn[2];
+  if (ad.x) ad.x += row * cvol, ad.m += row * cvol, ad.v += row * cvol;
+  if (ad.alpha_dev) ad.alpha_dev += adam_alpha_row(ad, row) * ad.alpha_stride;
+  march_n_column<T, CX>(gfine + row * fvol, gcoarse + row * cvol, nullptr, a, T(1), ad);
+}
+
 // P^T for the 4-D layouts: coarse volume J0 (blockIdx.y) collects the fine volumes 2 J0 and, halved,
 // 2 J0 +- 1 on a node-centred leading axis (volume J0 alone on a batch axis); one z-window of plane
 // sums per contributing fine volume.
@@ -1403,7 +1422,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_march_lead(const T* __res
   const bool node = a.lead_loc == kNode;
   int z0, z1, jy, jx0;
   if (!march_decode<CX>(a, z0, z1, jy, jx0)) return;
-  if (ad.alpha_dev) ad.alpha_dev += (int64_t)J0 * ad.alpha_stride;  // (an ensemble: the volume's own step size)
+  if (ad.alpha_dev) ad.alpha_dev += adam_alpha_row(ad, J0) * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   Adj6 ax[CX];
   column_taps<CX>(jx0, cnx, ax);
   const Adj6 ay = adj6(jy, cny);
@@ -1749,7 +1768,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_rows(const float* __restr
   const int64_t r = w / a.nzg;
   const int yc = (int)(r % a.nyc);
   const int64_t lead = r / a.nyc;
-  if (ad.alpha_dev) ad.alpha_dev += lead * ad.alpha_stride;  // (an ensemble: the volume's own step size)
+  if (ad.alpha_dev) ad.alpha_dev += adam_alpha_row(ad, lead) * ad.alpha_stride;  // (an ensemble: the volume's own step size)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane >> a.lxlog, lx = lane & ((1 << a.lxlog) - 1), pw = 64 >> a.lxlog;
   const int cz_first = (zg * (kBlock / 64) + wave) * pw;
@@ -1901,6 +1920,25 @@ int interp_adj_kind(const InterpArgs& a) {
 }
 template int interp_adj_kind<double>(const InterpArgs&);
 template int interp_adj_kind<float>(const InterpArgs&);
+
+// P^T of `nrows` stacked 'ncc' volumes whose single transpose is k_interp_adj_march_n (`one`: the layout of ONE volume):
+// 1 when launched, 0 when a single volume would not run that kernel, < 0 on error.
+template <typename T>
+int interp_adj_march_n_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
+                            const AdamArgs<T>& ad) {
+  MarchArgs m;
+  if (one.fn[0] != 1 || one.loc[1] != kNode || nrows < 1 || nrows > 65535 || !march_cx<T>(one, gfine, nullptr) ||
+      !march_setup(m, one, 1, adj_small_level(one) ? ODIL_ADJ_UNITS_SMALL : ODIL_ADJ_UNITS))
+    return 0;
+  const dim3 grid(unit_grid(m.usched), nrows);
+  hipLaunchKernelGGL((k_interp_adj_march_n_rows<T, 1>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, m, ad);
+  const int e = check_launch("k_interp_adj_march_n_rows");
+  return e ? e : 1;
+}
+template int interp_adj_march_n_rows<double>(const double*, double*, const InterpArgs&, int, hipStream_t,
+                                             const AdamArgs<double>&);
+template int interp_adj_march_n_rows<float>(const float*, float*, const InterpArgs&, int, hipStream_t,
+                                            const AdamArgs<float>&);
 
 template <typename T, int CX>
 static int adj_launch(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& a, T scale, hipStream_t stream,

@@ -163,4 +163,10 @@ enum AdjKind { kAdjGeneric = 0, kAdjFast, kAdjNode, kAdjRows, kAdjTile, kAdjMarc
 template <typename T>
 int interp_adj_kind(const InterpArgs& a);
 
+// P^T of `nrows` stacked 'ncc' volumes ([nrows, *shape] arrays) through the node-centred marching kernel ONE volume of
+// the layout `one` runs (kAdjNode), row by row on blockIdx.y: 1 when launched, 0 when not that case, < 0 on error.
+template <typename T>
+int interp_adj_march_n_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
+                            const AdamArgs<T>& ad);
+
 }  // namespace odil

@@ -402,6 +402,63 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_lead_node_wide(const T* _
   if (gscaled) *reinterpret_cast<VT*>(gscaled + J * vol + r) = sc;
 }
 
+// ------------------------------------------------------------------------------------
+// P^T of the layouts the generic kernel serves (a node-centred y or x axis: 'nc', 'cn', 'nn', 'n', ...) for the R rows of
+// [R, *shape] level arrays at once, with the update of the coarse level in the thread that forms its gradient.  The row
+// is blockIdx.y; the coarse elements of a row are numbered flat over blockIdx.x, so coarse rows of 3, 5 or 9 elements
+// fill the lanes like any other (no lane is parked behind the end of a short row, none walks a tail).  Every coarse
+// value is the sum of k_interp_adj over the same window in the same order: the bits of the generic kernel on that row alone.
+// ------------------------------------------------------------------------------------
+struct MemberArgs {
+  int cn[3], fn[3];  // the last three canonical axes of ONE row (leading ones of extent 1, loc '.')
+  int loc[3];
+  int64_t ccells, fcells;  // elements of a coarse / fine row
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_interp_adj_members(const T* __restrict__ gfine, T* __restrict__ gcoarse,
+                                                               MemberArgs a, AdamArgs<T> ad) {
+  const int64_t flat = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (flat >= a.ccells) return;
+  const int64_t row = blockIdx.y;
+  const int plane = a.cn[1] * a.cn[2];
+  const int at = (int)flat;
+  const int c1 = at / plane, r = at - c1 * plane, c2 = r / a.cn[2], c3 = r - c2 * a.cn[2];
+  const int64_t fs2 = a.fn[2], fs1 = (int64_t)a.fn[1] * fs2;
+  const AdjTaps t1 = make_adj_taps(a.loc[0], c1, a.cn[0], a.fn[0]);
+  const AdjTaps t2 = make_adj_taps(a.loc[1], c2, a.cn[1], a.fn[1]);
+  const AdjTaps t3 = make_adj_taps(a.loc[2], c3, a.cn[2], a.fn[2]);
+  const bool special = t1.special || t2.special || t3.special;
+  const T* __restrict__ gf = gfine + row * a.fcells;
+  T sc = T(0), sr = T(0);
+  // (the loops of k_interp_adj; its two leading axes are '.' here: one tap of weight 1 each)
+  for (int i1 = 0; i1 < t1.cnt; ++i1) {
+    if (t1.wc[i1] == 0.f && t1.wr[i1] == 0.f) continue;
+    for (int i2 = 0; i2 < t2.cnt; ++i2) {
+      if (t2.wc[i2] == 0.f && t2.wr[i2] == 0.f) continue;
+      const T wcl = T(1.f * t1.wc[i1] * t2.wc[i2]);
+      const T wrl = T(1.f * t1.wr[i1] * t2.wr[i2]);
+      const int64_t base = (t1.k0 + i1) * fs1 + (t2.k0 + i2) * fs2;
+      for (int i3 = 0; i3 < t3.cnt; ++i3) {
+        if (t3.wc[i3] == 0.f && t3.wr[i3] == 0.f) continue;
+        const T g = gf[base + t3.k0 + i3];
+        sc = sc + (wcl * T(t3.wc[i3])) * g;
+        if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
+      }
+    }
+  }
+  const T v = special ? T(2) * sc - sr : sc;
+  const int64_t ci = row * a.ccells + flat;
+  gcoarse[ci] = v;
+  if (ad.x) {
+    T xv = ad.x[ci], mv = ad.m[ci], vv = ad.v[ci];
+    adam_update<T>(xv, mv, vv, v, ad, row);
+    ad.x[ci] = xv;
+    ad.m[ci] = mv;
+    ad.v[ci] = vv;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_scale_copy(const T* __restrict__ x, T* __restrict__ y, int64_t n, T a) {
   const int64_t nthreads = (int64_t)gridDim.x * kBlock;
@@ -844,6 +901,132 @@ static int mg_synth_adj_adam_volumes(const T* gu, T* const* grads, const int64_t
                          alpha_dev, alpha_stride, 0);
 }
 
+// Would every transfer level of `nrows` rows ([nrows, *shape] arrays, layout '.' + loc, aligned to 16 bytes) compute what
+// the same level of ONE row (layout loc) computes -- the prolongation of odil_mg_synth and the transposed chain of
+// odil_mg_synth_adj_adam_members?  The prolongation kernels (generic, fast, marching) all sum in the reference's order:
+// whichever of them takes '.' + loc gives a row the bits of its own launch, once the shapes refine and fit.  The
+// transposes have summation orders of their own: a level whose single transpose is the generic kernel runs
+// k_interp_adj_members, one whose single transpose is the node-centred marching kernel ('ncc' with four coarse planes or
+// more) runs that kernel row by row, and any other level must run the same kind on the stacked array as on one row.
+// Fills bshapes with the nlvl x (ndim + 1) batched extents, locb with '.' + loc and kinds[l] with the single transpose
+// of level l.  Nothing is launched.
+template <typename T>
+static int members_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows,
+                                int64_t* bshapes, char* locb, int* kinds) {
+  if (ndim < 1 || ndim > 3 || !shapes || !loc || (int)strlen(loc) != ndim) {
+    set_error("%s: ndim %d (the rows are 1-D to 3-D), null shapes or a loc of another length", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  for (int d = 0; d < ndim; ++d)
+    if (loc[d] != 'c' && loc[d] != 'n') {
+      set_error("%s: loc '%s' (every axis of a row is 'c' or 'n')", what, loc);
+      return ODIL_E_INVAL;
+    }
+  if (nrows < 1 || nrows > 65535) {
+    set_error("%s: %d rows (1 ... 65535)", what, nrows);
+    return ODIL_E_INVAL;
+  }
+  if (nlvl < 2 || nlvl > ODIL_MAX_LEVELS) {
+    set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
+    return ODIL_E_INVAL;
+  }
+  locb[0] = '.';
+  for (int d = 0; d < ndim; ++d) locb[1 + d] = loc[d];
+  locb[1 + ndim] = 0;
+  for (int l = 0; l < nlvl; ++l) {
+    bshapes[l * (ndim + 1)] = nrows;
+    for (int d = 0; d < ndim; ++d) bshapes[l * (ndim + 1) + 1 + d] = shapes[l * ndim + d];
+  }
+  if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
+  for (int l = 1; l < nlvl; ++l) {
+    InterpArgs one, all;
+    if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+    if (int e = fill_interp_args(all, bshapes + l * (ndim + 1), ndim + 1, locb)) return e;
+    if (prod4(one.fn) >= ((int64_t)1 << 31)) {
+      set_error("%s: level %d of a row has 2^31 elements or more", what, l);
+      return ODIL_E_INVAL;
+    }
+    const int k1 = interp_adj_kind<T>(one), kb = interp_adj_kind<T>(all);
+    kinds[l] = k1;
+    const bool node_rows = k1 == kAdjNode && one.fn[0] == 1 && one.loc[1] == kNode;
+    if (k1 != kAdjGeneric && !node_rows && k1 != kb) {
+      set_error("%s: level %d of %d rows would not run the transposed prolongation one row runs", what, l, nrows);
+      return ODIL_E_INVAL;
+    }
+  }
+  return 0;
+}
+
+// mg_synth_adj on [R, *shape] level arrays of R rows (layout '.' + loc, any loc of 'c' / 'n', 1-D to 3-D rows): one
+// launch per level for all rows, the update of the levels >= 1 in the launch that forms their gradient, row r with the
+// step size alpha_dev[(r % period) * alpha_stride] (period 0: r itself).  x = m = v = null: the gradients alone.
+template <typename T>
+static int mg_synth_adj_adam_members(const T* gu, T* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                     const char* loc, int nrows, T* const* ax, T* const* am, T* const* av, T omb1, T omb2,
+                                     T eps, const T* alpha_dev, int64_t alpha_stride, int64_t period, void* stream) {
+  static const char* what = "mg_synth_adj_adam_members";
+  const bool update = ax || am || av;
+  if (!gu || !grads || !shapes || (update && (!ax || !am || !av || !alpha_dev))) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (alpha_stride < 0 || period < 0) {
+    set_error("%s: step-size stride %lld or period %lld is negative", what, (long long)alpha_stride, (long long)period);
+    return ODIL_E_INVAL;
+  }
+  int64_t bshapes[ODIL_MAX_LEVELS * 4];
+  char locb[8];
+  int kinds[ODIL_MAX_LEVELS];
+  if (int e = members_levels_check<T>(what, shapes, nlvl, ndim, loc, nrows, bshapes, locb, kinds)) return e;
+  for (int l = 1; l < nlvl; ++l)
+    if (!grads[l] || (update && (!ax[l] || !am[l] || !av[l]))) {
+      set_error("%s: null level array (level %d)", what, l);
+      return ODIL_E_INVAL;
+    }
+  // (the answer above is that of arrays aligned to 16 bytes)
+  for (int l = 0; l < nlvl; ++l) {
+    const T* g = l == 0 ? gu : grads[l];
+    if (reinterpret_cast<uintptr_t>(g) % 16 != 0) {
+      set_error("%s: gradient array of level %d is not aligned to 16 bytes", what, l);
+      return ODIL_E_INVAL;
+    }
+  }
+  const T* gfine = gu;
+  for (int l = 1; l < nlvl; ++l) {
+    AdamArgs<T> ad{nullptr, nullptr, nullptr, T(0), omb1, omb2, eps, nullptr, 0, 0, 0};
+    if (update) {
+      ad.x = ax[l], ad.m = am[l], ad.v = av[l];
+      ad.alpha_dev = alpha_dev;
+      ad.alpha_stride = alpha_stride, ad.alpha_period = period;  // (stride 0: one step size for all rows)
+      ad.member_axis = 3 - ndim;  // canonical axis of the rows: 2 ('.c'), 1 ('.cc'), 0 ('.ccc')
+    }
+    if (kinds[l] == kAdjGeneric) {
+      InterpArgs one;
+      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+      MemberArgs m;
+      for (int i = 0; i < 3; ++i) m.cn[i] = (int)one.cn[i + 1], m.fn[i] = (int)one.fn[i + 1], m.loc[i] = one.loc[i + 1];
+      m.ccells = prod4(one.cn), m.fcells = prod4(one.fn);
+      const dim3 grid((unsigned)((m.ccells + kBlock - 1) / kBlock), (unsigned)nrows);
+      hipLaunchKernelGGL(k_interp_adj_members<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, gfine, grads[l], m, ad);
+      if (int e = check_launch("k_interp_adj_members")) return e;
+    } else if (kinds[l] == kAdjNode) {
+      InterpArgs one;
+      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+      const int r = interp_adj_march_n_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
+      if (r < 0) return r;
+      if (r == 0) {
+        set_error("%s: level %d: the node-centred marching kernel does not take these arrays", what, l);
+        return ODIL_E_INVAL;
+      }
+    } else {
+      if (int e = interp_adj<T>(gfine, grads[l], nullptr, bshapes + l * (ndim + 1), ndim + 1, locb, T(1), stream, 0, 0, ad))
+        return e;
+    }
+    gfine = grads[l];
+  }
+  return 0;
+}
+
 }  // namespace odil
 
 using namespace odil;
@@ -1000,6 +1183,33 @@ int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const
                                      void* stream) {
   return mg_synth_adj_adam_batch<float>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2, eps,
                                         alpha_dev, alpha_stride, stream);
+}
+
+int odil_mg_members_levels_ok(const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows, int elem_size) {
+  int64_t bshapes[ODIL_MAX_LEVELS * 4];
+  char locb[8];
+  int kinds[ODIL_MAX_LEVELS];
+  if (elem_size != 8 && elem_size != 4) {
+    set_error("mg_members_levels: element size %d (8 or 4)", elem_size);
+    return ODIL_E_INVAL;
+  }
+  return elem_size == 8
+             ? members_levels_check<double>("mg_members_levels", shapes, nlvl, ndim, loc, nrows, bshapes, locb, kinds)
+             : members_levels_check<float>("mg_members_levels", shapes, nlvl, ndim, loc, nrows, bshapes, locb, kinds);
+}
+int odil_mg_synth_adj_adam_members_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       const char* loc, int nrows, double* const* x, double* const* m, double* const* v,
+                                       double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
+                                       int64_t alpha_stride, int64_t period, void* stream) {
+  return mg_synth_adj_adam_members<double>(gu, grads, shapes, nlvl, ndim, loc, nrows, x, m, v, one_minus_b1, one_minus_b2,
+                                           eps, alpha_dev, alpha_stride, period, stream);
+}
+int odil_mg_synth_adj_adam_members_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
+                                       const char* loc, int nrows, float* const* x, float* const* m, float* const* v,
+                                       float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
+                                       int64_t alpha_stride, int64_t period, void* stream) {
+  return mg_synth_adj_adam_members<float>(gu, grads, shapes, nlvl, ndim, loc, nrows, x, m, v, one_minus_b1, one_minus_b2,
+                                          eps, alpha_dev, alpha_stride, period, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@ reference runs a sweep as B processes and has no counterpart; `util` re-exports 
 `optimize_newton`, whose single runs every member reproduces.  Written once for both drivers: `_check_members`; for both
 Newton routes: `_newton_loop`.  `linearize_ensemble` (`EnsembleLinearizer`) is the linearisation of the Newton driver's
 stencil route, all members in one generated launch; the Adam driver's route for members that are not all the Poisson
-stencil is `fused.TracedLaunchEnsemble`.  `printlog` and `_pinfo` are `util`'s (one log sink).
+stencil is `fused.TracedLaunchEnsemble` (any number of grid unknowns at one location of 'c' / 'n').  `printlog` and `_pinfo` are `util`'s (one log sink).
 """
 
 import argparse
@@ -19,6 +19,7 @@ from .optimizer import make_optimizer
 
 # what members are compared by -> how a refusal calls it
 _LABELS = dict(shapes="level shapes", cshape="cells", dtype="dtype", device="device", spacing="grid spacing",
+               fields="grid unknowns (key, position in the state)", loc="location",
                params="Array unknowns (key, position in the state, shape)",
                nets="NeuralNet unknowns (key, position in the state, layer shapes)")
 
@@ -26,7 +27,8 @@ _LABELS = dict(shapes="level shapes", cshape="cells", dtype="dtype", device="dev
 def _check_members(who, problems, states, describe, arrays_ok=False):
     """The checks both drivers open with, structure only (no operator is probed, no state changes): as many states as
     problems, every state initialised with one unknown field (arrays_ok: `Array` unknowns beside it do not count, nor do
-    `NeuralNet` unknowns beside a grid field under a key where member 0 has a network beside its grid field), and
+    `NeuralNet` unknowns beside a grid field under a key where member 0 has a network beside its grid field; and the
+    members may have SEVERAL unknown fields, every member as many as member 0 -- what they are is `describe`'s), and
     `describe(b, problem, state, refuse) -> kind`, a dict of what the members must share (keys of `_LABELS`, compared in
     its order with member 0's) -- which also makes the driver's own refusals.  `refuse(member, reason)` raises
     ValueError("<who>: member <b>: <reason>").
@@ -37,7 +39,7 @@ def _check_members(who, problems, states, describe, arrays_ok=False):
     def refuse(member, reason):
         raise ValueError("{}: member {}: {}".format(who, member, reason))
 
-    first, net_keys = None, set()
+    first, net_keys, nfirst = None, set(), 1
     for b, (problem, state) in enumerate(zip(problems, states)):
         if not state.initialized:
             refuse(b, "uninitialized state, use `state = domain.init_state(state)`")
@@ -48,8 +50,11 @@ def _check_members(who, problems, states, describe, arrays_ok=False):
                 if b == 0:
                     net_keys = set(nets)
                 nfields -= sum(1 for key in nets if key in net_keys)
-        if nfields != 1:
-            refuse(b, "{} unknown fields (the Poisson problem has one)".format(nfields))
+        if arrays_ok and b == 0 and nfields > 1:
+            nfirst = nfields
+        if nfields != nfirst:
+            refuse(b, "{} unknown fields ({})".format(nfields, "the Poisson problem has one" if nfirst == 1 else
+                                                      "member 0 has {}".format(nfirst)))
         kind = describe(b, problem, state, refuse)
         first = first or kind
         for what, value in kind.items():
@@ -106,10 +111,20 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     synthesis, the generated forward kernels and gathers (`stencil_bind.EpochBatch`: one launch per group of members whose
     operators generate the same source), the transposed prolongations with the updates of the coarser levels, and
     `ops.adam_step_batch` for level 0 -- each covering all members.  'auto' then picks by dimension ('volumes' for 3-D).
-    Such members have ONE cell-centred grid unknown (and possibly `Array` unknowns: next paragraph), a plain `Field` (one
-    level: no transfers, exempt from the two-level rule of the forms) or a `MultigridField` with all factors 1, on a 1-D to 3-D grid, with level shapes that
-    `fused.traced_refusal` admits; operators whose kernels have no batched form (marching kernels, outputs in parameter
-    space that only the torch replay evaluates) raise ValueError naming the member.  The callback's pinfo carries the member's own
+    Such members have ANY NUMBER of grid unknowns (and possibly `Array` unknowns: next paragraph), each a plain `Field` (one
+    level: no transfers, exempt from the two-level rule of the forms) or a `MultigridField` with all factors 1 that coarsens
+    every axis, on a 1-D to 3-D grid.  The grid unknowns of a member share ONE location string, any mix of 'c' and 'n'
+    (velocity_from_tracer: u, vx, vy at 'ncc'; heat_tmax and infer_constant: a field at 'nc' beside an `Array`), one kind
+    and the same level shapes -- an operator whose fields or outputs live on several grids stays refused -- and all members
+    share keys, positions in the state, location and level shapes (else ValueError naming the member, before any state
+    changes and before any operator is traced).  The F fields of the B members are stacked on the member axis: one
+    [F B, *shape] tensor per level, row f B + b, so the synthesis, the transposed chain with the updates of the coarser
+    levels (`ops.mg_synth_adj_adam_members`) and the level-0 update are each ONE set of launches for all fields of all
+    members; ONE cell-centred unknown makes exactly the launches it always made.  The level shapes must be admitted by
+    `fused.traced_refusal` (members whose finest array is no multiple of 16 bytes are refused -- every float64 1-D
+    node-centred field among them --, and the library says whether every level of the stacked rows computes what that
+    level of one member computes: odil_mg_members_levels_ok); operators whose kernels have no batched form (marching
+    kernels, outputs in parameter space that only the torch replay evaluates) raise ValueError naming the member.  The callback's pinfo carries the member's own
     names, terms and norms.  Epochs are replayed as a graph only when no member has host scalars (functions of
     `problem.tracers`), which travel in the argument blocks and are uploaded again when they change.  With
     form='workgroup', or without tracing, a member that is not the Poisson operator stays refused.
@@ -136,8 +151,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     Not served: marching kernels (float32 members of three or more dimensions with a last axis of at least 128 cells),
     parameter-space outputs that only the torch replay evaluates (reductions, broadcasts: `param_expr.Unsupported`), Newton
     -- ValueError naming the member -- and, because a single run packs its arrays back to back and its 3-D transfer
-    kernels choose by alignment, a number of `Array` / `NeuralNet` elements before a 3-D multigrid field that is no
-    multiple of 4 (put them after the field).  `optimize_newton_ensemble` keeps refusing members with `Array` or
+    kernels choose by alignment, a number of elements (`Array`, `NeuralNet`, earlier grid fields) before a 3-D multigrid
+    field that is no multiple of 4 (put the parameters after the fields); 4-D members.  `optimize_newton_ensemble` keeps refusing members with `Array` or
     `NeuralNet` unknowns.
     Returns ([arrays of member b: its level arrays; with `Array` / `NeuralNet` unknowns all its arrays in state order], optinfo);
     optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route: "poisson" or "traced"; optinfo.form: the form that
@@ -190,9 +205,9 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     def describe(b, problem, state, refuse):
         nonlocal form, traceable
         domain = problem.domain
-        # the one grid unknown (its level arrays) and the `Array` unknowns beside it, by position in `arrays_from_state`
+        # the grid unknowns (their level arrays) and the `Array` unknowns beside them, by position in `arrays_from_state`
         # (and the `NeuralNet` unknowns, when the state holds a grid field at all: a network alone is "the unknown")
-        params, nets, arrays = [], [], None
+        params, nets, grids = [], [], []
         beside = any(not isinstance(field, (Array, NeuralNet)) for field in state.fields.values())
         for pos, (key, field) in enumerate(state.fields.items()):
             if isinstance(field, Array):
@@ -200,41 +215,70 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
             elif beside and isinstance(field, NeuralNet):
                 nets.append((key, pos, [tuple(int(n) for n in a.shape) for a in domain.arrays_from_field(field)]))
             else:
-                unknown, arrays, upos = field, domain.arrays_from_field(field), pos
+                grids.append((key, pos, field, domain.arrays_from_field(field)))
+        key0, upos, unknown, arrays = grids[0]
         shapes = [tuple(int(n) for n in a.shape) for a in arrays]
-        if shapes[0] != tuple(domain.cshape):
+        loc = getattr(unknown, "loc", None)
+        if not isinstance(loc, str) or len(loc) != domain.ndim or any(c not in "cn" for c in loc):
             refuse(b, "the unknown is not a cell-centred field of the domain")
+        if shapes[0] != tuple(domain.size(loc=loc)):
+            refuse(b, "the unknown is not a cell-centred field of the domain" if loc == "c" * domain.ndim else
+                   "the unknown '{}' at '{}' has the shape {}, a field of the domain has {}".format(
+                       key0, loc, shapes[0], tuple(domain.size(loc=loc))))
+        for key, _, field, held in grids[1:]:  # (several grid unknowns: one grid, one kind, one location)
+            if type(field) is not type(unknown):
+                refuse(b, "grid unknowns of two kinds: '{}' is a {}, '{}' a {}".format(key0, type(unknown).__name__, key,
+                                                                                      type(field).__name__))
+            if getattr(field, "loc", None) != loc:
+                refuse(b, "grid unknowns at two locations: '{}' at '{}', '{}' at '{}' (operators whose fields live on "
+                          "several grids are not served)".format(key0, loc, key, getattr(field, "loc", None)))
+            other = [tuple(int(n) for n in a.shape) for a in held]
+            if other != shapes:
+                refuse(b, "grid unknowns with different level shapes: '{}' {}, '{}' {}".format(key0, shapes, key, other))
+            if held[0].dtype != arrays[0].dtype or held[0].device != arrays[0].device:
+                refuse(b, "grid unknown '{}' is a {} tensor on {} ('{}': {} on {})".format(
+                    key, held[0].dtype, held[0].device, key0, arrays[0].dtype, arrays[0].device))
+        # anything but ONE cell-centred unknown is served by the traced route alone, like `Array` and `NeuralNet` unknowns
+        many = len(grids) > 1 or loc != "c" * domain.ndim
         if b == 0:
             # (L-BFGS-B has no one-workgroup form: 'auto' picks among the batched launches, by dimension)
-            form = _traced_form(form, shapes) if lbfgsb else fused.ensemble_form(form, shapes, arrays[0].dtype)
+            form = _traced_form(form, shapes) if lbfgsb or many else fused.ensemble_form(form, shapes, arrays[0].dtype)
             traceable = traceable and arrays[0].is_cuda
-        reasons = dict(poisson=predicates[form](shapes, arrays[0].dtype), traced=None)
-        if params or nets:  # (inverse problems: the traced route alone serves them)
+        reasons = dict(poisson=predicates[form](shapes, arrays[0].dtype) if not many else None, traced=None)
+        if params or nets or many:  # (inverse problems: the traced route alone serves them)
             count = " and ".join("{} {} unknown{}".format(len(lst), name, "" if len(lst) == 1 else "s")
                                  for lst, name in ((params, "Array"), (nets, "NeuralNet")) if lst)
-            reasons["poisson"] = ("{} beside the field: such members run as traced operators -- form='launches', "
-                                  "'volumes' or 'auto', with operators traced and the members on a device".format(count))
-        if traceable:
-            reasons["traced"] = _traced_member(domain, unknown, shapes, arrays[0].dtype, _traced_form(requested, shapes))
-            ahead = sum(math.prod(shape) for _, pos, shape in params if pos < upos)
-            nets_ahead = sum(math.prod(shape) for _, pos, shapes_ in nets if pos < upos for shape in shapes_)
-            ahead += nets_ahead
-            if reasons["traced"] is None and len(shapes[0]) == 3 and len(shapes) > 1 and ahead % 4:
-                # a single run packs its arrays back to back: with `ahead` elements in front, the levels of its field are
-                # not aligned to four elements, and its 3-D transfers take other kernels (other rounding) than those of
-                # the members' aligned level arrays here
-                reasons["traced"] = ("{} {} elements stand before the 3-D multigrid field: a single run's level arrays are "
-                                     "then not aligned to 4 elements and its transfer kernels round differently (put the "
-                                     "{} after the field, or a multiple of 4 elements before it)".format(
-                                         ahead, "Array and NeuralNet" if nets_ahead else "Array",
-                                         "NeuralNet" if nets_ahead else "Array"))
+            what = "{} beside the field".format(count) if count else (
+                "{} grid unknowns".format(len(grids)) if len(grids) > 1 else "a grid unknown at '{}'".format(loc))
+            if count and many:
+                what += ", {}".format("{} grid unknowns".format(len(grids)) if len(grids) > 1 else "the field at '{}'".format(loc))
+            reasons["poisson"] = ("{}: such members run as traced operators -- form='launches', "
+                                  "'volumes' or 'auto', with operators traced and the members on a device".format(what))
+        if traceable or many:  # (what is not one cell-centred unknown: its structure is checked wherever it runs)
+            reasons["traced"] = _traced_member(domain, [g[2] for g in grids], shapes, arrays[0].dtype,
+                                               _traced_form(requested, shapes), loc)
+            for _, gpos, _, _ in grids:  # (elements in front of every grid field: parameters and earlier grid fields)
+                ahead = sum(math.prod(shape) for _, pos, shape in params if pos < gpos)
+                nets_ahead = sum(math.prod(shape) for _, pos, shapes_ in nets if pos < gpos for shape in shapes_)
+                ahead += nets_ahead + sum(a.numel() for _, pos, _, arrs in grids if pos < gpos for a in arrs)
+                if reasons["traced"] is None and len(shapes[0]) == 3 and len(shapes) > 1 and ahead % 4:
+                    # a single run packs its arrays back to back: with `ahead` elements in front, the levels of its field are
+                    # not aligned to four elements, and its 3-D transfers take other kernels (other rounding) than those of
+                    # the members' aligned level arrays here
+                    reasons["traced"] = ("{} {} elements stand before the 3-D multigrid field: a single run's level arrays are "
+                                         "then not aligned to 4 elements and its transfer kernels round differently (put the "
+                                         "{} after the field, or a multiple of 4 elements before it)".format(
+                                             ahead, "Array and NeuralNet" if nets_ahead else "Array",
+                                             "NeuralNet" if nets_ahead else "Array"))
             held = [("Array", key, state.fields[key].array) for key, _, _ in params]
             held += [("NeuralNet", key, a) for key, _, _ in nets for a in domain.arrays_from_field(state.fields[key])]
             for what, key, array in held:
                 if reasons["traced"] is None and (array.dtype != arrays[0].dtype or array.device != arrays[0].device):
                     reasons["traced"] = "{} unknown '{}' is a {} tensor on {} (the field: {} on {})".format(
                         what, key, array.dtype, array.device, arrays[0].dtype, arrays[0].device)
-        if (params or nets) and not traceable:  # (said once the members have been compared with each other: `unserved`)
+        if many and reasons["traced"] is not None:  # (structure: said wherever the members live)
+            refuse(b, reasons["traced"])
+        if (params or nets or many) and not traceable:  # (said once the members have been compared with each other: `unserved`)
             unserved.append((b, reasons["poisson"]))
         elif (params or nets) and reasons["traced"] is not None:  # (the only route that serves them says why it does not)
             refuse(b, reasons["traced"])
@@ -243,7 +287,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
         for route, reason in reasons.items():
             if reason is not None and late[route] is None:
                 late[route] = (b, reason)
-        return dict(shapes=shapes, params=params, nets=nets, dtype=arrays[0].dtype, device=arrays[0].device,
+        return dict(shapes=shapes, params=params, nets=nets, fields=[(key, pos) for key, pos, _, _ in grids], loc=loc,
+                    dtype=arrays[0].dtype, device=arrays[0].device,
                     spacing=[float(domain.step_by_dim(i)) for i in range(domain.ndim)])
 
     kind, refuse = _check_members("optimize_ensemble", problems, states, describe, arrays_ok=True)
@@ -361,27 +406,26 @@ def _traced_form(requested, shapes):
     return requested
 
 
-def _traced_member(domain, field, shapes, dtype, form):
-    """Why a member whose grid unknown is `field` is not run by `fused.TracedLaunchEnsemble` in `form`, or None --
-    structure only: one cell-centred unknown, a plain `Field` or a `MultigridField` with all factors 1 that coarsens every
-    axis, level shapes that `fused.traced_refusal` admits.  (`Array` unknowns beside it: the caller's.)"""
+def _traced_member(domain, fields, shapes, dtype, form, loc):
+    """Why a member whose grid unknowns are `fields` (all at `loc`, all of these level shapes) is not run by
+    `fused.TracedLaunchEnsemble` in `form`, or None -- structure only: plain `Field`s or `MultigridField`s with all factors
+    1 that coarsen every axis, level shapes that `fused.traced_refusal` admits.  (What stands beside them: the caller's.)"""
     from . import fused
     from .core import MultigridField
 
-    if isinstance(field, MultigridField):
-        factors = field.factors or domain.mg_factors or [1] * len(field.terms)
-        if any(float(f) != 1.0 for f in factors):
-            return "multigrid factors {} (the batched transfers run factors 1)".format([float(f) for f in factors])
-        axes = field.axes or domain.mg_axes
-        if axes is not None and not all(axes):
-            return "multigrid axes {} (the batched transfers coarsen every axis)".format(list(axes))
-        if len(shapes) < 2:  # (only a plain Field is the one-level case)
-            return fused._too_few_levels(shapes)
-    elif type(field) is not Field:
-        return "the unknown is a {} (a cell-centred Field or MultigridField is needed)".format(type(field).__name__)
-    if field.loc != "c" * domain.ndim:
-        return "the unknown is not a cell-centred field of the domain"
-    return fused.traced_refusal(shapes, dtype, form)
+    for field in fields:
+        if isinstance(field, MultigridField):
+            factors = field.factors or domain.mg_factors or [1] * len(field.terms)
+            if any(float(f) != 1.0 for f in factors):
+                return "multigrid factors {} (the batched transfers run factors 1)".format([float(f) for f in factors])
+            axes = field.axes or domain.mg_axes
+            if axes is not None and not all(axes):
+                return "multigrid axes {} (the batched transfers coarsen every axis)".format(list(axes))
+            if len(shapes) < 2:  # (only a plain Field is the one-level case)
+                return fused._too_few_levels(shapes)
+        elif type(field) is not Field:
+            return "the unknown is a {} (a Field or MultigridField is needed)".format(type(field).__name__)
+    return fused.traced_refusal(shapes, dtype, form, loc=loc, nfields=len(fields))
 
 
 def optimize_newton_ensemble(args, problems, states, callback=None, linearize="batched", time_linearize=False,

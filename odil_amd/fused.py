@@ -287,25 +287,29 @@ class BatchedLaunches(_Members):
         self.fu, self.rhs = self.members(self.cshape, pad), self.members(self.cshape, pad)
         self.rhs.copy_(torch.stack([e.rhs.reshape(self.cshape) for e in evaluators]))
 
-    def _allocate(self, shapes, dtype, device, names, pad=0):
-        """The level-major state of len(names) members of these level shapes (all axes cell-centred): x, m, v, g, loss and
-        norm.  pad: extra elements between the members of m[0] and v[0]."""
+    def _allocate(self, shapes, dtype, device, names, pad=0, loc=None, nfields=1):
+        """The level-major state of len(names) members of these level shapes: x, m, v, g, loss and norm.  pad: extra
+        elements between the members of m[0] and v[0].  loc: the location string of a member's arrays (default: all axes
+        cell-centred); nfields: grid unknowns per member, stacked on the member axis (`nrows` = nfields B rows per level
+        tensor, row f B + b)."""
         self.shapes, self.dtype, self.device = [tuple(s) for s in shapes], dtype, device
         self.sizes = [math.prod(s) for s in self.shapes]
         self.cshape, self.ndim = self.shapes[0], len(self.shapes[0])
-        self.loc = "." + "c" * self.ndim
-        self.nbatch, self.nlvl, self.total, self.cells = len(names), len(self.shapes), sum(self.sizes), self.sizes[0]
+        self.loc = "." + (loc or "c" * self.ndim)
+        self.nbatch, self.nlvl, self.cells = len(names), len(self.shapes), self.sizes[0]
+        self.nfields, self.nrows, self.total = nfields, nfields * self.nbatch, nfields * sum(self.sizes)
         self.names = names
         level = lambda wide0=0: [self.members(s, wide0 if l == 0 else 0) for l, s in enumerate(self.shapes)]
         self.x, self.m, self.v, self.g = level(), level(pad), level(pad), level()
         self.loss, self.norm = (torch.zeros(self.nbatch, dtype=self.dtype, device=self.device) for _ in range(2))
 
     def members(self, shape, wide=0):
-        """Zeroed [B, *shape] tensor with `wide` extra elements between its contiguous members."""
+        """Zeroed [B, *shape] tensor ([nfields B, *shape] where the members' grid unknowns are stacked) with `wide` extra
+        elements between its contiguous members."""
         cells = math.prod(shape)
-        base = torch.zeros(self.nbatch * (cells + wide), dtype=self.dtype, device=self.device)
+        base = torch.zeros(self.nrows * (cells + wide), dtype=self.dtype, device=self.device)
         strides = [math.prod(shape[k + 1:]) for k in range(len(shape))]
-        return base.as_strided((self.nbatch,) + tuple(shape), [cells + wide] + strides)
+        return base.as_strided((self.nrows,) + tuple(shape), [cells + wide] + strides)
 
     def levels(self, packed, member):
         """The level arrays of one member: views of the [B, *shape] level tensors."""
@@ -462,10 +466,19 @@ class TracedLaunchEnsemble(BatchedLaunches):
     -- the sums of a single run (pgrad -> gviews, k_par adds, one Adam step over the packed vector), whose bits every
     member keeps, in ONE parameter launch beside `k_par_batch`; members without such outputs keep launch 6 as it was.
     `report` inserts the parameter-space terms and norms at their outputs' positions.
+    SEVERAL grid unknowns, node-centred axes: the F grid unknowns of a member share one location string (any mix of 'c'
+    and 'n'), one kind and their level shapes, and are STACKED on the member axis: x, m, v, g (and u) hold one
+    [F B, *shape] tensor per level, row f B + b for field f (`grid_keys` order) of member b; `loc` is "." + that location.
+    Launch 1 then synthesises all fields of all members, launch 4 is `ops.mg_synth_adj_adam_members` -- ONE chain for all
+    rows, the fast / marching kernel where a single member's level runs it, `k_interp_adj_members` where a single member
+    runs the generic transpose (a node-centred y or x axis) -- and launch 5 updates level 0 of all rows; the step sizes
+    of the rows are prepared once per run (`step_rows`).  `order` items are ("level", l, f); `levels`, `blocks`, `ranges`
+    and `total` follow `arrays_from_state`: field by field, level by level, parameters where the state has them.  ONE
+    cell-centred unknown (`stacked` False) makes exactly the launches 1 - 5 above.
     Not served: marching kernels, parameter-space outputs that only the torch replay evaluates."""
 
     def __init__(self, problems, states, form="launches"):
-        """The members have passed the structural checks of `ensemble.optimize_ensemble` (one grid unknown, the same
+        """The members have passed the structural checks of `ensemble.optimize_ensemble` (the same grid unknowns, the same
         `Array` and `NeuralNet` unknowns, same level shapes, dtype and device; `traced_refusal` admits the shapes).  A member whose
         operator has no batched kernels raises ValueError naming it."""
         from . import stencil_jit
@@ -476,7 +489,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
         arrays = domain.arrays_from_state(states[0])
         # the state's arrays in `arrays_from_state` order: ("level", l) of the grid unknown, ("param", offset, shape) of
         # an `Array`, or of one array of a `NeuralNet` (weights, then biases), in the members' packed parameters
-        self.order, self.param_keys, self.nparams, self.ranges = [], [], 0, []
+        self.order, self.param_keys, self.nparams, self.ranges, self.grid_keys = [], [], 0, [], []
         for key, field, pos, n in field_ranges(domain, states[0]):
             kind = "net" if isinstance(field, NeuralNet) else "array" if isinstance(field, Array) else "grid"
             self.ranges.append((key, kind, pos, n))
@@ -487,16 +500,19 @@ class TracedLaunchEnsemble(BatchedLaunches):
                     self.order.append(("param", self.nparams, shape))
                     self.nparams += math.prod(shape)
                 self.param_keys.append((key, start, self.nparams - start))
-            else:
-                grid_key, first = key, pos
-                self.order.extend(("level", l) for l in range(n))
-        nlvl = sum(1 for item in self.order if item[0] == "level")
+            else:  # (grid unknown number f: its levels are the rows f B ... f B + B - 1 of the level tensors)
+                if not self.grid_keys:
+                    first, nlvl, loc = pos, n, field.loc
+                self.order.extend(("level", l, len(self.grid_keys)) for l in range(n))
+                self.grid_keys.append(key)
         shapes = [tuple(int(n) for n in a.shape) for a in arrays[first:first + nlvl]]
         dtype, device = arrays[first].dtype, arrays[first].device
-        nb = len(problems)
-        reason = traced_refusal(shapes, dtype, form, nb)
+        nb, nfields = len(problems), len(self.grid_keys)
+        reason = traced_refusal(shapes, dtype, form, nb, loc=loc, nfields=nfields)
         if reason is not None:
             raise ValueError("ensemble of {} members: {}".format(nb, reason))
+        # one cell-centred unknown: the launches these ensembles always made; else the chain for stacked rows of any loc
+        self.stacked = nfields > 1 or loc != "c" * len(shapes[0])
         self.form = form
         self.traced = []
         for b, (problem, state) in enumerate(zip(problems, states)):
@@ -504,7 +520,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
                 self.traced.append(stencil_jit.TracedOperator(problem, state, batch="params"))
             except stencil_jit.TraceUnsupported as e:
                 raise ValueError("ensemble member {}: its operator has no batched kernels ({})".format(b, e))
-        self._allocate(shapes, dtype, device, [list(t.names) for t in self.traced])
+        self._allocate(shapes, dtype, device, [list(t.names) for t in self.traced], loc=loc, nfields=nfields)
         self.u = self.members(self.cshape) if self.nlvl > 1 else self.x[0]
         self.work = ([None] + [self.members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
         by_lib = dict()
@@ -529,8 +545,13 @@ class TracedLaunchEnsemble(BatchedLaunches):
                     self.gextra.params = torch.zeros_like(self.g.params)
                 more.update(par_vals=[[self.levels(self.x, b)[i] for i in lead.cg.par_index] for b in group],
                             par_grads=[[self.levels(self.gextra, b)[i] for i in lead.cg.par_index] for b in group])
-            self.batches.append(EpochBatch([self.traced[b] for b in group], [[self.u[b]] for b in group],
-                                           [{grid_key: self.g[0][b]} for b in group], out, **more))
+            row = {key: f * nb for f, key in enumerate(self.grid_keys)}
+            foreign = [key for key in lead.cg.src_keys if key not in row]
+            if foreign:
+                raise ValueError("ensemble member {}: its kernels read {} as grid arrays".format(group[0], foreign))
+            self.batches.append(EpochBatch([self.traced[b] for b in group],
+                                           [[self.u[row[key] + b] for key in lead.cg.src_keys] for b in group],
+                                           [{key: self.g[0][at + b] for key, at in row.items()} for b in group], out, **more))
         self.where = dict((b, (k, j)) for k, group in enumerate(self.groups) for j, b in enumerate(group))
         self.index = [torch.tensor(group, device=self.device) for group in self.groups]
         if len(self.groups) == 1:  # (column 0 of the packed `out` itself: nothing to collect)
@@ -572,18 +593,33 @@ class TracedLaunchEnsemble(BatchedLaunches):
     def levels(self, packed, member):
         """The arrays of one member in its `arrays_from_state` order: views of the [B, *shape] level tensors and, for
         `Array` unknowns, of its row of the packed parameters."""
-        params = getattr(packed, "params", None)
-        if params is None:
-            return [t[member] for t in packed]
-        return [packed[item[1]][member] if item[0] == "level" else params[member, item[1]:item[1] + math.prod(item[2])].view(item[2])
-                for item in self.order]
+        params, nb = getattr(packed, "params", None), self.nbatch
+        return [packed[item[1]][item[2] * nb + member] if item[0] == "level"
+                else params[member, item[1]:item[1] + math.prod(item[2])].view(item[2]) for item in self.order]
 
     def blocks(self, packed):
-        params = getattr(packed, "params", None)
-        if params is None:
-            return [t.view(self.nbatch, -1) for t in packed]
-        return [packed[item[1]].view(self.nbatch, -1) if item[0] == "level" else params[:, item[1]:item[1] + math.prod(item[2])]
-                for item in self.order]
+        params, nb = getattr(packed, "params", None), self.nbatch
+        return [packed[item[1]][item[2] * nb:(item[2] + 1) * nb].view(nb, -1) if item[0] == "level"
+                else params[:, item[1]:item[1] + math.prod(item[2])] for item in self.order]
+
+    def step_rows(self, table):
+        """The table of step sizes ([E] shared by all members, or [E, B]: a row per epoch) as the launches on the stacked
+        rows read it: [E, nfields B], row f B + b with member b's step size -- prepared once for a run, not per epoch."""
+        table = np.asarray(table)
+        return np.tile(table, (1, self.nfields)) if table.ndim == 2 and self.nfields > 1 else table
+
+    def _row_steps(self, alphas):
+        """DEVICE step sizes of one epoch as the stacked rows read them: one element, or one per row (a [B] vector that
+        `step_rows` has not prepared is repeated here)."""
+        if self.nfields > 1 and alphas.numel() == self.nbatch and self.nbatch > 1:
+            return alphas.repeat(self.nfields)
+        return alphas
+
+    def _transposes(self):
+        if not self.stacked:
+            return super()._transposes()
+        if self.nlvl > 1:
+            ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g)
 
     def _param_step(self, alphas=None, omb1=0.0, omb2=0.0, eps=0.0):
         """ONE launch for the `Array` and `NeuralNet` unknowns of all members, behind the gathers (which re-read them): the
@@ -640,11 +676,16 @@ class TracedLaunchEnsemble(BatchedLaunches):
             batch.launch()
         if not self.par_batches:
             self._collect_loss()
-        if self.nlvl > 1:
+        rows = self._row_steps(alphas)
+        if self.nlvl > 1 and self.stacked:  # (all fields of all members: ONE chain)
+            ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g, self.x, self.m, self.v, rows, omb1, omb2,
+                                          eps)
+        elif self.nlvl > 1:
             chain = ops.mg_synth_adj_adam_volumes if self.ndim == 3 else ops.mg_synth_adj_adam_batch
             chain(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
-        ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], alphas, omb1, omb2, eps)
-        self._evaluate(alphas, omb1, omb2, eps)
+        ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], rows, omb1, omb2, eps)
+        # (the parameters: one step size per MEMBER -- the leading B of the stacked rows')
+        self._evaluate(rows[:self.nbatch] if rows.numel() > self.nbatch else rows, omb1, omb2, eps)
 
     def loss_grad(self):
         if self.nlvl > 1:
@@ -657,11 +698,15 @@ class TracedLaunchEnsemble(BatchedLaunches):
         self._evaluate()
 
 
-def traced_refusal(shapes, dtype, form, nbatch=1):
+def traced_refusal(shapes, dtype, form, nbatch=1, loc=None, nfields=1):
     """Why members of these level shapes are not run by `TracedLaunchEnsemble` in `form` ('launches': 1-D / 2-D, 'volumes':
     3-D), or None: `launches_refusal` / `volumes_refusal`, the one-level case (a plain `Field`: no transfers) exempt from
-    their two-level rule."""
+    their two-level rule.  loc, nfields: the location string the members' grid unknowns share and how many a member has;
+    anything but ONE cell-centred unknown runs the chain for stacked rows, and the library says whether every level of the
+    nfields * nbatch rows would run what that level of one member runs (odil_mg_members_levels_ok)."""
     ndim = len(shapes[0])
+    if loc is not None and (nfields > 1 or loc != "c" * ndim):
+        return _members_refusal(shapes, dtype, form, nbatch * nfields, loc)
     if not 1 <= ndim <= 3:
         return "{}-D grid: the batched launches of traced operators run 1-D to 3-D grids".format(ndim)
     if dtype not in (torch.float64, torch.float32):
@@ -674,6 +719,27 @@ def traced_refusal(shapes, dtype, form, nbatch=1):
     if reason is None and nbatch > 1:
         reason = _volume_levels_refusal(shapes, nbatch, dtype) if ndim == 3 else _levels_refusal(shapes, nbatch)
     return reason
+
+
+def _members_refusal(shapes, dtype, form, nrows, loc):
+    """`traced_refusal` for members with several grid unknowns or node-centred axes (`nrows` stacked rows at `loc`)."""
+    ndim = len(shapes[0])
+    if not 1 <= ndim <= 3:
+        return "{}-D grid: the batched launches of traced operators run 1-D to 3-D grids".format(ndim)
+    if dtype not in (torch.float64, torch.float32):
+        return "dtype {}: the kernels run float64 and float32".format(dtype)
+    if (form == "volumes") != (ndim == 3):
+        return "{}-D grid: form '{}' runs {} grids".format(ndim, form, "3-D" if form == "volumes" else "1-D and 2-D")
+    reason = _unaligned_members(shapes, dtype)
+    if reason is not None or len(shapes) == 1:
+        return reason
+    from ._lib import i64, load
+
+    lib = load()
+    flat = [int(n) for shape in shapes for n in shape]
+    if lib.odil_mg_members_levels_ok(i64(flat), len(shapes), ndim, loc.encode(), int(nrows), 4 if dtype == torch.float32 else 8) == 0:
+        return None
+    return lib.odil_last_error().decode()
 
 
 def _library_refusal(entry, shapes, *more):

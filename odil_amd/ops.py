@@ -976,6 +976,32 @@ def mg_synth_adj_adam_volumes(gu, shapes, grads, x, m, v, alphas, one_minus_b1, 
     return grads
 
 
+def mg_synth_adj_adam_members(gu, shapes, loc, grads, x=None, m=None, v=None, alphas=None, one_minus_b1=0.0, one_minus_b2=0.0,
+                              eps=0.0, period=0):
+    """`mg_synth_adj_adam` on contiguous [R, *shape] level arrays of R rows (`shapes`: the level shapes of ONE row, `loc`:
+    its location string, any mix of 'c' and 'n', 1-D to 3-D): one launch per level for all rows, the update of the levels
+    >= 1 inside it.  alphas: DEVICE step sizes; row r reads alphas[r % period] (period 0: alphas[r]; one element: shared by
+    all rows).  x, m, v all None: the gradients alone.  Entry 0 of grads, x, m, v is not touched (the chain reads gu).
+    Per row: the gradients of `mg_synth_adj`, the x, m, v of `adam_step`, bit for bit."""
+    nr, nlvl = int(gu.shape[0]), len(shapes)
+    assert tuple(gu.shape) == (nr,) + tuple(shapes[0]) and gu.is_contiguous() and len(loc) == len(shapes[0])
+    update = x is not None or m is not None or v is not None
+    for arrs in (grads,) + ((x, m, v) if update else ()):  # (the launcher takes contiguous [R, *shape] level arrays)
+        assert all(tuple(t.shape) == (nr,) + tuple(s) and t.is_contiguous() and t.dtype == gu.dtype
+                   for t, s in zip(arrs[1:], shapes[1:]))
+    none0 = lambda arrs: ptr_array([None] + list(arrs[1:]))
+    stride, period = 0, int(period)
+    if update:
+        assert alphas.dtype == gu.dtype and alphas.is_cuda and alphas.is_contiguous()
+        assert alphas.numel() in (1, period or nr), (alphas.numel(), period, nr)
+        stride = 1 if alphas.numel() > 1 else 0
+    flat = [int(n) for s in shapes for n in s]
+    call("mg_synth_adj_adam_members", gu.dtype, ptr(gu), none0(grads), i64(flat), c_int(nlvl), c_int(len(shapes[0])),
+         loc.encode(), c_int(nr), *((none0(x), none0(m), none0(v)) if update else (None, None, None)), float(one_minus_b1),
+         float(one_minus_b2), float(eps), ptr(alphas) if update else None, c_int64(stride), c_int64(period), stream_ptr())
+    return grads
+
+
 def jacobi2_supported(shape, dtype):
     """Arrays whose rows are whole 16-byte packs (odil_poisson_jacobi2, odil_stencil_var_smooth2)."""
     pack = 2 if dtype == torch.float64 else 4

@@ -338,6 +338,8 @@ class AdamNativeOptimizer(Optimizer):
                 t.zero_()
         rows = np.array(table, dtype=np.float64)
         rows = rows.T if rows.ndim == 2 else rows  # a row per epoch
+        if hasattr(ensemble, "step_rows"):  # (members with stacked grid unknowns: a step size per ROW, prepared once)
+            rows = ensemble.step_rows(rows)
 
         def step(alpha):
             ensemble.epoch(alpha.view(-1), omb1, omb2, epsilon)
