@@ -799,12 +799,21 @@ int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, con
  * single transpose is the generic kernel (a node-centred y or x axis: 'nc', 'cn', 'nn', 'n') runs k_interp_adj_members,
  * the generic kernel's sum per coarse value with the row on a grid dimension and the update in the same thread.  Per row
  * the gradients are the bits of odil_mg_synth_adj on that row alone, x, m, v those of odil_adam_step.
- * Refused before anything is launched: null pointers, nrows outside 1 ... 65535, ndim outside 1 ... 3, a loc with '.',
+ * Refused before anything is launched: null pointers, nrows outside 1 ... 65535, ndim outside 1 ... 4, a loc with '.',
  * fewer than two levels, gradient arrays off the 16-byte grid, a negative stride or period, and rows one of whose levels
  * would not compute what that level of a single row computes.
  * odil_mg_members_levels_ok answers the last question -- for this chain and for the prolongation odil_mg_synth runs on
  * the same arrays, whose kernels all sum in the reference's order -- from shapes, loc, nrows and the element size alone
- * (0: they do; else the reason is the error text). */
+ * (0: they do; else the reason is the error text).
+ * Rows of FOUR axes (ndim 4, the (t, x, y, z) arrays of the space-time workloads): the canonical view of the transfer
+ * kernels has four axes, so the row cannot ride as a leading '.' axis.  A single 4-D array runs one of three transposes,
+ * and each has a row variant with the row on a grid dimension the single kernel does not use, base pointers offset by
+ * the row, schedule, arithmetic and summation order those of the single launch: the generic kernel
+ * (k_interp_adj_members4: a node-centred y or x axis), the fast kernel (the ROWS instantiations of k_interp_adj_fast)
+ * and the 'nccc' marching kernel (the ROWS instantiation of k_interp_adj_march_lead, the row on blockIdx.z).
+ * odil_mg_members_levels_ok refuses, naming the level, a level whose single kind is none of these and a level of the
+ * latter two kinds whose rows are no multiple of 16 bytes (the kernels read packs, and choose their columns per thread,
+ * by the alignment of row 0). */
 int odil_mg_members_levels_ok(const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows, int elem_size);
 int odil_mg_synth_adj_adam_members_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
                                        const char* loc, int nrows, double* const* x, double* const* m, double* const* v,
@@ -814,6 +823,17 @@ int odil_mg_synth_adj_adam_members_f32(const float* gu, float* const* grads, con
                                        const char* loc, int nrows, float* const* x, float* const* m, float* const* v,
                                        float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
                                        int64_t alpha_stride, int64_t period, void* stream);
+/* The synthesis of odil_mg_synth, all factors 1, on the same [nrows, *shape] level arrays of 1-D to 4-D rows:
+ * u[r] = sum_l P^l terms[l][r], one launch per level for all rows.  work[l] (1 <= l <= nlvl-2): scratch of the size of
+ * terms[l].  Rows of up to three axes are the '.' + loc call of odil_mg_synth; rows of four axes run the fast
+ * prolongation where it takes the layout, else the generic one, with the row on blockIdx.y (the ROWS instantiations of
+ * k_interp_add_fast and k_interp_add).  Every prolongation kernel sums in
+ * the reference's order, so row r gets the bits of odil_mg_synth on that row alone.  Refused before anything is launched:
+ * null pointers, nrows outside 1 ... 65535, ndim outside 1 ... 4, a loc with '.', shapes that do not refine. */
+int odil_mg_synth_members_f64(const double* const* terms, double* const* work, double* u, const int64_t* shapes, int nlvl,
+                              int ndim, const char* loc, int nrows, void* stream);
+int odil_mg_synth_members_f32(const float* const* terms, float* const* work, float* u, const int64_t* shapes, int nlvl,
+                              int ndim, const char* loc, int nrows, void* stream);
 /* The stencil adjoint of all members WITHOUT an update (the gradient of an ensemble whose optimizer is not Adam):
  * gu[b] = odil_poisson_adjoint of fu[b] for nbatch 1-D, 2-D or 3-D members in one launch, member b = blockIdx.y on the
  * single kernel's walk, bit for bit.  Strides as above (>= cells of a member, multiples of 16 bytes).  Refused before

@@ -44,9 +44,17 @@ __device__ inline Tap3 tap3(int j, int n) {
   return t;
 }
 
-template <typename T, bool YC>
+// ROWS: the R rows of [R, *shape] arrays whose rows have four axes: row blockIdx.y walks the schedule below on its own
+// arrays, prod(cn) / prod(fn) elements apart.  The instantiations without the flag are the kernel as it was.
+template <typename T, bool YC, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) void k_interp_add_fast(const T* __restrict__ coarse, const T* __restrict__ add,
                                                             T* __restrict__ fine, FastArgs a, T cscale, T ascale) {
+  if constexpr (ROWS) {
+    const int64_t row = blockIdx.y, fcells = (int64_t)a.fn[0] * a.fn[1] * a.fn[2] * a.fn[3];
+    coarse += row * ((int64_t)a.cn[0] * a.cn[1] * a.cn[2] * a.cn[3]);
+    if (add) add += row * fcells;
+    fine += row * fcells;
+  }
   const int cnx = a.cn[3], cny = a.cn[2];
   const int fnx = a.fn[3], fny = a.fn[2];
   const int64_t cplane = (int64_t)cny * cnx, fplane = (int64_t)fny * fnx;
@@ -191,10 +199,24 @@ __device__ inline void adj_weight(int loc, int J, int n, int F, int k, bool cut_
   }
 }
 
-template <typename T, bool YC>
+// ROWS: the R rows of [R, *shape] arrays whose rows have four axes (the canonical view has no axis left for the row).  Row
+// blockIdx.y walks the schedule below on its own arrays, prod(cn) / prod(fn) elements apart, and updates with its own
+// step size; gscaled is null.  The instantiations without the flag are the kernel as it was.
+template <typename T, bool YC, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) void k_interp_adj_fast(const T* __restrict__ gfine, T* __restrict__ gcoarse,
                                                             T* __restrict__ gscaled, FastArgs a, T scale,
                                                             AdamArgs<T> ad) {
+  if constexpr (ROWS) {
+    const int64_t row = blockIdx.y;
+    const int64_t ccells = (int64_t)a.cn[0] * a.cn[1] * a.cn[2] * a.cn[3];
+    gfine += row * ((int64_t)a.fn[0] * a.fn[1] * a.fn[2] * a.fn[3]);
+    gcoarse += row * ccells;
+    if (ad.x) ad.x += row * ccells, ad.m += row * ccells, ad.v += row * ccells;
+    if (ad.alpha_dev) {
+      ad.alpha_dev += adam_alpha_row(ad, row) * ad.alpha_stride;
+      ad.alpha_stride = 0;  // (the update below reads entry 0 whatever it takes for the member)
+    }
+  }
   const int cnx = a.cn[3], cny = a.cn[2];
   const int fnx = a.fn[3], fny = a.fn[2];
   const int64_t cplane = (int64_t)cny * cnx, fplane = (int64_t)fny * fnx;
@@ -351,6 +373,50 @@ int interp_adj_fast(const T* gfine, T* gcoarse, T* gscaled, const InterpArgs& a,
   return e ? e : 1;
 }
 
+template <typename T>
+int interp_add_fast_rows(const T* coarse, const T* add, T* fine, const InterpArgs& one, int nrows, hipStream_t stream) {
+  FastArgs f;
+  bool yc;
+  if (nrows < 1 || nrows > 65535 || one.cut_axis >= 0 || !fast_setup(f, one, yc)) return 0;
+  const dim3 grid(sched_grid(f.sched), nrows);  // (the schedule of interp_add_fast on ONE row)
+  if (yc)
+    hipLaunchKernelGGL((k_interp_add_fast<T, true, true>), grid, dim3(kBlock), 0, stream, coarse, add, fine, f, T(1), T(1));
+  else
+    hipLaunchKernelGGL((k_interp_add_fast<T, false, true>), grid, dim3(kBlock), 0, stream, coarse, add, fine, f, T(1), T(1));
+  const int e = check_launch("k_interp_add_fast<rows>");
+  return e ? e : 1;
+}
+template int interp_add_fast_rows<double>(const double*, const double*, double*, const InterpArgs&, int, hipStream_t);
+template int interp_add_fast_rows<float>(const float*, const float*, float*, const InterpArgs&, int, hipStream_t);
+
+template <typename T>
+int interp_adj_fast_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
+                         const AdamArgs<T>& ad) {
+  FastArgs f;
+  bool yc;
+  if (nrows < 1 || nrows > 65535 || one.cut_axis >= 0 || !fast_setup(f, one, yc)) return 0;
+  // every row starts where row 0 starts on the 16-byte grid (the rule of odil_mg_members_levels_ok)
+  constexpr int64_t pack = 16 / (int64_t)sizeof(T);
+  if (prod4(one.fn) % pack != 0 || prod4(one.cn) % pack != 0) return 0;
+  // the schedule of interp_adj_fast on ONE row
+  const int64_t planes = one.cn[0] * one.cn[1];
+  const int64_t ytiles = (f.cn[2] + f.ty - 1) / f.ty, xtiles = (f.cn[3] + f.tx - 1) / f.tx;
+  f.sched = make_sched(planes, ytiles, xtiles);
+  const dim3 grid(sched_grid(f.sched), nrows);
+  if (yc)
+    hipLaunchKernelGGL((k_interp_adj_fast<T, true, true>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, (T*)nullptr, f,
+                       T(1), ad);
+  else
+    hipLaunchKernelGGL((k_interp_adj_fast<T, false, true>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, (T*)nullptr, f,
+                       T(1), ad);
+  const int e = check_launch("k_interp_adj_fast<rows>");
+  return e ? e : 1;
+}
+
+template int interp_adj_fast_rows<double>(const double*, double*, const InterpArgs&, int, hipStream_t,
+                                          const AdamArgs<double>&);
+template int interp_adj_fast_rows<float>(const float*, float*, const InterpArgs&, int, hipStream_t,
+                                         const AdamArgs<float>&);
 template int interp_add_fast<double>(const double*, const double*, double*, const InterpArgs&, double, double,
                                      hipStream_t);
 template int interp_add_fast<float>(const float*, const float*, float*, const InterpArgs&, float, float, hipStream_t);

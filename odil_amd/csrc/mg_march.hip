@@ -1410,10 +1410,24 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_march_n_rows(const T* __r
 // P^T for the 4-D layouts: coarse volume J0 (blockIdx.y) collects the fine volumes 2 J0 and, halved,
 // 2 J0 +- 1 on a node-centred leading axis (volume J0 alone on a batch axis); one z-window of plane
 // sums per contributing fine volume.
-template <typename T, int CX, int NTAP>
+// ROWS: the rows of a stacked ensemble of 'nccc' members ([R, t, x, y, z] arrays).  blockIdx.y is the leading index as
+// above, row blockIdx.z walks the columns below on its own arrays, with its own step size; gscaled is null.  The
+// instantiations without the flag are the kernel as it was.
+template <typename T, int CX, int NTAP, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) void k_interp_adj_march_lead(const T* __restrict__ gfine,
                                                                   T* __restrict__ gcoarse, T* __restrict__ gscaled,
                                                                   MarchArgs a, T scale, AdamArgs<T> ad) {
+  if constexpr (ROWS) {
+    const int64_t row = blockIdx.z;
+    const int64_t cvol = (int64_t)a.lead_cn * a.lead_cstride;
+    gfine += row * ((int64_t)a.lead_fn * a.fn[0] * a.fn[1] * a.fn[2]);
+    gcoarse += row * cvol;
+    if (ad.x) ad.x += row * cvol, ad.m += row * cvol, ad.v += row * cvol;
+    if (ad.alpha_dev) {
+      ad.alpha_dev += adam_alpha_row(ad, row) * ad.alpha_stride;
+      ad.alpha_stride = 0;  // (the step size belongs to the row, not to the leading index)
+    }
+  }
   const int cnz = a.cn[0], cny = a.cn[1], cnx = a.cn[2];
   const int fnz = a.fn[0], fny = a.fn[1], fnx = a.fn[2];
   const int64_t cplane = (int64_t)cny * cnx, fplane = (int64_t)fny * fnx;
@@ -1935,6 +1949,30 @@ int interp_adj_march_n_rows(const T* gfine, T* gcoarse, const InterpArgs& one, i
   const int e = check_launch("k_interp_adj_march_n_rows");
   return e ? e : 1;
 }
+// P^T of `nrows` stacked 'nccc' arrays whose single transpose is k_interp_adj_march_lead<T, 1, 3> (its ROWS instantiation; `one`: the layout of
+// ONE row): 1 when launched, 0 when a single row would not run that kernel, < 0 on error.
+template <typename T>
+int interp_adj_march_lead_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
+                               const AdamArgs<T>& ad) {
+  MarchArgs m;
+  if (one.fn[0] == 1 || one.loc[0] != kNode || one.coarse_ld || nrows < 1 || nrows > 65535 ||
+      !march_cx<T>(one, gfine, nullptr) ||
+      !march_setup(m, one, 1, adj_small_level(one) ? ODIL_ADJ_UNITS_SMALL : ODIL_ADJ_UNITS))
+    return 0;
+  // every row starts where row 0 starts on the 16-byte grid (the rule of odil_mg_members_levels_ok)
+  constexpr int64_t pack = 16 / (int64_t)sizeof(T);
+  if (prod4(one.fn) % pack != 0 || prod4(one.cn) % pack != 0) return 0;
+  const dim3 grid(unit_grid(m.usched), m.lead_cn, nrows);
+  hipLaunchKernelGGL((k_interp_adj_march_lead<T, 1, 3, true>), grid, dim3(kBlock), 0, stream, gfine, gcoarse, (T*)nullptr, m,
+                     T(1), ad);
+  const int e = check_launch("k_interp_adj_march_lead<rows>");
+  return e ? e : 1;
+}
+template int interp_adj_march_lead_rows<double>(const double*, double*, const InterpArgs&, int, hipStream_t,
+                                                const AdamArgs<double>&);
+template int interp_adj_march_lead_rows<float>(const float*, float*, const InterpArgs&, int, hipStream_t,
+                                               const AdamArgs<float>&);
+
 template int interp_adj_march_n_rows<double>(const double*, double*, const InterpArgs&, int, hipStream_t,
                                              const AdamArgs<double>&);
 template int interp_adj_march_n_rows<float>(const float*, float*, const InterpArgs&, int, hipStream_t,

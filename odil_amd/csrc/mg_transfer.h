@@ -169,4 +169,17 @@ template <typename T>
 int interp_adj_march_n_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
                             const AdamArgs<T>& ad);
 
+// P^T of `nrows` stacked rows of FOUR axes ([nrows, *shape] arrays; `one`: the layout of ONE row), the row on a grid
+// dimension the single kernel does not use: the fast kernel (kAdjFast) and the 'nccc' marching kernel (kAdjNode with a
+// leading axis).  1 when launched, 0 when a single row would not run that kernel, < 0 on error.
+template <typename T>
+int interp_adj_fast_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
+                         const AdamArgs<T>& ad);
+// P of the same rows through the fast kernel (factors 1): 1 when launched, 0 when the fast kernel does not take the layout.
+template <typename T>
+int interp_add_fast_rows(const T* coarse, const T* add, T* fine, const InterpArgs& one, int nrows, hipStream_t stream);
+template <typename T>
+int interp_adj_march_lead_rows(const T* gfine, T* gcoarse, const InterpArgs& one, int nrows, hipStream_t stream,
+                               const AdamArgs<T>& ad);
+
 }  // namespace odil

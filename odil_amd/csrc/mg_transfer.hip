@@ -12,9 +12,18 @@
 
 namespace odil {
 
-template <typename T>
+// ROWS: the R rows of [R, *shape] arrays whose rows have four axes (the canonical view has no axis left for the row).  Row
+// blockIdx.y walks the schedule below on its own arrays, prod(cn) / prod(fn) elements apart.  The instantiation without
+// the flag is the kernel as it was.
+template <typename T, bool ROWS = false>
 __global__ __launch_bounds__(kBlock) void k_interp_add(const T* __restrict__ coarse, const T* __restrict__ add,
                                                        T* __restrict__ fine, InterpArgs a, T cscale, T ascale) {
+  if constexpr (ROWS) {
+    const int64_t row = blockIdx.y, fcells = a.fn[0] * a.fn[1] * a.fn[2] * a.fn[3];
+    coarse += row * (a.cn[0] * a.cn[1] * a.cn[2] * a.cn[3]);
+    if (add) add += row * fcells;
+    fine += row * fcells;
+  }
   const int64_t cs2 = a.cn[3], cs1 = a.cn[2] * cs2, cs0 = a.cn[1] * cs1;
   const int64_t fs2 = a.fn[3], fs1 = a.fn[2] * fs2, fs0 = a.fn[1] * fs1;
   const int64_t npairs = (a.fn[3] + 1) / 2;
@@ -444,6 +453,62 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_members(const T* __restri
         const T g = gf[base + t3.k0 + i3];
         sc = sc + (wcl * T(t3.wc[i3])) * g;
         if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
+      }
+    }
+  }
+  const T v = special ? T(2) * sc - sr : sc;
+  const int64_t ci = row * a.ccells + flat;
+  gcoarse[ci] = v;
+  if (ad.x) {
+    T xv = ad.x[ci], mv = ad.m[ci], vv = ad.v[ci];
+    adam_update<T>(xv, mv, vv, v, ad, row);
+    ad.x[ci] = xv;
+    ad.m[ci] = mv;
+    ad.v[ci] = vv;
+  }
+}
+
+// The same for rows of FOUR axes ([R, t, x, y, z] arrays: 'cccn', 'ccnc', 'nnnn', ...): the fourth tap loop outermost, as
+// k_interp_adj sums a 4-D array.
+struct MemberArgs4 {
+  int cn[4], fn[4];
+  int loc[4];
+  int64_t ccells, fcells;  // elements of a coarse / fine row
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_interp_adj_members4(const T* __restrict__ gfine, T* __restrict__ gcoarse,
+                                                                MemberArgs4 a, AdamArgs<T> ad) {
+  const int64_t flat = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (flat >= a.ccells) return;
+  const int64_t row = blockIdx.y;
+  const int plane = a.cn[2] * a.cn[3], vol = a.cn[1] * plane;
+  const int at = (int)flat;
+  const int c0 = at / vol, r0 = at - c0 * vol, c1 = r0 / plane, r = r0 - c1 * plane, c2 = r / a.cn[3], c3 = r - c2 * a.cn[3];
+  const int64_t fs2 = a.fn[3], fs1 = (int64_t)a.fn[2] * fs2, fs0 = (int64_t)a.fn[1] * fs1;
+  const AdjTaps t0 = make_adj_taps(a.loc[0], c0, a.cn[0], a.fn[0]);
+  const AdjTaps t1 = make_adj_taps(a.loc[1], c1, a.cn[1], a.fn[1]);
+  const AdjTaps t2 = make_adj_taps(a.loc[2], c2, a.cn[2], a.fn[2]);
+  const AdjTaps t3 = make_adj_taps(a.loc[3], c3, a.cn[3], a.fn[3]);
+  const bool special = t0.special || t1.special || t2.special || t3.special;
+  const T* __restrict__ gf = gfine + row * a.fcells;
+  T sc = T(0), sr = T(0);
+  // (the loops of k_interp_adj)
+  for (int i0 = 0; i0 < t0.cnt; ++i0) {
+    if (t0.wc[i0] == 0.f && t0.wr[i0] == 0.f) continue;
+    for (int i1 = 0; i1 < t1.cnt; ++i1) {
+      if (t1.wc[i1] == 0.f && t1.wr[i1] == 0.f) continue;
+      for (int i2 = 0; i2 < t2.cnt; ++i2) {
+        if (t2.wc[i2] == 0.f && t2.wr[i2] == 0.f) continue;
+        const T wcl = T(t0.wc[i0] * t1.wc[i1] * t2.wc[i2]);
+        const T wrl = T(t0.wr[i0] * t1.wr[i1] * t2.wr[i2]);
+        const int64_t base = (t0.k0 + i0) * fs0 + (t1.k0 + i1) * fs1 + (t2.k0 + i2) * fs2;
+        for (int i3 = 0; i3 < t3.cnt; ++i3) {
+          if (t3.wc[i3] == 0.f && t3.wr[i3] == 0.f) continue;
+          const T g = gf[base + t3.k0 + i3];
+          sc = sc + (wcl * T(t3.wc[i3])) * g;
+          if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
+        }
       }
     }
   }
@@ -913,8 +978,8 @@ static int mg_synth_adj_adam_volumes(const T* gu, T* const* grads, const int64_t
 template <typename T>
 static int members_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows,
                                 int64_t* bshapes, char* locb, int* kinds) {
-  if (ndim < 1 || ndim > 3 || !shapes || !loc || (int)strlen(loc) != ndim) {
-    set_error("%s: ndim %d (the rows are 1-D to 3-D), null shapes or a loc of another length", what, ndim);
+  if (ndim < 1 || ndim > 4 || !shapes || !loc || (int)strlen(loc) != ndim) {
+    set_error("%s: ndim %d (the rows are 1-D to 4-D), null shapes or a loc of another length", what, ndim);
     return ODIL_E_INVAL;
   }
   for (int d = 0; d < ndim; ++d)
@@ -929,6 +994,38 @@ static int members_levels_check(const char* what, const int64_t* shapes, int nlv
   if (nlvl < 2 || nlvl > ODIL_MAX_LEVELS) {
     set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
     return ODIL_E_INVAL;
+  }
+  if (ndim == 4) {
+    // rows of four axes: the canonical view has no axis left for the row, so every kind runs a row variant of its own
+    // (bshapes and locb stay unused).  A single 4-D array runs the generic kernel, the fast kernel or the 'nccc' marching
+    // kernel and nothing else.  Rows of the latter two kinds must be multiples of 16 bytes, fine and coarse: the kernels
+    // read the fine array in packs of two elements, and a single run, whose levels and fields lie back to back, keeps
+    // every later array where row 0 lies on the 16-byte grid only then (coarse rows can be odd: 'cccc' cells 6^4 have
+    // coarse rows of 81 elements, and such members are refused in both element sizes).
+    locb[0] = 0;
+    if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
+    const int64_t pack = 16 / (int64_t)sizeof(T);
+    for (int l = 1; l < nlvl; ++l) {
+      InterpArgs one;
+      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+      const int64_t fcells = prod4(one.fn), ccells = prod4(one.cn);
+      if (fcells >= ((int64_t)1 << 31)) {
+        set_error("%s: level %d of a row has 2^31 elements or more", what, l);
+        return ODIL_E_INVAL;
+      }
+      const int k1 = interp_adj_kind<T>(one);
+      kinds[l] = k1;
+      if (k1 != kAdjGeneric && k1 != kAdjFast && !(k1 == kAdjNode && one.loc[0] == kNode)) {
+        set_error("%s: level %d of %d rows: the transposed prolongation of a single row has no row variant", what, l, nrows);
+        return ODIL_E_INVAL;
+      }
+      if (k1 != kAdjGeneric && (fcells % pack != 0 || ccells % pack != 0)) {
+        set_error("%s: level %d of %d rows: rows of %lld / %lld elements do not all start on the 16-byte grid", what, l,
+                  nrows, (long long)fcells, (long long)ccells);
+        return ODIL_E_INVAL;
+      }
+    }
+    return 0;
   }
   locb[0] = '.';
   for (int d = 0; d < ndim; ++d) locb[1 + d] = loc[d];
@@ -998,9 +1095,31 @@ static int mg_synth_adj_adam_members(const T* gu, T* const* grads, const int64_t
       ad.x = ax[l], ad.m = am[l], ad.v = av[l];
       ad.alpha_dev = alpha_dev;
       ad.alpha_stride = alpha_stride, ad.alpha_period = period;  // (stride 0: one step size for all rows)
-      ad.member_axis = 3 - ndim;  // canonical axis of the rows: 2 ('.c'), 1 ('.cc'), 0 ('.ccc')
+      ad.member_axis = ndim == 4 ? 0 : 3 - ndim;  // canonical axis of the rows: 2 ('.c'), 1 ('.cc'), 0 ('.ccc'); 4-D: unused
     }
-    if (kinds[l] == kAdjGeneric) {
+    if (ndim == 4) {
+      InterpArgs one;
+      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+      int r = 0;
+      if (kinds[l] == kAdjGeneric) {
+        MemberArgs4 m;
+        for (int i = 0; i < 4; ++i) m.cn[i] = (int)one.cn[i], m.fn[i] = (int)one.fn[i], m.loc[i] = one.loc[i];
+        m.ccells = prod4(one.cn), m.fcells = prod4(one.fn);
+        const dim3 grid((unsigned)((m.ccells + kBlock - 1) / kBlock), (unsigned)nrows);
+        hipLaunchKernelGGL(k_interp_adj_members4<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, gfine, grads[l], m, ad);
+        if (int e = check_launch("k_interp_adj_members4")) return e;
+        r = 1;
+      } else if (kinds[l] == kAdjNode) {
+        r = interp_adj_march_lead_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
+      } else {
+        r = interp_adj_fast_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
+      }
+      if (r < 0) return r;
+      if (r == 0) {
+        set_error("%s: level %d: the row variant of the single transpose does not take these arrays", what, l);
+        return ODIL_E_INVAL;
+      }
+    } else if (kinds[l] == kAdjGeneric) {
       InterpArgs one;
       if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
       MemberArgs m;
@@ -1023,6 +1142,86 @@ static int mg_synth_adj_adam_members(const T* gu, T* const* grads, const int64_t
         return e;
     }
     gfine = grads[l];
+  }
+  return 0;
+}
+
+// mg_synth on [R, *shape] level arrays of R rows (factors 1): one launch per level for all rows.  Rows of up to three axes
+// are the '.' + loc call; rows of four axes run the fast or the generic prolongation, the row on blockIdx.y.  All prolongation
+// kernels sum in the reference's order, so a row gets the bits of odil_mg_synth on that row alone.
+template <typename T>
+static int mg_synth_members(const T* const* terms, T* const* work, T* u, const int64_t* shapes, int nlvl, int ndim,
+                            const char* loc, int nrows, void* stream) {
+  static const char* what = "mg_synth_members";
+  if (!terms || !u || !shapes) {
+    set_error("%s: null pointer", what);
+    return ODIL_E_INVAL;
+  }
+  if (ndim < 1 || ndim > 4 || !loc || (int)strlen(loc) != ndim) {
+    set_error("%s: ndim %d (the rows are 1-D to 4-D) or a loc of another length", what, ndim);
+    return ODIL_E_INVAL;
+  }
+  for (int d = 0; d < ndim; ++d)
+    if (loc[d] != 'c' && loc[d] != 'n') {
+      set_error("%s: loc '%s' (every axis of a row is 'c' or 'n')", what, loc);
+      return ODIL_E_INVAL;
+    }
+  if (nrows < 1 || nrows > 65535) {
+    set_error("%s: %d rows (1 ... 65535)", what, nrows);
+    return ODIL_E_INVAL;
+  }
+  if (nlvl < 1 || nlvl > ODIL_MAX_LEVELS) {
+    set_error("%s: nlvl=%d out of range [1,%d]", what, nlvl, ODIL_MAX_LEVELS);
+    return ODIL_E_INVAL;
+  }
+  for (int l = 0; l < nlvl; ++l)
+    if (!terms[l] || (l >= 1 && l <= nlvl - 2 && (!work || !work[l]))) {
+      set_error("%s: null level array (level %d)", what, l);
+      return ODIL_E_INVAL;
+    }
+  if (ndim <= 3) {
+    int64_t bshapes[ODIL_MAX_LEVELS * 4];
+    char locb[8];
+    locb[0] = '.';
+    for (int d = 0; d < ndim; ++d) locb[1 + d] = loc[d];
+    locb[1 + ndim] = 0;
+    for (int l = 0; l < nlvl; ++l) {
+      bshapes[l * (ndim + 1)] = nrows;
+      for (int d = 0; d < ndim; ++d) bshapes[l * (ndim + 1) + 1 + d] = shapes[l * ndim + d];
+    }
+    return mg_synth<T>(terms, nullptr, work, u, bshapes, nlvl, ndim + 1, locb, stream);
+  }
+  if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
+  if (nlvl == 1) {
+    int64_t n0 = nrows;
+    for (int d = 0; d < ndim; ++d) n0 *= shapes[d];
+    hipLaunchKernelGGL(k_scale_copy<T>, dim3(grid_flat(n0, kBlock * 2)), dim3(kBlock), 0, (hipStream_t)stream, terms[0], u,
+                       n0, T(1));
+    return check_launch("k_scale_copy");
+  }
+  const T* coarse = terms[nlvl - 1];
+  for (int l = nlvl - 2; l >= 0; --l) {
+    T* out = l == 0 ? u : work[l];
+    InterpArgs a;
+    if (int e = fill_interp_args(a, shapes + (l + 1) * ndim, ndim, loc)) return e;
+    const int64_t npairs = (a.fn[3] + 1) / 2, xsegs = (npairs + kBlock - 1) / kBlock;
+    if (prod4(a.fn) >= ((int64_t)1 << 31) || !sched_ok(a.fn[0] * a.fn[1], a.fn[2], xsegs)) {
+      set_error("%s: level %d of a row has 2^31 elements or more", what, l);
+      return ODIL_E_INVAL;
+    }
+    // the fast kernel where it serves the layout (last two axes cell-centred: its thread tile fills the lanes on short
+    // rows, the generic kernel leaves all but fn[3] / 2 lanes of a workgroup idle), else the generic one
+    if (const int r = interp_add_fast_rows<T>(coarse, terms[l], out, a, nrows, (hipStream_t)stream)) {
+      if (r < 0) return r;
+      coarse = out;
+      continue;
+    }
+    a.sched = make_sched(a.fn[0] * a.fn[1], a.fn[2], xsegs);
+    const dim3 grid((unsigned)sched_grid(a.sched), (unsigned)nrows);
+    hipLaunchKernelGGL((k_interp_add<T, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, coarse, terms[l], out, a, T(1),
+                       T(1));
+    if (int e = check_launch("k_interp_add<rows>")) return e;
+    coarse = out;
   }
   return 0;
 }
@@ -1196,6 +1395,14 @@ int odil_mg_members_levels_ok(const int64_t* shapes, int nlvl, int ndim, const c
   return elem_size == 8
              ? members_levels_check<double>("mg_members_levels", shapes, nlvl, ndim, loc, nrows, bshapes, locb, kinds)
              : members_levels_check<float>("mg_members_levels", shapes, nlvl, ndim, loc, nrows, bshapes, locb, kinds);
+}
+int odil_mg_synth_members_f64(const double* const* terms, double* const* work, double* u, const int64_t* shapes, int nlvl,
+                              int ndim, const char* loc, int nrows, void* stream) {
+  return mg_synth_members<double>(terms, work, u, shapes, nlvl, ndim, loc, nrows, stream);
+}
+int odil_mg_synth_members_f32(const float* const* terms, float* const* work, float* u, const int64_t* shapes, int nlvl,
+                              int ndim, const char* loc, int nrows, void* stream) {
+  return mg_synth_members<float>(terms, work, u, shapes, nlvl, ndim, loc, nrows, stream);
 }
 int odil_mg_synth_adj_adam_members_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
                                        const char* loc, int nrows, double* const* x, double* const* m, double* const* v,

@@ -110,10 +110,11 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     (optinfo.route == "traced", fused.TracedLaunchEnsemble): every epoch is the launches of a single traced run -- the
     synthesis, the generated forward kernels and gathers (`stencil_bind.EpochBatch`: one launch per group of members whose
     operators generate the same source), the transposed prolongations with the updates of the coarser levels, and
-    `ops.adam_step_batch` for level 0 -- each covering all members.  'auto' then picks by dimension ('volumes' for 3-D).
+    `ops.adam_step_batch` for level 0 -- each covering all members.  'auto' then picks by dimension ('volumes' for 3-D and 4-D).
     Such members have ANY NUMBER of grid unknowns (and possibly `Array` unknowns: next paragraph), each a plain `Field` (one
     level: no transfers, exempt from the two-level rule of the forms) or a `MultigridField` with all factors 1 that coarsens
-    every axis, on a 1-D to 3-D grid.  The grid unknowns of a member share ONE location string, any mix of 'c' and 'n'
+    every axis, on a 1-D to 4-D grid (4-D: velocity_from_tracer/veltracer3d, u, vx, vy, vz at 'nccc' on (t, x, y, z); form
+    'volumes' reads as "three dimensions and more", 'launches' refuses them by name).  The grid unknowns of a member share ONE location string, any mix of 'c' and 'n'
     (velocity_from_tracer: u, vx, vy at 'ncc'; heat_tmax and infer_constant: a field at 'nc' beside an `Array`), one kind
     and the same level shapes -- an operator whose fields or outputs live on several grids stays refused -- and all members
     share keys, positions in the state, location and level shapes (else ValueError naming the member, before any state
@@ -151,8 +152,8 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
     Not served: marching kernels (float32 members of three or more dimensions with a last axis of at least 128 cells),
     parameter-space outputs that only the torch replay evaluates (reductions, broadcasts: `param_expr.Unsupported`), Newton
     -- ValueError naming the member -- and, because a single run packs its arrays back to back and its 3-D transfer
-    kernels choose by alignment, a number of elements (`Array`, `NeuralNet`, earlier grid fields) before a 3-D multigrid
-    field that is no multiple of 4 (put the parameters after the fields); 4-D members.  `optimize_newton_ensemble` keeps refusing members with `Array` or
+    kernels choose by alignment, a number of elements (`Array`, `NeuralNet`, earlier grid fields) before a 3-D or 4-D
+    multigrid field that is no multiple of 4 (put the parameters after the fields).  `optimize_newton_ensemble` keeps refusing members with `Array` or
     `NeuralNet` unknowns.
     Returns ([arrays of member b: its level arrays; with `Array` / `NeuralNet` unknowns all its arrays in state order], optinfo);
     optinfo.losses / .norms: [B, epochs] device tensors; optinfo.route: "poisson" or "traced"; optinfo.form: the form that
@@ -254,6 +255,10 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
                 what += ", {}".format("{} grid unknowns".format(len(grids)) if len(grids) > 1 else "the field at '{}'".format(loc))
             reasons["poisson"] = ("{}: such members run as traced operators -- form='launches', "
                                   "'volumes' or 'auto', with operators traced and the members on a device".format(what))
+            if domain.ndim == 4:  # (said first: how the traced route lays 4-D members out, and what that needs)
+                reasons["poisson"] = ("4-D grid: the batched launches of traced operators run 1-D to 3-D grids as a leading "
+                                      "axis of the level arrays and 4-D grids as stacked rows on a grid dimension (form="
+                                      "'volumes' or 'auto'); " + reasons["poisson"])
         if traceable or many:  # (what is not one cell-centred unknown: its structure is checked wherever it runs)
             reasons["traced"] = _traced_member(domain, [g[2] for g in grids], shapes, arrays[0].dtype,
                                                _traced_form(requested, shapes), loc)
@@ -261,14 +266,17 @@ def optimize_ensemble(args, problems, states, callback=None, lrs=None, form="wor
                 ahead = sum(math.prod(shape) for _, pos, shape in params if pos < gpos)
                 nets_ahead = sum(math.prod(shape) for _, pos, shapes_ in nets if pos < gpos for shape in shapes_)
                 ahead += nets_ahead + sum(a.numel() for _, pos, _, arrs in grids if pos < gpos for a in arrs)
-                if reasons["traced"] is None and len(shapes[0]) == 3 and len(shapes) > 1 and ahead % 4:
+                if reasons["traced"] is None and len(shapes[0]) >= 3 and len(shapes) > 1 and ahead % 4:
                     # a single run packs its arrays back to back: with `ahead` elements in front, the levels of its field are
                     # not aligned to four elements, and its 3-D transfers take other kernels (other rounding) than those of
-                    # the members' aligned level arrays here
-                    reasons["traced"] = ("{} {} elements stand before the 3-D multigrid field: a single run's level arrays are "
+                    # the members' aligned level arrays here.  4-D fields too: an 'nccc' level off the grid of two elements
+                    # runs the fast transpose where the members' rows run the marching one.  Two elements would do for
+                    # the 4-D transposes; the rule stays at 4 for 3-D and 4-D alike (one rule, and the prolongation of a
+                    # single run picks its columns per thread by 16 bytes)
+                    reasons["traced"] = ("{} {} elements stand before the {}-D multigrid field: a single run's level arrays are "
                                          "then not aligned to 4 elements and its transfer kernels round differently (put the "
                                          "{} after the field, or a multiple of 4 elements before it)".format(
-                                             ahead, "Array and NeuralNet" if nets_ahead else "Array",
+                                             ahead, "Array and NeuralNet" if nets_ahead else "Array", len(shapes[0]),
                                              "NeuralNet" if nets_ahead else "Array"))
             held = [("Array", key, state.fields[key].array) for key, _, _ in params]
             held += [("NeuralNet", key, a) for key, _, _ in nets for a in domain.arrays_from_field(state.fields[key])]
@@ -402,7 +410,7 @@ def _traced_form(requested, shapes):
     """The form the traced route of `optimize_ensemble` runs members of these level shapes in: what the caller asked for,
     'auto' by dimension."""
     if requested == "auto":
-        return "volumes" if len(shapes[0]) == 3 else "launches"
+        return "volumes" if len(shapes[0]) >= 3 else "launches"
     return requested
 
 

@@ -475,6 +475,10 @@ class TracedLaunchEnsemble(BatchedLaunches):
     of the rows are prepared once per run (`step_rows`).  `order` items are ("level", l, f); `levels`, `blocks`, `ranges`
     and `total` follow `arrays_from_state`: field by field, level by level, parameters where the state has them.  ONE
     cell-centred unknown (`stacked` False) makes exactly the launches 1 - 5 above.
+    4-D members (velocity_from_tracer/veltracer3d: u, vx, vy, vz at 'nccc' on (t, x, y, z)) always take the stacked rows,
+    even ONE 'cccc' unknown (`stacked` True): "." + loc would have five axes, one more than the transfer kernels know, so
+    launch 1 is `ops.mg_synth_members` and launch 4 runs the row variants of the three transposes a single 4-D array
+    takes (generic, fast, 'nccc' marching), the row on a grid dimension the single kernel leaves free.
     Not served: marching kernels, parameter-space outputs that only the torch replay evaluates."""
 
     def __init__(self, problems, states, form="launches"):
@@ -512,7 +516,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
         if reason is not None:
             raise ValueError("ensemble of {} members: {}".format(nb, reason))
         # one cell-centred unknown: the launches these ensembles always made; else the chain for stacked rows of any loc
-        self.stacked = nfields > 1 or loc != "c" * len(shapes[0])
+        self.stacked = rows_stacked(nfields, loc)
         self.form = form
         self.traced = []
         for b, (problem, state) in enumerate(zip(problems, states)):
@@ -615,6 +619,14 @@ class TracedLaunchEnsemble(BatchedLaunches):
             return alphas.repeat(self.nfields)
         return alphas
 
+    def _synthesis(self):
+        """Launch 1: u of all rows.  Rows of four axes have no '.' + loc view (it would have five axes):
+        `ops.mg_synth_members` puts the row on a grid dimension."""
+        if self.nlvl > 1 and self.ndim == 4:
+            ops.mg_synth_members(self.x, self.loc[1:], work=self.work, out=self.u)
+        elif self.nlvl > 1:
+            ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+
     def _transposes(self):
         if not self.stacked:
             return super()._transposes()
@@ -670,8 +682,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
     def epoch(self, alphas, omb1, omb2, eps):
         """One Adam epoch of every member; alphas: DEVICE step sizes, [B] or one element shared by all members.  The [B]
         losses the epoch evaluated (before its update) land in self.loss."""
-        if self.nlvl > 1:
-            ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+        self._synthesis()
         for batch in self.batches:
             batch.launch()
         if not self.par_batches:
@@ -688,8 +699,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
         self._evaluate(rows[:self.nbatch] if rows.numel() > self.nbatch else rows, omb1, omb2, eps)
 
     def loss_grad(self):
-        if self.nlvl > 1:
-            ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
+        self._synthesis()
         for batch in self.batches:
             batch.launch()
         if not self.par_batches:
@@ -698,17 +708,27 @@ class TracedLaunchEnsemble(BatchedLaunches):
         self._evaluate()
 
 
+def rows_stacked(nfields, loc):
+    """Does `TracedLaunchEnsemble` run members with `nfields` grid unknowns at `loc` through the chain for stacked rows?
+    Anything but ONE cell-centred unknown does, and every 4-D member: its rows have no '.' + loc view, and the chain of
+    the volumes (`ops.mg_synth_adj_adam_volumes`) is 3-D only."""
+    return nfields > 1 or loc != "c" * len(loc) or len(loc) == 4
+
+
 def traced_refusal(shapes, dtype, form, nbatch=1, loc=None, nfields=1):
     """Why members of these level shapes are not run by `TracedLaunchEnsemble` in `form` ('launches': 1-D / 2-D, 'volumes':
-    3-D), or None: `launches_refusal` / `volumes_refusal`, the one-level case (a plain `Field`: no transfers) exempt from
+    three dimensions and more, i.e. 3-D and 4-D), or None: `launches_refusal` / `volumes_refusal`, the one-level case (a plain `Field`: no transfers) exempt from
     their two-level rule.  loc, nfields: the location string the members' grid unknowns share and how many a member has;
     anything but ONE cell-centred unknown runs the chain for stacked rows, and the library says whether every level of the
-    nfields * nbatch rows would run what that level of one member runs (odil_mg_members_levels_ok)."""
+    nfields * nbatch rows would run what that level of one member runs (odil_mg_members_levels_ok).  A 4-D member always
+    takes the stacked rows, even ONE 'cccc' unknown."""
     ndim = len(shapes[0])
-    if loc is not None and (nfields > 1 or loc != "c" * ndim):
+    if ndim == 4:  # (always the stacked rows, even ONE 'cccc' unknown: `mg_synth_adj_adam_volumes` is 3-D only)
+        loc = "c" * ndim if loc is None else loc
+    if loc is not None and rows_stacked(nfields, loc):
         return _members_refusal(shapes, dtype, form, nbatch * nfields, loc)
     if not 1 <= ndim <= 3:
-        return "{}-D grid: the batched launches of traced operators run 1-D to 3-D grids".format(ndim)
+        return "{}-D grid: the batched launches of traced operators run 1-D to 4-D grids".format(ndim)
     if dtype not in (torch.float64, torch.float32):
         return "dtype {}: the kernels run float64 and float32".format(dtype)
     if (form == "volumes") != (ndim == 3):
@@ -724,12 +744,12 @@ def traced_refusal(shapes, dtype, form, nbatch=1, loc=None, nfields=1):
 def _members_refusal(shapes, dtype, form, nrows, loc):
     """`traced_refusal` for members with several grid unknowns or node-centred axes (`nrows` stacked rows at `loc`)."""
     ndim = len(shapes[0])
-    if not 1 <= ndim <= 3:
-        return "{}-D grid: the batched launches of traced operators run 1-D to 3-D grids".format(ndim)
+    if not 1 <= ndim <= 4:
+        return "{}-D grid: the batched launches of traced operators run 1-D to 4-D grids".format(ndim)
     if dtype not in (torch.float64, torch.float32):
         return "dtype {}: the kernels run float64 and float32".format(dtype)
-    if (form == "volumes") != (ndim == 3):
-        return "{}-D grid: form '{}' runs {} grids".format(ndim, form, "3-D" if form == "volumes" else "1-D and 2-D")
+    if (form == "volumes") != (ndim >= 3):
+        return "{}-D grid: form '{}' runs {} grids".format(ndim, form, "3-D and 4-D" if form == "volumes" else "1-D and 2-D")
     reason = _unaligned_members(shapes, dtype)
     if reason is not None or len(shapes) == 1:
         return reason

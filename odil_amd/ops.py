@@ -979,7 +979,7 @@ def mg_synth_adj_adam_volumes(gu, shapes, grads, x, m, v, alphas, one_minus_b1, 
 def mg_synth_adj_adam_members(gu, shapes, loc, grads, x=None, m=None, v=None, alphas=None, one_minus_b1=0.0, one_minus_b2=0.0,
                               eps=0.0, period=0):
     """`mg_synth_adj_adam` on contiguous [R, *shape] level arrays of R rows (`shapes`: the level shapes of ONE row, `loc`:
-    its location string, any mix of 'c' and 'n', 1-D to 3-D): one launch per level for all rows, the update of the levels
+    its location string, any mix of 'c' and 'n', 1-D to 4-D): one launch per level for all rows, the update of the levels
     >= 1 inside it.  alphas: DEVICE step sizes; row r reads alphas[r % period] (period 0: alphas[r]; one element: shared by
     all rows).  x, m, v all None: the gradients alone.  Entry 0 of grads, x, m, v is not touched (the chain reads gu).
     Per row: the gradients of `mg_synth_adj`, the x, m, v of `adam_step`, bit for bit."""
@@ -1000,6 +1000,25 @@ def mg_synth_adj_adam_members(gu, shapes, loc, grads, x=None, m=None, v=None, al
          loc.encode(), c_int(nr), *((none0(x), none0(m), none0(v)) if update else (None, None, None)), float(one_minus_b1),
          float(one_minus_b2), float(eps), ptr(alphas) if update else None, c_int64(stride), c_int64(period), stream_ptr())
     return grads
+
+
+def mg_synth_members(terms, loc, work=None, out=None):
+    """`mg_synth` (factors 1) on contiguous [R, *shape] level arrays of R rows (`loc`: the location string of ONE row, any
+    mix of 'c' and 'n', 1-D to 4-D): one launch per level for all rows, row r the bits of `mg_synth` on that row alone.
+    Rows of four axes, which have no '.' + loc view, run the fast prolongation where it takes the layout and the generic
+    one elsewhere, the row on a grid dimension."""
+    nlvl, nr = len(terms), int(terms[0].shape[0])
+    shapes = [tuple(int(n) for n in t.shape[1:]) for t in terms]
+    assert len(loc) == len(shapes[0]) and all(t.shape[0] == nr and t.is_contiguous() and t.dtype == terms[0].dtype for t in terms)
+    if out is None:
+        out = torch.empty_like(terms[0])
+    if work is None:
+        work = ([None] + [torch.empty_like(t) for t in terms[1:-1]] + [None])[:nlvl]
+    assert out.shape == terms[0].shape and out.is_contiguous() and out.dtype == terms[0].dtype
+    assert all(w is None or (w.shape == t.shape and w.is_contiguous() and w.dtype == t.dtype) for w, t in zip(work, terms))
+    call("mg_synth_members", terms[0].dtype, ptr_array(terms), ptr_array(work), ptr(out), i64([n for s in shapes for n in s]),
+         c_int(nlvl), c_int(len(shapes[0])), loc.encode(), c_int(nr), stream_ptr())
+    return out
 
 
 def jacobi2_supported(shape, dtype):
