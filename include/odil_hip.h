@@ -692,15 +692,12 @@ int odil_poisson_small_epochs_batch_f32(float* x, float* m, float* v, float* g, 
  *                            (partials_stride >= odil_poisson_batch_partials(shape, ndim, elem_size))
  *   loss                     [nbatch] mean(fu[b]^2)
  *   alpha_dev                DEVICE step sizes, member b's at b * alpha_stride; alpha_stride = 0: one for all members
- * The synthesis needs no entry point of its own: odil_mg_synth on [nbatch, *shape] arrays with loc '.' + loc.
- * odil_mg_synth_adj_adam_batch is odil_mg_synth_adj_adam with factors 1 on contiguous [nbatch, *shape] level arrays,
- * `shapes` being the nlvl x ndim extents of ONE member, all axes cell-centred.
+ * The transfers need no entry points of their own: the synthesis is odil_mg_synth on [nbatch, *shape] arrays with loc
+ * '.' + loc, the transposed chain with the updates odil_mg_synth_adj_adam_members, declared below, with nrows = nbatch, loc 'c' or
+ * 'cc'; odil_mg_members_levels_ok says from the shapes alone whether a batch may run them, so that a host can refuse
+ * it before its first launch.
  * Refused before anything is launched: null pointers, nbatch outside 1 ... 65535, ndim outside 1 ... 2, a member stride
- * below a member's size or off the 16-byte grid, a partials workspace shorter than nbatch rows, and a batch whose
- * transfer levels would not run the kernel that a single member's levels run.  odil_mg_batch_levels_ok answers the
- * last question for both transfer chains from the shapes alone (0: they do; else the reason is the error text), so
- * that a host can refuse such a batch before its first launch. */
-int odil_mg_batch_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch);
+ * below a member's size or off the 16-byte grid, a partials workspace shorter than nbatch rows. */
 int64_t odil_poisson_batch_partials(const int64_t* shape, int ndim, int elem_size);
 int odil_poisson_residual_batch_f64(const double* u, const double* rhs, double* fu, int nbatch, int64_t u_stride,
                                     int64_t rhs_stride, int64_t fu_stride, const int64_t* shape, int ndim,
@@ -720,14 +717,6 @@ int odil_poisson_adjoint_adam_batch_f32(const float* fu, float* gu, float* x, fl
                                         int64_t v_stride, const int64_t* shape, int ndim, const float* h2, float scale,
                                         float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
                                         int64_t alpha_stride, void* stream);
-int odil_mg_synth_adj_adam_batch_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                     int nbatch, double* const* x, double* const* m, double* const* v, double one_minus_b1,
-                                     double one_minus_b2, double eps, const double* alpha_dev, int64_t alpha_stride,
-                                     void* stream);
-int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                     int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
-                                     float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
-                                     void* stream);
 
 /* An ENSEMBLE of nbatch 3-D Poisson problems of one shape as batched launches: every launch of a single 3-D problem's
  * epoch (odil_mg_synth on the coarse levels, odil_poisson_residual_synth, odil_poisson_adjoint_adam,
@@ -744,20 +733,16 @@ int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const
  *   loss                     [nbatch] mean(fu[b]^2) over the full plane range (there is no slab form)
  *   alpha_dev                DEVICE step sizes, member b's at b * alpha_stride; alpha_stride = 0: one for all members
  * odil_poisson_adjoint_adam_volumes is odil_poisson_adjoint_adam_batch for ndim = 3 (gu = NULL: the gradient is not
- * stored).  odil_mg_synth_adj_adam_volumes is odil_mg_synth_adj_adam with factors 1 on contiguous [nbatch, *shape] level
- * arrays as '.ccc', `shapes` being the nlvl x 3 extents of ONE member: a level runs the rows, tile, marching or fast
- * kernel that the same level of a single volume runs, and that kernel reads the step size of its volume.
+ * stored).  The transposed chain with the updates is odil_mg_synth_adj_adam_members, declared below, with nrows = nbatch, loc
+ * 'ccc': a level runs the rows, tile, marching or fast kernel that the same level of a single volume runs on the
+ * [nbatch, *shape] array as '.ccc', and that kernel reads the step size of its volume.
  * Refused before anything is launched: null pointers, nbatch outside 1 ... 65535, ndim != 3, a member stride below a
- * member's size or off the 16-byte grid, a partials or column-sum workspace that is too short, a grid beyond one launch,
- * gradient arrays off the 16-byte grid, and a batch one of whose transfer levels would not run the kernel that level of
- * a single member runs.  odil_mg_volumes_levels_ok answers the last question from the shapes, nbatch and the element
- * size alone (0: they do; else the reason is the error text).
+ * member's size or off the 16-byte grid, a partials or column-sum workspace that is too short, a grid beyond one launch.
  * odil_interp_adj_kind names the transposed prolongation odil_interp_adj runs for a coarse shape and layout on arrays
  * aligned to 16 bytes, nothing launched: 0 the generic kernel, 1 the fast kernel, 2 a node-centred marching kernel, 3 the
  * row-marching kernel (float), 4 the LDS-tile kernel, 5 the z-marching kernel; negative: an error.  Kernels 3, 4 and 5
  * round differently in float. */
 int odil_interp_adj_kind(const int64_t* cshape, int ndim, const char* loc, int elem_size);
-int odil_mg_volumes_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch, int elem_size);
 size_t odil_poisson_residual_synth_batch_workspace_bytes(const int64_t* cshape);
 int64_t odil_poisson_residual_synth_batch_partials(const int64_t* cshape);
 int odil_poisson_residual_synth_batch_f64(const double* coarse, const double* w0, const double* rhs, double* fu,
@@ -780,17 +765,10 @@ int odil_poisson_adjoint_adam_volumes_f32(const float* fu, float* gu, float* x, 
                                           int64_t v_stride, const int64_t* shape, int ndim, const float* h2, float scale,
                                           float one_minus_b1, float one_minus_b2, float eps, const float* alpha_dev,
                                           int64_t alpha_stride, void* stream);
-int odil_mg_synth_adj_adam_volumes_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                       int nbatch, double* const* x, double* const* m, double* const* v,
-                                       double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
-                                       int64_t alpha_stride, void* stream);
-int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                       int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
-                                       float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
-                                       void* stream);
-/* The transposed prolongation chain for the STACKED rows of an ensemble: [nrows, *shape] level arrays (contiguous, layout
- * '.' + loc) of 1-D to 3-D rows with ANY loc of 'c' / 'n' -- the F grid unknowns of B members as nrows = F B rows, row
- * f B + b.  `shapes` are the nlvl x ndim extents of ONE row.  One launch per level for all rows; the Adam update of the
+/* The transposed prolongation chain of EVERY ensemble that runs as batched launches: [nrows, *shape] level arrays
+ * (contiguous, layout '.' + loc) of 1-D to 4-D rows with ANY loc of 'c' / 'n' -- the B members of a Poisson ensemble
+ * (loc 'c', 'cc', 'ccc'), or the F grid unknowns of B members as nrows = F B rows, row f B + b.  `shapes` are the
+ * nlvl x ndim extents of ONE row.  One launch per level for all rows; the Adam update of the
  * levels >= 1 runs in the launch that forms their gradient, row r with the step size alpha_dev[(r % period) *
  * alpha_stride] (period 0: r itself; alpha_stride 0: one step size for all rows).  x = m = v = NULL: the gradients alone
  * (entry 0 of grads, x, m, v is never touched: the chain reads gu).  A level whose single transpose is the fast or a
@@ -799,9 +777,19 @@ int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, con
  * single transpose is the generic kernel (a node-centred y or x axis: 'nc', 'cn', 'nn', 'n') runs k_interp_adj_members,
  * the generic kernel's sum per coarse value with the row on a grid dimension and the update in the same thread.  Per row
  * the gradients are the bits of odil_mg_synth_adj on that row alone, x, m, v those of odil_adam_step.
- * Refused before anything is launched: null pointers, nrows outside 1 ... 65535, ndim outside 1 ... 4, a loc with '.',
- * fewer than two levels, gradient arrays off the 16-byte grid, a negative stride or period, and rows one of whose levels
- * would not compute what that level of a single row computes.
+ * All-cell rows ('c', 'cc', 'ccc') are generic only beyond the limits of the fast and the marching kernels: an extent of
+ * 2^30 or more, or a schedule that cannot be counted in 31 bits (a 3-D level with fewer than 4 coarse planes is fast, not
+ * generic).  Such a level is not refused: it runs k_interp_adj_members with the bits of the single run, like any other
+ * generic level.  A level that is NOT generic for one row must be of the same kind on the stacked array: 65535 members
+ * of (1 << 25,) -> (1 << 24,), fast alone and generic stacked, are refused, not rerouted.
+ * A level of 2^31 elements or more per row is refused where a row kernel, which numbers the elements of a row with an
+ * int, could meet it: on every level of rows of four axes or with a node-centred axis, and on a generic level of
+ * all-cell rows.  Other levels of all-cell rows of up to three axes run the single launch on the '.' + loc array and
+ * have no such limit -- for one unknown per member (the Poisson ensembles never had it) and for several alike.
+ * Refused before anything is launched: null pointers (the tables and every level array), nrows outside 1 ... 65535,
+ * ndim outside 1 ... 4, a loc with '.', fewer than two levels, levels that do not refine, a coarsest extent below 2,
+ * gradient arrays off the 16-byte grid, a negative stride or period, and rows one of whose levels would not compute what
+ * that level of a single row computes.
  * odil_mg_members_levels_ok answers the last question -- for this chain and for the prolongation odil_mg_synth runs on
  * the same arrays, whose kernels all sum in the reference's order -- from shapes, loc, nrows and the element size alone
  * (0: they do; else the reason is the error text).
@@ -809,7 +797,7 @@ int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, con
  * kernels has four axes, so the row cannot ride as a leading '.' axis.  A single 4-D array runs one of three transposes,
  * and each has a row variant with the row on a grid dimension the single kernel does not use, base pointers offset by
  * the row, schedule, arithmetic and summation order those of the single launch: the generic kernel
- * (k_interp_adj_members4: a node-centred y or x axis), the fast kernel (the ROWS instantiations of k_interp_adj_fast)
+ * (k_interp_adj_members, which has four row axes: a node-centred y or x axis), the fast kernel (the ROWS instantiations of k_interp_adj_fast)
  * and the 'nccc' marching kernel (the ROWS instantiation of k_interp_adj_march_lead, the row on blockIdx.z).
  * odil_mg_members_levels_ok refuses, naming the level, a level whose single kind is none of these and a level of the
  * latter two kinds whose rows are no multiple of 16 bytes (the kernels read packs, and choose their columns per thread,
@@ -838,8 +826,7 @@ int odil_mg_synth_members_f32(const float* const* terms, float* const* work, flo
  * gu[b] = odil_poisson_adjoint of fu[b] for nbatch 1-D, 2-D or 3-D members in one launch, member b = blockIdx.y on the
  * single kernel's walk, bit for bit.  Strides as above (>= cells of a member, multiples of 16 bytes).  Refused before
  * anything is launched: null pointers, nbatch outside 1 ... 65535, ndim outside 1 ... 3, such strides.  The transposed
- * prolongations need no entry point: odil_mg_synth_adj on [nbatch, *shape] arrays with loc '.' + loc runs the levels
- * that odil_mg_batch_levels_ok / odil_mg_volumes_levels_ok vouch for. */
+ * prolongations are odil_mg_synth_adj_adam_members with x = m = v = NULL. */
 int odil_poisson_adjoint_batch_f64(const double* fu, double* gu, int nbatch, int64_t fu_stride, int64_t g_stride,
                                    const int64_t* shape, int ndim, const double* h2, double scale, void* stream);
 int odil_poisson_adjoint_batch_f32(const float* fu, float* gu, int nbatch, int64_t fu_stride, int64_t g_stride,

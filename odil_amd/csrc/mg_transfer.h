@@ -136,6 +136,35 @@ __device__ inline AdjTaps make_adj_taps(int loc, int64_t J, int64_t n, int64_t F
   return t;
 }
 
+// One coarse value of P^T on a canonical 4-D array: the sums over the windows of the four axes, the leading axis
+// outermost, zero-weight taps skipped, the reflect sum only where some axis is special.  gfine: the fine array (of one
+// row), fs0 / fs1 / fs2 its strides.  The generic kernel and its row form (mg_transfer.hip) both sum here.
+template <typename T>
+__device__ __forceinline__ T interp_adj_gather(const AdjTaps& t0, const AdjTaps& t1, const AdjTaps& t2, const AdjTaps& t3,
+                                               int64_t fs0, int64_t fs1, int64_t fs2, const T* __restrict__ gfine) {
+  const bool special = t0.special || t1.special || t2.special || t3.special;
+  T sc = T(0), sr = T(0);
+  for (int i0 = 0; i0 < t0.cnt; ++i0) {
+    if (t0.wc[i0] == 0.f && t0.wr[i0] == 0.f) continue;
+    for (int i1 = 0; i1 < t1.cnt; ++i1) {
+      if (t1.wc[i1] == 0.f && t1.wr[i1] == 0.f) continue;
+      for (int i2 = 0; i2 < t2.cnt; ++i2) {
+        if (t2.wc[i2] == 0.f && t2.wr[i2] == 0.f) continue;
+        const T wcl = T(t0.wc[i0] * t1.wc[i1] * t2.wc[i2]);
+        const T wrl = T(t0.wr[i0] * t1.wr[i1] * t2.wr[i2]);
+        const int64_t base = (t0.k0 + i0) * fs0 + (t1.k0 + i1) * fs1 + (t2.k0 + i2) * fs2;
+        for (int i3 = 0; i3 < t3.cnt; ++i3) {
+          if (t3.wc[i3] == 0.f && t3.wr[i3] == 0.f) continue;
+          const T g = gfine[base + t3.k0 + i3];
+          sc = sc + (wcl * T(t3.wc[i3])) * g;
+          if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
+        }
+      }
+    }
+  }
+  return special ? T(2) * sc - sr : sc;
+}
+
 // Fast paths (mg_fast.hip): last axis 'c', second-to-last 'c' or '.', any leading axes.
 // Return 1 if they handled the call, 0 if the generic kernel must run, <0 on error.
 template <typename T>

@@ -95,27 +95,7 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj(const T* __restrict__ gfi
     if (c3 >= a.cn[3]) continue;
     const AdjTaps t3 = make_adj_taps(a.loc[3], c3, a.cn[3], a.fn[3], a.cut_axis == 3 && a.cut_lo,
                                         a.cut_axis == 3 && a.cut_hi);
-    const bool special = t0.special || t1.special || t2.special || t3.special;
-    T sc = T(0), sr = T(0);
-    for (int i0 = 0; i0 < t0.cnt; ++i0) {
-      if (t0.wc[i0] == 0.f && t0.wr[i0] == 0.f) continue;
-      for (int i1 = 0; i1 < t1.cnt; ++i1) {
-        if (t1.wc[i1] == 0.f && t1.wr[i1] == 0.f) continue;
-        for (int i2 = 0; i2 < t2.cnt; ++i2) {
-          if (t2.wc[i2] == 0.f && t2.wr[i2] == 0.f) continue;
-          const T wcl = T(t0.wc[i0] * t1.wc[i1] * t2.wc[i2]);
-          const T wrl = T(t0.wr[i0] * t1.wr[i1] * t2.wr[i2]);
-          const int64_t base = (t0.k0 + i0) * fs0 + (t1.k0 + i1) * fs1 + (t2.k0 + i2) * fs2;
-          for (int i3 = 0; i3 < t3.cnt; ++i3) {
-            if (t3.wc[i3] == 0.f && t3.wr[i3] == 0.f) continue;
-            const T g = gfine[base + t3.k0 + i3];
-            sc = sc + (wcl * T(t3.wc[i3])) * g;
-            if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
-          }
-        }
-      }
-    }
-    const T v = special ? T(2) * sc - sr : sc;
+    const T v = interp_adj_gather<T>(t0, t1, t2, t3, fs0, fs1, fs2, gfine);
     const int64_t ci = c0 * cs0 + c1 * cs1 + c2 * cs2 + c3;
     gcoarse[ci] = v;
     if (gscaled) gscaled[ci] = scale * v;
@@ -412,107 +392,37 @@ __global__ __launch_bounds__(kBlock) void k_interp_adj_lead_node_wide(const T* _
 }
 
 // ------------------------------------------------------------------------------------
-// P^T of the layouts the generic kernel serves (a node-centred y or x axis: 'nc', 'cn', 'nn', 'n', ...) for the R rows of
-// [R, *shape] level arrays at once, with the update of the coarse level in the thread that forms its gradient.  The row
-// is blockIdx.y; the coarse elements of a row are numbered flat over blockIdx.x, so coarse rows of 3, 5 or 9 elements
+// P^T of the layouts the generic kernel serves (a node-centred y or x axis: 'nc', 'cn', 'nn', 'n', 'cccn', ...) for the R
+// rows of [R, *shape] level arrays at once, with the update of the coarse level in the thread that forms its gradient.  The
+// row is blockIdx.y; the coarse elements of a row are numbered flat over blockIdx.x, so coarse rows of 3, 5 or 9 elements
 // fill the lanes like any other (no lane is parked behind the end of a short row, none walks a tail).  Every coarse
 // value is the sum of k_interp_adj over the same window in the same order: the bits of the generic kernel on that row alone.
 // ------------------------------------------------------------------------------------
 struct MemberArgs {
-  int cn[3], fn[3];  // the last three canonical axes of ONE row (leading ones of extent 1, loc '.')
-  int loc[3];
+  int cn[4], fn[4];  // the canonical axes of ONE row (rows of fewer than four axes: leading ones of extent 1, loc '.')
+  int loc[4];
   int64_t ccells, fcells;  // elements of a coarse / fine row
 };
 
-template <typename T>
+// LEAD: the rows have four axes.  Without it the leading axis is known to be '.' of extent 1 when the kernel is compiled:
+// its one tap of weight 1 and its division fold away, and with them a quarter of the tap tables, which live in scratch
+// (136 instead of 200 bytes per lane; rows of one to three axes were measurably slower without the flag: DESIGN.md).
+template <typename T, bool LEAD>
 __global__ __launch_bounds__(kBlock) void k_interp_adj_members(const T* __restrict__ gfine, T* __restrict__ gcoarse,
                                                                MemberArgs a, AdamArgs<T> ad) {
   const int64_t flat = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (flat >= a.ccells) return;
   const int64_t row = blockIdx.y;
-  const int plane = a.cn[1] * a.cn[2];
-  const int at = (int)flat;
-  const int c1 = at / plane, r = at - c1 * plane, c2 = r / a.cn[2], c3 = r - c2 * a.cn[2];
-  const int64_t fs2 = a.fn[2], fs1 = (int64_t)a.fn[1] * fs2;
-  const AdjTaps t1 = make_adj_taps(a.loc[0], c1, a.cn[0], a.fn[0]);
-  const AdjTaps t2 = make_adj_taps(a.loc[1], c2, a.cn[1], a.fn[1]);
-  const AdjTaps t3 = make_adj_taps(a.loc[2], c3, a.cn[2], a.fn[2]);
-  const bool special = t1.special || t2.special || t3.special;
-  const T* __restrict__ gf = gfine + row * a.fcells;
-  T sc = T(0), sr = T(0);
-  // (the loops of k_interp_adj; its two leading axes are '.' here: one tap of weight 1 each)
-  for (int i1 = 0; i1 < t1.cnt; ++i1) {
-    if (t1.wc[i1] == 0.f && t1.wr[i1] == 0.f) continue;
-    for (int i2 = 0; i2 < t2.cnt; ++i2) {
-      if (t2.wc[i2] == 0.f && t2.wr[i2] == 0.f) continue;
-      const T wcl = T(1.f * t1.wc[i1] * t2.wc[i2]);
-      const T wrl = T(1.f * t1.wr[i1] * t2.wr[i2]);
-      const int64_t base = (t1.k0 + i1) * fs1 + (t2.k0 + i2) * fs2;
-      for (int i3 = 0; i3 < t3.cnt; ++i3) {
-        if (t3.wc[i3] == 0.f && t3.wr[i3] == 0.f) continue;
-        const T g = gf[base + t3.k0 + i3];
-        sc = sc + (wcl * T(t3.wc[i3])) * g;
-        if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
-      }
-    }
-  }
-  const T v = special ? T(2) * sc - sr : sc;
-  const int64_t ci = row * a.ccells + flat;
-  gcoarse[ci] = v;
-  if (ad.x) {
-    T xv = ad.x[ci], mv = ad.m[ci], vv = ad.v[ci];
-    adam_update<T>(xv, mv, vv, v, ad, row);
-    ad.x[ci] = xv;
-    ad.m[ci] = mv;
-    ad.v[ci] = vv;
-  }
-}
-
-// The same for rows of FOUR axes ([R, t, x, y, z] arrays: 'cccn', 'ccnc', 'nnnn', ...): the fourth tap loop outermost, as
-// k_interp_adj sums a 4-D array.
-struct MemberArgs4 {
-  int cn[4], fn[4];
-  int loc[4];
-  int64_t ccells, fcells;  // elements of a coarse / fine row
-};
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_interp_adj_members4(const T* __restrict__ gfine, T* __restrict__ gcoarse,
-                                                                MemberArgs4 a, AdamArgs<T> ad) {
-  const int64_t flat = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (flat >= a.ccells) return;
-  const int64_t row = blockIdx.y;
   const int plane = a.cn[2] * a.cn[3], vol = a.cn[1] * plane;
   const int at = (int)flat;
-  const int c0 = at / vol, r0 = at - c0 * vol, c1 = r0 / plane, r = r0 - c1 * plane, c2 = r / a.cn[3], c3 = r - c2 * a.cn[3];
+  const int c0 = LEAD ? at / vol : 0, r0 = at - c0 * vol, c1 = r0 / plane, r = r0 - c1 * plane, c2 = r / a.cn[3],
+            c3 = r - c2 * a.cn[3];
   const int64_t fs2 = a.fn[3], fs1 = (int64_t)a.fn[2] * fs2, fs0 = (int64_t)a.fn[1] * fs1;
-  const AdjTaps t0 = make_adj_taps(a.loc[0], c0, a.cn[0], a.fn[0]);
+  const AdjTaps t0 = LEAD ? make_adj_taps(a.loc[0], c0, a.cn[0], a.fn[0]) : make_adj_taps(kNone, 0, 1, 1);
   const AdjTaps t1 = make_adj_taps(a.loc[1], c1, a.cn[1], a.fn[1]);
   const AdjTaps t2 = make_adj_taps(a.loc[2], c2, a.cn[2], a.fn[2]);
   const AdjTaps t3 = make_adj_taps(a.loc[3], c3, a.cn[3], a.fn[3]);
-  const bool special = t0.special || t1.special || t2.special || t3.special;
-  const T* __restrict__ gf = gfine + row * a.fcells;
-  T sc = T(0), sr = T(0);
-  // (the loops of k_interp_adj)
-  for (int i0 = 0; i0 < t0.cnt; ++i0) {
-    if (t0.wc[i0] == 0.f && t0.wr[i0] == 0.f) continue;
-    for (int i1 = 0; i1 < t1.cnt; ++i1) {
-      if (t1.wc[i1] == 0.f && t1.wr[i1] == 0.f) continue;
-      for (int i2 = 0; i2 < t2.cnt; ++i2) {
-        if (t2.wc[i2] == 0.f && t2.wr[i2] == 0.f) continue;
-        const T wcl = T(t0.wc[i0] * t1.wc[i1] * t2.wc[i2]);
-        const T wrl = T(t0.wr[i0] * t1.wr[i1] * t2.wr[i2]);
-        const int64_t base = (t0.k0 + i0) * fs0 + (t1.k0 + i1) * fs1 + (t2.k0 + i2) * fs2;
-        for (int i3 = 0; i3 < t3.cnt; ++i3) {
-          if (t3.wc[i3] == 0.f && t3.wr[i3] == 0.f) continue;
-          const T g = gf[base + t3.k0 + i3];
-          sc = sc + (wcl * T(t3.wc[i3])) * g;
-          if (special) sr = sr + (wrl * T(t3.wr[i3])) * g;
-        }
-      }
-    }
-  }
-  const T v = special ? T(2) * sc - sr : sc;
+  const T v = interp_adj_gather<T>(t0, t1, t2, t3, fs0, fs1, fs2, gfine + row * a.fcells);
   const int64_t ci = row * a.ccells + flat;
   gcoarse[ci] = v;
   if (ad.x) {
@@ -606,8 +516,8 @@ static int interp_adj(const T* gfine, T* gcoarse, T* gscaled, const int64_t* csh
     return ODIL_E_INVAL;
   }
   if (ad.x && ad.alpha_stride) {
-    // an ensemble with a step size per member: the fast kernel is the one that reads it (odil_mg_synth_adj_adam_batch
-    // has checked that it serves every level; never another arithmetic path, never a launch without the stride); the
+    // an ensemble with a step size per member: the fast kernel is the one that reads it (odil_mg_synth_adj_adam_members
+    // has checked that it serves the level; never another arithmetic path, never a launch without the stride); the
     // volumes of a '.ccc' ensemble (member_axis 0) go through the marching kernels first, as a single volume does
     if (ad.member_axis == 0 && a.loc[0] == kNone && !coarse_ld)
       if (int r = interp_adj_march<T>(gfine, gcoarse, gscaled, a, scale, (hipStream_t)stream, ad)) return r < 0 ? r : 0;
@@ -778,7 +688,7 @@ template <typename T>
 static int mg_synth_adj(const T* gu, T* const* grads, const T* factors, T* const* work, const int64_t* shapes,
                         int nlvl, int ndim, const char* loc, void* stream, T* const* ax = nullptr,
                         T* const* am = nullptr, T* const* av = nullptr, T alpha = T(0), T omb1 = T(0), T omb2 = T(0),
-                        T eps = T(0), const T* alpha_dev = nullptr, int64_t alpha_stride = 0, int member_axis = 0) {
+                        T eps = T(0), const T* alpha_dev = nullptr) {
   if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
   if (!gu || !grads) {
     set_error("mg_synth_adj: null pointer");
@@ -808,7 +718,7 @@ static int mg_synth_adj(const T* gu, T* const* grads, const T* factors, T* const
       unscaled = work[l];
       scaled = grads[l];
     }
-    AdamArgs<T> ad{nullptr, nullptr, nullptr, alpha, omb1, omb2, eps, alpha_dev, alpha_stride, member_axis};
+    AdamArgs<T> ad{nullptr, nullptr, nullptr, alpha, omb1, omb2, eps, alpha_dev};
     if (ax && ax[l]) {
       ad.x = ax[l];
       ad.m = am[l];
@@ -820,161 +730,35 @@ static int mg_synth_adj(const T* gu, T* const* grads, const T* factors, T* const
   return 0;
 }
 
-// Do all transfer levels of a batch of nbatch members ([nbatch, *shape] arrays, layout '.' + 'c' * ndim) run the fast
-// kernel that the levels of ONE member run?  Fills bshapes with the nlvl x (ndim + 1) batched extents.  Nothing is launched.
-static int batch_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, int nbatch, int64_t* bshapes) {
-  if (ndim < 1 || ndim > 2 || !shapes) {
-    set_error("%s: ndim %d (the ensemble runs 1-D and 2-D members) or null shapes", what, ndim);
-    return ODIL_E_INVAL;
-  }
-  if (nbatch < 1 || nbatch > 65535) {
-    set_error("%s: %d members (1 ... 65535)", what, nbatch);
-    return ODIL_E_INVAL;
-  }
-  if (nlvl < 2 || nlvl > ODIL_MAX_LEVELS) {
-    set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
-    return ODIL_E_INVAL;
-  }
-  const char* loc1 = ndim == 1 ? "c" : "cc";
-  const char* locb = ndim == 1 ? ".c" : ".cc";
+// The level arrays of `nrows` rows of up to three axes as ONE array per level with the rows as a leading axis that is not
+// coarsened: bshapes gets the nlvl x (ndim + 1) extents [nrows, *shape], locb '.' + loc.
+static void stacked_levels(const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows, int64_t* bshapes,
+                           char* locb) {
+  locb[0] = '.';
+  for (int d = 0; d < ndim; ++d) locb[1 + d] = loc[d];
+  locb[1 + ndim] = 0;
   for (int l = 0; l < nlvl; ++l) {
-    bshapes[l * (ndim + 1)] = nbatch;
+    bshapes[l * (ndim + 1)] = nrows;
     for (int d = 0; d < ndim; ++d) bshapes[l * (ndim + 1) + 1 + d] = shapes[l * ndim + d];
   }
-  if (int e = check_levels(shapes, nlvl, ndim, loc1)) return e;
-  for (int l = 1; l < nlvl; ++l) {
-    InterpArgs one, all;
-    if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc1)) return e;
-    if (int e = fill_interp_args(all, bshapes + l * (ndim + 1), ndim + 1, locb)) return e;
-    if (!interp_fast_serves(one) || !interp_fast_serves(all)) {
-      set_error("%s: level %d of %d members would not run the transfer kernel one member runs", what, l, nbatch);
-      return ODIL_E_INVAL;
-    }
-  }
-  return 0;
-}
-
-// mg_synth_adj with the updates, on [B, *shape] level arrays of B members (layout '.' + loc, all axes of a member
-// cell-centred): what B calls of the single form launch per level, in one launch per level.  Refuses, before anything
-// is launched, a batch whose levels would not all run the fast kernel a single member's levels run.
-template <typename T>
-static int mg_synth_adj_adam_batch(const T* gu, T* const* grads, const int64_t* shapes, int nlvl, int ndim, int nbatch,
-                                   T* const* ax, T* const* am, T* const* av, T omb1, T omb2, T eps, const T* alpha_dev,
-                                   int64_t alpha_stride, void* stream) {
-  static const char* what = "mg_synth_adj_adam_batch";
-  if (ndim < 1 || ndim > 2) {
-    set_error("%s: ndim %d (the ensemble runs 1-D and 2-D members)", what, ndim);
-    return ODIL_E_INVAL;
-  }
-  if (!gu || !grads || !shapes || !ax || !am || !av || !alpha_dev) {
-    set_error("%s: null pointer", what);
-    return ODIL_E_INVAL;
-  }
-  if (alpha_stride < 0) {
-    set_error("%s: step-size stride %lld is negative", what, (long long)alpha_stride);
-    return ODIL_E_INVAL;
-  }
-  int64_t bshapes[ODIL_MAX_LEVELS * 3];
-  if (int e = batch_levels_check(what, shapes, nlvl, ndim, nbatch, bshapes)) return e;
-  const char* locb = ndim == 1 ? ".c" : ".cc";
-  for (int l = 1; l < nlvl; ++l)
-    if (!grads[l] || !ax[l] || !am[l] || !av[l]) {
-      set_error("%s: null level array (level %d)", what, l);
-      return ODIL_E_INVAL;
-    }
-  // the member axis of the canonical 4-D view: 1 for '.cc' (a plane per member), 2 for '.c' (a row per member)
-  return mg_synth_adj<T>(gu, grads, nullptr, nullptr, bshapes, nlvl, ndim + 1, locb, stream, ax, am, av, T(0), omb1, omb2,
-                         eps, alpha_dev, alpha_stride, ndim == 2 ? 1 : 2);
-}
-
-// Does every transfer level of nbatch 3-D members ([nbatch, *shape] arrays, layout '.ccc', aligned to 16 bytes) run
-// the transposed prolongation that the same level of ONE member ('ccc') runs -- rows, tile, march or fast kernel, each
-// with a summation order of its own?  Their chunks and grids depend on the leading extent, a coarse value is formed by
-// one thread from its own window either way.  The generic kernel (its update is a launch of its own that reads one step
-// size) is refused.  Fills bshapes with the nlvl x 4 batched extents.  Nothing is launched.
-template <typename T>
-static int volumes_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, int nbatch,
-                                int64_t* bshapes) {
-  if (ndim != 3 || !shapes) {
-    set_error("%s: ndim %d (this ensemble runs 3-D members) or null shapes", what, ndim);
-    return ODIL_E_INVAL;
-  }
-  if (nbatch < 1 || nbatch > 65535) {
-    set_error("%s: %d members (1 ... 65535)", what, nbatch);
-    return ODIL_E_INVAL;
-  }
-  if (nlvl < 2 || nlvl > ODIL_MAX_LEVELS) {
-    set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
-    return ODIL_E_INVAL;
-  }
-  for (int l = 0; l < nlvl; ++l) {
-    bshapes[l * 4] = nbatch;
-    for (int d = 0; d < 3; ++d) bshapes[l * 4 + 1 + d] = shapes[l * 3 + d];
-  }
-  if (int e = check_levels(shapes, nlvl, 3, "ccc")) return e;
-  for (int l = 1; l < nlvl; ++l) {
-    InterpArgs one, all;
-    if (int e = fill_interp_args(one, shapes + l * 3, 3, "ccc")) return e;
-    if (int e = fill_interp_args(all, bshapes + l * 4, 4, ".ccc")) return e;
-    const int k1 = interp_adj_kind<T>(one), kb = interp_adj_kind<T>(all);
-    if (k1 != kb || k1 == kAdjGeneric || k1 == kAdjNode) {
-      set_error("%s: level %d of %d members would not run the transfer kernel one member runs", what, l, nbatch);
-      return ODIL_E_INVAL;
-    }
-  }
-  return 0;
-}
-
-// mg_synth_adj with the updates on [B, *shape] level arrays of B 3-D members (layout '.ccc'): the launches of a
-// single volume's chain, each covering all members, member b with its own step size.
-template <typename T>
-static int mg_synth_adj_adam_volumes(const T* gu, T* const* grads, const int64_t* shapes, int nlvl, int ndim, int nbatch,
-                                     T* const* ax, T* const* am, T* const* av, T omb1, T omb2, T eps,
-                                     const T* alpha_dev, int64_t alpha_stride, void* stream) {
-  static const char* what = "mg_synth_adj_adam_volumes";
-  if (ndim != 3) {
-    set_error("%s: ndim %d (this ensemble runs 3-D members)", what, ndim);
-    return ODIL_E_INVAL;
-  }
-  if (!gu || !grads || !shapes || !ax || !am || !av || !alpha_dev) {
-    set_error("%s: null pointer", what);
-    return ODIL_E_INVAL;
-  }
-  if (alpha_stride < 0) {
-    set_error("%s: step-size stride %lld is negative", what, (long long)alpha_stride);
-    return ODIL_E_INVAL;
-  }
-  int64_t bshapes[ODIL_MAX_LEVELS * 4];
-  if (int e = volumes_levels_check<T>(what, shapes, nlvl, ndim, nbatch, bshapes)) return e;
-  for (int l = 1; l < nlvl; ++l)
-    if (!grads[l] || !ax[l] || !am[l] || !av[l]) {
-      set_error("%s: null level array (level %d)", what, l);
-      return ODIL_E_INVAL;
-    }
-  // (the answer above is that of arrays aligned to 16 bytes; a level of a member is a multiple of 8 elements)
-  for (int l = 0; l < nlvl; ++l) {
-    const T* g = l == 0 ? gu : grads[l];
-    if (reinterpret_cast<uintptr_t>(g) % 16 != 0) {
-      set_error("%s: gradient array of level %d is not aligned to 16 bytes", what, l);
-      return ODIL_E_INVAL;
-    }
-  }
-  // grads[0] is gu itself or not wanted: the chain reads gu
-  T* g0[ODIL_MAX_LEVELS];
-  for (int l = 0; l < nlvl; ++l) g0[l] = l == 0 ? nullptr : grads[l];
-  return mg_synth_adj<T>(gu, g0, nullptr, nullptr, bshapes, nlvl, 4, ".ccc", stream, ax, am, av, T(0), omb1, omb2, eps,
-                         alpha_dev, alpha_stride, 0);
 }
 
 // Would every transfer level of `nrows` rows ([nrows, *shape] arrays, layout '.' + loc, aligned to 16 bytes) compute what
 // the same level of ONE row (layout loc) computes -- the prolongation of odil_mg_synth and the transposed chain of
 // odil_mg_synth_adj_adam_members?  The prolongation kernels (generic, fast, marching) all sum in the reference's order:
 // whichever of them takes '.' + loc gives a row the bits of its own launch, once the shapes refine and fit.  The
-// transposes have summation orders of their own: a level whose single transpose is the generic kernel runs
-// k_interp_adj_members, one whose single transpose is the node-centred marching kernel ('ncc' with four coarse planes or
-// more) runs that kernel row by row, and any other level must run the same kind on the stacked array as on one row.
-// Fills bshapes with the nlvl x (ndim + 1) batched extents, locb with '.' + loc and kinds[l] with the single transpose
-// of level l.  Nothing is launched.
+// transposes have summation orders of their own, so a level runs the kind its single transpose is (kinds[l]):
+//   generic   k_interp_adj_members, the row on blockIdx.y.  A node-centred y or x axis; an all-cell level only beyond the
+//             limits of the fast and the marching kernels (an extent of 2^30 or more, a schedule beyond 31 bits).
+//   node      the node-centred marching kernel row by row ('ncc' with four coarse planes or more; 4-D: 'nccc').
+//   others    rows of up to three axes: the single launch on the '.' + loc array, which must be of the same kind there
+//             (fast, rows, tile, march: all-cell members always come here or to the first line); rows of four axes, which
+//             have no such view: the row variant of the fast kernel, nothing else.
+// Rows of four axes that run the fast or the 'nccc' kernel must be multiples of 16 bytes, fine and coarse: the kernels
+// read the fine array in packs of two elements, and a single run, whose levels and fields lie back to back, keeps every
+// later array where row 0 lies on the 16-byte grid only then (coarse rows can be odd: 'cccc' cells 6^4 have coarse rows
+// of 81 elements, and such members are refused in both element sizes).
+// Fills kinds and, for rows of up to three axes, bshapes and locb (stacked_levels).  Nothing is launched.
 template <typename T>
 static int members_levels_check(const char* what, const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows,
                                 int64_t* bshapes, char* locb, int* kinds) {
@@ -982,11 +766,14 @@ static int members_levels_check(const char* what, const int64_t* shapes, int nlv
     set_error("%s: ndim %d (the rows are 1-D to 4-D), null shapes or a loc of another length", what, ndim);
     return ODIL_E_INVAL;
   }
-  for (int d = 0; d < ndim; ++d)
+  bool cells = true;
+  for (int d = 0; d < ndim; ++d) {
     if (loc[d] != 'c' && loc[d] != 'n') {
       set_error("%s: loc '%s' (every axis of a row is 'c' or 'n')", what, loc);
       return ODIL_E_INVAL;
     }
+    cells = cells && loc[d] == 'c';
+  }
   if (nrows < 1 || nrows > 65535) {
     set_error("%s: %d rows (1 ... 65535)", what, nrows);
     return ODIL_E_INVAL;
@@ -995,26 +782,23 @@ static int members_levels_check(const char* what, const int64_t* shapes, int nlv
     set_error("%s: nlvl=%d out of range [2,%d]", what, nlvl, ODIL_MAX_LEVELS);
     return ODIL_E_INVAL;
   }
-  if (ndim == 4) {
-    // rows of four axes: the canonical view has no axis left for the row, so every kind runs a row variant of its own
-    // (bshapes and locb stay unused).  A single 4-D array runs the generic kernel, the fast kernel or the 'nccc' marching
-    // kernel and nothing else.  Rows of the latter two kinds must be multiples of 16 bytes, fine and coarse: the kernels
-    // read the fine array in packs of two elements, and a single run, whose levels and fields lie back to back, keeps
-    // every later array where row 0 lies on the 16-byte grid only then (coarse rows can be odd: 'cccc' cells 6^4 have
-    // coarse rows of 81 elements, and such members are refused in both element sizes).
-    locb[0] = 0;
-    if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
-    const int64_t pack = 16 / (int64_t)sizeof(T);
-    for (int l = 1; l < nlvl; ++l) {
-      InterpArgs one;
-      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
-      const int64_t fcells = prod4(one.fn), ccells = prod4(one.cn);
-      if (fcells >= ((int64_t)1 << 31)) {
-        set_error("%s: level %d of a row has 2^31 elements or more", what, l);
-        return ODIL_E_INVAL;
-      }
-      const int k1 = interp_adj_kind<T>(one);
-      kinds[l] = k1;
+  locb[0] = 0;
+  if (ndim <= 3) stacked_levels(shapes, nlvl, ndim, loc, nrows, bshapes, locb);
+  if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
+  const int64_t pack = 16 / (int64_t)sizeof(T);
+  for (int l = 1; l < nlvl; ++l) {
+    InterpArgs one;
+    if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+    const int64_t fcells = prod4(one.fn), ccells = prod4(one.cn);
+    const int k1 = interp_adj_kind<T>(one);
+    kinds[l] = k1;
+    // the row kernels number the elements of a row with an int.  All-cell rows of up to three axes meet one only where
+    // the level is generic; rows with a node-centred axis and rows of four axes keep the limit on every level.
+    if (fcells >= ((int64_t)1 << 31) && (ndim == 4 || !cells || k1 == kAdjGeneric)) {
+      set_error("%s: level %d of a row has 2^31 elements or more", what, l);
+      return ODIL_E_INVAL;
+    }
+    if (ndim == 4) {
       if (k1 != kAdjGeneric && k1 != kAdjFast && !(k1 == kAdjNode && one.loc[0] == kNode)) {
         set_error("%s: level %d of %d rows: the transposed prolongation of a single row has no row variant", what, l, nrows);
         return ODIL_E_INVAL;
@@ -1024,29 +808,12 @@ static int members_levels_check(const char* what, const int64_t* shapes, int nlv
                   nrows, (long long)fcells, (long long)ccells);
         return ODIL_E_INVAL;
       }
+      continue;
     }
-    return 0;
-  }
-  locb[0] = '.';
-  for (int d = 0; d < ndim; ++d) locb[1 + d] = loc[d];
-  locb[1 + ndim] = 0;
-  for (int l = 0; l < nlvl; ++l) {
-    bshapes[l * (ndim + 1)] = nrows;
-    for (int d = 0; d < ndim; ++d) bshapes[l * (ndim + 1) + 1 + d] = shapes[l * ndim + d];
-  }
-  if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
-  for (int l = 1; l < nlvl; ++l) {
-    InterpArgs one, all;
-    if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+    InterpArgs all;
     if (int e = fill_interp_args(all, bshapes + l * (ndim + 1), ndim + 1, locb)) return e;
-    if (prod4(one.fn) >= ((int64_t)1 << 31)) {
-      set_error("%s: level %d of a row has 2^31 elements or more", what, l);
-      return ODIL_E_INVAL;
-    }
-    const int k1 = interp_adj_kind<T>(one), kb = interp_adj_kind<T>(all);
-    kinds[l] = k1;
     const bool node_rows = k1 == kAdjNode && one.fn[0] == 1 && one.loc[1] == kNode;
-    if (k1 != kAdjGeneric && !node_rows && k1 != kb) {
+    if (k1 != kAdjGeneric && !node_rows && k1 != interp_adj_kind<T>(all)) {
       set_error("%s: level %d of %d rows would not run the transposed prolongation one row runs", what, l, nrows);
       return ODIL_E_INVAL;
     }
@@ -1054,9 +821,10 @@ static int members_levels_check(const char* what, const int64_t* shapes, int nlv
   return 0;
 }
 
-// mg_synth_adj on [R, *shape] level arrays of R rows (layout '.' + loc, any loc of 'c' / 'n', 1-D to 3-D rows): one
-// launch per level for all rows, the update of the levels >= 1 in the launch that forms their gradient, row r with the
-// step size alpha_dev[(r % period) * alpha_stride] (period 0: r itself).  x = m = v = null: the gradients alone.
+// mg_synth_adj on [R, *shape] level arrays of R rows (layout '.' + loc, any loc of 'c' / 'n', 1-D to 4-D rows) -- the only
+// transposed chain of the ensembles: one launch per level for all rows, the update of the levels >= 1 in the launch that
+// forms their gradient, row r with the step size alpha_dev[(r % period) * alpha_stride] (period 0: r itself).
+// x = m = v = null: the gradients alone.
 template <typename T>
 static int mg_synth_adj_adam_members(const T* gu, T* const* grads, const int64_t* shapes, int nlvl, int ndim,
                                      const char* loc, int nrows, T* const* ax, T* const* am, T* const* av, T omb1, T omb2,
@@ -1097,49 +865,34 @@ static int mg_synth_adj_adam_members(const T* gu, T* const* grads, const int64_t
       ad.alpha_stride = alpha_stride, ad.alpha_period = period;  // (stride 0: one step size for all rows)
       ad.member_axis = ndim == 4 ? 0 : 3 - ndim;  // canonical axis of the rows: 2 ('.c'), 1 ('.cc'), 0 ('.ccc'); 4-D: unused
     }
-    if (ndim == 4) {
-      InterpArgs one;
-      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
-      int r = 0;
-      if (kinds[l] == kAdjGeneric) {
-        MemberArgs4 m;
-        for (int i = 0; i < 4; ++i) m.cn[i] = (int)one.cn[i], m.fn[i] = (int)one.fn[i], m.loc[i] = one.loc[i];
-        m.ccells = prod4(one.cn), m.fcells = prod4(one.fn);
-        const dim3 grid((unsigned)((m.ccells + kBlock - 1) / kBlock), (unsigned)nrows);
-        hipLaunchKernelGGL(k_interp_adj_members4<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, gfine, grads[l], m, ad);
-        if (int e = check_launch("k_interp_adj_members4")) return e;
-        r = 1;
-      } else if (kinds[l] == kAdjNode) {
-        r = interp_adj_march_lead_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
-      } else {
-        r = interp_adj_fast_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
-      }
-      if (r < 0) return r;
-      if (r == 0) {
-        set_error("%s: level %d: the row variant of the single transpose does not take these arrays", what, l);
-        return ODIL_E_INVAL;
-      }
-    } else if (kinds[l] == kAdjGeneric) {
-      InterpArgs one;
-      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+    InterpArgs one;
+    if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
+    int r;
+    if (kinds[l] == kAdjGeneric) {
       MemberArgs m;
-      for (int i = 0; i < 3; ++i) m.cn[i] = (int)one.cn[i + 1], m.fn[i] = (int)one.fn[i + 1], m.loc[i] = one.loc[i + 1];
+      for (int i = 0; i < 4; ++i) m.cn[i] = (int)one.cn[i], m.fn[i] = (int)one.fn[i], m.loc[i] = one.loc[i];
       m.ccells = prod4(one.cn), m.fcells = prod4(one.fn);
       const dim3 grid((unsigned)((m.ccells + kBlock - 1) / kBlock), (unsigned)nrows);
-      hipLaunchKernelGGL(k_interp_adj_members<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, gfine, grads[l], m, ad);
-      if (int e = check_launch("k_interp_adj_members")) return e;
+      if (ndim == 4)
+        hipLaunchKernelGGL((k_interp_adj_members<T, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, gfine, grads[l], m, ad);
+      else
+        hipLaunchKernelGGL((k_interp_adj_members<T, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, gfine, grads[l], m, ad);
+      const int e = check_launch("k_interp_adj_members");
+      r = e ? e : 1;
     } else if (kinds[l] == kAdjNode) {
-      InterpArgs one;
-      if (int e = fill_interp_args(one, shapes + l * ndim, ndim, loc)) return e;
-      const int r = interp_adj_march_n_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
-      if (r < 0) return r;
-      if (r == 0) {
-        set_error("%s: level %d: the node-centred marching kernel does not take these arrays", what, l);
-        return ODIL_E_INVAL;
-      }
+      r = ndim == 4 ? interp_adj_march_lead_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad)
+                    : interp_adj_march_n_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
+    } else if (ndim == 4) {
+      r = interp_adj_fast_rows<T>(gfine, grads[l], one, nrows, (hipStream_t)stream, ad);
     } else {
-      if (int e = interp_adj<T>(gfine, grads[l], nullptr, bshapes + l * (ndim + 1), ndim + 1, locb, T(1), stream, 0, 0, ad))
-        return e;
+      // the single launch on the '.' + loc array: its kernel reads the step size of the row through member_axis
+      const int e = interp_adj<T>(gfine, grads[l], nullptr, bshapes + l * (ndim + 1), ndim + 1, locb, T(1), stream, 0, 0, ad);
+      r = e ? e : 1;
+    }
+    if (r < 0) return r;
+    if (r == 0) {
+      set_error("%s: level %d: the row variant of the single transpose does not take these arrays", what, l);
+      return ODIL_E_INVAL;
     }
     gfine = grads[l];
   }
@@ -1182,13 +935,7 @@ static int mg_synth_members(const T* const* terms, T* const* work, T* u, const i
   if (ndim <= 3) {
     int64_t bshapes[ODIL_MAX_LEVELS * 4];
     char locb[8];
-    locb[0] = '.';
-    for (int d = 0; d < ndim; ++d) locb[1 + d] = loc[d];
-    locb[1 + ndim] = 0;
-    for (int l = 0; l < nlvl; ++l) {
-      bshapes[l * (ndim + 1)] = nrows;
-      for (int d = 0; d < ndim; ++d) bshapes[l * (ndim + 1) + 1 + d] = shapes[l * ndim + d];
-    }
+    stacked_levels(shapes, nlvl, ndim, loc, nrows, bshapes, locb);
     return mg_synth<T>(terms, nullptr, work, u, bshapes, nlvl, ndim + 1, locb, stream);
   }
   if (int e = check_levels(shapes, nlvl, ndim, loc)) return e;
@@ -1332,10 +1079,6 @@ int odil_mg_synth_adj_adam_f32(const float* gu, float* const* grads, const float
   return mg_synth_adj<float>(gu, grads, factors, work, shapes, nlvl, ndim, loc, stream, x, m, v, alpha, one_minus_b1,
                              one_minus_b2, eps, alpha_dev);
 }
-int odil_mg_batch_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch) {
-  int64_t bshapes[ODIL_MAX_LEVELS * 3];
-  return batch_levels_check("mg_batch_levels", shapes, nlvl, ndim, nbatch, bshapes);
-}
 int odil_interp_adj_kind(const int64_t* cshape, int ndim, const char* loc, int elem_size) {
   InterpArgs a;
   if (!cshape || (elem_size != 8 && elem_size != 4)) {
@@ -1346,44 +1089,6 @@ int odil_interp_adj_kind(const int64_t* cshape, int ndim, const char* loc, int e
   if (a.loc[0] == kNode && a.loc[1] == kNone && a.loc[2] == kNone && a.loc[3] == kNone) return kAdjNode;
   return elem_size == 8 ? interp_adj_kind<double>(a) : interp_adj_kind<float>(a);
 }
-int odil_mg_volumes_levels_ok(const int64_t* shapes, int nlvl, int ndim, int nbatch, int elem_size) {
-  int64_t bshapes[ODIL_MAX_LEVELS * 4];
-  if (elem_size != 8 && elem_size != 4) {
-    set_error("mg_volumes_levels: element size %d (8 or 4)", elem_size);
-    return ODIL_E_INVAL;
-  }
-  return elem_size == 8 ? volumes_levels_check<double>("mg_volumes_levels", shapes, nlvl, ndim, nbatch, bshapes)
-                        : volumes_levels_check<float>("mg_volumes_levels", shapes, nlvl, ndim, nbatch, bshapes);
-}
-int odil_mg_synth_adj_adam_volumes_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                       int nbatch, double* const* x, double* const* m, double* const* v,
-                                       double one_minus_b1, double one_minus_b2, double eps, const double* alpha_dev,
-                                       int64_t alpha_stride, void* stream) {
-  return mg_synth_adj_adam_volumes<double>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2,
-                                           eps, alpha_dev, alpha_stride, stream);
-}
-int odil_mg_synth_adj_adam_volumes_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                       int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
-                                       float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
-                                       void* stream) {
-  return mg_synth_adj_adam_volumes<float>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2,
-                                          eps, alpha_dev, alpha_stride, stream);
-}
-int odil_mg_synth_adj_adam_batch_f64(const double* gu, double* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                     int nbatch, double* const* x, double* const* m, double* const* v, double one_minus_b1,
-                                     double one_minus_b2, double eps, const double* alpha_dev, int64_t alpha_stride,
-                                     void* stream) {
-  return mg_synth_adj_adam_batch<double>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2, eps,
-                                         alpha_dev, alpha_stride, stream);
-}
-int odil_mg_synth_adj_adam_batch_f32(const float* gu, float* const* grads, const int64_t* shapes, int nlvl, int ndim,
-                                     int nbatch, float* const* x, float* const* m, float* const* v, float one_minus_b1,
-                                     float one_minus_b2, float eps, const float* alpha_dev, int64_t alpha_stride,
-                                     void* stream) {
-  return mg_synth_adj_adam_batch<float>(gu, grads, shapes, nlvl, ndim, nbatch, x, m, v, one_minus_b1, one_minus_b2, eps,
-                                        alpha_dev, alpha_stride, stream);
-}
-
 int odil_mg_members_levels_ok(const int64_t* shapes, int nlvl, int ndim, const char* loc, int nrows, int elem_size) {
   int64_t bshapes[ODIL_MAX_LEVELS * 4];
   char locb[8];

@@ -327,10 +327,10 @@ class BatchedLaunches(_Members):
         raise NotImplementedError
 
     def _transposes(self):
-        """The gradients of the levels >= 1 from g[0]: `ops.mg_synth_adj` on the [B, *shape] level arrays, the members as a
-        leading axis that is not coarsened -- the levels the ensemble's constructor has asked the library about."""
+        """The gradients of the levels >= 1 from g[0]: the chain of `epoch` without x, m and v, on the levels the
+        ensemble's constructor has asked the library about."""
         if self.nlvl > 1:
-            ops.mg_synth_adj(self.g[0], [(self.nbatch,) + s for s in self.shapes], self.loc, grads=self.g)
+            ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g)
 
     def epochs(self, alphas, losses, norms, omb1, omb2, eps):
         """losses.shape[1] epochs (the interface of PoissonEnsemble.epochs).  alphas: [B, E], or [E] shared by all members."""
@@ -346,12 +346,12 @@ class PoissonLaunchEnsemble(BatchedLaunches):
     launches of `PoissonEvaluator.loss_grad_arrays(adam=...)` for a 2-D problem -- synthesis, residual + loss, adjoint +
     update of level 0, transposed prolongations + updates of the other levels -- each covering all B members
     (odil_mg_synth on [B, *shape] arrays, odil_poisson_residual_batch, odil_poisson_adjoint_adam_batch,
-    odil_mg_synth_adj_adam_batch).  Level-major storage: x, m, v, g are lists of one [B, *shape] tensor per level.  Member
+    odil_mg_synth_adj_adam_members).  Level-major storage: x, m, v, g are lists of one [B, *shape] tensor per level.  Member
     b computes what its single run computes, bit for bit: the same per-thread arithmetic, the same summation order.
     pad: extra elements between the members of the arrays that only the stencil kernels touch (fu, rhs, m[0], v[0])."""
 
     def __init__(self, evaluators, pad=0):
-        super().__init__(evaluators, pad, lambda shapes, nbatch, dtype: _levels_refusal(shapes, nbatch))
+        super().__init__(evaluators, pad, _levels_refusal)
         self.u = self.members(self.cshape)
         self.work = ([None] + [self.members(s) for s in self.shapes[1:-1]] + [None])[: self.nlvl]
         npart = ops.poisson_batch_partials(self.cshape, self.dtype)
@@ -366,7 +366,8 @@ class PoissonLaunchEnsemble(BatchedLaunches):
         ops.poisson_residual_batch(self.u, self.rhs, self.h2, self.fu, self.loss, self.partials)
         ops.poisson_adjoint_adam_batch(self.fu, self.h2, self.scale, self.g[0], self.x[0], self.m[0], self.v[0], alphas, omb1,
                                        omb2, eps)
-        ops.mg_synth_adj_adam_batch(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+        ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g, self.x, self.m, self.v, alphas, omb1, omb2,
+                                      eps)
 
     def loss_grad(self):
         ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
@@ -380,13 +381,13 @@ class PoissonVolumeEnsemble(BatchedLaunches):
     `PoissonEvaluator.loss_grad_arrays(adam=...)` for a 3-D problem through its separate kernels -- synthesis of the
     coarse levels, residual with the last prolongation fused in + loss, adjoint + update of level 0, transposed
     prolongations + updates of the other levels -- each covering all B members (odil_mg_synth on [B, *shape] arrays,
-    odil_poisson_residual_synth_batch, odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_volumes).  Level-major
+    odil_poisson_residual_synth_batch, odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_members).  Level-major
     storage as in PoissonLaunchEnsemble.  Member b computes what its single run computes, bit for bit -- also where the
     single run takes the one-pass adjoint + first transpose launch, which equals the separate kernels bit for bit.
     pad: extra elements between the members of the arrays that only the stencil kernels touch (fu, rhs, m[0], v[0])."""
 
     def __init__(self, evaluators, pad=0):
-        super().__init__(evaluators, pad, _volume_levels_refusal)
+        super().__init__(evaluators, pad, _levels_refusal)
         # synthesis scratch of the levels 1 ... nlvl - 2 (level 1: the coarse operand of the residual)
         self.work = [None] + [self.members(s) for s in self.shapes[1:-1]] + [None]
         nsums, npart = ops.residual_synth_batch_workspace(self.shapes[1])
@@ -405,7 +406,8 @@ class PoissonVolumeEnsemble(BatchedLaunches):
         ops.poisson_residual_synth_batch(coarse, self.x[0], self.rhs, self.h2, self.fu, self.loss, self.partials, self.sums)
         ops.poisson_adjoint_adam_volumes(self.fu, self.h2, self.scale, self.g[0], self.x[0], self.m[0], self.v[0], alphas,
                                          omb1, omb2, eps)
-        ops.mg_synth_adj_adam_volumes(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
+        ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g, self.x, self.m, self.v, alphas, omb1, omb2,
+                                      eps)
 
     def loss_grad(self):
         if self.nlvl > 2:
@@ -432,8 +434,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
       2. the generated forward kernels of all members (`stencil_bind.EpochBatch`: k_fwd_batch, k_final_batch, k_loss_batch),
          ONE launch of each per group of members whose operators generated the same source;
       3. the generated gathers of all members into g[0];
-      4. the transposed prolongations with the updates of the levels >= 1 (`ops.mg_synth_adj_adam_batch` for 1-D / 2-D
-         members, `ops.mg_synth_adj_adam_volumes` for 3-D members);
+      4. the transposed prolongations with the updates of the levels >= 1 (`ops.mg_synth_adj_adam_members`);
       5. `ops.adam_step_batch` for level 0, after the chain has read g[0] (and after the gathers have re-read their
          sources: for a plain `Field` the source IS x[0]).
     Member b computes what its single run computes, bit for bit.  out [B, 1 + 2 nout_b] per group holds loss, terms and
@@ -515,7 +516,7 @@ class TracedLaunchEnsemble(BatchedLaunches):
         reason = traced_refusal(shapes, dtype, form, nb, loc=loc, nfields=nfields)
         if reason is not None:
             raise ValueError("ensemble of {} members: {}".format(nb, reason))
-        # one cell-centred unknown: the launches these ensembles always made; else the chain for stacked rows of any loc
+        # one cell-centred unknown: the rules of the Poisson forms admitted it; else those of the stacked rows of any loc
         self.stacked = rows_stacked(nfields, loc)
         self.form = form
         self.traced = []
@@ -627,12 +628,6 @@ class TracedLaunchEnsemble(BatchedLaunches):
         elif self.nlvl > 1:
             ops.mg_synth(self.x, self.loc, work=self.work, out=self.u)
 
-    def _transposes(self):
-        if not self.stacked:
-            return super()._transposes()
-        if self.nlvl > 1:
-            ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g)
-
     def _param_step(self, alphas=None, omb1=0.0, omb2=0.0, eps=0.0):
         """ONE launch for the `Array` and `NeuralNet` unknowns of all members, behind the gathers (which re-read them): the
         packed parameter gradient from the rows k_loss_batch wrote -- plus what k_par_batch left in `gextra` -- and, with
@@ -688,12 +683,9 @@ class TracedLaunchEnsemble(BatchedLaunches):
         if not self.par_batches:
             self._collect_loss()
         rows = self._row_steps(alphas)
-        if self.nlvl > 1 and self.stacked:  # (all fields of all members: ONE chain)
+        if self.nlvl > 1:  # (all fields of all members: ONE chain)
             ops.mg_synth_adj_adam_members(self.g[0], self.shapes, self.loc[1:], self.g, self.x, self.m, self.v, rows, omb1, omb2,
                                           eps)
-        elif self.nlvl > 1:
-            chain = ops.mg_synth_adj_adam_volumes if self.ndim == 3 else ops.mg_synth_adj_adam_batch
-            chain(self.g[0], self.shapes, self.g, self.x, self.m, self.v, alphas, omb1, omb2, eps)
         ops.adam_step_batch(self.x[0], self.m[0], self.v[0], self.g[0], rows, omb1, omb2, eps)
         # (the parameters: one step size per MEMBER -- the leading B of the stacked rows')
         self._evaluate(rows[:self.nbatch] if rows.numel() > self.nbatch else rows, omb1, omb2, eps)
@@ -710,8 +702,8 @@ class TracedLaunchEnsemble(BatchedLaunches):
 
 def rows_stacked(nfields, loc):
     """Does `TracedLaunchEnsemble` run members with `nfields` grid unknowns at `loc` through the chain for stacked rows?
-    Anything but ONE cell-centred unknown does, and every 4-D member: its rows have no '.' + loc view, and the chain of
-    the volumes (`ops.mg_synth_adj_adam_volumes`) is 3-D only."""
+    Anything but ONE cell-centred unknown does, and every 4-D member: its rows have no '.' + loc view.  The transposed
+    chain is the same either way; what this decides is whose rules admit the members (`traced_refusal`)."""
     return nfields > 1 or loc != "c" * len(loc) or len(loc) == 4
 
 
@@ -723,7 +715,7 @@ def traced_refusal(shapes, dtype, form, nbatch=1, loc=None, nfields=1):
     nfields * nbatch rows would run what that level of one member runs (odil_mg_members_levels_ok).  A 4-D member always
     takes the stacked rows, even ONE 'cccc' unknown."""
     ndim = len(shapes[0])
-    if ndim == 4:  # (always the stacked rows, even ONE 'cccc' unknown: `mg_synth_adj_adam_volumes` is 3-D only)
+    if ndim == 4:  # (always the stacked rows, even ONE 'cccc' unknown)
         loc = "c" * ndim if loc is None else loc
     if loc is not None and rows_stacked(nfields, loc):
         return _members_refusal(shapes, dtype, form, nbatch * nfields, loc)
@@ -737,7 +729,7 @@ def traced_refusal(shapes, dtype, form, nbatch=1, loc=None, nfields=1):
         return None
     reason = (volumes_refusal if ndim == 3 else launches_refusal)(shapes, dtype)
     if reason is None and nbatch > 1:
-        reason = _volume_levels_refusal(shapes, nbatch, dtype) if ndim == 3 else _levels_refusal(shapes, nbatch)
+        reason = _levels_refusal(shapes, nbatch, dtype)
     return reason
 
 
@@ -753,36 +745,24 @@ def _members_refusal(shapes, dtype, form, nrows, loc):
     reason = _unaligned_members(shapes, dtype)
     if reason is not None or len(shapes) == 1:
         return reason
+    return _levels_refusal(shapes, nrows, dtype, loc)
+
+
+def _levels_refusal(shapes, nrows, dtype=None, loc=None):
+    """The library's answer (odil_mg_members_levels_ok), the question every form ends with: why a transfer level of `nrows`
+    rows of these level shapes at `loc` (default: all axes cell-centred) would not compute what that level of one row
+    computes (level count, extents, refinement, schedule limits, the kernel a level runs), or None."""
     from ._lib import i64, load
 
     lib = load()
     flat = [int(n) for shape in shapes for n in shape]
-    if lib.odil_mg_members_levels_ok(i64(flat), len(shapes), ndim, loc.encode(), int(nrows), 4 if dtype == torch.float32 else 8) == 0:
+    ndim = len(shapes[0])
+    # (a caller without a dtype, `launches_refusal(shapes)`, is answered for 8 bytes: the kind of a 1-D or 2-D level does
+    # not depend on the element size, only the 3-D marching kernels choose by it)
+    item = 4 if dtype == torch.float32 else 8
+    if lib.odil_mg_members_levels_ok(i64(flat), len(shapes), ndim, (loc or "c" * ndim).encode(), int(nrows), item) == 0:
         return None
     return lib.odil_last_error().decode()
-
-
-def _library_refusal(entry, shapes, *more):
-    """None when the library's `entry(shapes, levels, ndim, *more)` returns 0, else its error text."""
-    from ._lib import i64, load
-
-    lib = load()
-    flat = [int(n) for shape in shapes for n in shape]
-    if getattr(lib, entry)(i64(flat), len(shapes), len(shapes[0]), *more) == 0:
-        return None
-    return lib.odil_last_error().decode()
-
-
-def _volume_levels_refusal(shapes, nbatch, dtype):
-    """The library's answer (odil_mg_volumes_levels_ok): why a transfer level of `nbatch` 3-D members of these level
-    shapes would not run the kernel that level of one member runs, or None."""
-    return _library_refusal("odil_mg_volumes_levels_ok", shapes, int(nbatch), 4 if dtype == torch.float32 else 8)
-
-
-def _levels_refusal(shapes, nbatch):
-    """The library's answer (odil_mg_batch_levels_ok): why the transfer levels of `nbatch` members of these level shapes
-    would not run the kernels one member's run (level count, extents, refinement, schedule limits), or None."""
-    return _library_refusal("odil_mg_batch_levels_ok", shapes, int(nbatch))
 
 
 # The shape-only refusals that the forms share: each the reason, or None where it does not apply.  Every predicate below
@@ -829,7 +809,7 @@ def volumes_refusal(shapes, dtype=None):
         if load().odil_interp_adj_kind(i64(shapes[1]), 3, b"ccc", 4) == 3:
             return ("levels {}: a float32 run of this shape takes the one-pass adjoint + transpose launch, and the "
                     "separate row-marching transpose of the ensemble rounds differently").format([tuple(s) for s in shapes])
-    return _volume_levels_refusal(shapes, 1, dtype)
+    return _levels_refusal(shapes, 1, dtype)
 
 
 def launches_refusal(shapes, dtype=None):
@@ -839,7 +819,7 @@ def launches_refusal(shapes, dtype=None):
         return ("{}-D grid: the batched launches run 1-D and 2-D grids (a 3-D run fuses the synthesis into its residual "
                 "and the first transpose into its adjoint)".format(len(shapes[0])))
     return (_too_few_levels(shapes) or _not_halving(shapes) or _coarsest_too_small(shapes)
-            or _unaligned_members(shapes, dtype) or _levels_refusal(shapes, 1))
+            or _unaligned_members(shapes, dtype) or _levels_refusal(shapes, 1, dtype))
 
 
 def ensemble_form(form, shapes, dtype):

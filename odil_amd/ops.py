@@ -899,23 +899,6 @@ def poisson_adjoint_adam_batch(fu, h2, scale, out, x, m, v, alphas, one_minus_b1
     return out
 
 
-def mg_synth_adj_adam_batch(gu, shapes, grads, x, m, v, alphas, one_minus_b1, one_minus_b2, eps):
-    """`mg_synth_adj_adam` on contiguous [B, *shape] level arrays (all axes of a member cell-centred; `shapes`: the level
-    shapes of ONE member): one launch per level for all members.  alphas: as in `poisson_adjoint_adam_batch`."""
-    nb, nlvl = int(gu.shape[0]), len(shapes)
-    assert alphas.dtype == gu.dtype and alphas.numel() in (1, nb)
-    assert tuple(gu.shape) == (nb,) + tuple(shapes[0]) and gu.is_contiguous()
-    for arrs in (grads, x, m, v):  # (the launcher takes contiguous [B, *shape] level arrays: no strides travel)
-        assert all(tuple(t.shape) == (nb,) + tuple(s) and t.is_contiguous() and t.dtype == gu.dtype
-                   for t, s in zip(arrs[1:], shapes[1:]))
-    none0 = lambda arrs: ptr_array([None] + list(arrs[1:]))
-    flat = [int(n) for s in shapes for n in s]
-    call("mg_synth_adj_adam_batch", gu.dtype, ptr(gu), ptr_array(grads), i64(flat), c_int(nlvl), c_int(len(shapes[0])),
-         c_int(nb), none0(x), none0(m), none0(v), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
-         c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
-    return grads
-
-
 def residual_synth_batch_workspace(cshape):
     """(float64 column sums, float64 partial sums) ONE member of `poisson_residual_synth_batch` needs, in elements; (0, 0):
     not a coarse shape it takes."""
@@ -956,24 +939,6 @@ def poisson_adjoint_adam_volumes(fu, h2, scale, out, x, m, v, alphas, one_minus_
          c_int(len(shape)), h2p, float(scale), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
          c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
     return out
-
-
-def mg_synth_adj_adam_volumes(gu, shapes, grads, x, m, v, alphas, one_minus_b1, one_minus_b2, eps):
-    """`mg_synth_adj_adam` on contiguous [B, *shape] level arrays of B 3-D members (`shapes`: the level shapes of ONE
-    member): the launches of a single volume's chain, each for all members.  alphas: as in `poisson_adjoint_adam_volumes`.
-    grads[0] is not written (the chain reads gu)."""
-    nb, nlvl = int(gu.shape[0]), len(shapes)
-    assert alphas.dtype == gu.dtype and alphas.numel() in (1, nb) and alphas.is_contiguous()
-    assert tuple(gu.shape) == (nb,) + tuple(shapes[0]) and gu.is_contiguous()
-    for arrs in (grads, x, m, v):  # (the launcher takes contiguous [B, *shape] level arrays: no strides travel)
-        assert all(tuple(t.shape) == (nb,) + tuple(s) and t.is_contiguous() and t.dtype == gu.dtype
-                   for t, s in zip(arrs[1:], shapes[1:]))
-    none0 = lambda arrs: ptr_array([None] + list(arrs[1:]))
-    flat = [int(n) for s in shapes for n in s]
-    call("mg_synth_adj_adam_volumes", gu.dtype, ptr(gu), none0(grads), i64(flat), c_int(nlvl), c_int(len(shapes[0])),
-         c_int(nb), none0(x), none0(m), none0(v), float(one_minus_b1), float(one_minus_b2), float(eps), ptr(alphas),
-         c_int64(1 if alphas.numel() == nb and nb > 1 else 0), stream_ptr())
-    return grads
 
 
 def mg_synth_adj_adam_members(gu, shapes, loc, grads, x=None, m=None, v=None, alphas=None, one_minus_b1=0.0, one_minus_b2=0.0,

@@ -1,5 +1,5 @@
 """The ensemble of Poisson problems as batched launches -- odil_poisson_residual_batch, odil_poisson_adjoint_adam_batch,
-odil_mg_synth_adj_adam_batch, odil_mg_synth on [B, *shape] arrays (csrc/poisson.hip, csrc/mg_transfer.hip, csrc/mg_fast.hip),
+odil_mg_synth_adj_adam_members, odil_mg_synth on [B, *shape] arrays (csrc/poisson.hip, csrc/mg_transfer.hip, csrc/mg_fast.hip),
 fused.PoissonLaunchEnsemble, AdamNativeOptimizer.run_ensemble, util.optimize_ensemble(form="launches") -- against each
 member's own loop of `PoissonEvaluator.loss_grad_arrays(adam=...)`: the launches a single `optimize_grad` run makes.
 

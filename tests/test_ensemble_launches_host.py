@@ -1,5 +1,5 @@
 """The ensemble of Poisson problems as batched launches (odil_poisson_residual_batch, odil_poisson_adjoint_adam_batch,
-odil_mg_synth_adj_adam_batch, fused.PoissonLaunchEnsemble, util.optimize_ensemble(form=...)) as far as it can be checked
+odil_mg_synth_adj_adam_members, fused.PoissonLaunchEnsemble, util.optimize_ensemble(form=...)) as far as it can be checked
 without a device: the library exports the entry points and header, library and `_lib.EXPORTED` agree; the launchers refuse
 malformed arguments with an error text before anything is launched (every pointer is a dummy, so a launch that did happen
 could not succeed: tests/test_ensemble_host.py is the model); `optimize_ensemble` names the first member that cannot join,
@@ -15,7 +15,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["odil_poisson_residual_batch", "odil_poisson_adjoint_adam_batch", "odil_mg_synth_adj_adam_batch"]
+NEW = ["odil_poisson_residual_batch", "odil_poisson_adjoint_adam_batch", "odil_mg_synth_adj_adam_members"]
 
 
 def test_library_header_and_bindings_agree_on_the_new_entry_points():
@@ -128,43 +128,57 @@ def test_adjoint_launcher_refuses_before_launching(suffix):
 
 @pytest.mark.parametrize("suffix", ["f64", "f32"])
 def test_transfer_launcher_refuses_before_launching(suffix):
-    from odil_amd import _lib
+    """The one transposed chain (odil_mg_synth_adj_adam_members) as the 1-D / 2-D ensembles call it: loc 'c' / 'cc', the
+    members as its rows."""
+    from odil_amd import _lib, fused
 
     lib = _lib.load()
-    fn = getattr(lib, "odil_mg_synth_adj_adam_batch_" + suffix)
+    fn = getattr(lib, "odil_mg_synth_adj_adam_members_" + suffix)
     shapes = [(16, 8), (8, 4), (4, 2)]
 
-    def launch(nbatch=3, shp=shapes, ndim=2, astride=1, null=None, null_level=None):
+    def launch(nbatch=3, shp=shapes, ndim=2, loc=None, astride=1, period=0, null=None, null_level=None, gu=1 << 20,
+               odd_level=False):
         nlvl = len(shp)
         tables = []
         for k in range(4):  # grads x m v: HOST arrays of (dummy) device pointers
             arr = (c_void_p * nlvl)(*[4096 * (16 * k + l + 1) for l in range(nlvl)])
             if null_level == k:
                 arr[1] = None
+            if odd_level and k == 0:
+                arr[1] = 4096 * 2 + 8
             tables.append(arr)
-        ptrs = [c_void_p(1 << 20), tables[0], _lib.i64([n for s in shp for n in s]), tables[1], tables[2], tables[3],
+        ptrs = [c_void_p(gu), tables[0], _lib.i64([n for s in shp for n in s]), tables[1], tables[2], tables[3],
                 c_void_p(1 << 21)]  # gu grads shapes x m v alpha_dev
         if null is not None:
             ptrs[null] = None
-        return fn(ptrs[0], ptrs[1], ptrs[2], c_int(nlvl), c_int(ndim), c_int(nbatch), ptrs[3], ptrs[4], ptrs[5], 0.1, 0.001,
-                  1e-7, ptrs[6], c_int64(astride), None)
+        loc = ("c" * ndim).encode() if loc is None else loc
+        return fn(ptrs[0], ptrs[1], ptrs[2], c_int(nlvl), c_int(ndim), loc, c_int(nbatch), ptrs[3], ptrs[4], ptrs[5], 0.1,
+                  0.001, 1e-7, ptrs[6], c_int64(astride), c_int64(period), None)
 
-    refused = lambda text, **kw: _refused(lib, "mg_synth_adj_adam_batch", launch(**kw), text)
+    refused = lambda text, **kw: _refused(lib, "mg_synth_adj_adam_members", launch(**kw), text)
     for k in range(7):
         refused(b"null pointer", null=k)
     for k in range(4):
         refused(b"null level array", null_level=k)
     for nbatch in (0, -1, 65536):
-        refused(b"members", nbatch=nbatch)
+        refused(b"rows (1 ... 65535)", nbatch=nbatch)  # (the members are the chain's rows)
     refused(b"negative", astride=-1)
+    refused(b"negative", period=-1)
     refused(b"nlvl=1", shp=shapes[:1])
-    refused(b"ndim 3", ndim=3, shp=[(8, 8, 8), (4, 4, 4)])
+    # the chain itself takes 1-D to 4-D rows: that the 1-D / 2-D form runs no volumes is `launches_refusal`'s rule
+    assert "3-D grid: the batched launches run 1-D and 2-D grids" in fused.launches_refusal([(8, 8, 8), (4, 4, 4)])
+    refused(b"ndim 5", ndim=5, shp=[(8,) * 5, (4,) * 5])
+    refused(b"ndim 0", ndim=0)
+    refused(b"loc of another length", loc=b"c")
+    refused(b"every axis of a row is 'c' or 'n'", loc=b".c")
+    refused(b"not aligned to 16 bytes", gu=(1 << 20) + 8)
+    refused(b"not aligned to 16 bytes", odd_level=True)
     # levels that do not refine each other, and a coarsest level too small for the transfer's taps
     assert launch(shp=[(16, 8), (8, 3)]) == -1 and b"does not refine" in lib.odil_last_error()
     assert launch(shp=[(4, 2), (2, 1)]) == -1 and b"must be >= 2" in lib.odil_last_error()
     # a batch whose rows cannot be counted in 31 bits would leave the fast kernel a single member runs: refused, not rerouted
     # (1-D: the members are the rows of the '.c' layout, 65535 of them x 2^16 segments of 256 coarse cells)
-    refused(b"would not run the transfer kernel one member runs", nbatch=65535, ndim=1, shp=[(1 << 25,), (1 << 24,)])
+    refused(b"would not run the transposed prolongation one row runs", nbatch=65535, ndim=1, shp=[(1 << 25,), (1 << 24,)])
 
 
 # ------------------------------------------------------------------------------------------- optimize_ensemble
@@ -269,4 +283,4 @@ def test_the_form_is_a_function_of_shapes_and_dtype():
     # the limits of the kernels are the library's: more levels than the transfer chains take, a batch beyond the schedule
     assert "nlvl=33" in fused.launches_refusal([(1 << (34 - l),) for l in range(33)])
     assert fused._levels_refusal([(1 << 25,), (1 << 24,)], 1) is None
-    assert "would not run the transfer kernel one member runs" in fused._levels_refusal([(1 << 25,), (1 << 24,)], 65535)
+    assert "would not run the transposed prolongation one row runs" in fused._levels_refusal([(1 << 25,), (1 << 24,)], 65535)

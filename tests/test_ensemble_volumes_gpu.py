@@ -1,5 +1,5 @@
 """The ensemble of 3-D Poisson problems as batched launches -- odil_poisson_residual_synth_batch,
-odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_volumes, odil_mg_synth on [B, *shape] arrays
+odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_members, odil_mg_synth on [B, *shape] arrays
 (csrc/poisson_synth_tile.hip, csrc/poisson.hip, csrc/mg_transfer.hip, csrc/mg_march.hip, csrc/mg_fast.hip),
 fused.PoissonVolumeEnsemble, AdamNativeOptimizer.run_ensemble, util.optimize_ensemble(form="volumes") -- against each
 member's own loop of `PoissonEvaluator.loss_grad_arrays(adam=...)`: the launches a single `optimize_grad` run makes.
@@ -240,7 +240,7 @@ def test_residual_and_adjoint_launches_equal_their_single_forms(grid, dname, per
 @pytest.mark.parametrize("per_member", [False, True], ids=["alpha", "alphas"])
 @pytest.mark.parametrize("grid,dname", CASES)
 def test_transpose_chain_equals_its_single_form(grid, dname, per_member):
-    """ops.mg_synth_adj_adam_volumes against ops.mg_synth_adj_adam on each member alone: the gradients and x, m, v of the
+    """ops.mg_synth_adj_adam_members on 'ccc' rows against ops.mg_synth_adj_adam on each member alone: the gradients and x, m, v of the
     levels 1 ... equal bit for bit (every level runs the kernel a single volume's level runs, and that kernel reads the
     member's step size); and the coarse synthesis on [B, *shape] arrays equals the single volumes'."""
     from odil_amd import ops
@@ -255,7 +255,7 @@ def test_transpose_chain_equals_its_single_form(grid, dname, per_member):
     x_in, m_in, v_in = [t.clone() for t in x], [t.clone() for t in m], [t.clone() for t in v]
     grads = [gu] + [torch.full((nb,) + s, 777.0, dtype=dtype, device="cuda:0") for s in shapes[1:]]
     alphas = torch.tensor([0.001, 0.002, 0.003] if per_member else [0.002], dtype=dtype, device="cuda:0")
-    ops.mg_synth_adj_adam_volumes(gu, shapes, grads, x, m, v, alphas, OMB1, OMB2, EPS)
+    ops.mg_synth_adj_adam_members(gu, shapes, "ccc", grads, x, m, v, alphas, OMB1, OMB2, EPS)
     for b in range(nb):
         x1, m1, v1 = [t[b].clone() for t in x_in], [t[b].clone() for t in m_in], [t[b].clone() for t in v_in]
         g1 = [gu[b].clone()] + [torch.empty(s, dtype=dtype, device="cuda:0") for s in shapes[1:]]

@@ -1,5 +1,5 @@
 """The ensemble of 3-D Poisson problems as batched launches (odil_poisson_residual_synth_batch,
-odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_volumes, fused.PoissonVolumeEnsemble,
+odil_poisson_adjoint_adam_volumes, odil_mg_synth_adj_adam_members, fused.PoissonVolumeEnsemble,
 util.optimize_ensemble(form="volumes")) as far as it can be checked without a device: the library exports the entry points
 and header, library and `_lib.EXPORTED` agree; the launchers refuse malformed arguments with an error text before anything
 is launched (every pointer is a dummy, so a launch that did happen could not succeed: tests/test_ensemble_launches_host.py
@@ -16,8 +16,8 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["odil_poisson_residual_synth_batch", "odil_poisson_adjoint_adam_volumes", "odil_mg_synth_adj_adam_volumes"]
-QUERIES = ["odil_mg_volumes_levels_ok", "odil_interp_adj_kind", "odil_poisson_residual_synth_batch_workspace_bytes",
+NEW = ["odil_poisson_residual_synth_batch", "odil_poisson_adjoint_adam_volumes", "odil_mg_synth_adj_adam_members"]
+QUERIES = ["odil_mg_members_levels_ok", "odil_interp_adj_kind", "odil_poisson_residual_synth_batch_workspace_bytes",
            "odil_poisson_residual_synth_batch_partials"]
 
 
@@ -159,13 +159,15 @@ def test_adjoint_launcher_refuses_before_launching(suffix):
 
 @pytest.mark.parametrize("suffix", ["f64", "f32"])
 def test_transfer_launcher_refuses_before_launching(suffix):
-    from odil_amd import _lib
+    """The one transposed chain (odil_mg_synth_adj_adam_members) as the 3-D ensembles call it: loc 'ccc', the members as
+    its rows."""
+    from odil_amd import _lib, fused
 
     lib = _lib.load()
-    fn = getattr(lib, "odil_mg_synth_adj_adam_volumes_" + suffix)
+    fn = getattr(lib, "odil_mg_synth_adj_adam_members_" + suffix)
     shapes = [(16, 8, 8), (8, 4, 4), (4, 2, 2)]
 
-    def launch(nbatch=3, shp=shapes, ndim=3, astride=1, null=None, null_level=None, gu=1 << 20, odd_level=False):
+    def launch(nbatch=3, shp=shapes, ndim=3, loc=None, astride=1, null=None, null_level=None, gu=1 << 20, odd_level=False):
         nlvl = len(shp)
         tables = []
         for k in range(4):  # grads x m v: HOST arrays of (dummy) device pointers
@@ -179,19 +181,23 @@ def test_transfer_launcher_refuses_before_launching(suffix):
                 c_void_p(1 << 21)]  # gu grads shapes x m v alpha_dev
         if null is not None:
             ptrs[null] = None
-        return fn(ptrs[0], ptrs[1], ptrs[2], c_int(nlvl), c_int(ndim), c_int(nbatch), ptrs[3], ptrs[4], ptrs[5], 0.1, 0.001,
-                  1e-7, ptrs[6], c_int64(astride), None)
+        loc = ("c" * ndim).encode() if loc is None else loc
+        return fn(ptrs[0], ptrs[1], ptrs[2], c_int(nlvl), c_int(ndim), loc, c_int(nbatch), ptrs[3], ptrs[4], ptrs[5], 0.1,
+                  0.001, 1e-7, ptrs[6], c_int64(astride), c_int64(0), None)
 
-    refused = lambda text, **kw: _refused(lib, "mg_synth_adj_adam_volumes", launch(**kw), text)
+    refused = lambda text, **kw: _refused(lib, "mg_synth_adj_adam_members", launch(**kw), text)
     for k in range(7):
         refused(b"null pointer", null=k)
     for k in range(4):
         refused(b"null level array", null_level=k)
     for nbatch in (0, -1, 65536):
-        refused(b"members", nbatch=nbatch)
+        refused(b"rows (1 ... 65535)", nbatch=nbatch)  # (the members are the chain's rows)
     refused(b"negative", astride=-1)
     refused(b"nlvl=1", shp=shapes[:1])
-    refused(b"ndim 2", ndim=2, shp=[(8, 8), (4, 4)])
+    # the chain itself takes 1-D to 4-D rows: that the volumes form runs 3-D members only is `volumes_refusal`'s rule
+    assert "2-D grid: the batched launches of volumes run 3-D grids" in fused.volumes_refusal([(8, 8), (4, 4)])
+    refused(b"loc of another length", ndim=2, shp=[(8, 8), (4, 4)], loc=b"ccc")
+    refused(b"ndim 5", ndim=5, shp=[(8,) * 5, (4,) * 5])
     refused(b"not aligned to 16 bytes", gu=(1 << 20) + 8)
     refused(b"not aligned to 16 bytes", odd_level=True)
     assert launch(shp=[(16, 8, 8), (8, 4, 3)]) == -1 and b"does not refine" in lib.odil_last_error()
@@ -199,11 +205,11 @@ def test_transfer_launcher_refuses_before_launching(suffix):
     # 65535 members of a level that one member runs through the fast kernel (coarse z extent below 4) cannot be counted
     # in its schedule: refused, not rerouted
     wide = [(4, 1 << 14, 1 << 14), (2, 1 << 13, 1 << 13)]
-    refused(b"would not run the transfer kernel one member runs", nbatch=65535, shp=wide)
+    refused(b"would not run the transposed prolongation one row runs", nbatch=65535, shp=wide)
 
 
 def test_levels_query_and_kernel_kinds():
-    """odil_mg_volumes_levels_ok / odil_interp_adj_kind, from shapes alone: the levels of the shapes the GPU tests run take
+    """odil_mg_members_levels_ok on 'ccc' rows / odil_interp_adj_kind, from shapes alone: the levels of the shapes the GPU tests run take
     the same kernel for one member and for a batch, and the kinds are the ones the GPU tests mean to reach."""
     from odil_amd import _lib, fused
 
@@ -217,23 +223,24 @@ def test_levels_query_and_kernel_kinds():
     assert kind((4, 4, 32), "ccc", 4) == kind((3, 4, 4, 32), ".ccc", 4) == ROWS and kind((4, 4, 32), "ccc", 8) == MARCH
     assert kind((4, 16, 256), "ccc", 4) == kind((3, 4, 16, 256), ".ccc", 4) == TILE
     assert kind((4, 4), "cc", 8) == FAST and kind((4, 4, 4), "ccc", 2) < 0 and lib.odil_interp_adj_kind(None, 3, b"ccc", 8) < 0
-    ok = lambda shapes, nb, item=8: lib.odil_mg_volumes_levels_ok(_lib.i64([n for s in shapes for n in s]), len(shapes),
-                                                                  len(shapes[0]), nb, item)
+    ok = lambda shapes, nb, item=8, loc=b"ccc": lib.odil_mg_members_levels_ok(_lib.i64([n for s in shapes for n in s]),
+                                                                              len(shapes), len(shapes[0]), loc, nb, item)
     halves = lambda shape, nlvl: [tuple(n >> l for n in shape) for l in range(nlvl)]
     for shapes in (halves((4, 4, 4), 2), halves((8, 12, 20), 3), halves((8, 40, 80), 2), halves((64, 8, 16), 3),
                    halves((8, 32, 128), 3), halves((32, 32, 32), 4), halves((64, 64, 64), 5)):
         for nb in (1, 3, 70, 65535):
             for item in (8, 4):
                 assert ok(shapes, nb, item) == 0, (shapes, nb, item, lib.odil_last_error())
-    assert ok([(8, 8), (4, 4)], 3) == -1 and b"ndim 2" in lib.odil_last_error()
+    assert ok([(8, 8), (4, 4)], 3) == -1 and b"loc of another length" in lib.odil_last_error()  # (loc b"ccc", two axes)
     assert ok([(8, 8, 8)], 3) == -1 and b"nlvl=1" in lib.odil_last_error()
-    assert ok(halves((8, 8, 8), 2), 0) == -1 and b"members" in lib.odil_last_error()
+    assert ok(halves((8, 8, 8), 2), 0) == -1 and b"rows (1 ... 65535)" in lib.odil_last_error()
     assert ok(halves((8, 8, 8), 2), 3, 2) == -1 and b"element size" in lib.odil_last_error()
     wide = [(4, 1 << 14, 1 << 14), (2, 1 << 13, 1 << 13)]
-    assert fused._volume_levels_refusal(wide, 1, torch.float64) is None
-    assert "would not run the transfer kernel one member runs" in fused._volume_levels_refusal(wide, 65535, torch.float64)
-    # the existing query keeps refusing volumes
-    assert lib.odil_mg_batch_levels_ok(_lib.i64([8, 8, 8, 4, 4, 4]), 2, 3, 3) == -1 and b"ndim 3" in lib.odil_last_error()
+    assert fused._levels_refusal(wide, 1, torch.float64) is None
+    assert "would not run the transposed prolongation one row runs" in fused._levels_refusal(wide, 65535, torch.float64)
+    # the query answers for 1-D to 4-D rows: that a form runs members of its dimensions only is the form's own rule
+    assert ok([(8, 8), (4, 4)], 3, loc=b"cc") == 0 and "2-D grid" in fused.volumes_refusal([(8, 8), (4, 4)], torch.float64)
+    assert ok(halves((8, 8, 8), 2), 3) == 0 and "3-D grid" in fused.launches_refusal(halves((8, 8, 8), 2))
 
 
 def test_the_form_is_a_function_of_shapes_and_dtype():

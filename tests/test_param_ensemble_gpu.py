@@ -316,5 +316,5 @@ def test_forward_members_issue_the_launches_they_issued(monkeypatch):
     _, info = odil.util.optimize_ensemble(run_args(epochs=3), [p for p, _ in built], [s for _, s in built], form=form)
     assert info.route == "traced" and info.ensemble.nparams == 0 and type(info.ensemble.x) is list
     assert params == [] and "adam_step_params_batch" not in called
-    epoch = ["mg_synth", "mg_synth_adj_adam_batch", "adam_step_batch"]
+    epoch = ["mg_synth", "mg_synth_adj_adam_members", "adam_step_batch"]
     assert [name for name in called if name in epoch or "adam" in name][-9:] == epoch * 3

@@ -346,6 +346,6 @@ def test_poisson_members_keep_their_route_and_their_launches(monkeypatch):
     monkeypatch.setattr(stencil_jit, "TracedOperator", no_trace)
     _, info = odil.util.optimize_ensemble(pargs, [p for p, _ in built], [s for _, s in built], form="launches")
     assert info.route == "poisson" and info.form == "launches" and type(info.ensemble) is fused.PoissonLaunchEnsemble
-    epoch = ["mg_synth", "poisson_residual_batch", "poisson_adjoint_adam_batch", "mg_synth_adj_adam_batch"]
+    epoch = ["mg_synth", "poisson_residual_batch", "poisson_adjoint_adam_batch", "mg_synth_adj_adam_members"]
     assert called[-12:] == epoch * 3  # (ahead of them: the probes of `fused.detect`, nothing of an epoch)
     assert not [name for name in called[:-12] if name in epoch or "adam" in name]
